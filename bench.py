@@ -21,7 +21,14 @@ self-test of that transport that all ranks agree on; otherwise through the torch
 the identical proof: STRONG scaling (total work fixed).  `--mode replicas` instead lets every rank prove its own instance (weak scaling, no collective);
 `--log-n 20` is BASELINE's cfg3.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the `--steps` proofs, writes their outputs when `--dump-outputs DIR` is given and prints the
+line.  Everything else the bench measures or checks (the verifier restatement on the timed proof, `host_witness`, `ntt`,
+`throughput_2_in_flight`, `scale_replay`, `cpu_baseline` and, for N > 1, `comm.other_bulk_transport`) runs only with `--full`;
+the `--no-*` options then leave single legs out.  `--dump-outputs DIR` writes the last timed proof (the serialised u64 words a
+caller of bj_prove_dev receives) as DIR/proof.npy: float64, one row per word, [low 32 bits, high 32 bits], exact; the inputs
+are seeded, so the same arguments give the same file on every run.
+
+Extra objects on the JSON line (ntt, scale_replay and cpu_baseline with --full only):
   roofline      the dominant kernel of a proof, the Poseidon2 leaf hashing of the witness tree: algorithmic bytes
                 (8*W + 32 per leaf) / its duration measured with HIP events on the launch stream inside the
                 timed proofs.  It is integer-VALU-bound by construction (~472 field multiplications per 64 absorbed bytes).
@@ -114,9 +121,16 @@ def main():
                     help="world sizes of the scale_replay leg (era_boojum_amd/scale_replay.py): rank r of a W-rank proof alone on this "
                          "GPU with its peers' all-gathered buffers replayed from a recording")
     ap.add_argument("--replay-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary legs and checks (verifier restatement, host witness, NTT, two in "
+                         "flight, scale_replay, CPU baseline, other bulk transport); a plain run times the headline proofs only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed proof to DIR/proof.npy (float64 [low 32 bits, high 32 bits] per u64 word)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     launched = "WORLD_SIZE" in os.environ and ("TORCHELASTIC_RUN_ID" in os.environ or int(os.environ["WORLD_SIZE"]) > 1)
     if args.gpus > 1 and not launched:
         raise SystemExit(self_launch(args.gpus))
@@ -281,15 +295,16 @@ def main():
         if comm is None:
             comm, transport = E.TorchComm(ctx), "torch.distributed all_gather_into_tensor through the bj_comm host callback"
         base_comm, peer_comm, peer_err = comm, None, None
-        try:     # no collective of its own (the control channel rides on the default group); every rank reports, all agree
-            peer_comm = E.PeerComm(ctx, base_comm)
-            okp = 1
-        except Exception as e:                    # noqa: BLE001
-            peer_err, okp = repr(e)[:200], 0
-        flagp = torch.tensor([okp], dtype=torch.int32, device=dev if backend == "nccl" else "cpu")
-        dist.all_reduce(flagp, op=dist.ReduceOp.MIN)
-        if int(flagp.item()) != 1:
-            peer_comm = None
+        if args.bulk_transport == "peer" or (args.full and not args.no_other_bulk):   # same arguments on every rank
+            try:     # no collective of its own (the control channel rides on the default group); every rank reports, all agree
+                peer_comm = E.PeerComm(ctx, base_comm)
+                okp = 1
+            except Exception as e:                    # noqa: BLE001
+                peer_err, okp = repr(e)[:200], 0
+            flagp = torch.tensor([okp], dtype=torch.int32, device=dev if backend == "nccl" else "cpu")
+            dist.all_reduce(flagp, op=dist.ReduceOp.MIN)
+            if int(flagp.item()) != 1:
+                peer_comm = None
         if args.bulk_transport == "peer" and peer_comm is not None:
             comm, transport = peer_comm, transport + " + full-mesh peer copies (HIP IPC) for the exchanges of >= 1 MiB per rank"
     setup = E.ProverSetup(ctx, circuit, args.fri_lde, args.cap, args.security, comm=comm, transcript=args.transcript)
@@ -319,6 +334,10 @@ def main():
             stage_acc[k] = stage_acc.get(k, 0.0) + v
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:       # every rank of a sharded proof holds the same bytes
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "proof.npy"),
+                np.stack([proof_buf & np.uint64(0xFFFFFFFF), proof_buf >> np.uint64(32)], axis=1).astype(np.float64))
     per_rank = None
     if dist is not None:
         mine = {"rank": rank, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "stages_ms": {k: round(v / args.steps, 3) for k, v in stage_acc.items()},
@@ -427,7 +446,7 @@ def main():
                                 "the slowest peer), summed over a proof; replicated work is ~25 ms per rank, measured by the replayed ranks of scale_replay (DESIGN.md §6)",
                         "transport": transport}
 
-    if sharded and peer_comm is not None and not args.no_other_bulk:
+    if sharded and peer_comm is not None and args.full and not args.no_other_bulk:
         # the OTHER bulk transport on a few extra proofs (after the headline's timed region, under a watchdog: a hang here must not cost the line)
         import threading
         other = base_comm if comm is peer_comm else peer_comm
@@ -463,7 +482,7 @@ def main():
         other_bulk_stuck = th2.is_alive()
         ran_other_bulk = True
     # ---- the drop-in call with a host witness (bj_prove): PCIe transfer of the 93 columns inside the timed region
-    if world == 1 and not args.no_host_witness:
+    if world == 1 and args.full and not args.no_host_witness:
         hv = torch.from_numpy(circuit.variables.view(np.int64)).pin_memory()
         hm = torch.from_numpy(circuit.multiplicities.view(np.int64)).pin_memory()
         hvn, hmn = hv.numpy().view(np.uint64), hm.numpy().view(np.uint64)
@@ -535,9 +554,9 @@ def main():
 
     # ---- secondary leg: cfg2 NTT (2^20 x 256 columns), the "NTT GB/s vs HBM peak" half of the metric
     shared_device = world > 1 and backend == "gloo" and torch.cuda.device_count() < world
-    if not args.no_ntt and shared_device:
+    if args.full and not args.no_ntt and shared_device:
         out["ntt"] = {"skipped": "ranks share a device (functional gloo mode): the stand-alone transform legs need ~30 GB of their own"}
-    if not args.no_ntt and not shared_device:
+    if args.full and not args.no_ntt and not shared_device:
         nlog, ncols = 20, 256
         src = torch.randint(0, 1 << 62, (ncols, 1 << nlog), dtype=torch.int64, device=dev)
         dst = torch.empty_like(src)
@@ -610,7 +629,7 @@ def main():
                                                 "frac": round(ib / ims / 1e6 / HBM_PEAK_GBPS, 4), "algorithmic_bytes": ib}
             del mono, lde
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # parity spot check of what was just timed: the oracle's verifier restatement must accept the timed proof
         from era_boojum_amd import proof_format
         from oracle import verifier as OV
@@ -624,7 +643,7 @@ def main():
         stuck_legs.append("host_witness_pipelined")
     if locals().get("other_bulk_stuck"):
         stuck_legs.append("other bulk transport")
-    if rank == 0 and world == 1 and not args.no_two_in_flight and not stuck_legs:
+    if rank == 0 and world == 1 and args.full and not args.no_two_in_flight and not stuck_legs:
         # secondary throughput figure: TWO proofs of the same circuit in flight on this one GPU — two contexts, two HIP streams, two
         # host threads (the shape of tests/test_gpu_prover.py::test_two_contexts_on_two_host_threads_prove_concurrently).  The
         # metric is rows per second, and the VALU-bound hashing of one proof can share the CUs with the HBM-bound passes and the
@@ -667,7 +686,7 @@ def main():
             torch.cuda.empty_cache()
         except Exception as e:                    # noqa: BLE001 — secondary leg
             out["throughput_2_in_flight"] = {"error": repr(e)[:300]}
-    if rank == 0 and world == 1 and not args.no_scale_replay and log_n >= 12 and not stuck_legs:
+    if rank == 0 and world == 1 and args.full and not args.no_scale_replay and log_n >= 12 and not stuck_legs:
         # one rank of the sharded proof alone on this GPU, peers replayed (the only multi-GPU evidence one GPU can give)
         from era_boojum_amd import scale_replay
         t1_ms = elapsed / args.steps * 1e3
@@ -736,7 +755,7 @@ def main():
                 sr["worlds"][str(w)] = {"error": repr(e)[:300]}
                 torch.cuda.empty_cache()
         out["scale_replay"] = sr
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         import oracle as O
         from oracle import prover as OP
         affinity = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)

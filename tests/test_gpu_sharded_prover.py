@@ -201,7 +201,7 @@ def test_plain_bench_command_with_gpus_2_starts_two_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--log-n", "16", "--steps", "2",
-           "--warmup", "1", "--no-ntt", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-ntt", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

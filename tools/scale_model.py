@@ -33,7 +33,7 @@ def main():
                     "(fitted to the replayed ranks of round 5: bench.py scale_replay; 3.0 in round 4)")
     ap.add_argument("--link-gbps", type=float, default=150.0, help="sustained rate of one xGMI link")
     ap.add_argument("--mb-per-rank-w8", type=float, default=350.0, help="bytes arriving per rank per proof at W = 8")
-    ap.add_argument("--replay", type=str, default=None, help="a bench.py JSON line (file) with scale_replay: printed next to the model")
+    ap.add_argument("--replay", type=str, default=None, help="a bench.py --full JSON line (file) with scale_replay: printed next to the model")
     a = ap.parse_args()
     rep = sh = 0.0
     rows = list(csv.DictReader(open(a.stats)))
