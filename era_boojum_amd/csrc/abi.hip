@@ -181,17 +181,13 @@ void load_env() {
     EnvConfig e;
     auto set = [](const char *name) { return getenv(name) != nullptr; };
     auto str = [](const char *name) { const char *v = getenv(name); return std::string(v ? v : ""); };
-    e.ntt_first_narrow = set("BJ_NTT_FIRST_NARROW");
-    e.ntt_generic = str("BJ_NTT_GENERIC").rfind("1", 0) == 0;
-    e.ntt_generic_remainder = set("BJ_NTT_GENERIC_REMAINDER");
-    e.bitrev_gather = set("BJ_BITREV_GATHER");
-    if (set("BJ_NTT_FRONT")) e.ntt_front = atoi(getenv("BJ_NTT_FRONT"));
-    e.ntt_first4_v = str("BJ_NTT_FIRST4_V").rfind("1", 0) == 0 ? 1 : 2;
-    if (set("BJ_NTT_FIRST4_MODE")) e.ntt_first4_mode = atoi(getenv("BJ_NTT_FIRST4_MODE"));
     e.ntt_two_pass = str("BJ_NTT_TWO_PASS").rfind("0", 0) != 0;
     e.mono_tiled = str("BJ_MONO_TILED").rfind("0", 0) != 0;
     if (set("BJ_ASYNC_MODE")) e.async_mode = atoi(getenv("BJ_ASYNC_MODE"));
     e.async_stagger = str("BJ_ASYNC_STAGGER").rfind("0", 0) != 0;
+    e.async_debug = set("BJ_ASYNC_DEBUG");
+    e.peer_debug = set("BJ_PEER_DEBUG");
+    if (set("BJ_PEER_TEST_FAIL_RANK")) e.peer_test_fail_rank = atoi(getenv("BJ_PEER_TEST_FAIL_RANK"));
     e.gate_no_aot = set("BJ_GATE_NO_AOT");
     e.gate_no_fuse = set("BJ_GATE_NO_FUSE");
     e.gate_no_jit = set("BJ_GATE_NO_JIT");
@@ -488,7 +484,7 @@ int lde_cosets_strided(bj_ctx *ctx, const u64 *d_mono, size_t in_col_stride, u64
 }
 
 // The monomial layout bj_prove keeps for 2^log_n-row columns: tiled (ntt_r16.hip) where the two-pass plan runs, natural elsewhere.
-bool mono_tiled(unsigned log_n) { return log_n == 22 && bj::env().ntt_two_pass && bj::env().mono_tiled && !bj::env().ntt_generic; }
+bool mono_tiled(unsigned log_n) { return log_n == 22 && bj::env().ntt_two_pass && bj::env().mono_tiled; }
 
 // ifft_natural_to_natural (fft/mod.rs:464-491) on the main domain with the result left in the TILED layout: front pass into scratch,
 // last pass storing the bit-reversed, 1/n-scaled positions directly — two HBM passes, no bit-reversal pass.  Columns on 16-byte

@@ -14,10 +14,6 @@ typedef uint64_t u64;
 // setenv, no per-proof lookups, and every context of a process (one per GPU, each on its own host thread) sees the same plan.
 // bj_env_reload() re-reads them for tests that exercise both sides of a switch in one process (not thread-safe by contract).
 struct EnvConfig {
-    bool ntt_first_narrow = false, ntt_generic = false, ntt_generic_remainder = false, bitrev_gather = false;
-    int ntt_front = 4;                  // BJ_NTT_FRONT: 0 remainder passes only, 5 first5 wherever it applies, default 4
-    int ntt_first4_v = 2;               // BJ_NTT_FIRST4_V: indices per lane of the four-round front pass
-    int ntt_first4_mode = 0;            // BJ_NTT_FIRST4_MODE: 0 inputs of the front pass kept in registers across the cosets (round 3: two waves per SIMD); 3 / 4: re-read per coset (L2), that many waves
     bool ntt_two_pass = true;           // BJ_NTT_TWO_PASS=0: 2^22-point transforms as 4 + 8 + 10 rounds (rounds 3-5) instead of 10 + 12
     bool mono_tiled = true;             // BJ_MONO_TILED=0: bj_prove keeps 2^22-row monomials in natural order (inverse transforms end in a bit-reversal pass)
     bool gate_no_aot = false, gate_no_fuse = false, gate_no_jit = false;
@@ -27,6 +23,9 @@ struct EnvConfig {
     bool prove_uniform_groups = false;   // BJ_PROVE_UNIFORM_GROUPS: equal groups of G columns, one multi-block absorption run per group (round 4's GROUPING only: its launches absorbed eight columns each)
     bool async_stagger = true;           // BJ_ASYNC_STAGGER=0: bj_prove_async lanes start whenever they are given work (A/B)
     int async_mode = -1;                 // BJ_ASYNC_MODE: what a bj_prove_async lane does while its sibling proves: -1 by witness size (default), 0 bj_prove as is (+ stagger), 1 whole witness first, 2 groups + one hash
+    bool async_debug = false;            // BJ_ASYNC_DEBUG: a bj_prove_async lane reports each proof it ran on stderr
+    bool peer_debug = false;             // BJ_PEER_DEBUG: the peer transport traces its bulk exchanges on stderr
+    int peer_test_fail_rank = -1;        // BJ_PEER_TEST_FAIL_RANK: test hook, this rank of the peer transport pretends it could not export its mailbox
     unsigned prove_h2d_group = 8;
     size_t nodes_lanepar_max = 16384;
     std::string jit_cache_dir, rccl_lib;

@@ -19,7 +19,6 @@
 #include <cstdint>
 #include <cstdlib>
 #include "kernels.h"
-#include <cstdlib>
 
 using gl::u64;
 using gl::u32;
@@ -221,7 +220,7 @@ static void launch_first_rounds(const u64 *src, u64 *d_out, const u64 *d_tw, con
     const size_t quarter = ((size_t)1 << log_n) >> R;
     // two indices per lane need 16-byte aligned columns and an even slice
     const bool wide = quarter % 512 == 0 && src_col_stride % 2 == 0 && src_coset_stride % 2 == 0 && out_col_stride % 2 == 0 &&
-                      ((uintptr_t)src % 16) == 0 && ((uintptr_t)d_out % 16) == 0 && !bj::env().ntt_first_narrow;
+                      ((uintptr_t)src % 16) == 0 && ((uintptr_t)d_out % 16) == 0;
     dim3 grid((unsigned)((quarter / (wide ? 2 : 1) + 255) / 256), n_cols, 1);
     if (wide) {
         if (R == 1)
@@ -254,14 +253,17 @@ static void launch_generic_pass(const u64 *src, u64 *d_out, const u64 *d_tw, con
     hipLaunchKernelGGL(ntt_pass_generic_kernel, dim3(tiles, n_cols, n_cosets), dim3(tpb), lds, s, a);
 }
 
-static bool force_generic() { return bj::env().ntt_generic; }
-
-// Pass plan.  log_n < 12 (or BJ_NTT_GENERIC=1): generic LDS passes.  Otherwise the last 12 rounds run in
-// ntt_local12, the rounds in front of it in radix-16 strided passes of 8 or 4 rounds, and a remainder of 1..3
-// rounds (log_n not of the form 12 + 4k) in one generic strided pass at the very front.
+// Pass plan.  log_n < 12: generic LDS passes.  Otherwise the last 12, 10 or 9 rounds run in ntt_local12 and the rounds in front
+// of it in radix-16 strided passes of 8 or 4 rounds, behind a front pass that reads the caller's column once for every coset
+// (up to 64 cosets):
+//   2^22, 16-byte columns   ntt_front10 + ntt_local12: two passes (BJ_NTT_TWO_PASS=0: the 14 + 4k plan below)
+//   14 + 4k rounds          ntt_first4, the local pass runs 10 (ntt_first5 and 9 when the columns are not on 16-byte boundaries)
+//   15 + 4k rounds          ntt_first5, the local pass runs 10
+//   13 + 4k rounds          ntt_first_rounds for the one remainder round
+// Above 64 cosets the 1..3 remainder rounds of a transform not of the form 12 + 4k take one generic strided pass at the front.
 bool ntt_two_pass_applies(const u64 *d_in, const u64 *d_out, unsigned log_n, unsigned n_cosets, size_t in_col_stride, size_t out_col_stride) {
     const bool io16 = ((uintptr_t)d_out % 16) == 0 && out_col_stride % 2 == 0 && ((uintptr_t)d_in % 16) == 0 && in_col_stride % 2 == 0;
-    return log_n == 22 && n_cosets <= 64 && io16 && bj::env().ntt_two_pass && !force_generic();
+    return log_n == 22 && n_cosets <= 64 && io16 && bj::env().ntt_two_pass;
 }
 void launch_ntt_passes(const u64 *d_in, u64 *d_out, const u64 *d_tw, const u64 *d_round_scale, unsigned log_n,
                        unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t out_col_stride,
@@ -282,7 +284,7 @@ void launch_ntt_passes(const u64 *d_in, u64 *d_out, const u64 *d_tw, const u64 *
         src_col_stride = out_col_stride;
         src_coset_stride = n;
     };
-    if (log_n < 12 || force_generic()) {
+    if (log_n < 12) {
         unsigned local = log_n < LOCAL_MAX ? log_n : LOCAL_MAX;
         unsigned rest = log_n - local;
         unsigned n_strided = (rest + STRIDED_MAX - 1) / STRIDED_MAX;
@@ -312,13 +314,12 @@ void launch_ntt_passes(const u64 *d_in, u64 *d_out, const u64 *d_tw, const u64 *
     // 14 + 4k and 15 + 4k rounds: the coset-expanding front pass is bound by its traffic whatever it computes, so it takes four
     // or five rounds (ntt_first4 / ntt_first5) and the local pass runs ten or nine instead of twelve — the same number of passes,
     // butterflies moved into idle VALU slots.  13 + 4k rounds keep the remainder pass of one round.
-    const int front_policy = bj::env().ntt_front;   // 0: remainder passes only (the round-1 plan); 5: first5 wherever it applies; default: measured best
     const bool aligned16 = ((uintptr_t)d_in % 16) == 0 && ((uintptr_t)d_out % 16) == 0 && in_col_stride % 2 == 0 &&
                            out_col_stride % 2 == 0;
     unsigned F = 0, Lr = 12;
-    if (n_cosets <= 64 && front_policy) {
+    if (n_cosets <= 64) {
         if (front % 4 == 2) {          // 2^22: 4 + 8 + 10 measured 283.5 ms per proof, 5 + 8 + 9 284.5 (2 + 8 + 12: 284.7)
-            if (front_policy < 5 && aligned16) F = 4, Lr = 10;
+            if (aligned16) F = 4, Lr = 10;
             else F = 5, Lr = 9;
         } else if (front % 4 == 3) {   // 2^23: 5 + 8 + 10 measured 560.0 ms per proof against 565.4 for 3 + 8 + 12
             F = 5, Lr = 10;
@@ -350,8 +351,7 @@ void launch_ntt_passes(const u64 *d_in, u64 *d_out, const u64 *d_tw, const u64 *
     }
     if (front % 4) {
         unsigned R = front % 4;
-        const bool old_remainder = bj::env().ntt_generic_remainder;
-        if (!old_remainder && n_cosets <= 64)
+        if (n_cosets <= 64)
             launch_first_rounds(src, d_out, d_tw, d_round_scale, log_n, R, n_cols, n_cosets, src_col_stride,
                                 src_coset_stride, out_col_stride, s);
         else
@@ -437,7 +437,7 @@ void launch_bitrev_scale(const u64 *d_in, u64 *d_out, unsigned log_n, unsigned n
                          size_t out_col_stride, u64 scale, u64 step, hipStream_t s) {
     size_t n = (size_t)1 << log_n;
     unsigned tpb = 256;
-    if (log_n >= 10 && !bj::env().bitrev_gather) {
+    if (log_n >= 10) {
         BitrevPowers pw{};
         const int stepped = step != 1;
         if (stepped) {

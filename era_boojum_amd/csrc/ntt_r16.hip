@@ -33,74 +33,17 @@ struct R16Args {
     size_t in_col_stride, in_coset_stride, out_col_stride;
 };
 
-#ifndef BJ_R16_WAVES
-#define BJ_R16_WAVES 3   // min waves per SIMD requested from the register allocator (tuned on MI355X: 2 -> 8.6 ms, 3 -> 7.9 ms, 4 -> 10.9 ms per 93 x 2^20 x 8 LDE)
-#endif
+static constexpr int R16_WAVES = 3;   // min waves per SIMD requested from the register allocator (tuned on MI355X: 2 -> 8.6 ms, 3 -> 7.9 ms, 4 -> 10.9 ms per 93 x 2^20 x 8 LDE)
 static constexpr u32 TILE = 4096;
 static constexpr u32 LDS_ELEMS = TILE + TILE / 16;
 
-// A/B builds for the question "what is the parked time of these passes waiting for" (tools/ntt_wait_ab.sh; results are WRONG
-// transforms, only their duration means something; never defined in the product build):
-//   -DBJ_R16_AB_NOLOAD     the 16 input words of a lane come from a register expression instead of HBM
-//   -DBJ_R16_AB_NOSTORE    the HBM stores sit behind a wave-uniform condition that is never true
-//   -DBJ_R16_AB_NOBARRIER  no workgroup barrier around the LDS transposes
-#ifdef BJ_R16_AB_NOLOAD
-#define BJ_R16_LD(base, off, salt) ((u64)(off) * 0x9E3779B97F4A7C15ull + (u64)(salt))
-#else
-#define BJ_R16_LD(base, off, salt) ld_off(base, off)
-#endif
-#ifdef BJ_R16_AB_NOSTORE
-#define BJ_R16_ST_GUARD(a) if ((a).n_cols == 0xFFFFFFFFu)
-#else
-#define BJ_R16_ST_GUARD(a)
-#endif
-// -DBJ_R16_AB_S8_NOMEM: only the strided pass loses its loads and its stores — its butterflies stay: what an LDE would cost if the
-// middle pass's 16 n words per column of HBM traffic went away with the arithmetic unchanged (the bound on fusing it into a neighbour)
-#ifdef BJ_R16_AB_S8_NOMEM
-#define BJ_R16_LD_S8(base, off, salt) ((u64)(off) * 0x9E3779B97F4A7C15ull + (u64)(salt))
-#define BJ_R16_ST_GUARD_S8(a) if ((a).n_cols == 0xFFFFFFFFu)
-#else
-#define BJ_R16_LD_S8(base, off, salt) BJ_R16_LD(base, off, salt)
-#define BJ_R16_ST_GUARD_S8(a) BJ_R16_ST_GUARD(a)
-#endif
-// Software pipeline over the columns of a workgroup (round 5, build switches): the loads of column c + 1 are issued before the stores
-// of column c and the barriers stop draining vmcnt (the ISA then waits with vmcnt(22..16) at the top of a column: the sixteen stores
-// stay in flight).  Measured on MI355X (profiles/r05_ntt_wait_ab.txt): parked wave-cycles of ntt_local12 24.4 % -> 20.7 %, issue-stall
-// cycles up by the same amount, duration 1.410 -> 1.415 ms at equal clocks (1.362 ms in the one run where the part held 1.89 GHz);
-// ntt_strided8 0.924 -> 0.959 ms (sixteen more register pairs: 125 -> 157 VGPRs, four resident waves per SIMD become three).  The
-// passes are not short of latency cover: they run at the power limit (1.77-1.80 GHz against 2.3 GHz for the hash kernels; without
-// their loads or their stores the SAME instruction stream runs at 1.93 / 2.18 GHz and 7-8 % fewer cycles).  Both default to off.
-#ifndef BJ_R16_PREFETCH_LOCAL
-#define BJ_R16_PREFETCH_LOCAL 0
-#endif
-#ifndef BJ_R16_PREFETCH_STRIDED
-#define BJ_R16_PREFETCH_STRIDED 0
-#endif
-#ifndef BJ_R16_WIDE_ST
-#define BJ_R16_WIDE_ST 0   // 1: ntt_local12 stores 16 bytes per lane (two adjacent words out of LDS) — half the store instructions
-#endif
-// Workgroup barrier that orders LDS traffic only (for the pipelined pass).  __syncthreads() is a workgroup-scope fence: it drains
-// vmcnt too, i.e. waits for every global store of the wave to be acknowledged and for the loads that were issued ahead for the NEXT
-// column — the two things the pipeline keeps in flight across the transposes.  All data exchanged between the lanes of a workgroup
-// here goes through LDS, so this wave's LDS operations being complete (lgkmcnt) before the barrier is all the ordering they need.
-#ifdef BJ_R16_AB_NOBARRIER
-#define BJ_R16_SYNC_FULL()
-#define BJ_R16_SYNC_LDS()
-#else
-#define BJ_R16_SYNC_FULL() __syncthreads()
-#define BJ_R16_SYNC_LDS() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#endif
+// The closed experiments on these passes (profiles/r05_ntt_wait_ab.txt): issuing the next column's loads ahead of
+// this column's stores with LDS-only barriers, 16-byte stores out of ntt_local12, and builds without loads, stores or barriers.
+// The passes are not short of latency cover — they run at the power limit — and none of it changed their wall time.
 
-#if BJ_R16_PREFETCH_LOCAL
-#define BJ_R16_SYNC_L() BJ_R16_SYNC_LDS()
-#else
-#define BJ_R16_SYNC_L() BJ_R16_SYNC_FULL()
-#endif
-#if BJ_R16_PREFETCH_STRIDED
-#define BJ_R16_SYNC_S() BJ_R16_SYNC_LDS()
-#else
-#define BJ_R16_SYNC_S() BJ_R16_SYNC_FULL()
-#endif
+// Workgroup barrier that orders LDS traffic only: this wave's LDS operations are complete (lgkmcnt), its HBM loads and stores may
+// still be in flight (__syncthreads() is a workgroup-scope fence and would drain vmcnt as well).
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __device__ __forceinline__ u32 pad(u32 l) { return l + (l >> 4); }
 __device__ __forceinline__ void set_prio(int p) {   // s_setprio takes an immediate: p is a constant after unrolling
@@ -239,7 +182,7 @@ __device__ __forceinline__ void stage_uniform_twiddles(u64 *lds_tw, const u64 *_
 // ROUNDS = 12, or 10 / 9: the same kernel without the first two / three rounds of step A (a 4096-element chunk is then four /
 // eight independent sub-transforms; the rounds that remain are exactly the last ROUNDS rounds, with the twiddle indices unchanged)
 template <bool SCALED, int ROUNDS = 12>
-__global__ void __launch_bounds__(256, BJ_R16_WAVES) ntt_local12_kernel(R16Args a) {
+__global__ void __launch_bounds__(256, R16_WAVES) ntt_local12_kernel(R16Args a) {
     __shared__ u64 lds[LDS_ELEMS + 16 + 16 * 16];
     u64 *lds_tw = lds + LDS_ELEMS;
     u64 *lds_twB = lds_tw + 16;               // [t >> 4][15 (+1 pad)] twiddles of step B (shared by 16 lanes each)
@@ -266,69 +209,47 @@ __global__ void __launch_bounds__(256, BJ_R16_WAVES) ntt_local12_kernel(R16Args 
     const unsigned col0 = blockIdx.y * a.cols_per_block;
     const unsigned col1 = min(col0 + a.cols_per_block, a.n_cols);
     const u32 ta = t >> 4, tc = t & 15;
-    // Software pipeline over the columns of this workgroup: VMEM returns in issue order and ONE counter (vmcnt) covers loads and
-    // stores, so a column's loads queued BEHIND the previous column's stores cannot be consumed before those stores have been
-    // acknowledged by the memory system (A/B builds: without the stores the pass is 23 % faster, without the loads 17 %,
-    // tools/ntt_wait_ab.sh).  Here the next column's 16 words are requested right after the data registers of the current one have
-    // gone to LDS for the last transpose, AHEAD of its stores: the wait at the top of the next iteration is vmcnt(16) — the stores
-    // stay in flight under the butterflies — and the load latency hides under the store phase.
-    auto request = [&](u64 (&v)[16], unsigned col) {
-        const gcptr src = uniform_gptr(a.in + (size_t)col * a.in_col_stride + (size_t)coset * a.in_coset_stride + (size_t)b * TILE);
-#pragma unroll
-        for (int j = 0; j < 16; j++) v[j] = BJ_R16_LD(src + j * 256, t * 8u, j + col);
-    };
     // The first column is peeled off the loop: the register scoreboard of the compiler is merged at a loop header, and with the
     // prologue's loads (nothing behind them) on one edge and the latch's loads (sixteen stores behind them) on the other it would
     // wait for vmcnt(0) at the top of every iteration — stores included.  With the peeled copy both edges look alike.
     u64 x[16];
     auto column = [&](unsigned col) {
         const gptr dst = (gptr)uniform_gptr(a.out + (size_t)col * a.out_col_stride + (size_t)coset * n + (size_t)b * TILE);
-        if (!BJ_R16_PREFETCH_LOCAL) request(x, col);
+        const gcptr src = uniform_gptr(a.in + (size_t)col * a.in_col_stride + (size_t)coset * a.in_coset_stride + (size_t)b * TILE);
+#pragma unroll
+        for (int j = 0; j < 16; j++) x[j] = ld_off(src + j * 256, t * 8u);
         radix16<false, 12 - ROUNDS>(x, lds_tw);   // step A: bits 11..8 in registers, twiddles uniform (LDS broadcasts at the point of use)
 #pragma unroll
         for (int j = 0; j < 16; j++) lds[pad(j * 256 + t)] = x[j];
-        BJ_R16_SYNC_L();
+        __syncthreads();
 #pragma unroll
         for (int j = 0; j < 16; j++) x[j] = lds[pad(ta * 256 + j * 16 + tc)];
-        BJ_R16_SYNC_L();
+        __syncthreads();
         radix16_lds<false>(x, lds_twB + ta * 16);   // step B: bits 7..4
 #pragma unroll
         for (int j = 0; j < 16; j++) lds[pad(ta * 256 + j * 16 + tc)] = x[j];
-        BJ_R16_SYNC_L();
+        __syncthreads();
 #pragma unroll
         for (int j = 0; j < 16; j++) x[j] = lds[pad(t * 16 + j)];
-        BJ_R16_SYNC_L();
+        __syncthreads();
         radix16<false>(x, twC);   // step C: bits 3..0
 #pragma unroll
         for (int j = 0; j < 16; j++) lds[pad(t * 16 + j)] = gl::canon(x[j]);   // the transform's output: canonical residues
-        BJ_R16_SYNC_L();
-        if (BJ_R16_PREFETCH_LOCAL && col + 1 < col1) request(x, col + 1);            // x is free: its values sit in LDS
-        if (BJ_R16_WIDE_ST) {   // lane t: words 2u, 2u + 1 (u = t & 127) of row 2k + (t >> 7): one 16-byte store, 1 KB per wave instruction
-            const u32 u2 = (t & 127u) * 2u, rh = t >> 7;
+        __syncthreads();
 #pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const u32 l = (2u * k + rh) * 256u + u2;
-                BJ_R16_ST_GUARD(a) st_off2(dst, l * 8u, lds[pad(l)], lds[pad(l + 1)]);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 16; j++) BJ_R16_ST_GUARD(a) st_off(dst + j * 256, t * 8u, lds[pad(j * 256 + t)]);
-        }
-        BJ_R16_SYNC_L();
+        for (int j = 0; j < 16; j++) st_off(dst + j * 256, t * 8u, lds[pad(j * 256 + t)]);
+        __syncthreads();
     };
     if (col0 >= col1) return;
-    if (BJ_R16_PREFETCH_LOCAL) request(x, col0);
     column(col0);
 #pragma nounroll
     for (unsigned col = col0 + 1; col < col1; col++) column(col);
 }
 
 // ---------------------------------------------------------------------------------------------------------
-#ifndef BJ_S8_WAVES
-#define BJ_S8_WAVES 3   // tuned: 3 -> 7.6 ms, 4 -> 9.7 ms (spills) per 93 x 2^20 x 8 LDE
-#endif
+static constexpr int S8_WAVES = 3;   // tuned: 3 -> 7.6 ms, 4 -> 9.7 ms (spills) per 93 x 2^20 x 8 LDE
 template <bool SCALED, bool UNIT_FIRST>
-__global__ void __launch_bounds__(256, BJ_S8_WAVES) ntt_strided8_kernel(R16Args a) {
+__global__ void __launch_bounds__(256, S8_WAVES) ntt_strided8_kernel(R16Args a) {
     __shared__ u64 lds[LDS_ELEMS + 16 + 16 * 16];
     u64 *lds_tw = lds + LDS_ELEMS;            // 15 block-uniform twiddles of the first step
     u64 *lds_tw2 = lds_tw + 16;               // [tm][15 (+1 pad)] twiddles of the second step: all twiddles live in LDS, which
@@ -359,40 +280,24 @@ __global__ void __launch_bounds__(256, BJ_S8_WAVES) ntt_strided8_kernel(R16Args 
     const u32 off_ld = ((tm << rem_log) + tl) * 8u, off_st = (((tm * 16) << rem_log) + tl) * 8u;   // bytes; a column is < 2^32 bytes
     const unsigned col0 = blockIdx.y * a.cols_per_block;
     const unsigned col1 = min(col0 + a.cols_per_block, a.n_cols);
-    // the same software pipeline as in ntt_local12_kernel: the next column's loads go out before this column's stores (here the
-    // stores leave from the data registers themselves, so the prefetched words take sixteen more register pairs: 121 -> ~153 VGPRs,
-    // still three waves per SIMD)
-    auto request = [&](u64 (&v)[16], unsigned col) {
-        const gcptr src = uniform_gptr(a.in + (size_t)col * a.in_col_stride + (size_t)coset * a.in_coset_stride + tile_base);
-#pragma unroll
-        for (int j = 0; j < 16; j++) v[j] = BJ_R16_LD_S8(src + ((size_t)(j * 16) << rem_log), off_ld, j + col);
-    };
     u64 x[16];
     auto column = [&](unsigned col) {
         const gptr dst = (gptr)uniform_gptr(a.out + (size_t)col * a.out_col_stride + (size_t)coset * n + tile_base);
-        if (!BJ_R16_PREFETCH_STRIDED) request(x, col);
+        const gcptr src = uniform_gptr(a.in + (size_t)col * a.in_col_stride + (size_t)coset * a.in_coset_stride + tile_base);
+#pragma unroll
+        for (int j = 0; j < 16; j++) x[j] = ld_off(src + ((size_t)(j * 16) << rem_log), off_ld);
         radix16_lds<UNIT_FIRST>(x, lds_tw);    // mid bits 7..4
 #pragma unroll
         for (int j = 0; j < 16; j++) lds[pad(j * 256 + t)] = x[j];
-        BJ_R16_SYNC_S();
+        __syncthreads();
 #pragma unroll
         for (int j = 0; j < 16; j++) x[j] = lds[pad(tm * 256 + j * 16 + tl)];
-        BJ_R16_SYNC_S();
-        // the next column's words are requested BEFORE the second step: they travel under its butterflies and are in the queue
-        // ahead of this column's stores (the copy nx -> x at the bottom then finds them there: vmcnt(16), the stores stay in flight)
-        u64 nx[16];
-        const bool more = BJ_R16_PREFETCH_STRIDED && col + 1 < col1;   // wave-uniform
-        if (more) request(nx, col + 1);
+        __syncthreads();
         radix16_lds<false>(x, lds_tw2 + tm * 16);   // mid bits 3..0
 #pragma unroll
-        for (int j = 0; j < 16; j++) BJ_R16_ST_GUARD_S8(a) st_off(dst + ((size_t)j << rem_log), off_st, x[j]);
-        if (more) {
-#pragma unroll
-            for (int j = 0; j < 16; j++) x[j] = nx[j];
-        }
+        for (int j = 0; j < 16; j++) st_off(dst + ((size_t)j << rem_log), off_st, x[j]);
     };
     if (col0 >= col1) return;
-    if (BJ_R16_PREFETCH_STRIDED) request(x, col0);
     column(col0);          // peeled (see ntt_local12_kernel): both edges into the loop carry loads with sixteen stores behind them
 #pragma nounroll
     for (unsigned col = col0 + 1; col < col1; col++) column(col);
@@ -437,14 +342,10 @@ __global__ void __launch_bounds__(256) ntt_strided4_kernel(R16Args a) {
 // these rounds are uniform per coset and live in LDS.  No tile and no barrier in the data path.  The pass is bound by its
 // 8 * (1 + cosets) * n bytes per column, so its butterflies ride on VALU slots that would idle anyway: the local pass behind
 // it then runs 10 rounds instead of 12 (ntt_local12_kernel<., 10>).
-// HOIST = true keeps the 16 (x V) input words of a lane in registers across the coset loop (206 VGPRs with V = 2: two waves per
-// SIMD, whose butterflies and stores then run one after the other: the pass took the SUM of its VALU time and its HBM time).
-// HOIST = false asks for them again for every coset through an opaque pointer — the seven repeats hit the L2 (a workgroup's
-// inputs are 64 KB) — so the register file holds one working set and four waves share a SIMD: stores of one wave drain under
-// the butterflies of the others.
-template <bool SCALED, int V, int WAVES /* 0: HOIST; else reload with this many waves per SIMD asked of the register allocator */>
-__global__ void __launch_bounds__(256, WAVES ? WAVES : 1) ntt_first4_kernel(R16Args a, unsigned n_cosets) {
-    constexpr bool HOIST = WAVES == 0;
+// The 2 x 16 input words of a lane stay in registers across the coset loop when every coset reads the same column (206 VGPRs: two
+// waves per SIMD); with a coset stride they are read per coset.
+template <bool SCALED>
+__global__ void __launch_bounds__(256, 1) ntt_first4_kernel(R16Args a, unsigned n_cosets) {
     __shared__ u64 tws[64 * 16];                          // [coset][15 (+1 pad)]
     const size_t n = (size_t)1 << a.log_n, sl = n >> 4;
     for (u32 t = threadIdx.x; t < n_cosets * 15; t += blockDim.x) {
@@ -456,49 +357,39 @@ __global__ void __launch_bounds__(256, WAVES ? WAVES : 1) ntt_first4_kernel(R16A
         tws[c * 16 + i] = v;
     }
     __syncthreads();
-    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 2;
     if (i >= sl) return;
     const u64 *src = a.in + (size_t)blockIdx.y * a.in_col_stride + i;
     u64 *dst = a.out + (size_t)blockIdx.y * a.out_col_stride + i;
     auto load = [](const u64 *p, u64 &lo, u64 &hi) {
-        if (V == 2) {
-            const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(p);
-            lo = q.x;
-            hi = q.y;
-        } else {
-            lo = p[0];
-        }
+        const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(p);
+        lo = q.x;
+        hi = q.y;
     };
     const bool shared_input = a.in_coset_stride == 0;
-    u64 in0[HOIST ? 16 : 1], in1[HOIST && V == 2 ? 16 : 1];
-    if (HOIST && shared_input) {
+    u64 in0[16], in1[16];
+    if (shared_input) {
 #pragma unroll
-        for (int m = 0; m < 16; m++) load(src + (size_t)m * sl, in0[m], in1[V == 2 ? m : 0]);
+        for (int m = 0; m < 16; m++) load(src + (size_t)m * sl, in0[m], in1[m]);
     }
     for (unsigned c = 0; c < n_cosets; c++) {
-        u64 x0[16], x1[V == 2 ? 16 : 1];
+        u64 x0[16], x1[16];
         const u64 *cs = src + (size_t)c * a.in_coset_stride;
-        if (!HOIST) asm volatile("" : "+v"(cs));          // a fresh pointer per coset: the loads below stay inside the loop
 #pragma unroll
         for (int m = 0; m < 16; m++) {
-            if (HOIST && shared_input) {
+            if (shared_input) {
                 x0[m] = in0[m];
-                if (V == 2) x1[m] = in1[m];
+                x1[m] = in1[m];
             } else {
-                load(cs + (size_t)m * sl, x0[m], x1[V == 2 ? m : 0]);
+                load(cs + (size_t)m * sl, x0[m], x1[m]);
             }
         }
         const u64 *tw = tws + c * 16;
         radix16<!SCALED>(x0, tw);   // unscaled: T[0] = 1, the first round is additions only
-        if constexpr (V == 2) radix16<!SCALED>(x1, tw);
+        radix16<!SCALED>(x1, tw);
         u64 *o = dst + (size_t)c * n;
 #pragma unroll
-        for (int m = 0; m < 16; m++) {
-            if (V == 2)
-                *reinterpret_cast<ulonglong2 *>(o + (size_t)m * sl) = make_ulonglong2(x0[m], x1[V == 2 ? m : 0]);
-            else
-                o[(size_t)m * sl] = x0[m];
-        }
+        for (int m = 0; m < 16; m++) *reinterpret_cast<ulonglong2 *>(o + (size_t)m * sl) = make_ulonglong2(x0[m], x1[m]);
     }
 }
 
@@ -592,13 +483,10 @@ struct F10Args {
 // inverse transform's last pass, whose results are the words (m, l = 2k) and (m, l = 2k + 1) of FOUR tiles for every m, leaves them
 // as 16-byte words in runs of 1 KB per wave store — the bit reversal of ifft_natural_to_natural (fft/mod.rs:464-491) happens in the
 // store addresses, no pass of its own — and (b) the front pass fetches 16-byte words (m, l pair) for its LDS tile in [m][l] order as before.
-#ifndef BJ_TILED_LB
-#define BJ_TILED_LB 3   // lo values per front-pass tile of the tiled layout = 2^LB.  3: 1024 x 8 tiles (64 KB), 512-thread workgroups, TWO per CU —
-                        // their barrier phases interleave; the half-line stores of tiles 2u, 2u + 1 meet in one XCD's L2 (blocks b, b + 8).
-                        // Measured with tiled (contiguous) reads: LDE 93 x 2^22 x 8 27.10 ms against 27.76 ms for 4 (full-line tiles, one
-                        // 1024-thread workgroup per CU); with natural-order reads (64-byte runs) the half-line tiles had lost.
-#endif
-constexpr int TILED_LB = BJ_TILED_LB;
+constexpr int TILED_LB = 3;   // lo values per front-pass tile of the tiled layout = 2^LB.  3: 1024 x 8 tiles (64 KB), 512-thread workgroups, TWO per CU —
+                              // their barrier phases interleave; the half-line stores of tiles 2u, 2u + 1 meet in one XCD's L2 (blocks b, b + 8).
+                              // Measured with tiled (contiguous) reads: LDE 93 x 2^22 x 8 27.10 ms against 27.76 ms for 4 (full-line tiles, one
+                              // 1024-thread workgroup per CU); with natural-order reads (64-byte runs) the half-line tiles had lost.
 __host__ __device__ constexpr size_t tiled_index(size_t e) {   // e = m * 4096 + r * 2^LB + l
     return ((e & 4095u) >> TILED_LB) * ((size_t)1024 << TILED_LB) + ((e & ((1u << TILED_LB) - 1u)) >> 1) * 2048u + (e >> 12) * 2u + (e & 1u);
 }
@@ -664,10 +552,8 @@ typedef void __attribute__((address_space(3))) *f10_ldst;
 //   steps B (bits 5..2) and C (bits 1..0 x four lo values) of wave w touch region w only — the B -> C transpose is an exchange
 //   among the lanes of ONE wave, ordered by the wave's own LDS queue, no barrier — and when wave w has read its step-C
 //   registers, region w is dead: it requests the next column's pieces at once, then computes step C and stores.
-// The coset's twiddle table (8 KB) is fetched once per workgroup, by LDS-DMA as well.
-#ifndef BJ_F10_PRIO
-#define BJ_F10_PRIO 1
-#endif
+// The coset's twiddle table (8 KB) is fetched once per workgroup, by LDS-DMA as well.  The butterflies run under falling issue
+// priorities (radix16's PRIO).
 template <bool UNIT_FIRST, int LB, bool TILED_IN = false>
 __global__ void __launch_bounds__(64 << LB, 4) ntt_front10_kernel(F10Args a) {
     static_assert(!TILED_IN || LB == TILED_LB, "the tiled layout is defined for one tile width");
@@ -728,25 +614,17 @@ __global__ void __launch_bounds__(64 << LB, 4) ntt_front10_kernel(F10Args a) {
         if (col == col0)
             asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
         else
-#ifdef BJ_F10_AB_NOWAIT   // timing experiment (wrong results): what the pass would cost if the tile were always there
-            asm volatile("s_barrier" ::: "memory");
-#else
             asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");   // this column's pieces have landed; the last eight stores may still fly
-#endif
         u64 x[16];
 #pragma unroll
         for (int i = 0; i < 16; i++) x[i] = lds[i * NT + t];
-        radix16<UNIT_FIRST, 0, BJ_F10_PRIO>(x, lds_tw);
+        radix16<UNIT_FIRST, 0, true>(x, lds_tw);
 #pragma unroll
         for (int i = 0; i < 16; i++) lds[i * NT + t] = x[i];          // in place: no barrier between the read and this write
-#ifdef BJ_F10_AB_NOBAR2
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
-        BJ_R16_SYNC_LDS();
-#endif
+        lds_barrier();
 #pragma unroll
         for (int i = 0; i < 16; i++) x[i] = f10_at(lds, jB1 + i * (32u << LB));
-        radix16_tab<false, BJ_F10_PRIO>(x, lds_tw, 15u + mhB, 31u + 2u * mhB, 63u + 4u * mhB, 127u + 8u * mhB);
+        radix16_tab<false, true>(x, lds_tw, 15u + mhB, 31u + 2u * mhB, 63u + 4u * mhB, 127u + 8u * mhB);
 #pragma unroll
         for (int i = 0; i < 16; i++) f10_at(lds, jB2 ^ (f10_bc<LB>(i * 4u, 0) * 8u)) = x[i];      // inside this wave's region
         const u64 w8 = lds_tw[255u + m92], w9a = lds_tw[511u + 2u * m92], w9b = lds_tw[512u + 2u * m92];
@@ -755,13 +633,13 @@ __global__ void __launch_bounds__(64 << LB, 4) ntt_front10_kernel(F10Args a) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of its region are complete: the region is dead
         if (col + 1 < col1) request_tile(col + 1);
         // round 8: mid bit 1 (registers 8 apart), group m92; round 9: mid bit 0 (registers 4 apart), groups 2 m92, 2 m92 + 1
-        if (BJ_F10_PRIO) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int ll = 0; ll < 4; ll += 2) {
             gl::butterfly2_weak(x[ll], x[8 + ll], w8, x[4 + ll], x[12 + ll], w8);
             gl::butterfly2_weak(x[ll + 1], x[9 + ll], w8, x[5 + ll], x[13 + ll], w8);
         }
-        if (BJ_F10_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
 #pragma unroll
         for (int ll = 0; ll < 4; ll++) gl::butterfly2_weak(x[ll], x[4 + ll], w9a, x[8 + ll], x[12 + ll], w9b);
         const gptr dst = dst0 + (size_t)col * a.out_col_stride;
@@ -796,10 +674,8 @@ struct PairArgs {
     unsigned n_cols, cols_per_block;
     size_t in_col_stride, out_col_stride;
 };
-#ifndef BJ_PAIR_WAVES
-#define BJ_PAIR_WAVES 3
-#endif
-__global__ void __launch_bounds__(256, BJ_PAIR_WAVES) ntt_local12_pair_tiled_kernel(PairArgs a) {
+static constexpr int PAIR_WAVES = 3;
+__global__ void __launch_bounds__(256, PAIR_WAVES) ntt_local12_pair_tiled_kernel(PairArgs a) {
     __shared__ u64 lds[LDS_ELEMS + 2 * 16 + 2 * 16 * 16];
     u64 *lds_twA = lds + LDS_ELEMS;           // [chunk][15 (+1)]
     u64 *lds_twB = lds_twA + 32;              // [chunk][t >> 4][15 (+1)]
@@ -916,10 +792,7 @@ __global__ void __launch_bounds__(256) tiled_permute_kernel(const u64 *in, u64 *
 
 static unsigned pick_cols_per_block(unsigned tiles, unsigned n_cols, unsigned n_cosets) {
     // amortise the per-workgroup twiddle preparation over several columns, but keep >= ~4096 workgroups in flight
-#ifndef BJ_R16_CPB
-#define BJ_R16_CPB 8
-#endif
-    unsigned cpb = BJ_R16_CPB;
+    unsigned cpb = 8;
     while (cpb > 1 && (size_t)tiles * ((n_cols + cpb - 1) / cpb) * n_cosets < 4096) cpb >>= 1;
     return cpb;
 }
@@ -1001,22 +874,11 @@ void launch_ntt_first4(const u64 *in, u64 *out, const u64 *tw, const u64 *round_
                        unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride, size_t out_col_stride, hipStream_t s) {
     R16Args a{in, out, tw, round_scale, log_n, 0, n_cols, 1, in_col_stride, in_coset_stride, out_col_stride};
     const size_t sl = ((size_t)1 << log_n) >> 4;
-    // two adjacent indices per lane (16-byte accesses, 206 VGPRs: 2 waves per SIMD) or one (8-byte accesses, 4 waves)
-    const int v = bj::env().ntt_first4_v;
-    const int mode = bj::env().ntt_first4_mode;      // 0: inputs hoisted (round 3), 3 / 4: reloaded per coset, waves per SIMD
-    dim3 grid((unsigned)((sl / v + 255) / 256), n_cols, 1);
-#define BJ_FIRST4(SC, VV, WV) hipLaunchKernelGGL((ntt_first4_kernel<SC, VV, WV>), grid, dim3(256), 0, s, a, n_cosets)
-    if (v == 2) {
-        if (round_scale) {
-            if (mode == 0) BJ_FIRST4(true, 2, 0); else if (mode == 3) BJ_FIRST4(true, 2, 3); else BJ_FIRST4(true, 2, 4);
-        } else {
-            if (mode == 0) BJ_FIRST4(false, 2, 0); else if (mode == 3) BJ_FIRST4(false, 2, 3); else BJ_FIRST4(false, 2, 4);
-        }
-    } else if (round_scale)
-        BJ_FIRST4(true, 1, 0);
+    dim3 grid((unsigned)((sl / 2 + 255) / 256), n_cols, 1);   // two adjacent indices per lane
+    if (round_scale)
+        hipLaunchKernelGGL(ntt_first4_kernel<true>, grid, dim3(256), 0, s, a, n_cosets);
     else
-        BJ_FIRST4(false, 1, 0);
-#undef BJ_FIRST4
+        hipLaunchKernelGGL(ntt_first4_kernel<false>, grid, dim3(256), 0, s, a, n_cosets);
 }
 
 void launch_ntt_first5(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, unsigned log_n, unsigned n_cols,
@@ -1031,13 +893,10 @@ void launch_ntt_first5(const u64 *in, u64 *out, const u64 *tw, const u64 *round_
 }
 
 // first ten rounds of all cosets (log_n == 22); d_table: n_cosets * 1024 words of device scratch for the twiddle table
-#ifndef BJ_F10_LB
-#define BJ_F10_LB 4   // lo values per tile = 2^LB: 3 -> 64-byte runs, 512 threads, two workgroups per CU; 4 -> full lines, 1024 threads, one
-#endif
 void launch_ntt_front10(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, u64 *d_table, unsigned log_n, unsigned n_cols,
                         unsigned n_cosets, size_t in_col_stride, size_t out_col_stride, hipStream_t s, bool tiled_in) {
     hipLaunchKernelGGL(front10_table_kernel, dim3(n_cosets * 4), dim3(256), 0, s, d_table, tw, round_scale, n_cosets);
-    constexpr int LBN = BJ_F10_LB;
+    constexpr int LBN = 4;   // natural-order input: lo values per tile = 2^LB: 3 -> 64-byte runs, 512 threads, two workgroups per CU; 4 -> full lines, 1024 threads, one
     const int lb = tiled_in ? TILED_LB : LBN;
     const unsigned tiles = 1u << (log_n - 10 - lb);
     const size_t n = (size_t)1 << log_n;

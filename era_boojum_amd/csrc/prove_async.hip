@@ -92,7 +92,6 @@ struct Lane {
             const size_t witness_bytes = ((size_t)(v + w + 1) << ln) * 8;
             int mode = bj::env().async_mode;
             if (mode < 0) mode = witness_bytes >= ((size_t)1 << 30) ? 1 : 0;
-            static const bool dbg = getenv("BJ_ASYNC_DEBUG") != nullptr;
             const auto t_pick = std::chrono::steady_clock::now();
             if (mode == 0) stagger(t->setup);
             {
@@ -105,7 +104,7 @@ struct Lane {
             const bool overlapped = sibling && sibling->busy() && mode != 0;
             const int rc = overlapped ? prove_host_copy_first(sub, t->setup, t->h_variables, t->h_multiplicities, pub, &p, mode)
                                       : bj_prove(sub, t->setup, t->h_variables, t->h_multiplicities, pub, &p);
-            if (dbg)
+            if (bj::env().async_debug)
                 fprintf(stderr, "[lane %p] mode %d overlapped %d: picked up, ran %.1f ms (stagger %.1f ms)\n", (void *)this, mode, (int)overlapped,
                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - started).count(),
                         std::chrono::duration<double, std::milli>(started - t_pick).count());

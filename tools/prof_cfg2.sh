@@ -2,7 +2,7 @@
 # rocprofv3 kernel stats + SQ counters of the cfg2 NTT command (tools/cfg2_ntt.py); outputs under gpurun_out/prof_cfg2_<tag>*
 set -u
 tag=${1:-x}
-quick=${2:-}          # "quick": kernel stats + the first SQ pass only (A/B builds selected through BOOJUM_HIP_LIB: tools/ntt_wait_ab.sh)
+quick=${2:-}          # "quick": kernel stats + the first SQ pass only (a variant library selected through BOOJUM_HIP_LIB)
 repo=$(pwd)
 export TMPDIR=/tmp
 cd /tmp
