@@ -48,6 +48,7 @@ _SIGNATURES = {
     "bj_merkle_tree_cap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
     "bj_merkle_tree_proof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "bj_poseidon2_permute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "bj_poseidon_permute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "bj_fri_fold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint64, C.c_uint64, C.c_uint64]),
     "bj_barycentric_weights": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bj_barycentric_eval_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -217,7 +218,8 @@ class Context:
 
     # -- plumbing
     def set_tree_hasher(self, hasher):
-        """1 = Poseidon2 (default), 2 = Blake2s-256: hasher of the merkle_tree_* / fri calls on this context."""
+        """1 = Poseidon2 (default), 2 = Blake2s-256, 3 = Keccak-256, 4 = Poseidon (v1): hasher of the merkle_tree_* / fri calls
+        on this context (BJ_HASHER_*)."""
         self._check(self._lib.bj_ctx_set_tree_hasher(self._h, int(hasher)))
 
     def set_stream(self, stream_handle):
@@ -413,6 +415,10 @@ class Context:
 
     def poseidon2_permute(self, d_states, n_states):
         self._check(self._lib.bj_poseidon2_permute(self._h, d_states, n_states))
+
+    def poseidon_permute(self, d_states, n_states):
+        """The Poseidon (v1) permutation (BJ_HASHER_POSEIDON / BJ_TRANSCRIPT_POSEIDON) on n_states 12-word device states."""
+        self._check(self._lib.bj_poseidon_permute(self._h, d_states, n_states))
 
     # -- FRI
     def fri_fold(self, d_c0, d_c1, length, d_o0, d_o1, log_full, coset_inv, ch):
@@ -907,8 +913,11 @@ class ProverSetup:
     (bj_setup_create_sharded)."""
 
     def __init__(self, ctx, circuit, fri_lde_factor=8, cap_size=16, security_level=100, pow_bits=0, comm=None,
-                 transcript="poseidon2", setup_base_dump=None, pow_runner="blake2s"):
+                 transcript="poseidon2", setup_base_dump=None, pow_runner="blake2s", tree_hasher=None):
         """pow_runner: "blake2s" | "keccak256" — the PoWRunner (pow.rs), independent of the transcript as in the reference.
+        tree_hasher: None pairs the transcript with its usual hasher (Poseidon2 trees for "poseidon2" / "poseidon", the same byte
+        hash for "blake2s" / "keccak256"); "poseidon2" | "poseidon" | "blake2s" | "keccak256" picks one (BJ_HASHER_*), e.g.
+        "poseidon" with transcript="poseidon" for GoldilocksPoseidonSponge trees + GoldilocksPoisedonTranscript.
         setup_base_dump: the bytes of the reference's `SetupBaseStorage::write_into_buffer` (bj_setup_create_from_dump): the
         columns, constant-column count, table-id column, selector paths, quotient degree and non-residues then come from the
         dump / are computed by the library, and `circuit` only has to carry the geometry and the gate list."""
@@ -945,7 +954,10 @@ class ProverSetup:
                       None if from_dump else nr.ctypes.data_as(C.POINTER(C.c_uint64)), len(c.public_inputs),
                       cols, rows, len(spec_list), spec if spec_list else None)
         self.transcript_kind = {"poseidon2": 1, "poseidon": 2, "blake2s": 3, "keccak256": 4}[transcript]
-        self.hasher_kind = {"blake2s": 2, "keccak256": 3}.get(transcript, 1)      # Transcript::CompatibleCap = TreeHasher::Output
+        if tree_hasher is None:
+            self.hasher_kind = {"blake2s": 2, "keccak256": 3}.get(transcript, 1)  # Transcript::CompatibleCap = TreeHasher::Output
+        else:
+            self.hasher_kind = {"poseidon2": 1, "blake2s": 2, "keccak256": 3, "poseidon": 4}[tree_hasher]
         cfg = _ProofConfig(fri_lde_factor, cap_size, security_level, pow_bits, self.transcript_kind, self.hasher_kind,
                            {"blake2s": 1, "keccak256": 2}[pow_runner])
         sig = np.ascontiguousarray(c.sigmas, dtype=np.uint64)

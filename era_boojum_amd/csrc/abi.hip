@@ -384,7 +384,7 @@ int bj_memcpy_d2d(bj_ctx *ctx, void *d_dst, const void *d_src, size_t bytes) {
 
 int bj_ctx_set_tree_hasher(bj_ctx *ctx, int hasher) {
     if (int rc = bind(ctx)) return rc;
-    if (hasher < BJ_HASHER_POSEIDON2 || hasher > BJ_HASHER_KECCAK256)
+    if (hasher < BJ_HASHER_POSEIDON2 || hasher > BJ_HASHER_POSEIDON)
         return fail(ctx, BJ_ERR_INVALID_ARG, "bj_ctx_set_tree_hasher: unknown hasher %d", hasher);
     ctx->hasher = hasher;
     return BJ_OK;
@@ -752,6 +752,15 @@ int bj_poseidon2_permute(bj_ctx *ctx, uint64_t *d_states, size_t n_states) {
     if (n_states == 0) return BJ_OK;
     if (!d_states) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_poseidon2_permute: null device pointer");
     bj::launch_poseidon2_permute_states(d_states, n_states, ctx->stream);
+    BJ_CHECK_LAUNCH(ctx);
+    return BJ_OK;
+}
+
+int bj_poseidon_permute(bj_ctx *ctx, uint64_t *d_states, size_t n_states) {
+    if (int rc = bind(ctx)) return rc;
+    if (n_states == 0) return BJ_OK;
+    if (!d_states) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_poseidon_permute: null device pointer");
+    bj::launch_poseidon1_permute_states(d_states, n_states, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }

@@ -221,6 +221,8 @@ void launch_tree_leaves(int hasher, const u64 *d_base, size_t col_stride, const 
         launch_blake2s_leaves(d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests, s);
     else if (hasher == BJ_HASHER_KECCAK256)
         launch_keccak_leaves(d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests, s);
+    else if (hasher == BJ_HASHER_POSEIDON)
+        launch_poseidon1_leaves(d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests, s);
     else
         launch_poseidon2_leaves(d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests, s);
 }
@@ -230,6 +232,8 @@ void launch_tree_leaves_chunked(int hasher, const u64 *d_src0, const u64 *d_src1
         launch_blake2s_leaves_chunked(d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests, s);
     else if (hasher == BJ_HASHER_KECCAK256)
         launch_keccak_leaves_chunked(d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests, s);
+    else if (hasher == BJ_HASHER_POSEIDON)
+        launch_poseidon1_leaves_chunked(d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests, s);
     else
         launch_poseidon2_leaves_chunked(d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests, s);
 }
@@ -238,8 +242,17 @@ void launch_tree_node_layers(int hasher, u64 *d_tree, size_t num_leaves, size_t 
         launch_blake2s_node_layers(d_tree, num_leaves, cap_size, s);
     else if (hasher == BJ_HASHER_KECCAK256)
         launch_keccak_node_layers(d_tree, num_leaves, cap_size, s);
+    else if (hasher == BJ_HASHER_POSEIDON)
+        launch_poseidon1_node_layers(d_tree, num_leaves, cap_size, s);
     else
         launch_poseidon2_node_layers(d_tree, num_leaves, cap_size, s);
+}
+void launch_tree_leaves_absorb(int hasher, const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves,
+                               u64 *d_capacity, u64 *d_digests, bool first, bool last, hipStream_t s) {
+    if (hasher == BJ_HASHER_POSEIDON)
+        launch_poseidon1_leaves_absorb(d_base, col_stride, n_cols, num_leaves, d_capacity, d_digests, first, last, s);
+    else
+        launch_poseidon2_leaves_absorb(d_base, col_stride, n_cols, num_leaves, d_capacity, d_digests, first, last, s);
 }
 
 }  // namespace bj

@@ -1,0 +1,238 @@
+// Poseidon (v1) (Goldilocks, t = 12, rate 8 / capacity 4, x^7, 4 + 22 + 4 rounds) Merkle-tree hashing for gfx950:
+// the tree hasher GoldilocksPoseidonSponge<AbsorptionModeOverwrite> of the reference.
+//
+// Must equal the reference's CPU tree hasher bit for bit (as canonical residues):
+//   permutation        src/implementations/poseidon_goldilocks_naive.rs:67-165
+//                      every round: + its 12 constants (the 360-entry table Poseidon2 uses), x^7 on all 12 words (rounds
+//                      0-3, 26-29) or on word 0 (rounds 4-25), then the circulant MDS M[row][col] = 2^EXPS[(col - row) mod 12]
+//   sponge             src/algebraic_props/sponge.rs:345-357 + 224-346   overwrite absorption, zero-padded tail, no length tag
+//   leaf / node hash   src/cs/oracle/mod.rs:114-176                      node = perm(L || R || 0)[0..4]
+//   tree               src/cs/oracle/merkle_tree.rs (the same layouts as poseidon2.hip)
+//
+// Mapping: as poseidon2.hip — one lane = one leaf (or one parent node), the 12-word sponge state in VGPRs, coalesced
+// column loads, wave-uniform round constants through the scalar cache.
+// Arithmetic is lazy as in poseidon2.hip: state words are weak residues (any u64 congruent to the value) between rounds;
+// the MDS layer's entries are powers of two: the low and the high 32-bit halves of the state are accumulated apart, one
+// multiply-add by 2^e per term (no reduction inside the sum), and folded once per output word.
+#include "gl.h"
+#include "kernels.h"
+#include "poseidon_rc.inc"
+
+using gl::u64;
+using gl::u32;
+
+namespace bj {
+
+__constant__ u64 POSEIDON1_RC[BJ_POSEIDON_NUM_RC] = BJ_POSEIDON_RC_TABLE;
+
+namespace {
+
+// weak + canonical constant -> weak: "+EPS" on carry; the wrapped sum is < rc < p, so adding EPS cannot carry again
+__device__ __forceinline__ u64 p1_add_rc(u64 x, u64 rc) {
+    const u64 s = x + rc;
+    return s < x ? s + 0xFFFFFFFFull : s;
+}
+__device__ __forceinline__ u64 p1_pow7(u64 x) {   // weak -> weak
+    const u64 x2 = gl::mul_weak(x, x), x3 = gl::mul_weak(x2, x), x4 = gl::mul_weak(x2, x2);
+    return gl::mul_weak(x4, x3);
+}
+
+// MDS_MATRIX_EXPS of poseidon_goldilocks_naive.rs; row `row` of the matrix is 2^EXPS[(col - row) mod 12]
+constexpr unsigned P1_EXPS[12] = {0, 0, 1, 0, 3, 5, 1, 8, 12, 3, 16, 10};
+
+// x * y + c on the 64-bit multiply-add (one VALU instruction; a shift-add chain is two, v_lshl_add_u64 shifts by at most 4);
+// the power of two travels in an SGPR (VOP3 has no literal operand on gfx950).  Callers bound the sums: no carry out.
+__device__ __forceinline__ u64 p1_mad(u32 x, u32 y, u64 c) {
+    u64 r;
+    asm("v_mad_u64_u32 %[r], vcc, %[x], %[y], %[c]" : [r] "=v"(r) : [x] "v"(x), [y] "s"(y), [c] "v"(c) : "vcc");
+    return r;
+}
+
+// out[row] = sum_col s[col] * 2^EXPS[(col - row) mod 12] for weak s, as a weak residue.
+//   A = sum lo32(s[col]) * 2^e,  B = sum hi32(s[col]) * 2^e:  each < 2^32 * sum_k 2^EXPS[k] = 2^32 * 70967 < 2^49 (no carry)
+//   value = A + B * 2^32 = A + hi32(B) * 2^64 + lo32(B) * 2^32 == A + hi32(B) * EPS + lo32(B) * 2^32   (mod p, 2^64 == EPS)
+//   T = A + hi32(B) * EPS < 2^49 + 2^49 (no carry);  r = T + (lo32(B) << 32) mod 2^64, "+EPS" on its wrap — after a wrap
+//   r < T < 2^50, so the correction cannot carry again.
+__device__ __forceinline__ void p1_mds(u64 (&s)[12]) {
+    u64 out[12];
+#pragma unroll
+    for (int row = 0; row < 12; row++) {
+        u64 A = 0, B = 0;
+#pragma unroll
+        for (int col = 0; col < 12; col++) {
+            const u32 m = 1u << P1_EXPS[(col + 12 - row) % 12];
+            A = p1_mad(gl::lo32(s[col]), m, A);
+            B = p1_mad(gl::hi32(s[col]), m, B);
+        }
+        const u64 T = p1_mad(gl::hi32(B), 0xFFFFFFFFu, A);
+        u32 c;
+        const u32 hi = __builtin_addc(gl::hi32(T), gl::lo32(B), 0u, &c);
+        out[row] = gl::pack(gl::lo32(T), hi) + (c ? 0xFFFFFFFFull : 0ull);
+    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = out[k];
+}
+
+__device__ __forceinline__ void p1_full_round(u64 (&s)[12], int r) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = p1_pow7(p1_add_rc(s[k], POSEIDON1_RC[12 * r + k]));
+    p1_mds(s);
+}
+
+}  // namespace
+
+// state in: any u64 words; state out: weak words (canonicalise what leaves the sponge with gl::canon)
+__device__ __forceinline__ void poseidon1_permutation(u64 (&s)[12]) {
+    int r = 0;
+#pragma unroll 1
+    for (int i = 0; i < 4; i++, r++) p1_full_round(s, r);
+#pragma unroll 1
+    for (int i = 0; i < 22; i++, r++) {
+        s[0] = p1_pow7(p1_add_rc(s[0], POSEIDON1_RC[12 * r]));
+#pragma unroll
+        for (int k = 1; k < 12; k++) s[k] = p1_add_rc(s[k], POSEIDON1_RC[12 * r + k]);
+        p1_mds(s);
+    }
+#pragma unroll 1
+    for (int i = 0; i < 4; i++, r++) p1_full_round(s, r);
+}
+
+__device__ __forceinline__ void p1_store_digest(u64 *digests, size_t i, const u64 (&s)[12]) {
+    ulonglong2 *d = reinterpret_cast<ulonglong2 *>(digests + 4 * i);
+    d[0] = make_ulonglong2(gl::canon(s[0]), gl::canon(s[1]));
+    d[1] = make_ulonglong2(gl::canon(s[2]), gl::canon(s[3]));
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// leaf hashing: leaf I = sponge(cols[0][I], cols[1][I], ...), columns as base + c * stride or through a device array of
+// column pointers.  One call site of the permutation (instruction-cache footprint); the zero-padded tail by wave-uniform
+// conditions.
+// ---------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+poseidon1_leaves_kernel(const u64 *base, size_t col_stride, const u64 *const *col_ptrs, unsigned n_cols, size_t num_leaves,
+                        u64 *digests) {
+    const size_t I = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= num_leaves) return;
+    u64 s[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = 0;
+    for (unsigned c = 0; c < n_cols; c += 8) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            if (c + k < n_cols) {
+                const u64 *p = col_ptrs ? col_ptrs[c + k] : base + (size_t)(c + k) * col_stride;
+                s[k] = p[I];
+            } else {
+                s[k] = 0;
+            }
+        }
+        poseidon1_permutation(s);
+    }
+    p1_store_digest(digests, I, s);
+}
+
+// a run of absorptions of the same sponge for columns that arrive in groups (bj_prove's group-wise witness plan): state[8..12]
+// <- what the previous group left in `capacity` ([4][num_leaves], zeros before the first group); every group but the last
+// holds a multiple of eight columns; the last writes the digest, the others their capacity words (poseidon2.hip: same plan)
+__global__ void __launch_bounds__(256)
+poseidon1_leaves_absorb_kernel(const u64 *base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *capacity, u64 *digests,
+                               int first, int last) {
+    const size_t I = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (I >= num_leaves) return;
+    u64 s[12];
+#pragma unroll
+    for (int k = 0; k < 4; k++) s[8 + k] = first ? 0 : capacity[(size_t)k * num_leaves + I];
+    for (unsigned c = 0; c < n_cols; c += 8) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) s[k] = c + k < n_cols ? base[(size_t)(c + k) * col_stride + I] : 0;
+        poseidon1_permutation(s);
+    }
+    if (last) {
+        p1_store_digest(digests, I, s);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) capacity[(size_t)k * num_leaves + I] = s[8 + k];
+    }
+}
+
+// leaf j = sponge( src0[jE..(j+1)E) || src1[jE..(j+1)E) )                  (FRI oracles, merkle_tree.rs:176-386)
+__global__ void __launch_bounds__(256)
+poseidon1_leaves_chunked_kernel(const u64 *src0, const u64 *src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
+                                u64 *digests) {
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= num_leaves) return;
+    const unsigned E = 1u << log_e;
+    const unsigned total = n_srcs * E;
+    u64 s[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = 0;
+    for (unsigned t = 0; t < total; t += 8) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const unsigned idx = t + k;   // wave-uniform
+            u64 v = 0;
+            if (idx < total) {
+                const u64 *p = (idx >> log_e) == 0 ? src0 : src1;
+                v = p[j * E + (idx & (E - 1))];
+            }
+            s[k] = v;
+        }
+        poseidon1_permutation(s);
+    }
+    p1_store_digest(digests, j, s);
+}
+
+// node layer: parent i = perm(left || right || 0000)[0..4]                 (oracle/mod.rs:162-168)
+__global__ void __launch_bounds__(256) poseidon1_nodes_kernel(const u64 *children, u64 *parents, size_t num_parents) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_parents) return;
+    const ulonglong2 *c = reinterpret_cast<const ulonglong2 *>(children + 8 * i);
+    const ulonglong2 a = c[0], b = c[1], e = c[2], f = c[3];
+    u64 s[12] = {a.x, a.y, b.x, b.y, e.x, e.y, f.x, f.y, 0, 0, 0, 0};
+    poseidon1_permutation(s);
+    p1_store_digest(parents, i, s);
+}
+
+__global__ void poseidon1_permute_states_kernel(u64 *states, size_t n_states) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_states) return;
+    u64 s[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) s[k] = states[12 * i + k];
+    poseidon1_permutation(s);
+#pragma unroll
+    for (int k = 0; k < 12; k++) states[12 * i + k] = gl::canon(s[k]);
+}
+
+void launch_poseidon1_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
+                             size_t num_leaves, u64 *d_digests, hipStream_t s) {
+    hipLaunchKernelGGL(poseidon1_leaves_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, s, d_base, col_stride,
+                       d_col_ptrs, n_cols, num_leaves, d_digests);
+}
+void launch_poseidon1_leaves_absorb(const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *d_capacity,
+                                    u64 *d_digests, bool first, bool last, hipStream_t s) {
+    hipLaunchKernelGGL(poseidon1_leaves_absorb_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, s, d_base,
+                       col_stride, n_cols, num_leaves, d_capacity, d_digests, first ? 1 : 0, last ? 1 : 0);
+}
+void launch_poseidon1_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
+                                     u64 *d_digests, hipStream_t s) {
+    hipLaunchKernelGGL(poseidon1_leaves_chunked_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, s, d_src0,
+                       d_src1, n_srcs, log_e, num_leaves, d_digests);
+}
+// tree layout: layer 0 = num_leaves digests, then num_leaves/2, ... down to cap_size (inclusive), back to back
+void launch_poseidon1_node_layers(u64 *d_tree, size_t num_leaves, size_t cap_size, hipStream_t s) {
+    u64 *prev = d_tree;
+    size_t len = num_leaves;
+    while (len > cap_size) {
+        u64 *next = prev + 4 * len;
+        const size_t nl = len / 2;
+        hipLaunchKernelGGL(poseidon1_nodes_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, prev, next, nl);
+        prev = next;
+        len = nl;
+    }
+}
+void launch_poseidon1_permute_states(u64 *d_states, size_t n_states, hipStream_t s) {
+    hipLaunchKernelGGL(poseidon1_permute_states_kernel, dim3((unsigned)((n_states + 63) / 64)), dim3(64), 0, s, d_states, n_states);
+}
+
+}  // namespace bj

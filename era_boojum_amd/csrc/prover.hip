@@ -277,11 +277,12 @@ int bj_setup_create_sharded(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: quotient degree / fri_lde_factor / cap must be powers of two");
     {
         const unsigned tk = cfg->transcript ? cfg->transcript : BJ_TRANSCRIPT_POSEIDON2, hk = cfg->tree_hasher ? cfg->tree_hasher : BJ_HASHER_POSEIDON2;
-        if (tk > BJ_TRANSCRIPT_KECCAK256 || hk > BJ_HASHER_KECCAK256) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: unknown transcript / tree hasher");
-        const bool byte_hasher = hk != BJ_HASHER_POSEIDON2, byte_transcript = tk == BJ_TRANSCRIPT_BLAKE2S || tk == BJ_TRANSCRIPT_KECCAK256;
+        if (tk > BJ_TRANSCRIPT_KECCAK256 || hk > BJ_HASHER_POSEIDON) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: unknown transcript / tree hasher");
+        const bool byte_hasher = hk == BJ_HASHER_BLAKE2S || hk == BJ_HASHER_KECCAK256,
+                   byte_transcript = tk == BJ_TRANSCRIPT_BLAKE2S || tk == BJ_TRANSCRIPT_KECCAK256;
         if (byte_hasher != byte_transcript)   // Transcript::CompatibleCap = TreeHasher::Output (prover.rs:153-168)
             return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: a byte tree hasher (Blake2s / Keccak256) goes with a byte transcript and "
-                                                     "the Poseidon2 tree hasher with an algebraic transcript");
+                                                     "an algebraic tree hasher (Poseidon2 / Poseidon) with an algebraic transcript");
     }
     if (cfg->fri_lde_factor > 64 || c->quotient_degree > 64)   // per-coset tables of the quotient kernels hold 64 entries
         return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: fri_lde_factor and quotient_degree are limited to 64");
@@ -746,12 +747,13 @@ int prove_impl(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, cons
         // groups up as they land.  Column nW - 1 is the multiplicity column when there are lookups.
         if (!ctx->copy_stream) BJ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
         // groups of G columns, at most 64 of them (one event each): a wide witness gets wider groups instead of an error.  With
-        // the Poseidon2 tree hasher and G a multiple of the sponge's rate, a group is also absorbed into the leaf sponges as soon
+        // an algebraic tree hasher (Poseidon2 / Poseidon) and G a multiple of the sponge's rate, a group is also absorbed into the leaf sponges as soon
         // as it is extended (the capacity words of every leaf wait in HBM between the groups), so that hashing — the dominant
         // kernel — runs under the transfer of the later groups instead of after the last one has landed.
         unsigned G = hw->group;
         if ((nW + G - 1) / G > 64) G = (nW + 63) / 64;
-        const bool absorb = ctx->hasher == BJ_HASHER_POSEIDON2 && !bj::env().prove_no_absorb && !hw->no_absorb;
+        const bool algebraic = ctx->hasher == BJ_HASHER_POSEIDON2 || ctx->hasher == BJ_HASHER_POSEIDON;
+        const bool absorb = algebraic && !bj::env().prove_no_absorb && !hw->no_absorb;
         if (absorb) G = (G + 7) / 8 * 8;
         // The plan: transfer / transform groups [c0, c1) with one event each, and after some of them one absorption run over the
         // columns extended since the last one.  Nothing can be hashed before the first G columns have crossed PCIe, so those go in
@@ -815,7 +817,8 @@ int prove_impl(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, cons
             if (!rc) rc = lde_cols(mono.p + (size_t)c0 * n, wit_lde.p + (size_t)c0 * Ln, Ln, c1 - c0, S->log_L, S->c0, S->cl);
             if (absorb && !rc && plan[g].absorb_from != NONE) {
                 const unsigned a0 = plan[g].absorb_from;
-                bj::launch_poseidon2_leaves_absorb(wit_lde.p + (size_t)a0 * Ln, Ln, c1 - a0, N, capacity.p, wit_tree.p, a0 == 0, c1 == nW, st);
+                bj::launch_tree_leaves_absorb(ctx->hasher, wit_lde.p + (size_t)a0 * Ln, Ln, c1 - a0, N, capacity.p, wit_tree.p, a0 == 0,
+                                              c1 == nW, st);
             }
         }
         if (absorb) BJ_HIP(ctx, hipEventRecord(ctx->ev1, st));

@@ -58,12 +58,12 @@ def record(ctx, setups, world, d_vars, d_mult, capture_bytes, device):
 
 
 def measure(circuit, world, fri_lde=8, cap=16, security=100, transcript="poseidon2", steps=3, warmup=1, device=0, ranks=None,
-            reference_proof=None, d_vars=None, d_mult=None, setup_cap=None):
+            reference_proof=None, d_vars=None, d_mult=None, setup_cap=None, tree_hasher=None):
     """Returns {"world", "ranks": {r: {"ms_per_step", "stages_ms", "ms_in_replayed_copies", "setup_bytes", "workspace"}}, "max_ms",
     "slowest_rank", "min_ms", "collectives_per_proof", "mb_gathered_per_proof", "record_pass_s"}.  Raises if any rank's proof differs
     from `reference_proof` (the single-GPU bytes) or a replayed contribution differs from the recording.  setup_cap: the setup
     oracle's cap (4 * cap u64, e.g. ProverSetup.cap() of a single-GPU setup): what the one collective of bj_setup_create_sharded
-    gathers; computed through a single-GPU setup when None."""
+    gathers; computed through a single-GPU setup when None.  tree_hasher: ProverSetup's (None: the transcript's usual hasher)."""
     import torch
     import era_boojum_amd as E
     dev = torch.device("cuda", device)
@@ -76,14 +76,15 @@ def measure(circuit, world, fri_lde=8, cap=16, security=100, transcript="poseido
     setups = [None] * world
     try:
         if setup_cap is None:
-            s1 = E.ProverSetup(ctx, circuit, fri_lde, cap, security, transcript=transcript)
+            s1 = E.ProverSetup(ctx, circuit, fri_lde, cap, security, transcript=transcript, tree_hasher=tree_hasher)
             setup_cap = s1.cap()
             s1.close()
         d_cap = torch.from_numpy(np.ascontiguousarray(setup_cap, dtype=np.uint64).view(np.uint8).copy()).to(dev)
         t0 = time.perf_counter()
         for r in range(world):
             comm = E.ReplayComm(ctx, r, world, [(d_cap.data_ptr(), d_cap.numel())], n_setup=1, keepalive=d_cap)
-            setups[r] = E.ProverSetup(ctx, circuit, fri_lde, cap, security, comm=comm, transcript=transcript)
+            setups[r] = E.ProverSetup(ctx, circuit, fri_lde, cap, security, comm=comm, transcript=transcript,
+                                      tree_hasher=tree_hasher)
             setups[r]._replay_keepalive = comm
             if not np.array_equal(np.asarray(setups[r].cap()).reshape(-1), np.asarray(setup_cap, dtype=np.uint64).reshape(-1)):
                 raise RuntimeError("rank %d: the sharded setup's cap differs from the single-GPU one" % r)

@@ -73,7 +73,8 @@ int bj_free(bj_ctx *ctx, void *d_ptr);
 int bj_memcpy_h2d(bj_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);
 int bj_memcpy_d2h(bj_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
 int bj_memcpy_d2d(bj_ctx *ctx, void *d_dst, const void *d_src, size_t bytes); /* stream-ordered, then synchronised */
-/* Tree hasher used by the bj_merkle_tree_* / bj_fri_prove calls on this context (BJ_HASHER_*, default Poseidon2);
+/* Tree hasher used by the bj_merkle_tree_* / bj_fri_prove calls on this context (BJ_HASHER_POSEIDON2..BJ_HASHER_POSEIDON,
+ * default Poseidon2);
  * bj_prove sets it from its proof config for the duration of the proof. */
 int bj_ctx_set_tree_hasher(bj_ctx *ctx, int hasher);
 
@@ -189,6 +190,8 @@ int bj_merkle_tree_proof(bj_ctx *ctx, const uint64_t *d_tree, size_t num_leaves,
                          uint64_t *h_leaf_digest, uint64_t *h_path);
 /* Raw permutation on n_states 12-word states in device memory (testing / transcript offload). */
 int bj_poseidon2_permute(bj_ctx *ctx, uint64_t *d_states, size_t n_states);
+/* The same for the Poseidon (v1) permutation of BJ_HASHER_POSEIDON / BJ_TRANSCRIPT_POSEIDON; canonical words out. */
+int bj_poseidon_permute(bj_ctx *ctx, uint64_t *d_states, size_t n_states);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * FRI.  Replaces fold_multiple / interpolate_* (src/cs/implementations/fri/mod.rs:362-678).
@@ -248,6 +251,8 @@ typedef struct bj_transcript bj_transcript;
 #define BJ_HASHER_POSEIDON2 1 /* GoldilocksPoseidon2Sponge<AbsorptionModeOverwrite>: four canonical field elements */
 #define BJ_HASHER_BLAKE2S 2   /* blake2::Blake2s256: the 32 digest bytes, little-endian packed into the four words */
 #define BJ_HASHER_KECCAK256 3 /* sha3::Keccak256 (original 0x01 padding, oracle/mod.rs:247-312): digest bytes as above */
+#define BJ_HASHER_POSEIDON 4  /* GoldilocksPoseidonSponge<AbsorptionModeOverwrite> (sponge.rs:345-357): the Poseidon2 sponge around
+                               * the Poseidon (v1) permutation (poseidon_goldilocks_naive.rs); four canonical field elements */
 /* bj_proof_config.pow_runner: the PoWRunner implementations of src/cs/implementations/pow.rs */
 #define BJ_POW_BLAKE2S256 1   /* pow.rs:50-133 */
 #define BJ_POW_KECCAK256 2    /* pow.rs:139-230 (original Keccak padding, as the tree hasher) */
@@ -487,8 +492,9 @@ typedef struct bj_proof_config { /* ProofConfig, prover.rs:55-73 */
     unsigned security_level;
     unsigned pow_bits; /* proof of work (pow.rs), <= 32; 0 = off as in the benches (NoPow).  The runner is pow_runner below */
     unsigned transcript;  /* 0 or BJ_TRANSCRIPT_POSEIDON2 (default), BJ_TRANSCRIPT_POSEIDON, BJ_TRANSCRIPT_BLAKE2S, _KECCAK256 */
-    unsigned tree_hasher; /* 0 or BJ_HASHER_POSEIDON2 (default, with an algebraic transcript), BJ_HASHER_BLAKE2S /
-                           * BJ_HASHER_KECCAK256 (with a byte transcript): the transcript's CompatibleCap must be the hasher's Output */
+    unsigned tree_hasher; /* 0 or BJ_HASHER_POSEIDON2 (default), BJ_HASHER_POSEIDON (both with an algebraic transcript),
+                           * BJ_HASHER_BLAKE2S / BJ_HASHER_KECCAK256 (with a byte transcript): the transcript's CompatibleCap must be
+                           * the hasher's Output */
     unsigned pow_runner;  /* the POW type parameter of prove_cpu_basic (prover.rs:153-168; trait PoWRunner, pow.rs:6-31), independent of
                            * the transcript and the tree hasher as in the reference: 0 or BJ_POW_BLAKE2S256 (impl PoWRunner for
                            * Blake2s256, pow.rs:50-133), BJ_POW_KECCAK256 (impl PoWRunner for Keccak256, pow.rs:139-230).  Both search

@@ -204,6 +204,11 @@ impl<P: crate::field::traits::field_like::PrimeFieldLikeVectorized<Base = F>, CF
     /// cosets over the processes of the communicator (one GPU each).
     /// `POW` is the proof-of-work type parameter of `prove_cpu_basic` (prover.rs:153-168; `NoPow`, `Blake2s256` or `Keccak256`,
     /// pow.rs): it travels to the library as `bj_proof_config.pow_runner` and is read only when `proof_config.pow_bits != 0`.
+    /// `tree_hasher_kind` names `H`: `GoldilocksPoseidon2Sponge<AbsorptionModeOverwrite>` → `BJ_HASHER_POSEIDON2`,
+    /// `GoldilocksPoseidonSponge<AbsorptionModeOverwrite>` → `BJ_HASHER_POSEIDON` (both with an algebraic transcript:
+    /// `GoldilocksPoisedon2Transcript` → `BJ_TRANSCRIPT_POSEIDON2`, `GoldilocksPoisedonTranscript` → `BJ_TRANSCRIPT_POSEIDON`),
+    /// `Blake2s256` → `BJ_HASHER_BLAKE2S`, `Keccak256` → `BJ_HASHER_KECCAK256` (with their byte transcripts).  Caps are four
+    /// words either way (`caps_from_words`).
     pub fn hip_setup<H: TreeHasher<F>, POW: crate::cs::implementations::pow::PoWRunner>(
         &self,
         ctx: &HipCtx,
