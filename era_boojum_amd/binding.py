@@ -11,6 +11,7 @@ u64p = C.POINTER(C.c_uint64)
 # every symbol include/boojum_hip.h declares (checked by tests/test_abi_symbols.py against the header text)
 _SIGNATURES = {
     "bj_abi_version": (C.c_int, []),
+    "bj_gate_kind_supported": (C.c_int, [C.c_int]),
     "bj_env_reload": (None, []),
     "bj_device_count": (C.c_int, []),
     "bj_status_string": (C.c_char_p, [C.c_int]),
@@ -575,7 +576,8 @@ class _GateDesc(C.Structure):
 
 
 def gate_desc_array(gates):
-    """bj_gate_desc[] for gates with the attributes of synthetic.Gate (kind, path, reps, var_stride, const_stride, num_terms)."""
+    """bj_gate_desc[] for gates with the attributes of synthetic.Gate (kind, path, reps, var_stride, const_stride, num_terms); an
+    op-list gate (kind 5) points at its program, which the caller keeps alive for the call."""
     arr = (_GateDesc * len(gates))()
     for i, g in enumerate(gates):
         arr[i].kind, arr[i].path_len = int(g.kind), len(g.path)
@@ -583,6 +585,8 @@ def gate_desc_array(gates):
             arr[i].path[b] = 1 if bit else 0
         arr[i].num_repetitions, arr[i].var_stride, arr[i].const_stride = int(g.reps), int(g.var_stride), int(g.const_stride)
         arr[i].num_terms, arr[i].program = int(g.num_terms), None
+        if int(g.kind) == 5 and getattr(g, "program", None) is not None:
+            arr[i].program = C.cast(C.pointer(g.program.struct), C.c_void_p)
     return arr
 
 
@@ -936,7 +940,7 @@ class ProverSetup:
                 g.reps, g.var_stride, g.const_stride, g.num_terms
             gates[i].wit_stride = getattr(g, "wit_stride", 0)
             prog = getattr(g, "program", None)       # seam S3: evaluate this gate from its op list (gate_program.py)
-            if prog is not None:
+            if prog is not None and g.kind != 7:     # BJ_GATE_POSEIDON_FLATTENED: its program serves the host-side checks only
                 gates[i].kind = 5
                 gates[i].program = C.cast(C.pointer(prog.struct), C.c_void_p)
         spec_list = list(getattr(c, "specialized_gates", []) or [])

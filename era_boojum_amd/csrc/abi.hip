@@ -226,6 +226,8 @@ extern "C" {
 
 int bj_abi_version(void) { return BJ_ABI_VERSION; }
 
+int bj_gate_kind_supported(int kind) { return kind >= BJ_GATE_CONSTANT_ALLOCATOR && kind <= BJ_GATE_POSEIDON_FLATTENED ? 1 : 0; }
+
 int bj_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;

@@ -19,6 +19,9 @@ namespace bj {
 void launch_quotient_poseidon2_flattened(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
                                          unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q,
                                          u64 *d_out0, u64 *d_out1, hipStream_t s);
+void launch_quotient_poseidon_flattened(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
+                                        unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q,
+                                        u64 *d_out0, u64 *d_out1, hipStream_t s);
 
 namespace {
 constexpr int MAX_TMP = BJ_GATE_PROGRAM_MAX_TEMPORARIES;
@@ -139,10 +142,10 @@ int DevProgram::upload(bj_ctx *ctx, const bj_gate_program *p) {
     reads_witness = C.wit_extent != 0;
     fp[0] = C.fp[0];
     fp[1] = C.fp[1];
-    // the fingerprint selects build-time kernels and the hand-written Poseidon2 evaluator: a hit whose structural summary is not
+    // the fingerprint selects build-time kernels and the hand-written Poseidon2 / Poseidon evaluators: a hit whose structural summary is not
     // the recorded one (a collision of the non-cryptographic mix, accidental or constructed) is not a hit — the program keeps a
     // fingerprint no table knows and goes to the run-time compiler / interpreter, which work from the op list itself
-    if ((gate_aot_known(fp[0], fp[1]) || gate_is_poseidon2_flattened(fp[0], fp[1])) &&
+    if ((gate_aot_known(fp[0], fp[1]) || gate_is_poseidon2_flattened(fp[0], fp[1]) || gate_is_poseidon_flattened(fp[0], fp[1])) &&
         !gate_aot_summary_matches(fp[0], C.num_ops, C.num_slots, C.num_terms, C.var_extent, C.const_extent, C.wit_extent))
         fp[0] = fp[1] = 0;
     const size_t bytes = rel.size() * sizeof(DevRelation) + vals.size() * 8 + 64;
@@ -154,7 +157,8 @@ int DevProgram::upload(bj_ctx *ctx, const bj_gate_program *p) {
     if (!rc) rc = bj_memcpy_h2d(ctx, d_rel, rel.data(), rel.size() * sizeof(DevRelation));
     // no build-time kernel for this function: compile one now (gate_jit.hip); the interpreter remains the fallback when the
     // run-time compiler is not installed or BJ_GATE_NO_JIT is set
-    if (!rc && !gate_aot_known(fp[0], fp[1]) && !gate_is_poseidon2_flattened(fp[0], fp[1])) jit = jit_gate_kernel(ctx, C);
+    if (!rc && !gate_aot_known(fp[0], fp[1]) && !gate_is_poseidon2_flattened(fp[0], fp[1]) && !gate_is_poseidon_flattened(fp[0], fp[1]))
+        jit = jit_gate_kernel(ctx, C);
     return rc;
 }
 void DevProgram::release() {
@@ -227,6 +231,11 @@ void launch_gate_program(const DevProgram &P, const u64 *d_vars, size_t var_stri
         launch_quotient_poseidon2_flattened(d_vars, var_stride, d_consts, const_stride, path_len, path, d_alphas, Q, d_out0, d_out1, s);
         return;
     }
+    // the same for the Poseidon (v1) flattened gate (csrc/gate_poseidon1.hip)
+    if (!no_aot && d_alphas && !d_terms && reps == 1 && gate_is_poseidon_flattened(P.fp[0], P.fp[1])) {
+        launch_quotient_poseidon_flattened(d_vars, var_stride, d_consts, const_stride, path_len, path, d_alphas, Q, d_out0, d_out1, s);
+        return;
+    }
     if (P.jit && launch_jit_gate(P.jit, a, grid.x, s)) return;                // compiled from this very op list at upload
     if (P.n_tmp <= 8)
         hipLaunchKernelGGL((gate_program_kernel<8, 1>), grid, block, 0, s, a);
@@ -246,7 +255,8 @@ extern "C" int bj_gate_program_generated(const bj_gate_program *program) {
     bj::canon::Program C;
     std::string err;
     if (bj::canon::canonicalize(program, &C, &err)) return 0;
-    return ((bj::gate_aot_known(C.fp[0], C.fp[1]) || bj::gate_is_poseidon2_flattened(C.fp[0], C.fp[1])) &&
+    return ((bj::gate_aot_known(C.fp[0], C.fp[1]) || bj::gate_is_poseidon2_flattened(C.fp[0], C.fp[1]) ||
+             bj::gate_is_poseidon_flattened(C.fp[0], C.fp[1])) &&
             bj::gate_aot_summary_matches(C.fp[0], C.num_ops, C.num_slots, C.num_terms, C.var_extent, C.const_extent, C.wit_extent)) ? 1 : 0;
 }
 

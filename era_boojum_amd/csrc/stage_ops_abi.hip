@@ -2,7 +2,9 @@
 // stand-alone operators): the kernels bj_prove runs, callable on caller-provided device columns so that each can be
 // compared with the reference function it replaces (and with oracle/prover_ops.c in tests/test_gpu_stage_ops.py).
 #include "ctx.h"
+#include "gate_program.h"
 
+#include <memory>
 #include <vector>
 
 using gl::u64;
@@ -14,6 +16,9 @@ void launch_copy_perm_stage2(const u64 *d_vars, size_t var_stride, const u64 *d_
 void launch_lookup_polys(const u64 *d_lvars, size_t var_stride, const u64 *d_table_id, const u64 *d_tables,
                          size_t tab_stride, const u64 *d_mult, unsigned reps, unsigned w, unsigned log_n,
                          const u64 *beta, const u64 *gamma, u64 *d_A, u64 *d_B, hipStream_t s);
+void launch_quotient_poseidon_flattened(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
+                                        unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q,
+                                        u64 *d_out0, u64 *d_out1, hipStream_t s);
 void launch_quotient_gates(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
                            const int *h_gates_flat, unsigned n_gates, const u64 *d_alphas, size_t Q, u64 *d_out0,
                            u64 *d_out1, hipStream_t s);
@@ -104,12 +109,37 @@ int bj_quotient_gates(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, un
     if (var_stride < num_points || const_stride < num_points)
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: column stride below the number of points");
     std::vector<int> flat;
+    std::vector<std::unique_ptr<bj::DevProgram>> programs(num_gates);   // op-list gates, uploaded below
     size_t n_terms = 0;
     for (unsigned g = 0; g < num_gates; g++) {
         const bj_gate_desc &G = gates[g];
+        if (G.kind == BJ_GATE_PROGRAM) {   // an op list in quotient mode, as bj_prove launches it (generated, compiled or interpreted)
+            unsigned ve = 0, ce = 0, we = 0;
+            if (G.program) bj::gate_program_extent(G.program, &ve, &ce, &we);
+            if (!G.program || G.path_len > 6 || G.num_repetitions == 0 || G.num_terms != G.program->num_writes)
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: bad gate descriptor %u", g);
+            if (we) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_quotient_gates: gate %u reads witness columns", g);
+            const size_t last_rep = G.num_repetitions - 1;
+            if (last_rep * G.var_stride + ve > num_gp_vars || G.path_len + last_rep * G.const_stride + ce > num_constant_cols)
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: gate %u reads past the given columns", g);
+            int f[12] = {G.kind, (int)G.path_len, (int)G.num_repetitions, (int)G.var_stride, (int)G.const_stride, (int)G.num_terms,
+                         0, 0, 0, 0, 0, 0};
+            for (unsigned b = 0; b < G.path_len; b++) f[6 + b] = G.path[b] ? 1 : 0;
+            flat.insert(flat.end(), f, f + 12);
+            n_terms += (size_t)G.num_repetitions * G.num_terms;
+            continue;
+        }
+        if (G.kind == BJ_GATE_POSEIDON_FLATTENED) {   // the hand-written v1 evaluator: one repetition over the first 130 columns
+            if (G.path_len > 6 || G.num_terms != 118 || G.num_repetitions != 1 || num_gp_vars < 130 || G.path_len > num_constant_cols)
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: bad gate descriptor %u", g);
+            int f[12] = {G.kind, (int)G.path_len, 1, 130, 0, 118, 0, 0, 0, 0, 0, 0};
+            for (unsigned b = 0; b < G.path_len; b++) f[6 + b] = G.path[b] ? 1 : 0;
+            flat.insert(flat.end(), f, f + 12);
+            n_terms += 118;
+            continue;
+        }
         if (G.kind < BJ_GATE_CONSTANT_ALLOCATOR || G.kind > BJ_GATE_NOP)
-            return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_quotient_gates: gate %u: only the hand-written evaluators (kinds 1..4); op lists go "
-                                                     "through bj_gate_program_eval", g);
+            return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_quotient_gates: gate %u: kind %d is not evaluated here", g, G.kind);
         if (G.path_len > 6 || (G.kind != BJ_GATE_NOP && G.num_terms != 1))
             return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: bad gate descriptor %u", g);
         static const unsigned width[5] = {0, 1, 4, 5, 0};
@@ -130,13 +160,48 @@ int bj_quotient_gates(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, un
         n_terms += (size_t)G.num_repetitions * G.num_terms;
     }
     if (n_terms && !h_alphas) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: null alpha powers");
+    for (unsigned g = 0; g < num_gates; g++)
+        if (gates[g].kind == BJ_GATE_PROGRAM) {
+            programs[g].reset(new bj::DevProgram);
+            if (int rc = programs[g]->upload(ctx, gates[g].program)) {
+                for (auto &p : programs)
+                    if (p) p->release();
+                return rc;
+            }
+        }
     Tmp al(ctx);
     if (int rc = al.alloc(16 * (n_terms + 1))) return rc;
     if (n_terms)
         if (int rc = bj::h2d_async(ctx, al.p, h_alphas, 16 * n_terms)) return rc;
     bj::launch_quotient_gates(d_vars, var_stride, d_consts, const_stride, flat.data(), num_gates, (const u64 *)al.p, num_points,
                               d_out0, d_out1, ctx->stream);
-    BJ_CHECK_LAUNCH(ctx);
+    size_t aoff = 0;   // gates with a kernel of their own add their terms on top, with their slice of the alpha powers
+    for (unsigned g = 0; g < num_gates; g++) {
+        const int *f = flat.data() + 12 * g;
+        if (f[0] == BJ_GATE_POSEIDON_FLATTENED) {
+            unsigned char path[8] = {0};
+            for (int b = 0; b < f[1]; b++) path[b] = (unsigned char)f[6 + b];
+            bj::launch_quotient_poseidon_flattened(d_vars, var_stride, d_consts, const_stride, (unsigned)f[1], path,
+                                                   (const u64 *)al.p + 2 * aoff, num_points, d_out0, d_out1, ctx->stream);
+        }
+        if (f[0] == BJ_GATE_PROGRAM) {
+            unsigned char path[8] = {0};
+            for (int b = 0; b < f[1]; b++) path[b] = (unsigned char)f[6 + b];
+            bj::launch_gate_program(*programs[g], d_vars, var_stride, d_consts, const_stride, (unsigned)f[1], path, (unsigned)f[2],
+                                    (unsigned)f[3], (unsigned)f[4], (const u64 *)al.p + 2 * aoff, num_points, d_out0, d_out1, nullptr,
+                                    ctx->stream);
+        }
+        aoff += (size_t)f[2] * f[5];
+    }
+    const hipError_t e = hipGetLastError();
+    bool synced = false;
+    for (auto &p : programs)
+        if (p) {   // the programs' device copies live until their kernels are done
+            if (!synced) (void)hipStreamSynchronize(ctx->stream);
+            synced = true;
+            p->release();
+        }
+    if (e != hipSuccess) return bj::fail(ctx, BJ_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     return BJ_OK;
 }
 

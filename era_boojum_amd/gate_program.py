@@ -548,6 +548,102 @@ def evaluate_poseidon2_flattened(c, num_witness_columns_used=0):
         c.push(c.sub(dst, src))
 
 
+POSEIDON1_MDS_EXPS = [0, 0, 1, 0, 3, 5, 1, 8, 12, 3, 16, 10]                # poseidon_goldilocks.rs:30 (MDS_MATRIX_EXPS)
+
+
+def poseidon1_mds_matrix():
+    """MDS_MATRIX of Poseidon v1 (poseidon_goldilocks.rs:32-51): circulant, M[row][col] = 2^EXPS[(12 - row + col) mod 12]."""
+    return [[1 << POSEIDON1_MDS_EXPS[(12 - r + col) % 12] for col in range(12)] for r in range(12)]
+
+
+def poseidon1_fused_constants():
+    """The fused partial-round tables (ROUND_CONSTANTS_FUZED_LAST_FULL_AND_FIRST_PARTIAL [12], FUZED_DENSE_MATRIX_LAST_FULL_AND_
+    FIRST_PARTIAL [12][12], ROUND_CONSTANTS_FOR_FUZED_SBOXES [22], VS_FOR_PARTIAL_ROUNDS [22][11], W_HATS_FOR_PARTIAL_ROUNDS
+    [22][11]) from the generated data table csrc/poseidon1_fused.inc (tools/gen_poseidon1_fused_constants.py restates the
+    reference's derivation, poseidon_goldilocks.rs:620-1010)."""
+    import os
+    import re
+    txt = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "poseidon1_fused.inc")).read()
+
+    def table(name):
+        body = txt.split("#define %s {" % name)[1].split("}")[0]
+        return [int(x, 16) for x in re.findall(r"0x([0-9a-fA-F]+)ULL", body)]
+    rc, dense, sbox_rc, vs, w_hats = (table(n) for n in ("BJ_P1_FUSED_RC", "BJ_P1_FUSED_DENSE", "BJ_P1_FUSED_SBOX_RC",
+                                                        "BJ_P1_FUSED_VS", "BJ_P1_FUSED_W_HATS"))
+    assert (len(rc), len(dense), len(sbox_rc), len(vs), len(w_hats)) == (12, 144, 22, 242, 242)
+    return (rc, [dense[12 * r: 12 * r + 12] for r in range(12)], sbox_rc, [vs[11 * r: 11 * r + 11] for r in range(22)],
+            [w_hats[11 * r: 11 * r + 11] for r in range(22)])
+
+
+def evaluate_poseidon_flattened(c, num_witness_columns_used=0):
+    """PoseidonRoundFunctionFlattenedEvaluator<F, 8, 12, 4, PoseidonGoldilocks>, poseidon.rs:199-464: the v1 permutation in its
+    fused form (poseidon_goldilocks.rs:374-420) over 12 inputs, 12 outputs and a fresh cell ("degree reset") for every full
+    S-box input from the second full round on and for every partial S-box input — witness columns first while they last, then
+    copiable ones.  Linear layers as the reference records them: dense 12 x 12 products with the global constants (the MDS,
+    the fused dense matrix), 11 + 11 products per partial round (M'' as its `v` row and `w_hat` column).  130 cells, 118 terms."""
+    rc = poseidon2_round_constants()                        # all_round_constants(): the same 360-entry table
+    fused_rc, dense, sbox_rc, vs, w_hats = poseidon1_fused_constants()
+    mds_matrix = [[c.value(x) for x in row] for row in poseidon1_mds_matrix()]
+    dense_matrix = [[c.value(x) for x in row] for row in dense]
+    off = {"var": 24, "wit": 0}
+
+    def next_cell():
+        if off["wit"] < num_witness_columns_used:
+            off["wit"] += 1
+            return c.wit(off["wit"] - 1)
+        off["var"] += 1
+        return c.var(off["var"] - 1)
+
+    def matmul(matrix, old_state):
+        out = []
+        for i in range(12):
+            tmp = c.zero()
+            for src, coeff in zip(old_state, matrix[i]):
+                tmp = c.mul_and_accumulate_into(tmp, src, coeff)
+            out.append(tmp)
+        return out
+
+    def reset_degree(state):
+        for i in range(12):
+            cell = next_cell()
+            c.push(c.sub(state[i], cell))
+            state[i] = cell
+
+    state = [c.var(i) for i in range(12)]
+    output = [c.var(12 + i) for i in range(12)]
+    for rnd in range(3):                                    # HALF_NUM_FULL_ROUNDS - 1
+        if rnd != 0:
+            reset_degree(state)
+        for idx in range(12):
+            state[idx] = c.small_pow(c.add(state[idx], c.value(rc[rnd][idx])), 7)
+        state = matmul(mds_matrix, state)
+    reset_degree(state)                                     # still S-box (round 3)
+    for idx in range(12):
+        state[idx] = c.small_pow(c.add(state[idx], c.value(rc[3][idx])), 7)
+    for idx in range(12):                                   # last full round fused with the first partial one
+        state[idx] = c.add(state[idx], c.value(fused_rc[idx]))
+    state = matmul(dense_matrix, state)
+    for rnd in range(22):
+        cell = next_cell()
+        c.push(c.sub(state[0], cell))
+        tmp = c.small_pow(cell, 7)
+        state[0] = c.add(tmp, c.value(sbox_rc[rnd]))
+        original_s0 = state[0]
+        new_state0 = original_s0
+        for src, coeff in zip(state[1:], vs[rnd]):
+            new_state0 = c.mul_and_accumulate_into(new_state0, src, c.value(coeff))
+        state[0] = new_state0
+        for i in range(1, 12):
+            state[i] = c.mul_and_accumulate_into(state[i], original_s0, c.value(w_hats[rnd][i - 1]))
+    for k in range(4):                                      # round 26 + k; the constants of round 26 were propagated up
+        reset_degree(state)
+        for idx in range(12):
+            state[idx] = c.small_pow(c.add(state[idx], c.value(rc[26 + k][idx])) if k else state[idx], 7)
+        state = matmul(mds_matrix, state)
+    for src, dst in zip(state, output):
+        c.push(c.sub(dst, src))
+
+
 def _program(evaluate, *args, **kw):
     b = GateProgramBuilder()
     evaluate(b, *args, **kw)
@@ -634,6 +730,69 @@ def poseidon2_flattened_compact_program():
             state[i] = v
         state = [pow7(s + rc[26 + k][i]) for i, s in enumerate(state)]
         state = ext(state)
+    for s_, o in zip(state, output):
+        b.push(o - s_)
+    assert nxt == 130 and len(b.writes) == 118
+    return b.build()
+
+
+def poseidon_flattened_program(num_witness_columns_used=0):
+    """The reference's own capture of the Poseidon (v1) flattened gate: 3 980 recorded relations (3 457 operations on 34 slots in
+    canonical form, csrc/gate_aot.hip)."""
+    return _program(evaluate_poseidon_flattened, num_witness_columns_used)
+
+
+def poseidon_flattened_compact_program():
+    """The same 118 terms with the MDS rows as sums of shifted words (no 0 + x, no x * 1) and the partial rounds' M'' as one
+    row and one column: a restatement for checking the capture above and for the CPU oracle's column-wise evaluation."""
+    rc = poseidon2_round_constants()
+    fused_rc, dense, sbox_rc, vs, w_hats = poseidon1_fused_constants()
+    exps = POSEIDON1_MDS_EXPS
+    b = GateProgramBuilder()
+
+    def mds(st):
+        out = []
+        for r in range(12):
+            acc = None
+            for col in range(12):
+                e = exps[(12 - r + col) % 12]
+                t = st[col] if e == 0 else st[col] * (1 << e)
+                acc = t if acc is None else acc + t
+            out.append(acc)
+        return out
+
+    def pow7(x):
+        x2 = x.square()
+        return x2.square() * (x2 * x)
+
+    state = [b.var(i) for i in range(12)]
+    output = [b.var(12 + i) for i in range(12)]
+    nxt = 24
+    for rnd in range(4):
+        if rnd != 0:
+            for i in range(12):
+                v = b.var(nxt)
+                nxt += 1
+                b.push(state[i] - v)
+                state[i] = v
+        state = [pow7(s + rc[rnd][i]) for i, s in enumerate(state)]
+        if rnd != 3:
+            state = mds(state)
+    state = [s + fused_rc[i] for i, s in enumerate(state)]
+    state = [sum((state[k] * dense[r][k] for k in range(1, 12)), state[0] * dense[r][0]) for r in range(12)]
+    for rnd in range(22):
+        v = b.var(nxt)
+        nxt += 1
+        b.push(state[0] - v)
+        s0 = pow7(v) + sbox_rc[rnd]
+        state = [sum((state[k] * vs[rnd][k - 1] for k in range(1, 12)), s0)] + [state[k] + s0 * w_hats[rnd][k - 1] for k in range(1, 12)]
+    for k in range(4):
+        for i in range(12):
+            v = b.var(nxt)
+            nxt += 1
+            b.push(state[i] - v)
+            state[i] = v
+        state = mds([pow7(s + rc[26 + k][i]) if k else pow7(s) for i, s in enumerate(state)])
     for s_, o in zip(state, output):
         b.push(o - s_)
     assert nxt == 130 and len(b.writes) == 118

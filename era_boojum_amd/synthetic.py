@@ -20,11 +20,14 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import field_np as F
+from . import gate_program as GP
+from .gate_program import EvaluatorContext
 
 P = F.P
 
 GATE_CONSTANT_ALLOCATOR, GATE_FMA, GATE_REDUCTION4, GATE_NOP = 1, 2, 3, 4
 GATE_POSEIDON2_FLATTENED = 6   # the hand-written evaluator of Poseidon2FlattenedGate (csrc/gate_poseidon2.hip)
+GATE_POSEIDON_FLATTENED = 7    # the hand-written evaluator of PoseidonFlattenedGate, Poseidon v1 (csrc/gate_poseidon1.hip)
 GATE_PROGRAM = 5     # evaluated from an op list (seam S3): GateDesc.program is an era_boojum_amd.gate_program.GateProgram
 
 
@@ -41,7 +44,8 @@ class GateDesc:
     num_terms: int           # quotient terms per repetition
     needs_selector: bool
     path: list = field(default_factory=list)   # selector path, True = constant, False = 1 - constant
-    program: object = None   # op list for kind GATE_PROGRAM (and, optionally, for the hand-written kinds)
+    program: object = None   # op list for kind GATE_PROGRAM (and, optionally, for the hand-written kinds; GATE_POSEIDON_FLATTENED
+                             # carries one always, for the host-side checks: the prover still gets the hand-written kind)
     wit_stride: int = 0      # per_chunk_offset.witnesses_offset: non-copiable witness columns per repetition
     params: object = None    # the evaluator's own parameters (MatrixMultiplicationGate: the matrix)
 
@@ -96,13 +100,16 @@ def host_gates(num_gp_vars=60, num_constant_cols=4, matrix=None):
     return g[:3] + [mm] + g[3:]
 
 
-def recursion_gates(num_gp_vars=130, num_constant_cols=8, poseidon2_as_op_list=False):
+def recursion_gates(num_gp_vars=130, num_constant_cols=8, poseidon2_as_op_list=False, poseidon1=None):
     """The evaluators over general-purpose columns of the golden proof's inner circuit (a recursion-layer circuit: 130
     general-purpose columns, 8 x 3 lookup columns, one boolean specialized column = the 155 variable columns of vk.json), in
-    its evaluator order; everything but the SHA bench's four hand-written ones is an op list."""
+    its evaluator order; everything but the SHA bench's four hand-written ones is an op list.  poseidon1 puts the Poseidon (v1)
+    flattened gate (poseidon.rs:12-500) in the Poseidon2 gate's place: "kind" as BJ_GATE_POSEIDON_FLATTENED, "op_list" as the
+    reference's capture, or an int W > 0 — the capture with num_witness_columns_used = W (its first W S-box cells in witness
+    columns, 130 - W variables)."""
     from . import gate_program as GP
     v = num_gp_vars
-    return [
+    gates = [
         GateDesc(GATE_CONSTANT_ALLOCATOR, "ConstantsAllocatorGate", 1, num_constant_cols, 1, min(num_constant_cols, v), 1, 1, 1, True),
         GateDesc(GATE_PROGRAM, "U8x4FMAGate", 2, 0, 26, v // 26, 26, 0, 2, True, program=GP.u8x4_fma_program()),
         (GateDesc(GATE_PROGRAM, "Poseidon2FlattenedGate", 7, 0, 130, 1, 130, 0, 118, True, program=GP.poseidon2_flattened_program())
@@ -116,14 +123,28 @@ def recursion_gates(num_gp_vars=130, num_constant_cols=8, poseidon2_as_op_list=F
         GateDesc(GATE_REDUCTION4, "ReductionGate<4>", 2, 4, 5, v // 5, 5, 0, 1, True),
         GateDesc(GATE_NOP, "NopGate", 0, 0, 0, 1, 0, 0, 0, True),
     ]
+    if poseidon1 == "kind":
+        gates[2] = GateDesc(GATE_POSEIDON_FLATTENED, "PoseidonFlattenedGate", 7, 0, 130, 1, 130, 0, 118, True,
+                            program=GP.poseidon_flattened_compact_program())
+    elif poseidon1 == "op_list":
+        gates[2] = GateDesc(GATE_PROGRAM, "PoseidonFlattenedGate", 7, 0, 130, 1, 130, 0, 118, True, program=GP.poseidon_flattened_program())
+    elif poseidon1:
+        w = int(poseidon1)
+        gates[2] = GateDesc(GATE_PROGRAM, "PoseidonFlattenedGate[witness]", 7, 0, 130 - w, 1, 130 - w, 0, 118, True,
+                            program=GP.poseidon_flattened_program(w), wit_stride=w)
+    return gates
 
 
-def recursion_like_circuit(log_n, seed=1, table_bits=2, poseidon2_as_op_list=False):
+def recursion_like_circuit(log_n, seed=1, table_bits=2, poseidon2_as_op_list=False, poseidon1=None):
     """Random satisfiable circuit with the geometry and the gate set of the golden proof's inner circuit: 130 + 24 + 1
-    variable columns, width-3 lookups, the Poseidon2 flattened gate (118 terms over 130 variables per row), quotient degree 8."""
+    variable columns, width-3 lookups, the Poseidon2 flattened gate (118 terms over 130 variables per row), quotient degree 8.
+    poseidon1: the Poseidon (v1) flattened gate in its place (recursion_gates); with witness cells, as many witness columns."""
+    w = int(poseidon1) if poseidon1 not in (None, "kind", "op_list") else 0
     return sha_shaped_circuit(log_n, seed=seed, table_bits=table_bits, num_gp_vars=130, num_constant_cols=8, lookup_width=3,
-                              lookup_reps=8, num_public_inputs=2, boolean_columns=1, gates=recursion_gates(130, 8, poseidon2_as_op_list),
-                              mix=(0.04, 0.08, 0.12, 0.08, 0.08, 0.12, 0.08, 0.08, 0.08, 0.12), max_allowed_constraint_degree=8)
+                              lookup_reps=8, num_public_inputs=2, boolean_columns=1,
+                              gates=recursion_gates(130, 8, poseidon2_as_op_list, poseidon1),
+                              mix=(0.04, 0.08, 0.12, 0.08, 0.08, 0.12, 0.08, 0.08, 0.08, 0.12), max_allowed_constraint_degree=8,
+                              num_witness_cols=w)
 
 
 # ---- selector placement: restatement of TreeNode::try_add_gate / try_find_placement_for_degree (setup.rs:1346-1572) ----
@@ -473,6 +494,14 @@ def sha_shaped_circuit(log_n, seed=42, table_bits=4, mix=(0.05, 0.45, 0.35), num
             assert len(cells) == 130
             for k, col in enumerate(cells):
                 variables[k, rows] = col
+        elif g.name.startswith("PoseidonFlattenedGate"):    # one v1 permutation per row: the evaluator itself, run forward
+            from .gate_program import evaluate_poseidon_flattened
+            ctx = _CellFill([rand_f(m) for _ in range(12)], m)
+            evaluate_poseidon_flattened(ctx, g.wit_stride)
+            for k in range(g.principal_width):
+                variables[k, rows] = ctx.cells[("var", k)]
+            for k in range(g.wit_stride):
+                witness[k, rows] = ctx.cells[("wit", k)]
         elif g.kind == GATE_REDUCTION4:
             cs = [rand_f(m) for _ in range(4)]
             for i in range(4):
@@ -554,6 +583,35 @@ def sha_shaped_circuit(log_n, seed=42, table_bits=4, mix=(0.05, 0.45, 0.35), num
                    table_id_as_variable=table_id_as_variable)
 
 
+class _CellFill(EvaluatorContext):
+    """A recording context (gate_program.EvaluatorContext) that EVALUATES an evaluator over whole columns and fills its cells:
+    the inputs are given; every other variable / witness cell is unknown until the evaluator first subtracts it from a value
+    ("state - cell" at a degree reset, "output - state" at the end), and then takes that value — the assignment that zeroes the
+    term.  For the flattened Poseidon gates this is exactly the witness the reference's value function computes."""
+
+    def __init__(self, inputs, m):
+        self.m, self.cells = m, {("var", k): x for k, x in enumerate(inputs)}
+
+    def var(self, i): return self.cells.get(("var", i), ("var", i))
+    def wit(self, i): return self.cells.get(("wit", i), ("wit", i))
+    def value(self, x): return np.full(self.m, int(x) % P, dtype=np.uint64)
+    def push(self, v): assert not v.any(), "a term that no cell can zero"
+    def _emit(self, op, a, b=None):
+        a, b = (self.cells.get(x, x) if isinstance(x, tuple) else x for x in (a, b))      # cells bound since they were read
+        if isinstance(a, tuple):                       # output - state: the output cell is the state
+            self.cells[a] = b
+            return np.zeros(self.m, dtype=np.uint64)
+        if isinstance(b, tuple):                        # state - cell: the cell is the state
+            self.cells[b] = a
+            return np.zeros(self.m, dtype=np.uint64)
+        if op == GP.OP_ADD: return F.add(a, b)
+        if op == GP.OP_SUB: return F.sub(a, b)
+        if op == GP.OP_MUL: return F.mul(a, b)
+        if op == GP.OP_SQUARE: return F.mul(a, a)
+        if op == GP.OP_DOUBLE: return F.add(a, a)
+        raise NotImplementedError(op)
+
+
 def check_satisfied(c: Circuit):
     """Row-level satisfiability (the semantics of check_if_satisfied, satisfiability_test.rs:15): gate terms vanish on
     their rows, linked cells hold equal values, every lookup tuple is in its table, multiplicities are exact."""
@@ -581,7 +639,7 @@ def check_satisfied(c: Circuit):
         elif g.kind == GATE_CONSTANT_ALLOCATOR:
             for r in range(g.reps):
                 assert not F.sub(var[r * g.var_stride], consts[d + r * g.const_stride])[m].any(), "ConstAlloc unsatisfied"
-        elif g.kind in (GATE_PROGRAM, GATE_POSEIDON2_FLATTENED) and m.any():      # op-list gates: the program itself on the gate's rows
+        elif g.kind in (GATE_PROGRAM, GATE_POSEIDON2_FLATTENED, GATE_POSEIDON_FLATTENED) and m.any():      # op-list gates: the program itself on the gate's rows
             rows = np.flatnonzero(m)
             prog = g.program
             if prog is None:

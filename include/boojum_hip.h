@@ -47,6 +47,9 @@ typedef struct bj_ctx bj_ctx;
  * bj_proof_workspace_bytes, bj_setup_device_bytes; 6: bj_prove_async / bj_proof_wait, the tiled-monomial operators, bj_comm_peer_create (round 6) */
 #define BJ_ABI_VERSION 6
 int bj_abi_version(void);
+/* 1 if bj_setup_create accepts bj_gate_desc.kind == kind, else 0: gate kinds are added within an ABI version (no layout
+ * changes with them), so a host asks for the one it needs — BJ_GATE_POSEIDON_FLATTENED came within version 6. */
+int bj_gate_kind_supported(int kind);
 int bj_device_count(void);
 const char *bj_status_string(int status);
 
@@ -304,8 +307,10 @@ typedef enum bj_gate_kind {
     BJ_GATE_REDUCTION4 = 3,         /* sum_i c_i*v_i - r          src/cs/gates/reduction_gate.rs:103-126              */
     BJ_GATE_NOP = 4,                /* no terms                   src/cs/gates/nop_gate.rs:41                         */
     BJ_GATE_PROGRAM = 5,            /* any evaluator, given as the op list of seam S3 (bj_gate_program below)          */
-    BJ_GATE_POSEIDON2_FLATTENED = 6 /* Poseidon2FlattenedGate<8,12,4>, 130 variables, 118 terms, one repetition per row:
-                                     * src/cs/gates/poseidon2.rs:165-410 (the gate of the recursion circuits), hand-written */
+    BJ_GATE_POSEIDON2_FLATTENED = 6, /* Poseidon2FlattenedGate<8,12,4>, 130 variables, 118 terms, one repetition per row:
+                                      * src/cs/gates/poseidon2.rs:165-410 (the gate of the recursion circuits), hand-written */
+    BJ_GATE_POSEIDON_FLATTENED = 7  /* PoseidonFlattenedGate<8,12,4> (Poseidon v1), 130 variables, 118 terms, one repetition per
+                                      * row, no witness columns: src/cs/gates/poseidon.rs:199-464, hand-written */
 } bj_gate_kind;
 
 /* Seam S3 — a gate as the reference's gpu_synthesizer describes it (GPUDataCapture::from_evaluator,
@@ -415,8 +420,9 @@ int bj_lookup_polys(bj_ctx *ctx, const uint64_t *d_lookup_vars, size_t var_strid
                     unsigned log_n, const uint64_t *h_beta, const uint64_t *h_gamma, uint64_t *d_A, uint64_t *d_B);
 /* Gate terms of the quotient numerator at num_points LDE points (prover.rs:1031-1080 with buffering_source.rs:133-362 and
  * the selectors of prover.rs:2775-2916): out = sum_g selector_g * sum_t alpha_t * term_t for the hand-written evaluators
- * (kinds 1..4; op lists are evaluated by bj_gate_program_eval).  h_alphas: one F_p^2 power per (gate, repetition, term) in
- * evaluator order.  OVERWRITES d_out0 / d_out1. */
+ * (kinds 1..4, and BJ_GATE_POSEIDON_FLATTENED over the first 130 columns) and for op lists without witness columns
+ * (BJ_GATE_PROGRAM: the kernel bj_prove would launch for it — generated, hand-written by fingerprint, run-time compiled or
+ * interpreted).  h_alphas: one F_p^2 power per (gate, repetition, term) in evaluator order.  OVERWRITES d_out0 / d_out1. */
 int bj_quotient_gates(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, unsigned num_gp_vars, const uint64_t *d_consts,
                       size_t const_stride, unsigned num_constant_cols, const bj_gate_desc *gates, unsigned num_gates,
                       const uint64_t *h_alphas, size_t num_points, uint64_t *d_out0, uint64_t *d_out1);

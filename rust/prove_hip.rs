@@ -174,8 +174,21 @@ fn builtin_kind(debug_name: &str) -> Option<i32> {
         Some(BJ_GATE_REDUCTION4)
     } else if debug_name.contains("Poseidon2FlattenedGate") || debug_name.contains("Poseidon2RoundFunctionFlattenedEvaluator") {
         Some(BJ_GATE_POSEIDON2_FLATTENED)
+    } else if debug_name.contains("PoseidonFlattenedGate") || debug_name.contains("PoseidonRoundFunctionFlattenedEvaluator") {
+        Some(BJ_GATE_POSEIDON_FLATTENED)
     } else {
         None
+    }
+}
+
+/// The flattened Poseidon kernels evaluate one repetition per row over 130 variable columns and no witness columns: the shape
+/// `compute_strategy` (poseidon.rs:565-585, poseidon2.rs) gives when the geometry has no witness columns and room for one
+/// instance.  Any other placement (witness cells, two instances on a row) goes through the captured op list.
+fn builtin_kind_fits(kind: i32, d: &bj_gate_desc) -> bool {
+    if kind == BJ_GATE_POSEIDON2_FLATTENED || kind == BJ_GATE_POSEIDON_FLATTENED {
+        d.num_repetitions == 1 && d.wit_stride == 0 && d.var_stride == 130
+    } else {
+        true
     }
 }
 
@@ -267,8 +280,8 @@ impl<P: crate::field::traits::field_like::PrimeFieldLikeVectorized<Base = F>, CF
                     d.num_terms = 0;
                 }
                 _ => match builtin_kind(&ev.debug_name) {
-                    Some(k) => d.kind = k,
-                    None => {
+                    Some(k) if builtin_kind_fits(k, &d) => d.kind = k,
+                    _ => {
                         let capture = gates_for_gpu
                             .descriptions
                             .iter()
