@@ -7,9 +7,11 @@
 // elements, i.e. 8 coalesced column loads.  Pure 32-bit add/xor/rotate (v_alignbit) work: ~1.3 k VALU instructions per
 // 64-byte block against ~14 k for one Poseidon2 permutation over the same 8 elements.
 // Digests are stored as four little-endian u64 words = the 32 digest bytes in memory order (never canonicalised).
+// Where a lane finds its words, the launch helper and the entry this file contributes to the hasher dispatch of tree_hash.hip
+// (which also walks the node layers): tree_plan.h.  The block loops (8 words + the byte counter t) are this file's own.
 #include "gl.h"
 #include "kernels.h"
-#include "../../include/boojum_hip.h"
+#include "tree_plan.h"
 
 using gl::u64;
 using gl::u32;
@@ -92,11 +94,7 @@ blake2s_leaves_kernel(const u64 *base, size_t col_stride, const u64 *const *col_
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const unsigned c = b * 8 + k;
-            u64 v = 0;
-            if (c < n_cols) {
-                const u64 *p = col_ptrs ? col_ptrs[c] : base + (size_t)c * col_stride;
-                v = gl::canon(p[I]);
-            }
+            const u64 v = c < n_cols ? gl::canon(leaf_word(base, col_stride, col_ptrs, c, I)) : 0;
             m[2 * k] = gl::lo32(v);
             m[2 * k + 1] = gl::hi32(v);
         }
@@ -122,11 +120,7 @@ blake2s_leaves_chunked_kernel(const u64 *src0, const u64 *src1, unsigned n_srcs,
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const unsigned e = b * 8 + k;
-            u64 v = 0;
-            if (e < total) {
-                const u64 *p = (e >> log_e) == 0 ? src0 : src1;
-                v = gl::canon(p[j * E + (e & (E - 1))]);
-            }
+            const u64 v = e < total ? gl::canon(chunk_word(src0, src1, log_e, E, j, e)) : 0;
             m[2 * k] = gl::lo32(v);
             m[2 * k + 1] = gl::hi32(v);
         }
@@ -188,71 +182,22 @@ void launch_blake2s_pow(const u64 *seed5, unsigned pow_bits, u64 base, u64 count
         ps.w[2 * k] = gl::lo32(seed5[k]);
         ps.w[2 * k + 1] = gl::hi32(seed5[k]);
     }
-    hipLaunchKernelGGL(blake2s_pow_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, ps, pow_bits, base, count,
-                       (unsigned long long *)d_result);
+    launch_1d(blake2s_pow_kernel, count, s, ps, pow_bits, base, count, (unsigned long long *)d_result);
 }
 
-void launch_blake2s_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
-                           size_t num_leaves, u64 *d_digests, hipStream_t s) {
-    hipLaunchKernelGGL(blake2s_leaves_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, s, d_base, col_stride,
-                       d_col_ptrs, n_cols, num_leaves, d_digests);
+static void launch_blake2s_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
+                                  size_t num_leaves, u64 *d_digests, hipStream_t s) {
+    launch_1d(blake2s_leaves_kernel, num_leaves, s, d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests);
 }
-void launch_blake2s_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
-                                   u64 *d_digests, hipStream_t s) {
-    hipLaunchKernelGGL(blake2s_leaves_chunked_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, s, d_src0,
-                       d_src1, n_srcs, log_e, num_leaves, d_digests);
+static void launch_blake2s_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
+                                          u64 *d_digests, hipStream_t s) {
+    launch_1d(blake2s_leaves_chunked_kernel, num_leaves, s, d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests);
 }
-void launch_blake2s_node_layers(u64 *d_tree, size_t num_leaves, size_t cap_size, hipStream_t s) {
-    u64 *prev = d_tree;
-    size_t len = num_leaves;
-    while (len > cap_size) {
-        u64 *next = prev + 4 * len;
-        const size_t nl = len / 2;
-        hipLaunchKernelGGL(blake2s_nodes_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, prev, next, nl);
-        prev = next;
-        len = nl;
-    }
+static void launch_blake2s_nodes(const u64 *d_children, u64 *d_parents, size_t num_parents, hipStream_t s) {
+    launch_1d(blake2s_nodes_kernel, num_parents, s, d_children, d_parents, num_parents);
 }
-
-// hasher-dispatching entry points used by the C ABI and the prover (tree layout is the same for both hashers)
-void launch_tree_leaves(int hasher, const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
-                        size_t num_leaves, u64 *d_digests, hipStream_t s) {
-    if (hasher == BJ_HASHER_BLAKE2S)
-        launch_blake2s_leaves(d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests, s);
-    else if (hasher == BJ_HASHER_KECCAK256)
-        launch_keccak_leaves(d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests, s);
-    else if (hasher == BJ_HASHER_POSEIDON)
-        launch_poseidon1_leaves(d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests, s);
-    else
-        launch_poseidon2_leaves(d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests, s);
-}
-void launch_tree_leaves_chunked(int hasher, const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e,
-                                size_t num_leaves, u64 *d_digests, hipStream_t s) {
-    if (hasher == BJ_HASHER_BLAKE2S)
-        launch_blake2s_leaves_chunked(d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests, s);
-    else if (hasher == BJ_HASHER_KECCAK256)
-        launch_keccak_leaves_chunked(d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests, s);
-    else if (hasher == BJ_HASHER_POSEIDON)
-        launch_poseidon1_leaves_chunked(d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests, s);
-    else
-        launch_poseidon2_leaves_chunked(d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests, s);
-}
-void launch_tree_node_layers(int hasher, u64 *d_tree, size_t num_leaves, size_t cap_size, hipStream_t s) {
-    if (hasher == BJ_HASHER_BLAKE2S)
-        launch_blake2s_node_layers(d_tree, num_leaves, cap_size, s);
-    else if (hasher == BJ_HASHER_KECCAK256)
-        launch_keccak_node_layers(d_tree, num_leaves, cap_size, s);
-    else if (hasher == BJ_HASHER_POSEIDON)
-        launch_poseidon1_node_layers(d_tree, num_leaves, cap_size, s);
-    else
-        launch_poseidon2_node_layers(d_tree, num_leaves, cap_size, s);
-}
-void launch_tree_leaves_absorb(int hasher, const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves,
-                               u64 *d_capacity, u64 *d_digests, bool first, bool last, hipStream_t s) {
-    if (hasher == BJ_HASHER_POSEIDON)
-        launch_poseidon1_leaves_absorb(d_base, col_stride, n_cols, num_leaves, d_capacity, d_digests, first, last, s);
-    else
-        launch_poseidon2_leaves_absorb(d_base, col_stride, n_cols, num_leaves, d_capacity, d_digests, first, last, s);
+TreeHasher blake2s_tree_hasher() {
+    return {launch_blake2s_leaves, launch_blake2s_leaves_chunked, launch_blake2s_nodes, nullptr};
 }
 
 }  // namespace bj

@@ -3,9 +3,11 @@
 //   leaf = Keccak256( le64(canonical(e_0)) || le64(canonical(e_1)) || ... ),   node = Keccak256( left[32] || right[32] )
 // lane = leaf / node; the 25-lane state lives in VGPRs (50 registers); a rate block is 17 field elements = 17 state lanes,
 // so absorbing is 17 coalesced column loads XORed straight into the state.  Digests: state lanes 0..3 (little endian).
+// Where a lane finds its words, the launch helper and the entry this file contributes to the hasher dispatch of tree_hash.hip
+// (which also walks the node layers): tree_plan.h.  The block loops (17 words + pad10*1) are this file's own.
 #include "gl.h"
 #include "kernels.h"
-#include "../../include/boojum_hip.h"
+#include "tree_plan.h"
 
 using gl::u64;
 using gl::u32;
@@ -87,8 +89,7 @@ keccak_leaves_kernel(const u64 *base, size_t col_stride, const u64 *const *col_p
     for (; c + 17 <= n_cols; c += 17) {   // full rate blocks
 #pragma unroll
         for (int k = 0; k < 17; k++) {
-            const u64 *p = col_ptrs ? col_ptrs[c + k] : base + (size_t)(c + k) * col_stride;
-            st.a[k] ^= gl::canon(p[I]);
+            st.a[k] ^= gl::canon(leaf_word(base, col_stride, col_ptrs, c + k, I));
         }
         keccak_f(st.a);
     }
@@ -96,8 +97,7 @@ keccak_leaves_kernel(const u64 *base, size_t col_stride, const u64 *const *col_p
 #pragma unroll
     for (int k = 0; k < 16; k++) {
         if ((unsigned)k < rem) {
-            const u64 *p = col_ptrs ? col_ptrs[c + k] : base + (size_t)(c + k) * col_stride;
-            st.a[k] ^= gl::canon(p[I]);
+            st.a[k] ^= gl::canon(leaf_word(base, col_stride, col_ptrs, c + k, I));
         }
     }
     st.pad_and_permute(rem);
@@ -116,9 +116,7 @@ keccak_leaves_chunked_kernel(const u64 *src0, const u64 *src1, unsigned n_srcs, 
     for (; e0 + 17 <= total; e0 += 17) {
 #pragma unroll
         for (int k = 0; k < 17; k++) {
-            const unsigned e = e0 + k;
-            const u64 *p = (e >> log_e) == 0 ? src0 : src1;
-            st.a[k] ^= gl::canon(p[j * E + (e & (E - 1))]);
+            st.a[k] ^= gl::canon(chunk_word(src0, src1, log_e, E, j, e0 + k));
         }
         keccak_f(st.a);
     }
@@ -126,9 +124,7 @@ keccak_leaves_chunked_kernel(const u64 *src0, const u64 *src1, unsigned n_srcs, 
 #pragma unroll
     for (int k = 0; k < 16; k++) {
         if ((unsigned)k < rem) {
-            const unsigned e = e0 + k;
-            const u64 *p = (e >> log_e) == 0 ? src0 : src1;
-            st.a[k] ^= gl::canon(p[j * E + (e & (E - 1))]);
+            st.a[k] ^= gl::canon(chunk_word(src0, src1, log_e, E, j, e0 + k));
         }
     }
     st.pad_and_permute(rem);
@@ -177,30 +173,22 @@ __global__ void __launch_bounds__(256) keccak_pow_kernel(KeccakPowSeed seed, uns
 void launch_keccak_pow(const u64 *seed5, unsigned pow_bits, u64 base, u64 count, u64 *d_result, hipStream_t s) {
     KeccakPowSeed ps;
     for (int k = 0; k < 5; k++) ps.w[k] = seed5[k];
-    hipLaunchKernelGGL(keccak_pow_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, ps, pow_bits, base, count,
-                       (unsigned long long *)d_result);
+    launch_1d(keccak_pow_kernel, count, s, ps, pow_bits, base, count, (unsigned long long *)d_result);
 }
 
-void launch_keccak_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
-                          size_t num_leaves, u64 *d_digests, hipStream_t s) {
-    hipLaunchKernelGGL(keccak_leaves_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, s, d_base, col_stride,
-                       d_col_ptrs, n_cols, num_leaves, d_digests);
+static void launch_keccak_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
+                                 size_t num_leaves, u64 *d_digests, hipStream_t s) {
+    launch_1d(keccak_leaves_kernel, num_leaves, s, d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests);
 }
-void launch_keccak_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
-                                  u64 *d_digests, hipStream_t s) {
-    hipLaunchKernelGGL(keccak_leaves_chunked_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, s, d_src0,
-                       d_src1, n_srcs, log_e, num_leaves, d_digests);
+static void launch_keccak_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
+                                         u64 *d_digests, hipStream_t s) {
+    launch_1d(keccak_leaves_chunked_kernel, num_leaves, s, d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests);
 }
-void launch_keccak_node_layers(u64 *d_tree, size_t num_leaves, size_t cap_size, hipStream_t s) {
-    u64 *prev = d_tree;
-    size_t len = num_leaves;
-    while (len > cap_size) {
-        u64 *next = prev + 4 * len;
-        const size_t nl = len / 2;
-        hipLaunchKernelGGL(keccak_nodes_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, prev, next, nl);
-        prev = next;
-        len = nl;
-    }
+static void launch_keccak_nodes(const u64 *d_children, u64 *d_parents, size_t num_parents, hipStream_t s) {
+    launch_1d(keccak_nodes_kernel, num_parents, s, d_children, d_parents, num_parents);
+}
+TreeHasher keccak_tree_hasher() {
+    return {launch_keccak_leaves, launch_keccak_leaves_chunked, launch_keccak_nodes, nullptr};
 }
 
 }  // namespace bj

@@ -71,40 +71,20 @@ void launch_ntt_strided4(const u64 *in, u64 *out, const u64 *tw, const u64 *roun
                          unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride,
                          size_t out_col_stride, hipStream_t s);
 
-// poseidon2.hip
-void launch_poseidon2_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
-                             size_t num_leaves, u64 *d_digests, hipStream_t s);
-// one absorption of up to eight columns per leaf; d_capacity [4][num_leaves] carries the sponge between the groups
-void launch_poseidon2_leaves_absorb(const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *d_capacity,
-                                    u64 *d_digests, bool first, bool last, hipStream_t s);
-void launch_poseidon2_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e,
-                                     size_t num_leaves, u64 *d_digests, hipStream_t s);
-void launch_poseidon2_node_layers(u64 *d_tree, size_t num_leaves, size_t cap_size, hipStream_t s);
-void launch_poseidon2_permute_states(u64 *d_states, size_t n_states, hipStream_t s);
-// poseidon1.hip: the same entry points for the Poseidon (v1) sponge (BJ_HASHER_POSEIDON)
-void launch_poseidon1_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
-                             size_t num_leaves, u64 *d_digests, hipStream_t s);
-void launch_poseidon1_leaves_absorb(const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *d_capacity,
-                                    u64 *d_digests, bool first, bool last, hipStream_t s);
-void launch_poseidon1_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e,
-                                     size_t num_leaves, u64 *d_digests, hipStream_t s);
-void launch_poseidon1_node_layers(u64 *d_tree, size_t num_leaves, size_t cap_size, hipStream_t s);
-void launch_poseidon1_permute_states(u64 *d_states, size_t n_states, hipStream_t s);
-// blake2s.hip: the same tree with Blake2s-256 digests, and the hasher-dispatching entry points (hasher = BJ_HASHER_*)
+// tree_hash.hip: the Merkle-tree entry points, dispatched on hasher = BJ_HASHER_* (what each hasher contributes: tree_plan.h)
 void launch_tree_leaves(int hasher, const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
                         size_t num_leaves, u64 *d_digests, hipStream_t s);
 void launch_tree_leaves_chunked(int hasher, const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e,
                                 size_t num_leaves, u64 *d_digests, hipStream_t s);
 void launch_tree_node_layers(int hasher, u64 *d_tree, size_t num_leaves, size_t cap_size, hipStream_t s);
-// group-wise absorption (launch_poseidon2_leaves_absorb) for the algebraic hashers, BJ_HASHER_POSEIDON2 / BJ_HASHER_POSEIDON
+// group-wise absorption for the algebraic hashers, BJ_HASHER_POSEIDON2 / BJ_HASHER_POSEIDON: one absorption run of a group of
+// columns per leaf; d_capacity [4][num_leaves] carries the sponge between the groups
 void launch_tree_leaves_absorb(int hasher, const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves,
                                u64 *d_capacity, u64 *d_digests, bool first, bool last, hipStream_t s);
-// keccak.hip
-void launch_keccak_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
-                          size_t num_leaves, u64 *d_digests, hipStream_t s);
-void launch_keccak_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
-                                  u64 *d_digests, hipStream_t s);
-void launch_keccak_node_layers(u64 *d_tree, size_t num_leaves, size_t cap_size, hipStream_t s);
+// poseidon2.hip, poseidon1.hip: the bare permutation on n_states 12-word states
+void launch_poseidon2_permute_states(u64 *d_states, size_t n_states, hipStream_t s);
+void launch_poseidon1_permute_states(u64 *d_states, size_t n_states, hipStream_t s);
+// keccak.hip, blake2s.hip
 void launch_keccak_pow(const u64 *seed5, unsigned pow_bits, u64 base, u64 count, u64 *d_result, hipStream_t s);
 // Blake2s proof of work over nonces [base, base + count): atomicMin of the valid ones into *d_result (pre-set to ~0)
 void launch_blake2s_pow(const u64 *seed5, unsigned pow_bits, u64 base, u64 count, u64 *d_result, hipStream_t s);

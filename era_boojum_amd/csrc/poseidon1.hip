@@ -5,18 +5,18 @@
 //   permutation        src/implementations/poseidon_goldilocks_naive.rs:67-165
 //                      every round: + its 12 constants (the 360-entry table Poseidon2 uses), x^7 on all 12 words (rounds
 //                      0-3, 26-29) or on word 0 (rounds 4-25), then the circulant MDS M[row][col] = 2^EXPS[(col - row) mod 12]
-//   sponge             src/algebraic_props/sponge.rs:345-357 + 224-346   overwrite absorption, zero-padded tail, no length tag
-//   leaf / node hash   src/cs/oracle/mod.rs:114-176                      node = perm(L || R || 0)[0..4]
-//   tree               src/cs/oracle/merkle_tree.rs (the same layouts as poseidon2.hip)
+//   sponge             src/algebraic_props/sponge.rs:345-357             the Poseidon2 sponge around this permutation
 //
-// Mapping: as poseidon2.hip — one lane = one leaf (or one parent node), the 12-word sponge state in VGPRs, coalesced
-// column loads, wave-uniform round constants through the scalar cache.
+// The sponge, the leaf / node hashes, the tree layouts and the mapping (one lane = one leaf or one parent node, the state in
+// VGPRs) are the plan of sponge_tree.h, shared with poseidon2.hip; the fetches, the launch helper and the entry this file
+// contributes to the hasher dispatch of tree_hash.hip are in tree_plan.h.  Here: the arithmetic, the permutation, the entry points.
 // Arithmetic is lazy as in poseidon2.hip: state words are weak residues (any u64 congruent to the value) between rounds;
 // the MDS layer's entries are powers of two: the low and the high 32-bit halves of the state are accumulated apart, one
 // multiply-add by 2^e per term (no reduction inside the sum), and folded once per output word.
 #include "gl.h"
 #include "kernels.h"
 #include "poseidon_rc.inc"
+#include "sponge_tree.h"
 
 using gl::u64;
 using gl::u32;
@@ -97,140 +97,58 @@ __device__ __forceinline__ void poseidon1_permutation(u64 (&s)[12]) {
     for (int i = 0; i < 4; i++, r++) p1_full_round(s, r);
 }
 
-__device__ __forceinline__ void p1_store_digest(u64 *digests, size_t i, const u64 (&s)[12]) {
-    ulonglong2 *d = reinterpret_cast<ulonglong2 *>(digests + 4 * i);
-    d[0] = make_ulonglong2(gl::canon(s[0]), gl::canon(s[1]));
-    d[1] = make_ulonglong2(gl::canon(s[2]), gl::canon(s[3]));
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// leaf hashing: leaf I = sponge(cols[0][I], cols[1][I], ...), columns as base + c * stride or through a device array of
-// column pointers.  One call site of the permutation (instruction-cache footprint); the zero-padded tail by wave-uniform
-// conditions.
-// ---------------------------------------------------------------------------------------------------------
+// the plan of sponge_tree.h around this permutation (the chunked leaves keep their loop here, as in poseidon2.hip)
 __global__ void __launch_bounds__(256)
 poseidon1_leaves_kernel(const u64 *base, size_t col_stride, const u64 *const *col_ptrs, unsigned n_cols, size_t num_leaves,
                         u64 *digests) {
-    const size_t I = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= num_leaves) return;
-    u64 s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = 0;
-    for (unsigned c = 0; c < n_cols; c += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            if (c + k < n_cols) {
-                const u64 *p = col_ptrs ? col_ptrs[c + k] : base + (size_t)(c + k) * col_stride;
-                s[k] = p[I];
-            } else {
-                s[k] = 0;
-            }
-        }
-        poseidon1_permutation(s);
-    }
-    p1_store_digest(digests, I, s);
+    sponge_leaves<poseidon1_permutation>(base, col_stride, col_ptrs, n_cols, num_leaves, digests);
 }
-
-// a run of absorptions of the same sponge for columns that arrive in groups (bj_prove's group-wise witness plan): state[8..12]
-// <- what the previous group left in `capacity` ([4][num_leaves], zeros before the first group); every group but the last
-// holds a multiple of eight columns; the last writes the digest, the others their capacity words (poseidon2.hip: same plan)
 __global__ void __launch_bounds__(256)
 poseidon1_leaves_absorb_kernel(const u64 *base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *capacity, u64 *digests,
                                int first, int last) {
-    const size_t I = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= num_leaves) return;
-    u64 s[12];
-#pragma unroll
-    for (int k = 0; k < 4; k++) s[8 + k] = first ? 0 : capacity[(size_t)k * num_leaves + I];
-    for (unsigned c = 0; c < n_cols; c += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) s[k] = c + k < n_cols ? base[(size_t)(c + k) * col_stride + I] : 0;
-        poseidon1_permutation(s);
-    }
-    if (last) {
-        p1_store_digest(digests, I, s);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) capacity[(size_t)k * num_leaves + I] = s[8 + k];
-    }
+    sponge_leaves_absorb<poseidon1_permutation>(base, col_stride, n_cols, num_leaves, capacity, digests, first, last);
 }
-
-// leaf j = sponge( src0[jE..(j+1)E) || src1[jE..(j+1)E) )                  (FRI oracles, merkle_tree.rs:176-386)
 __global__ void __launch_bounds__(256)
 poseidon1_leaves_chunked_kernel(const u64 *src0, const u64 *src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
                                 u64 *digests) {
     const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= num_leaves) return;
-    const unsigned E = 1u << log_e;
-    const unsigned total = n_srcs * E;
+    const unsigned E = 1u << log_e, total = n_srcs * E;
     u64 s[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) s[k] = 0;
     for (unsigned t = 0; t < total; t += 8) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const unsigned idx = t + k;   // wave-uniform
-            u64 v = 0;
-            if (idx < total) {
-                const u64 *p = (idx >> log_e) == 0 ? src0 : src1;
-                v = p[j * E + (idx & (E - 1))];
-            }
-            s[k] = v;
-        }
+        for (int k = 0; k < 8; k++) s[k] = t + k < total ? chunk_word(src0, src1, log_e, E, j, t + k) : 0;   // t + k is wave-uniform
         poseidon1_permutation(s);
     }
-    p1_store_digest(digests, j, s);
+    sponge_store_digest(digests, j, s);
 }
-
-// node layer: parent i = perm(left || right || 0000)[0..4]                 (oracle/mod.rs:162-168)
 __global__ void __launch_bounds__(256) poseidon1_nodes_kernel(const u64 *children, u64 *parents, size_t num_parents) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= num_parents) return;
-    const ulonglong2 *c = reinterpret_cast<const ulonglong2 *>(children + 8 * i);
-    const ulonglong2 a = c[0], b = c[1], e = c[2], f = c[3];
-    u64 s[12] = {a.x, a.y, b.x, b.y, e.x, e.y, f.x, f.y, 0, 0, 0, 0};
-    poseidon1_permutation(s);
-    p1_store_digest(parents, i, s);
+    sponge_nodes<poseidon1_permutation>(children, parents, num_parents);
+}
+__global__ void poseidon1_permute_states_kernel(u64 *states, size_t n_states) { sponge_permute_states<poseidon1_permutation>(states, n_states); }
+
+static void launch_poseidon1_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
+                                    size_t num_leaves, u64 *d_digests, hipStream_t s) {
+    launch_1d(poseidon1_leaves_kernel, num_leaves, s, d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests);
+}
+static void launch_poseidon1_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
+                                            u64 *d_digests, hipStream_t s) {
+    launch_1d(poseidon1_leaves_chunked_kernel, num_leaves, s, d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests);
+}
+static void launch_poseidon1_nodes(const u64 *d_children, u64 *d_parents, size_t num_parents, hipStream_t s) {
+    launch_1d(poseidon1_nodes_kernel, num_parents, s, d_children, d_parents, num_parents);
+}
+static void launch_poseidon1_leaves_absorb(const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *d_capacity,
+                                           u64 *d_digests, bool first, bool last, hipStream_t s) {
+    launch_1d(poseidon1_leaves_absorb_kernel, num_leaves, s, d_base, col_stride, n_cols, num_leaves, d_capacity, d_digests,
+              first, last);
+}
+TreeHasher poseidon1_tree_hasher() {
+    return {launch_poseidon1_leaves, launch_poseidon1_leaves_chunked, launch_poseidon1_nodes, launch_poseidon1_leaves_absorb};
 }
 
-__global__ void poseidon1_permute_states_kernel(u64 *states, size_t n_states) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_states) return;
-    u64 s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = states[12 * i + k];
-    poseidon1_permutation(s);
-#pragma unroll
-    for (int k = 0; k < 12; k++) states[12 * i + k] = gl::canon(s[k]);
-}
-
-void launch_poseidon1_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
-                             size_t num_leaves, u64 *d_digests, hipStream_t s) {
-    hipLaunchKernelGGL(poseidon1_leaves_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, s, d_base, col_stride,
-                       d_col_ptrs, n_cols, num_leaves, d_digests);
-}
-void launch_poseidon1_leaves_absorb(const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *d_capacity,
-                                    u64 *d_digests, bool first, bool last, hipStream_t s) {
-    hipLaunchKernelGGL(poseidon1_leaves_absorb_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, s, d_base,
-                       col_stride, n_cols, num_leaves, d_capacity, d_digests, first ? 1 : 0, last ? 1 : 0);
-}
-void launch_poseidon1_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
-                                     u64 *d_digests, hipStream_t s) {
-    hipLaunchKernelGGL(poseidon1_leaves_chunked_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, s, d_src0,
-                       d_src1, n_srcs, log_e, num_leaves, d_digests);
-}
-// tree layout: layer 0 = num_leaves digests, then num_leaves/2, ... down to cap_size (inclusive), back to back
-void launch_poseidon1_node_layers(u64 *d_tree, size_t num_leaves, size_t cap_size, hipStream_t s) {
-    u64 *prev = d_tree;
-    size_t len = num_leaves;
-    while (len > cap_size) {
-        u64 *next = prev + 4 * len;
-        const size_t nl = len / 2;
-        hipLaunchKernelGGL(poseidon1_nodes_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, prev, next, nl);
-        prev = next;
-        len = nl;
-    }
-}
 void launch_poseidon1_permute_states(u64 *d_states, size_t n_states, hipStream_t s) {
     hipLaunchKernelGGL(poseidon1_permute_states_kernel, dim3((unsigned)((n_states + 63) / 64)), dim3(64), 0, s, d_states, n_states);
 }

@@ -4,18 +4,15 @@
 //   permutation        src/implementations/poseidon2/state_generic_impl.rs:128-233
 //   external matrix    src/implementations/suggested_mds.rs:21-103      circ(2*M4, M4, M4)
 //   internal matrix    src/implementations/poseidon2/params.rs:38-39    1 + diag(2^{4,14,11,8,0,5,2,9,13,6,3,12})
-//   sponge             src/algebraic_props/sponge.rs:224-346            overwrite absorption, zero-padded tail, no length tag
-//   leaf / node hash   src/cs/oracle/mod.rs:114-176
-//   tree               src/cs/oracle/merkle_tree.rs:78-174 (construct), 176-386 (chunked), 388-449 (node layers)
-//
-// Mapping: one lane = one leaf (or one parent node).  The 12-word sponge state lives in VGPRs for the whole leaf;
-// for leaf I the lane reads element I of every column, so a wavefront reads 64 consecutive u64 of one column per
-// load (512 B, coalesced).  Round constants are wave-uniform and come through the scalar cache.
+// The sponge, the leaf / node hashes and the mapping (one lane = one leaf or one parent node, the state in VGPRs) are the
+// plan of sponge_tree.h, which poseidon1.hip shares; the fetches, the launch helper and the entry this file contributes to the
+// hasher dispatch of tree_hash.hip are in tree_plan.h.  Here: the arithmetic, the permutation, the kernels' entry points, and
+// the two lane-parallel kernels for small layers, which follow a plan of their own.
 // The work is integer-ALU bound (~472 field multiplications per 64 absorbed bytes), not HBM bound.
 #include "gl.h"
 #include "kernels.h"
 #include "poseidon_rc.inc"
-#include <cstdlib>
+#include "sponge_tree.h"
 
 using gl::u64;
 using gl::u32;
@@ -244,107 +241,36 @@ __device__ __forceinline__ void poseidon2_permutation(u64 (&s)[12]) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// leaf hashing: leaf I = sponge(cols[0][I], cols[1][I], ...)             (merkle_tree.rs:78-174)
-// cols given either as base + c*stride or through a device array of column pointers.
-// ---------------------------------------------------------------------------------------------------------
+// the plan of sponge_tree.h around this permutation.  The chunked leaves keep their loop here: wrapped in a function template
+// it compiles to a different instruction order (the body is optimised once on its own and again inside the kernel)
 __global__ void __launch_bounds__(256)
 poseidon2_leaves_kernel(const u64 *base, size_t col_stride, const u64 *const *col_ptrs, unsigned n_cols,
                         size_t num_leaves, u64 *digests) {
-    size_t I = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= num_leaves) return;
-    u64 s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = 0;
-    // ONE call site of the permutation: with a second copy for the zero-padded tail block the kernel is 72 KB of code,
-    // more than the 64 KB instruction cache two CUs share; the tail's zeros are selected by wave-uniform conditions
-    for (unsigned c = 0; c < n_cols; c += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            if (c + k < n_cols) {
-                const u64 *p = col_ptrs ? col_ptrs[c + k] : base + (size_t)(c + k) * col_stride;
-                s[k] = p[I];
-            } else {
-                s[k] = 0;
-            }
-        }
-        poseidon2_permutation(s);
-    }
-    // digest = state[0..4]; 32 B per lane
-    ulonglong2 *d = reinterpret_cast<ulonglong2 *>(digests + 4 * I);
-    d[0] = make_ulonglong2(gl::canon(s[0]), gl::canon(s[1]));
-    d[1] = make_ulonglong2(gl::canon(s[2]), gl::canon(s[3]));
+    sponge_leaves<poseidon2_permutation>(base, col_stride, col_ptrs, n_cols, num_leaves, digests);
 }
-
-// A RUN of absorptions of the same sponge, for leaves whose columns arrive in groups (bj_prove: the witness comes over PCIe
-// while the first groups are already being extended and hashed): state[8..12] <- what the previous group left in `capacity`
-// ([4][num_leaves], zeros before the first group); then, eight columns at a time, state[0..8] <- the group's next elements
-// (zero-padded in the last block of the last group), permute — every group but the last holds a multiple of eight columns;
-// the last group writes the digest, the others their capacity words.  Group by group this is exactly poseidon2_leaves_kernel's
-// loop (sponge.rs:224-346: overwrite mode, no length tag), with ONE call site of the permutation as there.
 __global__ void __launch_bounds__(256)
 poseidon2_leaves_absorb_kernel(const u64 *base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *capacity,
                                u64 *digests, int first, int last) {
-    size_t I = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= num_leaves) return;
-    u64 s[12];
-#pragma unroll
-    for (int k = 0; k < 4; k++) s[8 + k] = first ? 0 : capacity[(size_t)k * num_leaves + I];
-    for (unsigned c = 0; c < n_cols; c += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) s[k] = c + k < n_cols ? base[(size_t)(c + k) * col_stride + I] : 0;
-        poseidon2_permutation(s);
-    }
-    if (last) {
-        ulonglong2 *d = reinterpret_cast<ulonglong2 *>(digests + 4 * I);
-        d[0] = make_ulonglong2(gl::canon(s[0]), gl::canon(s[1]));
-        d[1] = make_ulonglong2(gl::canon(s[2]), gl::canon(s[3]));
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) capacity[(size_t)k * num_leaves + I] = s[8 + k];
-    }
+    sponge_leaves_absorb<poseidon2_permutation>(base, col_stride, n_cols, num_leaves, capacity, digests, first, last);
 }
-
-// leaf j = sponge( src0[jE..(j+1)E) || src1[jE..(j+1)E) || ... )           (merkle_tree.rs:176-386, FRI oracles)
 __global__ void __launch_bounds__(256)
 poseidon2_leaves_chunked_kernel(const u64 *src0, const u64 *src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
                                 u64 *digests) {
-    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= num_leaves) return;
-    const unsigned E = 1u << log_e;
-    const unsigned total = n_srcs * E;
+    const unsigned E = 1u << log_e, total = n_srcs * E;
     u64 s[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) s[k] = 0;
-    for (unsigned t = 0; t < total; t += 8) {   // one call site of the permutation (instruction-cache footprint, see above)
+    for (unsigned t = 0; t < total; t += 8) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const unsigned idx = t + k;             // wave-uniform
-            u64 v = 0;
-            if (idx < total) {
-                const u64 *p = (idx >> log_e) == 0 ? src0 : src1;
-                v = p[j * E + (idx & (E - 1))];
-            }
-            s[k] = v;
-        }
+        for (int k = 0; k < 8; k++) s[k] = t + k < total ? chunk_word(src0, src1, log_e, E, j, t + k) : 0;   // t + k is wave-uniform
         poseidon2_permutation(s);
     }
-    ulonglong2 *d = reinterpret_cast<ulonglong2 *>(digests + 4 * j);
-    d[0] = make_ulonglong2(gl::canon(s[0]), gl::canon(s[1]));
-    d[1] = make_ulonglong2(gl::canon(s[2]), gl::canon(s[3]));
+    sponge_store_digest(digests, j, s);
 }
-
-// node layer: parent i = perm(left || right || 0000)[0..4]                 (oracle/mod.rs:162-168)
 __global__ void __launch_bounds__(256) poseidon2_nodes_kernel(const u64 *children, u64 *parents, size_t num_parents) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= num_parents) return;
-    const ulonglong2 *c = reinterpret_cast<const ulonglong2 *>(children + 8 * i);
-    ulonglong2 a = c[0], b = c[1], e = c[2], f = c[3];
-    u64 s[12] = {a.x, a.y, b.x, b.y, e.x, e.y, f.x, f.y, 0, 0, 0, 0};
-    poseidon2_permutation(s);
-    ulonglong2 *d = reinterpret_cast<ulonglong2 *>(parents + 4 * i);
-    d[0] = make_ulonglong2(gl::canon(s[0]), gl::canon(s[1]));
-    d[1] = make_ulonglong2(gl::canon(s[2]), gl::canon(s[3]));
+    sponge_nodes<poseidon2_permutation>(children, parents, num_parents);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -453,62 +379,40 @@ poseidon2_leaves_chunked_lanepar_kernel(const u64 *src0, const u64 *src1, unsign
     if (live && l < 4) digests[4 * j + l] = gl::canon(s);
 }
 
-__global__ void poseidon2_permute_states_kernel(u64 *states, size_t n_states) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_states) return;
-    u64 s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = states[12 * i + k];
-    poseidon2_permutation(s);
-#pragma unroll
-    for (int k = 0; k < 12; k++) states[12 * i + k] = gl::canon(s[k]);
+__global__ void poseidon2_permute_states_kernel(u64 *states, size_t n_states) { sponge_permute_states<poseidon2_permutation>(states, n_states); }
+
+// layers and oracles of up to bj::env().nodes_lanepar_max items are latency-bound: the lane-parallel kernels, one item per
+// 16 lanes (BJ_NODES_LANEPAR_MAX=0: never)
+static void launch_poseidon2_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
+                                    size_t num_leaves, u64 *d_digests, hipStream_t s) {
+    launch_1d(poseidon2_leaves_kernel, num_leaves, s, d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests);
+}
+static void launch_poseidon2_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e,
+                                            size_t num_leaves, u64 *d_digests, hipStream_t s) {
+    if (num_leaves <= bj::env().nodes_lanepar_max)
+        hipLaunchKernelGGL(poseidon2_leaves_chunked_lanepar_kernel, dim3((unsigned)((num_leaves + BJ_LANEPAR_GROUPS - 1) / BJ_LANEPAR_GROUPS)),
+                           dim3(256), 0, s, d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests);
+    else
+        launch_1d(poseidon2_leaves_chunked_kernel, num_leaves, s, d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests);
+}
+static void launch_poseidon2_nodes(const u64 *d_children, u64 *d_parents, size_t num_parents, hipStream_t s) {
+    if (num_parents <= bj::env().nodes_lanepar_max)
+        hipLaunchKernelGGL(poseidon2_nodes_lanepar_kernel, dim3((unsigned)((num_parents + BJ_LANEPAR_GROUPS - 1) / BJ_LANEPAR_GROUPS)),
+                           dim3(256), 0, s, d_children, d_parents, num_parents);
+    else
+        launch_1d(poseidon2_nodes_kernel, num_parents, s, d_children, d_parents, num_parents);
+}
+static void launch_poseidon2_leaves_absorb(const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *d_capacity,
+                                           u64 *d_digests, bool first, bool last, hipStream_t s) {
+    launch_1d(poseidon2_leaves_absorb_kernel, num_leaves, s, d_base, col_stride, n_cols, num_leaves, d_capacity, d_digests,
+              first, last);
+}
+TreeHasher poseidon2_tree_hasher() {
+    return {launch_poseidon2_leaves, launch_poseidon2_leaves_chunked, launch_poseidon2_nodes, launch_poseidon2_leaves_absorb};
 }
 
-static size_t nodes_lanepar_max() {   // layers up to this many parents use the lane-parallel kernel (BJ_NODES_LANEPAR_MAX=0: never)
-    return bj::env().nodes_lanepar_max;
-}
-void launch_poseidon2_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
-                             size_t num_leaves, u64 *d_digests, hipStream_t s) {
-    unsigned tpb = 256;
-    hipLaunchKernelGGL(poseidon2_leaves_kernel, dim3((unsigned)((num_leaves + tpb - 1) / tpb)), dim3(tpb), 0, s,
-                       d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests);
-}
-void launch_poseidon2_leaves_absorb(const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *d_capacity,
-                                    u64 *d_digests, bool first, bool last, hipStream_t s) {
-    hipLaunchKernelGGL(poseidon2_leaves_absorb_kernel, dim3((unsigned)((num_leaves + 255) / 256)), dim3(256), 0, s, d_base,
-                       col_stride, n_cols, num_leaves, d_capacity, d_digests, first ? 1 : 0, last ? 1 : 0);
-}
-void launch_poseidon2_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e,
-                                     size_t num_leaves, u64 *d_digests, hipStream_t s) {
-    unsigned tpb = 256;
-    if (num_leaves <= nodes_lanepar_max())   // latency-bound: one leaf per 16 lanes
-        hipLaunchKernelGGL(poseidon2_leaves_chunked_lanepar_kernel, dim3((unsigned)((num_leaves + BJ_LANEPAR_GROUPS - 1) / BJ_LANEPAR_GROUPS)),
-                           dim3(tpb), 0, s, d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests);
-    else
-        hipLaunchKernelGGL(poseidon2_leaves_chunked_kernel, dim3((unsigned)((num_leaves + tpb - 1) / tpb)), dim3(tpb), 0,
-                           s, d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests);
-}
-// tree layout: layer 0 = num_leaves digests, then num_leaves/2, ... down to cap_size (inclusive), back to back
-void launch_poseidon2_node_layers(u64 *d_tree, size_t num_leaves, size_t cap_size, hipStream_t s) {
-    u64 *prev = d_tree;
-    size_t len = num_leaves;
-    while (len > cap_size) {
-        u64 *next = prev + 4 * len;
-        size_t nl = len / 2;
-        unsigned tpb = 256;
-        if (nl <= nodes_lanepar_max())   // latency-bound layer: one permutation per 16 lanes
-            hipLaunchKernelGGL(poseidon2_nodes_lanepar_kernel, dim3((unsigned)((nl + BJ_LANEPAR_GROUPS - 1) / BJ_LANEPAR_GROUPS)),
-                               dim3(tpb), 0, s, prev, next, nl);
-        else
-            hipLaunchKernelGGL(poseidon2_nodes_kernel, dim3((unsigned)((nl + tpb - 1) / tpb)), dim3(tpb), 0, s, prev, next, nl);
-        prev = next;
-        len = nl;
-    }
-}
 void launch_poseidon2_permute_states(u64 *d_states, size_t n_states, hipStream_t s) {
-    unsigned tpb = 64;
-    hipLaunchKernelGGL(poseidon2_permute_states_kernel, dim3((unsigned)((n_states + tpb - 1) / tpb)), dim3(tpb), 0, s,
-                       d_states, n_states);
+    hipLaunchKernelGGL(poseidon2_permute_states_kernel, dim3((unsigned)((n_states + 63) / 64)), dim3(64), 0, s, d_states, n_states);
 }
 
 }  // namespace bj

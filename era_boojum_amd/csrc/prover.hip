@@ -169,6 +169,13 @@ struct StageTimer {
     }
 };
 
+// the tree kernels of the calls in its scope follow the proof config, then the context's own setting returns
+struct HasherGuard {
+    bj_ctx *c;
+    int saved;
+    ~HasherGuard() { c->hasher = saved; }
+};
+
 }  // namespace
 
 namespace bj {
@@ -327,11 +334,7 @@ int bj_setup_create_sharded(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_
     }
     bj_setup *s = new bj_setup();
     s->device = ctx->device;
-    struct HasherGuard {   // the tree kernels of the calls below follow the proof config, then the context's own setting returns
-        bj_ctx *c;
-        int saved;
-        ~HasherGuard() { c->hasher = saved; }
-    } hasher_guard{ctx, ctx->hasher};
+    HasherGuard hasher_guard{ctx, ctx->hasher};
     ctx->hasher = cfg->tree_hasher ? (int)cfg->tree_hasher : BJ_HASHER_POSEIDON2;
     if (comm && comm->world > 1) {
         s->sh.rank = comm->rank;
@@ -688,11 +691,7 @@ int prove_impl(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, cons
         }
         ~InProof() { c->in_proof = false; }
     } in_proof(ctx);
-    struct HasherGuard {
-        bj_ctx *c;
-        int saved;
-        ~HasherGuard() { c->hasher = saved; }
-    } hasher_guard{ctx, ctx->hasher};
+    HasherGuard hasher_guard{ctx, ctx->hasher};
     struct CopyDrain {   // bj_prove: whatever way the proof ends, no queued copy may still read the caller's witness afterwards
         bj_ctx *c;
         bool active;

@@ -1,0 +1,42 @@
+// What the four Merkle-tree hashers (poseidon2.hip, poseidon1.hip, blake2s.hip, keccak.hip) share: where a lane finds the
+// words of its leaf, how a per-lane kernel is launched, and the entry each hasher contributes to the dispatch of tree_hash.hip.
+// How the words are absorbed (rate, padding, length tag) is each hasher's own.
+#pragma once
+#include "gl.h"
+
+namespace bj {
+typedef uint64_t u64;
+
+// word of column c for leaf I; columns are base + c * col_stride or come through a device array of column pointers.
+// c is wave-uniform, so a wavefront reads 64 consecutive words of one column (512 B, coalesced).
+__device__ __forceinline__ u64 leaf_word(const u64 *base, size_t col_stride, const u64 *const *col_ptrs, unsigned c, size_t I) {
+    const u64 *p = col_ptrs ? col_ptrs[c] : base + (size_t)c * col_stride;
+    return p[I];
+}
+// word idx of leaf j = src0[jE..(j+1)E) || src1[jE..(j+1)E), E = 2^log_e   (FRI oracles, merkle_tree.rs:176-386)
+__device__ __forceinline__ u64 chunk_word(const u64 *src0, const u64 *src1, unsigned log_e, unsigned E, size_t j, unsigned idx) {
+    const u64 *p = (idx >> log_e) == 0 ? src0 : src1;
+    return p[j * E + (idx & (E - 1))];
+}
+
+// one lane per item, 256-lane workgroups
+template <typename... Params, typename... Args>
+inline void launch_1d(void (*kernel)(Params...), size_t n, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, args...);
+}
+
+// a hasher's launchers, one table entry of tree_hash.hip
+struct TreeHasher {
+    void (*leaves)(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols, size_t num_leaves,
+                   u64 *d_digests, hipStream_t s);
+    void (*leaves_chunked)(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e, size_t num_leaves, u64 *d_digests,
+                           hipStream_t s);
+    void (*nodes)(const u64 *d_children, u64 *d_parents, size_t num_parents, hipStream_t s);   // one layer
+    // one absorption run of a group of columns per leaf, d_capacity [4][num_leaves] carries the sponge between the groups;
+    // null for the byte hashers
+    void (*leaves_absorb)(const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *d_capacity, u64 *d_digests,
+                          bool first, bool last, hipStream_t s);
+};
+TreeHasher poseidon2_tree_hasher(), blake2s_tree_hasher(), keccak_tree_hasher(), poseidon1_tree_hasher();
+
+}  // namespace bj
