@@ -162,8 +162,10 @@ __host__ __device__ __forceinline__ void mul_limbs(u64 a, u64 b, u32 &hi_hi, u32
 //   result = D + c*EPS mod 2^64 (one more multiply-add on the 0/1 carry).  Why that is right:
 //     b = 0: c = 1 means R < 2^64 - 2^33 + 1, so D + EPS cannot wrap;
 //     b = 1: D >= 2^64 - 2^32 + 1 = p (H.hi + cm <= 2^32 - 1); with c = 1 the wrap of D + EPS cancels the borrow;
-//            with c = 0 the value is D - EPS (no second borrow as D >= p).  That last case needs R < 2^32: probability
-//            2^-32 per product, so it is a wave-uniform branch around three instructions, not predicated code.
+//            with c = 0 the value is D - EPS (no second borrow as D >= p).  A borrow is rare on random operands: with
+//            c = 0 it needs H.lo = 0 and lo < 2^32 (~2^-64 per product), with c = 1 (entered, correction masked) ~2^-33,
+//            so it is a wave-uniform branch around three instructions, not predicated code.  Inputs that reach it inside
+//            the Poseidon S-boxes: tools/find_poseidon_sbox_rare.c.
 // Temporaries are fixed physical registers (clobbers): the sequence writes halves of 64-bit pairs, which operands allocated by
 // the compiler cannot express (no sub-register modifier for inline-asm operands on this target).  The s_nop covers the 2 wait
 // states gfx950 needs between a VALU write of an SGPR pair and a VALU read of it (the compiler cannot see inside the string).
