@@ -55,6 +55,13 @@ _SIGNATURES = {
     "bj_barycentric_eval_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bj_deep_quotient_accumulate": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_int]),
+    "bj_deep_quotient_accumulate_range": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_size_t, C.c_size_t, C.c_void_p,
+                                                    C.c_void_p, C.c_int]),
+    "bj_deep_quotient_accumulate_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_size_t, C.c_size_t,
+                                                   C.c_void_p, C.c_void_p, C.c_int]),
+    "bj_linear_combination": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_void_p]),
     "bj_copy_perm_stage2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint,
                                       C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bj_lookup_polys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint,
@@ -173,6 +180,12 @@ def load_library():
                                  % (path, lib.bj_abi_version(), ABI_VERSION))
         _lib = lib
     return _lib
+
+
+class DeepSet(C.Structure):
+    """bj_deep_set: one opening set of bj_deep_quotient_accumulate_sets."""
+    _fields_ = [("src_c0", C.POINTER(C.c_void_p)), ("src_c1", C.POINTER(C.c_void_p)), ("n_src", C.c_size_t),
+                ("values", C.c_void_p), ("challenges", C.c_void_p), ("at2", C.c_void_p)]
 
 
 def _np_ptr(a):
@@ -446,6 +459,39 @@ class Context:
         a = np.array(at, dtype=np.uint64)
         self._check(self._lib.bj_deep_quotient_accumulate(self._h, p0, p1, k, _np_ptr(v), _np_ptr(ch), _np_ptr(a), log_n,
                                                           log_lde, d_dst0, d_dst1, int(bool(accumulate))))
+
+    @staticmethod
+    def _deep_args(sources, values, challenges, at):
+        k = len(sources)
+        p0 = (C.c_void_p * k)(*[a for a, _ in sources])
+        p1 = (C.c_void_p * k)(*[b for _, b in sources])
+        v = np.ascontiguousarray(np.array(values, dtype=np.uint64).reshape(-1))
+        ch = np.ascontiguousarray(np.array(challenges, dtype=np.uint64).reshape(-1))
+        return p0, p1, k, v, ch, np.array(at, dtype=np.uint64)
+
+    def deep_quotient_accumulate_range(self, sources, values, challenges, at, log_n, log_lde, first, count, d_dst0, d_dst1,
+                                       accumulate=True):
+        """The same on the LDE indices [first, first + count): every pointer addresses the `count` entries of that range."""
+        p0, p1, k, v, ch, a = self._deep_args(sources, values, challenges, at)
+        self._check(self._lib.bj_deep_quotient_accumulate_range(self._h, p0, p1, k, _np_ptr(v), _np_ptr(ch), _np_ptr(a), log_n,
+                                                                log_lde, first, count, d_dst0, d_dst1, int(bool(accumulate))))
+
+    def deep_quotient_accumulate_sets(self, sets, log_n, log_lde, first, count, d_dst0, d_dst1, accumulate=True):
+        """sets: list of (sources, values, challenges, at), each as in deep_quotient_accumulate; one pass for all of them."""
+        keep = [self._deep_args(*s) for s in sets]
+        arr = (DeepSet * max(len(sets), 1))()
+        for t, (p0, p1, k, v, ch, a) in enumerate(keep):
+            arr[t] = DeepSet(p0, p1, k, _np_ptr(v), _np_ptr(ch), _np_ptr(a))
+        self._check(self._lib.bj_deep_quotient_accumulate_sets(self._h, C.cast(arr, C.c_void_p), len(sets), log_n, log_lde, first,
+                                                               count, d_dst0, d_dst1, int(bool(accumulate))))
+
+    def linear_combination(self, sources, challenges, n, d_out0, d_out1):
+        """out = sum_k ch_k * src_k over n entries; sources: list of (d_c0, d_c1_or_None) device pointers."""
+        k = len(sources)
+        p0 = (C.c_void_p * k)(*[a for a, _ in sources])
+        p1 = (C.c_void_p * k)(*[b for _, b in sources])
+        ch = np.ascontiguousarray(np.array(challenges, dtype=np.uint64).reshape(-1))
+        self._check(self._lib.bj_linear_combination(self._h, p0, p1, k, _np_ptr(ch), n, d_out0, d_out1))
 
     def fri_fold_step(self, d_c0, d_c1, length, k, d_o0, d_o1, log_full, coset_inv, ch):
         self._check(self._lib.bj_fri_fold_step(self._h, d_c0, d_c1, length, k, d_o0, d_o1, log_full, coset_inv, ch[0], ch[1]))

@@ -48,6 +48,17 @@ struct DevArgs {
         if (d) bj::tmp_free(ctx, d, from_arena);
     }
 };
+// [first, first + count) must lie inside the LDE domain: the kernels index the twiddle table by first + i
+int check_deep_range(bj_ctx *ctx, const char *who, unsigned log_n, unsigned log_lde, size_t first, size_t count) {
+    const unsigned log_full = log_n + log_lde;
+    if (log_n > 32 || log_lde > 32 || log_full == 0 || log_full > 32)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: bad domain", who);
+    const size_t N = (size_t)1 << log_full;
+    if (count == 0 || count > N || first > N - count)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: range [%zu, %zu + %zu) is empty or passes the 2^%u-point domain", who, first,
+                        first, count, log_full);
+    return BJ_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -96,6 +107,44 @@ int bj_deep_quotient_accumulate(bj_ctx *ctx, const uint64_t *const *h_src_c0, co
                                 uint64_t *d_dst_c1, int accumulate) {
     return bj::deep_accumulate_range(ctx, h_src_c0, h_src_c1, n_src, h_values, h_challenges, at2, log_n, log_lde,
                                      (size_t)1 << (log_n + log_lde), 0, d_dst_c0, d_dst_c1, accumulate);
+}
+
+int bj_deep_quotient_accumulate_range(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1,
+                                      size_t n_src, const uint64_t *h_values, const uint64_t *h_challenges,
+                                      const uint64_t *at2, unsigned log_n, unsigned log_lde, size_t first, size_t count,
+                                      uint64_t *d_dst_c0, uint64_t *d_dst_c1, int accumulate) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (int rc = check_deep_range(ctx, "bj_deep_quotient_accumulate_range", log_n, log_lde, first, count)) return rc;
+    return bj::deep_accumulate_range(ctx, h_src_c0, h_src_c1, n_src, h_values, h_challenges, at2, log_n, log_lde, count, first,
+                                     d_dst_c0, d_dst_c1, accumulate);
+}
+
+int bj_deep_quotient_accumulate_sets(bj_ctx *ctx, const bj_deep_set *sets, unsigned n_sets, unsigned log_n,
+                                     unsigned log_lde, size_t first, size_t count, uint64_t *d_dst_c0,
+                                     uint64_t *d_dst_c1, int accumulate) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!sets || !d_dst_c0 || !d_dst_c1)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_deep_quotient_accumulate_sets: null pointer");
+    if (n_sets == 0 || n_sets > (unsigned)bj::DEEP_MAX_SETS)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_deep_quotient_accumulate_sets: %u opening sets, one call takes 1..%d", n_sets,
+                        bj::DEEP_MAX_SETS);
+    if (int rc = check_deep_range(ctx, "bj_deep_quotient_accumulate_sets", log_n, log_lde, first, count)) return rc;
+    bj::DeepSetHost hs[bj::DEEP_MAX_SETS];
+    for (unsigned t = 0; t < n_sets; t++)
+        hs[t] = bj::DeepSetHost{sets[t].src_c0, sets[t].src_c1, sets[t].n_src, sets[t].values, sets[t].challenges, sets[t].at2};
+    return bj::deep_accumulate_multi(ctx, hs, n_sets, log_n, log_lde, count, first, d_dst_c0, d_dst_c1, accumulate);
+}
+
+int bj_linear_combination(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1, size_t n_src,
+                          const uint64_t *h_challenges, size_t n, uint64_t *d_out_c0, uint64_t *d_out_c1) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!h_src_c0 || !h_challenges || !d_out_c0 || !d_out_c1)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_linear_combination: null pointer");
+    if (n_src == 0 || n_src > (1u << 20)) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_linear_combination: bad source count");
+    if (n == 0) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_linear_combination: n = 0");
+    for (size_t k = 0; k < n_src; k++)
+        if (!h_src_c0[k]) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_linear_combination: null source %zu", k);
+    return bj::combine_monomials(ctx, h_src_c0, h_src_c1, n_src, h_challenges, n, d_out_c0, d_out_c1);
 }
 
 }  // extern "C"

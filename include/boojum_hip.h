@@ -232,6 +232,34 @@ int bj_deep_quotient_accumulate(bj_ctx *ctx, const uint64_t *const *h_src_c0, co
                                 size_t n_src, const uint64_t *h_values, const uint64_t *h_challenges,
                                 const uint64_t *at2, unsigned log_n, unsigned log_lde, uint64_t *d_dst_c0,
                                 uint64_t *d_dst_c1, int accumulate);
+/* The same on the LDE indices [first, first + count) only — the contiguous range of cosets one GPU of a sharded proof owns:
+ * every source and destination pointer addresses the `count` entries of that range (entry i belongs to the point
+ * I = first + i).  count = 0 and first + count > 2^(log_n+log_lde) are refused. */
+int bj_deep_quotient_accumulate_range(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1,
+                                      size_t n_src, const uint64_t *h_values, const uint64_t *h_challenges,
+                                      const uint64_t *at2, unsigned log_n, unsigned log_lde, size_t first, size_t count,
+                                      uint64_t *d_dst_c0, uint64_t *d_dst_c1, int accumulate);
+/* One opening set of bj_deep_quotient_accumulate_sets: the arguments of bj_deep_quotient_accumulate that belong to one
+ * point `at` (host arrays of device pointers, [n_src][2] values and challenges, the point as two words). */
+typedef struct bj_deep_set {
+    const uint64_t *const *src_c0;
+    const uint64_t *const *src_c1; /* NULL array or NULL entry = base-field source */
+    size_t n_src;
+    const uint64_t *values;
+    const uint64_t *challenges;
+    const uint64_t *at2;
+} bj_deep_set;
+/* n_sets (1..3) opening sets in ONE pass over [first, first + count): dst (+)= the sum of the sets' quotients, with one
+ * field inversion per lane for all of them and the destination written once.  The values are those of n_sets calls of
+ * bj_deep_quotient_accumulate_range (the prover opens at z, z*omega and 0 this way).  More than 3 sets are refused. */
+int bj_deep_quotient_accumulate_sets(bj_ctx *ctx, const bj_deep_set *sets, unsigned n_sets, unsigned log_n,
+                                     unsigned log_lde, size_t first, size_t count, uint64_t *d_dst_c0,
+                                     uint64_t *d_dst_c1, int accumulate);
+/* out[i] = sum_k ch_k * src_k[i] over n >= 1 entries: the DEEP numerator of a large opening set taken on the MONOMIAL
+ * forms (combined once over n coefficients, then extended by one two-column LDE).  Sources and h_challenges ([n_src][2])
+ * are given as in the DEEP call; d_out_c0 / d_out_c1 receive n canonical values each. */
+int bj_linear_combination(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1, size_t n_src,
+                          const uint64_t *h_challenges, size_t n, uint64_t *d_out_c0, uint64_t *d_out_c1);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Fiat–Shamir transcript (host side, tiny data, order-critical).  Replaces `Transcript` impls

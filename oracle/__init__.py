@@ -423,6 +423,28 @@ def deep_quotient_accumulate_range(sources, values, challenges, at, log_n, log_l
                                              C.c_int(threads))
 
 
+def linear_combination(sources, challenges, threads=1):
+    """out = sum_k ch_k * src_k; sources: list of (c0_array, c1_array_or_None) of one length; returns (out0, out1), canonical."""
+    k = len(sources)
+    keep = []
+    p0 = (u64p * k)()
+    p1 = (u64p * k)()
+    count = _arr(sources[0][0]).size
+    for i, (a, b) in enumerate(sources):
+        a = _arr(a); keep.append(a); p0[i] = _p(a)
+        assert a.ndim == 1 and a.size == count
+        if b is None:
+            p1[i] = None
+        else:
+            b = _arr(b); keep.append(b); p1[i] = _p(b)
+            assert b.ndim == 1 and b.size == count
+    chs = _arr(challenges).reshape(-1)
+    assert chs.size == 2 * k
+    o0, o1 = np.zeros(count, dtype=np.uint64), np.zeros(count, dtype=np.uint64)
+    lib().orc_linear_combination(p0, p1, C.c_size_t(k), _p(chs), C.c_size_t(count), _p(o0), _p(o1), C.c_int(threads))
+    return o0, o1
+
+
 def deep_quotient_point(f, values, challenges, at, x):
     """f: list of (c0, c1_or_None) python ints at ONE LDE point x; returns the (c0, c1) contribution."""
     k = len(f)

@@ -103,6 +103,8 @@ void orc_deep_quotient_accumulate(const uint64_t *const *src_c0, const uint64_t 
 void orc_deep_quotient_accumulate_range(const uint64_t *const *src_c0, const uint64_t *const *src_c1, size_t n_src,
                                         const uint64_t *values, const uint64_t *challenges, const uint64_t *at, unsigned log_n,
                                         unsigned log_lde, size_t first, size_t count, uint64_t *dst0, uint64_t *dst1, int threads);
+void orc_linear_combination(const uint64_t *const *src_c0, const uint64_t *const *src_c1, size_t n_src, const uint64_t *challenges,
+                            size_t count, uint64_t *out0, uint64_t *out1, int threads);
 
 #ifdef __cplusplus
 }

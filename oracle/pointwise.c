@@ -137,3 +137,21 @@ void orc_deep_quotient_accumulate(const uint64_t *const *src_c0, const uint64_t 
         free(f0); free(f1); free(ie);
     }
 }
+
+/* ---- linear combination of columns with F_p^2 coefficients (our own definition, not a restatement) ----
+ * out(i) = sum_k ch_k * f_k(i) over `count` entries, f_k = (src_c0[k], src_c1[k]) or the base column src_c0[k] embedded as (f, 0)
+ * when src_c1[k] == NULL.  Inputs may be any u64 representative; every product is reduced on its own (128-bit product, gl_mul),
+ * no lazy accumulation: this is the reference of the DEEP numerator taken on monomial forms. */
+void orc_linear_combination(const uint64_t *const *src_c0, const uint64_t *const *src_c1, size_t n_src,
+                            const uint64_t *challenges /*[n_src][2]*/, size_t count, uint64_t *out0, uint64_t *out1, int threads) {
+#pragma omp parallel for schedule(static) num_threads(threads)
+    for (size_t i = 0; i < count; i++) {
+        gl2_t acc = gl2_make(0, 0);
+        for (size_t k = 0; k < n_src; k++) {
+            gl2_t ch = gl2_make(gl_canon(challenges[2 * k]), gl_canon(challenges[2 * k + 1]));
+            gl2_t f = gl2_make(gl_canon(src_c0[k][i]), src_c1[k] ? gl_canon(src_c1[k][i]) : 0);
+            acc = gl2_add(acc, gl2_mul(f, ch));
+        }
+        out0[i] = acc.c0; out1[i] = acc.c1;
+    }
+}

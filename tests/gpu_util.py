@@ -59,6 +59,14 @@ def rand_gl(rng, shape, noncanonical=False):
     return a
 
 
+def scan_inputs(log_n, V=5):
+    """Variable and sigma columns ([V][2^log_n], random residues) and 32-bit multipliers k_c for the grand-product tests above
+    2^18 rows.  Fixed seeds: tests/test_oracle_openings.py checks on the CPU that no row of them has a zero denominator."""
+    rng = np.random.default_rng(1800 + log_n)
+    n = 1 << log_n
+    return rand_gl(rng, (V, n)), rand_gl(rng, (V, n)), [int(k) for k in rng.integers(1, 1 << 32, size=V)]
+
+
 class DevBuf:
     def __init__(self, arr=None, nelems=None):
         c = ctx()

@@ -10,7 +10,7 @@ import pytest
 import era_boojum_amd as E
 import oracle as O
 from era_boojum_amd import synthetic as S
-from gpu_util import DevBuf, ctx, rand_gl
+from gpu_util import DevBuf, ctx, oracle_threads, rand_gl, scan_inputs
 from oracle import prover as OP
 
 pytestmark = pytest.mark.gpu
@@ -73,6 +73,25 @@ def test_copy_permutation_with_noncanonical_inputs_and_strided_columns():
     d_v, d_s, d_z, d_p = DevBuf(vars_p), DevBuf(sig_p), DevBuf(nelems=2 * n), DevBuf(nelems=2 * (n_chunks - 1) * n)
     ctx().copy_perm_stage2(d_v.ptr, stride, d_s.ptr, stride, c.non_residues, V, q, log_n, BETA, GAMMA, d_z.ptr, d_p.ptr)
     assert np.array_equal(d_z.get((2, n)), wz) and np.array_equal(d_p.get((n_chunks - 1, 2, n)), wp)
+    for d in (d_v, d_s, d_z, d_p):
+        d.free()
+
+
+@pytest.mark.parametrize("log_n", [18, 19, 20])
+def test_grand_product_scan_above_2p18_rows(log_n):
+    """256, 512 and 1024 scan blocks of 1024 rows: scan_blocks_kernel (one workgroup, chunks of 256 block totals) makes one trip
+    exactly, then 2 and 4 with the running prefix carried across them — the sizes above stop at 8 blocks.  Random columns (the
+    operator is the same function of whatever it is given; tests/test_oracle_openings.py checks these seeds have no zero
+    denominator), V = 5 in chunks of 4: z and one partial-product column."""
+    V, chunk, n = 5, 4, 1 << log_n
+    variables, sigmas, non_res = scan_inputs(log_n, V)
+    wz, wp = OP.copy_perm_stage2(variables, sigmas, non_res, log_n, chunk, BETA, GAMMA, threads=oracle_threads(16))
+    d_v, d_s, d_z, d_p = DevBuf(variables), DevBuf(sigmas), DevBuf(nelems=2 * n), DevBuf(nelems=2 * n)
+    ctx().copy_perm_stage2(d_v.ptr, n, d_s.ptr, n, non_res, V, chunk, log_n, BETA, GAMMA, d_z.ptr, d_p.ptr)
+    z = d_z.get((2, n))
+    assert z[0][0] == 1 and z[1][0] == 0
+    assert np.array_equal(z, wz)
+    assert np.array_equal(d_p.get((1, 2, n)), wp)
     for d in (d_v, d_s, d_z, d_p):
         d.free()
 
