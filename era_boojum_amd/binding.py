@@ -64,6 +64,7 @@ _SIGNATURES = {
                                         C.c_void_p, C.c_void_p]),
     "bj_copy_perm_stage2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint,
                                       C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bj_sigmas_from_placement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t]),
     "bj_lookup_polys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint,
                                   C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bj_quotient_gates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p,
@@ -114,6 +115,8 @@ _SIGNATURES = {
     "bj_setup_shape": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bj_setup_dump_info": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p]),
     "bj_setup_create_from_dump": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "bj_setup_create_from_placement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(C.c_void_p)]),
     "bj_prove_from_dumps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
                                       C.POINTER(C.c_void_p)]),
     "bj_proof_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -333,6 +336,13 @@ class Context:
         nr = np.ascontiguousarray(non_residues, dtype=np.uint64)
         self._check(self._lib.bj_copy_perm_stage2(self._h, d_vars, var_stride, d_sigmas, sig_stride, _np_ptr(nr), num_vars, chunk,
                                                   log_n, _np_ptr(self._e2(beta)), _np_ptr(self._e2(gamma)), d_z, d_partials))
+
+    def sigmas_from_placement(self, d_placement, num_vars, log_n, non_residues, d_sigmas, place_stride=None, sig_stride=None):
+        """bj_sigmas_from_placement: d_placement [num_vars][n] copy-hint cells (bit 63 = placeholder) -> d_sigmas [num_vars][n]."""
+        nr = np.array([int(k) for k in non_residues], dtype=np.uint64)
+        n = 1 << log_n
+        self._check(self._lib.bj_sigmas_from_placement(self._h, d_placement, place_stride or n, num_vars, log_n, _np_ptr(nr), d_sigmas,
+                                                       sig_stride or n))
 
     def lookup_polys(self, d_lvars, var_stride, d_table_id, d_tables, table_stride, d_mult, reps, width, log_n, beta, gamma, d_A, d_B):
         self._check(self._lib.bj_lookup_polys(self._h, d_lvars, var_stride, d_table_id, d_tables, table_stride, d_mult, reps, width,
@@ -963,14 +973,17 @@ class ProverSetup:
     (bj_setup_create_sharded)."""
 
     def __init__(self, ctx, circuit, fri_lde_factor=8, cap_size=16, security_level=100, pow_bits=0, comm=None,
-                 transcript="poseidon2", setup_base_dump=None, pow_runner="blake2s", tree_hasher=None):
+                 transcript="poseidon2", setup_base_dump=None, pow_runner="blake2s", tree_hasher=None, variables_hint_dump=None):
         """pow_runner: "blake2s" | "keccak256" — the PoWRunner (pow.rs), independent of the transcript as in the reference.
         tree_hasher: None pairs the transcript with its usual hasher (Poseidon2 trees for "poseidon2" / "poseidon", the same byte
         hash for "blake2s" / "keccak256"); "poseidon2" | "poseidon" | "blake2s" | "keccak256" picks one (BJ_HASHER_*), e.g.
         "poseidon" with transcript="poseidon" for GoldilocksPoseidonSponge trees + GoldilocksPoisedonTranscript.
         setup_base_dump: the bytes of the reference's `SetupBaseStorage::write_into_buffer` (bj_setup_create_from_dump): the
         columns, constant-column count, table-id column, selector paths, quotient degree and non-residues then come from the
-        dump / are computed by the library, and `circuit` only has to carry the geometry and the gate list."""
+        dump / are computed by the library, and `circuit` only has to carry the geometry and the gate list.
+        variables_hint_dump: the bytes of `DenseVariablesCopyHint` (bj_setup_create_from_placement): `circuit.sigmas` is not read,
+        the copy-permutation polynomials are built on the device from the placement, which stays resident so that
+        `prove_from_dumps(witness_vec_dump, None)` works.  See `from_placement`."""
         self._ctx, self._lib, self.circuit = ctx, ctx._lib, circuit
         self._comm = comm
         self.fri_lde_factor, self.cap_size, self.security_level, self.pow_bits = fri_lde_factor, cap_size, security_level, pow_bits
@@ -1010,10 +1023,18 @@ class ProverSetup:
             self.hasher_kind = {"poseidon2": 1, "blake2s": 2, "keccak256": 3, "poseidon": 4}[tree_hasher]
         cfg = _ProofConfig(fri_lde_factor, cap_size, security_level, pow_bits, self.transcript_kind, self.hasher_kind,
                            {"blake2s": 1, "keccak256": 2}[pow_runner])
-        sig = np.ascontiguousarray(c.sigmas, dtype=np.uint64)
         con = np.ascontiguousarray(c.constants, dtype=np.uint64)
         tab = np.ascontiguousarray(c.tables, dtype=np.uint64)
         h = C.c_void_p()
+        if variables_hint_dump is not None:
+            if comm is not None or from_dump:
+                raise BoojumHipError("a setup from a placement is single-GPU and takes its columns from the circuit, not from a dump")
+            blob = bytes(variables_hint_dump)
+            ctx._check(self._lib.bj_setup_create_from_placement(ctx._h, C.byref(cc), blob, len(blob), _np_ptr(con),
+                                                                _np_ptr(tab) if c.lookup_reps else None, C.byref(cfg), C.byref(h)))
+            self._h = h
+            return
+        sig = np.ascontiguousarray(c.sigmas, dtype=np.uint64)
         if from_dump:
             if comm is not None:
                 raise BoojumHipError("a setup from a dump is single-GPU")
@@ -1025,6 +1046,13 @@ class ProverSetup:
                                                      _np_ptr(tab) if c.lookup_reps else None, C.byref(cfg),
                                                      C.byref(comm.struct) if comm is not None else None, C.byref(h)))
         self._h = h
+
+    @classmethod
+    def from_placement(cls, ctx, circuit, var_ids, *args, **kwargs):
+        """Setup from the variable placement instead of `circuit.sigmas`: var_ids [num_vars][n] integers, negative = empty cell
+        (what `DenseVariablesCopyHint` encodes).  Other arguments as for the constructor."""
+        from . import memcopy_format
+        return cls(ctx, circuit, *args, variables_hint_dump=memcopy_format.write_variables_hint(var_ids), **kwargs)
 
     def device_bytes(self):
         """HBM held by this setup (its shard when sharded): bj_setup_device_bytes."""
@@ -1126,11 +1154,12 @@ class ProverSetup:
 
     def prove_from_dumps(self, witness_vec_dump, variables_hint_dump, witness_hint_dump=None):
         """bj_prove_from_dumps: the reference's `WitnessVec` and `DenseVariablesCopyHint` (+ `DenseWitnessCopyHint`) bytes in, the
-        proof out."""
-        w, v = bytes(witness_vec_dump), bytes(variables_hint_dump)
+        proof out.  variables_hint_dump may be None on a setup made from a placement, which holds the hint itself."""
+        w = bytes(witness_vec_dump)
+        v = bytes(variables_hint_dump) if variables_hint_dump is not None else None
         x = bytes(witness_hint_dump) if witness_hint_dump is not None else None
         h = C.c_void_p()
-        self._ctx._check(self._lib.bj_prove_from_dumps(self._ctx._h, self._h, w, len(w), v, len(v), x, len(x) if x else 0, C.byref(h)))
+        self._ctx._check(self._lib.bj_prove_from_dumps(self._ctx._h, self._h, w, len(w), v, len(v) if v else 0, x, len(x) if x else 0, C.byref(h)))
         return self._finish(h)
 
     def prove_dev(self, d_variables, d_multiplicities, public_values=None):

@@ -6,6 +6,7 @@
 #include "kernels.h"
 
 #include <hip/hip_runtime.h>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -101,6 +102,29 @@ int lde_cosets_strided(bj_ctx *ctx, const gl::u64 *d_mono, size_t in_col_stride,
 bool mono_tiled(unsigned log_n);   // the monomial layout of bj_prove for this trace length (abi.hip)
 int intt_to_tiled(bj_ctx *ctx, const gl::u64 *d_in, size_t in_col_stride, gl::u64 *d_out, size_t out_col_stride, unsigned log_n,
                   unsigned n_cols);
+// setup_placement.hip: sigma from the variable placement.  The workspace lives in the context's scratch (valid until the next
+// ensure_scratch): u32 key / cell-number double buffers of the sort, its temporary storage, the non-residues, a flag word and
+// `staging_elems` words for the caller's uploads.  keys[0] takes the placement as u32 (PLACEMENT_NONE = placeholder).
+constexpr uint32_t PLACEMENT_NONE = 0xFFFFFFFFu;
+struct PlacementWorkspace {
+    size_t cells = 0, sort_bytes = 0;
+    uint32_t *keys[2] = {}, *vals[2] = {};
+    gl::u64 *sort_tmp = nullptr, *non_res = nullptr, *staging = nullptr;
+    unsigned *bad = nullptr;
+};
+int placement_workspace(bj_ctx *ctx, unsigned num_vars, unsigned log_n, size_t staging_elems, PlacementWorkspace *w);
+// copy-hint cells [cols][n] (bit 63 = placeholder, low 48 bits = index) -> u32; an index above 2^32 - 2 raises the flag word
+int placement_narrow(bj_ctx *ctx, const PlacementWorkspace &w, const gl::u64 *d_hint, size_t in_stride, unsigned cols, unsigned log_n,
+                     uint32_t *d_out);
+int placement_check(bj_ctx *ctx, const PlacementWorkspace &w);   // synchronises; BJ_ERR_UNSUPPORTED if the flag was raised
+int sigmas_from_keys(bj_ctx *ctx, const PlacementWorkspace &w, unsigned num_vars, unsigned log_n, const gl::u64 *h_non_residues,
+                     gl::u64 *d_sigmas, size_t sig_stride);      // sorts keys[0] (destroyed) and scatters
+// prover.hip: bj_setup_create[_sharded] with the sigma columns either from the host or written on the device by `fill_sigmas`
+// ([num_vars][n] at d_sigmas, called once the setup's buffers exist); a placement handed over is freed with the setup
+int setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const std::function<int(bj_setup *, gl::u64 *)> &fill_sigmas,
+                      const uint64_t *h_constants, const uint64_t *h_tables, const bj_proof_config *cfg, const bj_comm *comm, bj_setup **out);
+void setup_adopt_placement(bj_setup *s, uint32_t *d_placement);   // [num_vars][n] u32, hipMalloc'ed
+const uint32_t *setup_placement(const bj_setup *s);               // nullptr unless created from a placement
 inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 inline unsigned log2_exact(size_t x) {
     unsigned r = 0;

@@ -20,6 +20,7 @@
 #include "ctx.h"
 
 #include <cstring>
+#include <functional>
 #include <vector>
 
 using gl::u64;
@@ -148,20 +149,42 @@ std::vector<u64> make_non_residues(size_t count, u64 domain_size) {
 }
 
 constexpr u64 PLACEHOLDER_BIT = 1ull << 63, LOW_U48 = (1ull << 48) - 1;
+// a cell of the copy hint (u64: bit 63 = placeholder, low 48 bits = index) or of a setup's resident placement (u32)
+__device__ __forceinline__ bool cell_empty(u64 h) { return h & PLACEHOLDER_BIT; }
+__device__ __forceinline__ u64 cell_index(u64 h) { return h & LOW_U48; }
+__device__ __forceinline__ bool cell_empty(uint32_t h) { return h == bj::PLACEMENT_NONE; }
+__device__ __forceinline__ u64 cell_index(uint32_t h) { return h; }
 // witness_set_from_witness_vec (witness.rs:386-443): cell = value of its variable, 0 for a placeholder
-__global__ void materialize_cells_kernel(const u64 *hint, const u64 *values, size_t n_values, u64 *cells, size_t count, unsigned *bad) {
+template <typename Cell>
+__global__ void materialize_cells_kernel(const Cell *hint, const u64 *values, size_t n_values, u64 *cells, size_t count, unsigned *bad) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    const u64 h = hint[i];
+    const Cell h = hint[i];
     u64 v = 0;
-    if (!(h & PLACEHOLDER_BIT)) {
-        const u64 idx = h & LOW_U48;
+    if (!cell_empty(h)) {
+        const u64 idx = cell_index(h);
         if (idx < n_values)
             v = values[idx];
         else
             atomicOr(bad, 1u);
     }
     cells[i] = v;
+}
+
+// DenseVariablesCopyHint / DenseWitnessCopyHint: u64 columns, each a u64 length + its cells; cols[c] = the cells of column c inside the dump
+int read_copy_hint(bj_ctx *ctx, const char *what, const void *dump, size_t len, unsigned want, size_t n, const unsigned char **cols) {
+    Reader h(dump, len);
+    const uint64_t hint_cols = h.u64v();
+    if (!h.ok || hint_cols != want)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s dump: %llu columns, the circuit has %u", what, (unsigned long long)hint_cols, want);
+    for (unsigned c = 0; c < want; c++) {
+        const uint64_t clen = h.u64v();
+        if (!h.ok || clen != n) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s dump: column %u has %llu cells, not %zu", what, c, (unsigned long long)clen, n);
+        cols[c] = h.skip(n * 8);
+        if (!cols[c]) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s dump: truncated", what);
+    }
+    if (h.p != h.end) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s dump: trailing bytes", what);
+    return BJ_OK;
 }
 
 struct DeviceBlock {
@@ -280,11 +303,46 @@ int bj_setup_create_from_dump(bj_ctx *ctx, const bj_circuit *circuit, const void
     return bj_setup_create(ctx, &c, hs.data(), hc.data(), lookups ? ht.data() : nullptr, config, out);
 }
 
+int bj_setup_create_from_placement(bj_ctx *ctx, const bj_circuit *circuit, const void *variables_hint, size_t variables_hint_len,
+                                   const uint64_t *h_constants, const uint64_t *h_tables, const bj_proof_config *config, bj_setup **out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!circuit || !variables_hint || !config || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create_from_placement: null argument");
+    *out = nullptr;
+    const unsigned V = circuit->num_vars, log_n = circuit->log_n;
+    if (V == 0 || V > 4096 || log_n < 1 || log_n > 26 || !circuit->non_residues)   // bj_setup_create's own limits, before V columns are read
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create_from_placement: bad column counts / log_n out of range / no non-residues");
+    const size_t n = (size_t)1 << log_n;
+    std::vector<const unsigned char *> col(V);
+    if (int rc = read_copy_hint(ctx, "DenseVariablesCopyHint", variables_hint, variables_hint_len, V, n, col.data())) return rc;
+    // the hint goes up in groups of columns and stays as u32; sigma is written straight into the setup's natural-order columns
+    auto fill = [&](bj_setup *s, u64 *d_sigmas) -> int {
+        const unsigned G = V < 8 ? V : 8;
+        bj::PlacementWorkspace w;
+        if (int rc = bj::placement_workspace(ctx, V, log_n, (size_t)G * n, &w)) return rc;
+        uint32_t *d_place = nullptr;
+        BJ_HIP(ctx, hipMalloc((void **)&d_place, (size_t)V * n * 4));
+        bj::setup_adopt_placement(s, d_place);
+        for (unsigned c0 = 0; c0 < V; c0 += G) {
+            const unsigned g = V - c0 < G ? V - c0 : G;
+            for (unsigned k = 0; k < g; k++)
+                BJ_HIP(ctx, hipMemcpyAsync(w.staging + (size_t)k * n, col[c0 + k], n * 8, hipMemcpyHostToDevice, ctx->stream));
+            if (int rc = bj::placement_narrow(ctx, w, w.staging, n, g, log_n, d_place + (size_t)c0 * n)) return rc;
+            BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));   // as bj_prove_from_dumps: the staging block is reused by the next group
+        }
+        if (int rc = bj::placement_check(ctx, w)) return rc;
+        BJ_HIP(ctx, hipMemcpyAsync(w.keys[0], d_place, (size_t)V * n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        return bj::sigmas_from_keys(ctx, w, V, log_n, circuit->non_residues, d_sigmas, n);
+    };
+    return bj::setup_create_impl(ctx, circuit, nullptr, fill, h_constants, h_tables, config, nullptr, out);
+}
+
 int bj_prove_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_vec, size_t witness_vec_len,
                         const void *variables_hint, size_t variables_hint_len, const void *witness_hint, size_t witness_hint_len,
                         bj_proof **out) {
     if (int rc = bj::bind(ctx)) return rc;
-    if (!setup || !witness_vec || !variables_hint || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_from_dumps: null argument");
+    // no DenseVariablesCopyHint: the setup must hold the placement itself (bj_setup_create_from_placement)
+    const uint32_t *placement = setup && !variables_hint ? bj::setup_placement(setup) : nullptr;
+    if (!setup || !witness_vec || (!variables_hint && !placement) || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_from_dumps: null argument");
     unsigned log_n = 0, num_vars = 0, num_witness_cols = 0, num_public = 0;
     if (int rc = bj_setup_shape(setup, &log_n, &num_vars, &num_witness_cols, &num_public)) return rc;
     if ((num_witness_cols != 0) != (witness_hint != nullptr))
@@ -314,21 +372,11 @@ int bj_prove_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_
     // columns travel right behind the variable columns, as bj_prove_dev takes them
     const unsigned total_cols = num_vars + num_witness_cols;
     std::vector<const unsigned char *> hint_col(total_cols);
-    for (int which = 0; which < (num_witness_cols ? 2 : 1); which++) {
-        Reader h(which ? witness_hint : variables_hint, which ? witness_hint_len : variables_hint_len);
-        const char *what = which ? "DenseWitnessCopyHint" : "DenseVariablesCopyHint";
-        const unsigned want = which ? num_witness_cols : num_vars, first = which ? num_vars : 0;
-        const uint64_t hint_cols = h.u64v();
-        if (!h.ok || hint_cols != want)
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s dump: %llu columns, the circuit has %u", what, (unsigned long long)hint_cols, want);
-        for (unsigned c = 0; c < want; c++) {
-            const uint64_t len = h.u64v();
-            if (!h.ok || len != n) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s dump: column %u has %llu cells, not %zu", what, c, (unsigned long long)len, n);
-            hint_col[first + c] = h.skip(n * 8);
-            if (!hint_col[first + c]) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s dump: truncated", what);
-        }
-        if (h.p != h.end) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s dump: trailing bytes", what);
-    }
+    if (variables_hint)
+        if (int rc = read_copy_hint(ctx, "DenseVariablesCopyHint", variables_hint, variables_hint_len, num_vars, n, hint_col.data())) return rc;
+    if (num_witness_cols)
+        if (int rc = read_copy_hint(ctx, "DenseWitnessCopyHint", witness_hint, witness_hint_len, num_witness_cols, n, hint_col.data() + num_vars))
+            return rc;
     // cells on the device: all_values once, the hint in groups of columns, one gather per group
     DeviceBlock d_values, d_hint, d_cells, d_mult, d_bad;
     const unsigned G = 8;
@@ -339,12 +387,17 @@ int bj_prove_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_
     BJ_HIP(ctx, hipMalloc(&d_bad.p, 4));
     BJ_HIP(ctx, hipMemsetAsync(d_bad.p, 0, 4, ctx->stream));
     if (n_values) BJ_HIP(ctx, hipMemcpyAsync(d_values.p, values, n_values * 8, hipMemcpyHostToDevice, ctx->stream));
-    for (unsigned c0 = 0; c0 < total_cols; c0 += G) {
+    if (placement) {
+        const size_t count = (size_t)num_vars * n;
+        hipLaunchKernelGGL(materialize_cells_kernel<uint32_t>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, placement,
+                           (const u64 *)d_values.p, (size_t)n_values, (u64 *)d_cells.p, count, (unsigned *)d_bad.p);
+    }
+    for (unsigned c0 = placement ? num_vars : 0; c0 < total_cols; c0 += G) {
         const unsigned g = total_cols - c0 < G ? total_cols - c0 : G;
         for (unsigned k = 0; k < g; k++)
             BJ_HIP(ctx, hipMemcpyAsync((u64 *)d_hint.p + (size_t)k * n, hint_col[c0 + k], n * 8, hipMemcpyHostToDevice, ctx->stream));
         const size_t count = (size_t)g * n;
-        hipLaunchKernelGGL(materialize_cells_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, (const u64 *)d_hint.p,
+        hipLaunchKernelGGL(materialize_cells_kernel<u64>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, (const u64 *)d_hint.p,
                            (const u64 *)d_values.p, (size_t)n_values, (u64 *)d_cells.p + (size_t)c0 * n, count, (unsigned *)d_bad.p);
         BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the pageable source of the next group's copies is reused storage only for us
     }

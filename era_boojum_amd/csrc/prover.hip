@@ -109,6 +109,7 @@ struct bj_setup {
     u64 *d_tree = nullptr;         // local subtree
     u64 *d_non_res = nullptr;
     u64 *d_inv_xm1 = nullptr;      // 1 / (x - 1) on the points this GPU evaluates the quotient on (a property of the domain)
+    uint32_t *d_placement = nullptr;   // bj_setup_create_from_placement: variable index per cell [V][n], PLACEMENT_NONE = placeholder
     std::vector<u64> cap;
 };
 
@@ -264,6 +265,7 @@ void bj_setup_destroy(bj_setup *s) {
     if (s->d_tree) (void)hipFree(s->d_tree);
     if (s->d_non_res) (void)hipFree(s->d_non_res);
     if (s->d_inv_xm1) (void)hipFree(s->d_inv_xm1);
+    if (s->d_placement) (void)hipFree(s->d_placement);
     for (auto &p : s->programs) p.release();
     for (auto &g : s->spec) g.program.release();
     delete s;
@@ -276,10 +278,21 @@ int bj_setup_create(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, 
 
 int bj_setup_create_sharded(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const uint64_t *h_constants,
                             const uint64_t *h_tables, const bj_proof_config *cfg, const bj_comm *comm, bj_setup **out) {
+    return bj::setup_create_impl(ctx, c, h_sigmas, nullptr, h_constants, h_tables, cfg, comm, out);
+}
+
+}  // extern "C"
+
+void bj::setup_adopt_placement(bj_setup *s, uint32_t *d_placement) { s->d_placement = d_placement; }
+const uint32_t *bj::setup_placement(const bj_setup *s) { return s->d_placement; }
+
+int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const std::function<int(bj_setup *, u64 *)> &fill_sigmas,
+                          const uint64_t *h_constants, const uint64_t *h_tables, const bj_proof_config *cfg, const bj_comm *comm,
+                          bj_setup **out) {
     if (int rc = bj::bind(ctx)) return rc;
     if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: null out pointer");
     *out = nullptr;
-    if (!c || !cfg || !h_sigmas || !h_constants) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: null argument");
+    if (!c || !cfg || (!h_sigmas && !fill_sigmas) || !h_constants) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: null argument");
     if (c->log_n < 1 || c->log_n > 26) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: log_n out of range");
     if (c->num_gates == 0 || c->num_gates > 16 || !c->gates) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: 1..16 gates expected");
     if (!bj::is_pow2(c->quotient_degree) || !bj::is_pow2(cfg->fri_lde_factor) || cfg->fri_lde_factor < 2 ||
@@ -500,7 +513,7 @@ int bj_setup_create_sharded(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_
         hipMalloc((void **)&s->d_non_res, s->V * 8) != hipSuccess)
         return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_setup_create: device allocation failed"));
     // leaf order of the setup oracle: sigma || constants || tables (polynomial_storage.rs:667-676)
-    rc = bj_memcpy_h2d(ctx, s->d_nat, h_sigmas, (size_t)s->V * n * 8);
+    rc = fill_sigmas ? fill_sigmas(s, s->d_nat) : bj_memcpy_h2d(ctx, s->d_nat, h_sigmas, (size_t)s->V * n * 8);
     if (!rc) rc = bj_memcpy_h2d(ctx, s->d_nat + (size_t)s->V * n, h_constants, (size_t)s->nC * n * 8);
     if (!rc && nT) rc = bj_memcpy_h2d(ctx, s->d_nat + (size_t)(s->V + s->nC) * n, h_tables, (size_t)nT * n * 8);
     if (!rc) rc = bj_memcpy_h2d(ctx, s->d_non_res, s->non_residues.data(), s->V * 8);
@@ -534,6 +547,8 @@ int bj_setup_create_sharded(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_
     *out = s;
     return BJ_OK;
 }
+
+extern "C" {
 
 int bj_setup_shape(const bj_setup *s, unsigned *log_n, unsigned *num_vars, unsigned *num_witness_cols, unsigned *num_public_inputs) {
     if (s && num_public_inputs) *num_public_inputs = (unsigned)s->pub_cols.size();
@@ -588,6 +603,7 @@ int bj_setup_device_bytes(const bj_setup *s, size_t *bytes) {
     if (s->d_tree) b += bj_merkle_tree_digests(s->Nl, s->cap_l) * 32;
     if (s->d_non_res) b += (size_t)s->V * 8;
     if (s->d_inv_xm1) b += (n * s->q) / s->sh.world * 8;
+    if (s->d_placement) b += (size_t)s->V * n * 4;
     *bytes = b;
     return BJ_OK;
 }

@@ -438,6 +438,16 @@ int bj_gate_program_eval(bj_ctx *ctx, const bj_gate_program *program, const uint
 int bj_copy_perm_stage2(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, const uint64_t *d_sigmas, size_t sig_stride,
                         const uint64_t *h_non_residues, unsigned num_vars, unsigned chunk, unsigned log_n,
                         const uint64_t *h_beta, const uint64_t *h_gamma, uint64_t *d_z, uint64_t *d_partials);
+/* create_permutation_polys (src/cs/implementations/setup.rs:419-503) on the device: the copy-permutation polynomials from the
+ * variable placement.  d_placement [num_vars][n] in the encoding of DenseVariablesCopyHint (bit 63 = placeholder, low 48 bits =
+ * variable index), columns in bj_circuit order.  With the cells walked column-major (column major, row minor, placeholders
+ * skipped) and the cells of one variable c_0 < ... < c_{m-1}: sigma(c_i) = id(c_{i-1}), sigma(c_0) = id(c_{m-1}),
+ * id(col, row) = h_non_residues[col] * omega^row (omega: the 2^log_n domain generator of the transforms); a placeholder cell and
+ * the only cell of a variable keep their own id.  Out: d_sigmas [num_vars][n] at sig_stride, canonical.  The placement is not
+ * modified; the work (a stable radix sort of the cells by variable, one scatter pass) runs in the context's scratch.
+ * Limits, BJ_ERR_UNSUPPORTED with a message: variable indices up to 2^32 - 2, num_vars * n < 2^32, log_n <= 30. */
+int bj_sigmas_from_placement(bj_ctx *ctx, const uint64_t *d_placement, size_t place_stride, unsigned num_vars, unsigned log_n,
+                             const uint64_t *h_non_residues, uint64_t *d_sigmas, size_t sig_stride);
 /* compute_lookup_poly_pairs_specialized (src/cs/implementations/lookup_argument_in_ext.rs:320-700): A_i = 1 / (beta +
  * sum_j gamma^j col_ij + gamma^width table_id), B = multiplicity / (beta + sum_j gamma^j table_j) per row.
  * d_lookup_vars [reps*width][n], d_tables [width+1][n]; out d_A [reps][2][n], d_B [2][n].
@@ -626,7 +636,8 @@ int bj_comm_replay_captured(const bj_comm *comm, size_t *bytes);
 void bj_setup_destroy(bj_setup *s);
 int bj_setup_cap(const bj_setup *s, uint64_t *h_cap); /* vk.setup_merkle_tree_cap: cap_size*4 u64 */
 /* HBM held by a setup (its shard on a sharded setup): natural-order columns, monomials, the LDE of the cosets it owns, its
- * Merkle subtree, 1 / (x - 1) on its quotient points — the "per rank" column of DESIGN.md §6's memory table. */
+ * Merkle subtree, 1 / (x - 1) on its quotient points — the "per rank" column of DESIGN.md §6's memory table — and the u32
+ * placement of a setup made by bj_setup_create_from_placement. */
 int bj_setup_device_bytes(const bj_setup *s, size_t *bytes);
 int bj_setup_shape(const bj_setup *s, unsigned *log_n, unsigned *num_vars, unsigned *num_witness_cols,
                    unsigned *num_public_inputs); /* any out pointer may be NULL */
@@ -641,6 +652,15 @@ int bj_setup_shape(const bj_setup *s, unsigned *log_n, unsigned *num_vars, unsig
  * field is 0 (from the tree's depth + degree), non_residues when the pointer is NULL (make_non_residues, utils.rs:636-688). */
 int bj_setup_create_from_dump(bj_ctx *ctx, const bj_circuit *circuit, const void *setup_base, size_t setup_base_len,
                               const bj_proof_config *config, bj_setup **out);
+/* bj_setup_create without create_permutation_polys on the host: `variables_hint` is the DenseVariablesCopyHint dump
+ * (copy_permutation_data, the bytes bj_prove_from_dumps takes: circuit->num_vars columns of n cells).  The hint goes to the
+ * device in column groups, sigma is built there (bj_sigmas_from_placement, with circuit->non_residues, same limits) and the
+ * setup continues as bj_setup_create does from host sigmas: same monomials, LDEs, tree and cap.  The setup keeps the placement
+ * in HBM as u32 indices (0xFFFFFFFF = placeholder, 4 bytes per cell, counted by bj_setup_device_bytes), so that
+ * bj_prove_from_dumps needs no hint.  Single device only: a sharded host runs bj_sigmas_from_placement, reads the columns
+ * back and calls bj_setup_create_sharded. */
+int bj_setup_create_from_placement(bj_ctx *ctx, const bj_circuit *circuit, const void *variables_hint, size_t variables_hint_len,
+                                   const uint64_t *h_constants, const uint64_t *h_tables, const bj_proof_config *config, bj_setup **out);
 /* What a SetupBaseStorage dump holds, without a device: info8 = {rows n, copy-permutation polynomials, constant columns, table
  * columns, table-id columns, first table-id column, gate indices named by the selector tree (highest + 1), max (depth + degree)
  * in the low word | longest selector path << 32}.  BJ_ERR_INVALID_ARG for bytes that do not parse.  Host-only. */
@@ -648,7 +668,9 @@ int bj_setup_dump_info(const void *setup_base, size_t setup_base_len, uint64_t *
 /* witness_set_from_witness_vec (witness.rs:386-443) on the device — cell = all_values[hint & (2^48 - 1)], 0 where bit 63 marks a
  * placeholder; multiplicities zero-extended to the trace (witness.rs:225-272); public input values read from their cells — then
  * bj_prove_dev.  witness_hint: the DenseWitnessCopyHint dump (hints/mod.rs:17-21; same layout and indexing) when the circuit has
- * non-copiable witness columns, NULL / 0 otherwise. */
+ * non-copiable witness columns, NULL / 0 otherwise.  variables_hint may be NULL (length 0) only for a setup made by
+ * bj_setup_create_from_placement: the variable columns are then gathered through the placement the setup holds, and a proof
+ * needs all_values alone; for any other setup a NULL hint is BJ_ERR_INVALID_ARG. */
 int bj_prove_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_vec, size_t witness_vec_len,
                         const void *variables_hint, size_t variables_hint_len, const void *witness_hint, size_t witness_hint_len,
                         bj_proof **out);
