@@ -1,6 +1,7 @@
 """ctypes binding of include/boojum_hip.h.  Device buffers are plain integer addresses (e.g. ``tensor.data_ptr()``)."""
 import ctypes as C
 import os
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -119,6 +120,9 @@ _SIGNATURES = {
                                                  C.POINTER(C.c_void_p)]),
     "bj_prove_from_dumps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
                                       C.POINTER(C.c_void_p)]),
+    "bj_check_satisfied": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bj_check_satisfied_from_dumps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
+                                                C.c_void_p]),
     "bj_proof_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bj_proof_workspace_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "bj_proof_kernel_stats": (C.c_int, [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -958,6 +962,42 @@ class PeerComm:
             pass
 
 
+class _UnsatReport(C.Structure):  # bj_unsat_report
+    _fields_ = [("kind", C.c_uint32), ("gate", C.c_uint32), ("repetition", C.c_uint32), ("term", C.c_uint32), ("row", C.c_uint64),
+                ("value", C.c_uint64), ("expected", C.c_uint64), ("failures", C.c_uint64 * 5)]
+
+
+SAT, UNSAT_GATE, UNSAT_SPECIALIZED_GATE, UNSAT_LOOKUP, UNSAT_MULTIPLICITY = range(5)     # bj_unsat_kind
+
+
+@dataclass
+class SatisfiabilityReport:
+    """bj_unsat_report: the first failure of a witness (order: include/boojum_hip.h) and the number of failures per kind.
+    True when the witness satisfies the circuit; str() is worded like the panic of the reference's check_if_satisfied."""
+    kind: int = SAT
+    gate: int = 0
+    repetition: int = 0
+    term: int = 0
+    row: int = 0
+    value: int = 0
+    expected: int = 0
+    failures: tuple = (0, 0, 0, 0, 0)
+    gate_name: str = ""
+
+    def __bool__(self):
+        return self.kind == SAT
+
+    def __str__(self):
+        if self.kind == SAT:
+            return "Satisfied"
+        if self.kind in (UNSAT_GATE, UNSAT_SPECIALIZED_GATE):
+            return "Unsatisfied at row %d with value %d for term number %d for subinstance number %d of gate %s" % (
+                self.row, self.value, self.term, self.repetition, self.gate_name or "#%d" % self.gate)
+        if self.kind == UNSAT_LOOKUP:
+            return "Unsatisfied at row %d: the tuple of lookup sub-argument %d is in no table row" % (self.row, self.gate)
+        return "Unsatisfied at table row %d: multiplicities sum to %d, %d lookups" % (self.row, self.expected, self.value)
+
+
 class _Ticket:
     """A proof in flight (bj_ticket) + the host arrays it reads."""
 
@@ -1161,6 +1201,49 @@ class ProverSetup:
         h = C.c_void_p()
         self._ctx._check(self._lib.bj_prove_from_dumps(self._ctx._h, self._h, w, len(w), v, len(v) if v else 0, x, len(x) if x else 0, C.byref(h)))
         return self._finish(h)
+
+    def _report(self, r):
+        c, name = self.circuit, ""
+        if r.kind == UNSAT_GATE:
+            name = c.gates[r.gate].name
+        elif r.kind == UNSAT_SPECIALIZED_GATE:
+            name = c.specialized_gates[r.gate].name
+        return SatisfiabilityReport(int(r.kind), int(r.gate), int(r.repetition), int(r.term), int(r.row), int(r.value), int(r.expected),
+                                    tuple(int(x) for x in r.failures), name)
+
+    def check_satisfied_dev(self, d_variables, d_multiplicities):
+        """bj_check_satisfied on a witness already in HBM ([num_vars + num_witness_cols][n], multiplicities [n] or None)."""
+        r = _UnsatReport()
+        self._ctx._check(self._lib.bj_check_satisfied(self._ctx._h, self._h, d_variables, d_multiplicities, C.byref(r)))
+        return self._report(r)
+
+    def check_satisfied(self, variables=None, multiplicities=None):
+        """Where the witness fails the circuit (bj_check_satisfied): a SatisfiabilityReport, true when it does not.  Arrays default
+        to the circuit's own and are uploaded for the call."""
+        c = self.circuit
+        v = np.ascontiguousarray(c.variables if variables is None else variables, dtype=np.uint64)
+        if self.num_witness_cols and v.shape[0] == c.num_vars:
+            v = np.ascontiguousarray(np.concatenate([v, c.witness], axis=0))
+        d_v = self._ctx.upload(v)
+        d_m = None
+        try:
+            if c.lookup_reps:
+                d_m = self._ctx.upload(np.ascontiguousarray(c.multiplicities if multiplicities is None else multiplicities, dtype=np.uint64))
+            return self.check_satisfied_dev(d_v, d_m)
+        finally:
+            self._ctx.free(d_v)
+            if d_m is not None:
+                self._ctx.free(d_m)
+
+    def check_satisfied_from_dumps(self, witness_vec_dump, variables_hint_dump, witness_hint_dump=None):
+        """bj_check_satisfied_from_dumps: the arguments of prove_from_dumps, the report of check_satisfied."""
+        w = bytes(witness_vec_dump)
+        v = bytes(variables_hint_dump) if variables_hint_dump is not None else None
+        x = bytes(witness_hint_dump) if witness_hint_dump is not None else None
+        r = _UnsatReport()
+        self._ctx._check(self._lib.bj_check_satisfied_from_dumps(self._ctx._h, self._h, w, len(w), v, len(v) if v else 0, x, len(x) if x else 0,
+                                                                 C.byref(r)))
+        return self._report(r)
 
     def prove_dev(self, d_variables, d_multiplicities, public_values=None):
         """Witness already in HBM (bj_prove_dev)."""

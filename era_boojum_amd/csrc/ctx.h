@@ -125,6 +125,11 @@ int setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas
                       const uint64_t *h_constants, const uint64_t *h_tables, const bj_proof_config *cfg, const bj_comm *comm, bj_setup **out);
 void setup_adopt_placement(bj_setup *s, uint32_t *d_placement);   // [num_vars][n] u32, hipMalloc'ed
 const uint32_t *setup_placement(const bj_setup *s);               // nullptr unless created from a placement
+// dumps.hip: WitnessVec + copy-hint dumps -> [num_vars + num_witness_cols][n] cells, [n] multiplicities (device) and the public
+// input values (host), handed to `use` and freed when it returns; variables_hint may be NULL for a setup that holds its placement
+int witness_from_dumps(bj_ctx *ctx, const char *who, const bj_setup *setup, const void *witness_vec, size_t witness_vec_len,
+                       const void *variables_hint, size_t variables_hint_len, const void *witness_hint, size_t witness_hint_len,
+                       const std::function<int(const uint64_t *d_cells, const uint64_t *d_mult, const uint64_t *h_public)> &use);
 inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 inline unsigned log2_exact(size_t x) {
     unsigned r = 0;

@@ -336,18 +336,21 @@ int bj_setup_create_from_placement(bj_ctx *ctx, const bj_circuit *circuit, const
     return bj::setup_create_impl(ctx, circuit, nullptr, fill, h_constants, h_tables, config, nullptr, out);
 }
 
-int bj_prove_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_vec, size_t witness_vec_len,
-                        const void *variables_hint, size_t variables_hint_len, const void *witness_hint, size_t witness_hint_len,
-                        bj_proof **out) {
-    if (int rc = bj::bind(ctx)) return rc;
+}  // extern "C"
+
+// The reader and the gather of the from-dumps entry points (bj_prove_from_dumps, bj_check_satisfied_from_dumps): WitnessVec +
+// copy hints -> the witness columns, the multiplicities and the public input values, resident for the duration of `use`.
+int bj::witness_from_dumps(bj_ctx *ctx, const char *who, const bj_setup *setup, const void *witness_vec, size_t witness_vec_len,
+                           const void *variables_hint, size_t variables_hint_len, const void *witness_hint, size_t witness_hint_len,
+                           const std::function<int(const uint64_t *, const uint64_t *, const uint64_t *)> &use) {
     // no DenseVariablesCopyHint: the setup must hold the placement itself (bj_setup_create_from_placement)
     const uint32_t *placement = setup && !variables_hint ? bj::setup_placement(setup) : nullptr;
-    if (!setup || !witness_vec || (!variables_hint && !placement) || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_from_dumps: null argument");
+    if (!setup || !witness_vec || (!variables_hint && !placement)) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: null argument", who);
     unsigned log_n = 0, num_vars = 0, num_witness_cols = 0, num_public = 0;
     if (int rc = bj_setup_shape(setup, &log_n, &num_vars, &num_witness_cols, &num_public)) return rc;
     if ((num_witness_cols != 0) != (witness_hint != nullptr))
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_from_dumps: the setup has %u non-copiable witness columns: a DenseWitnessCopyHint "
-                        "dump is %s", num_witness_cols, num_witness_cols ? "required" : "not expected");
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: the setup has %u non-copiable witness columns: a DenseWitnessCopyHint "
+                        "dump is %s", who, num_witness_cols, num_witness_cols ? "required" : "not expected");
     const size_t n = (size_t)1 << log_n;
     Reader w(witness_vec, witness_vec_len);
     const uint64_t n_pub = w.u64v();
@@ -419,7 +422,16 @@ int bj_prove_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_
         if (pub_col[i] >= num_vars || pub_row[i] >= n) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "WitnessVec dump: public input %llu outside the trace", (unsigned long long)i);
         BJ_HIP(ctx, hipMemcpy(&pub[i], (u64 *)d_cells.p + pub_col[i] * n + pub_row[i], 8, hipMemcpyDeviceToHost));
     }
-    return bj_prove_dev(ctx, setup, (const u64 *)d_cells.p, (const u64 *)d_mult.p, pub.data(), out);
+    return use((const u64 *)d_cells.p, (const u64 *)d_mult.p, pub.data());
 }
 
-}  // extern "C"
+extern "C" int bj_prove_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_vec, size_t witness_vec_len,
+                                   const void *variables_hint, size_t variables_hint_len, const void *witness_hint, size_t witness_hint_len,
+                                   bj_proof **out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_from_dumps: null argument");
+    return bj::witness_from_dumps(ctx, "bj_prove_from_dumps", setup, witness_vec, witness_vec_len, variables_hint, variables_hint_len, witness_hint,
+                                  witness_hint_len, [&](const uint64_t *d_cells, const uint64_t *d_mult, const uint64_t *h_pub) {
+                                      return bj_prove_dev(ctx, setup, d_cells, d_mult, h_pub, out);
+                                  });
+}

@@ -12,6 +12,7 @@
 #include "host_transcript.hpp"
 #include "fri_types.h"
 #include "gate_program.h"
+#include "setup.h"
 
 #include <chrono>
 #include <cstring>
@@ -69,49 +70,6 @@ struct DeepSetHost {
 int deep_accumulate_multi(bj_ctx *ctx, const DeepSetHost *sets, unsigned n_sets, unsigned log_n, unsigned log_lde, size_t N_local,
                           size_t I0, uint64_t *d_dst_c0, uint64_t *d_dst_c1, int accumulate);
 }  // namespace bj
-
-struct bj_setup {
-    int device = 0;
-    // circuit
-    unsigned log_n = 0, V = 0, num_gp_vars = 0, nC = 0, lookup_w = 0, lookup_reps = 0, table_id_col = 0, q = 0;
-    unsigned Wc = 0;               // non-copiable witness columns (behind the V variable columns in the witness oracle)
-    bool tid_var = false;          // UseSpecializedColumnsWithTableIdAsVariable: the table id is the last of lookup_cps = lookup_w + 1
-    unsigned lookup_cps = 0;       // variable columns of a sub-argument (specialized_columns_per_subargument, cs/mod.rs:300-312)
-    std::vector<unsigned> gate_wit_stride;   // per general-purpose gate: per_chunk_offset.witnesses_offset
-    std::vector<int> gates_flat;   // 12 ints per gate
-    std::vector<bj::DevProgram> programs;   // per gate; empty (block == nullptr) unless kind == BJ_GATE_PROGRAM
-    unsigned n_gates = 0;
-    struct SpecGate {                        // a gate over specialized columns: op list, no selector, own columns
-        bj::DevProgram program;
-        unsigned reps = 0, width = 0, terms = 0, first_col = 0;
-        unsigned first_const = 0, const_width = 0;   // its constant columns: reps * const_width of them from first_const on
-    };
-    std::vector<SpecGate> spec;
-    unsigned n_spec_terms = 0;
-    std::vector<u64> non_residues;
-    bool small_non_residues = false;   // every k_c < 2^32 (canonical): quotient_copy_perm multiplies by them as 32-bit integers
-    std::vector<unsigned> pub_cols, pub_rows;
-    // proof config
-    unsigned fri_lde = 0, cap_size = 0, security = 0, pow_bits = 0, transcript = BJ_TRANSCRIPT_POSEIDON2, hasher = BJ_HASHER_POSEIDON2;
-    unsigned pow_runner = BJ_POW_BLAKE2S256;   // the POW type parameter of prove_cpu_basic (pow.rs:6-31)
-    unsigned L = 0, log_L = 0, log_fri = 0, log_q = 0;
-    unsigned n_cols = 0;           // V sigmas + nC constants + (w+1) tables
-    // shard of the LDE domain held by this GPU: cosets [c0, c0 + cl), i.e. flat indices [c0*n, (c0+cl)*n)
-    bj::Shard sh;
-    unsigned c0 = 0, cl = 0;
-    size_t Ls = 0;                 // column stride of every LDE array = cl * n
-    size_t Nl = 0;                 // Merkle leaves held here (n * fri_lde / world)
-    size_t cap_l = 0;              // cap nodes of the local subtree (cap_size / world)
-    u64 *d_nat = nullptr;          // [n_cols][n] natural-order values (replicated)
-    u64 *d_mono = nullptr;         // [n_cols][n] monomial forms (replicated; the DEEP numerator is combined on them)
-    bool tiled = false;            // monomials (these and every proof's) in the tiled layout of ntt_r16.hip: 2^22-row traces
-    u64 *d_lde = nullptr;          // [n_cols][cl][n]
-    u64 *d_tree = nullptr;         // local subtree
-    u64 *d_non_res = nullptr;
-    u64 *d_inv_xm1 = nullptr;      // 1 / (x - 1) on the points this GPU evaluates the quotient on (a property of the domain)
-    uint32_t *d_placement = nullptr;   // bj_setup_create_from_placement: variable index per cell [V][n], PLACEMENT_NONE = placeholder
-    std::vector<u64> cap;
-};
 
 struct bj_proof {
     std::vector<u64> data;
@@ -637,6 +595,66 @@ int bj_prove_dev(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, co
 
 }  // extern "C"
 
+namespace bj {
+// Every gate evaluator of the circuit over `points` points of caller-given columns (the quotient stage runs it on the LDE, the
+// satisfiability check on the trace itself): GATES_GENERAL OVERWRITES (t0, t1) with the hand-written kinds' sum and adds the
+// Poseidon evaluators and the op-list gates over general-purpose columns; GATES_SPECIALIZED ADDS the gates over specialized
+// columns.  a_gates / a_spec: one F_p^2 power per (gate, repetition, term) in evaluator order.
+void launch_circuit_gates(bj_ctx *ctx, const bj_setup *S, const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
+                          size_t points, const u64 *a_gates, const u64 *a_spec, u64 *t0, u64 *t1, hipStream_t st, unsigned parts) {
+    if (parts & GATES_GENERAL) {
+        // gate evaluation, SURVEY §8d: 8 (V + consts) qn + 16 qn — V = the general-purpose columns the gates read
+        const int pg = bj::probe_begin(ctx, "quotient_gates", 8.0 * (S->num_gp_vars + S->nC) * (double)points + 16.0 * (double)points);
+        bj::launch_quotient_gates(d_vars, var_stride, d_consts, const_stride, S->gates_flat.data(), S->n_gates, a_gates, points, t0, t1, st);
+        bj::probe_end(ctx, pg);
+        unsigned aoff = 0;   // op-list gates (seam S3) add their contribution on top, with their own slice of alpha powers
+        std::vector<bj::GateLaunch> prog_gates;
+        for (unsigned g = 0; g < S->n_gates; g++) {
+            const int *f = S->gates_flat.data() + 12 * g;
+            if (f[0] == BJ_GATE_POSEIDON2_FLATTENED) {
+                unsigned char path[8] = {0};
+                for (int b = 0; b < f[1]; b++) path[b] = (unsigned char)f[6 + b];
+                bj::launch_quotient_poseidon2_flattened(d_vars, var_stride, d_consts, const_stride, (unsigned)f[1], path,
+                                                        a_gates + 2 * (size_t)aoff, points, t0, t1, st);
+            }
+            if (f[0] == BJ_GATE_POSEIDON_FLATTENED) {
+                unsigned char path[8] = {0};
+                for (int b = 0; b < f[1]; b++) path[b] = (unsigned char)f[6 + b];
+                bj::launch_quotient_poseidon_flattened(d_vars, var_stride, d_consts, const_stride, (unsigned)f[1], path,
+                                                       a_gates + 2 * (size_t)aoff, points, t0, t1, st);
+            }
+            if (f[0] == BJ_GATE_PROGRAM) {
+                bj::GateLaunch L{};
+                L.program = &S->programs[g];
+                L.path_len = (unsigned)f[1];
+                for (int b = 0; b < f[1]; b++) L.path[b] = (unsigned char)f[6 + b];
+                L.reps = (unsigned)f[2];
+                L.rep_var_stride = (unsigned)f[3];
+                L.rep_const_stride = (unsigned)f[4];
+                L.rep_wit_stride = S->gate_wit_stride[g];
+                L.d_alphas = a_gates + 2 * (size_t)aoff;
+                prog_gates.push_back(L);
+            }
+            aoff += (unsigned)(f[2] * f[5]);
+        }
+        // the op-list gates: one fused launch for those with generated bodies (they all sweep the general-purpose columns)
+        bj::launch_gate_programs(prog_gates.data(), (unsigned)prog_gates.size(), d_vars, var_stride, d_consts, const_stride, points, t0, t1, st,
+                                 S->Wc ? d_vars + (size_t)S->V * var_stride : nullptr);
+    }
+    if (parts & GATES_SPECIALIZED) {
+        unsigned soff = 0;   // gates over specialized columns: every row, no selector
+        const unsigned char no_path[8] = {0};
+        for (const auto &sg : S->spec) {
+            bj::launch_gate_program(sg.program, d_vars + (size_t)sg.first_col * var_stride, var_stride,
+                                    d_consts + (size_t)sg.first_const * const_stride, const_stride, 0, no_path, sg.reps, sg.width,
+                                    sg.const_width, a_spec + 2 * (size_t)soff, points, t0, t1, nullptr, st);
+            soff += sg.reps * sg.terms;
+        }
+    }
+}
+}  // namespace bj
+
+
 namespace {
 int prove_impl(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, const uint64_t *d_multiplicities,
                const uint64_t *h_public_values, bj_proof **out, const HostWitness *hw) {
@@ -918,52 +936,9 @@ int prove_impl(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, cons
     const u64 *a_lookup = d_alphas.p, *a_spec = d_alphas.p + 2 * n_lookup_terms, *a_gates = a_spec + 2 * n_spec_terms,
               *a_l1 = a_gates + 2 * n_gate_terms;
     const u64 *d_sig_lde = S->d_lde, *d_con_lde = S->d_lde + (size_t)V * Ln, *d_tab_lde = S->d_lde + (size_t)(V + nC) * Ln;
-    if (Qe) {
-        // gate evaluation, SURVEY §8d: 8 (V + consts) qn + 16 qn — V = the general-purpose columns the gates read
-        const int pg = bj::probe_begin(ctx, "quotient_gates", 8.0 * (S->num_gp_vars + nC) * (double)Qe + 16.0 * (double)Qe);
-        bj::launch_quotient_gates(wit_lde.p, Ln, d_con_lde, Ln, S->gates_flat.data(), S->n_gates, a_gates, Qe, t0, t1, st);
-        bj::probe_end(ctx, pg);
-        unsigned aoff = 0;   // op-list gates (seam S3) add their contribution on top, with their own slice of alpha powers
-        std::vector<bj::GateLaunch> prog_gates;
-        for (unsigned g = 0; g < S->n_gates; g++) {
-            const int *f = S->gates_flat.data() + 12 * g;
-            if (f[0] == BJ_GATE_POSEIDON2_FLATTENED) {
-                unsigned char path[8] = {0};
-                for (int b = 0; b < f[1]; b++) path[b] = (unsigned char)f[6 + b];
-                bj::launch_quotient_poseidon2_flattened(wit_lde.p, Ln, d_con_lde, Ln, (unsigned)f[1], path, a_gates + 2 * (size_t)aoff,
-                                                        Qe, t0, t1, st);
-            }
-            if (f[0] == BJ_GATE_POSEIDON_FLATTENED) {
-                unsigned char path[8] = {0};
-                for (int b = 0; b < f[1]; b++) path[b] = (unsigned char)f[6 + b];
-                bj::launch_quotient_poseidon_flattened(wit_lde.p, Ln, d_con_lde, Ln, (unsigned)f[1], path, a_gates + 2 * (size_t)aoff,
-                                                       Qe, t0, t1, st);
-            }
-            if (f[0] == BJ_GATE_PROGRAM) {
-                bj::GateLaunch L{};
-                L.program = &S->programs[g];
-                L.path_len = (unsigned)f[1];
-                for (int b = 0; b < f[1]; b++) L.path[b] = (unsigned char)f[6 + b];
-                L.reps = (unsigned)f[2];
-                L.rep_var_stride = (unsigned)f[3];
-                L.rep_const_stride = (unsigned)f[4];
-                L.rep_wit_stride = S->gate_wit_stride[g];
-                L.d_alphas = a_gates + 2 * (size_t)aoff;
-                prog_gates.push_back(L);
-            }
-            aoff += (unsigned)(f[2] * f[5]);
-        }
-        // the op-list gates: one fused launch for those with generated bodies (they all sweep the general-purpose columns)
-        bj::launch_gate_programs(prog_gates.data(), (unsigned)prog_gates.size(), wit_lde.p, Ln, d_con_lde, Ln, Qe, t0, t1, st,
-                                 S->Wc ? wit_lde.p + (size_t)V * Ln : nullptr);
-        unsigned soff = 0;   // gates over specialized columns: every row, no selector
-        const unsigned char no_path[8] = {0};
-        for (const auto &sg : S->spec) {
-            bj::launch_gate_program(sg.program, wit_lde.p + (size_t)sg.first_col * Ln, Ln, d_con_lde + (size_t)sg.first_const * Ln, Ln, 0,
-                                    no_path, sg.reps, sg.width, sg.const_width, a_spec + 2 * (size_t)soff, Qe, t0, t1, nullptr, st);
-            soff += sg.reps * sg.terms;
-        }
-    }
+    if (Qe)
+        bj::launch_circuit_gates(ctx, S, wit_lde.p, Ln, d_con_lde, Ln, Qe, a_gates, a_spec, t0, t1, st,
+                                 bj::GATES_GENERAL | bj::GATES_SPECIALIZED);
     if (has_lookup && Qe) {
         const u64 *dA = s2_lde.p + (size_t)(2 + 2 * n_part) * Ln, *dB = dA + (size_t)2 * S->lookup_reps * Ln;
         bj::launch_quotient_lookup(wit_lde.p + (size_t)S->num_gp_vars * Ln, Ln, S->tid_var ? nullptr : d_con_lde + (size_t)S->table_id_col * Ln, d_tab_lde,

@@ -1,0 +1,60 @@
+// Internal: the setup object behind the opaque `bj_setup` of include/boojum_hip.h, shared by prover.hip (which creates and
+// proves with it) and check_satisfied.hip (which only reads the replicated natural-order columns and the gate list).
+#pragma once
+#include "ctx.h"
+#include "fri_types.h"
+#include "gate_program.h"
+
+#include <vector>
+
+struct bj_setup {
+    int device = 0;
+    // circuit
+    unsigned log_n = 0, V = 0, num_gp_vars = 0, nC = 0, lookup_w = 0, lookup_reps = 0, table_id_col = 0, q = 0;
+    unsigned Wc = 0;               // non-copiable witness columns (behind the V variable columns in the witness oracle)
+    bool tid_var = false;          // UseSpecializedColumnsWithTableIdAsVariable: the table id is the last of lookup_cps = lookup_w + 1
+    unsigned lookup_cps = 0;       // variable columns of a sub-argument (specialized_columns_per_subargument, cs/mod.rs:300-312)
+    std::vector<unsigned> gate_wit_stride;   // per general-purpose gate: per_chunk_offset.witnesses_offset
+    std::vector<int> gates_flat;   // 12 ints per gate
+    std::vector<bj::DevProgram> programs;   // per gate; empty (block == nullptr) unless kind == BJ_GATE_PROGRAM
+    unsigned n_gates = 0;
+    struct SpecGate {                        // a gate over specialized columns: op list, no selector, own columns
+        bj::DevProgram program;
+        unsigned reps = 0, width = 0, terms = 0, first_col = 0;
+        unsigned first_const = 0, const_width = 0;   // its constant columns: reps * const_width of them from first_const on
+    };
+    std::vector<SpecGate> spec;
+    unsigned n_spec_terms = 0;
+    std::vector<gl::u64> non_residues;
+    bool small_non_residues = false;   // every k_c < 2^32 (canonical): quotient_copy_perm multiplies by them as 32-bit integers
+    std::vector<unsigned> pub_cols, pub_rows;
+    // proof config
+    unsigned fri_lde = 0, cap_size = 0, security = 0, pow_bits = 0, transcript = BJ_TRANSCRIPT_POSEIDON2, hasher = BJ_HASHER_POSEIDON2;
+    unsigned pow_runner = BJ_POW_BLAKE2S256;   // the POW type parameter of prove_cpu_basic (pow.rs:6-31)
+    unsigned L = 0, log_L = 0, log_fri = 0, log_q = 0;
+    unsigned n_cols = 0;           // V sigmas + nC constants + (w+1) tables
+    // shard of the LDE domain held by this GPU: cosets [c0, c0 + cl), i.e. flat indices [c0*n, (c0+cl)*n)
+    bj::Shard sh;
+    unsigned c0 = 0, cl = 0;
+    size_t Ls = 0;                 // column stride of every LDE array = cl * n
+    size_t Nl = 0;                 // Merkle leaves held here (n * fri_lde / world)
+    size_t cap_l = 0;              // cap nodes of the local subtree (cap_size / world)
+    gl::u64 *d_nat = nullptr;          // [n_cols][n] natural-order values (replicated)
+    gl::u64 *d_mono = nullptr;         // [n_cols][n] monomial forms (replicated; the DEEP numerator is combined on them)
+    bool tiled = false;            // monomials (these and every proof's) in the tiled layout of ntt_r16.hip: 2^22-row traces
+    gl::u64 *d_lde = nullptr;          // [n_cols][cl][n]
+    gl::u64 *d_tree = nullptr;         // local subtree
+    gl::u64 *d_non_res = nullptr;
+    gl::u64 *d_inv_xm1 = nullptr;      // 1 / (x - 1) on the points this GPU evaluates the quotient on (a property of the domain)
+    uint32_t *d_placement = nullptr;   // bj_setup_create_from_placement: variable index per cell [V][n], PLACEMENT_NONE = placeholder
+    std::vector<gl::u64> cap;
+};
+
+
+namespace bj {
+enum : unsigned { GATES_GENERAL = 1, GATES_SPECIALIZED = 2 };
+// prover.hip: every gate evaluator of the setup's circuit over `points` points of caller-given columns
+void launch_circuit_gates(bj_ctx *ctx, const bj_setup *S, const gl::u64 *d_vars, size_t var_stride, const gl::u64 *d_consts,
+                          size_t const_stride, size_t points, const gl::u64 *a_gates, const gl::u64 *a_spec, gl::u64 *t0, gl::u64 *t1,
+                          hipStream_t st, unsigned parts);
+}  // namespace bj

@@ -684,6 +684,53 @@ int bj_prove(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_variables, co
 /* same with the witness already resident in HBM ([num_vars + num_witness_cols][n] contiguous; not modified) */
 int bj_prove_dev(bj_ctx *ctx, const bj_setup *setup, const uint64_t *d_variables, const uint64_t *d_multiplicities,
                  const uint64_t *h_public_values, bj_proof **out);
+/* ---- where a witness fails: CSReferenceAssembly::check_if_satisfied (src/cs/implementations/satisfiability_test.rs:15-353) ----
+ * bj_prove refuses an unsatisfied witness only after the quotient stage and names nothing; a wrong lookup or multiplicity it
+ * does not notice at all.  bj_check_satisfied evaluates every term of every gate on its rows and both sides of the lookup
+ * argument, on the setup's replicated natural-order columns, and names the FIRST failure in this order (the reference's,
+ * extended to lookups):
+ *   1. BJ_UNSAT_GATE by ascending row; within the row the one selected gate, then ascending repetition, then ascending term;
+ *   2. BJ_UNSAT_SPECIALIZED_GATE by ascending row, then gate in declaration order, then repetition, then term;
+ *   3. BJ_UNSAT_LOOKUP by ascending row, then sub-argument: the looked-up tuple (with its table id) equals no table row;
+ *   4. BJ_UNSAT_MULTIPLICITY by ascending table row.  Equal table rows (the all-zero padding rows among them) form a class, named
+ *      by its smallest row: the sum of the class's multiplicities, as a field element, must be the number of looked-up tuples
+ *      equal to it.
+ * `kind` is the first category with any failure; failures[] is filled for all four whatever `kind` is.
+ * Gate rows are found with ONE pass of the prover's evaluators over the n rows under a random linear combination: term k (in
+ * evaluator order: general-purpose gates, repetition-major, then the gates over specialized columns) is weighted by the F_p^2
+ * element (x_2k, x_2k+1), x_i = SplitMix64 output i from the state 0x626A5F636865636B ("bj_check"), reduced mod p.  A row with
+ * a non-zero term is missed with probability at most 1/p^2 (< 2^-127) for independent weights; the weights are fixed, so a
+ * witness built against them is not covered: this is a diagnosis, not a proof.  What is REPORTED is exact: the named row is
+ * evaluated again term by term with unit weights, and the lookup part involves no randomness.
+ * NOT checked: copy constraints.  They hold by construction for a witness gathered through a placement (bj_*_from_dumps), the
+ * reference's checker does not test them either, and raw columns that break them keep bj_prove's refusal.
+ * Arguments as for bj_prove_dev / bj_prove_from_dumps (values canonical or not; d_multiplicities NULL only without lookups);
+ * nothing is modified.  Runs on the context's stream, in the context's scratch, and synchronises; a proof made afterwards is
+ * byte for byte the proof made before.  Works on a sharded setup (replicated columns only, no communication).  Not while a
+ * proof runs on the context.  Returns BJ_OK whenever the check ran — the verdict is in *out. */
+typedef enum bj_unsat_kind {
+    BJ_SAT = 0,
+    BJ_UNSAT_GATE = 1,              /* evaluator over general-purpose columns   */
+    BJ_UNSAT_SPECIALIZED_GATE = 2,  /* evaluator over specialized columns       */
+    BJ_UNSAT_LOOKUP = 3,            /* a looked-up tuple is in no table row     */
+    BJ_UNSAT_MULTIPLICITY = 4       /* a table row's multiplicity is not its count */
+} bj_unsat_kind;
+typedef struct bj_unsat_report {
+    uint32_t kind;        /* first failure in the order above; BJ_SAT if none */
+    uint32_t gate;        /* 1: index into bj_circuit.gates; 2: into specialized_gates; 3: sub-argument; 4: 0 */
+    uint32_t repetition;  /* 1, 2: sub-instance (chunk_idx of the reference's message); else 0 */
+    uint32_t term;        /* 1, 2: term number inside the repetition; else 0 */
+    uint64_t row;         /* 1-3: trace row; 4: smallest table row of the class */
+    uint64_t value;       /* 1, 2: the term's canonical value; 4: number of looked-up tuples equal to that row; 3: 0 */
+    uint64_t expected;    /* 4: sum of the class's multiplicities (canonical field element); else 0 */
+    uint64_t failures[5]; /* per kind: 1, 2 rows with a non-zero term; 3 (row, sub-argument) pairs; 4 classes; [0] unused */
+} bj_unsat_report;
+int bj_check_satisfied(bj_ctx *ctx, const bj_setup *setup, const uint64_t *d_variables, const uint64_t *d_multiplicities,
+                       bj_unsat_report *out);
+int bj_check_satisfied_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_vec, size_t witness_vec_len,
+                                  const void *variables_hint, size_t variables_hint_len, const void *witness_hint,
+                                  size_t witness_hint_len, bj_unsat_report *out);
+
 /* The host loop over witnesses around prove_cpu_basic (prover.rs:153-168, convenience.rs:119-196), pipelined from ONE host
  * thread: bj_prove_async queues bj_prove(setup, witness) on one of the context's two internal lanes (each its own HIP stream,
  * workspace and witness staging, driven by a library-owned worker thread; created on first use) and returns at once;

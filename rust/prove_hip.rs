@@ -434,6 +434,31 @@ impl<P: crate::field::traits::field_like::PrimeFieldLikeVectorized<Base = F>, CF
         proof_from_bjpf::<H, EXT>(&words, proof_config)
     }
 
+    /// `check_if_satisfied` (satisfiability_test.rs:15-353) on the device, for a witness `prove_hip` would refuse or — a wrong
+    /// lookup or multiplicity — would not notice: uploads the witness, runs `bj_check_satisfied` and returns its report
+    /// (`kind == BJ_SAT as u32` when every gate term vanishes and both sides of the lookup argument agree).  The order that
+    /// defines the first failure and what is not covered (copy constraints) are documented in include/boojum_hip.h.
+    pub fn check_satisfied_hip(&self, ctx: &HipCtx, setup: &HipSetup, witness_set: &WitnessSet<F>) -> bj_unsat_report {
+        assert_eq!(witness_set.variables.len(), setup.num_vars);
+        let vars = flatten(witness_set.variables.iter().chain(witness_set.witness.iter()).map(|p| &p.storage[..]), setup.n);
+        let mult = flatten(witness_set.multiplicities.iter().map(|p| &p.storage[..]), setup.n);
+        let mut report = bj_unsat_report { kind: 0, gate: 0, repetition: 0, term: 0, row: 0, value: 0, expected: 0, failures: [0; 5] };
+        let (mut d_vars, mut d_mult) = (std::ptr::null_mut(), std::ptr::null_mut());
+        unsafe {
+            ctx.check(bj_malloc(ctx.raw, vars.len() * 8, &mut d_vars));
+            ctx.check(bj_memcpy_h2d(ctx.raw, d_vars, vars.as_ptr() as *const _, vars.len() * 8));
+            if setup.has_lookup {
+                ctx.check(bj_malloc(ctx.raw, mult.len() * 8, &mut d_mult));
+                ctx.check(bj_memcpy_h2d(ctx.raw, d_mult, mult.as_ptr() as *const _, mult.len() * 8));
+            }
+            let rc = bj_check_satisfied(ctx.raw, setup.raw, d_vars as *const u64, d_mult as *const u64, &mut report);
+            bj_free(ctx.raw, d_vars);
+            bj_free(ctx.raw, d_mult);
+            ctx.check(rc);
+        }
+        report
+    }
+
     /// The pipelined form of `prove_hip` for a host that loops over witnesses (the shape of convenience.rs:119-196 called in a
     /// loop): queues the proof on one of the context's two lanes and returns at once; `HipTicket::wait` hands the `Proof` over.
     ///     let mut prev = cs.prove_hip_async(&ctx, &setup, ws[0].clone());
