@@ -1,4 +1,4 @@
-// Internal: the object behind the opaque `bj_fri` (shared by fri_prover.hip and prover.hip).
+// Internal: the object behind the opaque `bj_fri` (shared by fri_prover.hip, setup.hip and prover.hip).
 #pragma once
 #include "gl.h"
 #include "../../include/boojum_hip.h"

@@ -1,4 +1,4 @@
-// Internal: device-side form of a bj_gate_program (seam S3), shared by gate_program.hip and prover.hip.
+// Internal: device-side form of a bj_gate_program (seam S3), shared by gate_program.hip, setup.hip and prover.hip.
 #pragma once
 #include "ctx.h"
 #include "gate_body_rt.h"

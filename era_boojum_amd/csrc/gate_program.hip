@@ -16,13 +16,6 @@ using gl::u64;
 using gl::u32;
 
 namespace bj {
-void launch_quotient_poseidon2_flattened(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
-                                         unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q,
-                                         u64 *d_out0, u64 *d_out1, hipStream_t s);
-void launch_quotient_poseidon_flattened(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
-                                        unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q,
-                                        u64 *d_out0, u64 *d_out1, hipStream_t s);
-
 namespace {
 constexpr int MAX_TMP = BJ_GATE_PROGRAM_MAX_TEMPORARIES;
 

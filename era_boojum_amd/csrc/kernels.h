@@ -94,7 +94,53 @@ void launch_fri_fold(const u64 *d_c0, const u64 *d_c1, size_t len, u64 *d_o0, u6
                      u64 coset_inv, u64 ch0, u64 ch1, hipStream_t s);
 void launch_fri_fold_step(const u64 *d_c0, const u64 *d_c1, size_t len, unsigned k, u64 *d_o0, u64 *d_o1,
                           const u64 *d_roots, u64 coset_inv, u64 ch0, u64 ch1, hipStream_t s, size_t j0 = 0);
-// openings.hip: several DEEP opening sets in one launch (device-side argument pointers, canonical scalars)
+// stage2.hip
+void launch_copy_perm_stage2(const u64 *d_vars, size_t var_stride, const u64 *d_sigmas, size_t sig_stride,
+                             const u64 *d_non_res, unsigned V, unsigned chunk, unsigned log_n, const u64 *d_tw_fwd,
+                             const u64 *beta, const u64 *gamma, u64 *d_tmp, u64 *d_z, u64 *d_partials, hipStream_t s, bool small_non_residues);
+void launch_lookup_polys(const u64 *d_lvars, size_t var_stride, const u64 *d_table_id, const u64 *d_tables,
+                         size_t tab_stride, const u64 *d_mult, unsigned reps, unsigned w, unsigned log_n,
+                         const u64 *beta, const u64 *gamma, u64 *d_A, u64 *d_B, hipStream_t s);
+// quotient.hip
+void launch_quotient_gates(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
+                           const int *h_gates_flat, unsigned n_gates, const u64 *d_alphas, size_t Q, u64 *d_out0,
+                           u64 *d_out1, hipStream_t s);
+void launch_quotient_lookup(const u64 *d_lvars, size_t var_stride, const u64 *d_table_id, const u64 *d_tables,
+                            size_t tab_stride, const u64 *d_mult, const u64 *d_A, const u64 *d_B, size_t s2_stride,
+                            unsigned reps, unsigned w, const u64 *lbeta, const u64 *lgamma, const u64 *d_alphas,
+                            size_t Q, u64 *d_out0, u64 *d_out1, hipStream_t s);
+void launch_quotient_copy_perm(const u64 *d_vars, size_t var_stride, const u64 *d_sigmas, size_t sig_stride,
+                               const u64 *d_stage2, size_t s2_stride, const u64 *d_non_res, unsigned V, unsigned chunk,
+                               unsigned log_n, unsigned log_L, const u64 *d_tw_fwd, const u64 *beta, const u64 *gamma,
+                               const u64 *alpha_l1, const u64 *d_alphas_cp, size_t Q_local, size_t I0, const u64 *d_inv_xm1, u64 *d_out0,
+                               u64 *d_out1, hipStream_t s, bool small_non_residues);
+void launch_inv_x_minus_one(const u64 *d_tw_fwd, size_t Q, size_t I0, u64 *d_out, hipStream_t s);
+bool launch_combine_residues(const u64 *d_residues, unsigned W, size_t E, unsigned n_cols, const u64 *h_a, u64 *d_out, hipStream_t s);
+void launch_gather_rows(const u64 *d_base, size_t col_stride, unsigned n_cols, const u64 *d_idx, unsigned n_idx,
+                        u64 *d_out, hipStream_t s);
+void launch_merkle_paths(const u64 *d_tree, size_t num_leaves, unsigned depth, const u64 *d_idx, unsigned n_idx,
+                         u64 *d_out, hipStream_t s);
+void launch_gather_fri_leaves(const u64 *d_c0, const u64 *d_c1, unsigned log_e, const u64 *d_leaf_idx, unsigned n_idx,
+                              u64 *d_out, hipStream_t s);
+// gate_poseidon2.hip, gate_poseidon1.hip
+void launch_quotient_poseidon2_flattened(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
+                                         unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q,
+                                         u64 *d_out0, u64 *d_out1, hipStream_t s);
+void launch_quotient_poseidon_flattened(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
+                                        unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q,
+                                        u64 *d_out0, u64 *d_out1, hipStream_t s);
+// openings.hip
+void launch_barycentric_weights(u64 *d_w0, u64 *d_w1, const u64 *d_tw_fwd, unsigned log_n, u64 coset, const u64 *at,
+                                hipStream_t s);
+unsigned barycentric_num_blocks(size_t n);
+void launch_barycentric_eval(const u64 *const *d_col_ptrs, unsigned n_cols, size_t n, const u64 *d_w0, const u64 *d_w1,
+                             u64 *d_partials, u64 *d_out, hipStream_t s);
+void launch_linear_combination(const u64 *const *d_col_ptrs, const u64 *d_coefs, unsigned n_cols, size_t n, u64 *d_out0,
+                               u64 *d_out1, hipStream_t s);
+void launch_deep_accumulate(const u64 *const *d_col_ptrs, const u64 *d_coefs, unsigned n_cols, size_t N, size_t I0,
+                            const u64 *d_tw_fwd, u64 c0, u64 c1, u64 at0, u64 at1, u64 *d_dst0, u64 *d_dst1,
+                            int accumulate, hipStream_t s);
+// several DEEP opening sets in one launch (device-side argument pointers, canonical scalars)
 constexpr int DEEP_MAX_SETS = 3;
 struct DeepSetHostArgs {
     const u64 *const *d_cols;

@@ -5,34 +5,6 @@
 
 using gl::u64;
 
-namespace bj {
-void launch_barycentric_weights(u64 *d_w0, u64 *d_w1, const u64 *d_tw_fwd, unsigned log_n, u64 coset, const u64 *at,
-                                hipStream_t s);
-unsigned barycentric_num_blocks(size_t n);
-void launch_barycentric_eval(const u64 *const *d_col_ptrs, unsigned n_cols, size_t n, const u64 *d_w0, const u64 *d_w1,
-                             u64 *d_partials, u64 *d_out, hipStream_t s);
-void launch_deep_accumulate(const u64 *const *d_col_ptrs, const u64 *d_coefs, unsigned n_cols, size_t N, size_t I0,
-                            const u64 *d_tw_fwd, u64 c0, u64 c1, u64 at0, u64 at1, u64 *d_dst0, u64 *d_dst1,
-                            int accumulate, hipStream_t s);
-}  // namespace bj
-
-namespace bj {
-void launch_linear_combination(const u64 *const *d_col_ptrs, const u64 *d_coefs, unsigned n_cols, size_t n, u64 *d_out0,
-                               u64 *d_out1, hipStream_t s);
-int combine_monomials(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1, size_t n_src,
-                      const uint64_t *h_challenges, size_t n, uint64_t *d_out0, uint64_t *d_out1);
-int deep_accumulate_range(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1, size_t n_src,
-                          const uint64_t *h_values, const uint64_t *h_challenges, const uint64_t *at2, unsigned log_n,
-                          unsigned log_lde, size_t N_local, size_t I0, uint64_t *d_dst_c0, uint64_t *d_dst_c1,
-                          int accumulate);
-struct DeepSetHost {   // one opening set, host side: sources (device pointers), values and challenges as F_p^2 pairs, the point
-    const uint64_t *const *src_c0, *const *src_c1;
-    size_t n_src;
-    const uint64_t *values, *challenges, *at2;
-};
-int deep_accumulate_multi(bj_ctx *ctx, const DeepSetHost *sets, unsigned n_sets, unsigned log_n, unsigned log_lde, size_t N_local,
-                          size_t I0, uint64_t *d_dst_c0, uint64_t *d_dst_c1, int accumulate);
-}
 namespace {
 // device-side argument block: [ptrs (n_cols)] [coefs (2*n_cols)] in one temporary allocation
 struct DevArgs {

@@ -1,5 +1,5 @@
-// Internal: the setup object behind the opaque `bj_setup` of include/boojum_hip.h, shared by prover.hip (which creates and
-// proves with it) and check_satisfied.hip (which only reads the replicated natural-order columns and the gate list).
+// Internal: the setup object behind the opaque `bj_setup` of include/boojum_hip.h, shared by setup.hip (which creates it),
+// prover.hip (which proves with it) and check_satisfied.hip (which only reads the replicated natural-order columns and the gate list).
 #pragma once
 #include "ctx.h"
 #include "fri_types.h"
@@ -52,6 +52,13 @@ struct bj_setup {
 
 
 namespace bj {
+// the tree kernels of the calls in its scope follow the proof config, then the context's own setting returns
+struct HasherGuard {
+    bj_ctx *c;
+    int saved;
+    ~HasherGuard() { c->hasher = saved; }
+};
+
 enum : unsigned { GATES_GENERAL = 1, GATES_SPECIALIZED = 2 };
 // prover.hip: every gate evaluator of the setup's circuit over `points` points of caller-given columns
 void launch_circuit_gates(bj_ctx *ctx, const bj_setup *S, const gl::u64 *d_vars, size_t var_stride, const gl::u64 *d_consts,

@@ -1,0 +1,351 @@
+// Setup creation: bj_setup_create[_sharded] and the accessors of the setup object (setup.h).  The circuit's description is
+// checked, the sigma / constant / table columns are brought to the device, inverse-transformed, extended over this GPU's cosets
+// of the LDE domain and committed to (setup.rs, prover.rs:211); proofs (prover.hip) only read the result.
+#include "ctx.h"
+#include "fri_types.h"
+#include "gate_program.h"
+#include "setup.h"
+
+#include <cstring>
+
+using gl::u64;
+
+namespace bj {
+unsigned setup_world(const bj_setup *s) { return s ? s->sh.world : 0; }
+}  // namespace bj
+
+extern "C" {
+
+int bj_setup_set_comm(bj_setup *s, const bj_comm *comm) {
+    if (!s || !comm) return BJ_ERR_INVALID_ARG;
+    if (s->sh.world < 2 || comm->world != s->sh.world || comm->rank != s->sh.rank || (!comm->all_gather && !comm->all_gather_stream))
+        return BJ_ERR_INVALID_ARG;   // only the transport changes: the shard this setup holds is fixed
+    s->sh.comm = *comm;
+    return BJ_OK;
+}
+
+void bj_setup_destroy(bj_setup *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    if (s->d_nat) (void)hipFree(s->d_nat);
+    if (s->d_mono) (void)hipFree(s->d_mono);
+    if (s->d_lde) (void)hipFree(s->d_lde);
+    if (s->d_tree) (void)hipFree(s->d_tree);
+    if (s->d_non_res) (void)hipFree(s->d_non_res);
+    if (s->d_inv_xm1) (void)hipFree(s->d_inv_xm1);
+    if (s->d_placement) (void)hipFree(s->d_placement);
+    for (auto &p : s->programs) p.release();
+    for (auto &g : s->spec) g.program.release();
+    delete s;
+}
+
+int bj_setup_create(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const uint64_t *h_constants,
+                    const uint64_t *h_tables, const bj_proof_config *cfg, bj_setup **out) {
+    return bj_setup_create_sharded(ctx, c, h_sigmas, h_constants, h_tables, cfg, nullptr, out);
+}
+
+int bj_setup_create_sharded(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const uint64_t *h_constants,
+                            const uint64_t *h_tables, const bj_proof_config *cfg, const bj_comm *comm, bj_setup **out) {
+    return bj::setup_create_impl(ctx, c, h_sigmas, nullptr, h_constants, h_tables, cfg, comm, out);
+}
+
+}  // extern "C"
+
+void bj::setup_adopt_placement(bj_setup *s, uint32_t *d_placement) { s->d_placement = d_placement; }
+const uint32_t *bj::setup_placement(const bj_setup *s) { return s->d_placement; }
+
+int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const std::function<int(bj_setup *, u64 *)> &fill_sigmas,
+                          const uint64_t *h_constants, const uint64_t *h_tables, const bj_proof_config *cfg, const bj_comm *comm,
+                          bj_setup **out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: null out pointer");
+    *out = nullptr;
+    if (!c || !cfg || (!h_sigmas && !fill_sigmas) || !h_constants) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: null argument");
+    if (c->log_n < 1 || c->log_n > 26) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: log_n out of range");
+    if (c->num_gates == 0 || c->num_gates > 16 || !c->gates) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: 1..16 gates expected");
+    if (!bj::is_pow2(c->quotient_degree) || !bj::is_pow2(cfg->fri_lde_factor) || cfg->fri_lde_factor < 2 ||
+        !bj::is_pow2(cfg->cap_size))
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: quotient degree / fri_lde_factor / cap must be powers of two");
+    {
+        const unsigned tk = cfg->transcript ? cfg->transcript : BJ_TRANSCRIPT_POSEIDON2, hk = cfg->tree_hasher ? cfg->tree_hasher : BJ_HASHER_POSEIDON2;
+        if (tk > BJ_TRANSCRIPT_KECCAK256 || hk > BJ_HASHER_POSEIDON) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: unknown transcript / tree hasher");
+        const bool byte_hasher = hk == BJ_HASHER_BLAKE2S || hk == BJ_HASHER_KECCAK256,
+                   byte_transcript = tk == BJ_TRANSCRIPT_BLAKE2S || tk == BJ_TRANSCRIPT_KECCAK256;
+        if (byte_hasher != byte_transcript)   // Transcript::CompatibleCap = TreeHasher::Output (prover.rs:153-168)
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: a byte tree hasher (Blake2s / Keccak256) goes with a byte transcript and "
+                                                     "an algebraic tree hasher (Poseidon2 / Poseidon) with an algebraic transcript");
+    }
+    if (cfg->fri_lde_factor > 64 || c->quotient_degree > 64)   // per-coset tables of the quotient kernels hold 64 entries
+        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: fri_lde_factor and quotient_degree are limited to 64");
+    if (c->num_public_inputs && (!c->public_input_cols || !c->public_input_rows))
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: public input locations missing");
+    for (unsigned i = 0; i < c->num_public_inputs; i++)
+        if (c->public_input_cols[i] >= c->num_vars || (c->public_input_rows[i] >> c->log_n) != 0)
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: public input %u at (column %u, row %u) is outside the %u x 2^%u trace",
+                            i, c->public_input_cols[i], c->public_input_rows[i], c->num_vars, c->log_n);
+    if (cfg->pow_bits > 32 || cfg->pow_bits >= cfg->security_level)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: pow_bits must be <= 32 and below the security level (pow.rs:53, prover.rs:2293)");
+    if (cfg->pow_runner > BJ_POW_KECCAK256)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: pow_runner %u (0 / BJ_POW_BLAKE2S256 / BJ_POW_KECCAK256)", cfg->pow_runner);
+    // LookupParameters::UseSpecializedColumnsWithTableIdAsVariable (cs/mod.rs:237-241): table_ids_column_idxes is empty (setup.rs:970-971)
+    // and a sub-argument owns width + 1 variable columns, the last one the table id (lookup_argument_in_ext.rs:354-366, 949-1000)
+    const bool tid_var = c->lookup_reps && c->table_id_col == BJ_TABLE_ID_AS_VARIABLE;
+    const unsigned lookup_cps = c->lookup_width + (tid_var ? 1u : 0u);
+    if (c->lookup_reps && (!h_tables || c->lookup_width == 0 || c->lookup_width > 8 || (!tid_var && c->table_id_col >= c->num_constant_cols)))
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: bad lookup parameters");
+    if ((uint64_t)c->num_vars < (uint64_t)c->num_gp_vars + (uint64_t)lookup_cps * c->lookup_reps || !c->non_residues)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: bad column counts");
+    if (c->num_vars > 4096)   // the copy-permutation quotient keeps k_c * beta of every column in LDS (16 bytes per column)
+        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: %u copiable columns, at most 4096 are supported", c->num_vars);
+    unsigned n_chunks = (c->num_vars + c->quotient_degree - 1) / c->quotient_degree;
+    if (n_chunks < 2) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: a single copy-permutation chunk is not supported");
+    if (comm && comm->world > 1) {
+        const unsigned W = comm->world;
+        if (!bj::is_pow2(W) || W > 8 || comm->rank >= W || (!comm->all_gather && !comm->all_gather_stream))
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create_sharded: world must be a power of two <= 8, rank < world, callback set");
+        if (cfg->fri_lde_factor % W || cfg->cap_size % W || c->quotient_degree > cfg->fri_lde_factor)
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create_sharded: world must divide fri_lde_factor and cap_size, and "
+                                                     "quotient_degree must not exceed fri_lde_factor");
+        const unsigned cl = cfg->fri_lde_factor / W;
+        if ((((size_t)1 << c->log_n) * cl) < cfg->cap_size / W)
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create_sharded: shard smaller than its cap fragment");
+        const size_t Qe_rank = ((size_t)c->quotient_degree << c->log_n) / W;   // every rank evaluates q n / W points of the quotient
+        if (Qe_rank < 2 || !bj::is_pow2(Qe_rank))                              // and inverse-transforms them: a power of two
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create_sharded: q n / world = %zu quotient points per rank (a power of two >= 2 is needed)", Qe_rank);
+    }
+    bj_setup *s = new bj_setup();
+    s->device = ctx->device;
+    bj::HasherGuard hasher_guard{ctx, ctx->hasher};
+    ctx->hasher = cfg->tree_hasher ? (int)cfg->tree_hasher : BJ_HASHER_POSEIDON2;
+    if (comm && comm->world > 1) {
+        s->sh.rank = comm->rank;
+        s->sh.world = comm->world;
+        s->sh.comm = *comm;
+    }
+    s->log_n = c->log_n; s->V = c->num_vars; s->num_gp_vars = c->num_gp_vars; s->nC = c->num_constant_cols;
+    s->Wc = c->num_witness_cols;
+    s->lookup_w = c->lookup_width; s->lookup_reps = c->lookup_reps; s->table_id_col = tid_var ? 0 : c->table_id_col;
+    s->tid_var = tid_var; s->lookup_cps = lookup_cps;
+    s->q = c->quotient_degree;
+    s->n_gates = c->num_gates;
+    if (c->num_gates > 16) {
+        bj_setup_destroy(s);
+        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: %u gate types over general-purpose columns (at most 16)", c->num_gates);
+    }
+    for (unsigned g = 0; g < c->num_gates; g++) {
+        const bj_gate_desc &G = c->gates[g];
+        const bool p2 = G.kind == BJ_GATE_POSEIDON2_FLATTENED || G.kind == BJ_GATE_POSEIDON_FLATTENED;
+        if (G.kind < 1 || G.kind > BJ_GATE_POSEIDON_FLATTENED || G.path_len > 6 || (G.kind == BJ_GATE_PROGRAM && !G.program) ||
+            (p2 && (G.num_terms != 118 || G.num_repetitions != 1 || c->num_gp_vars < 130)) ||
+            (G.kind != BJ_GATE_PROGRAM && G.kind != BJ_GATE_NOP && !p2 && G.num_terms != 1)) {
+            bj_setup_destroy(s);
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: bad gate descriptor %u", g);
+        }
+        {   // every column index the evaluator will form must exist: (reps - 1) * stride + the widest operand, after the selector path
+            unsigned var_extent = 0, const_extent = 0, wit_extent = 0;
+            bool const_per_rep = true;
+            switch (G.kind) {
+                case BJ_GATE_CONSTANT_ALLOCATOR: var_extent = 1; const_extent = 1; break;
+                case BJ_GATE_FMA_NO_CONSTANT: var_extent = 4; const_extent = 2; const_per_rep = false; break;
+                case BJ_GATE_REDUCTION4: var_extent = 5; const_extent = 4; const_per_rep = false; break;
+                case BJ_GATE_POSEIDON2_FLATTENED: var_extent = 130; break;
+                case BJ_GATE_POSEIDON_FLATTENED: var_extent = 130; break;
+                case BJ_GATE_PROGRAM: bj::gate_program_extent(G.program, &var_extent, &const_extent, &wit_extent); break;
+                default: break;
+            }
+            s->gate_wit_stride.push_back(G.wit_stride);
+            if (wit_extent && (size_t)(G.num_repetitions ? G.num_repetitions - 1 : 0) * G.wit_stride + wit_extent > c->num_witness_cols) {
+                bj_setup_destroy(s);
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: gate %u reads witness column %zu of %u", g,
+                                (size_t)(G.num_repetitions - 1) * G.wit_stride + wit_extent, c->num_witness_cols);
+            }
+            const size_t last = G.num_repetitions ? G.num_repetitions - 1 : 0;
+            const size_t var_end = var_extent ? last * G.var_stride + var_extent : 0;
+            const size_t const_end = G.path_len + (const_extent ? (const_per_rep ? last * G.const_stride : 0) + const_extent : 0);
+            if (G.kind != BJ_GATE_NOP && (G.num_repetitions == 0 || var_end > c->num_gp_vars || const_end > c->num_constant_cols)) {
+                bj_setup_destroy(s);
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: gate %u reads variable column %zu / constant column %zu of %u / %u "
+                                "(repetitions x stride + operand index, after a selector path of %u)", g, var_end, const_end,
+                                c->num_gp_vars, c->num_constant_cols, G.path_len);
+            }
+            if (G.path_len > c->num_constant_cols) {
+                bj_setup_destroy(s);
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: gate %u: selector path longer than the constant columns", g);
+            }
+        }
+        s->programs.emplace_back();
+        if (G.kind == BJ_GATE_PROGRAM) {
+            if (G.program->num_writes != G.num_terms) {
+                bj_setup_destroy(s);
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: gate %u: program writes %u terms, descriptor says %u", g,
+                                G.program->num_writes, G.num_terms);
+            }
+            if (int prc = s->programs.back().upload(ctx, G.program)) {
+                bj_setup_destroy(s);
+                return prc;
+            }
+        }
+        int f[12] = {G.kind, (int)G.path_len, (int)G.num_repetitions, (int)G.var_stride, (int)G.const_stride,
+                     (int)G.num_terms, 0, 0, 0, 0, 0, 0};
+        for (unsigned b = 0; b < G.path_len; b++) f[6 + b] = G.path[b] ? 1 : 0;
+        s->gates_flat.insert(s->gates_flat.end(), f, f + 12);
+    }
+    {   // gates over specialized columns (evaluator_data.rs:124-240, prover.rs:635-800): their variable columns follow the lookup ones
+        // in declaration order; their constant columns follow the general-purpose gates' ones and the table-id column (which is the
+        // first "special purpose" constant: setup.rs:963-1010), num_repetitions * const_stride columns each — every repetition its
+        // own principal_width.num_constants columns (share_constants = false, per_repetition_offset.constants_offset = that width)
+        // (64-bit sums: the sizes are the caller's, a wrapped 32-bit total must not pass the range checks)
+        uint64_t col = (uint64_t)c->num_gp_vars + (uint64_t)lookup_cps * c->lookup_reps;
+        uint64_t spec_consts = 0;
+        for (unsigned g = 0; c->specialized_gates && g < c->num_specialized_gates; g++) {
+            const uint64_t per_gate = (uint64_t)c->specialized_gates[g].num_repetitions * c->specialized_gates[g].const_stride;
+            if (per_gate > c->num_constant_cols) { spec_consts = (uint64_t)c->num_constant_cols + 1; break; }
+            spec_consts += per_gate;
+        }
+        if (spec_consts > c->num_constant_cols ||
+            (c->lookup_reps && !tid_var && (uint64_t)c->table_id_col + 1 + spec_consts != c->num_constant_cols)) {
+            bj_setup_destroy(s);
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: %u constant columns declared; the specialized gates' %llu must be the "
+                            "last ones, right behind the table-id column", c->num_constant_cols, (unsigned long long)spec_consts);
+        }
+        unsigned ccol = c->num_constant_cols - (unsigned)spec_consts;
+        s->spec.resize(c->num_specialized_gates);
+        for (unsigned g = 0; g < c->num_specialized_gates; g++) {
+            const bj_gate_desc &G = c->specialized_gates[g];
+            bool ok = c->specialized_gates && G.kind == BJ_GATE_PROGRAM && G.program && G.path_len == 0 && G.num_repetitions &&
+                      G.var_stride && G.program->num_writes == G.num_terms;
+            unsigned ve = 0, ce = 0, we = 0;
+            if (ok) {
+                bj::gate_program_extent(G.program, &ve, &ce, &we);
+                // a repetition reads its own var_stride variable columns and its own const_stride constant columns, no witness column.
+                // Constants SHARED by the repetitions (share_constants = true with constants) are refused: the reference itself hands
+                // such an evaluator an empty constant range (per_repetition_offset.constants_offset = 0, prover.rs:748-772)
+                ok = ve <= G.var_stride && we == 0 && ce <= G.const_stride;
+            }
+            if (!ok) {
+                bj_setup_destroy(s);
+                return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: specialized gate %u must be an op list without a selector path "
+                                "whose repetitions each read their own var_stride variable and const_stride constant columns "
+                                "(share_constants = false) and no witness column", g);
+            }
+            bj_setup::SpecGate &sg = s->spec[g];
+            if (int prc = sg.program.upload(ctx, G.program)) {
+                bj_setup_destroy(s);
+                return prc;
+            }
+            if (col + (uint64_t)G.num_repetitions * G.var_stride > c->num_vars) {
+                bj_setup_destroy(s);
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: specialized gate %u runs past the %u declared variable columns", g,
+                                c->num_vars);
+            }
+            sg.reps = G.num_repetitions; sg.width = G.var_stride; sg.terms = G.num_terms; sg.first_col = (unsigned)col;
+            sg.first_const = ccol; sg.const_width = G.const_stride;
+            col += (uint64_t)sg.reps * sg.width;
+            ccol += sg.reps * sg.const_width;
+            s->n_spec_terms += sg.reps * sg.terms;
+        }
+        if (col != c->num_vars) {
+            bj_setup_destroy(s);
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: %u variable columns declared, geometry + lookups + "
+                            "specialized gates make %llu", c->num_vars, (unsigned long long)col);
+        }
+    }
+    s->non_residues.assign(c->non_residues, c->non_residues + c->num_vars);
+    s->small_non_residues = true;
+    for (u64 k : s->non_residues) s->small_non_residues = s->small_non_residues && gl::canon(k) < ((u64)1 << 32);
+    for (unsigned i = 0; i < c->num_public_inputs; i++) {
+        s->pub_cols.push_back(c->public_input_cols[i]);
+        s->pub_rows.push_back(c->public_input_rows[i]);
+    }
+    s->fri_lde = cfg->fri_lde_factor; s->cap_size = cfg->cap_size; s->security = cfg->security_level; s->pow_bits = cfg->pow_bits;
+    s->pow_runner = cfg->pow_runner ? cfg->pow_runner : BJ_POW_BLAKE2S256;
+    s->transcript = cfg->transcript ? cfg->transcript : BJ_TRANSCRIPT_POSEIDON2;
+    s->hasher = cfg->tree_hasher ? cfg->tree_hasher : BJ_HASHER_POSEIDON2;
+    s->L = s->fri_lde > s->q ? s->fri_lde : s->q;   // used_lde_degree (prover.rs:313)
+    s->log_L = bj::log2_exact(s->L); s->log_fri = bj::log2_exact(s->fri_lde); s->log_q = bj::log2_exact(s->q);
+    const size_t n = (size_t)1 << s->log_n;
+    const unsigned nT = s->lookup_reps ? s->lookup_w + 1 : 0;
+    s->n_cols = s->V + s->nC + nT;
+    s->cl = s->L / s->sh.world;
+    s->c0 = s->sh.rank * s->cl;
+    s->Ls = (size_t)s->cl * n;
+    s->Nl = n * s->fri_lde / s->sh.world;
+    s->cap_l = s->cap_size / s->sh.world;
+    int rc = BJ_OK;
+    auto bail = [&](int code) {
+        bj_setup_destroy(s);
+        return code;
+    };
+    if (hipMalloc((void **)&s->d_nat, (size_t)s->n_cols * n * 8) != hipSuccess ||
+        hipMalloc((void **)&s->d_lde, (size_t)s->n_cols * s->Ls * 8) != hipSuccess ||
+        hipMalloc((void **)&s->d_non_res, s->V * 8) != hipSuccess)
+        return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_setup_create: device allocation failed"));
+    // leaf order of the setup oracle: sigma || constants || tables (polynomial_storage.rs:667-676)
+    rc = fill_sigmas ? fill_sigmas(s, s->d_nat) : bj_memcpy_h2d(ctx, s->d_nat, h_sigmas, (size_t)s->V * n * 8);
+    if (!rc) rc = bj_memcpy_h2d(ctx, s->d_nat + (size_t)s->V * n, h_constants, (size_t)s->nC * n * 8);
+    if (!rc && nT) rc = bj_memcpy_h2d(ctx, s->d_nat + (size_t)(s->V + s->nC) * n, h_tables, (size_t)nT * n * 8);
+    if (!rc) rc = bj_memcpy_h2d(ctx, s->d_non_res, s->non_residues.data(), s->V * 8);
+    if (rc) return bail(rc);
+    {   // monomials (kept), LDE into d_lde
+        if (hipMalloc((void **)&s->d_mono, (size_t)s->n_cols * n * 8) != hipSuccess)
+            return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_setup_create: device allocation failed"));
+        s->tiled = bj::mono_tiled(s->log_n);
+        rc = s->tiled ? bj::intt_to_tiled(ctx, s->d_nat, n, s->d_mono, n, s->log_n, s->n_cols)
+                      : bj_intt_batch(ctx, s->d_nat, s->d_mono, s->log_n, s->n_cols, n, 1);
+        if (!rc) rc = bj::lde_cosets_strided(ctx, s->d_mono, n, s->d_lde, s->Ls, s->log_n, s->n_cols, s->log_L, s->c0, s->cl, s->tiled);
+        if (!rc) rc = bj_sync(ctx);
+        if (rc) return bail(rc);
+    }
+    {   // the points the quotient is evaluated on here (prove_impl: Qe, I0) and 1 / (x - 1) on them, for the L_1 term
+        const size_t Qe = (n * s->q) / s->sh.world;
+        if (Qe) {
+            if ((rc = bj::ensure_twiddles(ctx, s->log_n + s->log_L, false))) return bail(rc);
+            if (hipMalloc((void **)&s->d_inv_xm1, Qe * 8) != hipSuccess)
+                return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_setup_create: device allocation failed"));
+            bj::launch_inv_x_minus_one(ctx->tw_fwd, Qe, (size_t)s->c0 * n, s->d_inv_xm1, ctx->stream);
+            if (hipGetLastError() != hipSuccess) return bail(bj::fail(ctx, BJ_ERR_HIP, "bj_setup_create: launch failed"));
+        }
+    }
+    if (hipMalloc((void **)&s->d_tree, bj_merkle_tree_digests(s->Nl, s->cap_l) * 32) != hipSuccess)
+        return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_setup_create: tree allocation failed"));
+    rc = bj_merkle_tree_build(ctx, s->d_lde, s->Ls, s->n_cols, s->Nl, s->cap_l, s->d_tree);
+    s->cap.resize(4 * s->cap_size);
+    if (!rc) rc = bj::gather_cap(ctx, s->sh, s->d_tree, s->Nl, s->cap_size, s->cap.data());
+    if (rc) return bail(rc);
+    *out = s;
+    return BJ_OK;
+}
+
+extern "C" {
+
+int bj_setup_shape(const bj_setup *s, unsigned *log_n, unsigned *num_vars, unsigned *num_witness_cols, unsigned *num_public_inputs) {
+    if (s && num_public_inputs) *num_public_inputs = (unsigned)s->pub_cols.size();
+    if (!s) return BJ_ERR_INVALID_ARG;
+    if (log_n) *log_n = s->log_n;
+    if (num_vars) *num_vars = s->V;
+    if (num_witness_cols) *num_witness_cols = s->Wc;
+    return BJ_OK;
+}
+
+int bj_setup_cap(const bj_setup *s, uint64_t *h_cap) {
+    if (!s || !h_cap) return BJ_ERR_INVALID_ARG;
+    std::memcpy(h_cap, s->cap.data(), s->cap.size() * 8);
+    return BJ_OK;
+}
+
+int bj_setup_device_bytes(const bj_setup *s, size_t *bytes) {
+    if (!s || !bytes) return BJ_ERR_INVALID_ARG;
+    const size_t n = (size_t)1 << s->log_n;
+    size_t b = 0;
+    if (s->d_nat) b += (size_t)s->n_cols * n * 8;
+    if (s->d_mono) b += (size_t)s->n_cols * n * 8;
+    if (s->d_lde) b += (size_t)s->n_cols * s->Ls * 8;
+    if (s->d_tree) b += bj_merkle_tree_digests(s->Nl, s->cap_l) * 32;
+    if (s->d_non_res) b += (size_t)s->V * 8;
+    if (s->d_inv_xm1) b += (n * s->q) / s->sh.world * 8;
+    if (s->d_placement) b += (size_t)s->V * n * 4;
+    *bytes = b;
+    return BJ_OK;
+}
+
+}  // extern "C"

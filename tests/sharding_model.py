@@ -131,7 +131,7 @@ def combine_residues(residues, a_values):
 
 
 def sharded_quotient_monomials(evals_local_bitrev, log_n, log_lde, q, world, rank, ifft_natural_to_natural, bitreverse, device=None):
-    """What prove_impl does for the quotient on W ranks (csrc/prover.hip, round 4): `evals_local_bitrev` = this rank's values of T on
+    """What the prover does for the quotient on W ranks (csrc/prover.hip: exchange_residues, since round 4): `evals_local_bitrev` = this rank's values of T on
     the first E = q n / W points of ITS OWN coset range (one array of E words per component), inverse-transformed to the residue
     T mod (x^E - a_rank), all-gathered (torch.distributed), combined.  Returns the q n coefficients of T per component."""
     import torch

@@ -500,7 +500,7 @@ def test_pipelined_drop_in_call_gives_the_serial_proofs():
 
 
 def test_host_witness_group_plans_and_non_residue_paths_give_the_same_proof():
-    """bj_prove takes the witness over PCIe in groups and hashes it group by group (prover.hip: quarters of the first eight
+    """bj_prove takes the witness over PCIe in groups and hashes it group by group (csrc/witness_plan.h: quarters of the first eight
     columns, then 8, 16, 16, 24, ... columns per absorption run); bj_prove_dev hashes the resident witness in one kernel.  Every
     plan — the default one, the round-4 uniform one, other group widths, no group-wise absorption — and both forms of the
     copy-permutation numerator (32-bit non-residue multipliers, the default for make_non_residues' output, and 64-bit products)
