@@ -68,6 +68,9 @@ _SIGNATURES = {
     "bj_sigmas_from_placement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t]),
     "bj_lookup_polys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint,
                                   C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bj_lookup_multiplicities": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint,
+                                           C.c_void_p]),
+    "bj_setup_lookup_multiplicities": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bj_quotient_gates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p,
                                     C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "bj_quotient_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
@@ -351,6 +354,11 @@ class Context:
     def lookup_polys(self, d_lvars, var_stride, d_table_id, d_tables, table_stride, d_mult, reps, width, log_n, beta, gamma, d_A, d_B):
         self._check(self._lib.bj_lookup_polys(self._h, d_lvars, var_stride, d_table_id, d_tables, table_stride, d_mult, reps, width,
                                               log_n, _np_ptr(self._e2(beta)), _np_ptr(self._e2(gamma)), d_A, d_B))
+
+    def lookup_multiplicities(self, d_lvars, var_stride, d_table_id, d_tables, table_stride, reps, width, log_n, d_mult):
+        """bj_lookup_multiplicities: the multiplicity column [n] counted from raw columns (those of lookup_polys) into d_mult."""
+        self._check(self._lib.bj_lookup_multiplicities(self._h, d_lvars, var_stride, d_table_id, d_tables, table_stride, reps, width,
+                                                       log_n, d_mult))
 
     def quotient_gates(self, d_vars, var_stride, num_gp_vars, d_consts, const_stride, num_constant_cols, gates, alphas, num_points,
                        d_out0, d_out1):
@@ -1148,8 +1156,9 @@ class ProverSetup:
         stages["witness_tree_leaf_kernel"] = float(ms[7])
         return buf, stages
 
-    def prove(self, variables=None, multiplicities=None, public_values=None):
-        """Host-memory entry point (bj_prove): returns (serialised proof u64 array, per-stage ms)."""
+    def prove(self, variables=None, multiplicities=None, public_values=None, count_multiplicities=False):
+        """Host-memory entry point (bj_prove): returns (serialised proof u64 array, per-stage ms).  count_multiplicities: no column
+        is handed over (NULL), the prover counts it on the device."""
         c = self.circuit
         v = np.ascontiguousarray(c.variables if variables is None else variables, dtype=np.uint64)
         if self.num_witness_cols and v.shape[0] == c.num_vars:     # the non-copiable witness columns travel behind the variables
@@ -1159,13 +1168,14 @@ class ProverSetup:
         if pv.size == 0:
             pv = np.zeros(1, dtype=np.uint64)
         h = C.c_void_p()
-        self._ctx._check(self._lib.bj_prove(self._ctx._h, self._h, _np_ptr(v), _np_ptr(m) if c.lookup_reps else None,
+        self._ctx._check(self._lib.bj_prove(self._ctx._h, self._h, _np_ptr(v), _np_ptr(m) if c.lookup_reps and not count_multiplicities else None,
                                             _np_ptr(pv), C.byref(h)))
         return self._finish(h)
 
-    def prove_async(self, variables=None, multiplicities=None, public_values=None):
+    def prove_async(self, variables=None, multiplicities=None, public_values=None, count_multiplicities=False):
         """bj_prove_async: queues the proof on one of the context's two lanes and returns a ticket for `wait`.  Arrays passed in
-        are used in place when they are contiguous uint64 (e.g. views of pinned tensors) and kept alive by the ticket."""
+        are used in place when they are contiguous uint64 (e.g. views of pinned tensors) and kept alive by the ticket.
+        count_multiplicities: as for `prove`."""
         c = self.circuit
         v = np.ascontiguousarray(c.variables if variables is None else variables, dtype=np.uint64)
         if self.num_witness_cols and v.shape[0] == c.num_vars:
@@ -1175,7 +1185,7 @@ class ProverSetup:
         if pv.size == 0:
             pv = np.zeros(1, dtype=np.uint64)
         t = C.c_void_p()
-        self._ctx._check(self._lib.bj_prove_async(self._ctx._h, self._h, _np_ptr(v), _np_ptr(m) if c.lookup_reps else None,
+        self._ctx._check(self._lib.bj_prove_async(self._ctx._h, self._h, _np_ptr(v), _np_ptr(m) if c.lookup_reps and not count_multiplicities else None,
                                                   _np_ptr(pv), C.byref(t)))
         return _Ticket(t, (v, m))
 
@@ -1245,8 +1255,29 @@ class ProverSetup:
                                                                  C.byref(r)))
         return self._report(r)
 
-    def prove_dev(self, d_variables, d_multiplicities, public_values=None):
-        """Witness already in HBM (bj_prove_dev)."""
+    def count_multiplicities_dev(self, d_variables, d_multiplicities):
+        """bj_setup_lookup_multiplicities on a witness already in HBM: writes the column [n] at d_multiplicities."""
+        self._ctx._check(self._lib.bj_setup_lookup_multiplicities(self._ctx._h, self._h, d_variables, d_multiplicities))
+
+    def count_multiplicities(self, variables=None):
+        """The multiplicity column [1, n] of the witness, counted on the device (bj_setup_lookup_multiplicities): per class of equal
+        table rows the number of looked-up tuples equal to it, on the class's smallest row.  `variables` defaults to the circuit's
+        own and is uploaded for the call.  Raises, naming the first (row, sub-argument), if a looked-up tuple is in no table row."""
+        c = self.circuit
+        v = np.ascontiguousarray(c.variables if variables is None else variables, dtype=np.uint64)
+        d_v, d_m = self._ctx.upload(v), self._ctx.malloc(8 * c.n)
+        try:
+            self.count_multiplicities_dev(d_v, d_m)
+            return self._ctx.d2h(d_m, (1, c.n))
+        finally:
+            self._ctx.free(d_v)
+            self._ctx.free(d_m)
+
+    def prove_dev(self, d_variables, d_multiplicities, public_values=None, count_multiplicities=False):
+        """Witness already in HBM (bj_prove_dev).  count_multiplicities: d_multiplicities is ignored and NULL handed over, the
+        prover counts the column on the device."""
+        if count_multiplicities:
+            d_multiplicities = None
         c = self.circuit
         pv = np.array([p[2] for p in c.public_inputs] if public_values is None else public_values, dtype=np.uint64)
         if pv.size == 0:

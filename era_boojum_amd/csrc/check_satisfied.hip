@@ -4,63 +4,29 @@
 //   gates    phase 1: every evaluator of the circuit once over the n trace rows (launch_circuit_gates, the block the quotient stage
 //            runs on the LDE) with fixed pseudo-random F_p^2 weights, then one reduction for the first non-zero row and their
 //            number; phase 2, only on a failure: that one row, replicated over a block of points, term by term with unit weights.
-//   lookups  an open-addressing hash table over the table rows (classes of equal rows, representative = smallest row), one probe
+//   lookups  the index over the table rows of lookup_index.h (classes of equal rows, representative = smallest row), one probe
 //            per looked-up tuple, then expected (sum of the class's multiplicities) against counted per class.
 //   report   first failure in the order of include/boojum_hip.h.
 // All scratch is the context's (ensure_scratch); nothing here allocates, and no input is written.
 #include "ctx.h"
+#include "lookup_index.h"
 #include "setup.h"
 
 #include <cstring>
 #include <vector>
 
 using gl::u64;
+using namespace bj::lookup;   // LookupShape, find_class, lookup_build_kernel, block_min_count, the slot conventions
 
 namespace {
 
-constexpr unsigned CHECK_BLOCK = 256;       // threads per block of every kernel here; also the points a row is replicated over
-constexpr unsigned MAX_TUPLE = 16;          // lookup_width + 1 words held in registers
-constexpr uint32_t SLOT_EMPTY = 0xFFFFFFFFu;
-constexpr u64 NONE64 = ~0ull;
+constexpr unsigned CHECK_BLOCK = bj::lookup::INDEX_BLOCK;   // threads per block of every kernel here; also the points a row is replicated over
 constexpr u64 ALPHA_SEED = 0x626A5F636865636Bull;   // "bj_check" (include/boojum_hip.h)
 
 // counters the kernels reduce into: [2k] smallest key, [2k + 1] number, k = bj_unsat_kind - 1
 struct Counters {
     u64 v[8];
 };
-
-__device__ __forceinline__ unsigned lane_id() { return threadIdx.x & 63u; }
-
-// smallest key and number of the block's `bad` threads: one atomicMin and one atomicAdd per block that has any
-__device__ __forceinline__ void block_min_count(bool bad, u64 key, u64 *out_min, u64 *out_cnt) {
-    __shared__ u64 s_min[CHECK_BLOCK / 64];
-    __shared__ unsigned s_cnt[CHECK_BLOCK / 64];
-    u64 k = bad ? key : NONE64;
-    const unsigned cnt = (unsigned)__popcll(__ballot(bad));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const u64 o = __shfl_down(k, off);
-        k = o < k ? o : k;
-    }
-    if (lane_id() == 0) {
-        s_min[threadIdx.x >> 6] = k;
-        s_cnt[threadIdx.x >> 6] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 m = s_min[0];
-        unsigned c = s_cnt[0];
-#pragma unroll
-        for (unsigned w = 1; w < CHECK_BLOCK / 64; w++) {
-            m = s_min[w] < m ? s_min[w] : m;
-            c += s_cnt[w];
-        }
-        if (c) {
-            atomicMin((unsigned long long *)out_min, (unsigned long long)m);
-            atomicAdd((unsigned long long *)out_cnt, (unsigned long long)c);
-        }
-    }
-}
 
 // rows whose weighted sum of terms is not zero
 __global__ void __launch_bounds__(CHECK_BLOCK) nonzero_rows_kernel(const u64 *t0, const u64 *t1, size_t n, u64 *out_min, u64 *out_cnt) {
@@ -79,67 +45,6 @@ __global__ void __launch_bounds__(CHECK_BLOCK) replicate_row_kernel(const u64 *s
     if (threadIdx.x == 0) flat[c] = v;
 }
 
-struct LookupShape {
-    const u64 *tables;    // [w + 1][n]
-    const u64 *lvars;     // [reps * cps][n]
-    const u64 *table_id;  // [n], or nullptr: the id is the last variable column of the sub-argument
-    size_t n;
-    unsigned w, reps, cps, mask;   // mask: slots - 1
-};
-
-__device__ __forceinline__ uint32_t tuple_hash(const u64 *t, unsigned words) {
-    u64 h = 0x9E3779B97F4A7C15ull;
-    for (unsigned j = 0; j < words; j++) {
-        h = (h ^ t[j]) * 0xBF58476D1CE4E5B9ull;
-        h ^= h >> 29;
-    }
-    h *= 0x94D049BB133111EBull;
-    return (uint32_t)(h >> 32);
-}
-__device__ __forceinline__ void load_table_row(const LookupShape &L, size_t r, u64 *t) {
-    for (unsigned j = 0; j <= L.w; j++) t[j] = gl::canon(L.tables[(size_t)j * L.n + r]);
-}
-__device__ __forceinline__ bool table_row_equals(const LookupShape &L, size_t r, const u64 *t) {
-    bool eq = true;
-    for (unsigned j = 0; j <= L.w; j++) eq = eq && gl::canon(L.tables[(size_t)j * L.n + r]) == t[j];
-    return eq;
-}
-__device__ __forceinline__ uint32_t slot_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// representative of the tuple's class, SLOT_EMPTY if no table row holds it (the table must be complete)
-__device__ __forceinline__ uint32_t find_class(const LookupShape &L, const uint32_t *slots, const u64 *t) {
-    uint32_t s = tuple_hash(t, L.w + 1) & L.mask;
-    for (;;) {
-        const uint32_t cur = slot_load(slots + s);
-        if (cur == SLOT_EMPTY) return SLOT_EMPTY;
-        if (table_row_equals(L, cur, t)) return cur;
-        s = (s + 1) & L.mask;
-    }
-}
-
-// one thread per table row: claim an empty slot, or lower the row number of the slot that holds an equal row.  The rows of a
-// class (the all-zero padding rows are the large one) never probe past their class's slot, and only a row below the number
-// they read there issues an atomic.
-__global__ void __launch_bounds__(CHECK_BLOCK) lookup_build_kernel(LookupShape L, uint32_t *slots) {
-    const size_t r = (size_t)blockIdx.x * CHECK_BLOCK + threadIdx.x;
-    if (r >= L.n) return;
-    u64 t[MAX_TUPLE];
-    load_table_row(L, r, t);
-    uint32_t s = tuple_hash(t, L.w + 1) & L.mask;
-    for (;;) {
-        uint32_t cur = slot_load(slots + s);
-        if (cur == SLOT_EMPTY) {
-            cur = atomicCAS(slots + s, SLOT_EMPTY, (uint32_t)r);
-            if (cur == SLOT_EMPTY) return;
-        }
-        if (table_row_equals(L, cur, t)) {
-            if ((uint32_t)r < cur) atomicMin(slots + s, (uint32_t)r);
-            return;
-        }
-        s = (s + 1) & L.mask;
-    }
-}
-
 // one thread per (sub-argument, row): count[class] += 1, or a miss keyed row * reps + sub-argument
 __global__ void __launch_bounds__(CHECK_BLOCK) lookup_probe_kernel(LookupShape L, const uint32_t *slots, unsigned long long *count, u64 *miss_min,
                                                                   u64 *miss_cnt) {
@@ -150,8 +55,7 @@ __global__ void __launch_bounds__(CHECK_BLOCK) lookup_probe_kernel(LookupShape L
     if (live) {
         const size_t sub = i / L.n, row = i - sub * L.n;
         u64 t[MAX_TUPLE];
-        for (unsigned j = 0; j < L.w; j++) t[j] = gl::canon(L.lvars[((size_t)sub * L.cps + j) * L.n + row]);
-        t[L.w] = gl::canon(L.table_id ? L.table_id[row] : L.lvars[((size_t)sub * L.cps + L.w) * L.n + row]);
+        load_looked_up(L, sub, row, t);
         cls = find_class(L, slots, t);
         key = (u64)row * L.reps + sub;
     }
@@ -281,7 +185,7 @@ int check_impl(bj_ctx *ctx, const bj_setup *S, const u64 *d_variables, const u64
         L.tables = d_tables;
         L.lvars = d_variables + (size_t)S->num_gp_vars * n;
         L.table_id = S->tid_var ? nullptr : d_consts + (size_t)S->table_id_col * n;
-        L.n = n;
+        L.n = L.tstride = L.vstride = n;
         L.w = S->lookup_w;
         L.reps = S->lookup_reps;
         L.cps = S->lookup_cps;

@@ -139,6 +139,12 @@ int setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas
                       const uint64_t *h_constants, const uint64_t *h_tables, const bj_proof_config *cfg, const bj_comm *comm, bj_setup **out);
 void setup_adopt_placement(bj_setup *s, uint32_t *d_placement);   // [num_vars][n] u32, hipMalloc'ed
 const uint32_t *setup_placement(const bj_setup *s);               // nullptr unless created from a placement
+// lookup_multiplicities.hip: the multiplicity column [n] counted from raw columns (the arguments of bj_lookup_multiplicities) or
+// from a setup's replicated natural-order columns and the variables.  In the context's scratch, on its stream; synchronises.
+// A looked-up tuple that is in no table row: BJ_ERR_INVALID_ARG, the message starts with `who` and names the first such lookup.
+int lookup_multiplicities(bj_ctx *ctx, const char *who, const gl::u64 *d_lvars, size_t var_stride, const gl::u64 *d_table_id,
+                          const gl::u64 *d_tables, size_t table_stride, unsigned reps, unsigned width, unsigned log_n, gl::u64 *d_out);
+int setup_lookup_multiplicities(bj_ctx *ctx, const char *who, const bj_setup *S, const gl::u64 *d_variables, gl::u64 *d_out);
 // dumps.hip: WitnessVec + copy-hint dumps -> [num_vars + num_witness_cols][n] cells, [n] multiplicities (device) and the public
 // input values (host), handed to `use` and freed when it returns; variables_hint may be NULL for a setup that holds its placement
 int witness_from_dumps(bj_ctx *ctx, const char *who, const bj_setup *setup, const void *witness_vec, size_t witness_vec_len,

@@ -264,6 +264,7 @@ struct Proving {
     const u64 *d_variables, *d_multiplicities, *h_public_values;
     const HostWitness *hw;   // nullptr: the witness is resident (bj_prove_dev)
     bool has_lookup;
+    bool count_mult;         // no multiplicity column was supplied: round 1 counts it (count_multiplicities)
     unsigned log_n, V, q, nC;
     // N / Ln: leaves / column stride HELD BY THIS GPU (the whole domain on one GPU); Q: points of the quotient domain
     size_t n, N, Q, Ln, I0, capl;
@@ -289,9 +290,10 @@ struct Proving {
     bj_fri *fri = nullptr;
     u64 pow_challenge = 0;
 
-    Proving(bj_ctx *c, const bj_setup *s, const u64 *d_vars, const u64 *d_mult, const u64 *h_pub, const HostWitness *h)
+    Proving(bj_ctx *c, const bj_setup *s, const u64 *d_vars, const u64 *d_mult, const u64 *h_pub, const HostWitness *h, bool count)
         : ctx(c), S(s), sh(s->sh), st(c->stream), d_variables(d_vars), d_multiplicities(d_mult), h_public_values(h_pub), hw(h) {
         has_lookup = S->lookup_reps > 0;
+        count_mult = has_lookup && count;
         log_n = S->log_n, V = S->V, q = S->q, nC = S->nC;
         n = (size_t)1 << log_n, N = S->Nl, Q = n * q, Ln = S->Ls, I0 = (size_t)S->c0 * n, capl = S->cap_l;
         Qe = Q / sh.world;
@@ -304,6 +306,7 @@ struct Proving {
     int reserve_workspace();
     int check_public_inputs();
     int open_transcript();
+    int count_multiplicities();
     int round1_witness();
     int witness_from_host(bool *hashed_in_groups);
     int round2_stage2();
@@ -363,7 +366,8 @@ int Proving::reserve_workspace() {
                                                                                                // entry point the proof came through: a context that alternates between bj_prove and
                                                                                                // bj_prove_dev (the lanes of bj_prove_async do) must not re-allocate its arena (1.8 s for 64 GB)
                 + (size_t)2 * N * (1 + S->pub_cols.size())                                     // DEEP: one extended numerator per large opening set beyond the first
-                + (S->tiled ? 2 * Q : 0);                                                      // the quotient's chunks once more, in the tiled layout
+                + (S->tiled ? 2 * Q : 0)                                                       // the quotient's chunks once more, in the tiled layout
+                + (count_mult && !d_multiplicities ? n + slack : 0);                           // the counted multiplicity column of a resident witness
     // `need` is an upper bound by construction of the list above — checked on every proof the test suite makes (the binding
     // raises when a proof had to take an overflow slab) — and a context that has seen a larger proof keeps its size
     if (need < ctx->arena_learned) need = ctx->arena_learned;
@@ -433,7 +437,7 @@ int Proving::witness_from_host(bool *hashed_in_groups) {
         if (c0 < v1)
             BJ_HIP(ctx, hipMemcpyAsync(const_cast<uint64_t *>(d_variables) + (size_t)c0 * n, hw->h_variables + (size_t)c0 * n,
                                        (size_t)(v1 - c0) * n * 8, hipMemcpyHostToDevice, ctx->copy_stream));
-        if (has_lookup && c1 == nW)
+        if (has_lookup && !count_mult && c1 == nW)
             BJ_HIP(ctx, hipMemcpyAsync(const_cast<uint64_t *>(d_multiplicities), hw->h_multiplicities, n * 8, hipMemcpyHostToDevice,
                                        ctx->copy_stream));
         BJ_HIP(ctx, hipEventRecord(ctx->copy_ev[g], ctx->copy_stream));
@@ -443,6 +447,7 @@ int Proving::witness_from_host(bool *hashed_in_groups) {
         const unsigned c0 = plan[g].c0, c1 = plan[g].c1;
         const unsigned v1 = c1 < VW ? c1 : VW;
         BJ_HIP(ctx, hipStreamWaitEvent(st, ctx->copy_ev[g], 0));
+        if (count_mult && c1 == nW && (rc = count_multiplicities())) break;   // the last group: every lookup column has landed
         if (c0 < v1) rc = intt_cols(d_variables + (size_t)c0 * n, mono.p + (size_t)c0 * n, v1 - c0);
         if (!rc && has_lookup && c1 == nW) rc = intt_cols(d_multiplicities, mono.p + (size_t)VW * n, 1);
         if (!rc) rc = lde_cols(mono.p + (size_t)c0 * n, wit_lde.p + (size_t)c0 * Ln, Ln, c1 - c0, S->log_L, S->c0, S->cl);
@@ -456,12 +461,26 @@ int Proving::witness_from_host(bool *hashed_in_groups) {
     return rc;
 }
 
+// No multiplicity column came with the witness: it is counted from the setup's table columns and the lookup columns of the
+// variables (lookup_multiplicities.hip), into the witness staging behind the variables where the witness came from the host, into
+// a column of the arena otherwise.  Synchronises (the number of misses is read); a tuple that is in no table row ends the proof.
+// Reads d_variables; sets d_multiplicities where it was nullptr.
+int Proving::count_multiplicities() {
+    if (!d_multiplicities) {
+        ArenaBuf col;
+        if (int rc = col.alloc(ctx, n)) return rc;
+        d_multiplicities = col.p;
+    }
+    return bj::setup_lookup_multiplicities(ctx, hw ? "bj_prove" : "bj_prove_dev", S, d_variables, const_cast<u64 *>(d_multiplicities));
+}
+
 // ---------------- round 1: witness LDE + tree (prover.rs:270-353) ----------------
 // Reads d_variables, d_multiplicities (hw: the host witness).  Adds wit_lde, mono, mono_s2 (allocated only), wit_tree, wit_cap;
 // the transcript absorbs wit_cap; proof->stage_ms[7] is the leaf kernel's time.
 int Proving::round1_witness() {
     int rc = BJ_OK;
     bool hashed_in_groups = false;               // bj_prove: the witness leaves were absorbed group by group under the transfer
+    if (count_mult && !hw && (rc = count_multiplicities())) return rc;   // before any proof work
     if ((rc = wit_lde.alloc(ctx, (size_t)nW * Ln))) return rc;
     if ((rc = mono.alloc(ctx, (size_t)nW * n))) return rc;
     if ((rc = mono_s2.alloc(ctx, (size_t)nS2 * n))) return rc;
@@ -1140,15 +1159,14 @@ struct FriGuard {
 };
 
 int prove_impl(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, const uint64_t *d_multiplicities,
-               const uint64_t *h_public_values, bj_proof **out, const HostWitness *hw) {
+               const uint64_t *h_public_values, bj_proof **out, const HostWitness *hw, bool count) {
     if (int rc = bj::bind(ctx)) return rc;
     if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_dev: null out pointer");
     *out = nullptr;
     if (!S || !d_variables) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_dev: null argument");
-    if (S->lookup_reps > 0 && !d_multiplicities) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_dev: multiplicities required");
     if (!S->pub_cols.empty() && !h_public_values) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_dev: public input values required");
     int rc = BJ_OK;
-    Proving P(ctx, S, d_variables, d_multiplicities, h_public_values, hw);
+    Proving P(ctx, S, d_variables, d_multiplicities, h_public_values, hw, count);
     P.proof = new bj_proof();
     ProofGuard guard{P.proof};
     if ((rc = P.reserve_workspace())) return rc;
@@ -1201,20 +1219,19 @@ static int stage_witness(bj_ctx *ctx, const bj_setup *S) {
 
 int bj_prove_dev(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, const uint64_t *d_multiplicities,
                  const uint64_t *h_public_values, bj_proof **out) {
-    return prove_impl(ctx, S, d_variables, d_multiplicities, h_public_values, out, nullptr);
+    return prove_impl(ctx, S, d_variables, d_multiplicities, h_public_values, out, nullptr, d_multiplicities == nullptr);   // NULL: counted
 }
 
 int bj_prove(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_variables, const uint64_t *h_multiplicities,
              const uint64_t *h_public_values, bj_proof **out) {
     if (int rc = bj::bind(ctx)) return rc;
     if (!S || !h_variables || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove: null argument");
-    if (S->lookup_reps && !h_multiplicities) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove: multiplicities required");
     if (int rc = stage_witness(ctx, S)) return rc;
     const size_t n = (size_t)1 << S->log_n;
     const unsigned group = bj::env().prove_h2d_group;
     const HostWitness hw{h_variables, h_multiplicities, group, false};
     // the copies are queued inside the proof (after the workspace is reserved); a previous proof on this context has drained
-    return prove_impl(ctx, S, ctx->wit_stage, ctx->wit_stage + (size_t)(S->V + S->Wc) * n, h_public_values, out, &hw);
+    return prove_impl(ctx, S, ctx->wit_stage, ctx->wit_stage + (size_t)(S->V + S->Wc) * n, h_public_values, out, &hw, h_multiplicities == nullptr);
 }
 
 }  // extern "C"
@@ -1227,17 +1244,16 @@ int prove_host_copy_first(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_vari
                           const uint64_t *h_public_values, bj_proof **out, int mode) {
     if (int rc = bind(ctx)) return rc;
     if (!S || !h_variables || !out) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove: null argument");
-    if (S->lookup_reps && !h_multiplicities) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove: multiplicities required");
     if (int rc = stage_witness(ctx, S)) return rc;
     const size_t n = (size_t)1 << S->log_n, vw = (size_t)(S->V + S->Wc) * n;
     if (mode == 2) {   // transfer and transform in groups as bj_prove does, but ONE leaf kernel at the end: the sibling lane's kernels
                        // cover the transfer, so nothing is gained by absorbing group by group (extra launches, capacity round trips)
         const HostWitness hw{h_variables, h_multiplicities, env().prove_h2d_group, true};
-        return prove_impl(ctx, S, ctx->wit_stage, ctx->wit_stage + vw, h_public_values, out, &hw);
+        return prove_impl(ctx, S, ctx->wit_stage, ctx->wit_stage + vw, h_public_values, out, &hw, h_multiplicities == nullptr);
     }
     BJ_HIP(ctx, hipMemcpyAsync(ctx->wit_stage, h_variables, vw * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (S->lookup_reps) BJ_HIP(ctx, hipMemcpyAsync(ctx->wit_stage + vw, h_multiplicities, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = prove_impl(ctx, S, ctx->wit_stage, ctx->wit_stage + vw, h_public_values, out, nullptr);
+    if (S->lookup_reps && h_multiplicities) BJ_HIP(ctx, hipMemcpyAsync(ctx->wit_stage + vw, h_multiplicities, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = prove_impl(ctx, S, ctx->wit_stage, ctx->wit_stage + vw, h_public_values, out, nullptr, h_multiplicities == nullptr);
     (void)hipStreamSynchronize(ctx->stream);   // no queued copy may read the caller's witness after this returns
     return rc;
 }

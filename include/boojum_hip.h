@@ -456,6 +456,20 @@ int bj_sigmas_from_placement(bj_ctx *ctx, const uint64_t *d_placement, size_t pl
 int bj_lookup_polys(bj_ctx *ctx, const uint64_t *d_lookup_vars, size_t var_stride, const uint64_t *d_table_id,
                     const uint64_t *d_tables, size_t table_stride, const uint64_t *d_multiplicities, unsigned reps, unsigned width,
                     unsigned log_n, const uint64_t *h_beta, const uint64_t *h_gamma, uint64_t *d_A, uint64_t *d_B);
+/* The multiplicity column bj_lookup_polys takes, counted on the device: d_multiplicities[r] = number of (sub-argument, row) pairs
+ * whose tuple (width cells, then the table id) equals table row r.  It replaces the counters the reference accumulates as a side
+ * effect of synthesis (lookup_multiplicities, src/cs/implementations/reference_cs.rs:54 and cs.rs:818, flattened by
+ * materialize_multiplicities_polynomials, witness.rs:225-272) and the hash map a host without that constraint system has to run
+ * over n * reps tuples.  Columns and d_table_id == NULL as for bj_lookup_polys; cells canonical or not.  Equal table rows (the
+ * all-zero padding rows behind the tables among them) form one class: its count goes to its smallest row, its other rows get 0 —
+ * the reference's column wherever table rows are distinct, and one the lookup argument accepts in every case.  Every word of
+ * d_multiplicities [n] is written, canonical.  A tuple that is in no table row: BJ_ERR_INVALID_ARG, bj_last_error names the
+ * smallest (row, sub-argument) and the number of such lookups, the output is unspecified.  Limits, BJ_ERR_UNSUPPORTED: log_n <= 30,
+ * width <= 15.  Runs on the context's stream, in the context's scratch, and synchronises (the number of misses is read); no input
+ * is written.  Not while a proof runs on the context. */
+int bj_lookup_multiplicities(bj_ctx *ctx, const uint64_t *d_lookup_vars, size_t var_stride, const uint64_t *d_table_id,
+                             const uint64_t *d_tables, size_t table_stride, unsigned reps, unsigned width, unsigned log_n,
+                             uint64_t *d_multiplicities);
 /* Gate terms of the quotient numerator at num_points LDE points (prover.rs:1031-1080 with buffering_source.rs:133-362 and
  * the selectors of prover.rs:2775-2916): out = sum_g selector_g * sum_t alpha_t * term_t for the hand-written evaluators
  * (kinds 1..4, and BJ_GATE_POSEIDON_FLATTENED over the first 130 columns) and for op lists without witness columns
@@ -676,7 +690,9 @@ int bj_prove_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_
                         bj_proof **out);
 
 /* WitnessSet (witness.rs:21-27) in: variables, then the non-copiable witness columns: [num_vars + num_witness_cols][n] natural
- * order, multiplicities [n] (NULL without lookups),
+ * order, multiplicities [n] (NULL without lookups; NULL with lookups: the column is counted on the device as by
+ * bj_setup_lookup_multiplicities below, once the lookup columns are resident and before the witness is committed — it replaces
+ * the host-side count — and a tuple that is in no table row refuses the proof with that call's message),
  * public input values in location order.  Proof out (bj_proof_serialize).  Returns BJ_ERR_INVALID_ARG with
  * "constraint system is not satisfied" where the reference panics "unsatisfied" (prover.rs:1425-1438). */
 int bj_prove(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_variables, const uint64_t *h_multiplicities,
@@ -684,6 +700,11 @@ int bj_prove(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_variables, co
 /* same with the witness already resident in HBM ([num_vars + num_witness_cols][n] contiguous; not modified) */
 int bj_prove_dev(bj_ctx *ctx, const bj_setup *setup, const uint64_t *d_variables, const uint64_t *d_multiplicities,
                  const uint64_t *h_public_values, bj_proof **out);
+/* bj_lookup_multiplicities on a setup: d_variables as for bj_prove_dev, the tables and the table id from the setup's replicated
+ * natural-order columns; out d_multiplicities [n].  It replaces the multiplicities argument of bj_prove / bj_prove_dev /
+ * bj_prove_async for a host that does not run the reference's constraint system (WitnessSet::multiplicities, witness.rs:21-27).
+ * A setup without lookups is BJ_ERR_INVALID_ARG.  Works on a sharded setup (replicated columns only, no communication). */
+int bj_setup_lookup_multiplicities(bj_ctx *ctx, const bj_setup *setup, const uint64_t *d_variables, uint64_t *d_multiplicities);
 /* ---- where a witness fails: CSReferenceAssembly::check_if_satisfied (src/cs/implementations/satisfiability_test.rs:15-353) ----
  * bj_prove refuses an unsatisfied witness only after the quotient stage and names nothing; a wrong lookup or multiplicity it
  * does not notice at all.  bj_check_satisfied evaluates every term of every gate on its rows and both sides of the lookup
@@ -740,7 +761,8 @@ int bj_check_satisfied_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void
  * FRI tail, transcript round trips) of proof k-1: throughput of the drop-in call >= the rate of bj_prove_dev on a resident
  * witness; every proof is byte for byte what bj_prove returns.  At most two proofs are in flight — a third submission blocks
  * until the lane it is due on is free.  h_variables / h_multiplicities (pinned host memory for full PCIe speed) must stay
- * valid and unchanged until bj_proof_wait returns; h_public_values is copied.  Errors of the proof (unsatisfied witness, out
+ * valid and unchanged until bj_proof_wait returns (h_multiplicities NULL as for bj_prove: each lane counts the column in its own
+ * scratch); h_public_values is copied.  Errors of the proof (unsatisfied witness, out
  * of memory) come back from bj_proof_wait with the text in bj_last_error(ctx).  Every ticket must be waited for exactly once.
  * Memory: each lane holds a workspace of its own (bj_proof_workspace_bytes); bj_ctx_release_workspace frees the lanes' too.
  * Single-device setups only (a sharded proof is a collective: its ranks are already concurrent). */
@@ -762,7 +784,8 @@ int bj_proof_stage_ms(const bj_proof *p, float *out8);
 /* Per-kernel measurements of the proof (measurement only; SURVEY §8d "each evidenced by ... HBM GB/s against the roofline"): the
  * FIRST launch inside this proof of each probed kernel — "quotient_gates" (prover.rs:1031-1080), "quotient_copy_perm"
  * (copy_permutation.rs:1000-1249), "barycentric_eval" (utils.rs:907-1242; the set at z), "deep_accumulate_multi"
- * (prover.rs:2523-2706), "fri_fold_first" (fri/mod.rs:362-678) — bracketed by HIP events on the launch stream: its duration in
+ * (prover.rs:2523-2706), "fri_fold_first" (fri/mod.rs:362-678), and in a proof that counts its multiplicity column
+ * "lookup_index_build" and "lookup_count" (bj_lookup_multiplicities; bytes: the table / looked-up columns read once) — bracketed by HIP events on the launch stream: its duration in
  * ms and the algorithmic bytes of that launch by SURVEY §8d's per-unit figures.  index = 0, 1, ... until BJ_ERR_INVALID_ARG;
  * *name points to a string with static storage.  Any out pointer may be NULL. */
 int bj_proof_kernel_stats(const bj_proof *p, unsigned index, const char **name, float *ms, double *algorithmic_bytes);

@@ -415,7 +415,7 @@ impl<P: crate::field::traits::field_like::PrimeFieldLikeVectorized<Base = F>, CF
         assert_eq!(variables.len(), setup.num_vars);
         // the non-copiable witness columns travel right behind the variable columns (leaf = variables || witness || multiplicities)
         let vars = flatten(variables.iter().chain(witness.iter()).map(|p| &p.storage[..]), setup.n);
-        let mult = flatten(multiplicities.iter().map(|p| &p.storage[..]), setup.n);
+        let mult = flatten(multiplicities.iter().map(|p| &p.storage[..]), setup.n);   // bj_prove also accepts None (NULL) here and counts the column on the device
         let publics: Vec<u64> = public_inputs_values.iter().map(|el| el.as_u64_reduced()).collect();
         let mut proof = std::ptr::null_mut();
         ctx.check(unsafe {
