@@ -126,6 +126,12 @@ _SIGNATURES = {
     "bj_check_satisfied": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bj_check_satisfied_from_dumps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
                                                 C.c_void_p]),
+    "bj_vk_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "bj_vk_from_setup": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "bj_vk_destroy": (None, [C.c_void_p]),
+    "bj_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p]),
+    "bj_verify_proof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bj_verify_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "bj_proof_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bj_proof_workspace_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "bj_proof_kernel_stats": (C.c_int, [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -970,6 +976,128 @@ class PeerComm:
             pass
 
 
+def circuit_struct(c, from_dump=False):
+    """bj_circuit for a circuit of era_boojum_amd.synthetic.Circuit shape, and the ctypes objects it points into (keep them alive
+    for the call).  from_dump: paths, constant-column count, table-id column, quotient degree and non-residues are left to
+    bj_setup_create_from_dump."""
+    gates = (_GateDesc * len(c.gates))()
+    for i, g in enumerate(c.gates):
+        gates[i].kind = g.kind
+        gates[i].path_len = 0 if from_dump else len(g.path)
+        for b, bit in enumerate([] if from_dump else list(g.path)[:8]):
+            gates[i].path[b] = 1 if bit else 0
+        gates[i].num_repetitions, gates[i].var_stride, gates[i].const_stride, gates[i].num_terms = \
+            g.reps, g.var_stride, g.const_stride, g.num_terms
+        gates[i].wit_stride = getattr(g, "wit_stride", 0)
+        prog = getattr(g, "program", None)       # seam S3: evaluate this gate from its op list (gate_program.py)
+        if prog is not None and g.kind != 7:     # BJ_GATE_POSEIDON_FLATTENED: its program serves the host-side checks only
+            gates[i].kind = 5
+            gates[i].program = C.cast(C.pointer(prog.struct), C.c_void_p)
+    spec_list = list(getattr(c, "specialized_gates", []) or [])
+    spec = (_GateDesc * max(1, len(spec_list)))()
+    for i, g in enumerate(spec_list):                # gates over specialized columns: op lists, no selector
+        spec[i].kind, spec[i].path_len = 5, 0
+        spec[i].num_repetitions, spec[i].var_stride, spec[i].const_stride, spec[i].num_terms = g.reps, g.var_stride, g.const_stride, g.num_terms
+        spec[i].program = C.cast(C.pointer(g.program.struct), C.c_void_p)
+    nr = np.array(c.non_residues, dtype=np.uint64)
+    cols = (C.c_uint * max(1, len(c.public_inputs)))(*[p[0] for p in c.public_inputs])
+    rows = (C.c_uint * max(1, len(c.public_inputs)))(*[p[1] for p in c.public_inputs])
+    cc = _Circuit(c.log_n, c.num_vars, c.num_gp_vars, int(getattr(c, "num_witness_cols", 0)), 0 if from_dump else c.num_constant_cols,
+                  c.lookup_width, c.lookup_reps, 0 if from_dump else c.table_id_col, 0 if from_dump else c.quotient_degree, len(c.gates), gates,
+                  None if from_dump else nr.ctypes.data_as(C.POINTER(C.c_uint64)), len(c.public_inputs),
+                  cols, rows, len(spec_list), spec if spec_list else None)
+    return cc, (gates, spec, nr, cols, rows)
+
+
+def proof_config_struct(fri_lde_factor, cap_size, security_level, pow_bits, transcript="poseidon2", tree_hasher=None, pow_runner="blake2s"):
+    """bj_proof_config; tree_hasher None pairs the transcript with its usual hasher (Transcript::CompatibleCap = TreeHasher::Output)."""
+    transcript_kind = {"poseidon2": 1, "poseidon": 2, "blake2s": 3, "keccak256": 4}[transcript]
+    if tree_hasher is None:
+        hasher_kind = {"blake2s": 2, "keccak256": 3}.get(transcript, 1)
+    else:
+        hasher_kind = {"poseidon2": 1, "blake2s": 2, "keccak256": 3, "poseidon": 4}[tree_hasher]
+    return _ProofConfig(fri_lde_factor, cap_size, security_level, pow_bits, transcript_kind, hasher_kind, {"blake2s": 1, "keccak256": 2}[pow_runner])
+
+
+class _VerifyReport(C.Structure):  # bj_verify_report
+    _fields_ = [("stage", C.c_uint32), ("query", C.c_uint32), ("oracle", C.c_uint32), ("queries_checked", C.c_uint32)]
+
+
+(VERIFY_OK, VERIFY_SHAPE, VERIFY_LOOKUP_SUM, VERIFY_QUOTIENT, VERIFY_POW, VERIFY_MERKLE, VERIFY_FRI_VALUE, VERIFY_FRI_MERKLE,
+ VERIFY_FINAL) = range(9)     # bj_verify_stage
+VERIFY_STAGE_NAMES = ["ok", "shape", "lookup_sum", "quotient", "pow", "merkle", "fri_value", "fri_merkle", "final"]
+VERIFY_PARTIAL_QUERIES = 1
+
+
+@dataclass
+class VerifyReport:
+    """bj_verify_report: true when the proof is valid under the key; otherwise the first failing check."""
+    stage: int = VERIFY_OK
+    query: int = 0
+    oracle: int = 0
+    queries_checked: int = 0
+
+    def __bool__(self):
+        return self.stage == VERIFY_OK
+
+    def __str__(self):
+        if self.stage == VERIFY_OK:
+            return "valid (%d queries)" % self.queries_checked
+        return "invalid: %s (query %d, oracle %d)" % (VERIFY_STAGE_NAMES[self.stage], self.query, self.oracle)
+
+
+class Verifier:
+    """A verification key (bj_vk) and bj_verify.  Making the key needs no device: Verifier(circuit, cap, config) with config a dict
+    of the keyword arguments of `proof_config_struct`; ProverSetup.verifier() takes the same key out of a setup."""
+
+    def __init__(self, circuit=None, cap=None, config=None, _handle=None, _lib=None):
+        self._lib = _lib or load_library()
+        if _handle is not None:
+            self._h = _handle
+            return
+        cc, keep = circuit_struct(circuit)
+        cfg = proof_config_struct(**config)
+        cap = np.ascontiguousarray(cap, dtype=np.uint64).reshape(-1)
+        if cap.size != 4 * int(cfg.cap_size):
+            raise BoojumHipError("bj_vk_create: the setup cap has %d words, cap_size %d needs %d" % (cap.size, cfg.cap_size, 4 * cfg.cap_size))
+        h = C.c_void_p()
+        rc = self._lib.bj_vk_create(C.byref(cc), _np_ptr(cap), C.byref(cfg), C.byref(h))
+        del keep
+        if rc != 0:
+            raise BoojumHipError("%s (%d): %s" % (self._lib.bj_status_string(rc).decode(), rc, self._lib.bj_last_error(None).decode()))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bj_vk_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def verify(self, ctx, buf, partial=False):
+        """bj_verify on the serialised proof words: a VerifyReport (true when valid).  partial: the buffer carries only the first
+        k > 0 query openings (BJ_VERIFY_PARTIAL_QUERIES)."""
+        a = np.ascontiguousarray(buf, dtype=np.uint64).reshape(-1)
+        if a.size == 0:
+            a = np.zeros(1, dtype=np.uint64)
+            n = 0
+        else:
+            n = a.size
+        r = _VerifyReport()
+        ctx._check(self._lib.bj_verify(ctx._h, self._h, _np_ptr(a), n, VERIFY_PARTIAL_QUERIES if partial else 0, C.byref(r)))
+        return VerifyReport(int(r.stage), int(r.query), int(r.oracle), int(r.queries_checked))
+
+    def kernel_ms(self, ctx):
+        """HIP-event durations (openings, DEEP + FRI) of the two kernels of the last verify on ctx."""
+        a, b = C.c_float(), C.c_float()
+        ctx._check(self._lib.bj_verify_kernel_ms(ctx._h, C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
+
 class _UnsatReport(C.Structure):  # bj_unsat_report
     _fields_ = [("kind", C.c_uint32), ("gate", C.c_uint32), ("repetition", C.c_uint32), ("term", C.c_uint32), ("row", C.c_uint64),
                 ("value", C.c_uint64), ("expected", C.c_uint64), ("failures", C.c_uint64 * 5)]
@@ -1036,41 +1164,12 @@ class ProverSetup:
         self._comm = comm
         self.fri_lde_factor, self.cap_size, self.security_level, self.pow_bits = fri_lde_factor, cap_size, security_level, pow_bits
         c = circuit
-        gates = (_GateDesc * len(c.gates))()
         from_dump = setup_base_dump is not None
-        for i, g in enumerate(c.gates):
-            gates[i].kind = g.kind
-            gates[i].path_len = 0 if from_dump else len(g.path)
-            for b, bit in enumerate([] if from_dump else g.path):
-                gates[i].path[b] = 1 if bit else 0
-            gates[i].num_repetitions, gates[i].var_stride, gates[i].const_stride, gates[i].num_terms = \
-                g.reps, g.var_stride, g.const_stride, g.num_terms
-            gates[i].wit_stride = getattr(g, "wit_stride", 0)
-            prog = getattr(g, "program", None)       # seam S3: evaluate this gate from its op list (gate_program.py)
-            if prog is not None and g.kind != 7:     # BJ_GATE_POSEIDON_FLATTENED: its program serves the host-side checks only
-                gates[i].kind = 5
-                gates[i].program = C.cast(C.pointer(prog.struct), C.c_void_p)
-        spec_list = list(getattr(c, "specialized_gates", []) or [])
-        spec = (_GateDesc * max(1, len(spec_list)))()
-        for i, g in enumerate(spec_list):                # gates over specialized columns: op lists, no selector
-            spec[i].kind, spec[i].path_len = 5, 0
-            spec[i].num_repetitions, spec[i].var_stride, spec[i].const_stride, spec[i].num_terms = g.reps, g.var_stride, g.const_stride, g.num_terms
-            spec[i].program = C.cast(C.pointer(g.program.struct), C.c_void_p)
-        nr = np.array(c.non_residues, dtype=np.uint64)
-        cols = (C.c_uint * max(1, len(c.public_inputs)))(*[p[0] for p in c.public_inputs])
-        rows = (C.c_uint * max(1, len(c.public_inputs)))(*[p[1] for p in c.public_inputs])
+        cc, self._keep = circuit_struct(c, from_dump)
         self.num_witness_cols = int(getattr(c, "num_witness_cols", 0))
-        cc = _Circuit(c.log_n, c.num_vars, c.num_gp_vars, self.num_witness_cols, 0 if from_dump else c.num_constant_cols, c.lookup_width,
-                      c.lookup_reps, 0 if from_dump else c.table_id_col, 0 if from_dump else c.quotient_degree, len(c.gates), gates,
-                      None if from_dump else nr.ctypes.data_as(C.POINTER(C.c_uint64)), len(c.public_inputs),
-                      cols, rows, len(spec_list), spec if spec_list else None)
-        self.transcript_kind = {"poseidon2": 1, "poseidon": 2, "blake2s": 3, "keccak256": 4}[transcript]
-        if tree_hasher is None:
-            self.hasher_kind = {"blake2s": 2, "keccak256": 3}.get(transcript, 1)  # Transcript::CompatibleCap = TreeHasher::Output
-        else:
-            self.hasher_kind = {"poseidon2": 1, "blake2s": 2, "keccak256": 3, "poseidon": 4}[tree_hasher]
-        cfg = _ProofConfig(fri_lde_factor, cap_size, security_level, pow_bits, self.transcript_kind, self.hasher_kind,
-                           {"blake2s": 1, "keccak256": 2}[pow_runner])
+        self.transcript, self.tree_hasher, self.pow_runner = transcript, tree_hasher, pow_runner
+        cfg = proof_config_struct(fri_lde_factor, cap_size, security_level, pow_bits, transcript, tree_hasher, pow_runner)
+        self.transcript_kind, self.hasher_kind = int(cfg.transcript), int(cfg.tree_hasher)
         con = np.ascontiguousarray(c.constants, dtype=np.uint64)
         tab = np.ascontiguousarray(c.tables, dtype=np.uint64)
         h = C.c_void_p()
@@ -1129,6 +1228,39 @@ class ProverSetup:
         self._ctx._check(self._lib.bj_setup_cap(self._h, _np_ptr(out)))
         return out
 
+    def config(self):
+        """The proof config as the keyword arguments of `proof_config_struct` / the `config` of `Verifier`."""
+        return dict(fri_lde_factor=self.fri_lde_factor, cap_size=self.cap_size, security_level=self.security_level, pow_bits=self.pow_bits,
+                    transcript=self.transcript, tree_hasher=self.tree_hasher, pow_runner=self.pow_runner)
+
+    def verifier(self):
+        """The verification key of this setup (bj_vk_from_setup)."""
+        h = C.c_void_p()
+        self._ctx._check(self._lib.bj_vk_from_setup(self._h, C.byref(h)))
+        return Verifier(_handle=h, _lib=self._lib)
+
+    def verify(self, buf, partial=False):
+        """bj_verify of serialised proof words under this setup's key: a VerifyReport."""
+        vk = self.verifier()
+        try:
+            return vk.verify(self._ctx, buf, partial)
+        finally:
+            vk.close()
+
+    def prove_verified(self, vk, variables=None, multiplicities=None, public_values=None, count_multiplicities=False):
+        """Service-side convenience, and the binding of bj_verify_proof: bj_prove, then the check of the handle it returned under
+        the key `vk` (a Verifier), before the proof is serialised — what a proving service does with every proof it ships.
+        Arguments as for `prove`.  Returns (serialised proof, VerifyReport); the proof is returned whatever the verdict."""
+        c = self.circuit
+        v, m, pv = self._host_witness(variables, multiplicities, public_values)
+        h = C.c_void_p()
+        self._ctx._check(self._lib.bj_prove(self._ctx._h, self._h, _np_ptr(v), _np_ptr(m) if c.lookup_reps and not count_multiplicities else None, _np_ptr(pv), C.byref(h)))
+        r = _VerifyReport()
+        rc = self._lib.bj_verify_proof(self._ctx._h, vk._h, h, C.byref(r))
+        buf, _ = self._finish(h)
+        self._ctx._check(rc)
+        return buf, VerifyReport(int(r.stage), int(r.query), int(r.oracle), int(r.queries_checked))
+
     def _finish(self, h):
         n = self._lib.bj_proof_size_u64(h)
         buf = np.empty(n, dtype=np.uint64)
@@ -1156,9 +1288,9 @@ class ProverSetup:
         stages["witness_tree_leaf_kernel"] = float(ms[7])
         return buf, stages
 
-    def prove(self, variables=None, multiplicities=None, public_values=None, count_multiplicities=False):
-        """Host-memory entry point (bj_prove): returns (serialised proof u64 array, per-stage ms).  count_multiplicities: no column
-        is handed over (NULL), the prover counts it on the device."""
+    def _host_witness(self, variables, multiplicities, public_values):
+        """The host arrays bj_prove / bj_prove_async take (variables with the witness columns behind them, multiplicities, public
+        values); every argument defaults to the circuit's own."""
         c = self.circuit
         v = np.ascontiguousarray(c.variables if variables is None else variables, dtype=np.uint64)
         if self.num_witness_cols and v.shape[0] == c.num_vars:     # the non-copiable witness columns travel behind the variables
@@ -1167,6 +1299,13 @@ class ProverSetup:
         pv = np.array([p[2] for p in c.public_inputs] if public_values is None else public_values, dtype=np.uint64)
         if pv.size == 0:
             pv = np.zeros(1, dtype=np.uint64)
+        return v, m, pv
+
+    def prove(self, variables=None, multiplicities=None, public_values=None, count_multiplicities=False):
+        """Host-memory entry point (bj_prove): returns (serialised proof u64 array, per-stage ms).  count_multiplicities: no column
+        is handed over (NULL), the prover counts it on the device."""
+        c = self.circuit
+        v, m, pv = self._host_witness(variables, multiplicities, public_values)
         h = C.c_void_p()
         self._ctx._check(self._lib.bj_prove(self._ctx._h, self._h, _np_ptr(v), _np_ptr(m) if c.lookup_reps and not count_multiplicities else None,
                                             _np_ptr(pv), C.byref(h)))
@@ -1177,13 +1316,7 @@ class ProverSetup:
         are used in place when they are contiguous uint64 (e.g. views of pinned tensors) and kept alive by the ticket.
         count_multiplicities: as for `prove`."""
         c = self.circuit
-        v = np.ascontiguousarray(c.variables if variables is None else variables, dtype=np.uint64)
-        if self.num_witness_cols and v.shape[0] == c.num_vars:
-            v = np.ascontiguousarray(np.concatenate([v, c.witness], axis=0))
-        m = np.ascontiguousarray(c.multiplicities if multiplicities is None else multiplicities, dtype=np.uint64)
-        pv = np.array([p[2] for p in c.public_inputs] if public_values is None else public_values, dtype=np.uint64)
-        if pv.size == 0:
-            pv = np.zeros(1, dtype=np.uint64)
+        v, m, pv = self._host_witness(variables, multiplicities, public_values)
         t = C.c_void_p()
         self._ctx._check(self._lib.bj_prove_async(self._ctx._h, self._h, _np_ptr(v), _np_ptr(m) if c.lookup_reps and not count_multiplicities else None,
                                                   _np_ptr(pv), C.byref(t)))

@@ -16,6 +16,12 @@ using gl::u64;
 
 namespace bj {
 
+// message of the last failed call that has no context (bj_vk_create), per host thread: bj_last_error(NULL)
+static std::string &thread_error() {
+    static thread_local std::string e;
+    return e;
+}
+
 int fail(bj_ctx *ctx, int code, const char *fmt, ...) {
     char buf[512];
     va_list ap;
@@ -23,6 +29,7 @@ int fail(bj_ctx *ctx, int code, const char *fmt, ...) {
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
     if (ctx) ctx->err = buf;
+    else thread_error() = buf;
     return code;
 }
 
@@ -291,6 +298,8 @@ void bj_ctx_destroy(bj_ctx *ctx) {
     if (ctx->arena) (void)hipFree(ctx->arena);
     for (auto &sl : ctx->arena_slabs) (void)hipFree(sl.first);
     if (ctx->h_ring) (void)hipHostFree(ctx->h_ring);
+    for (auto &e : ctx->verify_ev)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     delete ctx;
@@ -327,7 +336,10 @@ int bj_ctx_set_stream(bj_ctx *ctx, void *hip_stream) {
     return BJ_OK;
 }
 
-const char *bj_last_error(const bj_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
+const char *bj_last_error(const bj_ctx *ctx) {
+    if (ctx) return ctx->err.c_str();
+    return bj::thread_error().empty() ? "null context" : bj::thread_error().c_str();
+}
 
 int bj_sync(bj_ctx *ctx) {
     if (int rc = bind(ctx)) return rc;

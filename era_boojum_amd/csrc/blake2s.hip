@@ -12,6 +12,7 @@
 #include "gl.h"
 #include "kernels.h"
 #include "tree_plan.h"
+#include "verify_open.h"
 
 using gl::u64;
 using gl::u32;
@@ -150,6 +151,47 @@ __global__ void __launch_bounds__(256) blake2s_nodes_kernel(const u64 *prev, u64
     st.store(next + 4 * i);
 }
 
+// bj_verify: one (query, oracle) Merkle chain per lane (verify_open.h) over the leaf and node hashes above
+struct B2sVerifyHasher {
+    static __device__ __forceinline__ void digest(const B2s &st, u64 (&d)[4]) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = gl::pack(st.h[2 * k], st.h[2 * k + 1]);
+    }
+    static __device__ __forceinline__ void leaf(const u64 *w, unsigned n, u64 (&d)[4]) {
+        B2s st;
+        st.init();
+        const unsigned n_blocks = n ? (n + 7) / 8 : 1;
+        for (unsigned b = 0; b < n_blocks; b++) {
+            u32 m[16];
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const unsigned c = b * 8 + k;
+                const u64 v = c < n ? gl::canon(w[c]) : 0;
+                m[2 * k] = gl::lo32(v);
+                m[2 * k + 1] = gl::hi32(v);
+            }
+            const bool last = b + 1 == n_blocks;
+            st.compress(m, last ? (u64)n * 8 : (u64)(b + 1) * 64, last);
+        }
+        digest(st, d);
+    }
+    static __device__ __forceinline__ void node(const u64 (&l)[4], const u64 (&r)[4], u64 (&d)[4]) {
+        u32 m[16];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            m[2 * k] = gl::lo32(l[k]);
+            m[2 * k + 1] = gl::hi32(l[k]);
+            m[8 + 2 * k] = gl::lo32(r[k]);
+            m[8 + 2 * k + 1] = gl::hi32(r[k]);
+        }
+        B2s st;
+        st.init();
+        st.compress(m, 64, true);
+        digest(st, d);
+    }
+};
+__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) blake2s_verify_openings_kernel(VerifyOpenArgs A) { verify_open_bytes<B2sVerifyHasher>(A); }
+
 // Proof of work (impl PoWRunner for Blake2s256, src/cs/implementations/pow.rs:50-133): the smallest nonce such that the
 // first 8 digest bytes of Blake2s(seed || le64(nonce)), read as a little-endian u64, have >= pow_bits trailing zeros.
 // seed = 5 field elements = 40 bytes, so seed || nonce is one 48-byte block.  lane = nonce; the minimum over the launch.
@@ -196,8 +238,11 @@ static void launch_blake2s_leaves_chunked(const u64 *d_src0, const u64 *d_src1, 
 static void launch_blake2s_nodes(const u64 *d_children, u64 *d_parents, size_t num_parents, hipStream_t s) {
     launch_1d(blake2s_nodes_kernel, num_parents, s, d_children, d_parents, num_parents);
 }
+static void launch_blake2s_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
+    hipLaunchKernelGGL(blake2s_verify_openings_kernel, dim3((A.n_queries + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
+}
 TreeHasher blake2s_tree_hasher() {
-    return {launch_blake2s_leaves, launch_blake2s_leaves_chunked, launch_blake2s_nodes, nullptr};
+    return {launch_blake2s_leaves, launch_blake2s_leaves_chunked, launch_blake2s_nodes, nullptr, launch_blake2s_verify_openings};
 }
 
 }  // namespace bj

@@ -70,6 +70,9 @@ struct bj_ctx {
     } probes[BJ_MAX_KERNEL_PROBES];
     unsigned probe_n = 0;
     bj::Pipeline *pipe = nullptr;   // bj_prove_async: created on first use, destroyed with the context
+    // bj_verify: events around its two kernels (created on first use), read by bj_verify_kernel_ms
+    hipEvent_t verify_ev[4] = {};
+    bool verify_timed = false;      // the last bj_verify on this context launched its kernels
 };
 
 namespace bj {
@@ -77,7 +80,9 @@ namespace bj {
 // already probed in this proof, or table full — the caller just launches); probe_end records the closing event
 int probe_begin(bj_ctx *ctx, const char *name, double algorithmic_bytes);
 void probe_end(bj_ctx *ctx, int idx);
-int fail(bj_ctx *ctx, int code, const char *fmt, ...);
+int fail(bj_ctx *ctx, int code, const char *fmt, ...);   // ctx == nullptr (host-only calls): the message goes to the calling thread's slot
+// setup.hip: what bj_setup_create refuses about a circuit description and a proof config (no device work); `who` starts the messages
+int circuit_check(bj_ctx *ctx, const char *who, const bj_circuit *c, const bj_proof_config *cfg, bool has_tables, const bj_comm *comm);
 int bind(bj_ctx *ctx);
 // host block -> device, ordered on ctx->stream like a kernel launch; returns without waiting (h_src may be reused at once)
 int h2d_async(bj_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);

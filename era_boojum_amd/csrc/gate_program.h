@@ -2,6 +2,9 @@
 #pragma once
 #include "ctx.h"
 #include "gate_body_rt.h"
+#include "gate_canon.h"
+
+#include <vector>
 
 // slots of the interpreter's private (scratch-memory) variant; the canonical form of gate_canon.h needs far fewer for every
 // evaluator of the reference (13 for a 12 x 12 matrix gate, ~40 for the Poseidon2 flattened capture); a program whose
@@ -20,9 +23,13 @@ struct DevProgram {
     unsigned var_extent = 0, const_extent = 0, wit_extent = 0;
     uint64_t fp[2] = {0, 0};      // structural fingerprint (gate_canon.h): selects a generated kernel when one exists
     const JitKernel *jit = nullptr;   // compiled at upload when no generated kernel exists (owned by the process-wide cache)
+    std::vector<DevRelation> h_rel;   // host copy of what d_rel / d_values hold: a verification key takes its op lists from here
+    std::vector<gl::u64> h_values;
     int upload(bj_ctx *ctx, const bj_gate_program *p);   // canonicalises, packs and copies the program
     void release();
 };
+// the canonical program in the interpreter's packed form (operands kind << 28 | slot or index, OP_WRITE pseudo relations)
+void pack_program(const canon::Program &C, std::vector<DevRelation> *rel, std::vector<gl::u64> *values);
 // highest variable / constant column index (relative to the repetition) the program reads, + 1; 0 if it reads none
 void gate_program_extent(const bj_gate_program *p, unsigned *var_extent, unsigned *const_extent, unsigned *wit_extent = nullptr);
 // quotient mode (d_alphas != nullptr): out += selector * sum alpha * term; stand-alone mode (d_terms != nullptr): raw terms

@@ -111,23 +111,29 @@ void gate_program_extent(const bj_gate_program *p, unsigned *var_extent, unsigne
 // Whatever numbering and order the host's list has (the reference hands over one fresh temporary per operation from a
 // process-wide counter, gpu_synthesizer/mod.rs:210-352), the device sees the canonical schedule of gate_canon.h: slots by
 // live range, and a fingerprint of the evaluator's function that finds a generated kernel or names the one compiled here.
+void pack_program(const canon::Program &C, std::vector<DevRelation> *rel, std::vector<u64> *values) {
+    auto pack = [&](const canon::Operand &x) -> uint32_t {
+        return (x.kind << 28) | (x.kind == BJ_IDX_TEMPORARY ? C.slot_of[x.index] : x.index);
+    };
+    rel->resize(C.nodes.size());
+    for (size_t i = 0; i < C.nodes.size(); i++) {
+        const canon::Node &n = C.nodes[i];
+        const bool binary = n.op == BJ_OP_ADD || n.op == BJ_OP_SUB || n.op == BJ_OP_MUL;
+        (*rel)[i] = DevRelation{n.op, n.dst, pack(n.a), binary ? pack(n.b) : 0u};
+    }
+    *values = C.values;
+    if (values->empty()) values->push_back(0);
+}
+
 int DevProgram::upload(bj_ctx *ctx, const bj_gate_program *p) {
     canon::Program C;
     std::string err;
     if (int rc = canon::canonicalize(p, &C, &err)) return fail(ctx, rc, "%s", err.c_str());
     if (C.num_slots > (unsigned)BJ_GATE_PROGRAM_MAX_SLOTS)
         return fail(ctx, BJ_ERR_UNSUPPORTED, "gate program: %u values live at once (at most %d)", C.num_slots, BJ_GATE_PROGRAM_MAX_SLOTS);
-    auto pack = [&](const canon::Operand &x) -> uint32_t {
-        return (x.kind << 28) | (x.kind == BJ_IDX_TEMPORARY ? C.slot_of[x.index] : x.index);
-    };
-    std::vector<DevRelation> rel(C.nodes.size());
-    for (size_t i = 0; i < C.nodes.size(); i++) {
-        const canon::Node &n = C.nodes[i];
-        const bool binary = n.op == BJ_OP_ADD || n.op == BJ_OP_SUB || n.op == BJ_OP_MUL;
-        rel[i] = DevRelation{n.op, n.dst, pack(n.a), binary ? pack(n.b) : 0u};
-    }
-    std::vector<u64> vals = C.values;
-    if (vals.empty()) vals.push_back(0);
+    pack_program(C, &h_rel, &h_values);
+    const std::vector<DevRelation> &rel = h_rel;
+    const std::vector<u64> &vals = h_values;
     n_rel = (unsigned)rel.size();
     n_tmp = C.num_slots;
     n_writes = C.num_terms;

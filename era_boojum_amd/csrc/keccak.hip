@@ -8,6 +8,7 @@
 #include "gl.h"
 #include "kernels.h"
 #include "tree_plan.h"
+#include "verify_open.h"
 
 using gl::u64;
 using gl::u32;
@@ -147,6 +148,40 @@ __global__ void __launch_bounds__(256) keccak_nodes_kernel(const u64 *prev, u64 
     st.store(next + 4 * i);
 }
 
+// bj_verify: one (query, oracle) Merkle chain per lane (verify_open.h) over the leaf and node hashes above
+struct KeccakVerifyHasher {
+    static __device__ __forceinline__ void leaf(const u64 *w, unsigned n, u64 (&d)[4]) {
+        Keccak st;
+        st.init();
+        unsigned c = 0;
+        for (; c + 17 <= n; c += 17) {
+#pragma unroll
+            for (int k = 0; k < 17; k++) st.a[k] ^= gl::canon(w[c + k]);
+            keccak_f(st.a);
+        }
+        const unsigned rem = n - c;
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            if ((unsigned)k < rem) st.a[k] ^= gl::canon(w[c + k]);
+        st.pad_and_permute(rem);
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = st.a[k];
+    }
+    static __device__ __forceinline__ void node(const u64 (&l)[4], const u64 (&r)[4], u64 (&d)[4]) {
+        Keccak st;
+        st.init();
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            st.a[k] = l[k];
+            st.a[4 + k] = r[k];
+        }
+        st.pad_and_permute(8);
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = st.a[k];
+    }
+};
+__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) keccak_verify_openings_kernel(VerifyOpenArgs A) { verify_open_bytes<KeccakVerifyHasher>(A); }
+
 // Proof of work (impl PoWRunner for Keccak256, src/cs/implementations/pow.rs:139-230): the smallest nonce such that the first
 // 8 digest bytes of Keccak256(seed || le64(nonce)), read as a little-endian u64, have >= pow_bits trailing zeros.  seed = 5 field
 // elements = 40 bytes, so seed || nonce is six lanes of one rate block; lane = nonce, the minimum over the launch.
@@ -187,8 +222,11 @@ static void launch_keccak_leaves_chunked(const u64 *d_src0, const u64 *d_src1, u
 static void launch_keccak_nodes(const u64 *d_children, u64 *d_parents, size_t num_parents, hipStream_t s) {
     launch_1d(keccak_nodes_kernel, num_parents, s, d_children, d_parents, num_parents);
 }
+static void launch_keccak_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
+    hipLaunchKernelGGL(keccak_verify_openings_kernel, dim3((A.n_queries + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
+}
 TreeHasher keccak_tree_hasher() {
-    return {launch_keccak_leaves, launch_keccak_leaves_chunked, launch_keccak_nodes, nullptr};
+    return {launch_keccak_leaves, launch_keccak_leaves_chunked, launch_keccak_nodes, nullptr, launch_keccak_verify_openings};
 }
 
 }  // namespace bj

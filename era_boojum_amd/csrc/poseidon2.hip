@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include "poseidon_rc.inc"
 #include "sponge_tree.h"
+#include "verify_open.h"
 
 using gl::u64;
 using gl::u32;
@@ -379,6 +380,12 @@ poseidon2_leaves_chunked_lanepar_kernel(const u64 *src0, const u64 *src1, unsign
     if (live && l < 4) digests[4 * j + l] = gl::canon(s);
 }
 
+// bj_verify: one (query, oracle) Merkle chain per lane (verify_open.h)
+__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) poseidon2_verify_openings_kernel(VerifyOpenArgs A) { verify_open_sponge<poseidon2_permutation>(A); }
+static void launch_poseidon2_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
+    hipLaunchKernelGGL(poseidon2_verify_openings_kernel, dim3((A.n_queries + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
+}
+
 __global__ void poseidon2_permute_states_kernel(u64 *states, size_t n_states) { sponge_permute_states<poseidon2_permutation>(states, n_states); }
 
 // layers and oracles of up to bj::env().nodes_lanepar_max items are latency-bound: the lane-parallel kernels, one item per
@@ -408,7 +415,8 @@ static void launch_poseidon2_leaves_absorb(const u64 *d_base, size_t col_stride,
               first, last);
 }
 TreeHasher poseidon2_tree_hasher() {
-    return {launch_poseidon2_leaves, launch_poseidon2_leaves_chunked, launch_poseidon2_nodes, launch_poseidon2_leaves_absorb};
+    return {launch_poseidon2_leaves, launch_poseidon2_leaves_chunked, launch_poseidon2_nodes, launch_poseidon2_leaves_absorb,
+            launch_poseidon2_verify_openings};
 }
 
 void launch_poseidon2_permute_states(u64 *d_states, size_t n_states, hipStream_t s) {

@@ -72,6 +72,7 @@ struct StageTimer {
 }  // namespace
 
 namespace bj {
+const std::vector<u64> &proof_words(const bj_proof *p) { return p->data; }   // bj_verify_proof (verifier.hip)
 int all_gather(bj_ctx *ctx, const Shard &sh, const u64 *d_send, u64 *d_recv, size_t elems) {
     if (!elems) return BJ_OK;
     if (sh.world == 1) {

@@ -54,6 +54,162 @@ int bj_setup_create_sharded(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_
 void bj::setup_adopt_placement(bj_setup *s, uint32_t *d_placement) { s->d_placement = d_placement; }
 const uint32_t *bj::setup_placement(const bj_setup *s) { return s->d_placement; }
 
+// Everything bj_setup_create refuses about a circuit description and a proof config, without touching a device: the geometry,
+// the config, the sharding requirements (comm != nullptr), every gate descriptor with the column ranges it will form, and the op
+// lists, which are brought into canonical form here (a malformed list is refused with the canonicaliser's message).  bj_vk_create
+// runs the same function, so a key is refused exactly where a setup is, in the same words after the caller's name.
+#define BJ_WHO "%s: "
+#define BJ_WHO_SHARDED "%s_sharded: "
+static int check_program(bj_ctx *ctx, const bj_gate_program *p) {
+    bj::canon::Program C;
+    std::string err;
+    if (int rc = bj::canon::canonicalize(p, &C, &err)) return bj::fail(ctx, rc, "%s", err.c_str());
+    if (C.num_slots > (unsigned)BJ_GATE_PROGRAM_MAX_SLOTS)
+        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "gate program: %u values live at once (at most %d)", C.num_slots, BJ_GATE_PROGRAM_MAX_SLOTS);
+    return BJ_OK;
+}
+
+int bj::circuit_check(bj_ctx *ctx, const char *who, const bj_circuit *c, const bj_proof_config *cfg, bool has_tables, const bj_comm *comm) {
+    if (c->log_n < 1 || c->log_n > 26) return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "log_n out of range", who);
+    if (c->num_gates == 0 || c->num_gates > 16 || !c->gates) return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "1..16 gates expected", who);
+    if (!bj::is_pow2(c->quotient_degree) || !bj::is_pow2(cfg->fri_lde_factor) || cfg->fri_lde_factor < 2 ||
+        !bj::is_pow2(cfg->cap_size))
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "quotient degree / fri_lde_factor / cap must be powers of two", who);
+    {
+        const unsigned tk = cfg->transcript ? cfg->transcript : BJ_TRANSCRIPT_POSEIDON2, hk = cfg->tree_hasher ? cfg->tree_hasher : BJ_HASHER_POSEIDON2;
+        if (tk > BJ_TRANSCRIPT_KECCAK256 || hk > BJ_HASHER_POSEIDON) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, BJ_WHO "unknown transcript / tree hasher", who);
+        const bool byte_hasher = hk == BJ_HASHER_BLAKE2S || hk == BJ_HASHER_KECCAK256,
+                   byte_transcript = tk == BJ_TRANSCRIPT_BLAKE2S || tk == BJ_TRANSCRIPT_KECCAK256;
+        if (byte_hasher != byte_transcript)   // Transcript::CompatibleCap = TreeHasher::Output (prover.rs:153-168)
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "a byte tree hasher (Blake2s / Keccak256) goes with a byte transcript and "
+                                                     "an algebraic tree hasher (Poseidon2 / Poseidon) with an algebraic transcript", who);
+    }
+    if (cfg->fri_lde_factor > 64 || c->quotient_degree > 64)   // per-coset tables of the quotient kernels hold 64 entries
+        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, BJ_WHO "fri_lde_factor and quotient_degree are limited to 64", who);
+    if (c->num_public_inputs && (!c->public_input_cols || !c->public_input_rows))
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "public input locations missing", who);
+    for (unsigned i = 0; i < c->num_public_inputs; i++)
+        if (c->public_input_cols[i] >= c->num_vars || (c->public_input_rows[i] >> c->log_n) != 0)
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "public input %u at (column %u, row %u) is outside the %u x 2^%u trace", who,
+                            i, c->public_input_cols[i], c->public_input_rows[i], c->num_vars, c->log_n);
+    if (cfg->pow_bits > 32 || cfg->pow_bits >= cfg->security_level)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "pow_bits must be <= 32 and below the security level (pow.rs:53, prover.rs:2293)", who);
+    if (cfg->pow_runner > BJ_POW_KECCAK256)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "pow_runner %u (0 / BJ_POW_BLAKE2S256 / BJ_POW_KECCAK256)", who, cfg->pow_runner);
+    // LookupParameters::UseSpecializedColumnsWithTableIdAsVariable (cs/mod.rs:237-241): table_ids_column_idxes is empty (setup.rs:970-971)
+    // and a sub-argument owns width + 1 variable columns, the last one the table id (lookup_argument_in_ext.rs:354-366, 949-1000)
+    const bool tid_var = c->lookup_reps && c->table_id_col == BJ_TABLE_ID_AS_VARIABLE;
+    const unsigned lookup_cps = c->lookup_width + (tid_var ? 1u : 0u);
+    if (c->lookup_reps && (!has_tables || c->lookup_width == 0 || c->lookup_width > 8 || (!tid_var && c->table_id_col >= c->num_constant_cols)))
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "bad lookup parameters", who);
+    if ((uint64_t)c->num_vars < (uint64_t)c->num_gp_vars + (uint64_t)lookup_cps * c->lookup_reps || !c->non_residues)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "bad column counts", who);
+    if (c->num_vars > 4096)   // the copy-permutation quotient keeps k_c * beta of every column in LDS (16 bytes per column)
+        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, BJ_WHO "%u copiable columns, at most 4096 are supported", who, c->num_vars);
+    unsigned n_chunks = (c->num_vars + c->quotient_degree - 1) / c->quotient_degree;
+    if (n_chunks < 2) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, BJ_WHO "a single copy-permutation chunk is not supported", who);
+    if (comm && comm->world > 1) {
+        const unsigned W = comm->world;
+        if (!bj::is_pow2(W) || W > 8 || comm->rank >= W || (!comm->all_gather && !comm->all_gather_stream))
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO_SHARDED "world must be a power of two <= 8, rank < world, callback set", who);
+        if (cfg->fri_lde_factor % W || cfg->cap_size % W || c->quotient_degree > cfg->fri_lde_factor)
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO_SHARDED "world must divide fri_lde_factor and cap_size, and "
+                                                     "quotient_degree must not exceed fri_lde_factor", who);
+        const unsigned cl = cfg->fri_lde_factor / W;
+        if ((((size_t)1 << c->log_n) * cl) < cfg->cap_size / W)
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO_SHARDED "shard smaller than its cap fragment", who);
+        const size_t Qe_rank = ((size_t)c->quotient_degree << c->log_n) / W;   // every rank evaluates q n / W points of the quotient
+        if (Qe_rank < 2 || !bj::is_pow2(Qe_rank))                              // and inverse-transforms them: a power of two
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO_SHARDED "q n / world = %zu quotient points per rank (a power of two >= 2 is needed)", who, Qe_rank);
+    }
+    if (c->num_gates > 16)
+        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, BJ_WHO "%u gate types over general-purpose columns (at most 16)", who, c->num_gates);
+    for (unsigned g = 0; g < c->num_gates; g++) {
+        const bj_gate_desc &G = c->gates[g];
+        const bool p2 = G.kind == BJ_GATE_POSEIDON2_FLATTENED || G.kind == BJ_GATE_POSEIDON_FLATTENED;
+        if (G.kind < 1 || G.kind > BJ_GATE_POSEIDON_FLATTENED || G.path_len > 6 || (G.kind == BJ_GATE_PROGRAM && !G.program) ||
+            (p2 && (G.num_terms != 118 || G.num_repetitions != 1 || c->num_gp_vars < 130)) ||
+            (G.kind != BJ_GATE_PROGRAM && G.kind != BJ_GATE_NOP && !p2 && G.num_terms != 1))
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "bad gate descriptor %u", who, g);
+        {   // every column index the evaluator will form must exist: (reps - 1) * stride + the widest operand, after the selector path
+            unsigned var_extent = 0, const_extent = 0, wit_extent = 0;
+            bool const_per_rep = true;
+            switch (G.kind) {
+                case BJ_GATE_CONSTANT_ALLOCATOR: var_extent = 1; const_extent = 1; break;
+                case BJ_GATE_FMA_NO_CONSTANT: var_extent = 4; const_extent = 2; const_per_rep = false; break;
+                case BJ_GATE_REDUCTION4: var_extent = 5; const_extent = 4; const_per_rep = false; break;
+                case BJ_GATE_POSEIDON2_FLATTENED: var_extent = 130; break;
+                case BJ_GATE_POSEIDON_FLATTENED: var_extent = 130; break;
+                case BJ_GATE_PROGRAM: bj::gate_program_extent(G.program, &var_extent, &const_extent, &wit_extent); break;
+                default: break;
+            }
+            if (wit_extent && (size_t)(G.num_repetitions ? G.num_repetitions - 1 : 0) * G.wit_stride + wit_extent > c->num_witness_cols)
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "gate %u reads witness column %zu of %u", who, g,
+                                (size_t)(G.num_repetitions - 1) * G.wit_stride + wit_extent, c->num_witness_cols);
+            const size_t last = G.num_repetitions ? G.num_repetitions - 1 : 0;
+            const size_t var_end = var_extent ? last * G.var_stride + var_extent : 0;
+            const size_t const_end = G.path_len + (const_extent ? (const_per_rep ? last * G.const_stride : 0) + const_extent : 0);
+            if (G.kind != BJ_GATE_NOP && (G.num_repetitions == 0 || var_end > c->num_gp_vars || const_end > c->num_constant_cols))
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "gate %u reads variable column %zu / constant column %zu of %u / %u "
+                                "(repetitions x stride + operand index, after a selector path of %u)", who, g, var_end, const_end,
+                                c->num_gp_vars, c->num_constant_cols, G.path_len);
+            if (G.path_len > c->num_constant_cols)
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "gate %u: selector path longer than the constant columns", who, g);
+        }
+        if (G.kind == BJ_GATE_PROGRAM) {
+            if (G.program->num_writes != G.num_terms)
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "gate %u: program writes %u terms, descriptor says %u", who, g,
+                                G.program->num_writes, G.num_terms);
+            if (int prc = check_program(ctx, G.program)) return prc;
+        }
+    }
+    {   // gates over specialized columns (evaluator_data.rs:124-240, prover.rs:635-800): their variable columns follow the lookup ones
+        // in declaration order; their constant columns follow the general-purpose gates' ones and the table-id column (which is the
+        // first "special purpose" constant: setup.rs:963-1010), num_repetitions * const_stride columns each — every repetition its
+        // own principal_width.num_constants columns (share_constants = false, per_repetition_offset.constants_offset = that width)
+        // (64-bit sums: the sizes are the caller's, a wrapped 32-bit total must not pass the range checks)
+        uint64_t col = (uint64_t)c->num_gp_vars + (uint64_t)lookup_cps * c->lookup_reps;
+        uint64_t spec_consts = 0;
+        for (unsigned g = 0; c->specialized_gates && g < c->num_specialized_gates; g++) {
+            const uint64_t per_gate = (uint64_t)c->specialized_gates[g].num_repetitions * c->specialized_gates[g].const_stride;
+            if (per_gate > c->num_constant_cols) { spec_consts = (uint64_t)c->num_constant_cols + 1; break; }
+            spec_consts += per_gate;
+        }
+        if (spec_consts > c->num_constant_cols ||
+            (c->lookup_reps && !tid_var && (uint64_t)c->table_id_col + 1 + spec_consts != c->num_constant_cols))
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "%u constant columns declared; the specialized gates' %llu must be the "
+                            "last ones, right behind the table-id column", who, c->num_constant_cols, (unsigned long long)spec_consts);
+        for (unsigned g = 0; g < c->num_specialized_gates; g++) {
+            const bj_gate_desc &G = c->specialized_gates[g];
+            bool ok = c->specialized_gates && G.kind == BJ_GATE_PROGRAM && G.program && G.path_len == 0 && G.num_repetitions &&
+                      G.var_stride && G.program->num_writes == G.num_terms;
+            unsigned ve = 0, ce = 0, we = 0;
+            if (ok) {
+                bj::gate_program_extent(G.program, &ve, &ce, &we);
+                // a repetition reads its own var_stride variable columns and its own const_stride constant columns, no witness column.
+                // Constants SHARED by the repetitions (share_constants = true with constants) are refused: the reference itself hands
+                // such an evaluator an empty constant range (per_repetition_offset.constants_offset = 0, prover.rs:748-772)
+                ok = ve <= G.var_stride && we == 0 && ce <= G.const_stride;
+            }
+            if (!ok)
+                return bj::fail(ctx, BJ_ERR_UNSUPPORTED, BJ_WHO "specialized gate %u must be an op list without a selector path "
+                                "whose repetitions each read their own var_stride variable and const_stride constant columns "
+                                "(share_constants = false) and no witness column", who, g);
+            if (int prc = check_program(ctx, G.program)) return prc;
+            if (col + (uint64_t)G.num_repetitions * G.var_stride > c->num_vars)
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "specialized gate %u runs past the %u declared variable columns", who, g,
+                                c->num_vars);
+            col += (uint64_t)G.num_repetitions * G.var_stride;
+        }
+        if (col != c->num_vars)
+            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "%u variable columns declared, geometry + lookups + "
+                            "specialized gates make %llu", who, c->num_vars, (unsigned long long)col);
+    }
+    return BJ_OK;
+}
+#undef BJ_WHO
+#undef BJ_WHO_SHARDED
+
 int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const std::function<int(bj_setup *, u64 *)> &fill_sigmas,
                           const uint64_t *h_constants, const uint64_t *h_tables, const bj_proof_config *cfg, const bj_comm *comm,
                           bj_setup **out) {
@@ -61,58 +217,9 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
     if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: null out pointer");
     *out = nullptr;
     if (!c || !cfg || (!h_sigmas && !fill_sigmas) || !h_constants) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: null argument");
-    if (c->log_n < 1 || c->log_n > 26) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: log_n out of range");
-    if (c->num_gates == 0 || c->num_gates > 16 || !c->gates) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: 1..16 gates expected");
-    if (!bj::is_pow2(c->quotient_degree) || !bj::is_pow2(cfg->fri_lde_factor) || cfg->fri_lde_factor < 2 ||
-        !bj::is_pow2(cfg->cap_size))
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: quotient degree / fri_lde_factor / cap must be powers of two");
-    {
-        const unsigned tk = cfg->transcript ? cfg->transcript : BJ_TRANSCRIPT_POSEIDON2, hk = cfg->tree_hasher ? cfg->tree_hasher : BJ_HASHER_POSEIDON2;
-        if (tk > BJ_TRANSCRIPT_KECCAK256 || hk > BJ_HASHER_POSEIDON) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: unknown transcript / tree hasher");
-        const bool byte_hasher = hk == BJ_HASHER_BLAKE2S || hk == BJ_HASHER_KECCAK256,
-                   byte_transcript = tk == BJ_TRANSCRIPT_BLAKE2S || tk == BJ_TRANSCRIPT_KECCAK256;
-        if (byte_hasher != byte_transcript)   // Transcript::CompatibleCap = TreeHasher::Output (prover.rs:153-168)
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: a byte tree hasher (Blake2s / Keccak256) goes with a byte transcript and "
-                                                     "an algebraic tree hasher (Poseidon2 / Poseidon) with an algebraic transcript");
-    }
-    if (cfg->fri_lde_factor > 64 || c->quotient_degree > 64)   // per-coset tables of the quotient kernels hold 64 entries
-        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: fri_lde_factor and quotient_degree are limited to 64");
-    if (c->num_public_inputs && (!c->public_input_cols || !c->public_input_rows))
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: public input locations missing");
-    for (unsigned i = 0; i < c->num_public_inputs; i++)
-        if (c->public_input_cols[i] >= c->num_vars || (c->public_input_rows[i] >> c->log_n) != 0)
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: public input %u at (column %u, row %u) is outside the %u x 2^%u trace",
-                            i, c->public_input_cols[i], c->public_input_rows[i], c->num_vars, c->log_n);
-    if (cfg->pow_bits > 32 || cfg->pow_bits >= cfg->security_level)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: pow_bits must be <= 32 and below the security level (pow.rs:53, prover.rs:2293)");
-    if (cfg->pow_runner > BJ_POW_KECCAK256)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: pow_runner %u (0 / BJ_POW_BLAKE2S256 / BJ_POW_KECCAK256)", cfg->pow_runner);
-    // LookupParameters::UseSpecializedColumnsWithTableIdAsVariable (cs/mod.rs:237-241): table_ids_column_idxes is empty (setup.rs:970-971)
-    // and a sub-argument owns width + 1 variable columns, the last one the table id (lookup_argument_in_ext.rs:354-366, 949-1000)
+    if (int rc = bj::circuit_check(ctx, "bj_setup_create", c, cfg, h_tables != nullptr, comm)) return rc;
     const bool tid_var = c->lookup_reps && c->table_id_col == BJ_TABLE_ID_AS_VARIABLE;
     const unsigned lookup_cps = c->lookup_width + (tid_var ? 1u : 0u);
-    if (c->lookup_reps && (!h_tables || c->lookup_width == 0 || c->lookup_width > 8 || (!tid_var && c->table_id_col >= c->num_constant_cols)))
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: bad lookup parameters");
-    if ((uint64_t)c->num_vars < (uint64_t)c->num_gp_vars + (uint64_t)lookup_cps * c->lookup_reps || !c->non_residues)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: bad column counts");
-    if (c->num_vars > 4096)   // the copy-permutation quotient keeps k_c * beta of every column in LDS (16 bytes per column)
-        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: %u copiable columns, at most 4096 are supported", c->num_vars);
-    unsigned n_chunks = (c->num_vars + c->quotient_degree - 1) / c->quotient_degree;
-    if (n_chunks < 2) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: a single copy-permutation chunk is not supported");
-    if (comm && comm->world > 1) {
-        const unsigned W = comm->world;
-        if (!bj::is_pow2(W) || W > 8 || comm->rank >= W || (!comm->all_gather && !comm->all_gather_stream))
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create_sharded: world must be a power of two <= 8, rank < world, callback set");
-        if (cfg->fri_lde_factor % W || cfg->cap_size % W || c->quotient_degree > cfg->fri_lde_factor)
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create_sharded: world must divide fri_lde_factor and cap_size, and "
-                                                     "quotient_degree must not exceed fri_lde_factor");
-        const unsigned cl = cfg->fri_lde_factor / W;
-        if ((((size_t)1 << c->log_n) * cl) < cfg->cap_size / W)
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create_sharded: shard smaller than its cap fragment");
-        const size_t Qe_rank = ((size_t)c->quotient_degree << c->log_n) / W;   // every rank evaluates q n / W points of the quotient
-        if (Qe_rank < 2 || !bj::is_pow2(Qe_rank))                              // and inverse-transforms them: a power of two
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create_sharded: q n / world = %zu quotient points per rank (a power of two >= 2 is needed)", Qe_rank);
-    }
     bj_setup *s = new bj_setup();
     s->device = ctx->device;
     bj::HasherGuard hasher_guard{ctx, ctx->hasher};
@@ -128,58 +235,11 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
     s->tid_var = tid_var; s->lookup_cps = lookup_cps;
     s->q = c->quotient_degree;
     s->n_gates = c->num_gates;
-    if (c->num_gates > 16) {
-        bj_setup_destroy(s);
-        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: %u gate types over general-purpose columns (at most 16)", c->num_gates);
-    }
     for (unsigned g = 0; g < c->num_gates; g++) {
         const bj_gate_desc &G = c->gates[g];
-        const bool p2 = G.kind == BJ_GATE_POSEIDON2_FLATTENED || G.kind == BJ_GATE_POSEIDON_FLATTENED;
-        if (G.kind < 1 || G.kind > BJ_GATE_POSEIDON_FLATTENED || G.path_len > 6 || (G.kind == BJ_GATE_PROGRAM && !G.program) ||
-            (p2 && (G.num_terms != 118 || G.num_repetitions != 1 || c->num_gp_vars < 130)) ||
-            (G.kind != BJ_GATE_PROGRAM && G.kind != BJ_GATE_NOP && !p2 && G.num_terms != 1)) {
-            bj_setup_destroy(s);
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: bad gate descriptor %u", g);
-        }
-        {   // every column index the evaluator will form must exist: (reps - 1) * stride + the widest operand, after the selector path
-            unsigned var_extent = 0, const_extent = 0, wit_extent = 0;
-            bool const_per_rep = true;
-            switch (G.kind) {
-                case BJ_GATE_CONSTANT_ALLOCATOR: var_extent = 1; const_extent = 1; break;
-                case BJ_GATE_FMA_NO_CONSTANT: var_extent = 4; const_extent = 2; const_per_rep = false; break;
-                case BJ_GATE_REDUCTION4: var_extent = 5; const_extent = 4; const_per_rep = false; break;
-                case BJ_GATE_POSEIDON2_FLATTENED: var_extent = 130; break;
-                case BJ_GATE_POSEIDON_FLATTENED: var_extent = 130; break;
-                case BJ_GATE_PROGRAM: bj::gate_program_extent(G.program, &var_extent, &const_extent, &wit_extent); break;
-                default: break;
-            }
-            s->gate_wit_stride.push_back(G.wit_stride);
-            if (wit_extent && (size_t)(G.num_repetitions ? G.num_repetitions - 1 : 0) * G.wit_stride + wit_extent > c->num_witness_cols) {
-                bj_setup_destroy(s);
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: gate %u reads witness column %zu of %u", g,
-                                (size_t)(G.num_repetitions - 1) * G.wit_stride + wit_extent, c->num_witness_cols);
-            }
-            const size_t last = G.num_repetitions ? G.num_repetitions - 1 : 0;
-            const size_t var_end = var_extent ? last * G.var_stride + var_extent : 0;
-            const size_t const_end = G.path_len + (const_extent ? (const_per_rep ? last * G.const_stride : 0) + const_extent : 0);
-            if (G.kind != BJ_GATE_NOP && (G.num_repetitions == 0 || var_end > c->num_gp_vars || const_end > c->num_constant_cols)) {
-                bj_setup_destroy(s);
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: gate %u reads variable column %zu / constant column %zu of %u / %u "
-                                "(repetitions x stride + operand index, after a selector path of %u)", g, var_end, const_end,
-                                c->num_gp_vars, c->num_constant_cols, G.path_len);
-            }
-            if (G.path_len > c->num_constant_cols) {
-                bj_setup_destroy(s);
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: gate %u: selector path longer than the constant columns", g);
-            }
-        }
+        s->gate_wit_stride.push_back(G.wit_stride);
         s->programs.emplace_back();
         if (G.kind == BJ_GATE_PROGRAM) {
-            if (G.program->num_writes != G.num_terms) {
-                bj_setup_destroy(s);
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: gate %u: program writes %u terms, descriptor says %u", g,
-                                G.program->num_writes, G.num_terms);
-            }
             if (int prc = s->programs.back().upload(ctx, G.program)) {
                 bj_setup_destroy(s);
                 return prc;
@@ -190,64 +250,26 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
         for (unsigned b = 0; b < G.path_len; b++) f[6 + b] = G.path[b] ? 1 : 0;
         s->gates_flat.insert(s->gates_flat.end(), f, f + 12);
     }
-    {   // gates over specialized columns (evaluator_data.rs:124-240, prover.rs:635-800): their variable columns follow the lookup ones
-        // in declaration order; their constant columns follow the general-purpose gates' ones and the table-id column (which is the
-        // first "special purpose" constant: setup.rs:963-1010), num_repetitions * const_stride columns each — every repetition its
-        // own principal_width.num_constants columns (share_constants = false, per_repetition_offset.constants_offset = that width)
-        // (64-bit sums: the sizes are the caller's, a wrapped 32-bit total must not pass the range checks)
+    {   // gates over specialized columns: their variable columns follow the lookup ones in declaration order, their constant columns
+        // are the last ones (the layout bj::circuit_check has verified)
         uint64_t col = (uint64_t)c->num_gp_vars + (uint64_t)lookup_cps * c->lookup_reps;
         uint64_t spec_consts = 0;
-        for (unsigned g = 0; c->specialized_gates && g < c->num_specialized_gates; g++) {
-            const uint64_t per_gate = (uint64_t)c->specialized_gates[g].num_repetitions * c->specialized_gates[g].const_stride;
-            if (per_gate > c->num_constant_cols) { spec_consts = (uint64_t)c->num_constant_cols + 1; break; }
-            spec_consts += per_gate;
-        }
-        if (spec_consts > c->num_constant_cols ||
-            (c->lookup_reps && !tid_var && (uint64_t)c->table_id_col + 1 + spec_consts != c->num_constant_cols)) {
-            bj_setup_destroy(s);
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: %u constant columns declared; the specialized gates' %llu must be the "
-                            "last ones, right behind the table-id column", c->num_constant_cols, (unsigned long long)spec_consts);
-        }
+        for (unsigned g = 0; g < c->num_specialized_gates; g++)
+            spec_consts += (uint64_t)c->specialized_gates[g].num_repetitions * c->specialized_gates[g].const_stride;
         unsigned ccol = c->num_constant_cols - (unsigned)spec_consts;
         s->spec.resize(c->num_specialized_gates);
         for (unsigned g = 0; g < c->num_specialized_gates; g++) {
             const bj_gate_desc &G = c->specialized_gates[g];
-            bool ok = c->specialized_gates && G.kind == BJ_GATE_PROGRAM && G.program && G.path_len == 0 && G.num_repetitions &&
-                      G.var_stride && G.program->num_writes == G.num_terms;
-            unsigned ve = 0, ce = 0, we = 0;
-            if (ok) {
-                bj::gate_program_extent(G.program, &ve, &ce, &we);
-                // a repetition reads its own var_stride variable columns and its own const_stride constant columns, no witness column.
-                // Constants SHARED by the repetitions (share_constants = true with constants) are refused: the reference itself hands
-                // such an evaluator an empty constant range (per_repetition_offset.constants_offset = 0, prover.rs:748-772)
-                ok = ve <= G.var_stride && we == 0 && ce <= G.const_stride;
-            }
-            if (!ok) {
-                bj_setup_destroy(s);
-                return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_create: specialized gate %u must be an op list without a selector path "
-                                "whose repetitions each read their own var_stride variable and const_stride constant columns "
-                                "(share_constants = false) and no witness column", g);
-            }
             bj_setup::SpecGate &sg = s->spec[g];
             if (int prc = sg.program.upload(ctx, G.program)) {
                 bj_setup_destroy(s);
                 return prc;
-            }
-            if (col + (uint64_t)G.num_repetitions * G.var_stride > c->num_vars) {
-                bj_setup_destroy(s);
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: specialized gate %u runs past the %u declared variable columns", g,
-                                c->num_vars);
             }
             sg.reps = G.num_repetitions; sg.width = G.var_stride; sg.terms = G.num_terms; sg.first_col = (unsigned)col;
             sg.first_const = ccol; sg.const_width = G.const_stride;
             col += (uint64_t)sg.reps * sg.width;
             ccol += sg.reps * sg.const_width;
             s->n_spec_terms += sg.reps * sg.terms;
-        }
-        if (col != c->num_vars) {
-            bj_setup_destroy(s);
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: %u variable columns declared, geometry + lookups + "
-                            "specialized gates make %llu", c->num_vars, (unsigned long long)col);
         }
     }
     s->non_residues.assign(c->non_residues, c->non_residues + c->num_vars);

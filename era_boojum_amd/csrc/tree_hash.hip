@@ -2,6 +2,7 @@
 // hasher files contribute (tree_plan.h), and the walk over the node layers, which is the same for every hasher.
 #include "kernels.h"
 #include "tree_plan.h"
+#include "verify_open.h"
 #include "../../include/boojum_hip.h"
 
 namespace bj {
@@ -37,5 +38,6 @@ void launch_tree_leaves_absorb(int hasher, const u64 *d_base, size_t col_stride,
     const TreeHasher &h = tree_hasher(hasher);   // callers ask for an algebraic hasher; any other value is Poseidon2, as above
     (h.leaves_absorb ? h : tree_hasher(BJ_HASHER_POSEIDON2)).leaves_absorb(d_base, col_stride, n_cols, num_leaves, d_capacity, d_digests, first, last, s);
 }
+void launch_verify_openings(int hasher, const VerifyOpenArgs &args, hipStream_t s) { tree_hasher(hasher).verify_openings(args, s); }
 
 }  // namespace bj

@@ -25,6 +25,8 @@ inline void launch_1d(void (*kernel)(Params...), size_t n, hipStream_t s, Args..
     hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, args...);
 }
 
+struct VerifyOpenArgs;   // verify_open.h
+
 // a hasher's launchers, one table entry of tree_hash.hip
 struct TreeHasher {
     void (*leaves)(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols, size_t num_leaves,
@@ -36,6 +38,8 @@ struct TreeHasher {
     // null for the byte hashers
     void (*leaves_absorb)(const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *d_capacity, u64 *d_digests,
                           bool first, bool last, hipStream_t s);
+    // bj_verify: the (query, oracle) Merkle chains of a proof's query section (verify_open.h)
+    void (*verify_openings)(const VerifyOpenArgs &args, hipStream_t s);
 };
 TreeHasher poseidon2_tree_hasher(), blake2s_tree_hasher(), keccak_tree_hasher(), poseidon1_tree_hasher();
 

@@ -1,0 +1,919 @@
+// bj_vk_* / bj_verify: Verifier::verify (src/cs/implementations/verifier.rs:888-2524) for the circuit class bj_prove handles.
+//
+// Host (tiny data, order-critical, on top of host_transcript.hpp): the transcript replay (:924-1076), the split of the openings
+// (:1150-1206), the challenge powers in the order lookup | specialized | general | L1 | chunks (:1000-1060), the lookup sum
+// (:1236-1256), the quotient identity at z (:1090-1810) — hand-written kinds by formula, op lists interpreted over F_p^2 in the
+// canonical form of gate_canon.h, the two flattened Poseidon gates by the F_p^2 restatement of their evaluators below — the DEEP
+// and FRI challenges (:1819-1955), the proof of work (:1957-1983), the public-input tuples and the query indices.
+// Device (the verifier's only volume, ~200 dependent permutations per query): verify_openings (verify_open.h, one kernel per tree
+// hasher) walks every Merkle chain; verify_deep_fri_kernel here, one wave per query, simulates the DEEP value from the four
+// opened leaves (:2233-2290), folds it through the schedule (:2387-2519) and compares with the final monomials at the point.
+// Both write one status word per chain / query; the host reduces them to the report (include/boojum_hip.h has the order).
+#include "ctx.h"
+#include "gate_program.h"
+#include "host_transcript.hpp"
+#include "poseidon1_fused.inc"
+#include "setup.h"
+#include "verify_open.h"
+
+#include <cstring>
+#include <vector>
+
+using gl::e2;
+using gl::u64;
+
+namespace bj {
+void launch_verify_openings(int hasher, const VerifyOpenArgs &args, hipStream_t s);   // tree_hash.hip
+}
+
+namespace bj {
+const std::vector<u64> &proof_words(const bj_proof *p);   // prover.hip: the serialised words a proof handle holds
+}
+
+struct bj_vk {
+    unsigned log_n = 0, V = 0, num_gp_vars = 0, Wc = 0, nC = 0, lookup_w = 0, lookup_reps = 0, table_id_col = 0, q = 0, lookup_cps = 0;
+    bool tid_var = false;
+    struct Program {   // canonical op list, packed as the interpreter kernels take it (gate_program.h: pack_program)
+        std::vector<bj::DevRelation> rel;
+        std::vector<u64> values;
+        unsigned n_slots = 0;
+    };
+    struct Gate {
+        int kind = 0;
+        unsigned path_len = 0, reps = 0, var_stride = 0, wit_stride = 0, const_stride = 0, num_terms = 0;
+        unsigned char path[8] = {};
+        unsigned first_col = 0, first_const = 0;   // gates over specialized columns: where their columns start
+        Program prog;
+    };
+    std::vector<Gate> gates, spec;
+    std::vector<u64> non_residues;
+    std::vector<unsigned> pub_cols, pub_rows;
+    unsigned fri_lde = 0, cap_size = 0, security = 0, pow_bits = 0, transcript = BJ_TRANSCRIPT_POSEIDON2, hasher = BJ_HASHER_POSEIDON2,
+             pow_runner = BJ_POW_BLAKE2S256, log_fri = 0;
+    std::vector<u64> cap;
+};
+
+namespace {
+
+const e2 ZERO2{0, 0}, ONE2{1, 0};
+e2 e2c(const u64 *p) { return {gl::canon(p[0]), gl::canon(p[1])}; }
+e2 base2(u64 x) { return {gl::canon(x), 0}; }
+bool eq2(e2 a, e2 b) { return a.c0 == b.c0 && a.c1 == b.c1; }
+e2 pow7(e2 x) {
+    const e2 x2 = gl::e2_sqr(x), x3 = gl::e2_mul(x2, x), x4 = gl::e2_sqr(x2);
+    return gl::e2_mul(x4, x3);
+}
+
+unsigned slots_of(const std::vector<bj::DevRelation> &rel) {
+    unsigned n = 0;
+    for (const auto &r : rel)
+        if (r.op != bj::canon::OP_WRITE && r.dst + 1 > n) n = r.dst + 1;
+    return n;
+}
+
+// one repetition of an op list over F_p^2 (Relation / Index of gpu_synthesizer/mod.rs:113-133); false for an operand outside the
+// opened columns (the key was checked against its geometry, so this is a defence, not a path)
+bool program_terms(const bj_vk::Program &P, const e2 *var, size_t n_var, const e2 *con, size_t n_con, const e2 *wit, size_t n_wit,
+                   std::vector<e2> &slots, e2 *terms, unsigned n_terms) {
+    slots.assign(P.n_slots ? P.n_slots : 1, ZERO2);
+    bool ok = true;
+    auto get = [&](uint32_t x) -> e2 {
+        const uint32_t k = x >> 28, i = x & 0x0FFFFFFFu;
+        switch (k) {
+            case BJ_IDX_VARIABLE_POLY: if (i < n_var) return var[i]; break;
+            case BJ_IDX_WITNESS_POLY: if (i < n_wit) return wit[i]; break;
+            case BJ_IDX_CONSTANT_POLY: if (i < n_con) return con[i]; break;
+            case BJ_IDX_TEMPORARY: if (i < slots.size()) return slots[i]; break;
+            case BJ_IDX_CONSTANT_VALUE: if (i < P.values.size()) return base2(P.values[i]); break;
+            default: break;
+        }
+        ok = false;
+        return ZERO2;
+    };
+    for (const auto &r : P.rel) {
+        const e2 a = get(r.a);
+        if (r.op == bj::canon::OP_WRITE) {
+            if (r.dst < n_terms) terms[r.dst] = a;
+            else ok = false;
+            continue;
+        }
+        e2 v = ZERO2;
+        switch (r.op) {
+            case BJ_OP_ADD: v = gl::e2_add(a, get(r.b)); break;
+            case BJ_OP_DOUBLE: v = gl::e2_add(a, a); break;
+            case BJ_OP_SUB: v = gl::e2_sub(a, get(r.b)); break;
+            case BJ_OP_NEGATE: v = gl::e2_sub(ZERO2, a); break;
+            case BJ_OP_MUL: v = gl::e2_mul(a, get(r.b)); break;
+            case BJ_OP_SQUARE: v = gl::e2_sqr(a); break;
+            case BJ_OP_INVERSE: v = gl::e2_inv(a); break;   // inverse of 0 is 0, as in the kernels
+            default: ok = false; break;
+        }
+        if (r.dst < slots.size()) slots[r.dst] = v;
+        else ok = false;
+    }
+    return ok;
+}
+
+// ---- the flattened Poseidon gates over F_p^2: the evaluators of gate_poseidon2.hip / gate_poseidon1.hip with every base-field
+// operation replaced by its F_p^2 counterpart (matrix entries and round constants stay base-field scalars); 118 terms each ----
+void ext_mds2(e2 *s) {   // circ(2 M4, M4, M4), M4 = [[5,7,1,3],[4,6,1,1],[1,3,5,7],[1,1,4,6]] (suggested_mds.rs:21-103)
+    auto m4 = [](e2 *x) {
+        auto dbl = [](e2 a) { return gl::e2_add(a, a); };
+        const e2 t0 = gl::e2_add(x[0], x[1]), t1 = gl::e2_add(x[2], x[3]);
+        const e2 t2 = gl::e2_add(dbl(x[1]), t1), t3 = gl::e2_add(dbl(x[3]), t0);
+        const e2 t4 = gl::e2_add(dbl(dbl(t1)), t3), t5 = gl::e2_add(dbl(dbl(t0)), t2);
+        x[0] = gl::e2_add(t3, t5); x[1] = t5; x[2] = gl::e2_add(t2, t4); x[3] = t4;
+    };
+    m4(s); m4(s + 4); m4(s + 8);
+    for (int j = 0; j < 4; j++) {
+        const e2 sum = gl::e2_add(gl::e2_add(s[j], s[4 + j]), s[8 + j]);
+        s[j] = gl::e2_add(s[j], sum); s[4 + j] = gl::e2_add(s[4 + j], sum); s[8 + j] = gl::e2_add(s[8 + j], sum);
+    }
+}
+e2 add_rc(e2 x, u64 rc) { return {gl::add(x.c0, gl::canon(rc)), x.c1}; }
+
+void poseidon2_flattened_terms(const e2 *var, e2 *terms) {   // src/cs/gates/poseidon2.rs:165-410
+    static const unsigned SH[12] = {4, 14, 11, 8, 0, 5, 2, 9, 13, 6, 3, 12};
+    const u64 *RC = bj::host::rc_table();
+    unsigned t = 0, nxt = 24;
+    e2 s[12];
+    for (int i = 0; i < 12; i++) s[i] = var[i];
+    ext_mds2(s);
+    for (int rnd = 0; rnd < 4; rnd++) {
+        if (rnd)
+            for (int i = 0; i < 12; i++) {
+                const e2 v = var[nxt++];
+                terms[t++] = gl::e2_sub(s[i], v);
+                s[i] = v;
+            }
+        for (int i = 0; i < 12; i++) s[i] = pow7(add_rc(s[i], RC[12 * rnd + i]));
+        ext_mds2(s);
+    }
+    for (int rnd = 0; rnd < 22; rnd++) {
+        s[0] = add_rc(s[0], RC[12 * (4 + rnd)]);
+        const e2 v = var[nxt++];
+        terms[t++] = gl::e2_sub(s[0], v);
+        s[0] = pow7(v);
+        e2 tot = s[0];
+        for (int i = 1; i < 12; i++) tot = gl::e2_add(tot, s[i]);
+        for (int i = 0; i < 12; i++) s[i] = gl::e2_add(gl::e2_mul_base(s[i], (u64)1 << SH[i]), tot);
+    }
+    for (int k = 0; k < 4; k++) {
+        for (int i = 0; i < 12; i++) {
+            const e2 v = var[nxt++];
+            terms[t++] = gl::e2_sub(s[i], v);
+            s[i] = v;
+        }
+        for (int i = 0; i < 12; i++) s[i] = pow7(add_rc(s[i], RC[12 * (26 + k) + i]));
+        ext_mds2(s);
+    }
+    for (int i = 0; i < 12; i++) terms[t++] = gl::e2_sub(var[12 + i], s[i]);
+}
+
+void poseidon1_flattened_terms(const e2 *var, e2 *terms) {   // src/cs/gates/poseidon.rs:199-464, fused form (poseidon_goldilocks.rs:374-420)
+    static const unsigned EXPS[12] = {0, 0, 1, 0, 3, 5, 1, 8, 12, 3, 16, 10};
+    static const u64 FUSED_RC[12] = BJ_P1_FUSED_RC, DENSE[144] = BJ_P1_FUSED_DENSE, SBOX_RC[22] = BJ_P1_FUSED_SBOX_RC,
+                     VS[22 * 11] = BJ_P1_FUSED_VS, W_HATS[22 * 11] = BJ_P1_FUSED_W_HATS;
+    const u64 *RC = bj::host::rc_table();
+    unsigned t = 0, nxt = 24;
+    e2 s[12];
+    auto mds = [&]() {   // M[row][col] = 2^EXPS[(col - row) mod 12]
+        e2 out[12];
+        for (int row = 0; row < 12; row++) {
+            e2 acc = ZERO2;
+            for (int col = 0; col < 12; col++) acc = gl::e2_add(acc, gl::e2_mul_base(s[col], (u64)1 << EXPS[(col + 12 - row) % 12]));
+            out[row] = acc;
+        }
+        for (int k = 0; k < 12; k++) s[k] = out[k];
+    };
+    auto reset = [&]() {
+        for (int i = 0; i < 12; i++) {
+            const e2 v = var[nxt++];
+            terms[t++] = gl::e2_sub(s[i], v);
+            s[i] = v;
+        }
+    };
+    for (int i = 0; i < 12; i++) s[i] = var[i];
+    for (int rnd = 0; rnd < 4; rnd++) {
+        if (rnd) reset();
+        for (int i = 0; i < 12; i++) s[i] = pow7(add_rc(s[i], RC[12 * rnd + i]));
+        if (rnd != 3) mds();
+    }
+    {
+        e2 tt[12], out[12];
+        for (int i = 0; i < 12; i++) tt[i] = add_rc(s[i], FUSED_RC[i]);
+        for (int r = 0; r < 12; r++) {
+            e2 acc = ZERO2;
+            for (int k = 0; k < 12; k++) acc = gl::e2_add(acc, gl::e2_mul_base(tt[k], gl::canon(DENSE[12 * r + k])));
+            out[r] = acc;
+        }
+        for (int i = 0; i < 12; i++) s[i] = out[i];
+    }
+    for (int rnd = 0; rnd < 22; rnd++) {
+        const e2 v = var[nxt++];
+        terms[t++] = gl::e2_sub(s[0], v);
+        const e2 s0 = add_rc(pow7(v), SBOX_RC[rnd]);
+        e2 acc = ZERO2;
+        for (int k = 1; k < 12; k++) acc = gl::e2_add(acc, gl::e2_mul_base(s[k], gl::canon(VS[11 * rnd + k - 1])));
+        s[0] = gl::e2_add(acc, s0);
+        for (int k = 1; k < 12; k++) s[k] = gl::e2_add(s[k], gl::e2_mul_base(s0, gl::canon(W_HATS[11 * rnd + k - 1])));
+    }
+    reset();   // round 26: its constants were propagated into the partial rounds
+    for (int i = 0; i < 12; i++) s[i] = pow7(s[i]);
+    mds();
+    for (int r = 27; r < 30; r++) {
+        reset();
+        for (int i = 0; i < 12; i++) s[i] = pow7(add_rc(s[i], RC[12 * r + i]));
+        mds();
+    }
+    for (int i = 0; i < 12; i++) terms[t++] = gl::e2_sub(var[12 + i], s[i]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// device: DEEP value, fold chain, final monomials — one wave per query
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t NO_C1 = 0xFFFFFFFFu;        // a term whose source is a base-field column
+constexpr uint32_t DEEP_FINAL = 0x10000u;      // status: 0 ok, 1 + l = the value carried into layer l is not in its leaf, DEEP_FINAL
+
+struct VerifyDeepArgs {
+    const u64 *queries, *indices;
+    const u64 *terms;     // [n_terms][3]: leaf word of c0 | leaf word of c1 << 32 (NO_C1: base field), challenge power (c0, c1)
+    const u64 *sets;      // [n_sets][6]: first term, end term, the point (c0, c1), sum_k ch_k * value_k (c0, c1)
+    const u64 *fri_ch;    // [n_fri][2]
+    const u64 *final0, *final1;   // final monomials
+    const u64 *roots;     // inverse bit-reversed twiddles of the 2^log_full domain
+    uint32_t *status;     // [n_queries]
+    uint32_t n_queries, query_words, n_sets, n_fri, final_degree, log_full, total_folds;
+    u64 omega, kappa;     // generator of the 2^log_full domain; 1 / 7
+    uint32_t fri_off[32];
+    unsigned char sched[32];
+};
+
+__device__ __forceinline__ u64 shfl64(u64 v, unsigned src) { return (u64)__shfl((unsigned long long)v, (int)src); }
+__device__ __forceinline__ e2 shfl2(e2 v, unsigned src) { return {shfl64(v.c0, src), shfl64(v.c1, src)}; }
+__device__ __forceinline__ e2 wave_sum(e2 v) {
+#pragma unroll
+    for (int m = 32; m; m >>= 1) {
+        const e2 o{(u64)__shfl_xor((unsigned long long)v.c0, m), (u64)__shfl_xor((unsigned long long)v.c1, m)};
+        v = gl::e2_add(v, o);
+    }
+    return v;
+}
+
+__global__ void __launch_bounds__(64) verify_deep_fri_kernel(VerifyDeepArgs A) {
+    const unsigned c = blockIdx.x, lane = threadIdx.x;
+    if (c >= A.n_queries) return;
+    const u64 *Q = A.queries + (size_t)c * A.query_words;
+    const u64 idx = A.indices[c];
+    const u64 x = gl::mul(gl::GEN, gl::pow(A.omega, (u64)gl::bitrev32((gl::u32)idx, A.log_full)));   // x_I = g * w^bitrev(I)
+    // h = sum over the opening sets of [ sum_k ch_k f_k(x) - sum_k ch_k v_k ] / (x - at): source order of verifier.rs:2233-2290, one
+    // inversion per set; the sources of a set are spread over the lanes
+    e2 h{0, 0};
+    for (unsigned s = 0; s < A.n_sets; s++) {
+        const u64 *S = A.sets + 6 * (size_t)s;
+        e2 acc{0, 0};
+        for (u64 t = S[0] + lane; t < S[1]; t += 64) {
+            const u64 *T = A.terms + 3 * t;
+            const uint32_t o0 = (uint32_t)T[0], o1 = (uint32_t)(T[0] >> 32);
+            const e2 ch{T[1], T[2]};
+            const u64 a = gl::canon(Q[o0]);
+            acc = gl::e2_add(acc, o1 == NO_C1 ? gl::e2_mul_base(ch, a) : gl::e2_mul(ch, e2{a, gl::canon(Q[o1])}));
+        }
+        acc = wave_sum(acc);
+        const e2 den{gl::sub(x, S[2]), gl::neg(S[3])};
+        h = gl::e2_add(h, gl::e2_mul(gl::e2_sub(acc, e2{S[4], S[5]}), gl::e2_inv(den)));
+    }
+    // the fold chain (verifier.rs:2387-2519), the prover's convention (fri.hip): element i of a leaf lives in lane i; one fold takes
+    // lanes (2i, 2i + 1) to lane i with roots[leaf * outs + i] * kappa, kappa squared per fold, the challenge squared inside a step
+    uint32_t status = 0;
+    e2 cur = h;
+    u64 fidx = idx, kappa = A.kappa;
+    for (unsigned l = 0; l < A.n_fri; l++) {
+        const unsigned k = A.sched[l], m = 1u << k;
+        const unsigned sub = (unsigned)fidx & (m - 1);
+        const u64 tree = fidx >> k;
+        const u64 *L = Q + A.fri_off[l];
+        e2 v{0, 0};
+        if (lane < m) v = e2{gl::canon(L[lane]), gl::canon(L[m + lane])};
+        const e2 carried = shfl2(v, sub);
+        if (!status && (carried.c0 != cur.c0 || carried.c1 != cur.c1)) status = 1 + l;
+        e2 chal{A.fri_ch[2 * l], A.fri_ch[2 * l + 1]};
+        for (unsigned f = 0; f < k; f++) {
+            const unsigned outs = m >> (f + 1);
+            const e2 a = shfl2(v, (2 * lane) & 63), b = shfl2(v, (2 * lane + 1) & 63);
+            u64 r = lane < outs ? gl::canon(A.roots[tree * outs + lane]) : 0;
+            r = gl::mul(r, kappa);
+            const e2 t = gl::e2_mul(gl::e2_mul_base(gl::e2_sub(a, b), r), chal);
+            v = e2{gl::add(gl::add(t.c0, a.c0), b.c0), gl::add(gl::add(t.c1, a.c1), b.c1)};
+            chal = gl::e2_sqr(chal);
+            kappa = gl::sqr(kappa);
+        }
+        cur = shfl2(v, 0);
+        fidx = tree;
+    }
+    u64 xx = x;
+    for (unsigned i = 0; i < A.total_folds; i++) xx = gl::sqr(xx);
+    e2 acc{0, 0};
+    for (unsigned j = A.final_degree; j-- > 0;) acc = gl::e2_add(gl::e2_mul_base(acc, xx), e2{A.final0[j], A.final1[j]});
+    if (!status && (acc.c0 != cur.c0 || acc.c1 != cur.c1)) status = DEEP_FINAL;
+    if (lane == 0) A.status[c] = status;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------------------------------------------------------
+struct Failure {
+    uint32_t stage = BJ_VERIFY_OK, query = 0, oracle = 0;
+};
+
+int verdict(bj_verify_report *out, uint32_t stage, uint32_t query = 0, uint32_t oracle = 0, uint32_t checked = 0) {
+    out->stage = stage;
+    out->query = query;
+    out->oracle = oracle;
+    out->queries_checked = checked;
+    return BJ_OK;
+}
+
+bool pow_holds(unsigned runner, const u64 *seed5, unsigned bits, u64 nonce) {   // POW::verify_from_field_elements (pow.rs:16-31)
+    unsigned char msg[48], out[32];
+    for (int i = 0; i < 5; i++)
+        for (int b = 0; b < 8; b++) msg[8 * i + b] = (unsigned char)(seed5[i] >> (8 * b));
+    for (int b = 0; b < 8; b++) msg[40 + b] = (unsigned char)(nonce >> (8 * b));
+    if (runner == BJ_POW_KECCAK256) {
+        bj::host::Keccak256 h;
+        h.update(msg, 48);
+        h.finalize_reset(out);
+    } else {
+        bj::host::Blake2s h;
+        h.update(msg, 48);
+        h.finalize_reset(out);
+    }
+    u64 first = 0;
+    for (int b = 0; b < 8; b++) first |= (u64)out[b] << (8 * b);
+    const unsigned tz = first ? (unsigned)__builtin_ctzll(first) : 64u;
+    return tz >= bits;
+}
+
+int verify_impl(bj_ctx *ctx, const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, bj_verify_report *out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!K || !W || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: null argument");
+    if (flags & ~BJ_VERIFY_PARTIAL_QUERIES) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: unknown flags %#x", flags);
+    if (ctx->in_proof) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: a proof is running on this context");
+    std::memset(out, 0, sizeof(*out));
+    ctx->verify_timed = false;
+
+    // ---- shape: every count is the key's before it sizes anything ----
+    const unsigned log_n = K->log_n, V = K->V, Wc = K->Wc, nC = K->nC, q = K->q, log_fri = K->log_fri, LOGN = log_n + log_fri;
+    const size_t n = (size_t)1 << log_n, N = n << log_fri, cap = K->cap_size;
+    const bool has_lookup = K->lookup_reps > 0;
+    const unsigned n_chunks = (V + q - 1) / q, n_partials = n_chunks - 1;
+    const unsigned n_lookup_terms = has_lookup ? K->lookup_reps + 1 : 0;
+    const unsigned n_lookup_polys = has_lookup ? K->lookup_reps + 2 + K->lookup_w + 1 : 0;
+    const size_t nz = (size_t)V + Wc + nC + V + 1 + n_partials + n_lookup_polys + q;
+    const unsigned widths[4] = {V + Wc + (has_lookup ? 1u : 0u), 2 * (1 + n_partials) + (has_lookup ? 2 * (K->lookup_reps + 1) : 0u), 2 * q,
+                                V + nC + (has_lookup ? K->lookup_w + 1 : 0u)};
+    uint32_t sched[32], new_pow = 0;
+    size_t num_queries = 0, sched_len = 0, final_degree = 0;
+    if (bj_fri_schedule(K->security, cap, K->pow_bits, log_fri, log_n, &new_pow, &num_queries, sched, &sched_len, &final_degree) || sched_len > 32)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: compute_fri_schedule failed for the key's config");
+    if (N < cap || LOGN > 32) return verdict(out, BJ_VERIFY_SHAPE);
+    const unsigned depth = bj::log2_exact(N / cap);
+    if (n_words < 19 || W[0] != 0x424A5046ULL || W[1] != 2) return verdict(out, BJ_VERIFY_SHAPE);
+    const size_t n_pub = K->pub_cols.size();
+    const u64 nq64 = W[9];
+    const bool partial = (flags & BJ_VERIFY_PARTIAL_QUERIES) != 0;
+    if (W[2] != n_pub || W[3] != cap || W[4] != nz || W[5] != 1 || W[6] != n_lookup_terms || W[7] != sched_len || W[8] != final_degree ||
+        !(nq64 == num_queries || (partial && nq64 > 0 && nq64 < num_queries)) || W[10] != widths[0] || W[11] != widths[1] ||
+        W[12] != widths[2] || W[13] != widths[3] || W[14] != depth || W[15] != log_n || W[16] != K->fri_lde || W[17] != K->pow_bits)
+        return verdict(out, BJ_VERIFY_SHAPE);
+    const size_t nq = (size_t)nq64;
+    unsigned fri_depth[32], total_folds = 0;
+    size_t query_words = 1;
+    for (int o = 0; o < 4; o++) query_words += widths[o] + (size_t)depth * 4;
+    {
+        size_t ln = N;
+        for (size_t l = 0; l < sched_len; l++) {
+            const unsigned k = sched[l];
+            if (k < 1 || k > 3 || (ln >> k) < cap) return verdict(out, BJ_VERIFY_SHAPE);   // a schedule the prover cannot emit
+            fri_depth[l] = bj::log2_exact((ln >> k) / cap);
+            query_words += ((size_t)2 << k) + (size_t)fri_depth[l] * 4;
+            ln >>= k;
+            total_folds += k;
+        }
+    }
+    const size_t fixed = 19 + sched_len + n_pub + 3 * cap * 4 + 2 * (nz + 1 + n_lookup_terms) + sched_len * cap * 4 + 2 * final_degree;
+    if (n_words != fixed + nq * query_words) return verdict(out, BJ_VERIFY_SHAPE);
+    const u64 pow_challenge = W[18];
+    const u64 *p = W + 19;
+    for (size_t l = 0; l < sched_len; l++)
+        if (p[l] != sched[l]) return verdict(out, BJ_VERIFY_SHAPE);
+    p += sched_len;
+    const u64 *pub = p; p += n_pub;
+    const u64 *wit_cap = p; p += cap * 4;
+    const u64 *s2_cap = p; p += cap * 4;
+    const u64 *q_cap = p; p += cap * 4;
+    const u64 *vz_w = p; p += 2 * nz;
+    const u64 *vzo_w = p; p += 2;
+    const u64 *v0_w = p; p += 2 * (size_t)n_lookup_terms;
+    const u64 *fri_caps = p; p += sched_len * cap * 4;
+    const u64 *fm0 = p; p += final_degree;
+    const u64 *fm1 = p; p += final_degree;
+    const u64 *queries = p;
+
+    // ---- transcript replay (verifier.rs:924-1076) ----
+    bj::host::Transcript t;
+    t.kind = (int)K->transcript;
+    auto challenge2 = [&]() {
+        const u64 a = t.challenge(), b = t.challenge();
+        return e2{gl::canon(a), gl::canon(b)};
+    };
+    t.absorb_cap(K->cap.data(), K->cap.size());
+    t.absorb(pub, n_pub);
+    t.absorb_cap(wit_cap, cap * 4);
+    const e2 beta = challenge2(), gamma = challenge2();
+    e2 lbeta = ZERO2, lgamma = ZERO2;
+    if (has_lookup) {
+        lbeta = challenge2();
+        lgamma = challenge2();
+    }
+    t.absorb_cap(s2_cap, cap * 4);
+    const e2 alpha = challenge2();
+    t.absorb_cap(q_cap, cap * 4);
+    const e2 z = challenge2();
+    t.absorb(vz_w, 2 * nz);
+    t.absorb(vzo_w, 2);
+    t.absorb(v0_w, 2 * (size_t)n_lookup_terms);
+
+    // ---- the openings, split (verifier.rs:1150-1206) ----
+    std::vector<e2> vz(nz), v0(n_lookup_terms);
+    for (size_t i = 0; i < nz; i++) vz[i] = e2c(vz_w + 2 * i);
+    for (size_t i = 0; i < n_lookup_terms; i++) v0[i] = e2c(v0_w + 2 * i);
+    const e2 z_at_zo = e2c(vzo_w);
+    const e2 *var_z = vz.data(), *wit_z = var_z + V, *con_z = wit_z + Wc, *sig_z = con_z + nC;
+    const e2 z_at_z = sig_z[V];
+    const e2 *part_z = sig_z + V + 1, *lk = part_z + n_partials;
+    const e2 *mult_z = lk, *A_z = lk + (has_lookup ? 1 : 0), *B_z = A_z + K->lookup_reps, *tab_z = B_z + (has_lookup ? 1 : 0);
+    const e2 *qch_z = lk + n_lookup_polys;
+
+    // ---- challenge powers: lookup | specialized | general | L1 | chunks (prover.rs:599-625, verifier.rs:1000-1060) ----
+    size_t n_gate_terms = 0, n_spec_terms = 0;
+    for (const auto &g : K->gates) n_gate_terms += (size_t)g.reps * g.num_terms;
+    for (const auto &g : K->spec) n_spec_terms += (size_t)g.reps * g.num_terms;
+    const size_t total_terms = n_lookup_terms + n_spec_terms + n_gate_terms + 1 + n_chunks;
+    std::vector<e2> alphas(total_terms);
+    alphas[0] = ONE2;
+    for (size_t i = 1; i < total_terms; i++) alphas[i] = gl::e2_mul(alphas[i - 1], alpha);
+    const e2 *a_lookup = alphas.data(), *a_spec = a_lookup + n_lookup_terms, *a_gates = a_spec + n_spec_terms, *a_rest = a_gates + n_gate_terms;
+
+    e2 T = ZERO2;
+    if (has_lookup) {
+        e2 sa = ZERO2;   // the sum of the A_i(0) is B(0) (verifier.rs:1236-1256)
+        for (unsigned i = 0; i < K->lookup_reps; i++) sa = gl::e2_add(sa, v0[i]);
+        if (!eq2(sa, v0[K->lookup_reps])) return verdict(out, BJ_VERIFY_LOOKUP_SUM);
+        std::vector<e2> gp(K->lookup_w + 1);
+        gp[0] = ONE2;
+        for (unsigned j = 1; j <= K->lookup_w; j++) gp[j] = gl::e2_mul(gp[j - 1], lgamma);
+        for (unsigned i = 0; i < K->lookup_reps; i++) {   // verifier.rs:1397-1470
+            e2 d = lbeta;
+            for (unsigned j = 0; j < K->lookup_cps; j++) d = gl::e2_add(d, gl::e2_mul(gp[j], var_z[K->num_gp_vars + i * K->lookup_cps + j]));
+            if (!K->tid_var) d = gl::e2_add(d, gl::e2_mul(gp[K->lookup_w], con_z[K->table_id_col]));
+            T = gl::e2_add(T, gl::e2_mul(gl::e2_sub(gl::e2_mul(A_z[i], d), ONE2), a_lookup[i]));
+        }
+        e2 d = lbeta;
+        for (unsigned j = 0; j <= K->lookup_w; j++) d = gl::e2_add(d, gl::e2_mul(gp[j], tab_z[j]));
+        T = gl::e2_add(T, gl::e2_mul(gl::e2_sub(gl::e2_mul(B_z[0], d), mult_z[0]), a_lookup[K->lookup_reps]));
+    }
+    std::vector<e2> slots, terms;
+    bool well_formed = true;
+    {   // gates over specialized columns: no selector, their own columns (verifier.rs:1560-1638)
+        size_t off = 0;
+        for (const auto &g : K->spec) {
+            terms.assign(g.num_terms ? g.num_terms : 1, ZERO2);
+            for (unsigned r = 0; r < g.reps; r++) {
+                const size_t vb = g.first_col + (size_t)r * g.var_stride, cb = g.first_const + (size_t)r * g.const_stride;
+                well_formed = program_terms(g.prog, var_z + vb, g.var_stride, con_z + cb, g.const_stride, nullptr, 0, slots, terms.data(), g.num_terms) && well_formed;
+                for (unsigned k = 0; k < g.num_terms; k++) T = gl::e2_add(T, gl::e2_mul(terms[k], a_spec[off++]));
+            }
+        }
+    }
+    {   // gates over general-purpose columns under their selectors (verifier.rs:1640-1720)
+        size_t off = 0;
+        for (const auto &g : K->gates) {
+            if (!g.num_terms) continue;
+            e2 sel = ONE2;
+            for (unsigned b = 0; b < g.path_len; b++) sel = gl::e2_mul(sel, g.path[b] ? con_z[b] : gl::e2_sub(ONE2, con_z[b]));
+            const unsigned d = g.path_len;
+            e2 acc = ZERO2;
+            terms.assign(g.num_terms, ZERO2);
+            for (unsigned r = 0; r < g.reps; r++) {
+                const size_t vb = (size_t)r * g.var_stride, cb = d + (size_t)r * g.const_stride;
+                const e2 *v = var_z + vb;
+                switch (g.kind) {
+                    case BJ_GATE_CONSTANT_ALLOCATOR: terms[0] = gl::e2_sub(v[0], con_z[cb]); break;
+                    case BJ_GATE_FMA_NO_CONSTANT:
+                        terms[0] = gl::e2_sub(gl::e2_add(gl::e2_mul(v[2], con_z[d + 1]), gl::e2_mul(con_z[d], gl::e2_mul(v[0], v[1]))), v[3]);
+                        break;
+                    case BJ_GATE_REDUCTION4: {
+                        e2 s = ZERO2;
+                        for (int k = 0; k < 4; k++) s = gl::e2_add(s, gl::e2_mul(v[k], con_z[d + k]));
+                        terms[0] = gl::e2_sub(s, v[4]);
+                        break;
+                    }
+                    case BJ_GATE_POSEIDON2_FLATTENED: poseidon2_flattened_terms(v, terms.data()); break;
+                    case BJ_GATE_POSEIDON_FLATTENED: poseidon1_flattened_terms(v, terms.data()); break;
+                    default:   // BJ_GATE_PROGRAM
+                        if (vb > K->num_gp_vars || cb > nC || (size_t)r * g.wit_stride > Wc) {
+                            well_formed = false;
+                            break;
+                        }
+                        well_formed = program_terms(g.prog, v, K->num_gp_vars - vb, con_z + cb, nC - cb, wit_z + (size_t)r * g.wit_stride,
+                                                    Wc - (size_t)r * g.wit_stride, slots, terms.data(), g.num_terms) && well_formed;
+                        break;
+                }
+                for (unsigned k = 0; k < g.num_terms; k++) acc = gl::e2_add(acc, gl::e2_mul(terms[k], a_gates[off++]));
+            }
+            T = gl::e2_add(T, gl::e2_mul(acc, sel));
+        }
+    }
+    // (z(x) - 1) L1 and the copy-permutation chain (verifier.rs:1722-1790)
+    e2 z_n = z;
+    for (unsigned i = 0; i < log_n; i++) z_n = gl::e2_sqr(z_n);
+    const e2 vanishing = gl::e2_sub(z_n, ONE2);
+    const e2 l1 = gl::e2_mul(vanishing, gl::e2_inv(gl::e2_sub(z, ONE2)));
+    T = gl::e2_add(T, gl::e2_mul(gl::e2_mul(gl::e2_sub(z_at_z, ONE2), l1), a_rest[0]));
+    for (unsigned j = 0; j < n_chunks; j++) {
+        e2 lhs = j + 1 < n_chunks ? part_z[j] : z_at_zo, rhs = j ? part_z[j - 1] : z_at_z;
+        for (unsigned c = j * q; c < (j + 1) * q && c < V; c++) {
+            lhs = gl::e2_mul(lhs, gl::e2_add(gl::e2_add(gl::e2_mul(sig_z[c], beta), var_z[c]), gamma));
+            rhs = gl::e2_mul(rhs, gl::e2_add(gl::e2_add(gl::e2_mul(gl::e2_mul_base(z, gl::canon(K->non_residues[c])), beta), var_z[c]), gamma));
+        }
+        T = gl::e2_add(T, gl::e2_mul(gl::e2_sub(lhs, rhs), a_rest[1 + j]));
+    }
+    e2 t_chunks = ZERO2, pw = ONE2;
+    for (unsigned i = 0; i < q; i++) {
+        t_chunks = gl::e2_add(t_chunks, gl::e2_mul(qch_z[i], pw));
+        pw = gl::e2_mul(pw, z_n);
+    }
+    if (!well_formed || !eq2(T, gl::e2_mul(t_chunks, vanishing))) return verdict(out, BJ_VERIFY_QUOTIENT);
+
+    // ---- DEEP / FRI challenges, proof of work (verifier.rs:1819-1983) ----
+    const e2 cch = challenge2();
+    std::vector<u64> fri_ch(2 * sched_len);
+    for (size_t l = 0; l < sched_len; l++) {
+        t.absorb_cap(fri_caps + l * cap * 4, cap * 4);
+        const e2 ch = challenge2();
+        fri_ch[2 * l] = ch.c0;
+        fri_ch[2 * l + 1] = ch.c1;
+    }
+    t.absorb(fm0, final_degree);
+    t.absorb(fm1, final_degree);
+    if (new_pow) {
+        u64 seed[5];
+        for (int i = 0; i < 5; i++) seed[i] = gl::canon(t.challenge());
+        if (!pow_holds(K->pow_runner, seed, new_pow, pow_challenge)) return verdict(out, BJ_VERIFY_POW);
+        const u64 lh[2] = {pow_challenge & 0xFFFFFFFFULL, pow_challenge >> 32};
+        t.absorb(lh, 2);
+    }
+    // ---- query indices: drawn in order; the stored words are the proof's claim ----
+    std::vector<u64> indices(2 * nq);
+    bj::host::BoolsBuffer bools;
+    bools.max_needed = LOGN;
+    int first_mismatch = -1;
+    for (size_t i = 0; i < nq; i++) {
+        indices[i] = bools.query_index(t, log_n, log_fri);
+        const u64 stored = queries[i * query_words];
+        if (stored >= N) return verdict(out, BJ_VERIFY_SHAPE, (uint32_t)i, 0, (uint32_t)i);   // not an index of the domain at all
+        indices[nq + i] = stored;
+        if (stored != indices[i] && first_mismatch < 0) first_mismatch = (int)i;
+    }
+
+    // ---- the DEEP sources in opening order (verifier.rs:2233-2290) as words of a query's block ----
+    uint32_t leaf_off[4];
+    {
+        uint32_t o = 1;
+        for (int k = 0; k < 4; k++) {
+            leaf_off[k] = o;
+            o += widths[k] + depth * 4;
+        }
+    }
+    const uint32_t oW = leaf_off[0], oS2 = leaf_off[1], oQ = leaf_off[2], oSU = leaf_off[3];
+    struct Term { uint32_t o0, o1; };
+    std::vector<Term> src;
+    auto base_run = [&](uint32_t at, size_t count) { for (size_t i = 0; i < count; i++) src.push_back({at + (uint32_t)i, NO_C1}); };
+    auto ext_run = [&](uint32_t at, size_t pairs) { for (size_t i = 0; i < pairs; i++) src.push_back({at + 2 * (uint32_t)i, at + 2 * (uint32_t)i + 1}); };
+    base_run(oW, V + Wc);             // variables, witness columns
+    base_run(oSU + V, nC);            // constants
+    base_run(oSU, V);                 // sigmas
+    ext_run(oS2, 1 + n_partials);     // z, partial products
+    const uint32_t oLk = oS2 + 2 * (1 + n_partials);
+    if (has_lookup) {
+        base_run(oW + V + Wc, 1);             // multiplicities
+        ext_run(oLk, K->lookup_reps + 1);     // A_i, B
+        base_run(oSU + V + nC, K->lookup_w + 1);
+    }
+    ext_run(oQ, q);
+    if (src.size() != nz) return bj::fail(ctx, BJ_ERR_HIP, "bj_verify: internal error: %zu DEEP sources for %zu openings", src.size(), nz);
+    struct PubSet { u64 at; std::vector<uint32_t> cols; std::vector<u64> vals; };
+    std::vector<PubSet> pubs;
+    {
+        const u64 om = gl::omega(log_n);
+        for (size_t i = 0; i < n_pub; i++) {
+            const u64 at = gl::pow(om, K->pub_rows[i]);
+            size_t pos = 0;
+            for (; pos < pubs.size(); pos++)
+                if (pubs[pos].at == at) break;
+            if (pos == pubs.size()) pubs.push_back({at, {}, {}});
+            pubs[pos].cols.push_back(K->pub_cols[i]);
+            pubs[pos].vals.push_back(gl::canon(pub[i]));
+        }
+    }
+    const size_t n_sets = 2 + (has_lookup ? 1 : 0) + pubs.size();
+    size_t n_terms = nz + 1 + n_lookup_terms + n_pub;
+    std::vector<u64> term_words(3 * n_terms), set_words(6 * n_sets);
+    {
+        e2 chp = ONE2;
+        size_t tno = 0, sno = 0;
+        auto open_set = [&](e2 at) {
+            u64 *S = set_words.data() + 6 * sno;
+            S[0] = tno; S[2] = at.c0; S[3] = at.c1; S[4] = 0; S[5] = 0;
+        };
+        auto add_term = [&](Term s, e2 value) {
+            u64 *Tw = term_words.data() + 3 * tno++;
+            Tw[0] = (u64)s.o0 | ((u64)s.o1 << 32);
+            Tw[1] = chp.c0; Tw[2] = chp.c1;
+            u64 *S = set_words.data() + 6 * sno;
+            const e2 c = gl::e2_add(e2{S[4], S[5]}, gl::e2_mul(chp, value));
+            S[4] = c.c0; S[5] = c.c1;
+            chp = gl::e2_mul(chp, cch);
+        };
+        auto close_set = [&]() { set_words[6 * sno++ + 1] = tno; };
+        open_set(z);
+        for (size_t i = 0; i < nz; i++) add_term(src[i], vz[i]);
+        close_set();
+        open_set(gl::e2_mul_base(z, gl::omega(log_n)));
+        add_term({oS2, oS2 + 1}, z_at_zo);
+        close_set();
+        if (has_lookup) {
+            open_set(ZERO2);
+            for (unsigned i = 0; i < n_lookup_terms; i++) add_term({oLk + 2 * i, oLk + 2 * i + 1}, v0[i]);
+            close_set();
+        }
+        for (const auto &ps : pubs) {
+            open_set(e2{ps.at, 0});
+            for (size_t i = 0; i < ps.cols.size(); i++) add_term({oW + ps.cols[i], NO_C1}, e2{ps.vals[i], 0});
+            close_set();
+        }
+    }
+
+    // ---- device: the query section once, the small tables behind it ----
+    const size_t n_oracles = 4 + sched_len, cap_words = cap * 4;
+    size_t off = 0;
+    auto take = [&off](size_t words) {
+        const size_t at = off;
+        off += (words + 1) & ~(size_t)1;
+        return at;
+    };
+    const size_t o_q = take(nq * query_words), o_small = off;
+    const size_t o_idx = take(2 * nq), o_caps = take(n_oracles * cap_words), o_terms = take(term_words.size()), o_sets = take(set_words.size());
+    const size_t o_frich = take(fri_ch.size()), o_fm = take(2 * final_degree), small_words = off - o_small;
+    const size_t o_st_open = take((n_oracles * nq + 1) / 2), o_st_deep = take((nq + 1) / 2);
+    if (int rc = bj::ensure_scratch(ctx, off)) return rc;
+    if (int rc = bj::ensure_twiddles(ctx, LOGN, true)) return rc;
+    u64 *D = ctx->d_scratch;
+    hipStream_t st = ctx->stream;
+    {
+        std::vector<u64> small(small_words, 0);
+        u64 *s = small.data() - o_small;
+        std::memcpy(s + o_idx, indices.data(), indices.size() * 8);
+        std::memcpy(s + o_caps, wit_cap, cap_words * 8);
+        std::memcpy(s + o_caps + cap_words, s2_cap, cap_words * 8);
+        std::memcpy(s + o_caps + 2 * cap_words, q_cap, cap_words * 8);
+        std::memcpy(s + o_caps + 3 * cap_words, K->cap.data(), cap_words * 8);
+        std::memcpy(s + o_caps + 4 * cap_words, fri_caps, sched_len * cap_words * 8);
+        std::memcpy(s + o_terms, term_words.data(), term_words.size() * 8);
+        std::memcpy(s + o_sets, set_words.data(), set_words.size() * 8);
+        std::memcpy(s + o_frich, fri_ch.data(), fri_ch.size() * 8);
+        for (size_t i = 0; i < final_degree; i++) {
+            s[o_fm + i] = gl::canon(fm0[i]);
+            s[o_fm + final_degree + i] = gl::canon(fm1[i]);
+        }
+        if (int rc = bj_memcpy_h2d(ctx, D + o_q, queries, nq * query_words * 8)) return rc;
+        if (int rc = bj_memcpy_h2d(ctx, D + o_small, small.data(), small_words * 8)) return rc;
+    }
+    bj::VerifyOpenArgs OA{};
+    OA.queries = D + o_q;
+    OA.caps = D + o_caps;
+    OA.status = (uint32_t *)(D + o_st_open);
+    OA.n_queries = (uint32_t)nq;
+    OA.query_words = (uint32_t)query_words;
+    OA.n_oracles = (uint32_t)n_oracles;
+    VerifyDeepArgs DA{};
+    DA.queries = D + o_q;
+    DA.terms = D + o_terms;
+    DA.sets = D + o_sets;
+    DA.fri_ch = D + o_frich;
+    DA.final0 = D + o_fm;
+    DA.final1 = D + o_fm + final_degree;
+    DA.roots = ctx->tw_inv;
+    DA.status = (uint32_t *)(D + o_st_deep);
+    DA.n_queries = (uint32_t)nq;
+    DA.query_words = (uint32_t)query_words;
+    DA.n_sets = (uint32_t)n_sets;
+    DA.n_fri = (uint32_t)sched_len;
+    DA.final_degree = (uint32_t)final_degree;
+    DA.log_full = LOGN;
+    DA.total_folds = total_folds;
+    DA.omega = gl::omega(LOGN);
+    DA.kappa = gl::inv(gl::GEN);
+    for (int o = 0; o < 4; o++) OA.oracle[o] = bj::VerifyOracle{leaf_off[o], widths[o], depth, 0, (uint32_t)(o * cap_words)};
+    {
+        uint32_t o = leaf_off[3] + widths[3] + depth * 4, shift = 0;
+        for (size_t l = 0; l < sched_len; l++) {
+            shift += sched[l];
+            OA.oracle[4 + l] = bj::VerifyOracle{o, 2u << sched[l], fri_depth[l], shift, (uint32_t)((4 + l) * cap_words)};
+            DA.fri_off[l] = o;
+            DA.sched[l] = (unsigned char)sched[l];
+            o += (2u << sched[l]) + fri_depth[l] * 4;
+        }
+    }
+    std::vector<uint32_t> st_open(n_oracles * nq), st_deep(nq);
+    // every chain of the proof judged at one set of indices; the first failure in the order of include/boojum_hip.h
+    auto judge = [&](const u64 *d_indices, bool timed, Failure *f) -> int {
+        OA.indices = DA.indices = d_indices;
+        if (timed)
+            for (auto &e : ctx->verify_ev)
+                if (!e) BJ_HIP(ctx, hipEventCreate(&e));
+        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_ev[0], st));
+        bj::launch_verify_openings((int)K->hasher, OA, st);
+        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_ev[1], st));
+        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_ev[2], st));
+        hipLaunchKernelGGL(verify_deep_fri_kernel, dim3((unsigned)nq), dim3(64), 0, st, DA);
+        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_ev[3], st));
+        BJ_CHECK_LAUNCH(ctx);
+        if (int rc = bj_memcpy_d2h(ctx, st_open.data(), OA.status, st_open.size() * 4)) return rc;
+        if (int rc = bj_memcpy_d2h(ctx, st_deep.data(), DA.status, st_deep.size() * 4)) return rc;
+        if (timed) ctx->verify_timed = true;
+        *f = Failure{};
+        for (size_t i = 0; i < nq; i++) {
+            for (uint32_t o = 0; o < 4; o++)
+                if (!st_open[o * nq + i]) { *f = Failure{BJ_VERIFY_MERKLE, (uint32_t)i, o}; return BJ_OK; }
+            for (uint32_t l = 0; l < sched_len; l++) {
+                if (st_deep[i] == 1 + l) { *f = Failure{BJ_VERIFY_FRI_VALUE, (uint32_t)i, l}; return BJ_OK; }
+                if (!st_open[(4 + l) * nq + i]) { *f = Failure{BJ_VERIFY_FRI_MERKLE, (uint32_t)i, l}; return BJ_OK; }
+            }
+            if (st_deep[i]) { *f = Failure{BJ_VERIFY_FINAL, (uint32_t)i, 0}; return BJ_OK; }
+        }
+        return BJ_OK;
+    };
+    Failure at_drawn, at_stored;
+    if (int rc = judge(D + o_idx, true, &at_drawn)) return rc;
+    if (at_drawn.stage == BJ_VERIFY_OK) {
+        if (first_mismatch < 0) return verdict(out, BJ_VERIFY_OK, 0, 0, (uint32_t)nq);
+        return verdict(out, BJ_VERIFY_SHAPE, (uint32_t)first_mismatch, 0, (uint32_t)first_mismatch);
+    }
+    if (first_mismatch < 0) return verdict(out, at_drawn.stage, at_drawn.query, at_drawn.oracle, at_drawn.query);
+    // The stored indices are not the drawn ones and the drawn ones fail: what do the openings the proof carries fail at?  This second
+    // pass exists for two rows of the stage table alone and never turns a rejection into an acceptance: a final monomial and a FRI
+    // cap are absorbed BEFORE the indices are drawn, so editing either moves every index — at the drawn indices such a proof fails
+    // at the witness path of query 0, whatever was edited; BJ_VERIFY_FINAL for the monomial and BJ_VERIFY_FRI_VALUE for a FRI leaf
+    // whose path (and therefore cap entry) was recomputed can only be told at the indices the prover opened.
+    if (int rc = judge(D + o_idx + nq, false, &at_stored)) return rc;
+    if (at_stored.stage == BJ_VERIFY_OK) return verdict(out, BJ_VERIFY_SHAPE, (uint32_t)first_mismatch, 0, (uint32_t)first_mismatch);
+    return verdict(out, at_stored.stage, at_stored.query, at_stored.oracle, at_stored.query);
+}
+
+void take_gate(bj_vk::Gate &g, const bj_gate_desc &G) {
+    g.kind = G.kind;
+    g.path_len = G.path_len;
+    for (unsigned b = 0; b < G.path_len && b < 8; b++) g.path[b] = G.path[b] ? 1 : 0;
+    g.reps = G.num_repetitions; g.var_stride = G.var_stride; g.wit_stride = G.wit_stride; g.const_stride = G.const_stride;
+    g.num_terms = G.num_terms;
+}
+
+void finish_config(bj_vk *k, unsigned fri_lde, unsigned cap_size, unsigned security, unsigned pow_bits, unsigned transcript, unsigned hasher,
+                   unsigned pow_runner) {
+    k->fri_lde = fri_lde; k->cap_size = cap_size; k->security = security; k->pow_bits = pow_bits;
+    k->transcript = transcript ? transcript : BJ_TRANSCRIPT_POSEIDON2;
+    k->hasher = hasher ? hasher : BJ_HASHER_POSEIDON2;
+    k->pow_runner = pow_runner ? pow_runner : BJ_POW_BLAKE2S256;
+    k->log_fri = bj::log2_exact(fri_lde);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bj_vk_create(const bj_circuit *c, const uint64_t *setup_cap, const bj_proof_config *cfg, bj_vk **out) {
+    if (!out) return bj::fail(nullptr, BJ_ERR_INVALID_ARG, "bj_vk_create: null out pointer");
+    *out = nullptr;
+    if (!c || !cfg || !setup_cap) return bj::fail(nullptr, BJ_ERR_INVALID_ARG, "bj_vk_create: null argument");
+    if (int rc = bj::circuit_check(nullptr, "bj_vk_create", c, cfg, true, nullptr)) return rc;
+    bj_vk *k = new bj_vk();
+    k->log_n = c->log_n; k->V = c->num_vars; k->num_gp_vars = c->num_gp_vars; k->Wc = c->num_witness_cols; k->nC = c->num_constant_cols;
+    k->lookup_w = c->lookup_width; k->lookup_reps = c->lookup_reps; k->q = c->quotient_degree;
+    k->tid_var = c->lookup_reps && c->table_id_col == BJ_TABLE_ID_AS_VARIABLE;
+    k->table_id_col = k->tid_var ? 0 : c->table_id_col;
+    k->lookup_cps = c->lookup_width + (k->tid_var ? 1u : 0u);
+    auto take_program = [](bj_vk::Program &P, const bj_gate_program *p) {   // circuit_check has canonicalised it once: it cannot fail here
+        bj::canon::Program C;
+        std::string err;
+        if (bj::canon::canonicalize(p, &C, &err)) return;
+        bj::pack_program(C, &P.rel, &P.values);
+        P.n_slots = C.num_slots;
+    };
+    k->gates.resize(c->num_gates);
+    for (unsigned g = 0; g < c->num_gates; g++) {
+        take_gate(k->gates[g], c->gates[g]);
+        if (c->gates[g].kind == BJ_GATE_PROGRAM) take_program(k->gates[g].prog, c->gates[g].program);
+    }
+    uint64_t col = (uint64_t)c->num_gp_vars + (uint64_t)k->lookup_cps * c->lookup_reps, spec_consts = 0;
+    for (unsigned g = 0; g < c->num_specialized_gates; g++)
+        spec_consts += (uint64_t)c->specialized_gates[g].num_repetitions * c->specialized_gates[g].const_stride;
+    unsigned ccol = c->num_constant_cols - (unsigned)spec_consts;
+    k->spec.resize(c->num_specialized_gates);
+    for (unsigned g = 0; g < c->num_specialized_gates; g++) {
+        bj_vk::Gate &sg = k->spec[g];
+        take_gate(sg, c->specialized_gates[g]);
+        take_program(sg.prog, c->specialized_gates[g].program);
+        sg.first_col = (unsigned)col;
+        sg.first_const = ccol;
+        col += (uint64_t)sg.reps * sg.var_stride;
+        ccol += sg.reps * sg.const_stride;
+    }
+    k->non_residues.assign(c->non_residues, c->non_residues + c->num_vars);
+    for (unsigned i = 0; i < c->num_public_inputs; i++) {
+        k->pub_cols.push_back(c->public_input_cols[i]);
+        k->pub_rows.push_back(c->public_input_rows[i]);
+    }
+    finish_config(k, cfg->fri_lde_factor, cfg->cap_size, cfg->security_level, cfg->pow_bits, cfg->transcript, cfg->tree_hasher, cfg->pow_runner);
+    k->cap.assign(setup_cap, setup_cap + 4 * (size_t)cfg->cap_size);
+    *out = k;
+    return BJ_OK;
+}
+
+int bj_vk_from_setup(const bj_setup *S, bj_vk **out) {
+    if (!out) return bj::fail(nullptr, BJ_ERR_INVALID_ARG, "bj_vk_from_setup: null out pointer");
+    *out = nullptr;
+    if (!S) return bj::fail(nullptr, BJ_ERR_INVALID_ARG, "bj_vk_from_setup: null setup");
+    bj_vk *k = new bj_vk();
+    k->log_n = S->log_n; k->V = S->V; k->num_gp_vars = S->num_gp_vars; k->Wc = S->Wc; k->nC = S->nC;
+    k->lookup_w = S->lookup_w; k->lookup_reps = S->lookup_reps; k->q = S->q;
+    k->tid_var = S->tid_var; k->table_id_col = S->table_id_col; k->lookup_cps = S->lookup_cps;
+    auto take_program = [](bj_vk::Program &P, const bj::DevProgram &d) {
+        P.rel = d.h_rel;
+        P.values = d.h_values;
+        P.n_slots = slots_of(P.rel);
+    };
+    k->gates.resize(S->n_gates);
+    for (unsigned g = 0; g < S->n_gates; g++) {
+        const int *f = S->gates_flat.data() + 12 * g;
+        bj_vk::Gate &G = k->gates[g];
+        G.kind = f[0]; G.path_len = (unsigned)f[1]; G.reps = (unsigned)f[2]; G.var_stride = (unsigned)f[3]; G.const_stride = (unsigned)f[4];
+        G.num_terms = (unsigned)f[5];
+        for (unsigned b = 0; b < G.path_len && b < 6; b++) G.path[b] = (unsigned char)f[6 + b];
+        G.wit_stride = S->gate_wit_stride[g];
+        if (G.kind == BJ_GATE_PROGRAM) take_program(G.prog, S->programs[g]);
+    }
+    k->spec.resize(S->spec.size());
+    for (size_t g = 0; g < S->spec.size(); g++) {
+        const bj_setup::SpecGate &sg = S->spec[g];
+        bj_vk::Gate &G = k->spec[g];
+        G.kind = BJ_GATE_PROGRAM; G.reps = sg.reps; G.var_stride = sg.width; G.const_stride = sg.const_width; G.num_terms = sg.terms;
+        G.first_col = sg.first_col; G.first_const = sg.first_const;
+        take_program(G.prog, sg.program);
+    }
+    k->non_residues = S->non_residues;
+    k->pub_cols = S->pub_cols;
+    k->pub_rows = S->pub_rows;
+    finish_config(k, S->fri_lde, S->cap_size, S->security, S->pow_bits, S->transcript, S->hasher, S->pow_runner);
+    k->cap = S->cap;
+    *out = k;
+    return BJ_OK;
+}
+
+void bj_vk_destroy(bj_vk *vk) { delete vk; }
+
+int bj_verify(bj_ctx *ctx, const bj_vk *vk, const uint64_t *proof_words, size_t n_words, unsigned flags, bj_verify_report *out) {
+    return verify_impl(ctx, vk, proof_words, n_words, flags, out);
+}
+
+int bj_verify_proof(bj_ctx *ctx, const bj_vk *vk, const bj_proof *proof, bj_verify_report *out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!proof) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_proof: null proof");
+    const std::vector<u64> &w = bj::proof_words(proof);
+    return verify_impl(ctx, vk, w.data(), w.size(), 0, out);
+}
+
+int bj_verify_kernel_ms(bj_ctx *ctx, float *openings_ms, float *deep_fri_ms) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!ctx->verify_timed) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_kernel_ms: the last bj_verify on this context did not reach its kernels");
+    float a = 0, b = 0;
+    BJ_HIP(ctx, hipEventSynchronize(ctx->verify_ev[3]));
+    BJ_HIP(ctx, hipEventElapsedTime(&a, ctx->verify_ev[0], ctx->verify_ev[1]));
+    BJ_HIP(ctx, hipEventElapsedTime(&b, ctx->verify_ev[2], ctx->verify_ev[3]));
+    if (openings_ms) *openings_ms = a;
+    if (deep_fri_ms) *deep_fri_ms = b;
+    return BJ_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-"""Parser of the flat u64 proof serialisation produced by bj_proof_serialize (csrc/prover.hip) into a dict with the field
+"""Parser (and its inverse) of the flat u64 proof serialisation produced by bj_proof_serialize (csrc/prover.hip) into a dict with the field
 names of the reference's `Proof` (src/cs/implementations/proof.rs:121-136).
 
 Layout (all u64, little endian):
@@ -72,3 +72,53 @@ def parse(buf, security_level=None, pow_bits=0):
     proof["_query_indices"] = indices
     proof["_schedule"] = sched
     return proof
+
+
+def serialize(proof, log_n=None):
+    """The inverse of `parse`: the BJPF version 2 words of a proof dict (parse(serialize(p)) == p up to the fields the words do not
+    carry: security_level comes back as given to `parse`).  The header fields are derived from the dict — the leaf widths and the
+    path depth from the first query, the schedule from `_schedule` or from the FRI leaf sizes, log_n from the depth unless given —
+    so a dict cut out of the reference's `Proof` JSON (tests/golden) serialises as well as one that `parse` returned; a proof
+    without queries needs log_n and serialises zero widths."""
+    cfg = proof["proof_config"]
+    cap, fri_lde = int(cfg["merkle_tree_cap_size"]), int(cfg["fri_lde_factor"])
+    queries = proof["queries_per_fri_repetition"]
+    fri_caps = [proof["fri_base_oracle_cap"]] + list(proof["fri_intermediate_oracles_caps"])
+    names = ("witness_query", "stage_2_query", "quotient_query", "setup_query")
+    if queries:
+        q0 = queries[0]
+        widths = [len(q0[k]["leaf_elements"]) for k in names]
+        depth = len(q0["witness_query"]["proof"])
+        sched = [int(k) for k in proof["_schedule"]] if "_schedule" in proof else [(len(f["leaf_elements"]) // 2).bit_length() - 1 for f in q0["fri_queries"]]
+        if log_n is None:
+            log_n = depth + cap.bit_length() - 1 - (fri_lde.bit_length() - 1)
+    else:
+        widths, depth, sched = [0, 0, 0, 0], 0, [int(k) for k in proof.get("_schedule", [])]
+        if log_n is None:
+            raise ValueError("a proof without queries does not tell its trace length: pass log_n")
+    if len(sched) != len(fri_caps):
+        raise ValueError("schedule and FRI caps disagree")
+    fm = proof["final_fri_monomials"]
+    indices = proof.get("_query_indices")
+    if indices is None or len(indices) != len(queries):
+        raise ValueError("_query_indices: one stored index per query is needed")
+    out = [MAGIC, 2, len(proof["public_inputs"]), cap, len(proof["values_at_z"]), len(proof["values_at_z_omega"]), len(proof["values_at_0"]),
+           len(fri_caps), len(fm[0]), len(queries)] + widths + [depth, int(log_n), fri_lde, int(cfg.get("pow_bits") or 0),
+                                                                int(proof.get("pow_challenge") or 0)]
+    out += sched
+    out += [int(x) for x in proof["public_inputs"]]
+
+    def flat(rows):
+        return [int(x) for row in rows for x in row]
+    for k in ("witness_oracle_cap", "stage_2_oracle_cap", "quotient_oracle_cap", "values_at_z", "values_at_z_omega", "values_at_0"):
+        out += flat(proof[k])
+    for c in fri_caps:
+        out += flat(c)
+    out += [int(x) for x in fm[0]] + [int(x) for x in fm[1]]
+    for idx, qd in zip(indices, queries):
+        out.append(int(idx))
+        for k in names:
+            out += [int(x) for x in qd[k]["leaf_elements"]] + flat(qd[k]["proof"])
+        for f in qd["fri_queries"]:
+            out += [int(x) for x in f["leaf_elements"]] + flat(f["proof"])
+    return np.array(out, dtype=np.uint64)

@@ -44,7 +44,8 @@ typedef struct bj_ctx bj_ctx;
 
 /* 2: bj_gate_desc.wit_stride, bj_comm.all_gather_stream (round 2); 3: op lists in any numbering, run-time compiled gates;
  * 4: bj_proof_config.pow_runner, bj_circuit.table_id_col = BJ_TABLE_ID_AS_VARIABLE (round 5); 5: bj_comm_replay_capture,
- * bj_proof_workspace_bytes, bj_setup_device_bytes; 6: bj_prove_async / bj_proof_wait, the tiled-monomial operators, bj_comm_peer_create (round 6) */
+ * bj_proof_workspace_bytes, bj_setup_device_bytes; 6: bj_prove_async / bj_proof_wait, the tiled-monomial operators, bj_comm_peer_create (round 6);
+ * entry points added within version 6 (no layout of an existing struct changes with them): bj_check_satisfied, bj_lookup_multiplicities, bj_vk_* / bj_verify */
 #define BJ_ABI_VERSION 6
 int bj_abi_version(void);
 /* 1 if bj_setup_create accepts bj_gate_desc.kind == kind, else 0: gate kinds are added within an ABI version (no layout
@@ -751,6 +752,64 @@ int bj_check_satisfied(bj_ctx *ctx, const bj_setup *setup, const uint64_t *d_var
 int bj_check_satisfied_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_vec, size_t witness_vec_len,
                                   const void *variables_hint, size_t variables_hint_len, const void *witness_hint,
                                   size_t witness_hint_len, bj_unsat_report *out);
+
+/* ---- is this a proof under my key: Verifier::verify (src/cs/implementations/verifier.rs:888-2524) and verify_circuit
+ * (src/cs/implementations/convenience.rs:198) ----
+ * bj_vk is the VerificationKey (verifier.rs:28-60): the fixed parameters of a circuit — geometry, the gate list with the selector
+ * paths and the canonical op lists (gate_canon.h), lookup parameters, non-residues, public input locations, the proof config —
+ * and the setup cap.  No columns, no LDE, no tree: a few KB of host memory and nothing on a device, so a verifying host needs no
+ * setup.  bj_vk_create is host-only: it checks the circuit and the config exactly as bj_setup_create does (the same refusals in
+ * the same words; sigma / constant / table columns are not asked for) and copies what it needs; the caller's arrays may go
+ * away.  A context-free call has no bj_ctx to leave its message in: bj_last_error(NULL) returns the message of the last failed
+ * context-free call of the calling thread.  bj_vk_from_setup takes the same key out of a setup (sharded or not). */
+typedef struct bj_vk bj_vk;
+int bj_vk_create(const bj_circuit *circuit, const uint64_t *setup_cap /* cap_size*4 */, const bj_proof_config *config, bj_vk **out);
+int bj_vk_from_setup(const bj_setup *setup, bj_vk **out);
+void bj_vk_destroy(bj_vk *vk);
+
+typedef enum bj_verify_stage {            /* first failing check, in the order of verifier.rs:888-2524 */
+    BJ_VERIFY_OK = 0,
+    BJ_VERIFY_SHAPE,            /* header / counts / widths / depths / schedule do not match the key (incl. a stored query index that is not the drawn one) */
+    BJ_VERIFY_LOOKUP_SUM,       /* verifier.rs:1236-1256 */
+    BJ_VERIFY_QUOTIENT,         /* identity at z, verifier.rs:1090-1810 */
+    BJ_VERIFY_POW,              /* verifier.rs:1957-1983 */
+    BJ_VERIFY_MERKLE,           /* a base-oracle opening: oracle = 0 witness, 1 stage 2, 2 quotient, 3 setup */
+    BJ_VERIFY_FRI_VALUE,        /* value carried into FRI layer `oracle` is not in the opened leaf (layer 0: the DEEP value) */
+    BJ_VERIFY_FRI_MERKLE,       /* FRI layer `oracle` */
+    BJ_VERIFY_FINAL             /* last fold != final monomials at the point */
+} bj_verify_stage;
+typedef struct bj_verify_report {
+    uint32_t stage;             /* bj_verify_stage */
+    uint32_t query;             /* stages BJ_VERIFY_MERKLE..BJ_VERIFY_FINAL, and BJ_VERIFY_SHAPE for an index word: the smallest failing query */
+    uint32_t oracle;            /* BJ_VERIFY_MERKLE: base oracle; BJ_VERIFY_FRI_VALUE / _FRI_MERKLE: layer */
+    uint32_t queries_checked;   /* BJ_VERIFY_OK: the query openings the proof carries; otherwise the queries that passed before the named one */
+} bj_verify_report;
+
+#define BJ_VERIFY_PARTIAL_QUERIES 1u   /* the proof carries only the first k > 0 query openings; indices are drawn in order */
+
+/* proof_words: BJPF version 2 (bj_proof_serialize; layout in era_boojum_amd/proof_format.py).  Returns BJ_OK whenever the check ran
+ * — the verdict is in *out, as for bj_check_satisfied; a negative status only for null arguments, a key whose tree hasher the
+ * context cannot run, or a HIP failure.  A buffer that is not a proof of the key's shape — wrong magic or version, counts,
+ * widths, depths or schedule that are not the key's, too short, too long — is BJ_OK with stage BJ_VERIFY_SHAPE: every count is
+ * compared with the value the key dictates before it sizes anything, and the total length with n_words before any word behind
+ * the header is read.
+ * Host (csrc/verifier.hip): transcript replay, the lookup sum, the quotient identity at z (op lists are interpreted over F_p^2),
+ * the DEEP and FRI challenges, the proof of work, the query indices.  Device, two kernels over the query section uploaded once:
+ * every Merkle chain (query x {4 base oracles, FRI layers}), and per query the DEEP value from the four opened leaves
+ * (verifier.rs:2233-2290), the fold chain through the schedule and the final monomials at the point.
+ * Per-query failures: the smallest failing query and, inside it, the reference's order — the four base oracles, then per FRI
+ * layer the carried value and the layer's path, then the final check.  They are judged at the DRAWN index.  Where a query fails
+ * there and its stored index word is not the drawn one, the openings are judged again at the stored index and that diagnosis is
+ * reported (a word that went into the transcript before the indices were drawn — a final monomial, a FRI cap — moves every index:
+ * what is named is then the check that word breaks, not the path of a leaf the prover never opened); openings that pass at an
+ * index that is not the drawn one are BJ_VERIFY_SHAPE.  A proof is accepted only if every check passes at the drawn indices and
+ * every stored index is the drawn one.
+ * Runs on the context's stream, in the context's scratch, and synchronises; nothing of the context that a proof depends on is
+ * modified: a proof made afterwards is byte for byte the proof made before.  Not while a proof runs on the context. */
+int bj_verify(bj_ctx *ctx, const bj_vk *vk, const uint64_t *proof_words, size_t n_words, unsigned flags, bj_verify_report *out);
+int bj_verify_proof(bj_ctx *ctx, const bj_vk *vk, const bj_proof *proof, bj_verify_report *out);   /* the handle bj_prove returned */
+/* HIP-event durations of the two kernels of the last bj_verify on this context that reached them (measurement only). */
+int bj_verify_kernel_ms(bj_ctx *ctx, float *openings_ms, float *deep_fri_ms);
 
 /* The host loop over witnesses around prove_cpu_basic (prover.rs:153-168, convenience.rs:119-196), pipelined from ONE host
  * thread: bj_prove_async queues bj_prove(setup, witness) on one of the context's two internal lanes (each its own HIP stream,

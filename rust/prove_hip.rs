@@ -208,6 +208,38 @@ impl Drop for HipSetup {
     }
 }
 
+/// The verification key of a setup (`VerificationKey`, verifier.rs:28-60: fixed parameters + setup cap) as the library holds it:
+/// host memory only.  A verifying host that has no setup makes the same key with `bj_vk_create` from the `bj_circuit`
+/// description `hip_setup` builds, the setup cap of `vk.json` and the proof config.
+pub struct HipVk {
+    raw: *mut bj_vk,
+}
+impl Drop for HipVk {
+    fn drop(&mut self) {
+        unsafe { bj_vk_destroy(self.raw) }
+    }
+}
+impl HipSetup {
+    pub fn verification_key(&self) -> HipVk {
+        let mut raw = std::ptr::null_mut();
+        let rc = unsafe { bj_vk_from_setup(self.raw, &mut raw) };
+        assert_eq!(rc, 0, "bj_vk_from_setup: {}", unsafe { CStr::from_ptr(bj_last_error(std::ptr::null())) }.to_string_lossy());
+        HipVk { raw }
+    }
+}
+
+/// The sibling of `prove_hip` on the checking side — `Verifier::verify` (verifier.rs:888-2524) / `verify_circuit`
+/// (convenience.rs:198) — on the BJPF words `bj_proof_serialize` wrote: transcript replay, lookup sum and quotient identity on the
+/// host, every Merkle chain, the DEEP values and the fold chains on the device.  `report.stage == BJ_VERIFY_OK as u32` is
+/// "valid"; any other stage names the first failing check (include/boojum_hip.h).  `partial_queries`: the words carry only the
+/// first k query openings.
+pub fn verify_hip(ctx: &HipCtx, vk: &HipVk, words: &[u64], partial_queries: bool) -> bj_verify_report {
+    let mut report = bj_verify_report { stage: 0, query: 0, oracle: 0, queries_checked: 0 };
+    let flags = if partial_queries { BJ_VERIFY_PARTIAL_QUERIES } else { 0 };
+    ctx.check(unsafe { bj_verify(ctx.raw, vk.raw, words.as_ptr(), words.len(), flags, &mut report) });
+    report
+}
+
 impl<P: crate::field::traits::field_like::PrimeFieldLikeVectorized<Base = F>, CFG: CSConfig, A: GoodAllocator>
     CSReferenceAssembly<F, P, CFG, A>
 {
