@@ -126,6 +126,9 @@ _SIGNATURES = {
     "bj_check_satisfied": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bj_check_satisfied_from_dumps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
                                                 C.c_void_p]),
+    "bj_sigma_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "bj_check_copy_constraints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bj_vk_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "bj_vk_from_setup": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "bj_vk_destroy": (None, [C.c_void_p]),
@@ -356,6 +359,17 @@ class Context:
         n = 1 << log_n
         self._check(self._lib.bj_sigmas_from_placement(self._h, d_placement, place_stride or n, num_vars, log_n, _np_ptr(nr), d_sigmas,
                                                        sig_stride or n))
+
+    def sigma_cells(self, d_sigmas, num_vars, log_n, non_residues, d_cells, sig_stride=None, cell_stride=None):
+        """bj_sigma_cells, the inverse of sigmas_from_placement: d_sigmas [num_vars][n] u64 -> d_cells [num_vars][n] u32, the cell
+        j * n + r each word k_j * omega^r names, 0xFFFFFFFF for a word in no coset.  Returns (first_invalid, num_invalid):
+        the smallest key row * num_vars + column of such a word (None when there is none) and their number."""
+        n = 1 << log_n
+        nr = np.ascontiguousarray(non_residues[:num_vars], dtype=np.uint64)
+        first, count = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.bj_sigma_cells(self._h, d_sigmas, sig_stride or n, num_vars, log_n, _np_ptr(nr), d_cells, cell_stride or n,
+                                             C.byref(first), C.byref(count)))
+        return (None if first.value == NO_CELL_KEY else int(first.value)), int(count.value)
 
     def lookup_polys(self, d_lvars, var_stride, d_table_id, d_tables, table_stride, d_mult, reps, width, log_n, beta, gamma, d_A, d_B):
         self._check(self._lib.bj_lookup_polys(self._h, d_lvars, var_stride, d_table_id, d_tables, table_stride, d_mult, reps, width,
@@ -1134,6 +1148,46 @@ class SatisfiabilityReport:
         return "Unsatisfied at table row %d: multiplicities sum to %d, %d lookups" % (self.row, self.expected, self.value)
 
 
+class _CopyReport(C.Structure):  # bj_copy_report
+    _fields_ = [("kind", C.c_uint32), ("column", C.c_uint32), ("partner_column", C.c_uint32), ("row", C.c_uint64), ("partner_row", C.c_uint64),
+                ("value", C.c_uint64), ("partner_value", C.c_uint64), ("variable", C.c_uint32), ("failures", C.c_uint64 * 4)]
+
+
+COPY_OK, COPY_SIGMA_INVALID, COPY_SIGMA_NOT_PERMUTATION, COPY_VALUE_MISMATCH = range(4)     # bj_copy_kind
+NO_CELL = 0xFFFFFFFF                # bj_sigma_cells: a word in no coset; bj_copy_report.variable: no placement index
+NO_CELL_KEY = (1 << 64) - 1         # bj_sigma_cells: *first_invalid when every word is valid
+
+
+@dataclass
+class CopyReport:
+    """bj_copy_report: the first cell that breaks a copy constraint (categories and order: include/boojum_hip.h) and the number of
+    failures per kind.  True when sigma is a permutation of the cells and every cell holds the value of the cell its sigma names."""
+    kind: int = COPY_OK
+    column: int = 0
+    row: int = 0
+    partner_column: int = 0
+    partner_row: int = 0
+    value: int = 0
+    partner_value: int = 0
+    variable: int = NO_CELL
+    failures: tuple = (0, 0, 0, 0)
+
+    def __bool__(self):
+        return self.kind == COPY_OK
+
+    def __str__(self):
+        if self.kind == COPY_OK:
+            return "Copy constraints hold"
+        if self.kind == COPY_SIGMA_INVALID:
+            return "sigma at column %d row %d names no cell" % (self.column, self.row)
+        if self.kind == COPY_SIGMA_NOT_PERMUTATION:
+            return "sigma is no permutation: column %d row %d names column %d row %d, and so does another cell" % (
+                self.column, self.row, self.partner_column, self.partner_row)
+        return "column %d row %d holds %d, the cell its sigma names (column %d row %d) holds %d%s" % (
+            self.column, self.row, self.value, self.partner_column, self.partner_row, self.partner_value,
+            "" if self.variable == NO_CELL else " (variable %d)" % self.variable)
+
+
 class _Ticket:
     """A proof in flight (bj_ticket) + the host arrays it reads."""
 
@@ -1387,6 +1441,14 @@ class ProverSetup:
         self._ctx._check(self._lib.bj_check_satisfied_from_dumps(self._ctx._h, self._h, w, len(w), v, len(v) if v else 0, x, len(x) if x else 0,
                                                                  C.byref(r)))
         return self._report(r)
+
+    def check_copy_constraints(self, d_variables):
+        """bj_check_copy_constraints on a witness in HBM (the pointer prove_dev takes): a CopyReport, true when every copy
+        constraint holds.  bj_check_satisfied does not look at them, and bj_prove refuses such a witness without naming a cell."""
+        r = _CopyReport()
+        self._ctx._check(self._lib.bj_check_copy_constraints(self._ctx._h, self._h, d_variables, C.byref(r)))
+        return CopyReport(int(r.kind), int(r.column), int(r.row), int(r.partner_column), int(r.partner_row), int(r.value),
+                          int(r.partner_value), int(r.variable), tuple(int(x) for x in r.failures))
 
     def count_multiplicities_dev(self, d_variables, d_multiplicities):
         """bj_setup_lookup_multiplicities on a witness already in HBM: writes the column [n] at d_multiplicities."""

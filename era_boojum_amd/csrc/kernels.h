@@ -150,4 +150,12 @@ struct DeepSetHostArgs {
 };
 void launch_deep_accumulate_multi(const DeepSetHostArgs *sets, unsigned n_sets, size_t N, size_t I0, const u64 *d_tw_fwd,
                                   u64 *d_dst0, u64 *d_dst1, int accumulate, hipStream_t s);
+// copy_check.hip: sigma words -> cell numbers with the decoding table of that file (d_table); the one-pass check of a setup's
+// sigma columns against the variables (both [num_vars][n] at stride n) and its second pass for a sigma that is no permutation
+void launch_sigma_cells(const u64 *d_sigmas, size_t sig_stride, unsigned num_vars, unsigned log_n, const u64 *d_table, uint32_t *d_cells,
+                        size_t cell_stride, u64 *d_ctr, hipStream_t s);
+void launch_copy_check(const u64 *d_sigmas, const u64 *d_vars, unsigned num_vars, unsigned log_n, const u64 *d_table, uint32_t *d_seen,
+                       uint32_t *d_multi, u64 *d_ctr, hipStream_t s);
+void launch_copy_shared_target(const u64 *d_sigmas, unsigned num_vars, unsigned log_n, const u64 *d_table, const uint32_t *d_multi, u64 *d_ctr,
+                               hipStream_t s);
 }  // namespace bj

@@ -45,7 +45,8 @@ typedef struct bj_ctx bj_ctx;
 /* 2: bj_gate_desc.wit_stride, bj_comm.all_gather_stream (round 2); 3: op lists in any numbering, run-time compiled gates;
  * 4: bj_proof_config.pow_runner, bj_circuit.table_id_col = BJ_TABLE_ID_AS_VARIABLE (round 5); 5: bj_comm_replay_capture,
  * bj_proof_workspace_bytes, bj_setup_device_bytes; 6: bj_prove_async / bj_proof_wait, the tiled-monomial operators, bj_comm_peer_create (round 6);
- * entry points added within version 6 (no layout of an existing struct changes with them): bj_check_satisfied, bj_lookup_multiplicities, bj_vk_* / bj_verify */
+ * entry points added within version 6 (no layout of an existing struct changes with them): bj_check_satisfied, bj_lookup_multiplicities, bj_vk_* / bj_verify,
+ * bj_sigma_cells, bj_check_copy_constraints */
 #define BJ_ABI_VERSION 6
 int bj_abi_version(void);
 /* 1 if bj_setup_create accepts bj_gate_desc.kind == kind, else 0: gate kinds are added within an ABI version (no layout
@@ -724,8 +725,8 @@ int bj_setup_lookup_multiplicities(bj_ctx *ctx, const bj_setup *setup, const uin
  * a non-zero term is missed with probability at most 1/p^2 (< 2^-127) for independent weights; the weights are fixed, so a
  * witness built against them is not covered: this is a diagnosis, not a proof.  What is REPORTED is exact: the named row is
  * evaluated again term by term with unit weights, and the lookup part involves no randomness.
- * NOT checked: copy constraints.  They hold by construction for a witness gathered through a placement (bj_*_from_dumps), the
- * reference's checker does not test them either, and raw columns that break them keep bj_prove's refusal.
+ * NOT checked: copy constraints.  They hold by construction for a witness gathered through a placement (bj_*_from_dumps) and the
+ * reference's checker does not test them either; for raw columns bj_check_copy_constraints below names the cells that break them.
  * Arguments as for bj_prove_dev / bj_prove_from_dumps (values canonical or not; d_multiplicities NULL only without lookups);
  * nothing is modified.  Runs on the context's stream, in the context's scratch, and synchronises; a proof made afterwards is
  * byte for byte the proof made before.  Works on a sharded setup (replicated columns only, no communication).  Not while a
@@ -752,6 +753,54 @@ int bj_check_satisfied(bj_ctx *ctx, const bj_setup *setup, const uint64_t *d_var
 int bj_check_satisfied_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_vec, size_t witness_vec_len,
                                   const void *variables_hint, size_t variables_hint_len, const void *witness_hint,
                                   size_t witness_hint_len, bj_unsat_report *out);
+
+/* ---- which cells break a copy constraint: the copy-permutation argument (src/cs/implementations/copy_permutation.rs) cell by cell ----
+ * Raw columns handed to bj_prove / bj_prove_dev / bj_prove_async can satisfy every gate (bj_check_satisfied says BJ_SAT) and
+ * still be refused after the quotient stage: two cells of one variable hold different values, sigma was taken from another
+ * circuit, or sigma is no permutation.  These two calls name the cells.
+ *
+ * bj_sigma_cells is the inverse of bj_sigmas_from_placement (create_permutation_polys, src/cs/implementations/setup.rs:419-503),
+ * with that call's arguments: d_cells[c * cell_stride + row] = j * n + r where sigma[c][row] = h_non_residues[j] * omega^r (mod p),
+ * omega the 2^log_n domain generator of the transforms; 0xFFFFFFFF where the value lies in no coset h_non_residues[j] * H (0 is
+ * such a value).  Input words may be any u64.  *num_invalid counts the 0xFFFFFFFF cells, *first_invalid is the smallest key
+ * row * num_vars + column among them, UINT64_MAX when all are valid.  A discrete logarithm per cell: sigma^n selects the column
+ * (binary search among the k_j^n), Pohlig-Hellman in the 2-power subgroup gives the row (era_boojum_amd/csrc/copy_check.hip).
+ * Limits, BJ_ERR_UNSUPPORTED with a message: log_n <= 30, num_vars * n < 2^32, num_vars <= 4096.  BJ_ERR_INVALID_ARG: a null
+ * pointer, a stride below n, a non-residue that is 0, two non-residues with k_i^n = k_j^n (they name the same coset).  Every refusal
+ * happens before anything is launched or read.  Runs on the context's stream, in the context's scratch, and synchronises; no input
+ * is written.  Not while a proof runs on the context. */
+int bj_sigma_cells(bj_ctx *ctx, const uint64_t *d_sigmas, size_t sig_stride, unsigned num_vars, unsigned log_n,
+                   const uint64_t *h_non_residues, uint32_t *d_cells, size_t cell_stride, uint64_t *first_invalid,
+                   uint64_t *num_invalid);
+/* bj_check_copy_constraints: the sigma columns of a setup (its replicated natural-order columns) against the first num_vars
+ * columns of d_variables (the pointer bj_prove_dev takes; witness columns and multiplicities play no part).  Categories, in the
+ * order in which `kind` reports them; in each the named cell is the one with the smallest key row * num_vars + column (ascending
+ * row, as bj_check_satisfied orders its findings):
+ *   1. BJ_COPY_SIGMA_INVALID: a sigma value names no cell.  partner_* are 0.
+ *   2. BJ_COPY_SIGMA_NOT_PERMUTATION: a cell is named by more than one sigma entry.  failures[2] = entries minus distinct named
+ *      cells (entries of category 1 aside); the named cell is the smallest among the entries whose target another entry names too,
+ *      partner_* that target.
+ *   3. BJ_COPY_VALUE_MISMATCH: the canonical values of a cell and of the cell its sigma names differ.  failures[3] counts such
+ *      cells; value / partner_value are the two values.
+ * Decoding and comparing are one pass; category 2 costs a second pass over sigma only when it occurs.  Contract as for
+ * bj_check_satisfied: BJ_OK whenever the check ran, the verdict in *out; a negative status for null arguments, a setup on another
+ * device, a proof running on the context, or the limits of bj_sigma_cells.  Nothing is modified: a proof made afterwards is byte
+ * for byte the proof made before.  Works on a sharded setup (replicated columns only, no communication). */
+typedef enum bj_copy_kind {
+    BJ_COPY_OK = 0,
+    BJ_COPY_SIGMA_INVALID = 1,
+    BJ_COPY_SIGMA_NOT_PERMUTATION = 2,
+    BJ_COPY_VALUE_MISMATCH = 3
+} bj_copy_kind;
+typedef struct bj_copy_report {
+    uint32_t kind;                 /* first category with a failure, in the order above */
+    uint32_t column, partner_column;
+    uint64_t row, partner_row;     /* the named cell, and the cell its sigma names */
+    uint64_t value, partner_value; /* kind 3: the two canonical values; else 0 */
+    uint32_t variable;             /* kind 3, setups made by bj_setup_create_from_placement: the placement's index of the named cell; else 0xFFFFFFFF */
+    uint64_t failures[4];          /* per kind, filled for all three whatever `kind` is; [0] unused */
+} bj_copy_report;
+int bj_check_copy_constraints(bj_ctx *ctx, const bj_setup *setup, const uint64_t *d_variables, bj_copy_report *out);
 
 /* ---- is this a proof under my key: Verifier::verify (src/cs/implementations/verifier.rs:888-2524) and verify_circuit
  * (src/cs/implementations/convenience.rs:198) ----

@@ -240,6 +240,19 @@ pub fn verify_hip(ctx: &HipCtx, vk: &HipVk, words: &[u64], partial_queries: bool
     report
 }
 
+/// Which cells break a copy constraint: the claim of the copy-permutation argument (copy_permutation.rs) over the sigma columns
+/// `create_permutation_polys` (setup.rs:419-503) made, tested cell by cell on the device — for raw columns that satisfy every gate
+/// (`check_satisfied_hip` says `BJ_SAT`) and are still refused by `prove_hip`.  `d_variables`: the device pointer `bj_prove_dev`
+/// takes; only the copiable columns are read.  `report.kind == BJ_COPY_OK as u32` when sigma is a permutation of the cells and
+/// every cell holds the value of the cell its sigma names; the categories and their order are documented in include/boojum_hip.h.
+pub fn check_copy_constraints_hip(ctx: &HipCtx, setup: &HipSetup, d_variables: *const u64) -> bj_copy_report {
+    let mut report = bj_copy_report {
+        kind: 0, column: 0, partner_column: 0, row: 0, partner_row: 0, value: 0, partner_value: 0, variable: 0, failures: [0; 4],
+    };
+    ctx.check(unsafe { bj_check_copy_constraints(ctx.raw, setup.raw, d_variables, &mut report) });
+    report
+}
+
 impl<P: crate::field::traits::field_like::PrimeFieldLikeVectorized<Base = F>, CFG: CSConfig, A: GoodAllocator>
     CSReferenceAssembly<F, P, CFG, A>
 {
@@ -469,7 +482,8 @@ impl<P: crate::field::traits::field_like::PrimeFieldLikeVectorized<Base = F>, CF
     /// `check_if_satisfied` (satisfiability_test.rs:15-353) on the device, for a witness `prove_hip` would refuse or — a wrong
     /// lookup or multiplicity — would not notice: uploads the witness, runs `bj_check_satisfied` and returns its report
     /// (`kind == BJ_SAT as u32` when every gate term vanishes and both sides of the lookup argument agree).  The order that
-    /// defines the first failure and what is not covered (copy constraints) are documented in include/boojum_hip.h.
+    /// defines the first failure and what is not covered (copy constraints: `check_copy_constraints_hip`) are documented in
+    /// include/boojum_hip.h.
     pub fn check_satisfied_hip(&self, ctx: &HipCtx, setup: &HipSetup, witness_set: &WitnessSet<F>) -> bj_unsat_report {
         assert_eq!(witness_set.variables.len(), setup.num_vars);
         let vars = flatten(witness_set.variables.iter().chain(witness_set.witness.iter()).map(|p| &p.storage[..]), setup.n);
