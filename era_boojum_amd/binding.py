@@ -135,6 +135,8 @@ _SIGNATURES = {
     "bj_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p]),
     "bj_verify_proof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bj_verify_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "bj_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_uint, C.c_void_p]),
+    "bj_verify_batch_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "bj_proof_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bj_proof_workspace_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "bj_proof_kernel_stats": (C.c_int, [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1104,6 +1106,23 @@ class Verifier:
         r = _VerifyReport()
         ctx._check(self._lib.bj_verify(ctx._h, self._h, _np_ptr(a), n, VERIFY_PARTIAL_QUERIES if partial else 0, C.byref(r)))
         return VerifyReport(int(r.stage), int(r.query), int(r.oracle), int(r.queries_checked))
+
+    def verify_batch(self, ctx, proofs, partial_queries=False):
+        """bj_verify_batch: the proofs of `proofs` (serialised words each; None or an empty buffer is a proof of no words) under this
+        key in one call; a list with the VerifyReport bj_verify would give each of them."""
+        bufs = [np.zeros(0, dtype=np.uint64) if p is None else np.ascontiguousarray(p, dtype=np.uint64).reshape(-1) for p in proofs]
+        n = len(bufs)
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        sizes = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        reports = (_VerifyReport * max(n, 1))()
+        ctx._check(self._lib.bj_verify_batch(ctx._h, self._h, ptrs, sizes, n, VERIFY_PARTIAL_QUERIES if partial_queries else 0, reports))
+        return [VerifyReport(int(r.stage), int(r.query), int(r.oracle), int(r.queries_checked)) for r in reports[:n]]
+
+    def batch_ms(self, ctx):
+        """Of the last verify_batch on ctx: (host wall ms, upload ms, openings kernel ms, DEEP + FRI kernel ms)."""
+        v = [C.c_float() for _ in range(4)]
+        ctx._check(self._lib.bj_verify_batch_ms(ctx._h, *[C.byref(x) for x in v]))
+        return tuple(float(x.value) for x in v)
 
     def kernel_ms(self, ctx):
         """HIP-event durations (openings, DEEP + FRI) of the two kernels of the last verify on ctx."""

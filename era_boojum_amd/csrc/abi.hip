@@ -207,6 +207,10 @@ void load_env() {
         e.prove_h2d_group = v ? v : 8u;
     }
     if (set("BJ_NODES_LANEPAR_MAX")) e.nodes_lanepar_max = (size_t)strtoull(getenv("BJ_NODES_LANEPAR_MAX"), nullptr, 10);
+    if (set("BJ_VERIFY_THREADS")) {
+        const long v = strtol(getenv("BJ_VERIFY_THREADS"), nullptr, 10);
+        e.verify_threads = v < 1 ? 1u : v > 16 ? 16u : (unsigned)v;
+    }
     e.jit_cache_dir = str("BJ_GATE_JIT_CACHE");
     e.rccl_lib = str("BJ_RCCL_LIB");
     g_env = e;
@@ -299,6 +303,8 @@ void bj_ctx_destroy(bj_ctx *ctx) {
     for (auto &sl : ctx->arena_slabs) (void)hipFree(sl.first);
     if (ctx->h_ring) (void)hipHostFree(ctx->h_ring);
     for (auto &e : ctx->verify_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : ctx->verify_batch_ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

@@ -241,8 +241,13 @@ static void launch_blake2s_nodes(const u64 *d_children, u64 *d_parents, size_t n
 static void launch_blake2s_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
     hipLaunchKernelGGL(blake2s_verify_openings_kernel, dim3((A.n_queries + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
 }
+// bj_verify_batch: the chains of every proof of a batch, chain -> (proof, query) through the record table (verify_open.h)
+__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) blake2s_verify_openings_batch_kernel(VerifyOpenBatchArgs A) { verify_open_bytes_batch<B2sVerifyHasher>(A); }
+static void launch_blake2s_verify_openings_batch(const VerifyOpenBatchArgs &A, hipStream_t s) {
+    hipLaunchKernelGGL(blake2s_verify_openings_batch_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
+}
 TreeHasher blake2s_tree_hasher() {
-    return {launch_blake2s_leaves, launch_blake2s_leaves_chunked, launch_blake2s_nodes, nullptr, launch_blake2s_verify_openings};
+    return {launch_blake2s_leaves, launch_blake2s_leaves_chunked, launch_blake2s_nodes, nullptr, launch_blake2s_verify_openings, launch_blake2s_verify_openings_batch};
 }
 
 }  // namespace bj

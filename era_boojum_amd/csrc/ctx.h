@@ -73,6 +73,10 @@ struct bj_ctx {
     // bj_verify: events around its two kernels (created on first use), read by bj_verify_kernel_ms
     hipEvent_t verify_ev[4] = {};
     bool verify_timed = false;      // the last bj_verify on this context launched its kernels
+    // bj_verify_batch: events before / after its uploads and after each of its two kernels, read by bj_verify_batch_ms
+    hipEvent_t verify_batch_ev[4] = {};
+    float verify_batch_host_ms = 0;   // wall time of the host phase of the last batch
+    int verify_batch_state = 0;       // the last batch: 0 none (or refused), 1 ended in its host phase, 2 launched its kernels
 };
 
 namespace bj {

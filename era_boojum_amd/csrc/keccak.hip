@@ -225,8 +225,13 @@ static void launch_keccak_nodes(const u64 *d_children, u64 *d_parents, size_t nu
 static void launch_keccak_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
     hipLaunchKernelGGL(keccak_verify_openings_kernel, dim3((A.n_queries + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
 }
+// bj_verify_batch: the chains of every proof of a batch, chain -> (proof, query) through the record table (verify_open.h)
+__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) keccak_verify_openings_batch_kernel(VerifyOpenBatchArgs A) { verify_open_bytes_batch<KeccakVerifyHasher>(A); }
+static void launch_keccak_verify_openings_batch(const VerifyOpenBatchArgs &A, hipStream_t s) {
+    hipLaunchKernelGGL(keccak_verify_openings_batch_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
+}
 TreeHasher keccak_tree_hasher() {
-    return {launch_keccak_leaves, launch_keccak_leaves_chunked, launch_keccak_nodes, nullptr, launch_keccak_verify_openings};
+    return {launch_keccak_leaves, launch_keccak_leaves_chunked, launch_keccak_nodes, nullptr, launch_keccak_verify_openings, launch_keccak_verify_openings_batch};
 }
 
 }  // namespace bj

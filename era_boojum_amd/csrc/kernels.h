@@ -27,6 +27,7 @@ struct EnvConfig {
     bool peer_debug = false;             // BJ_PEER_DEBUG: the peer transport traces its bulk exchanges on stderr
     int peer_test_fail_rank = -1;        // BJ_PEER_TEST_FAIL_RANK: test hook, this rank of the peer transport pretends it could not export its mailbox
     unsigned prove_h2d_group = 8;
+    unsigned verify_threads = 8;         // BJ_VERIFY_THREADS (1..16): host threads of bj_verify_batch; never sized by the machine's core count
     size_t nodes_lanepar_max = 16384;
     std::string jit_cache_dir, rccl_lib;
 };

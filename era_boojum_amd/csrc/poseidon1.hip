@@ -133,6 +133,11 @@ __global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) poseidon1_verify_openings_k
 static void launch_poseidon1_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
     hipLaunchKernelGGL(poseidon1_verify_openings_kernel, dim3((A.n_queries + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
 }
+// bj_verify_batch: the chains of every proof of a batch, chain -> (proof, query) through the record table (verify_open.h)
+__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) poseidon1_verify_openings_batch_kernel(VerifyOpenBatchArgs A) { verify_open_sponge_batch<poseidon1_permutation>(A); }
+static void launch_poseidon1_verify_openings_batch(const VerifyOpenBatchArgs &A, hipStream_t s) {
+    hipLaunchKernelGGL(poseidon1_verify_openings_batch_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
+}
 __global__ void poseidon1_permute_states_kernel(u64 *states, size_t n_states) { sponge_permute_states<poseidon1_permutation>(states, n_states); }
 
 static void launch_poseidon1_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
@@ -153,7 +158,7 @@ static void launch_poseidon1_leaves_absorb(const u64 *d_base, size_t col_stride,
 }
 TreeHasher poseidon1_tree_hasher() {
     return {launch_poseidon1_leaves, launch_poseidon1_leaves_chunked, launch_poseidon1_nodes, launch_poseidon1_leaves_absorb,
-            launch_poseidon1_verify_openings};
+            launch_poseidon1_verify_openings, launch_poseidon1_verify_openings_batch};
 }
 
 void launch_poseidon1_permute_states(u64 *d_states, size_t n_states, hipStream_t s) {

@@ -25,7 +25,8 @@ inline void launch_1d(void (*kernel)(Params...), size_t n, hipStream_t s, Args..
     hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, args...);
 }
 
-struct VerifyOpenArgs;   // verify_open.h
+struct VerifyOpenArgs;        // verify_open.h
+struct VerifyOpenBatchArgs;
 
 // a hasher's launchers, one table entry of tree_hash.hip
 struct TreeHasher {
@@ -40,6 +41,8 @@ struct TreeHasher {
                           bool first, bool last, hipStream_t s);
     // bj_verify: the (query, oracle) Merkle chains of a proof's query section (verify_open.h)
     void (*verify_openings)(const VerifyOpenArgs &args, hipStream_t s);
+    // bj_verify_batch: the same chains for every proof of a batch in one launch
+    void (*verify_openings_batch)(const VerifyOpenBatchArgs &args, hipStream_t s);
 };
 TreeHasher poseidon2_tree_hasher(), blake2s_tree_hasher(), keccak_tree_hasher(), poseidon1_tree_hasher();
 

@@ -9,6 +9,10 @@
 // hasher) walks every Merkle chain; verify_deep_fri_kernel here, one wave per query, simulates the DEEP value from the four
 // opened leaves (:2233-2290), folds it through the schedule (:2387-2519) and compares with the final monomials at the point.
 // Both write one status word per chain / query; the host reduces them to the report (include/boojum_hip.h has the order).
+//
+// The host half is prepare() — everything up to the tables the kernels read, no context in it, so bj_verify_batch runs it for N
+// proofs on worker threads — and a judge: bj_verify's over one proof, bj_verify_batch's over every proof of the batch that got as
+// far, in one launch of each kernel (verify_batch_plan.h lays the batch out in the context's scratch).
 #include "ctx.h"
 #include "gate_program.h"
 #include "host_transcript.hpp"
@@ -16,7 +20,12 @@
 #include "setup.h"
 #include "verify_open.h"
 
+#include <atomic>
+#include <chrono>
+#include <cstdarg>
 #include <cstring>
+#include <string>
+#include <thread>
 #include <vector>
 
 using gl::e2;
@@ -24,6 +33,7 @@ using gl::u64;
 
 namespace bj {
 void launch_verify_openings(int hasher, const VerifyOpenArgs &args, hipStream_t s);   // tree_hash.hip
+void launch_verify_openings_batch(int hasher, const VerifyOpenBatchArgs &args, hipStream_t s);
 }
 
 namespace bj {
@@ -235,18 +245,29 @@ void poseidon1_flattened_terms(const e2 *var, e2 *terms) {   // src/cs/gates/pos
 constexpr uint32_t NO_C1 = 0xFFFFFFFFu;        // a term whose source is a base-field column
 constexpr uint32_t DEEP_FINAL = 0x10000u;      // status: 0 ok, 1 + l = the value carried into layer l is not in its leaf, DEEP_FINAL
 
+struct VerifyDeepShared {   // what the key fixes: the same for every proof of a batch
+    const u64 *roots;     // inverse bit-reversed twiddles of the 2^log_full domain
+    uint32_t query_words, n_sets, n_fri, final_degree, log_full, total_folds;
+    u64 omega, kappa;     // generator of the 2^log_full domain; 1 / 7
+    uint32_t fri_off[32];
+    unsigned char sched[32];
+};
 struct VerifyDeepArgs {
     const u64 *queries, *indices;
     const u64 *terms;     // [n_terms][3]: leaf word of c0 | leaf word of c1 << 32 (NO_C1: base field), challenge power (c0, c1)
     const u64 *sets;      // [n_sets][6]: first term, end term, the point (c0, c1), sum_k ch_k * value_k (c0, c1)
     const u64 *fri_ch;    // [n_fri][2]
     const u64 *final0, *final1;   // final monomials
-    const u64 *roots;     // inverse bit-reversed twiddles of the 2^log_full domain
     uint32_t *status;     // [n_queries]
-    uint32_t n_queries, query_words, n_sets, n_fri, final_degree, log_full, total_folds;
-    u64 omega, kappa;     // generator of the 2^log_full domain; 1 / 7
-    uint32_t fri_off[32];
-    unsigned char sched[32];
+    uint32_t n_queries;
+    VerifyDeepShared sh;
+};
+struct VerifyDeepBatchArgs {   // bj_verify_batch: the per-proof pointers come out of the record table (verify_batch_plan.h)
+    const u64 *base;
+    const bj::VerifyBatchProof *proofs;
+    uint32_t *status;     // [n_chains]
+    uint32_t n_proofs, n_chains;
+    VerifyDeepShared sh;
 };
 
 __device__ __forceinline__ u64 shfl64(u64 v, unsigned src) { return (u64)__shfl((unsigned long long)v, (int)src); }
@@ -260,20 +281,18 @@ __device__ __forceinline__ e2 wave_sum(e2 v) {
     return v;
 }
 
-__global__ void __launch_bounds__(64) verify_deep_fri_kernel(VerifyDeepArgs A) {
-    const unsigned c = blockIdx.x, lane = threadIdx.x;
-    if (c >= A.n_queries) return;
-    const u64 *Q = A.queries + (size_t)c * A.query_words;
-    const u64 idx = A.indices[c];
+// the status word of one query (DEEP_FINAL above); the whole wave calls it and every lane returns the same word
+__device__ __forceinline__ uint32_t deep_fri_status(const VerifyDeepShared &A, const u64 *Q, u64 idx, const u64 *terms, const u64 *sets,
+                                                    const u64 *fri_ch, const u64 *final0, const u64 *final1, unsigned lane) {
     const u64 x = gl::mul(gl::GEN, gl::pow(A.omega, (u64)gl::bitrev32((gl::u32)idx, A.log_full)));   // x_I = g * w^bitrev(I)
     // h = sum over the opening sets of [ sum_k ch_k f_k(x) - sum_k ch_k v_k ] / (x - at): source order of verifier.rs:2233-2290, one
     // inversion per set; the sources of a set are spread over the lanes
     e2 h{0, 0};
     for (unsigned s = 0; s < A.n_sets; s++) {
-        const u64 *S = A.sets + 6 * (size_t)s;
+        const u64 *S = sets + 6 * (size_t)s;
         e2 acc{0, 0};
         for (u64 t = S[0] + lane; t < S[1]; t += 64) {
-            const u64 *T = A.terms + 3 * t;
+            const u64 *T = terms + 3 * t;
             const uint32_t o0 = (uint32_t)T[0], o1 = (uint32_t)(T[0] >> 32);
             const e2 ch{T[1], T[2]};
             const u64 a = gl::canon(Q[o0]);
@@ -297,7 +316,7 @@ __global__ void __launch_bounds__(64) verify_deep_fri_kernel(VerifyDeepArgs A) {
         if (lane < m) v = e2{gl::canon(L[lane]), gl::canon(L[m + lane])};
         const e2 carried = shfl2(v, sub);
         if (!status && (carried.c0 != cur.c0 || carried.c1 != cur.c1)) status = 1 + l;
-        e2 chal{A.fri_ch[2 * l], A.fri_ch[2 * l + 1]};
+        e2 chal{fri_ch[2 * l], fri_ch[2 * l + 1]};
         for (unsigned f = 0; f < k; f++) {
             const unsigned outs = m >> (f + 1);
             const e2 a = shfl2(v, (2 * lane) & 63), b = shfl2(v, (2 * lane + 1) & 63);
@@ -314,9 +333,30 @@ __global__ void __launch_bounds__(64) verify_deep_fri_kernel(VerifyDeepArgs A) {
     u64 xx = x;
     for (unsigned i = 0; i < A.total_folds; i++) xx = gl::sqr(xx);
     e2 acc{0, 0};
-    for (unsigned j = A.final_degree; j-- > 0;) acc = gl::e2_add(gl::e2_mul_base(acc, xx), e2{A.final0[j], A.final1[j]});
+    for (unsigned j = A.final_degree; j-- > 0;) acc = gl::e2_add(gl::e2_mul_base(acc, xx), e2{final0[j], final1[j]});
     if (!status && (acc.c0 != cur.c0 || acc.c1 != cur.c1)) status = DEEP_FINAL;
+    return status;
+}
+
+__global__ void __launch_bounds__(64) verify_deep_fri_kernel(VerifyDeepArgs A) {
+    const unsigned c = blockIdx.x, lane = threadIdx.x;
+    if (c >= A.n_queries) return;
+    const uint32_t status = deep_fri_status(A.sh, A.queries + (size_t)c * A.sh.query_words, A.indices[c], A.terms, A.sets, A.fri_ch, A.final0,
+                                            A.final1, lane);
     if (lane == 0) A.status[c] = status;
+}
+
+// bj_verify_batch: one wave per (proof, query) of the whole batch; the search is over a wave-uniform chain, so it is scalar
+__global__ void __launch_bounds__(64) verify_deep_fri_batch_kernel(VerifyDeepBatchArgs A) {
+    const unsigned g = blockIdx.x, lane = threadIdx.x;
+    if (g >= A.n_chains) return;
+    const bj::VerifyBatchProof P = A.proofs[bj::verify_batch_proof_of(A.proofs, A.n_proofs, g)];
+    const unsigned c = g - P.chain0;
+    if (c >= P.nq) return;
+    const u64 *B = A.base;
+    const uint32_t status = deep_fri_status(A.sh, B + P.queries + (size_t)c * A.sh.query_words, B[P.indices + c], B + P.terms, B + P.sets,
+                                            B + P.fri_ch, B + P.final0, B + P.final1, lane);
+    if (lane == 0) A.status[g] = status;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -354,13 +394,41 @@ bool pow_holds(unsigned runner, const u64 *seed5, unsigned bits, u64 nonce) {   
     return tz >= bits;
 }
 
-int verify_impl(bj_ctx *ctx, const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, bj_verify_report *out) {
-    if (int rc = bj::bind(ctx)) return rc;
-    if (!K || !W || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: null argument");
-    if (flags & ~BJ_VERIFY_PARTIAL_QUERIES) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: unknown flags %#x", flags);
-    if (ctx->in_proof) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: a proof is running on this context");
-    std::memset(out, 0, sizeof(*out));
-    ctx->verify_timed = false;
+// What the key fixes about the device work, as prepare() works it out: the same in every proof of a batch.
+struct Geometry {
+    bj::VerifyBatchGeometry sizes;
+    unsigned LOGN = 0, n_sets = 0, n_fri = 0, total_folds = 0;
+    bj::VerifyOracle oracle[bj::VERIFY_MAX_ORACLES] = {};
+    uint32_t fri_off[32] = {};
+    unsigned char sched[32] = {};
+};
+// A proof after the host half.  device == false: `report` is the verdict (or rc < 0 and err say why there is none).  device ==
+// true: the host checks passed; the tables (verify_batch_plan.h: verify_tables) and the query section wait for a judge.
+struct Prepared {
+    int rc = BJ_OK;
+    std::string err;
+    bj_verify_report report = {};
+    bool device = false;
+    size_t nq = 0;
+    int first_mismatch = -1;       // first query whose stored index is not the drawn one
+    const u64 *queries = nullptr;  // the query section, inside the caller's buffer
+    std::vector<u64> tables;
+    Geometry geo;
+    int refuse(int code, const char *fmt, ...) {
+        char buf[256];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof buf, fmt, ap);
+        va_end(ap);
+        err = buf;
+        return rc = code;
+    }
+};
+
+// The host half: shape, transcript replay, lookup sum, quotient identity, proof of work, indices, DEEP tables.  Touches no context
+// and no global state: bj_verify_batch runs it on several threads at once.  Returns R->rc.
+int prepare(const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, Prepared *R) {
+    bj_verify_report *out = &R->report;
 
     // ---- shape: every count is the key's before it sizes anything ----
     const unsigned log_n = K->log_n, V = K->V, Wc = K->Wc, nC = K->nC, q = K->q, log_fri = K->log_fri, LOGN = log_n + log_fri;
@@ -375,10 +443,10 @@ int verify_impl(bj_ctx *ctx, const bj_vk *K, const u64 *W, size_t n_words, unsig
     uint32_t sched[32], new_pow = 0;
     size_t num_queries = 0, sched_len = 0, final_degree = 0;
     if (bj_fri_schedule(K->security, cap, K->pow_bits, log_fri, log_n, &new_pow, &num_queries, sched, &sched_len, &final_degree) || sched_len > 32)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: compute_fri_schedule failed for the key's config");
+        return R->refuse(BJ_ERR_INVALID_ARG, "bj_verify: compute_fri_schedule failed for the key's config");
     if (N < cap || LOGN > 32) return verdict(out, BJ_VERIFY_SHAPE);
     const unsigned depth = bj::log2_exact(N / cap);
-    if (n_words < 19 || W[0] != 0x424A5046ULL || W[1] != 2) return verdict(out, BJ_VERIFY_SHAPE);
+    if (!W || n_words < 19 || W[0] != 0x424A5046ULL || W[1] != 2) return verdict(out, BJ_VERIFY_SHAPE);
     const size_t n_pub = K->pub_cols.size();
     const u64 nq64 = W[9];
     const bool partial = (flags & BJ_VERIFY_PARTIAL_QUERIES) != 0;
@@ -612,7 +680,7 @@ int verify_impl(bj_ctx *ctx, const bj_vk *K, const u64 *W, size_t n_words, unsig
         base_run(oSU + V + nC, K->lookup_w + 1);
     }
     ext_run(oQ, q);
-    if (src.size() != nz) return bj::fail(ctx, BJ_ERR_HIP, "bj_verify: internal error: %zu DEEP sources for %zu openings", src.size(), nz);
+    if (src.size() != nz) return R->refuse(BJ_ERR_HIP, "bj_verify: internal error: %zu DEEP sources for %zu openings", src.size(), nz);
     struct PubSet { u64 at; std::vector<uint32_t> cols; std::vector<u64> vals; };
     std::vector<PubSet> pubs;
     {
@@ -665,79 +733,158 @@ int verify_impl(bj_ctx *ctx, const bj_vk *K, const u64 *W, size_t n_words, unsig
         }
     }
 
-    // ---- device: the query section once, the small tables behind it ----
+    // ---- what a judge needs: the geometry, and the tables in the block layout of verify_tables ----
     const size_t n_oracles = 4 + sched_len, cap_words = cap * 4;
+    Geometry &G = R->geo;
+    G.sizes.query_words = query_words;
+    G.sizes.n_oracles = n_oracles;
+    G.sizes.cap_words = cap_words;
+    G.sizes.term_words = term_words.size();
+    G.sizes.set_words = set_words.size();
+    G.sizes.fri_words = fri_ch.size();
+    G.sizes.final_degree = final_degree;
+    G.LOGN = LOGN;
+    G.n_sets = (unsigned)n_sets;
+    G.n_fri = (unsigned)sched_len;
+    G.total_folds = total_folds;
+    for (int o = 0; o < 4; o++) G.oracle[o] = bj::VerifyOracle{leaf_off[o], widths[o], depth, 0, (uint32_t)(o * cap_words)};
+    {
+        uint32_t o = leaf_off[3] + widths[3] + depth * 4, shift = 0;
+        for (size_t l = 0; l < sched_len; l++) {
+            shift += sched[l];
+            G.oracle[4 + l] = bj::VerifyOracle{o, 2u << sched[l], fri_depth[l], shift, (uint32_t)((4 + l) * cap_words)};
+            G.fri_off[l] = o;
+            G.sched[l] = (unsigned char)sched[l];
+            o += (2u << sched[l]) + fri_depth[l] * 4;
+        }
+    }
+    const bj::VerifyTables at = bj::verify_tables(G.sizes, nq);
+    R->tables.assign(at.words, 0);
+    u64 *s = R->tables.data();
+    std::memcpy(s + at.idx, indices.data(), indices.size() * 8);
+    std::memcpy(s + at.caps, wit_cap, cap_words * 8);
+    std::memcpy(s + at.caps + cap_words, s2_cap, cap_words * 8);
+    std::memcpy(s + at.caps + 2 * cap_words, q_cap, cap_words * 8);
+    std::memcpy(s + at.caps + 3 * cap_words, K->cap.data(), cap_words * 8);
+    std::memcpy(s + at.caps + 4 * cap_words, fri_caps, sched_len * cap_words * 8);
+    std::memcpy(s + at.terms, term_words.data(), term_words.size() * 8);
+    std::memcpy(s + at.sets, set_words.data(), set_words.size() * 8);
+    std::memcpy(s + at.fri_ch, fri_ch.data(), fri_ch.size() * 8);
+    for (size_t i = 0; i < final_degree; i++) {
+        s[at.fm + i] = gl::canon(fm0[i]);
+        s[at.fm + final_degree + i] = gl::canon(fm1[i]);
+    }
+    R->nq = nq;
+    R->first_mismatch = first_mismatch;
+    R->queries = queries;
+    R->device = true;
+    return BJ_OK;
+}
+
+VerifyDeepShared deep_shared(const bj_ctx *ctx, const Geometry &G) {
+    VerifyDeepShared sh{};
+    sh.roots = ctx->tw_inv;
+    sh.query_words = (uint32_t)G.sizes.query_words;
+    sh.n_sets = G.n_sets;
+    sh.n_fri = G.n_fri;
+    sh.final_degree = (uint32_t)G.sizes.final_degree;
+    sh.log_full = G.LOGN;
+    sh.total_folds = G.total_folds;
+    sh.omega = gl::omega(G.LOGN);
+    sh.kappa = gl::inv(gl::GEN);
+    std::memcpy(sh.fri_off, G.fri_off, sizeof sh.fri_off);
+    std::memcpy(sh.sched, G.sched, sizeof sh.sched);
+    return sh;
+}
+
+// the first failure of one proof in the order of include/boojum_hip.h; st_open is [n_oracles][stride] from this proof's first
+// chain on, st_deep [nq]
+Failure first_failure(const uint32_t *st_open, size_t stride, const uint32_t *st_deep, size_t nq, size_t n_fri) {
+    for (size_t i = 0; i < nq; i++) {
+        for (uint32_t o = 0; o < 4; o++)
+            if (!st_open[o * stride + i]) return Failure{BJ_VERIFY_MERKLE, (uint32_t)i, o};
+        for (uint32_t l = 0; l < n_fri; l++) {
+            if (st_deep[i] == 1 + l) return Failure{BJ_VERIFY_FRI_VALUE, (uint32_t)i, l};
+            if (!st_open[(4 + l) * stride + i]) return Failure{BJ_VERIFY_FRI_MERKLE, (uint32_t)i, l};
+        }
+        if (st_deep[i]) return Failure{BJ_VERIFY_FINAL, (uint32_t)i, 0};
+    }
+    return Failure{};
+}
+
+// The verdict over a proof that reached its kernels.  at_drawn: its first failure at the drawn indices.  Returns true when the
+// verdict needs the first failure at the stored indices, too (second == nullptr), and uses it when given.
+// The stored indices are not the drawn ones and the drawn ones fail: what do the openings the proof carries fail at?  This second
+// pass exists for two rows of the stage table alone and never turns a rejection into an acceptance: a final monomial and a FRI
+// cap are absorbed BEFORE the indices are drawn, so editing either moves every index — at the drawn indices such a proof fails
+// at the witness path of query 0, whatever was edited; BJ_VERIFY_FINAL for the monomial and BJ_VERIFY_FRI_VALUE for a FRI leaf
+// whose path (and therefore cap entry) was recomputed can only be told at the indices the prover opened.
+bool device_verdict(bj_verify_report *out, size_t nq, int first_mismatch, const Failure &at_drawn, const Failure *at_stored) {
+    if (at_drawn.stage == BJ_VERIFY_OK) {
+        if (first_mismatch < 0) verdict(out, BJ_VERIFY_OK, 0, 0, (uint32_t)nq);
+        else verdict(out, BJ_VERIFY_SHAPE, (uint32_t)first_mismatch, 0, (uint32_t)first_mismatch);
+        return false;
+    }
+    if (first_mismatch < 0) {
+        verdict(out, at_drawn.stage, at_drawn.query, at_drawn.oracle, at_drawn.query);
+        return false;
+    }
+    if (!at_stored) return true;
+    if (at_stored->stage == BJ_VERIFY_OK) verdict(out, BJ_VERIFY_SHAPE, (uint32_t)first_mismatch, 0, (uint32_t)first_mismatch);
+    else verdict(out, at_stored->stage, at_stored->query, at_stored->oracle, at_stored->query);
+    return false;
+}
+
+int verify_impl(bj_ctx *ctx, const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, bj_verify_report *out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!K || !W || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: null argument");
+    if (flags & ~BJ_VERIFY_PARTIAL_QUERIES) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: unknown flags %#x", flags);
+    if (ctx->in_proof) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: a proof is running on this context");
+    std::memset(out, 0, sizeof(*out));
+    ctx->verify_timed = false;
+    Prepared R;
+    if (int rc = prepare(K, W, n_words, flags, &R)) return bj::fail(ctx, rc, "%s", R.err.c_str());
+    *out = R.report;
+    if (!R.device) return BJ_OK;
+
+    // ---- device: the query section once, the small tables behind it ----
+    const Geometry &G = R.geo;
+    const size_t nq = R.nq, n_oracles = G.sizes.n_oracles, query_words = G.sizes.query_words;
+    const bj::VerifyTables at = bj::verify_tables(G.sizes, nq);
     size_t off = 0;
     auto take = [&off](size_t words) {
         const size_t at = off;
         off += (words + 1) & ~(size_t)1;
         return at;
     };
-    const size_t o_q = take(nq * query_words), o_small = off;
-    const size_t o_idx = take(2 * nq), o_caps = take(n_oracles * cap_words), o_terms = take(term_words.size()), o_sets = take(set_words.size());
-    const size_t o_frich = take(fri_ch.size()), o_fm = take(2 * final_degree), small_words = off - o_small;
+    const size_t o_q = take(nq * query_words), o_small = take(at.words);
     const size_t o_st_open = take((n_oracles * nq + 1) / 2), o_st_deep = take((nq + 1) / 2);
     if (int rc = bj::ensure_scratch(ctx, off)) return rc;
-    if (int rc = bj::ensure_twiddles(ctx, LOGN, true)) return rc;
+    if (int rc = bj::ensure_twiddles(ctx, G.LOGN, true)) return rc;
     u64 *D = ctx->d_scratch;
     hipStream_t st = ctx->stream;
-    {
-        std::vector<u64> small(small_words, 0);
-        u64 *s = small.data() - o_small;
-        std::memcpy(s + o_idx, indices.data(), indices.size() * 8);
-        std::memcpy(s + o_caps, wit_cap, cap_words * 8);
-        std::memcpy(s + o_caps + cap_words, s2_cap, cap_words * 8);
-        std::memcpy(s + o_caps + 2 * cap_words, q_cap, cap_words * 8);
-        std::memcpy(s + o_caps + 3 * cap_words, K->cap.data(), cap_words * 8);
-        std::memcpy(s + o_caps + 4 * cap_words, fri_caps, sched_len * cap_words * 8);
-        std::memcpy(s + o_terms, term_words.data(), term_words.size() * 8);
-        std::memcpy(s + o_sets, set_words.data(), set_words.size() * 8);
-        std::memcpy(s + o_frich, fri_ch.data(), fri_ch.size() * 8);
-        for (size_t i = 0; i < final_degree; i++) {
-            s[o_fm + i] = gl::canon(fm0[i]);
-            s[o_fm + final_degree + i] = gl::canon(fm1[i]);
-        }
-        if (int rc = bj_memcpy_h2d(ctx, D + o_q, queries, nq * query_words * 8)) return rc;
-        if (int rc = bj_memcpy_h2d(ctx, D + o_small, small.data(), small_words * 8)) return rc;
-    }
+    if (int rc = bj_memcpy_h2d(ctx, D + o_q, R.queries, nq * query_words * 8)) return rc;
+    if (int rc = bj_memcpy_h2d(ctx, D + o_small, R.tables.data(), at.words * 8)) return rc;
     bj::VerifyOpenArgs OA{};
     OA.queries = D + o_q;
-    OA.caps = D + o_caps;
+    OA.caps = D + o_small + at.caps;
     OA.status = (uint32_t *)(D + o_st_open);
     OA.n_queries = (uint32_t)nq;
     OA.query_words = (uint32_t)query_words;
     OA.n_oracles = (uint32_t)n_oracles;
+    std::memcpy(OA.oracle, G.oracle, sizeof OA.oracle);
     VerifyDeepArgs DA{};
     DA.queries = D + o_q;
-    DA.terms = D + o_terms;
-    DA.sets = D + o_sets;
-    DA.fri_ch = D + o_frich;
-    DA.final0 = D + o_fm;
-    DA.final1 = D + o_fm + final_degree;
-    DA.roots = ctx->tw_inv;
+    DA.terms = D + o_small + at.terms;
+    DA.sets = D + o_small + at.sets;
+    DA.fri_ch = D + o_small + at.fri_ch;
+    DA.final0 = D + o_small + at.fm;
+    DA.final1 = D + o_small + at.fm + G.sizes.final_degree;
     DA.status = (uint32_t *)(D + o_st_deep);
     DA.n_queries = (uint32_t)nq;
-    DA.query_words = (uint32_t)query_words;
-    DA.n_sets = (uint32_t)n_sets;
-    DA.n_fri = (uint32_t)sched_len;
-    DA.final_degree = (uint32_t)final_degree;
-    DA.log_full = LOGN;
-    DA.total_folds = total_folds;
-    DA.omega = gl::omega(LOGN);
-    DA.kappa = gl::inv(gl::GEN);
-    for (int o = 0; o < 4; o++) OA.oracle[o] = bj::VerifyOracle{leaf_off[o], widths[o], depth, 0, (uint32_t)(o * cap_words)};
-    {
-        uint32_t o = leaf_off[3] + widths[3] + depth * 4, shift = 0;
-        for (size_t l = 0; l < sched_len; l++) {
-            shift += sched[l];
-            OA.oracle[4 + l] = bj::VerifyOracle{o, 2u << sched[l], fri_depth[l], shift, (uint32_t)((4 + l) * cap_words)};
-            DA.fri_off[l] = o;
-            DA.sched[l] = (unsigned char)sched[l];
-            o += (2u << sched[l]) + fri_depth[l] * 4;
-        }
-    }
+    DA.sh = deep_shared(ctx, G);
     std::vector<uint32_t> st_open(n_oracles * nq), st_deep(nq);
-    // every chain of the proof judged at one set of indices; the first failure in the order of include/boojum_hip.h
+    // every chain of the proof judged at one set of indices
     auto judge = [&](const u64 *d_indices, bool timed, Failure *f) -> int {
         OA.indices = DA.indices = d_indices;
         if (timed)
@@ -753,33 +900,136 @@ int verify_impl(bj_ctx *ctx, const bj_vk *K, const u64 *W, size_t n_words, unsig
         if (int rc = bj_memcpy_d2h(ctx, st_open.data(), OA.status, st_open.size() * 4)) return rc;
         if (int rc = bj_memcpy_d2h(ctx, st_deep.data(), DA.status, st_deep.size() * 4)) return rc;
         if (timed) ctx->verify_timed = true;
-        *f = Failure{};
-        for (size_t i = 0; i < nq; i++) {
-            for (uint32_t o = 0; o < 4; o++)
-                if (!st_open[o * nq + i]) { *f = Failure{BJ_VERIFY_MERKLE, (uint32_t)i, o}; return BJ_OK; }
-            for (uint32_t l = 0; l < sched_len; l++) {
-                if (st_deep[i] == 1 + l) { *f = Failure{BJ_VERIFY_FRI_VALUE, (uint32_t)i, l}; return BJ_OK; }
-                if (!st_open[(4 + l) * nq + i]) { *f = Failure{BJ_VERIFY_FRI_MERKLE, (uint32_t)i, l}; return BJ_OK; }
-            }
-            if (st_deep[i]) { *f = Failure{BJ_VERIFY_FINAL, (uint32_t)i, 0}; return BJ_OK; }
-        }
+        *f = first_failure(st_open.data(), nq, st_deep.data(), nq, G.n_fri);
         return BJ_OK;
     };
     Failure at_drawn, at_stored;
-    if (int rc = judge(D + o_idx, true, &at_drawn)) return rc;
-    if (at_drawn.stage == BJ_VERIFY_OK) {
-        if (first_mismatch < 0) return verdict(out, BJ_VERIFY_OK, 0, 0, (uint32_t)nq);
-        return verdict(out, BJ_VERIFY_SHAPE, (uint32_t)first_mismatch, 0, (uint32_t)first_mismatch);
+    if (int rc = judge(D + o_small + at.idx, true, &at_drawn)) return rc;
+    if (!device_verdict(out, nq, R.first_mismatch, at_drawn, nullptr)) return BJ_OK;
+    if (int rc = judge(D + o_small + at.idx + nq, false, &at_stored)) return rc;
+    device_verdict(out, nq, R.first_mismatch, at_drawn, &at_stored);
+    return BJ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// bj_verify_batch: N proofs of one key — prepare() on worker threads, one upload, one launch of each kernel over every chain
+// ---------------------------------------------------------------------------------------------------------------------------
+int verify_batch_impl(bj_ctx *ctx, const bj_vk *K, const u64 *const *proofs, const size_t *n_words, size_t n_proofs, unsigned flags,
+                      bj_verify_report *out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!K) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: null key");
+    if (flags & ~BJ_VERIFY_PARTIAL_QUERIES) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: unknown flags %#x", flags);
+    if (ctx->in_proof) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: a proof is running on this context");
+    if (!n_proofs) return BJ_OK;
+    if (!proofs || !n_words || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: null argument");
+    if (n_proofs > bj::VERIFY_BATCH_MAX_PROOFS)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: %zu proofs in one call, at most %zu", n_proofs, bj::VERIFY_BATCH_MAX_PROOFS);
+    for (size_t i = 0; i < n_proofs; i++)
+        if (!proofs[i] && n_words[i]) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: proof %zu is null with %zu words", i, n_words[i]);
+    std::memset(out, 0, n_proofs * sizeof(*out));
+    ctx->verify_batch_state = 0;
+
+    // ---- host: prepare() of every proof, proofs handed out in order to a bounded pool ----
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<Prepared> R(n_proofs);
+    {
+        const unsigned limit = bj::env().verify_threads;
+        const size_t n_workers = n_proofs < limit ? n_proofs : limit;
+        std::atomic<size_t> next{0};
+        auto work = [&]() {
+            for (size_t i; (i = next.fetch_add(1)) < n_proofs;) prepare(K, proofs[i], n_words[i], flags, &R[i]);
+        };
+        std::vector<std::thread> pool;
+        for (size_t w = 1; w < n_workers; w++) pool.emplace_back(work);
+        work();
+        for (auto &t : pool) t.join();
     }
-    if (first_mismatch < 0) return verdict(out, at_drawn.stage, at_drawn.query, at_drawn.oracle, at_drawn.query);
-    // The stored indices are not the drawn ones and the drawn ones fail: what do the openings the proof carries fail at?  This second
-    // pass exists for two rows of the stage table alone and never turns a rejection into an acceptance: a final monomial and a FRI
-    // cap are absorbed BEFORE the indices are drawn, so editing either moves every index — at the drawn indices such a proof fails
-    // at the witness path of query 0, whatever was edited; BJ_VERIFY_FINAL for the monomial and BJ_VERIFY_FRI_VALUE for a FRI leaf
-    // whose path (and therefore cap entry) was recomputed can only be told at the indices the prover opened.
-    if (int rc = judge(D + o_idx + nq, false, &at_stored)) return rc;
-    if (at_stored.stage == BJ_VERIFY_OK) return verdict(out, BJ_VERIFY_SHAPE, (uint32_t)first_mismatch, 0, (uint32_t)first_mismatch);
-    return verdict(out, at_stored.stage, at_stored.query, at_stored.oracle, at_stored.query);
+    ctx->verify_batch_host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (size_t i = 0; i < n_proofs; i++)
+        if (R[i].rc) return bj::fail(ctx, R[i].rc, "%s (proof %zu of the batch)", R[i].err.c_str(), i);
+    std::vector<size_t> dev;   // the proofs that reached the device phase, ascending
+    std::vector<uint32_t> nqs;
+    for (size_t i = 0; i < n_proofs; i++) {
+        out[i] = R[i].report;
+        if (R[i].device) {
+            dev.push_back(i);
+            nqs.push_back((uint32_t)R[i].nq);
+        }
+    }
+    ctx->verify_batch_state = 1;
+    if (dev.empty()) return BJ_OK;
+
+    // ---- device: every query section and every table block once, then two launches over every chain ----
+    const Geometry &G = R[dev[0]].geo;   // the key's: the same in every proof
+    const size_t n_oracles = G.sizes.n_oracles;
+    bj::VerifyBatchPlan P;
+    if (!bj::plan_verify_batch(G.sizes, nqs.data(), dev.size(), &P))
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: the batch has more than 2^31 query openings");
+    if (int rc = bj::ensure_scratch(ctx, P.total_words)) return rc;   // before anything is uploaded
+    if (int rc = bj::ensure_twiddles(ctx, G.LOGN, true)) return rc;
+    u64 *D = ctx->d_scratch;
+    hipStream_t st = ctx->stream;
+    for (auto &e : ctx->verify_batch_ev)
+        if (!e) BJ_HIP(ctx, hipEventCreate(&e));
+    std::vector<u64> block(P.host_words);
+    for (size_t k = 0; k < dev.size(); k++)
+        std::memcpy(block.data() + (P.tables[k] - P.host_block), R[dev[k]].tables.data(), R[dev[k]].tables.size() * 8);
+    std::memcpy(block.data() + (P.record_table - P.host_block), P.records.data(), P.records.size() * sizeof(bj::VerifyBatchProof));
+    // stream-ordered copies out of the caller's buffers and `block`: all of them outlive the synchronisation below
+    BJ_HIP(ctx, hipEventRecord(ctx->verify_batch_ev[0], st));
+    for (size_t k = 0; k < dev.size(); k++)
+        BJ_HIP(ctx, hipMemcpyAsync(D + P.records[k].queries, R[dev[k]].queries, (size_t)nqs[k] * G.sizes.query_words * 8, hipMemcpyHostToDevice, st));
+    BJ_HIP(ctx, hipMemcpyAsync(D + P.host_block, block.data(), block.size() * 8, hipMemcpyHostToDevice, st));
+    BJ_HIP(ctx, hipEventRecord(ctx->verify_batch_ev[1], st));
+    bj::VerifyOpenBatchArgs OA{};
+    OA.base = D;
+    OA.status = (uint32_t *)(D + P.status_open);
+    OA.query_words = (uint32_t)G.sizes.query_words;
+    OA.n_oracles = (uint32_t)n_oracles;
+    std::memcpy(OA.oracle, G.oracle, sizeof OA.oracle);
+    VerifyDeepBatchArgs DA{};
+    DA.base = D;
+    DA.status = (uint32_t *)(D + P.status_deep);
+    DA.sh = deep_shared(ctx, G);
+    std::vector<uint32_t> status;
+    // both kernels over `n` records at d_records, `chains` chains in all; the status words land in `status`: openings, then DEEP
+    auto launch = [&](const u64 *d_records, size_t n, uint32_t chains, bool timed) -> int {
+        OA.proofs = DA.proofs = (const bj::VerifyBatchProof *)d_records;
+        OA.n_proofs = DA.n_proofs = (uint32_t)n;
+        OA.n_chains = DA.n_chains = chains;
+        bj::launch_verify_openings_batch((int)K->hasher, OA, st);
+        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_batch_ev[2], st));
+        hipLaunchKernelGGL(verify_deep_fri_batch_kernel, dim3(chains), dim3(64), 0, st, DA);
+        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_batch_ev[3], st));
+        BJ_CHECK_LAUNCH(ctx);
+        status.resize((n_oracles + 1) * (size_t)chains);
+        BJ_HIP(ctx, hipMemcpyAsync(status.data(), OA.status, n_oracles * (size_t)chains * 4, hipMemcpyDeviceToHost, st));
+        BJ_HIP(ctx, hipMemcpyAsync(status.data() + n_oracles * (size_t)chains, DA.status, (size_t)chains * 4, hipMemcpyDeviceToHost, st));
+        BJ_HIP(ctx, hipStreamSynchronize(st));
+        return BJ_OK;
+    };
+    auto failure_of = [&](const bj::VerifyBatchProof &r, uint32_t chains) {
+        return first_failure(status.data() + r.chain0, chains, status.data() + n_oracles * (size_t)chains + r.chain0, r.nq, G.n_fri);
+    };
+    if (int rc = launch(D + P.record_table, dev.size(), P.n_chains, true)) return rc;
+    ctx->verify_batch_state = 2;
+    std::vector<Failure> at_drawn(dev.size());
+    std::vector<size_t> again;   // positions in dev whose verdict needs the stored indices
+    for (size_t k = 0; k < dev.size(); k++) {
+        at_drawn[k] = failure_of(P.records[k], P.n_chains);
+        if (device_verdict(&out[dev[k]], nqs[k], R[dev[k]].first_mismatch, at_drawn[k], nullptr)) again.push_back(k);
+    }
+    if (again.empty()) return BJ_OK;
+    std::vector<bj::VerifyBatchProof> second;
+    const uint32_t chains2 = bj::plan_verify_second_pass(P, again, &second);
+    BJ_HIP(ctx, hipMemcpyAsync(D + P.record_table2, second.data(), second.size() * sizeof(bj::VerifyBatchProof), hipMemcpyHostToDevice, st));
+    if (int rc = launch(D + P.record_table2, second.size(), chains2, false)) return rc;
+    for (size_t j = 0; j < again.size(); j++) {
+        const size_t k = again[j];
+        const Failure at_stored = failure_of(second[j], chains2);
+        device_verdict(&out[dev[k]], nqs[k], R[dev[k]].first_mismatch, at_drawn[k], &at_stored);
+    }
+    return BJ_OK;
 }
 
 void take_gate(bj_vk::Gate &g, const bj_gate_desc &G) {
@@ -902,6 +1152,27 @@ int bj_verify_proof(bj_ctx *ctx, const bj_vk *vk, const bj_proof *proof, bj_veri
     if (!proof) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_proof: null proof");
     const std::vector<u64> &w = bj::proof_words(proof);
     return verify_impl(ctx, vk, w.data(), w.size(), 0, out);
+}
+
+int bj_verify_batch(bj_ctx *ctx, const bj_vk *vk, const uint64_t *const *proofs, const size_t *n_words, size_t n_proofs, unsigned flags,
+                    bj_verify_report *out) {
+    return verify_batch_impl(ctx, vk, proofs, n_words, n_proofs, flags, out);
+}
+
+int bj_verify_batch_ms(bj_ctx *ctx, float *host_ms, float *upload_ms, float *openings_ms, float *deep_fri_ms) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!ctx->verify_batch_state) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch_ms: no bj_verify_batch has run on this context");
+    float up = 0, a = 0, b = 0;
+    if (ctx->verify_batch_state == 2) {   // the batch reached its kernels (it synchronised behind them)
+        BJ_HIP(ctx, hipEventElapsedTime(&up, ctx->verify_batch_ev[0], ctx->verify_batch_ev[1]));
+        BJ_HIP(ctx, hipEventElapsedTime(&a, ctx->verify_batch_ev[1], ctx->verify_batch_ev[2]));
+        BJ_HIP(ctx, hipEventElapsedTime(&b, ctx->verify_batch_ev[2], ctx->verify_batch_ev[3]));
+    }
+    if (host_ms) *host_ms = ctx->verify_batch_host_ms;
+    if (upload_ms) *upload_ms = up;
+    if (openings_ms) *openings_ms = a;
+    if (deep_fri_ms) *deep_fri_ms = b;
+    return BJ_OK;
 }
 
 int bj_verify_kernel_ms(bj_ctx *ctx, float *openings_ms, float *deep_fri_ms) {

@@ -8,8 +8,15 @@
 // of that oracle, 64 lanes per workgroup: the lanes of a wave work on ONE oracle, so leaf width and path depth — the number of
 // permutations — are wave-uniform.  A chain reads its own query's words (a few hundred, uncoalesced: the whole query section is
 // under 2 MB) and writes one status word; nothing here traps, whatever the words are.
+//
+// bj_verify_batch runs the same chains for many proofs of ONE key in one launch: blockIdx.y stays the oracle, blockIdx.x * 64 +
+// lane is a chain of the whole batch, and the (proof, query) it belongs to comes out of a table of per-proof records in device
+// memory (VerifyBatchProof, ordered by first chain) by a binary search of at most 17 steps — a few dozen cached loads in front
+// of ~200 dependent permutations, against a chain -> proof array of up to 2^16 x queries words that would have to be built and
+// uploaded per call.  Chains of different proofs share waves; the oracle table is the key's and therefore the batch's.
 #pragma once
 #include "gl.h"
+#include "verify_batch_plan.h"
 
 namespace bj {
 typedef uint64_t u64;
@@ -33,6 +40,25 @@ struct VerifyOpenArgs {
     VerifyOracle oracle[VERIFY_MAX_ORACLES];
 };
 
+struct VerifyOpenBatchArgs {
+    const u64 *base;
+    const VerifyBatchProof *proofs;   // [n_proofs], chain0 ascending
+    uint32_t *status;                 // [n_oracles][n_chains]
+    uint32_t n_proofs, n_chains, query_words, n_oracles;
+    VerifyOracle oracle[VERIFY_MAX_ORACLES];
+};
+
+// the record chain g of a batch belongs to: the last one with chain0 <= g (records without queries never own a chain)
+__device__ __forceinline__ unsigned verify_batch_proof_of(const VerifyBatchProof *proofs, unsigned n_proofs, unsigned g) {
+    unsigned lo = 0, hi = n_proofs;
+    while (hi - lo > 1) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (proofs[mid].chain0 <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // the algebraic hashers (sponge_tree.h: overwrite absorption of 8 words, zero-padded tail; node = perm(left || right || 0)).
 // ONE call site of the permutation serves the leaf's blocks and the path's nodes: which of the two a round is depends on the
 // oracle alone, so the branch is wave-uniform (sponge_tree.h: a leaf kernel with two copies of the Poseidon2 stream is 72 KB of
@@ -40,12 +66,9 @@ struct VerifyOpenArgs {
 // sponge_leaves / sponge_nodes: the permutation takes any u64 representative, so a word and word + p hash alike, which is what
 // the prover's own trees do; the byte hashers hash canonical bytes, as theirs do
 template <void (*PERMUTE)(u64 (&)[12])>
-__device__ __forceinline__ void verify_open_sponge(const VerifyOpenArgs &A) {
-    const unsigned c = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
-    if (c >= A.n_queries) return;
-    const VerifyOracle O = A.oracle[o];
-    const u64 *leaf = A.queries + (size_t)c * A.query_words + O.leaf_off, *path = leaf + O.width;
-    u64 ti = A.indices[c] >> O.shift;
+__device__ __forceinline__ bool verify_chain_sponge(const u64 *query, u64 index, const VerifyOracle &O, const u64 *caps) {
+    const u64 *leaf = query + O.leaf_off, *path = leaf + O.width;
+    u64 ti = index >> O.shift;
     const unsigned n_blocks = (O.width + 7) / 8, rounds = n_blocks + O.depth;
     u64 s[12];
 #pragma unroll
@@ -69,22 +92,39 @@ __device__ __forceinline__ void verify_open_sponge(const VerifyOpenArgs &A) {
         }
         PERMUTE(s);
     }
-    const u64 *cap = A.caps + O.cap_off + 4 * ti;
+    const u64 *cap = caps + O.cap_off + 4 * ti;
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 4; k++) ok = ok && gl::canon(s[k]) == cap[k];
+    return ok;
+}
+template <void (*PERMUTE)(u64 (&)[12])>
+__device__ __forceinline__ void verify_open_sponge(const VerifyOpenArgs &A) {
+    const unsigned c = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
+    if (c >= A.n_queries) return;
+    const bool ok = verify_chain_sponge<PERMUTE>(A.queries + (size_t)c * A.query_words, A.indices[c], A.oracle[o], A.caps);
     A.status[(size_t)o * A.n_queries + c] = ok ? 1u : 0u;
+}
+template <void (*PERMUTE)(u64 (&)[12])>
+__device__ __forceinline__ void verify_open_sponge_batch(const VerifyOpenBatchArgs &A) {
+    const unsigned g = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
+    if (g >= A.n_chains) return;
+    const VerifyBatchProof &P = A.proofs[verify_batch_proof_of(A.proofs, A.n_proofs, g)];
+    const unsigned c = g - P.chain0;
+    if (c >= P.nq) return;
+    // three values per lane where the single-proof kernel has three wave-uniform ones: nothing else of the record stays live
+    const u64 *query = A.base + P.queries + (size_t)c * A.query_words, *caps = A.base + P.caps;
+    const u64 index = A.base[P.indices + c];
+    const bool ok = verify_chain_sponge<PERMUTE>(query, index, A.oracle[o], caps);
+    A.status[(size_t)o * A.n_chains + g] = ok ? 1u : 0u;
 }
 
 // the byte hashers: H::leaf(words, n, digest) hashes the canonical little-endian bytes of n field elements, H::node(l, r, digest)
 // the 64 bytes of two digests; digests are four raw words
 template <typename H>
-__device__ __forceinline__ void verify_open_bytes(const VerifyOpenArgs &A) {
-    const unsigned c = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
-    if (c >= A.n_queries) return;
-    const VerifyOracle O = A.oracle[o];
-    const u64 *leaf = A.queries + (size_t)c * A.query_words + O.leaf_off, *path = leaf + O.width;
-    u64 ti = A.indices[c] >> O.shift;
+__device__ __forceinline__ bool verify_chain_bytes(const u64 *query, u64 index, const VerifyOracle &O, const u64 *caps) {
+    const u64 *leaf = query + O.leaf_off, *path = leaf + O.width;
+    u64 ti = index >> O.shift;
     u64 d[4];
     H::leaf(leaf, O.width, d);
     for (unsigned j = 0; j < O.depth; j++) {
@@ -99,11 +139,30 @@ __device__ __forceinline__ void verify_open_bytes(const VerifyOpenArgs &A) {
         }
         H::node(l, r, d);
     }
-    const u64 *cap = A.caps + O.cap_off + 4 * ti;
+    const u64 *cap = caps + O.cap_off + 4 * ti;
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 4; k++) ok = ok && d[k] == cap[k];
+    return ok;
+}
+template <typename H>
+__device__ __forceinline__ void verify_open_bytes(const VerifyOpenArgs &A) {
+    const unsigned c = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
+    if (c >= A.n_queries) return;
+    const bool ok = verify_chain_bytes<H>(A.queries + (size_t)c * A.query_words, A.indices[c], A.oracle[o], A.caps);
     A.status[(size_t)o * A.n_queries + c] = ok ? 1u : 0u;
+}
+template <typename H>
+__device__ __forceinline__ void verify_open_bytes_batch(const VerifyOpenBatchArgs &A) {
+    const unsigned g = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
+    if (g >= A.n_chains) return;
+    const VerifyBatchProof &P = A.proofs[verify_batch_proof_of(A.proofs, A.n_proofs, g)];
+    const unsigned c = g - P.chain0;
+    if (c >= P.nq) return;
+    const u64 *query = A.base + P.queries + (size_t)c * A.query_words, *caps = A.base + P.caps;
+    const u64 index = A.base[P.indices + c];
+    const bool ok = verify_chain_bytes<H>(query, index, A.oracle[o], caps);
+    A.status[(size_t)o * A.n_chains + g] = ok ? 1u : 0u;
 }
 
 }  // namespace bj

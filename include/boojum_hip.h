@@ -46,7 +46,7 @@ typedef struct bj_ctx bj_ctx;
  * 4: bj_proof_config.pow_runner, bj_circuit.table_id_col = BJ_TABLE_ID_AS_VARIABLE (round 5); 5: bj_comm_replay_capture,
  * bj_proof_workspace_bytes, bj_setup_device_bytes; 6: bj_prove_async / bj_proof_wait, the tiled-monomial operators, bj_comm_peer_create (round 6);
  * entry points added within version 6 (no layout of an existing struct changes with them): bj_check_satisfied, bj_lookup_multiplicities, bj_vk_* / bj_verify,
- * bj_sigma_cells, bj_check_copy_constraints */
+ * bj_sigma_cells, bj_check_copy_constraints, bj_verify_batch / bj_verify_batch_ms */
 #define BJ_ABI_VERSION 6
 int bj_abi_version(void);
 /* 1 if bj_setup_create accepts bj_gate_desc.kind == kind, else 0: gate kinds are added within an ABI version (no layout
@@ -859,6 +859,28 @@ int bj_verify(bj_ctx *ctx, const bj_vk *vk, const uint64_t *proof_words, size_t 
 int bj_verify_proof(bj_ctx *ctx, const bj_vk *vk, const bj_proof *proof, bj_verify_report *out);   /* the handle bj_prove returned */
 /* HIP-event durations of the two kernels of the last bj_verify on this context that reached them (measurement only). */
 int bj_verify_kernel_ms(bj_ctx *ctx, float *openings_ms, float *deep_fri_ms);
+
+#define BJ_VERIFY_BATCH_MAX_PROOFS 65536u
+/* n_proofs proofs under ONE key in one call: out[i] is, field for field, what bj_verify(ctx, vk, proofs[i], n_words[i], flags,
+ * &out[i]) reports.  The host half of every proof (everything bj_verify does before its kernels) runs on min(n_proofs,
+ * BJ_VERIFY_THREADS) threads of the library's own — the environment variable is read with the other BJ_* switches at the first
+ * bj_ctx_create / bj_env_reload, defaults to 8 and is clamped to 1..16; a proof that fails there (shape, lookup sum, quotient
+ * identity, proof of work) takes no part in the device work.  The query sections of all other proofs are packed back to back
+ * into the context's scratch with a table of per-proof records behind them, by stream-ordered copies; ONE launch walks every
+ * Merkle chain of every proof (chains of different proofs share waves), a second runs one wave per (proof, query) for DEEP, folds
+ * and final monomials, and the call synchronises once behind them.  Proofs that fail at their drawn indices and store other
+ * indices are judged again at the stored ones, as in bj_verify, in one more pair of launches over those proofs alone.
+ * With BJ_VERIFY_PARTIAL_QUERIES the proofs of a batch may carry different numbers of query openings.
+ * Returns BJ_OK whenever the checks ran; a negative status only where bj_verify returns one (null arguments, a hasher the context
+ * cannot run, a HIP failure — a scratch that cannot grow to hold the batch among them, found before anything is uploaded), for
+ * n_proofs above BJ_VERIFY_BATCH_MAX_PROOFS and for a null proofs[i] with n_words[i] > 0.  A null proofs[i] with n_words[i] == 0
+ * is BJ_VERIFY_SHAPE for that proof alone.  n_proofs == 0: BJ_OK, nothing is touched.  Same context rules as bj_verify: the
+ * context's stream and scratch, nothing left behind that a later proof depends on, not while a proof runs on the context. */
+int bj_verify_batch(bj_ctx *ctx, const bj_vk *vk, const uint64_t *const *proofs, const size_t *n_words, size_t n_proofs, unsigned flags,
+                    bj_verify_report *out /* [n_proofs] */);
+/* Of the last bj_verify_batch on this context (measurement only): wall time of its host phase, HIP-event durations of its
+ * uploads and of the two kernels of its first pass — zero for a batch whose proofs all ended in the host phase. */
+int bj_verify_batch_ms(bj_ctx *ctx, float *host_ms, float *upload_ms, float *openings_ms, float *deep_fri_ms);
 
 /* The host loop over witnesses around prove_cpu_basic (prover.rs:153-168, convenience.rs:119-196), pipelined from ONE host
  * thread: bj_prove_async queues bj_prove(setup, witness) on one of the context's two internal lanes (each its own HIP stream,

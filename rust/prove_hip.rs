@@ -240,6 +240,20 @@ pub fn verify_hip(ctx: &HipCtx, vk: &HipVk, words: &[u64], partial_queries: bool
     report
 }
 
+/// `verify_hip` for many proofs of ONE key in one call (`bj_verify_batch`): the host halves run on the library's bounded thread
+/// pool, every query section crosses once, and two launches cover every Merkle chain and every (proof, query) of the batch.
+/// `reports[i]` is what `verify_hip(ctx, vk, proofs[i], partial_queries)` returns; an empty slice is a proof of no words
+/// (`BJ_VERIFY_SHAPE`).  With `partial_queries` the proofs may carry different numbers of query openings.
+pub fn verify_batch_hip(ctx: &HipCtx, vk: &HipVk, proofs: &[&[u64]], partial_queries: bool) -> Vec<bj_verify_report> {
+    let ptrs: Vec<*const u64> = proofs.iter().map(|p| if p.is_empty() { std::ptr::null() } else { p.as_ptr() }).collect();
+    let sizes: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+    let mut reports: Vec<bj_verify_report> =
+        (0..proofs.len()).map(|_| bj_verify_report { stage: 0, query: 0, oracle: 0, queries_checked: 0 }).collect();
+    let flags = if partial_queries { BJ_VERIFY_PARTIAL_QUERIES } else { 0 };
+    ctx.check(unsafe { bj_verify_batch(ctx.raw, vk.raw, ptrs.as_ptr(), sizes.as_ptr(), proofs.len(), flags, reports.as_mut_ptr()) });
+    reports
+}
+
 /// Which cells break a copy constraint: the claim of the copy-permutation argument (copy_permutation.rs) over the sigma columns
 /// `create_permutation_polys` (setup.rs:419-503) made, tested cell by cell on the device — for raw columns that satisfy every gate
 /// (`check_satisfied_hip` says `BJ_SAT`) and are still refused by `prove_hip`.  `d_variables`: the device pointer `bj_prove_dev`

@@ -7,7 +7,13 @@ Shapes: sha16 / sha20 — the SHA-256 circuit at 2^16 / 2^20 rows with the bench
 100); rec16 — the recursion-class circuit at 2^16 rows with the golden proof's config (fri_lde_factor 2, cap 16, security 100:
 100 queries).  Per shape, median of 5: the whole bj_verify call (wall clock around the synchronous call: upload of the query
 section, host replay, both kernels, status read-back), its two kernels alone (HIP events, bj_verify_kernel_ms), and bj_prove_dev of
-the same witness (median of 3)."""
+the same witness (median of 3).
+
+    python tools/verify_rate.py --batch 1,8,64,512 [--shapes sha12,sha16]
+
+adds the batch leg: per N, bj_verify_batch over N copies-with-distinct-buffers of the proof next to N looped bj_verify calls on the
+same buffers, alternating the two for 5 rounds after one warm-up of each (proofs/s from the median wall time), and the four
+phase times of bj_verify_batch_ms of the median batch.  `--batch N` with one number is the same for that N alone."""
 import argparse
 import json
 import os
@@ -23,6 +29,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="sha16,sha20,rec16")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--batch", default=None, help="comma-separated batch sizes for the bj_verify_batch leg, e.g. 1,8,64,512")
     args = ap.parse_args()
     try:
         import torch
@@ -72,6 +79,30 @@ def main():
                "verify_openings_kernel_ms": statistics.median(k_open), "verify_deep_fri_kernel_ms": statistics.median(k_deep),
                "prove_dev_ms": statistics.median(prove), "prove_dev_runs_ms": prove,
                "verify_over_prove": statistics.median(whole) / statistics.median(prove)}
+        if args.batch:
+            res["batch"] = []
+            for n in [int(x) for x in args.batch.split(",")]:
+                proofs = [np.array(buf, copy=True) for _ in range(n)]      # N buffers: nothing is served from one cached copy
+                assert all(vk.verify_batch(ctx, proofs)) and all(vk.verify(ctx, p) for p in proofs)      # warm-up of both, and the verdicts
+                loop_ms, batch_ms, phases = [], [], []
+                for _ in range(5):
+                    ctx.sync()
+                    t = time.perf_counter()
+                    for p in proofs:
+                        vk.verify(ctx, p)
+                    loop_ms.append((time.perf_counter() - t) * 1e3)
+                    ctx.sync()
+                    t = time.perf_counter()
+                    vk.verify_batch(ctx, proofs)
+                    batch_ms.append((time.perf_counter() - t) * 1e3)
+                    phases.append(vk.batch_ms(ctx))
+                lm, bm = statistics.median(loop_ms), statistics.median(batch_ms)
+                ph = phases[batch_ms.index(sorted(batch_ms)[2])]
+                row = {"n": n, "loop_ms": lm, "batch_ms": bm, "loop_proofs_per_s": n / lm * 1e3, "batch_proofs_per_s": n / bm * 1e3,
+                       "loop_runs_ms": loop_ms, "batch_runs_ms": batch_ms, "host_ms": ph[0], "upload_ms": ph[1], "openings_ms": ph[2],
+                       "deep_fri_ms": ph[3]}
+                print("  batch", json.dumps(row), flush=True)
+                res["batch"].append(row)
         print(json.dumps(res), flush=True)
         results.append(res)
         vk.close()
