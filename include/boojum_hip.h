@@ -847,7 +847,10 @@ typedef struct bj_verify_report {
  * every Merkle chain (query x {4 base oracles, FRI layers}), and per query the DEEP value from the four opened leaves
  * (verifier.rs:2233-2290), the fold chain through the schedule and the final monomials at the point.
  * Per-query failures: the smallest failing query and, inside it, the reference's order — the four base oracles, then per FRI
- * layer the carried value and the layer's path, then the final check.  They are judged at the DRAWN index.  Where a query fails
+ * layer the carried value and the layer's path, then the final check.  So one changed word of layer l's opened leaf is
+ * BJ_VERIFY_FRI_VALUE at l where it is one of the two words (c0, c1) of the carried slot and BJ_VERIFY_FRI_MERKLE at l anywhere
+ * else: the fold out of a leaf is first compared at layer l + 1, behind the path of l.
+ * They are judged at the DRAWN index.  Where a query fails
  * there and its stored index word is not the drawn one, the openings are judged again at the stored index and that diagnosis is
  * reported (a word that went into the transcript before the indices were drawn — a final monomial, a FRI cap — moves every index:
  * what is named is then the check that word breaks, not the path of a leaf the prover never opened); openings that pass at an

@@ -2,7 +2,8 @@
 
 Keccak-256 (the original Keccak padding 0x01 … 0x80 of the `sha3::Keccak256` type the reference uses as a tree hasher,
 src/cs/oracle/mod.rs:247-312, and in Keccak256Transcript, transcript.rs:264-372) — python's hashlib only has the FIPS-202
-variant (padding 0x06), so the sponge is restated here on numpy uint64 lanes, vectorised over many messages, and PINNED
+variant (padding 0x06), so the sponge is restated here — on numpy uint64 lanes, vectorised over many messages, and on python
+integers for a single message — and PINNED
 through hashlib: with the domain byte switched to 0x06 the very same code must reproduce hashlib.sha3_256
 (tests/test_keccak.py).  `layer()` gives the merkle_* / Transcript / QueryIndexer / do_fri set of oracle/blake.py over it.
 """
@@ -64,6 +65,26 @@ def hash_words(words, domain=0x01):
     return np.ascontiguousarray(a[:4].T)
 
 
+_M64 = (1 << 64) - 1
+_PI = [(x + 5 * y, y + 5 * ((2 * x + 3 * y) % 5), _ROT[x][y]) for x in range(5) for y in range(5)]    # (from, to, rotation)
+_CHI = [(i - i % 5 + (i + 1) % 5, i - i % 5 + (i + 2) % 5) for i in range(25)]
+
+
+def _keccak_f_ints(a):
+    """Keccak-f[1600] on a list of 25 python integers: the rounds of keccak_f above for ONE state, without numpy's cost per
+    operation (a Merkle path or a transcript hashes one short message at a time)."""
+    for rc in _RC:
+        c = [a[x] ^ a[x + 5] ^ a[x + 10] ^ a[x + 15] ^ a[x + 20] for x in range(5)]
+        d = [c[(x + 4) % 5] ^ (((c[(x + 1) % 5] << 1) | (c[(x + 1) % 5] >> 63)) & _M64) for x in range(5)]
+        b = [0] * 25
+        for src, dst, n in _PI:
+            v = a[src] ^ d[src % 5]
+            b[dst] = ((v << n) | (v >> (64 - n))) & _M64
+        a = [b[i] ^ (~b[j] & b[k]) for i, (j, k) in enumerate(_CHI)]
+        a[0] ^= rc
+    return a
+
+
 def keccak256_bytes(data, domain=0x01):
     """One message given as bytes (any length): 32 digest bytes."""
     rate = 8 * RATE_LANES
@@ -72,13 +93,12 @@ def keccak256_bytes(data, domain=0x01):
     while len(msg) % rate:
         msg.append(0)
     msg[-1] |= 0x80
-    a = np.zeros((25, 1), dtype=np.uint64)
+    a = [0] * 25
     for off in range(0, len(msg), rate):
-        blk = np.frombuffer(bytes(msg[off:off + rate]), dtype="<u8")
         for k in range(RATE_LANES):
-            a[k, 0] ^= blk[k]
-        keccak_f(a)
-    return a[:4, 0].astype("<u8").tobytes()
+            a[k] ^= int.from_bytes(msg[off + 8 * k: off + 8 * k + 8], "little")
+        a = _keccak_f_ints(a)
+    return b"".join(x.to_bytes(8, "little") for x in a[:4])
 
 
 def layer():

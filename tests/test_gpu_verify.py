@@ -8,7 +8,7 @@ import pytest
 import era_boojum_amd as E
 from era_boojum_amd import binding as B, proof_format, synthetic as S
 from gpu_util import ctx
-from verify_util import SWEEP_CLASSES, Layout, P, bump, golden_circuit, golden_config, golden_proof_dict, sweep_positions
+from verify_util import SWEEP_CLASSES, Layout, P, bump, fri_value_edit, golden_circuit, golden_config, golden_proof_dict, sweep_positions
 
 pytestmark = pytest.mark.gpu
 
@@ -177,25 +177,9 @@ def test_edited_query_openings(proven):
 def test_edited_fri_leaf_with_its_path_recomputed(proven):
     """The carried slot of query 0's layer-1 leaf changed, the path walked again and the cap entry it ends at replaced: the layer's
     path verifies, the value folded out of layer 0 is no longer in the leaf."""
-    import oracle as O
     pr, L = proven, proven.L
-    words = np.array(pr.buf, copy=True)
-    layer, q = 1, L.query[0]
-    idx = int(words[L.index_words[0]])
-    before = sum(L.sched[:layer])
-    k = L.sched[layer]
-    fidx = idx >> before
-    sub, tree = fidx & ((1 << k) - 1), fidx >> k
-    a, b = q["fri%d_leaf" % layer]
-    words = bump(words, a + sub)
-    cur = O.hash_leaf(words[a:b])
-    pa, pb = q["fri%d_path" % layer]
-    for j in range((pb - pa) // 4):
-        sib = words[pa + 4 * j: pa + 4 * j + 4]
-        cur = O.hash_node(cur, sib) if tree % 2 == 0 else O.hash_node(sib, cur)
-        tree //= 2
-    cap0 = L.ranges["fri_caps"][0] + layer * L.cap * 4 + 4 * tree
-    words[cap0:cap0 + 4] = cur
+    layer = 1
+    words = fri_value_edit(pr.buf, L, layer, query=0)
     r = _both_reject(pr, words)
     assert (r.stage, r.query, r.oracle) == (B.VERIFY_FRI_VALUE, 0, layer)
 

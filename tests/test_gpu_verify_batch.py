@@ -10,7 +10,7 @@ import pytest
 import era_boojum_amd as E
 from era_boojum_amd import binding as B, proof_format, synthetic as S
 from gpu_util import ctx
-from verify_util import Layout, P, bump, golden_circuit, golden_config, golden_proof_dict
+from verify_util import Layout, P, bump, fri_value_edit, golden_circuit, golden_config, golden_proof_dict
 from test_gpu_verify import _circuit, _golden_words, proven  # noqa: F401  (proven: the module-scoped fixture of the single-proof tests)
 
 pytestmark = pytest.mark.gpu
@@ -73,25 +73,7 @@ def test_batch_equals_the_loop_all_valid(name, count, cfg, nq):
 # ---------------------------------------------------------------------------------------------------------------------------
 def _fri_value_edit(pr, layer=1, query=0):
     """test_gpu_verify.py::test_edited_fri_leaf_with_its_path_recomputed: the carried slot changed, path and cap entry recomputed."""
-    import oracle as O
-    L = pr.L
-    words = np.array(pr.buf, copy=True)
-    q = L.query[query]
-    idx = int(words[L.index_words[query]])
-    k = L.sched[layer]
-    fidx = idx >> sum(L.sched[:layer])
-    sub, tree = fidx & ((1 << k) - 1), fidx >> k
-    a, b = q["fri%d_leaf" % layer]
-    words = bump(words, a + sub)
-    cur = O.hash_leaf(words[a:b])
-    pa, pb = q["fri%d_path" % layer]
-    for j in range((pb - pa) // 4):
-        sib = words[pa + 4 * j: pa + 4 * j + 4]
-        cur = O.hash_node(cur, sib) if tree % 2 == 0 else O.hash_node(sib, cur)
-        tree //= 2
-    cap0 = L.ranges["fri_caps"][0] + layer * L.cap * 4 + 4 * tree
-    words[cap0:cap0 + 4] = cur
-    return words
+    return fri_value_edit(pr.buf, pr.L, layer, query)
 
 
 def _device_stage_edits(pr):

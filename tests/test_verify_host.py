@@ -8,7 +8,7 @@ import pytest
 
 import era_boojum_amd as E
 from era_boojum_amd import binding as B, proof_format, synthetic as S
-from verify_util import golden_circuit, golden_config, golden_proof_dict
+from verify_util import drawn_indices, golden_circuit, golden_config, golden_proof_dict
 
 
 def test_serialize_round_trips_an_oracle_prover_proof():
@@ -17,7 +17,7 @@ def test_serialize_round_trips_an_oracle_prover_proof():
     setup = OP.Setup(c, 4, 8, threads=2)
     proof = OP.prove(c, setup, 4, 8, security_level=20, threads=2)
     # the oracle prover's dict carries no stored indices (the reference's Proof has none): draw them as its verifier does
-    proof["_query_indices"] = _drawn_indices(c, np.asarray(setup.cap), proof, 8, 4)
+    proof["_query_indices"] = drawn_indices(c, np.asarray(setup.cap), proof, 8, 4)
     words = proof_format.serialize(proof)
     back = proof_format.parse(words, security_level=20)
     for k, v in back.items():
@@ -49,33 +49,6 @@ def _plain(x):
     if isinstance(x, (list, tuple, np.ndarray)):
         return [_plain(v) for v in x]
     return int(x) if x is not None else None
-
-
-def _drawn_indices(c, cap, proof, log_n, fri_lde):
-    """Replays the oracle's transcript up to the query indices (oracle/verifier.py, Poseidon2, no proof of work)."""
-    import oracle as O
-    t = O.Transcript()
-    t.absorb_cap(cap)
-    t.absorb(proof["public_inputs"])
-    t.absorb_cap(np.array(proof["witness_oracle_cap"], dtype=np.uint64))
-    for _ in range(4 if c.lookup_reps else 2):
-        t.challenge_ext()
-    t.absorb_cap(np.array(proof["stage_2_oracle_cap"], dtype=np.uint64))
-    t.challenge_ext()
-    t.absorb_cap(np.array(proof["quotient_oracle_cap"], dtype=np.uint64))
-    t.challenge_ext()
-    for grp in ("values_at_z", "values_at_z_omega", "values_at_0"):
-        for v in proof[grp]:
-            t.absorb(v)
-    t.challenge_ext()
-    for cap_ in [proof["fri_base_oracle_cap"]] + proof["fri_intermediate_oracles_caps"]:
-        t.absorb_cap(np.array(cap_, dtype=np.uint64))
-        t.challenge_ext()
-    t.absorb(proof["final_fri_monomials"][0])
-    t.absorb(proof["final_fri_monomials"][1])
-    log_fri = fri_lde.bit_length() - 1
-    qi = O.QueryIndexer(log_n, log_fri)
-    return [qi.next(t) for _ in proof["queries_per_fri_repetition"]]
 
 
 CONFIG = dict(fri_lde_factor=8, cap_size=16, security_level=20, pow_bits=0)
