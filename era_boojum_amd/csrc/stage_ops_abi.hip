@@ -1,6 +1,7 @@
 // C-ABI entry points of seam S2 for the prover's second round and its quotient terms (rows a9, a10, a12 of SURVEY §8 as
 // stand-alone operators): the kernels bj_prove runs, callable on caller-provided device columns so that each can be
-// compared with the reference function it replaces (and with oracle/prover_ops.c in tests/test_gpu_stage_ops.py).
+// compared with the reference function it replaces (with oracle/prover_ops.c on satisfied circuits in tests/test_gpu_stage_ops.py,
+// with the definitions in python integers on arbitrary columns in tests/test_gpu_quotient_terms.py).
 #include "ctx.h"
 #include "gate_program.h"
 
@@ -212,8 +213,11 @@ int bj_quotient_copy_perm(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_copy_perm: bad geometry (1..4096 columns, LDE factor at most 64)");
     const size_t n = (size_t)1 << log_n;
     if (first_point + num_points > (n << log_lde)) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_copy_perm: points past the LDE domain");
-    if (var_stride < num_points || sig_stride < num_points || stage2_stride < num_points)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_copy_perm: column stride below the number of points");
+    // the kernel takes the index inside the coset from the LOCAL index, and reads z(omega x) anywhere in the coset of its point
+    if (first_point & (n - 1)) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_copy_perm: first_point is not a multiple of n");
+    const size_t whole_cosets = (num_points + n - 1) & ~(n - 1);
+    if (var_stride < whole_cosets || sig_stride < whole_cosets || stage2_stride < whole_cosets)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_copy_perm: column stride below the number of points rounded up to whole cosets");
     if (int rc = bj::ensure_twiddles(ctx, log_n + log_lde, false)) return rc;
     const unsigned n_chunks = (num_vars + chunk - 1) / chunk;
     Tmp nr(ctx), al(ctx);

@@ -12,20 +12,11 @@ import oracle as O
 from era_boojum_amd import synthetic as S
 from gpu_util import DevBuf, ctx, oracle_threads, rand_gl, scan_inputs
 from oracle import prover as OP
+from quotient_cases import (BETA, GAMMA, LBETA, LGAMMA, circuit as _circuit, lookup_vars as _lookup_vars,
+                            oracle_quotient as _oracle_quotient, quotient_inputs as _quotient_inputs)
 
 pytestmark = pytest.mark.gpu
 P = O.P
-
-BETA, GAMMA = (0x1234567890ABCDEF % P, 0x0FEDCBA987654321), (77, P - 5)
-LBETA, LGAMMA = (P - 1, 3), (0xDEADBEEFCAFEF00D % P, 0x1111111122222222)
-ALPHA = (0x9E3779B97F4A7C15 % P, 0xBF58476D1CE4E5B9 % P)
-
-
-def _circuit(log_n, **kw):
-    c = S.sha_shaped_circuit(log_n, seed=31 + log_n, table_bits=2, **kw)
-    S.check_satisfied(c)
-    return c
-
 
 @pytest.mark.parametrize("log_n,kw", [(8, {}), (11, {}), (13, dict(num_gp_vars=24, lookup_width=3, lookup_reps=4, num_public_inputs=0)),
                                       (10, dict(num_gp_vars=7, lookup_width=4, lookup_reps=1, num_public_inputs=1))])
@@ -96,11 +87,6 @@ def test_grand_product_scan_above_2p18_rows(log_n):
         d.free()
 
 
-def _lookup_vars(c):
-    """The lookup sub-arguments' variable columns: width per sub-argument, width + 1 with the table id as a variable."""
-    return np.ascontiguousarray(c.variables[c.num_gp_vars:c.num_gp_vars + c.lookup_reps * c.lookup_cols_per_sub])
-
-
 # table_id_as_variable: LookupParameters::UseSpecializedColumnsWithTableIdAsVariable (lookup_argument_in_ext.rs:354-366) — the
 # operators take d_table_id = NULL and read the id from the (width+1)-th variable column of every sub-argument
 @pytest.mark.parametrize("log_n,kw", [(8, {}), (12, {}), (10, dict(num_gp_vars=24, lookup_width=3, lookup_reps=4, num_public_inputs=0)),
@@ -124,42 +110,6 @@ def test_lookup_polynomials(log_n, kw):
     assert tot0 == 0 and tot1 == 0
     for d in (d_l, d_t, d_tab, d_m, d_A, d_B):
         d.free()
-
-
-def _quotient_inputs(c):
-    """LDEs of every column the quotient reads, restricted to the first q cosets, by the oracle; plus the alpha powers."""
-    log_n, q, V = c.log_n, c.quotient_degree, c.num_vars
-    log_q = q.bit_length() - 1
-    Q = c.n * q
-    z, partials = OP.copy_perm_stage2(c.variables, c.sigmas, c.non_residues, log_n, q, BETA, GAMMA, threads=8)
-    stage2 = [z[0], z[1]] + [partials[j][k] for j in range(partials.shape[0]) for k in range(2)]
-    reps, w = c.lookup_reps, c.lookup_width
-    A, B = OP.lookup_polys(_lookup_vars(c), OP.lookup_table_id(c, c.constants), c.tables, c.multiplicities[0], reps, w, log_n, LBETA, LGAMMA,
-                           threads=8)
-    stage2 += [A[i][k] for i in range(reps) for k in range(2)] + [B[0], B[1]]
-
-    def lde_q(cols):
-        cols = np.ascontiguousarray(np.stack(cols) if isinstance(cols, list) else cols)
-        return np.ascontiguousarray(O.lde_batch(O.ifft_batch(cols, 1, threads=8), log_q, threads=8).reshape(cols.shape[0], Q))
-    d = dict(vars=lde_q(c.variables), mult=lde_q(c.multiplicities[:1])[0], sig=lde_q(c.sigmas), con=lde_q(c.constants),
-             tab=lde_q(c.tables), s2=lde_q(stage2))
-    n_part = partials.shape[0]
-    d["n_part"], d["Q"], d["log_q"] = n_part, Q, log_q
-    n_lookup, n_gate = reps + 1, sum(g.reps * g.num_terms for g in c.gates)
-    n_chunks = (V + q - 1) // q
-    al = [(1, 0)]
-    while len(al) < n_lookup + n_gate + 1 + n_chunks:
-        al.append(OP.emul(al[-1], ALPHA))
-    d["alphas"], d["n_lookup"], d["n_gate"], d["n_chunks"] = al, n_lookup, n_gate, n_chunks
-    return d
-
-
-def _oracle_quotient(c, d, alphas):
-    s2, n_part, reps = d["s2"], d["n_part"], c.lookup_reps
-    o = 2 + 2 * n_part
-    return OP.quotient(d["vars"], d["con"], d["sig"], np.ascontiguousarray(s2[0:2]), np.ascontiguousarray(s2[2:o]),
-                       np.ascontiguousarray(s2[o:o + 2 * reps]), np.ascontiguousarray(s2[o + 2 * reps:]), d["mult"], d["tab"], c,
-                       d["log_q"], alphas, BETA, GAMMA, LBETA, LGAMMA, threads=8)
 
 
 @pytest.mark.parametrize("log_n,kw", [(9, {}), (11, dict(num_gp_vars=24, lookup_width=3, lookup_reps=4, num_public_inputs=0)),
@@ -252,6 +202,10 @@ def test_stage_operators_report_bad_arguments():
         ctx().quotient_gates(d.ptr, 8, 3, d.ptr, 8, 8, g, [(1, 0)] * 40, 8, d.ptr, d.ptr)              # 60-column gates on 3 columns
     with pytest.raises(E.BoojumHipError):
         ctx().quotient_copy_perm(d.ptr, 8, d.ptr, 8, d.ptr, 8, [1], 1, 4, 3, 7, BETA, GAMMA, [(1, 0)] * 2, 8, 0, d.ptr, d.ptr)   # LDE 128
+    with pytest.raises(E.BoojumHipError, match="multiple of n"):                                          # n = 8: first_point inside a coset
+        ctx().quotient_copy_perm(d.ptr, 8, d.ptr, 8, d.ptr, 8, [1], 1, 4, 3, 1, BETA, GAMMA, [(1, 0)] * 2, 4, 4, d.ptr, d.ptr)
+    with pytest.raises(E.BoojumHipError, match="whole cosets"):                                           # half a coset at a stride of n / 2
+        ctx().quotient_copy_perm(d.ptr, 4, d.ptr, 4, d.ptr, 4, [1], 1, 4, 3, 1, BETA, GAMMA, [(1, 0)] * 2, 4, 0, d.ptr, d.ptr)
     d.free()
 
 
