@@ -302,10 +302,9 @@ void bj_ctx_destroy(bj_ctx *ctx) {
     if (ctx->arena) (void)hipFree(ctx->arena);
     for (auto &sl : ctx->arena_slabs) (void)hipFree(sl.first);
     if (ctx->h_ring) (void)hipHostFree(ctx->h_ring);
-    for (auto &e : ctx->verify_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : ctx->verify_batch_ev)
-        if (e) (void)hipEventDestroy(e);
+    for (auto *t : {&ctx->verify_timing, &ctx->verify_batch_timing})
+        for (auto &e : t->ev)
+            if (e) (void)hipEventDestroy(e);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     delete ctx;

@@ -151,7 +151,7 @@ __global__ void __launch_bounds__(256) blake2s_nodes_kernel(const u64 *prev, u64
     st.store(next + 4 * i);
 }
 
-// bj_verify: one (query, oracle) Merkle chain per lane (verify_open.h) over the leaf and node hashes above
+// bj_verify / bj_verify_batch: what a (query, oracle) Merkle chain (verify_open.h) takes from the leaf and node hashes above
 struct B2sVerifyHasher {
     static __device__ __forceinline__ void digest(const B2s &st, u64 (&d)[4]) {
 #pragma unroll
@@ -190,7 +190,6 @@ struct B2sVerifyHasher {
         digest(st, d);
     }
 };
-__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) blake2s_verify_openings_kernel(VerifyOpenArgs A) { verify_open_bytes<B2sVerifyHasher>(A); }
 
 // Proof of work (impl PoWRunner for Blake2s256, src/cs/implementations/pow.rs:50-133): the smallest nonce such that the
 // first 8 digest bytes of Blake2s(seed || le64(nonce)), read as a little-endian u64, have >= pow_bits trailing zeros.
@@ -238,16 +237,14 @@ static void launch_blake2s_leaves_chunked(const u64 *d_src0, const u64 *d_src1, 
 static void launch_blake2s_nodes(const u64 *d_children, u64 *d_parents, size_t num_parents, hipStream_t s) {
     launch_1d(blake2s_nodes_kernel, num_parents, s, d_children, d_parents, num_parents);
 }
+// bj_verify / bj_verify_batch: one (query, oracle) Merkle chain per lane over every proof of the launch, chain -> (proof, query)
+// through the record table (verify_open.h)
+__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) blake2s_verify_openings_kernel(VerifyOpenArgs A) { verify_open_bytes<B2sVerifyHasher>(A); }
 static void launch_blake2s_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
-    hipLaunchKernelGGL(blake2s_verify_openings_kernel, dim3((A.n_queries + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
-}
-// bj_verify_batch: the chains of every proof of a batch, chain -> (proof, query) through the record table (verify_open.h)
-__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) blake2s_verify_openings_batch_kernel(VerifyOpenBatchArgs A) { verify_open_bytes_batch<B2sVerifyHasher>(A); }
-static void launch_blake2s_verify_openings_batch(const VerifyOpenBatchArgs &A, hipStream_t s) {
-    hipLaunchKernelGGL(blake2s_verify_openings_batch_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
+    hipLaunchKernelGGL(blake2s_verify_openings_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
 }
 TreeHasher blake2s_tree_hasher() {
-    return {launch_blake2s_leaves, launch_blake2s_leaves_chunked, launch_blake2s_nodes, nullptr, launch_blake2s_verify_openings, launch_blake2s_verify_openings_batch};
+    return {launch_blake2s_leaves, launch_blake2s_leaves_chunked, launch_blake2s_nodes, nullptr, launch_blake2s_verify_openings};
 }
 
 }  // namespace bj

@@ -70,13 +70,13 @@ struct bj_ctx {
     } probes[BJ_MAX_KERNEL_PROBES];
     unsigned probe_n = 0;
     bj::Pipeline *pipe = nullptr;   // bj_prove_async: created on first use, destroyed with the context
-    // bj_verify: events around its two kernels (created on first use), read by bj_verify_kernel_ms
-    hipEvent_t verify_ev[4] = {};
-    bool verify_timed = false;      // the last bj_verify on this context launched its kernels
-    // bj_verify_batch: events before / after its uploads and after each of its two kernels, read by bj_verify_batch_ms
-    hipEvent_t verify_batch_ev[4] = {};
-    float verify_batch_host_ms = 0;   // wall time of the host phase of the last batch
-    int verify_batch_state = 0;       // the last batch: 0 none (or refused), 1 ended in its host phase, 2 launched its kernels
+    // bj_verify and bj_verify_batch keep one each, for bj_verify_kernel_ms and bj_verify_batch_ms: of the last call, events
+    // (created on first use) before / after its uploads and after each of its two kernels, and the wall time of its host phase
+    struct VerifyTiming {
+        hipEvent_t ev[4] = {};
+        int state = 0;        // the last call: 0 none (or refused, or bj_verify ended on the host), 1 the batch ended in its host phase, 2 launched its kernels
+        float host_ms = 0;    // bj_verify_batch only
+    } verify_timing, verify_batch_timing;
 };
 
 namespace bj {

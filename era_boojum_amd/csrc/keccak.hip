@@ -148,7 +148,7 @@ __global__ void __launch_bounds__(256) keccak_nodes_kernel(const u64 *prev, u64 
     st.store(next + 4 * i);
 }
 
-// bj_verify: one (query, oracle) Merkle chain per lane (verify_open.h) over the leaf and node hashes above
+// bj_verify / bj_verify_batch: what a (query, oracle) Merkle chain (verify_open.h) takes from the leaf and node hashes above
 struct KeccakVerifyHasher {
     static __device__ __forceinline__ void leaf(const u64 *w, unsigned n, u64 (&d)[4]) {
         Keccak st;
@@ -180,7 +180,6 @@ struct KeccakVerifyHasher {
         for (int k = 0; k < 4; k++) d[k] = st.a[k];
     }
 };
-__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) keccak_verify_openings_kernel(VerifyOpenArgs A) { verify_open_bytes<KeccakVerifyHasher>(A); }
 
 // Proof of work (impl PoWRunner for Keccak256, src/cs/implementations/pow.rs:139-230): the smallest nonce such that the first
 // 8 digest bytes of Keccak256(seed || le64(nonce)), read as a little-endian u64, have >= pow_bits trailing zeros.  seed = 5 field
@@ -222,16 +221,14 @@ static void launch_keccak_leaves_chunked(const u64 *d_src0, const u64 *d_src1, u
 static void launch_keccak_nodes(const u64 *d_children, u64 *d_parents, size_t num_parents, hipStream_t s) {
     launch_1d(keccak_nodes_kernel, num_parents, s, d_children, d_parents, num_parents);
 }
+// bj_verify / bj_verify_batch: one (query, oracle) Merkle chain per lane over every proof of the launch, chain -> (proof, query)
+// through the record table (verify_open.h)
+__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) keccak_verify_openings_kernel(VerifyOpenArgs A) { verify_open_bytes<KeccakVerifyHasher>(A); }
 static void launch_keccak_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
-    hipLaunchKernelGGL(keccak_verify_openings_kernel, dim3((A.n_queries + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
-}
-// bj_verify_batch: the chains of every proof of a batch, chain -> (proof, query) through the record table (verify_open.h)
-__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) keccak_verify_openings_batch_kernel(VerifyOpenBatchArgs A) { verify_open_bytes_batch<KeccakVerifyHasher>(A); }
-static void launch_keccak_verify_openings_batch(const VerifyOpenBatchArgs &A, hipStream_t s) {
-    hipLaunchKernelGGL(keccak_verify_openings_batch_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
+    hipLaunchKernelGGL(keccak_verify_openings_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
 }
 TreeHasher keccak_tree_hasher() {
-    return {launch_keccak_leaves, launch_keccak_leaves_chunked, launch_keccak_nodes, nullptr, launch_keccak_verify_openings, launch_keccak_verify_openings_batch};
+    return {launch_keccak_leaves, launch_keccak_leaves_chunked, launch_keccak_nodes, nullptr, launch_keccak_verify_openings};
 }
 
 }  // namespace bj

@@ -380,15 +380,11 @@ poseidon2_leaves_chunked_lanepar_kernel(const u64 *src0, const u64 *src1, unsign
     if (live && l < 4) digests[4 * j + l] = gl::canon(s);
 }
 
-// bj_verify: one (query, oracle) Merkle chain per lane (verify_open.h)
+// bj_verify / bj_verify_batch: one (query, oracle) Merkle chain per lane over every proof of the launch, chain -> (proof, query)
+// through the record table (verify_open.h)
 __global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) poseidon2_verify_openings_kernel(VerifyOpenArgs A) { verify_open_sponge<poseidon2_permutation>(A); }
 static void launch_poseidon2_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
-    hipLaunchKernelGGL(poseidon2_verify_openings_kernel, dim3((A.n_queries + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
-}
-// bj_verify_batch: the chains of every proof of a batch, chain -> (proof, query) through the record table (verify_open.h)
-__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) poseidon2_verify_openings_batch_kernel(VerifyOpenBatchArgs A) { verify_open_sponge_batch<poseidon2_permutation>(A); }
-static void launch_poseidon2_verify_openings_batch(const VerifyOpenBatchArgs &A, hipStream_t s) {
-    hipLaunchKernelGGL(poseidon2_verify_openings_batch_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
+    hipLaunchKernelGGL(poseidon2_verify_openings_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
 }
 
 __global__ void poseidon2_permute_states_kernel(u64 *states, size_t n_states) { sponge_permute_states<poseidon2_permutation>(states, n_states); }
@@ -421,7 +417,7 @@ static void launch_poseidon2_leaves_absorb(const u64 *d_base, size_t col_stride,
 }
 TreeHasher poseidon2_tree_hasher() {
     return {launch_poseidon2_leaves, launch_poseidon2_leaves_chunked, launch_poseidon2_nodes, launch_poseidon2_leaves_absorb,
-            launch_poseidon2_verify_openings, launch_poseidon2_verify_openings_batch};
+            launch_poseidon2_verify_openings};
 }
 
 void launch_poseidon2_permute_states(u64 *d_states, size_t n_states, hipStream_t s) {

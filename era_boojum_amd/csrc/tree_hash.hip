@@ -39,6 +39,5 @@ void launch_tree_leaves_absorb(int hasher, const u64 *d_base, size_t col_stride,
     (h.leaves_absorb ? h : tree_hasher(BJ_HASHER_POSEIDON2)).leaves_absorb(d_base, col_stride, n_cols, num_leaves, d_capacity, d_digests, first, last, s);
 }
 void launch_verify_openings(int hasher, const VerifyOpenArgs &args, hipStream_t s) { tree_hasher(hasher).verify_openings(args, s); }
-void launch_verify_openings_batch(int hasher, const VerifyOpenBatchArgs &args, hipStream_t s) { tree_hasher(hasher).verify_openings_batch(args, s); }
 
 }  // namespace bj

@@ -26,7 +26,6 @@ inline void launch_1d(void (*kernel)(Params...), size_t n, hipStream_t s, Args..
 }
 
 struct VerifyOpenArgs;        // verify_open.h
-struct VerifyOpenBatchArgs;
 
 // a hasher's launchers, one table entry of tree_hash.hip
 struct TreeHasher {
@@ -39,10 +38,8 @@ struct TreeHasher {
     // null for the byte hashers
     void (*leaves_absorb)(const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *d_capacity, u64 *d_digests,
                           bool first, bool last, hipStream_t s);
-    // bj_verify: the (query, oracle) Merkle chains of a proof's query section (verify_open.h)
+    // bj_verify / bj_verify_batch: the (query, oracle) Merkle chains of every proof of a batch in one launch (verify_open.h)
     void (*verify_openings)(const VerifyOpenArgs &args, hipStream_t s);
-    // bj_verify_batch: the same chains for every proof of a batch in one launch
-    void (*verify_openings_batch)(const VerifyOpenBatchArgs &args, hipStream_t s);
 };
 TreeHasher poseidon2_tree_hasher(), blake2s_tree_hasher(), keccak_tree_hasher(), poseidon1_tree_hasher();
 

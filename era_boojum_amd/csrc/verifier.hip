@@ -6,13 +6,13 @@
 // canonical form of gate_canon.h, the two flattened Poseidon gates by the F_p^2 restatement of their evaluators below — the DEEP
 // and FRI challenges (:1819-1955), the proof of work (:1957-1983), the public-input tuples and the query indices.
 // Device (the verifier's only volume, ~200 dependent permutations per query): verify_openings (verify_open.h, one kernel per tree
-// hasher) walks every Merkle chain; verify_deep_fri_kernel here, one wave per query, simulates the DEEP value from the four
+// hasher) walks every Merkle chain; verify_deep_fri_kernel here, one wave per (proof, query), simulates the DEEP value from the four
 // opened leaves (:2233-2290), folds it through the schedule (:2387-2519) and compares with the final monomials at the point.
 // Both write one status word per chain / query; the host reduces them to the report (include/boojum_hip.h has the order).
 //
-// The host half is prepare() — everything up to the tables the kernels read, no context in it, so bj_verify_batch runs it for N
-// proofs on worker threads — and a judge: bj_verify's over one proof, bj_verify_batch's over every proof of the batch that got as
-// far, in one launch of each kernel (verify_batch_plan.h lays the batch out in the context's scratch).
+// The host half is prepare() — named stages from the proof's shape to the tables the kernels read, no context in it, so
+// bj_verify_batch runs it for N proofs on worker threads.  The device half is judge(): every proof that got as far, in one launch of
+// each kernel (verify_batch_plan.h lays them out in the context's scratch).  bj_verify is that path with one proof.
 #include "ctx.h"
 #include "gate_program.h"
 #include "host_transcript.hpp"
@@ -30,13 +30,10 @@
 
 using gl::e2;
 using gl::u64;
+using VerifyTiming = bj_ctx::VerifyTiming;
 
 namespace bj {
 void launch_verify_openings(int hasher, const VerifyOpenArgs &args, hipStream_t s);   // tree_hash.hip
-void launch_verify_openings_batch(int hasher, const VerifyOpenBatchArgs &args, hipStream_t s);
-}
-
-namespace bj {
 const std::vector<u64> &proof_words(const bj_proof *p);   // prover.hip: the serialised words a proof handle holds
 }
 
@@ -252,19 +249,12 @@ struct VerifyDeepShared {   // what the key fixes: the same for every proof of a
     uint32_t fri_off[32];
     unsigned char sched[32];
 };
+// the per-proof tables come out of the record table (verify_batch_plan.h), as word offsets from `base`: queries and indices as in
+// verify_open.h; terms [n_terms][3]: leaf word of c0 | leaf word of c1 << 32 (NO_C1: base field), challenge power (c0, c1); sets
+// [n_sets][6]: first term, end term, the point (c0, c1), sum_k ch_k * value_k (c0, c1); fri_ch [n_fri][2]; the final monomials
 struct VerifyDeepArgs {
-    const u64 *queries, *indices;
-    const u64 *terms;     // [n_terms][3]: leaf word of c0 | leaf word of c1 << 32 (NO_C1: base field), challenge power (c0, c1)
-    const u64 *sets;      // [n_sets][6]: first term, end term, the point (c0, c1), sum_k ch_k * value_k (c0, c1)
-    const u64 *fri_ch;    // [n_fri][2]
-    const u64 *final0, *final1;   // final monomials
-    uint32_t *status;     // [n_queries]
-    uint32_t n_queries;
-    VerifyDeepShared sh;
-};
-struct VerifyDeepBatchArgs {   // bj_verify_batch: the per-proof pointers come out of the record table (verify_batch_plan.h)
     const u64 *base;
-    const bj::VerifyBatchProof *proofs;
+    const bj::VerifyBatchProof *proofs;   // [n_proofs], chain0 ascending
     uint32_t *status;     // [n_chains]
     uint32_t n_proofs, n_chains;
     VerifyDeepShared sh;
@@ -338,16 +328,8 @@ __device__ __forceinline__ uint32_t deep_fri_status(const VerifyDeepShared &A, c
     return status;
 }
 
+// one wave per (proof, query) of the whole launch; the search is over a wave-uniform chain, so it is scalar
 __global__ void __launch_bounds__(64) verify_deep_fri_kernel(VerifyDeepArgs A) {
-    const unsigned c = blockIdx.x, lane = threadIdx.x;
-    if (c >= A.n_queries) return;
-    const uint32_t status = deep_fri_status(A.sh, A.queries + (size_t)c * A.sh.query_words, A.indices[c], A.terms, A.sets, A.fri_ch, A.final0,
-                                            A.final1, lane);
-    if (lane == 0) A.status[c] = status;
-}
-
-// bj_verify_batch: one wave per (proof, query) of the whole batch; the search is over a wave-uniform chain, so it is scalar
-__global__ void __launch_bounds__(64) verify_deep_fri_batch_kernel(VerifyDeepBatchArgs A) {
     const unsigned g = blockIdx.x, lane = threadIdx.x;
     if (g >= A.n_chains) return;
     const bj::VerifyBatchProof P = A.proofs[bj::verify_batch_proof_of(A.proofs, A.n_proofs, g)];
@@ -403,7 +385,7 @@ struct Geometry {
     unsigned char sched[32] = {};
 };
 // A proof after the host half.  device == false: `report` is the verdict (or rc < 0 and err say why there is none).  device ==
-// true: the host checks passed; the tables (verify_batch_plan.h: verify_tables) and the query section wait for a judge.
+// true: the host checks passed; the tables (verify_batch_plan.h: verify_tables) and the query section wait for the judge.
 struct Prepared {
     int rc = BJ_OK;
     std::string err;
@@ -425,243 +407,334 @@ struct Prepared {
     }
 };
 
-// The host half: shape, transcript replay, lookup sum, quotient identity, proof of work, indices, DEEP tables.  Touches no context
-// and no global state: bj_verify_batch runs it on several threads at once.  Returns R->rc.
-int prepare(const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, Prepared *R) {
-    bj_verify_report *out = &R->report;
+// ---- the stages of prepare(), in the order it runs them.  A stage that returns bool has put the verdict (or the refusal) into
+// the Prepared when it returns false; what one stage hands to the next is in the plain structs below ----
 
-    // ---- shape: every count is the key's before it sizes anything ----
-    const unsigned log_n = K->log_n, V = K->V, Wc = K->Wc, nC = K->nC, q = K->q, log_fri = K->log_fri, LOGN = log_n + log_fri;
-    const size_t n = (size_t)1 << log_n, N = n << log_fri, cap = K->cap_size;
-    const bool has_lookup = K->lookup_reps > 0;
-    const unsigned n_chunks = (V + q - 1) / q, n_partials = n_chunks - 1;
-    const unsigned n_lookup_terms = has_lookup ? K->lookup_reps + 1 : 0;
-    const unsigned n_lookup_polys = has_lookup ? K->lookup_reps + 2 + K->lookup_w + 1 : 0;
-    const size_t nz = (size_t)V + Wc + nC + V + 1 + n_partials + n_lookup_polys + q;
+// The counts the key dictates and where the sections of one proof lie (pointers into the caller's buffer).
+struct ProofView {
+    unsigned log_n, V, Wc, nC, q, log_fri, LOGN, depth, n_chunks, n_partials, n_lookup_terms, n_lookup_polys, total_folds;
+    bool has_lookup;
+    size_t N, cap, nz, n_pub, nq, query_words, sched_len, final_degree;
+    unsigned widths[4], fri_depth[32];
+    uint32_t sched[32], new_pow;
+    u64 pow_challenge;
+    const u64 *pub, *wit_cap, *s2_cap, *q_cap, *vz_w, *vzo_w, *v0_w, *fri_caps, *fm0, *fm1, *queries;
+};
+struct Challenges { e2 beta, gamma, lbeta, lgamma, alpha, z; };
+// The values the proof claims at z, z * omega and 0, split by kind (verifier.rs:1150-1206); the pointers go into vz.
+struct Openings {
+    std::vector<e2> vz, v0;
+    e2 z_at_zo, z_at_z;
+    const e2 *var_z, *wit_z, *con_z, *sig_z, *part_z, *mult_z, *A_z, *B_z, *tab_z, *qch_z;
+};
+// What the transcript yields after the quotient identity: the DEEP and FRI challenges and the query indices.
+struct Draw {
+    e2 cch = ZERO2;
+    std::vector<u64> fri_ch;    // [sched_len][2]
+    std::vector<u64> indices;   // [nq] drawn, then [nq] stored: the proof's claim
+    int first_mismatch = -1;
+};
+// The DEEP sources in opening order as the kernel reads them (VerifyDeepArgs: terms, sets), and the leaf offsets they rest on.
+struct DeepTables {
+    uint32_t leaf_off[4] = {};
+    std::vector<u64> term_words, set_words;
+    size_t n_sets = 0;
+};
+
+e2 challenge2(bj::host::Transcript &t) {
+    const u64 a = t.challenge(), b = t.challenge();
+    return e2{gl::canon(a), gl::canon(b)};
+}
+
+// shape: every count is the key's before it sizes anything
+bool parse_proof(const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, Prepared *R, ProofView *P) {
+    bj_verify_report *out = &R->report;
+    const unsigned V = P->V = K->V, Wc = P->Wc = K->Wc, nC = P->nC = K->nC, q = P->q = K->q;
+    const unsigned log_n = P->log_n = K->log_n, log_fri = P->log_fri = K->log_fri, LOGN = P->LOGN = log_n + log_fri;
+    const size_t n = (size_t)1 << log_n, N = P->N = n << log_fri, cap = P->cap = K->cap_size;
+    const bool has_lookup = P->has_lookup = K->lookup_reps > 0;
+    P->n_chunks = (V + q - 1) / q;
+    const unsigned n_partials = P->n_partials = P->n_chunks - 1;
+    const unsigned n_lookup_terms = P->n_lookup_terms = has_lookup ? K->lookup_reps + 1 : 0;
+    const unsigned n_lookup_polys = P->n_lookup_polys = has_lookup ? K->lookup_reps + 2 + K->lookup_w + 1 : 0;
+    const size_t nz = P->nz = (size_t)V + Wc + nC + V + 1 + n_partials + n_lookup_polys + q;
     const unsigned widths[4] = {V + Wc + (has_lookup ? 1u : 0u), 2 * (1 + n_partials) + (has_lookup ? 2 * (K->lookup_reps + 1) : 0u), 2 * q,
                                 V + nC + (has_lookup ? K->lookup_w + 1 : 0u)};
-    uint32_t sched[32], new_pow = 0;
+    std::memcpy(P->widths, widths, sizeof widths);
+    uint32_t *sched = P->sched;
     size_t num_queries = 0, sched_len = 0, final_degree = 0;
-    if (bj_fri_schedule(K->security, cap, K->pow_bits, log_fri, log_n, &new_pow, &num_queries, sched, &sched_len, &final_degree) || sched_len > 32)
-        return R->refuse(BJ_ERR_INVALID_ARG, "bj_verify: compute_fri_schedule failed for the key's config");
-    if (N < cap || LOGN > 32) return verdict(out, BJ_VERIFY_SHAPE);
-    const unsigned depth = bj::log2_exact(N / cap);
-    if (!W || n_words < 19 || W[0] != 0x424A5046ULL || W[1] != 2) return verdict(out, BJ_VERIFY_SHAPE);
-    const size_t n_pub = K->pub_cols.size();
+    if (bj_fri_schedule(K->security, cap, K->pow_bits, log_fri, log_n, &P->new_pow, &num_queries, sched, &sched_len, &final_degree) || sched_len > 32) {
+        R->refuse(BJ_ERR_INVALID_ARG, "bj_verify: compute_fri_schedule failed for the key's config");
+        return false;
+    }
+    P->sched_len = sched_len;
+    P->final_degree = final_degree;
+    auto shape = [&]() { verdict(out, BJ_VERIFY_SHAPE); return false; };
+    if (N < cap || LOGN > 32) return shape();
+    const unsigned depth = P->depth = bj::log2_exact(N / cap);
+    if (!W || n_words < 19 || W[0] != 0x424A5046ULL || W[1] != 2) return shape();
+    const size_t n_pub = P->n_pub = K->pub_cols.size();
     const u64 nq64 = W[9];
     const bool partial = (flags & BJ_VERIFY_PARTIAL_QUERIES) != 0;
     if (W[2] != n_pub || W[3] != cap || W[4] != nz || W[5] != 1 || W[6] != n_lookup_terms || W[7] != sched_len || W[8] != final_degree ||
         !(nq64 == num_queries || (partial && nq64 > 0 && nq64 < num_queries)) || W[10] != widths[0] || W[11] != widths[1] ||
         W[12] != widths[2] || W[13] != widths[3] || W[14] != depth || W[15] != log_n || W[16] != K->fri_lde || W[17] != K->pow_bits)
-        return verdict(out, BJ_VERIFY_SHAPE);
-    const size_t nq = (size_t)nq64;
-    unsigned fri_depth[32], total_folds = 0;
+        return shape();
+    const size_t nq = P->nq = (size_t)nq64;
     size_t query_words = 1;
     for (int o = 0; o < 4; o++) query_words += widths[o] + (size_t)depth * 4;
     {
         size_t ln = N;
         for (size_t l = 0; l < sched_len; l++) {
             const unsigned k = sched[l];
-            if (k < 1 || k > 3 || (ln >> k) < cap) return verdict(out, BJ_VERIFY_SHAPE);   // a schedule the prover cannot emit
-            fri_depth[l] = bj::log2_exact((ln >> k) / cap);
-            query_words += ((size_t)2 << k) + (size_t)fri_depth[l] * 4;
+            if (k < 1 || k > 3 || (ln >> k) < cap) return shape();   // a schedule the prover cannot emit
+            P->fri_depth[l] = bj::log2_exact((ln >> k) / cap);
+            query_words += ((size_t)2 << k) + (size_t)P->fri_depth[l] * 4;
             ln >>= k;
-            total_folds += k;
+            P->total_folds += k;
         }
     }
+    P->query_words = query_words;
     const size_t fixed = 19 + sched_len + n_pub + 3 * cap * 4 + 2 * (nz + 1 + n_lookup_terms) + sched_len * cap * 4 + 2 * final_degree;
-    if (n_words != fixed + nq * query_words) return verdict(out, BJ_VERIFY_SHAPE);
-    const u64 pow_challenge = W[18];
+    if (n_words != fixed + nq * query_words) return shape();
+    P->pow_challenge = W[18];
     const u64 *p = W + 19;
     for (size_t l = 0; l < sched_len; l++)
-        if (p[l] != sched[l]) return verdict(out, BJ_VERIFY_SHAPE);
+        if (p[l] != sched[l]) return shape();
     p += sched_len;
-    const u64 *pub = p; p += n_pub;
-    const u64 *wit_cap = p; p += cap * 4;
-    const u64 *s2_cap = p; p += cap * 4;
-    const u64 *q_cap = p; p += cap * 4;
-    const u64 *vz_w = p; p += 2 * nz;
-    const u64 *vzo_w = p; p += 2;
-    const u64 *v0_w = p; p += 2 * (size_t)n_lookup_terms;
-    const u64 *fri_caps = p; p += sched_len * cap * 4;
-    const u64 *fm0 = p; p += final_degree;
-    const u64 *fm1 = p; p += final_degree;
-    const u64 *queries = p;
+    P->pub = p; p += n_pub;
+    P->wit_cap = p; p += cap * 4;
+    P->s2_cap = p; p += cap * 4;
+    P->q_cap = p; p += cap * 4;
+    P->vz_w = p; p += 2 * nz;
+    P->vzo_w = p; p += 2;
+    P->v0_w = p; p += 2 * (size_t)n_lookup_terms;
+    P->fri_caps = p; p += sched_len * cap * 4;
+    P->fm0 = p; p += final_degree;
+    P->fm1 = p; p += final_degree;
+    P->queries = p;
+    return true;
+}
 
-    // ---- transcript replay (verifier.rs:924-1076) ----
-    bj::host::Transcript t;
+// transcript replay up to the openings (verifier.rs:924-1076); `t` goes on to draw_challenges_and_indices
+Challenges replay_transcript(const bj_vk *K, const ProofView &P, bj::host::Transcript &t) {
+    Challenges C{};
     t.kind = (int)K->transcript;
-    auto challenge2 = [&]() {
-        const u64 a = t.challenge(), b = t.challenge();
-        return e2{gl::canon(a), gl::canon(b)};
-    };
     t.absorb_cap(K->cap.data(), K->cap.size());
-    t.absorb(pub, n_pub);
-    t.absorb_cap(wit_cap, cap * 4);
-    const e2 beta = challenge2(), gamma = challenge2();
-    e2 lbeta = ZERO2, lgamma = ZERO2;
-    if (has_lookup) {
-        lbeta = challenge2();
-        lgamma = challenge2();
+    t.absorb(P.pub, P.n_pub);
+    t.absorb_cap(P.wit_cap, P.cap * 4);
+    C.beta = challenge2(t);
+    C.gamma = challenge2(t);
+    if (P.has_lookup) {
+        C.lbeta = challenge2(t);
+        C.lgamma = challenge2(t);
     }
-    t.absorb_cap(s2_cap, cap * 4);
-    const e2 alpha = challenge2();
-    t.absorb_cap(q_cap, cap * 4);
-    const e2 z = challenge2();
-    t.absorb(vz_w, 2 * nz);
-    t.absorb(vzo_w, 2);
-    t.absorb(v0_w, 2 * (size_t)n_lookup_terms);
+    t.absorb_cap(P.s2_cap, P.cap * 4);
+    C.alpha = challenge2(t);
+    t.absorb_cap(P.q_cap, P.cap * 4);
+    C.z = challenge2(t);
+    t.absorb(P.vz_w, 2 * P.nz);
+    t.absorb(P.vzo_w, 2);
+    t.absorb(P.v0_w, 2 * (size_t)P.n_lookup_terms);
+    return C;
+}
 
-    // ---- the openings, split (verifier.rs:1150-1206) ----
-    std::vector<e2> vz(nz), v0(n_lookup_terms);
-    for (size_t i = 0; i < nz; i++) vz[i] = e2c(vz_w + 2 * i);
-    for (size_t i = 0; i < n_lookup_terms; i++) v0[i] = e2c(v0_w + 2 * i);
-    const e2 z_at_zo = e2c(vzo_w);
-    const e2 *var_z = vz.data(), *wit_z = var_z + V, *con_z = wit_z + Wc, *sig_z = con_z + nC;
-    const e2 z_at_z = sig_z[V];
-    const e2 *part_z = sig_z + V + 1, *lk = part_z + n_partials;
-    const e2 *mult_z = lk, *A_z = lk + (has_lookup ? 1 : 0), *B_z = A_z + K->lookup_reps, *tab_z = B_z + (has_lookup ? 1 : 0);
-    const e2 *qch_z = lk + n_lookup_polys;
+// the openings, split (verifier.rs:1150-1206)
+void split_openings(const bj_vk *K, const ProofView &P, Openings *O) {
+    O->vz.resize(P.nz);
+    O->v0.resize(P.n_lookup_terms);
+    for (size_t i = 0; i < P.nz; i++) O->vz[i] = e2c(P.vz_w + 2 * i);
+    for (size_t i = 0; i < P.n_lookup_terms; i++) O->v0[i] = e2c(P.v0_w + 2 * i);
+    O->z_at_zo = e2c(P.vzo_w);
+    O->var_z = O->vz.data();
+    O->wit_z = O->var_z + P.V;
+    O->con_z = O->wit_z + P.Wc;
+    O->sig_z = O->con_z + P.nC;
+    O->z_at_z = O->sig_z[P.V];
+    O->part_z = O->sig_z + P.V + 1;
+    const e2 *lk = O->part_z + P.n_partials;
+    O->mult_z = lk;
+    O->A_z = lk + (P.has_lookup ? 1 : 0);
+    O->B_z = O->A_z + K->lookup_reps;
+    O->tab_z = O->B_z + (P.has_lookup ? 1 : 0);
+    O->qch_z = lk + P.n_lookup_polys;
+}
 
-    // ---- challenge powers: lookup | specialized | general | L1 | chunks (prover.rs:599-625, verifier.rs:1000-1060) ----
-    size_t n_gate_terms = 0, n_spec_terms = 0;
-    for (const auto &g : K->gates) n_gate_terms += (size_t)g.reps * g.num_terms;
-    for (const auto &g : K->spec) n_spec_terms += (size_t)g.reps * g.num_terms;
-    const size_t total_terms = n_lookup_terms + n_spec_terms + n_gate_terms + 1 + n_chunks;
-    std::vector<e2> alphas(total_terms);
-    alphas[0] = ONE2;
-    for (size_t i = 1; i < total_terms; i++) alphas[i] = gl::e2_mul(alphas[i - 1], alpha);
-    const e2 *a_lookup = alphas.data(), *a_spec = a_lookup + n_lookup_terms, *a_gates = a_spec + n_spec_terms, *a_rest = a_gates + n_gate_terms;
-
+// the lookup sub-arguments at z (verifier.rs:1397-1470)
+e2 lookup_terms(const bj_vk *K, const Challenges &C, const Openings &O, const e2 *a_lookup) {
     e2 T = ZERO2;
-    if (has_lookup) {
-        e2 sa = ZERO2;   // the sum of the A_i(0) is B(0) (verifier.rs:1236-1256)
-        for (unsigned i = 0; i < K->lookup_reps; i++) sa = gl::e2_add(sa, v0[i]);
-        if (!eq2(sa, v0[K->lookup_reps])) return verdict(out, BJ_VERIFY_LOOKUP_SUM);
-        std::vector<e2> gp(K->lookup_w + 1);
-        gp[0] = ONE2;
-        for (unsigned j = 1; j <= K->lookup_w; j++) gp[j] = gl::e2_mul(gp[j - 1], lgamma);
-        for (unsigned i = 0; i < K->lookup_reps; i++) {   // verifier.rs:1397-1470
-            e2 d = lbeta;
-            for (unsigned j = 0; j < K->lookup_cps; j++) d = gl::e2_add(d, gl::e2_mul(gp[j], var_z[K->num_gp_vars + i * K->lookup_cps + j]));
-            if (!K->tid_var) d = gl::e2_add(d, gl::e2_mul(gp[K->lookup_w], con_z[K->table_id_col]));
-            T = gl::e2_add(T, gl::e2_mul(gl::e2_sub(gl::e2_mul(A_z[i], d), ONE2), a_lookup[i]));
-        }
-        e2 d = lbeta;
-        for (unsigned j = 0; j <= K->lookup_w; j++) d = gl::e2_add(d, gl::e2_mul(gp[j], tab_z[j]));
-        T = gl::e2_add(T, gl::e2_mul(gl::e2_sub(gl::e2_mul(B_z[0], d), mult_z[0]), a_lookup[K->lookup_reps]));
+    std::vector<e2> gp(K->lookup_w + 1);
+    gp[0] = ONE2;
+    for (unsigned j = 1; j <= K->lookup_w; j++) gp[j] = gl::e2_mul(gp[j - 1], C.lgamma);
+    for (unsigned i = 0; i < K->lookup_reps; i++) {
+        e2 d = C.lbeta;
+        for (unsigned j = 0; j < K->lookup_cps; j++) d = gl::e2_add(d, gl::e2_mul(gp[j], O.var_z[K->num_gp_vars + i * K->lookup_cps + j]));
+        if (!K->tid_var) d = gl::e2_add(d, gl::e2_mul(gp[K->lookup_w], O.con_z[K->table_id_col]));
+        T = gl::e2_add(T, gl::e2_mul(gl::e2_sub(gl::e2_mul(O.A_z[i], d), ONE2), a_lookup[i]));
     }
+    e2 d = C.lbeta;
+    for (unsigned j = 0; j <= K->lookup_w; j++) d = gl::e2_add(d, gl::e2_mul(gp[j], O.tab_z[j]));
+    return gl::e2_add(T, gl::e2_mul(gl::e2_sub(gl::e2_mul(O.B_z[0], d), O.mult_z[0]), a_lookup[K->lookup_reps]));
+}
+
+// gates over specialized columns: no selector, their own columns (verifier.rs:1560-1638)
+e2 specialized_gate_terms(const bj_vk *K, const Openings &O, const e2 *a_spec, bool *well_formed) {
+    e2 T = ZERO2;
     std::vector<e2> slots, terms;
-    bool well_formed = true;
-    {   // gates over specialized columns: no selector, their own columns (verifier.rs:1560-1638)
-        size_t off = 0;
-        for (const auto &g : K->spec) {
-            terms.assign(g.num_terms ? g.num_terms : 1, ZERO2);
-            for (unsigned r = 0; r < g.reps; r++) {
-                const size_t vb = g.first_col + (size_t)r * g.var_stride, cb = g.first_const + (size_t)r * g.const_stride;
-                well_formed = program_terms(g.prog, var_z + vb, g.var_stride, con_z + cb, g.const_stride, nullptr, 0, slots, terms.data(), g.num_terms) && well_formed;
-                for (unsigned k = 0; k < g.num_terms; k++) T = gl::e2_add(T, gl::e2_mul(terms[k], a_spec[off++]));
-            }
+    size_t off = 0;
+    for (const auto &g : K->spec) {
+        terms.assign(g.num_terms ? g.num_terms : 1, ZERO2);
+        for (unsigned r = 0; r < g.reps; r++) {
+            const size_t vb = g.first_col + (size_t)r * g.var_stride, cb = g.first_const + (size_t)r * g.const_stride;
+            *well_formed = program_terms(g.prog, O.var_z + vb, g.var_stride, O.con_z + cb, g.const_stride, nullptr, 0, slots, terms.data(), g.num_terms) && *well_formed;
+            for (unsigned k = 0; k < g.num_terms; k++) T = gl::e2_add(T, gl::e2_mul(terms[k], a_spec[off++]));
         }
     }
-    {   // gates over general-purpose columns under their selectors (verifier.rs:1640-1720)
-        size_t off = 0;
-        for (const auto &g : K->gates) {
-            if (!g.num_terms) continue;
-            e2 sel = ONE2;
-            for (unsigned b = 0; b < g.path_len; b++) sel = gl::e2_mul(sel, g.path[b] ? con_z[b] : gl::e2_sub(ONE2, con_z[b]));
-            const unsigned d = g.path_len;
-            e2 acc = ZERO2;
-            terms.assign(g.num_terms, ZERO2);
-            for (unsigned r = 0; r < g.reps; r++) {
-                const size_t vb = (size_t)r * g.var_stride, cb = d + (size_t)r * g.const_stride;
-                const e2 *v = var_z + vb;
-                switch (g.kind) {
-                    case BJ_GATE_CONSTANT_ALLOCATOR: terms[0] = gl::e2_sub(v[0], con_z[cb]); break;
-                    case BJ_GATE_FMA_NO_CONSTANT:
-                        terms[0] = gl::e2_sub(gl::e2_add(gl::e2_mul(v[2], con_z[d + 1]), gl::e2_mul(con_z[d], gl::e2_mul(v[0], v[1]))), v[3]);
-                        break;
-                    case BJ_GATE_REDUCTION4: {
-                        e2 s = ZERO2;
-                        for (int k = 0; k < 4; k++) s = gl::e2_add(s, gl::e2_mul(v[k], con_z[d + k]));
-                        terms[0] = gl::e2_sub(s, v[4]);
+    return T;
+}
+
+// gates over general-purpose columns under their selectors (verifier.rs:1640-1720)
+e2 general_gate_terms(const bj_vk *K, const ProofView &P, const Openings &O, const e2 *a_gates, bool *well_formed) {
+    const unsigned nC = P.nC, Wc = P.Wc;
+    const e2 *var_z = O.var_z, *wit_z = O.wit_z, *con_z = O.con_z;
+    e2 T = ZERO2;
+    std::vector<e2> slots, terms;
+    size_t off = 0;
+    for (const auto &g : K->gates) {
+        if (!g.num_terms) continue;
+        e2 sel = ONE2;
+        for (unsigned b = 0; b < g.path_len; b++) sel = gl::e2_mul(sel, g.path[b] ? con_z[b] : gl::e2_sub(ONE2, con_z[b]));
+        const unsigned d = g.path_len;
+        e2 acc = ZERO2;
+        terms.assign(g.num_terms, ZERO2);
+        for (unsigned r = 0; r < g.reps; r++) {
+            const size_t vb = (size_t)r * g.var_stride, cb = d + (size_t)r * g.const_stride;
+            const e2 *v = var_z + vb;
+            switch (g.kind) {
+                case BJ_GATE_CONSTANT_ALLOCATOR: terms[0] = gl::e2_sub(v[0], con_z[cb]); break;
+                case BJ_GATE_FMA_NO_CONSTANT:
+                    terms[0] = gl::e2_sub(gl::e2_add(gl::e2_mul(v[2], con_z[d + 1]), gl::e2_mul(con_z[d], gl::e2_mul(v[0], v[1]))), v[3]);
+                    break;
+                case BJ_GATE_REDUCTION4: {
+                    e2 s = ZERO2;
+                    for (int k = 0; k < 4; k++) s = gl::e2_add(s, gl::e2_mul(v[k], con_z[d + k]));
+                    terms[0] = gl::e2_sub(s, v[4]);
+                    break;
+                }
+                case BJ_GATE_POSEIDON2_FLATTENED: poseidon2_flattened_terms(v, terms.data()); break;
+                case BJ_GATE_POSEIDON_FLATTENED: poseidon1_flattened_terms(v, terms.data()); break;
+                default:   // BJ_GATE_PROGRAM
+                    if (vb > K->num_gp_vars || cb > nC || (size_t)r * g.wit_stride > Wc) {
+                        *well_formed = false;
                         break;
                     }
-                    case BJ_GATE_POSEIDON2_FLATTENED: poseidon2_flattened_terms(v, terms.data()); break;
-                    case BJ_GATE_POSEIDON_FLATTENED: poseidon1_flattened_terms(v, terms.data()); break;
-                    default:   // BJ_GATE_PROGRAM
-                        if (vb > K->num_gp_vars || cb > nC || (size_t)r * g.wit_stride > Wc) {
-                            well_formed = false;
-                            break;
-                        }
-                        well_formed = program_terms(g.prog, v, K->num_gp_vars - vb, con_z + cb, nC - cb, wit_z + (size_t)r * g.wit_stride,
-                                                    Wc - (size_t)r * g.wit_stride, slots, terms.data(), g.num_terms) && well_formed;
-                        break;
-                }
-                for (unsigned k = 0; k < g.num_terms; k++) acc = gl::e2_add(acc, gl::e2_mul(terms[k], a_gates[off++]));
+                    *well_formed = program_terms(g.prog, v, K->num_gp_vars - vb, con_z + cb, nC - cb, wit_z + (size_t)r * g.wit_stride,
+                                                 Wc - (size_t)r * g.wit_stride, slots, terms.data(), g.num_terms) && *well_formed;
+                    break;
             }
-            T = gl::e2_add(T, gl::e2_mul(acc, sel));
+            for (unsigned k = 0; k < g.num_terms; k++) acc = gl::e2_add(acc, gl::e2_mul(terms[k], a_gates[off++]));
         }
+        T = gl::e2_add(T, gl::e2_mul(acc, sel));
     }
-    // (z(x) - 1) L1 and the copy-permutation chain (verifier.rs:1722-1790)
-    e2 z_n = z;
-    for (unsigned i = 0; i < log_n; i++) z_n = gl::e2_sqr(z_n);
-    const e2 vanishing = gl::e2_sub(z_n, ONE2);
+    return T;
+}
+
+// (z(x) - 1) L1 and the copy-permutation chain (verifier.rs:1722-1790); a_rest: the power of L1, then one per chunk
+e2 copy_permutation_terms(const bj_vk *K, const ProofView &P, const Challenges &C, const Openings &O, e2 vanishing, const e2 *a_rest) {
+    const e2 z = C.z, beta = C.beta, gamma = C.gamma;
     const e2 l1 = gl::e2_mul(vanishing, gl::e2_inv(gl::e2_sub(z, ONE2)));
-    T = gl::e2_add(T, gl::e2_mul(gl::e2_mul(gl::e2_sub(z_at_z, ONE2), l1), a_rest[0]));
-    for (unsigned j = 0; j < n_chunks; j++) {
-        e2 lhs = j + 1 < n_chunks ? part_z[j] : z_at_zo, rhs = j ? part_z[j - 1] : z_at_z;
-        for (unsigned c = j * q; c < (j + 1) * q && c < V; c++) {
-            lhs = gl::e2_mul(lhs, gl::e2_add(gl::e2_add(gl::e2_mul(sig_z[c], beta), var_z[c]), gamma));
-            rhs = gl::e2_mul(rhs, gl::e2_add(gl::e2_add(gl::e2_mul(gl::e2_mul_base(z, gl::canon(K->non_residues[c])), beta), var_z[c]), gamma));
+    e2 T = gl::e2_mul(gl::e2_mul(gl::e2_sub(O.z_at_z, ONE2), l1), a_rest[0]);
+    for (unsigned j = 0; j < P.n_chunks; j++) {
+        e2 lhs = j + 1 < P.n_chunks ? O.part_z[j] : O.z_at_zo, rhs = j ? O.part_z[j - 1] : O.z_at_z;
+        for (unsigned c = j * P.q; c < (j + 1) * P.q && c < P.V; c++) {
+            lhs = gl::e2_mul(lhs, gl::e2_add(gl::e2_add(gl::e2_mul(O.sig_z[c], beta), O.var_z[c]), gamma));
+            rhs = gl::e2_mul(rhs, gl::e2_add(gl::e2_add(gl::e2_mul(gl::e2_mul_base(z, gl::canon(K->non_residues[c])), beta), O.var_z[c]), gamma));
         }
         T = gl::e2_add(T, gl::e2_mul(gl::e2_sub(lhs, rhs), a_rest[1 + j]));
     }
+    return T;
+}
+
+// The lookup sum and the quotient identity at z (verifier.rs:1090-1810): BJ_VERIFY_OK, or the stage that fails.  Challenge
+// powers in the order lookup | specialized | general | L1 | chunks (prover.rs:599-625, verifier.rs:1000-1060).
+uint32_t quotient_identity(const bj_vk *K, const ProofView &P, const Challenges &C, const Openings &O) {
+    size_t n_gate_terms = 0, n_spec_terms = 0;
+    for (const auto &g : K->gates) n_gate_terms += (size_t)g.reps * g.num_terms;
+    for (const auto &g : K->spec) n_spec_terms += (size_t)g.reps * g.num_terms;
+    const size_t total_terms = P.n_lookup_terms + n_spec_terms + n_gate_terms + 1 + P.n_chunks;
+    std::vector<e2> alphas(total_terms);
+    alphas[0] = ONE2;
+    for (size_t i = 1; i < total_terms; i++) alphas[i] = gl::e2_mul(alphas[i - 1], C.alpha);
+    const e2 *a_lookup = alphas.data(), *a_spec = a_lookup + P.n_lookup_terms, *a_gates = a_spec + n_spec_terms, *a_rest = a_gates + n_gate_terms;
+
+    e2 T = ZERO2;
+    if (P.has_lookup) {
+        e2 sa = ZERO2;   // the sum of the A_i(0) is B(0) (verifier.rs:1236-1256)
+        for (unsigned i = 0; i < K->lookup_reps; i++) sa = gl::e2_add(sa, O.v0[i]);
+        if (!eq2(sa, O.v0[K->lookup_reps])) return BJ_VERIFY_LOOKUP_SUM;
+        T = lookup_terms(K, C, O, a_lookup);
+    }
+    bool well_formed = true;
+    T = gl::e2_add(T, specialized_gate_terms(K, O, a_spec, &well_formed));
+    T = gl::e2_add(T, general_gate_terms(K, P, O, a_gates, &well_formed));
+    e2 z_n = C.z;
+    for (unsigned i = 0; i < P.log_n; i++) z_n = gl::e2_sqr(z_n);
+    const e2 vanishing = gl::e2_sub(z_n, ONE2);
+    T = gl::e2_add(T, copy_permutation_terms(K, P, C, O, vanishing, a_rest));
     e2 t_chunks = ZERO2, pw = ONE2;
-    for (unsigned i = 0; i < q; i++) {
-        t_chunks = gl::e2_add(t_chunks, gl::e2_mul(qch_z[i], pw));
+    for (unsigned i = 0; i < P.q; i++) {
+        t_chunks = gl::e2_add(t_chunks, gl::e2_mul(O.qch_z[i], pw));
         pw = gl::e2_mul(pw, z_n);
     }
-    if (!well_formed || !eq2(T, gl::e2_mul(t_chunks, vanishing))) return verdict(out, BJ_VERIFY_QUOTIENT);
+    return well_formed && eq2(T, gl::e2_mul(t_chunks, vanishing)) ? BJ_VERIFY_OK : BJ_VERIFY_QUOTIENT;
+}
 
-    // ---- DEEP / FRI challenges, proof of work (verifier.rs:1819-1983) ----
-    const e2 cch = challenge2();
-    std::vector<u64> fri_ch(2 * sched_len);
-    for (size_t l = 0; l < sched_len; l++) {
-        t.absorb_cap(fri_caps + l * cap * 4, cap * 4);
-        const e2 ch = challenge2();
-        fri_ch[2 * l] = ch.c0;
-        fri_ch[2 * l + 1] = ch.c1;
+// DEEP / FRI challenges, proof of work (verifier.rs:1819-1983), then the query indices: drawn in order; the stored words are the
+// proof's claim
+bool draw_challenges_and_indices(const bj_vk *K, const ProofView &P, bj::host::Transcript &t, Prepared *R, Draw *D) {
+    auto stop = [&](uint32_t stage, size_t query) { verdict(&R->report, stage, (uint32_t)query, 0, (uint32_t)query); return false; };
+    D->cch = challenge2(t);
+    D->fri_ch.resize(2 * P.sched_len);
+    for (size_t l = 0; l < P.sched_len; l++) {
+        t.absorb_cap(P.fri_caps + l * P.cap * 4, P.cap * 4);
+        const e2 ch = challenge2(t);
+        D->fri_ch[2 * l] = ch.c0;
+        D->fri_ch[2 * l + 1] = ch.c1;
     }
-    t.absorb(fm0, final_degree);
-    t.absorb(fm1, final_degree);
-    if (new_pow) {
+    t.absorb(P.fm0, P.final_degree);
+    t.absorb(P.fm1, P.final_degree);
+    if (P.new_pow) {
         u64 seed[5];
         for (int i = 0; i < 5; i++) seed[i] = gl::canon(t.challenge());
-        if (!pow_holds(K->pow_runner, seed, new_pow, pow_challenge)) return verdict(out, BJ_VERIFY_POW);
-        const u64 lh[2] = {pow_challenge & 0xFFFFFFFFULL, pow_challenge >> 32};
+        if (!pow_holds(K->pow_runner, seed, P.new_pow, P.pow_challenge)) return stop(BJ_VERIFY_POW, 0);
+        const u64 lh[2] = {P.pow_challenge & 0xFFFFFFFFULL, P.pow_challenge >> 32};
         t.absorb(lh, 2);
     }
-    // ---- query indices: drawn in order; the stored words are the proof's claim ----
-    std::vector<u64> indices(2 * nq);
+    const size_t nq = P.nq;
+    D->indices.resize(2 * nq);
     bj::host::BoolsBuffer bools;
-    bools.max_needed = LOGN;
-    int first_mismatch = -1;
+    bools.max_needed = P.LOGN;
     for (size_t i = 0; i < nq; i++) {
-        indices[i] = bools.query_index(t, log_n, log_fri);
-        const u64 stored = queries[i * query_words];
-        if (stored >= N) return verdict(out, BJ_VERIFY_SHAPE, (uint32_t)i, 0, (uint32_t)i);   // not an index of the domain at all
-        indices[nq + i] = stored;
-        if (stored != indices[i] && first_mismatch < 0) first_mismatch = (int)i;
+        D->indices[i] = bools.query_index(t, P.log_n, P.log_fri);
+        const u64 stored = P.queries[i * P.query_words];
+        if (stored >= P.N) return stop(BJ_VERIFY_SHAPE, i);   // not an index of the domain at all
+        D->indices[nq + i] = stored;
+        if (stored != D->indices[i] && D->first_mismatch < 0) D->first_mismatch = (int)i;
     }
+    return true;
+}
 
-    // ---- the DEEP sources in opening order (verifier.rs:2233-2290) as words of a query's block ----
-    uint32_t leaf_off[4];
+// the DEEP sources in opening order (verifier.rs:2233-2290) as words of a query's block
+bool deep_tables(const bj_vk *K, const ProofView &P, const Challenges &C, const Openings &O, const Draw &D, Prepared *R, DeepTables *DT) {
+    const unsigned V = P.V, Wc = P.Wc, nC = P.nC, n_partials = P.n_partials, n_lookup_terms = P.n_lookup_terms, log_n = P.log_n;
+    const size_t nz = P.nz, n_pub = P.n_pub;
+    const bool has_lookup = P.has_lookup;
+    uint32_t *leaf_off = DT->leaf_off;
     {
         uint32_t o = 1;
         for (int k = 0; k < 4; k++) {
             leaf_off[k] = o;
-            o += widths[k] + depth * 4;
+            o += P.widths[k] + P.depth * 4;
         }
     }
     const uint32_t oW = leaf_off[0], oS2 = leaf_off[1], oQ = leaf_off[2], oSU = leaf_off[3];
@@ -679,8 +752,11 @@ int prepare(const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, Prepar
         ext_run(oLk, K->lookup_reps + 1);     // A_i, B
         base_run(oSU + V + nC, K->lookup_w + 1);
     }
-    ext_run(oQ, q);
-    if (src.size() != nz) return R->refuse(BJ_ERR_HIP, "bj_verify: internal error: %zu DEEP sources for %zu openings", src.size(), nz);
+    ext_run(oQ, P.q);
+    if (src.size() != nz) {
+        R->refuse(BJ_ERR_HIP, "bj_verify: internal error: %zu DEEP sources for %zu openings", src.size(), nz);
+        return false;
+    }
     struct PubSet { u64 at; std::vector<uint32_t> cols; std::vector<u64> vals; };
     std::vector<PubSet> pubs;
     {
@@ -692,92 +768,113 @@ int prepare(const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, Prepar
                 if (pubs[pos].at == at) break;
             if (pos == pubs.size()) pubs.push_back({at, {}, {}});
             pubs[pos].cols.push_back(K->pub_cols[i]);
-            pubs[pos].vals.push_back(gl::canon(pub[i]));
+            pubs[pos].vals.push_back(gl::canon(P.pub[i]));
         }
     }
-    const size_t n_sets = 2 + (has_lookup ? 1 : 0) + pubs.size();
-    size_t n_terms = nz + 1 + n_lookup_terms + n_pub;
-    std::vector<u64> term_words(3 * n_terms), set_words(6 * n_sets);
-    {
-        e2 chp = ONE2;
-        size_t tno = 0, sno = 0;
-        auto open_set = [&](e2 at) {
-            u64 *S = set_words.data() + 6 * sno;
-            S[0] = tno; S[2] = at.c0; S[3] = at.c1; S[4] = 0; S[5] = 0;
-        };
-        auto add_term = [&](Term s, e2 value) {
-            u64 *Tw = term_words.data() + 3 * tno++;
-            Tw[0] = (u64)s.o0 | ((u64)s.o1 << 32);
-            Tw[1] = chp.c0; Tw[2] = chp.c1;
-            u64 *S = set_words.data() + 6 * sno;
-            const e2 c = gl::e2_add(e2{S[4], S[5]}, gl::e2_mul(chp, value));
-            S[4] = c.c0; S[5] = c.c1;
-            chp = gl::e2_mul(chp, cch);
-        };
-        auto close_set = [&]() { set_words[6 * sno++ + 1] = tno; };
-        open_set(z);
-        for (size_t i = 0; i < nz; i++) add_term(src[i], vz[i]);
+    const size_t n_sets = DT->n_sets = 2 + (has_lookup ? 1 : 0) + pubs.size();
+    const size_t n_terms = nz + 1 + n_lookup_terms + n_pub;
+    std::vector<u64> &term_words = DT->term_words, &set_words = DT->set_words;
+    term_words.assign(3 * n_terms, 0);
+    set_words.assign(6 * n_sets, 0);
+    e2 chp = ONE2;
+    size_t tno = 0, sno = 0;
+    auto open_set = [&](e2 at) {
+        u64 *S = set_words.data() + 6 * sno;
+        S[0] = tno; S[2] = at.c0; S[3] = at.c1; S[4] = 0; S[5] = 0;
+    };
+    auto add_term = [&](Term s, e2 value) {
+        u64 *Tw = term_words.data() + 3 * tno++;
+        Tw[0] = (u64)s.o0 | ((u64)s.o1 << 32);
+        Tw[1] = chp.c0; Tw[2] = chp.c1;
+        u64 *S = set_words.data() + 6 * sno;
+        const e2 c = gl::e2_add(e2{S[4], S[5]}, gl::e2_mul(chp, value));
+        S[4] = c.c0; S[5] = c.c1;
+        chp = gl::e2_mul(chp, D.cch);
+    };
+    auto close_set = [&]() { set_words[6 * sno++ + 1] = tno; };
+    open_set(C.z);
+    for (size_t i = 0; i < nz; i++) add_term(src[i], O.vz[i]);
+    close_set();
+    open_set(gl::e2_mul_base(C.z, gl::omega(log_n)));
+    add_term({oS2, oS2 + 1}, O.z_at_zo);
+    close_set();
+    if (has_lookup) {
+        open_set(ZERO2);
+        for (unsigned i = 0; i < n_lookup_terms; i++) add_term({oLk + 2 * i, oLk + 2 * i + 1}, O.v0[i]);
         close_set();
-        open_set(gl::e2_mul_base(z, gl::omega(log_n)));
-        add_term({oS2, oS2 + 1}, z_at_zo);
-        close_set();
-        if (has_lookup) {
-            open_set(ZERO2);
-            for (unsigned i = 0; i < n_lookup_terms; i++) add_term({oLk + 2 * i, oLk + 2 * i + 1}, v0[i]);
-            close_set();
-        }
-        for (const auto &ps : pubs) {
-            open_set(e2{ps.at, 0});
-            for (size_t i = 0; i < ps.cols.size(); i++) add_term({oW + ps.cols[i], NO_C1}, e2{ps.vals[i], 0});
-            close_set();
-        }
     }
+    for (const auto &ps : pubs) {
+        open_set(e2{ps.at, 0});
+        for (size_t i = 0; i < ps.cols.size(); i++) add_term({oW + ps.cols[i], NO_C1}, e2{ps.vals[i], 0});
+        close_set();
+    }
+    return true;
+}
 
-    // ---- what a judge needs: the geometry, and the tables in the block layout of verify_tables ----
-    const size_t n_oracles = 4 + sched_len, cap_words = cap * 4;
+// what the judge needs: the geometry, and the tables in the block layout of verify_tables
+void fill_device_tables(const bj_vk *K, const ProofView &P, const Draw &D, const DeepTables &DT, Prepared *R) {
+    const size_t sched_len = P.sched_len, final_degree = P.final_degree, nq = P.nq, n_oracles = 4 + sched_len, cap_words = P.cap * 4;
+    const unsigned depth = P.depth;
     Geometry &G = R->geo;
-    G.sizes.query_words = query_words;
+    G.sizes.query_words = P.query_words;
     G.sizes.n_oracles = n_oracles;
     G.sizes.cap_words = cap_words;
-    G.sizes.term_words = term_words.size();
-    G.sizes.set_words = set_words.size();
-    G.sizes.fri_words = fri_ch.size();
+    G.sizes.term_words = DT.term_words.size();
+    G.sizes.set_words = DT.set_words.size();
+    G.sizes.fri_words = D.fri_ch.size();
     G.sizes.final_degree = final_degree;
-    G.LOGN = LOGN;
-    G.n_sets = (unsigned)n_sets;
+    G.LOGN = P.LOGN;
+    G.n_sets = (unsigned)DT.n_sets;
     G.n_fri = (unsigned)sched_len;
-    G.total_folds = total_folds;
-    for (int o = 0; o < 4; o++) G.oracle[o] = bj::VerifyOracle{leaf_off[o], widths[o], depth, 0, (uint32_t)(o * cap_words)};
+    G.total_folds = P.total_folds;
+    for (int o = 0; o < 4; o++) G.oracle[o] = bj::VerifyOracle{DT.leaf_off[o], P.widths[o], depth, 0, (uint32_t)(o * cap_words)};
     {
-        uint32_t o = leaf_off[3] + widths[3] + depth * 4, shift = 0;
+        uint32_t o = DT.leaf_off[3] + P.widths[3] + depth * 4, shift = 0;
         for (size_t l = 0; l < sched_len; l++) {
-            shift += sched[l];
-            G.oracle[4 + l] = bj::VerifyOracle{o, 2u << sched[l], fri_depth[l], shift, (uint32_t)((4 + l) * cap_words)};
+            shift += P.sched[l];
+            G.oracle[4 + l] = bj::VerifyOracle{o, 2u << P.sched[l], P.fri_depth[l], shift, (uint32_t)((4 + l) * cap_words)};
             G.fri_off[l] = o;
-            G.sched[l] = (unsigned char)sched[l];
-            o += (2u << sched[l]) + fri_depth[l] * 4;
+            G.sched[l] = (unsigned char)P.sched[l];
+            o += (2u << P.sched[l]) + P.fri_depth[l] * 4;
         }
     }
     const bj::VerifyTables at = bj::verify_tables(G.sizes, nq);
     R->tables.assign(at.words, 0);
     u64 *s = R->tables.data();
-    std::memcpy(s + at.idx, indices.data(), indices.size() * 8);
-    std::memcpy(s + at.caps, wit_cap, cap_words * 8);
-    std::memcpy(s + at.caps + cap_words, s2_cap, cap_words * 8);
-    std::memcpy(s + at.caps + 2 * cap_words, q_cap, cap_words * 8);
+    std::memcpy(s + at.idx, D.indices.data(), D.indices.size() * 8);
+    std::memcpy(s + at.caps, P.wit_cap, cap_words * 8);
+    std::memcpy(s + at.caps + cap_words, P.s2_cap, cap_words * 8);
+    std::memcpy(s + at.caps + 2 * cap_words, P.q_cap, cap_words * 8);
     std::memcpy(s + at.caps + 3 * cap_words, K->cap.data(), cap_words * 8);
-    std::memcpy(s + at.caps + 4 * cap_words, fri_caps, sched_len * cap_words * 8);
-    std::memcpy(s + at.terms, term_words.data(), term_words.size() * 8);
-    std::memcpy(s + at.sets, set_words.data(), set_words.size() * 8);
-    std::memcpy(s + at.fri_ch, fri_ch.data(), fri_ch.size() * 8);
+    std::memcpy(s + at.caps + 4 * cap_words, P.fri_caps, sched_len * cap_words * 8);
+    std::memcpy(s + at.terms, DT.term_words.data(), DT.term_words.size() * 8);
+    std::memcpy(s + at.sets, DT.set_words.data(), DT.set_words.size() * 8);
+    std::memcpy(s + at.fri_ch, D.fri_ch.data(), D.fri_ch.size() * 8);
     for (size_t i = 0; i < final_degree; i++) {
-        s[at.fm + i] = gl::canon(fm0[i]);
-        s[at.fm + final_degree + i] = gl::canon(fm1[i]);
+        s[at.fm + i] = gl::canon(P.fm0[i]);
+        s[at.fm + final_degree + i] = gl::canon(P.fm1[i]);
     }
     R->nq = nq;
-    R->first_mismatch = first_mismatch;
-    R->queries = queries;
+    R->first_mismatch = D.first_mismatch;
+    R->queries = P.queries;
     R->device = true;
+}
+
+// The host half: the stages above, first verdict wins.  Touches no context and no global state: bj_verify_batch runs it on
+// several threads at once.  Returns R->rc.
+int prepare(const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, Prepared *R) {
+    ProofView P{};
+    if (!parse_proof(K, W, n_words, flags, R, &P)) return R->rc;
+    bj::host::Transcript t;
+    const Challenges C = replay_transcript(K, P, t);
+    Openings O{};
+    split_openings(K, P, &O);
+    if (const uint32_t stage = quotient_identity(K, P, C, O)) return verdict(&R->report, stage);
+    Draw D;
+    if (!draw_challenges_and_indices(K, P, t, R, &D)) return R->rc;
+    DeepTables DT;
+    if (!deep_tables(K, P, C, O, D, R, &DT)) return R->rc;
+    fill_device_tables(K, P, D, DT, R);
     return BJ_OK;
 }
 
@@ -835,131 +932,20 @@ bool device_verdict(bj_verify_report *out, size_t nq, int first_mismatch, const 
     return false;
 }
 
-int verify_impl(bj_ctx *ctx, const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, bj_verify_report *out) {
-    if (int rc = bj::bind(ctx)) return rc;
-    if (!K || !W || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: null argument");
-    if (flags & ~BJ_VERIFY_PARTIAL_QUERIES) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: unknown flags %#x", flags);
-    if (ctx->in_proof) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: a proof is running on this context");
-    std::memset(out, 0, sizeof(*out));
-    ctx->verify_timed = false;
-    Prepared R;
-    if (int rc = prepare(K, W, n_words, flags, &R)) return bj::fail(ctx, rc, "%s", R.err.c_str());
-    *out = R.report;
-    if (!R.device) return BJ_OK;
-
-    // ---- device: the query section once, the small tables behind it ----
-    const Geometry &G = R.geo;
-    const size_t nq = R.nq, n_oracles = G.sizes.n_oracles, query_words = G.sizes.query_words;
-    const bj::VerifyTables at = bj::verify_tables(G.sizes, nq);
-    size_t off = 0;
-    auto take = [&off](size_t words) {
-        const size_t at = off;
-        off += (words + 1) & ~(size_t)1;
-        return at;
-    };
-    const size_t o_q = take(nq * query_words), o_small = take(at.words);
-    const size_t o_st_open = take((n_oracles * nq + 1) / 2), o_st_deep = take((nq + 1) / 2);
-    if (int rc = bj::ensure_scratch(ctx, off)) return rc;
-    if (int rc = bj::ensure_twiddles(ctx, G.LOGN, true)) return rc;
-    u64 *D = ctx->d_scratch;
-    hipStream_t st = ctx->stream;
-    if (int rc = bj_memcpy_h2d(ctx, D + o_q, R.queries, nq * query_words * 8)) return rc;
-    if (int rc = bj_memcpy_h2d(ctx, D + o_small, R.tables.data(), at.words * 8)) return rc;
-    bj::VerifyOpenArgs OA{};
-    OA.queries = D + o_q;
-    OA.caps = D + o_small + at.caps;
-    OA.status = (uint32_t *)(D + o_st_open);
-    OA.n_queries = (uint32_t)nq;
-    OA.query_words = (uint32_t)query_words;
-    OA.n_oracles = (uint32_t)n_oracles;
-    std::memcpy(OA.oracle, G.oracle, sizeof OA.oracle);
-    VerifyDeepArgs DA{};
-    DA.queries = D + o_q;
-    DA.terms = D + o_small + at.terms;
-    DA.sets = D + o_small + at.sets;
-    DA.fri_ch = D + o_small + at.fri_ch;
-    DA.final0 = D + o_small + at.fm;
-    DA.final1 = D + o_small + at.fm + G.sizes.final_degree;
-    DA.status = (uint32_t *)(D + o_st_deep);
-    DA.n_queries = (uint32_t)nq;
-    DA.sh = deep_shared(ctx, G);
-    std::vector<uint32_t> st_open(n_oracles * nq), st_deep(nq);
-    // every chain of the proof judged at one set of indices
-    auto judge = [&](const u64 *d_indices, bool timed, Failure *f) -> int {
-        OA.indices = DA.indices = d_indices;
-        if (timed)
-            for (auto &e : ctx->verify_ev)
-                if (!e) BJ_HIP(ctx, hipEventCreate(&e));
-        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_ev[0], st));
-        bj::launch_verify_openings((int)K->hasher, OA, st);
-        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_ev[1], st));
-        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_ev[2], st));
-        hipLaunchKernelGGL(verify_deep_fri_kernel, dim3((unsigned)nq), dim3(64), 0, st, DA);
-        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_ev[3], st));
-        BJ_CHECK_LAUNCH(ctx);
-        if (int rc = bj_memcpy_d2h(ctx, st_open.data(), OA.status, st_open.size() * 4)) return rc;
-        if (int rc = bj_memcpy_d2h(ctx, st_deep.data(), DA.status, st_deep.size() * 4)) return rc;
-        if (timed) ctx->verify_timed = true;
-        *f = first_failure(st_open.data(), nq, st_deep.data(), nq, G.n_fri);
-        return BJ_OK;
-    };
-    Failure at_drawn, at_stored;
-    if (int rc = judge(D + o_small + at.idx, true, &at_drawn)) return rc;
-    if (!device_verdict(out, nq, R.first_mismatch, at_drawn, nullptr)) return BJ_OK;
-    if (int rc = judge(D + o_small + at.idx + nq, false, &at_stored)) return rc;
-    device_verdict(out, nq, R.first_mismatch, at_drawn, &at_stored);
-    return BJ_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// bj_verify_batch: N proofs of one key — prepare() on worker threads, one upload, one launch of each kernel over every chain
-// ---------------------------------------------------------------------------------------------------------------------------
-int verify_batch_impl(bj_ctx *ctx, const bj_vk *K, const u64 *const *proofs, const size_t *n_words, size_t n_proofs, unsigned flags,
-                      bj_verify_report *out) {
-    if (int rc = bj::bind(ctx)) return rc;
-    if (!K) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: null key");
-    if (flags & ~BJ_VERIFY_PARTIAL_QUERIES) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: unknown flags %#x", flags);
-    if (ctx->in_proof) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: a proof is running on this context");
-    if (!n_proofs) return BJ_OK;
-    if (!proofs || !n_words || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: null argument");
-    if (n_proofs > bj::VERIFY_BATCH_MAX_PROOFS)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: %zu proofs in one call, at most %zu", n_proofs, bj::VERIFY_BATCH_MAX_PROOFS);
-    for (size_t i = 0; i < n_proofs; i++)
-        if (!proofs[i] && n_words[i]) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: proof %zu is null with %zu words", i, n_words[i]);
-    std::memset(out, 0, n_proofs * sizeof(*out));
-    ctx->verify_batch_state = 0;
-
-    // ---- host: prepare() of every proof, proofs handed out in order to a bounded pool ----
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<Prepared> R(n_proofs);
-    {
-        const unsigned limit = bj::env().verify_threads;
-        const size_t n_workers = n_proofs < limit ? n_proofs : limit;
-        std::atomic<size_t> next{0};
-        auto work = [&]() {
-            for (size_t i; (i = next.fetch_add(1)) < n_proofs;) prepare(K, proofs[i], n_words[i], flags, &R[i]);
-        };
-        std::vector<std::thread> pool;
-        for (size_t w = 1; w < n_workers; w++) pool.emplace_back(work);
-        work();
-        for (auto &t : pool) t.join();
-    }
-    ctx->verify_batch_host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (size_t i = 0; i < n_proofs; i++)
-        if (R[i].rc) return bj::fail(ctx, R[i].rc, "%s (proof %zu of the batch)", R[i].err.c_str(), i);
+// The device half of bj_verify (n == 1) and bj_verify_batch: the proofs of R[0..n) that reached it (R[i].device) judged in one
+// launch of each kernel over every chain — plan (verify_batch_plan.h), scratch and twiddles before anything is uploaded, every
+// query section and ONE host block of table blocks and records up, two launches, the status words down, the verdicts into out[i];
+// then the same pair of launches over the proofs whose verdict needs the stored indices (device_verdict).  out[i] of a proof that
+// ended on the host is not touched.  T: the caller's timing state; T->state becomes 2 once the kernels have run.
+int judge(bj_ctx *ctx, const bj_vk *K, const Prepared *R, size_t n, bj_verify_report *out, VerifyTiming *T) {
     std::vector<size_t> dev;   // the proofs that reached the device phase, ascending
     std::vector<uint32_t> nqs;
-    for (size_t i = 0; i < n_proofs; i++) {
-        out[i] = R[i].report;
+    for (size_t i = 0; i < n; i++)
         if (R[i].device) {
             dev.push_back(i);
             nqs.push_back((uint32_t)R[i].nq);
         }
-    }
-    ctx->verify_batch_state = 1;
     if (dev.empty()) return BJ_OK;
-
-    // ---- device: every query section and every table block once, then two launches over every chain ----
     const Geometry &G = R[dev[0]].geo;   // the key's: the same in every proof
     const size_t n_oracles = G.sizes.n_oracles;
     bj::VerifyBatchPlan P;
@@ -969,38 +955,38 @@ int verify_batch_impl(bj_ctx *ctx, const bj_vk *K, const u64 *const *proofs, con
     if (int rc = bj::ensure_twiddles(ctx, G.LOGN, true)) return rc;
     u64 *D = ctx->d_scratch;
     hipStream_t st = ctx->stream;
-    for (auto &e : ctx->verify_batch_ev)
+    for (auto &e : T->ev)
         if (!e) BJ_HIP(ctx, hipEventCreate(&e));
     std::vector<u64> block(P.host_words);
     for (size_t k = 0; k < dev.size(); k++)
         std::memcpy(block.data() + (P.tables[k] - P.host_block), R[dev[k]].tables.data(), R[dev[k]].tables.size() * 8);
     std::memcpy(block.data() + (P.record_table - P.host_block), P.records.data(), P.records.size() * sizeof(bj::VerifyBatchProof));
     // stream-ordered copies out of the caller's buffers and `block`: all of them outlive the synchronisation below
-    BJ_HIP(ctx, hipEventRecord(ctx->verify_batch_ev[0], st));
+    BJ_HIP(ctx, hipEventRecord(T->ev[0], st));
     for (size_t k = 0; k < dev.size(); k++)
         BJ_HIP(ctx, hipMemcpyAsync(D + P.records[k].queries, R[dev[k]].queries, (size_t)nqs[k] * G.sizes.query_words * 8, hipMemcpyHostToDevice, st));
     BJ_HIP(ctx, hipMemcpyAsync(D + P.host_block, block.data(), block.size() * 8, hipMemcpyHostToDevice, st));
-    BJ_HIP(ctx, hipEventRecord(ctx->verify_batch_ev[1], st));
-    bj::VerifyOpenBatchArgs OA{};
+    BJ_HIP(ctx, hipEventRecord(T->ev[1], st));
+    bj::VerifyOpenArgs OA{};
     OA.base = D;
     OA.status = (uint32_t *)(D + P.status_open);
     OA.query_words = (uint32_t)G.sizes.query_words;
     OA.n_oracles = (uint32_t)n_oracles;
     std::memcpy(OA.oracle, G.oracle, sizeof OA.oracle);
-    VerifyDeepBatchArgs DA{};
+    VerifyDeepArgs DA{};
     DA.base = D;
     DA.status = (uint32_t *)(D + P.status_deep);
     DA.sh = deep_shared(ctx, G);
     std::vector<uint32_t> status;
-    // both kernels over `n` records at d_records, `chains` chains in all; the status words land in `status`: openings, then DEEP
-    auto launch = [&](const u64 *d_records, size_t n, uint32_t chains, bool timed) -> int {
+    // both kernels over `n_records` records at d_records, `chains` chains in all; the status words land in `status`: openings, then DEEP
+    auto launch = [&](const u64 *d_records, size_t n_records, uint32_t chains, bool timed) -> int {
         OA.proofs = DA.proofs = (const bj::VerifyBatchProof *)d_records;
-        OA.n_proofs = DA.n_proofs = (uint32_t)n;
+        OA.n_proofs = DA.n_proofs = (uint32_t)n_records;
         OA.n_chains = DA.n_chains = chains;
-        bj::launch_verify_openings_batch((int)K->hasher, OA, st);
-        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_batch_ev[2], st));
-        hipLaunchKernelGGL(verify_deep_fri_batch_kernel, dim3(chains), dim3(64), 0, st, DA);
-        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->verify_batch_ev[3], st));
+        bj::launch_verify_openings((int)K->hasher, OA, st);
+        if (timed) BJ_HIP(ctx, hipEventRecord(T->ev[2], st));
+        hipLaunchKernelGGL(verify_deep_fri_kernel, dim3(chains), dim3(64), 0, st, DA);
+        if (timed) BJ_HIP(ctx, hipEventRecord(T->ev[3], st));
         BJ_CHECK_LAUNCH(ctx);
         status.resize((n_oracles + 1) * (size_t)chains);
         BJ_HIP(ctx, hipMemcpyAsync(status.data(), OA.status, n_oracles * (size_t)chains * 4, hipMemcpyDeviceToHost, st));
@@ -1012,7 +998,7 @@ int verify_batch_impl(bj_ctx *ctx, const bj_vk *K, const u64 *const *proofs, con
         return first_failure(status.data() + r.chain0, chains, status.data() + n_oracles * (size_t)chains + r.chain0, r.nq, G.n_fri);
     };
     if (int rc = launch(D + P.record_table, dev.size(), P.n_chains, true)) return rc;
-    ctx->verify_batch_state = 2;
+    T->state = 2;
     std::vector<Failure> at_drawn(dev.size());
     std::vector<size_t> again;   // positions in dev whose verdict needs the stored indices
     for (size_t k = 0; k < dev.size(); k++) {
@@ -1030,6 +1016,20 @@ int verify_batch_impl(bj_ctx *ctx, const bj_vk *K, const u64 *const *proofs, con
         device_verdict(&out[dev[k]], nqs[k], R[dev[k]].first_mismatch, at_drawn[k], &at_stored);
     }
     return BJ_OK;
+}
+
+// bj_verify / bj_verify_proof: the batch path with one proof
+int verify_impl(bj_ctx *ctx, const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, bj_verify_report *out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!K || !W || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: null argument");
+    if (flags & ~BJ_VERIFY_PARTIAL_QUERIES) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: unknown flags %#x", flags);
+    if (ctx->in_proof) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify: a proof is running on this context");
+    std::memset(out, 0, sizeof(*out));
+    ctx->verify_timing.state = 0;
+    Prepared R;
+    if (int rc = prepare(K, W, n_words, flags, &R)) return bj::fail(ctx, rc, "%s", R.err.c_str());
+    *out = R.report;
+    return judge(ctx, K, &R, 1, out, &ctx->verify_timing);
 }
 
 void take_gate(bj_vk::Gate &g, const bj_gate_desc &G) {
@@ -1154,21 +1154,57 @@ int bj_verify_proof(bj_ctx *ctx, const bj_vk *vk, const bj_proof *proof, bj_veri
     return verify_impl(ctx, vk, w.data(), w.size(), 0, out);
 }
 
-int bj_verify_batch(bj_ctx *ctx, const bj_vk *vk, const uint64_t *const *proofs, const size_t *n_words, size_t n_proofs, unsigned flags,
+// bj_verify_batch: N proofs of one key — prepare() on worker threads, then the judge over those that got as far
+int bj_verify_batch(bj_ctx *ctx, const bj_vk *K, const uint64_t *const *proofs, const size_t *n_words, size_t n_proofs, unsigned flags,
                     bj_verify_report *out) {
-    return verify_batch_impl(ctx, vk, proofs, n_words, n_proofs, flags, out);
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!K) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: null key");
+    if (flags & ~BJ_VERIFY_PARTIAL_QUERIES) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: unknown flags %#x", flags);
+    if (ctx->in_proof) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: a proof is running on this context");
+    if (!n_proofs) return BJ_OK;
+    if (!proofs || !n_words || !out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: null argument");
+    if (n_proofs > bj::VERIFY_BATCH_MAX_PROOFS)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: %zu proofs in one call, at most %zu", n_proofs, bj::VERIFY_BATCH_MAX_PROOFS);
+    for (size_t i = 0; i < n_proofs; i++)
+        if (!proofs[i] && n_words[i]) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: proof %zu is null with %zu words", i, n_words[i]);
+    std::memset(out, 0, n_proofs * sizeof(*out));
+    VerifyTiming &T = ctx->verify_batch_timing;
+    T.state = 0;
+
+    // prepare() of every proof, proofs handed out in order to a bounded pool
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<Prepared> R(n_proofs);
+    {
+        const unsigned limit = bj::env().verify_threads;
+        const size_t n_workers = n_proofs < limit ? n_proofs : limit;
+        std::atomic<size_t> next{0};
+        auto work = [&]() {
+            for (size_t i; (i = next.fetch_add(1)) < n_proofs;) prepare(K, proofs[i], n_words[i], flags, &R[i]);
+        };
+        std::vector<std::thread> pool;
+        for (size_t w = 1; w < n_workers; w++) pool.emplace_back(work);
+        work();
+        for (auto &t : pool) t.join();
+    }
+    T.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (size_t i = 0; i < n_proofs; i++)
+        if (R[i].rc) return bj::fail(ctx, R[i].rc, "%s (proof %zu of the batch)", R[i].err.c_str(), i);
+    for (size_t i = 0; i < n_proofs; i++) out[i] = R[i].report;
+    T.state = 1;
+    return judge(ctx, K, R.data(), n_proofs, out, &T);
 }
 
 int bj_verify_batch_ms(bj_ctx *ctx, float *host_ms, float *upload_ms, float *openings_ms, float *deep_fri_ms) {
     if (int rc = bj::bind(ctx)) return rc;
-    if (!ctx->verify_batch_state) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch_ms: no bj_verify_batch has run on this context");
+    const VerifyTiming &T = ctx->verify_batch_timing;
+    if (!T.state) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch_ms: no bj_verify_batch has run on this context");
     float up = 0, a = 0, b = 0;
-    if (ctx->verify_batch_state == 2) {   // the batch reached its kernels (it synchronised behind them)
-        BJ_HIP(ctx, hipEventElapsedTime(&up, ctx->verify_batch_ev[0], ctx->verify_batch_ev[1]));
-        BJ_HIP(ctx, hipEventElapsedTime(&a, ctx->verify_batch_ev[1], ctx->verify_batch_ev[2]));
-        BJ_HIP(ctx, hipEventElapsedTime(&b, ctx->verify_batch_ev[2], ctx->verify_batch_ev[3]));
+    if (T.state == 2) {   // the batch reached its kernels (it synchronised behind them)
+        BJ_HIP(ctx, hipEventElapsedTime(&up, T.ev[0], T.ev[1]));
+        BJ_HIP(ctx, hipEventElapsedTime(&a, T.ev[1], T.ev[2]));
+        BJ_HIP(ctx, hipEventElapsedTime(&b, T.ev[2], T.ev[3]));
     }
-    if (host_ms) *host_ms = ctx->verify_batch_host_ms;
+    if (host_ms) *host_ms = T.host_ms;
     if (upload_ms) *upload_ms = up;
     if (openings_ms) *openings_ms = a;
     if (deep_fri_ms) *deep_fri_ms = b;
@@ -1177,11 +1213,11 @@ int bj_verify_batch_ms(bj_ctx *ctx, float *host_ms, float *upload_ms, float *ope
 
 int bj_verify_kernel_ms(bj_ctx *ctx, float *openings_ms, float *deep_fri_ms) {
     if (int rc = bj::bind(ctx)) return rc;
-    if (!ctx->verify_timed) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_kernel_ms: the last bj_verify on this context did not reach its kernels");
+    const VerifyTiming &T = ctx->verify_timing;
+    if (T.state != 2) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_kernel_ms: the last bj_verify on this context did not reach its kernels");
     float a = 0, b = 0;
-    BJ_HIP(ctx, hipEventSynchronize(ctx->verify_ev[3]));
-    BJ_HIP(ctx, hipEventElapsedTime(&a, ctx->verify_ev[0], ctx->verify_ev[1]));
-    BJ_HIP(ctx, hipEventElapsedTime(&b, ctx->verify_ev[2], ctx->verify_ev[3]));
+    BJ_HIP(ctx, hipEventElapsedTime(&a, T.ev[1], T.ev[2]));
+    BJ_HIP(ctx, hipEventElapsedTime(&b, T.ev[2], T.ev[3]));
     if (openings_ms) *openings_ms = a;
     if (deep_fri_ms) *deep_fri_ms = b;
     return BJ_OK;

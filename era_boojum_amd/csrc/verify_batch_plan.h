@@ -1,5 +1,5 @@
-// bj_verify_batch: where everything of a batch lies in the context's scratch, and the per-proof records the two batched kernels
-// read (verify_open.h, verifier.hip).  Plain C++ without a device type in it: a stand-alone host program builds it under the
+// bj_verify_batch (and bj_verify, its batch of one): where everything of a batch lies in the context's scratch, and the per-proof
+// records the two verifier kernels read (verify_open.h, verifier.hip).  Plain C++ without a device type in it: a stand-alone host program builds it under the
 // address and undefined-behaviour sanitizers (tests/verify_batch_plan_check.cpp).
 //
 // Scratch, in words from its base:   query sections of the proofs, back to back | the proofs' table blocks | record table of the
@@ -13,7 +13,7 @@
 
 namespace bj {
 
-// One proof of a batch as the two batched kernels find it: every offset is in words from the base of the batch's scratch.
+// One proof of a batch as the two kernels find it: every offset is in words from the base of the batch's scratch.
 // chain0 is the prefix sum of nq over the records before this one: the proof's first chain of the launch and its first status slot.
 struct VerifyBatchProof {
     uint32_t chain0, nq;
@@ -30,17 +30,17 @@ struct VerifyBatchGeometry {   // what the key fixes
     size_t query_words = 0, n_oracles = 0, cap_words = 0, term_words = 0, set_words = 0, fri_words = 0, final_degree = 0;
 };
 // a proof's table block: drawn indices, stored indices | caps of every oracle | terms | sets | FRI challenges | final monomials,
-// each at an even word (what a single bj_verify uploads behind its query section, too)
+// each at an even word
 struct VerifyTables {
     size_t idx = 0, caps = 0, terms = 0, sets = 0, fri_ch = 0, fm = 0, words = 0;
 };
-inline size_t verify_even(size_t words) { return (words + 1) & ~(size_t)1; }
+inline size_t verify_padded(size_t words) { return (words + 1) & ~(size_t)1; }
 inline VerifyTables verify_tables(const VerifyBatchGeometry &G, size_t nq) {
     VerifyTables t;
     size_t off = 0;
     auto take = [&off](size_t words) {
         const size_t at = off;
-        off += verify_even(words);
+        off += verify_padded(words);
         return at;
     };
     t.idx = take(2 * nq);
@@ -77,7 +77,7 @@ inline bool plan_verify_batch(const VerifyBatchGeometry &G, const uint32_t *nq, 
         P->records[i].chain0 = chain;
         P->records[i].nq = nq[i];
         P->records[i].queries = off;
-        off += verify_even((size_t)nq[i] * G.query_words);
+        off += verify_padded((size_t)nq[i] * G.query_words);
         chain += nq[i];
     }
     P->n_chains = chain;
@@ -99,9 +99,9 @@ inline bool plan_verify_batch(const VerifyBatchGeometry &G, const uint32_t *nq, 
     off += n * VERIFY_BATCH_RECORD_WORDS;
     P->host_words = off - P->host_block;
     P->status_open = off;
-    off += verify_even((G.n_oracles * (size_t)chain + 1) / 2);
+    off += verify_padded((G.n_oracles * (size_t)chain + 1) / 2);
     P->status_deep = off;
-    off += verify_even(((size_t)chain + 1) / 2);
+    off += verify_padded(((size_t)chain + 1) / 2);
     P->record_table2 = off;
     off += n * VERIFY_BATCH_RECORD_WORDS;
     P->total_words = off;

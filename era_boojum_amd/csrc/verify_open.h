@@ -1,19 +1,18 @@
-// bj_verify, the Merkle half of the per-query work (verifier.rs:2150-2232 for the base oracles, :2387-2519 for the FRI
-// layers): one chain per (query, oracle) — hash the opened leaf, walk the sibling path with the bits of the leaf's index,
+// bj_verify / bj_verify_batch, the Merkle half of the per-query work (verifier.rs:2150-2232 for the base oracles, :2387-2519 for
+// the FRI layers): one chain per (query, oracle) — hash the opened leaf, walk the sibling path with the bits of the leaf's index,
 // compare with the cap entry the walk ends at.  The bodies here are templates over what each tree hasher brings (the sponge
 // permutation of poseidon2.hip / poseidon1.hip, the leaf and node functions of blake2s.hip / keccak.hip); every hasher file
 // wraps one in a __global__ kernel of its own and adds its launcher to the dispatch of tree_hash.hip.
 //
-// Grid: blockIdx.y = oracle (0 witness, 1 stage 2, 2 quotient, 3 setup, 4 + l = FRI layer l), blockIdx.x * 64 + lane = chain
-// of that oracle, 64 lanes per workgroup: the lanes of a wave work on ONE oracle, so leaf width and path depth — the number of
-// permutations — are wave-uniform.  A chain reads its own query's words (a few hundred, uncoalesced: the whole query section is
-// under 2 MB) and writes one status word; nothing here traps, whatever the words are.
-//
-// bj_verify_batch runs the same chains for many proofs of ONE key in one launch: blockIdx.y stays the oracle, blockIdx.x * 64 +
-// lane is a chain of the whole batch, and the (proof, query) it belongs to comes out of a table of per-proof records in device
-// memory (VerifyBatchProof, ordered by first chain) by a binary search of at most 17 steps — a few dozen cached loads in front
-// of ~200 dependent permutations, against a chain -> proof array of up to 2^16 x queries words that would have to be built and
-// uploaded per call.  Chains of different proofs share waves; the oracle table is the key's and therefore the batch's.
+// One launch runs the chains of every proof of a batch under ONE key; bj_verify is the batch of one.  Grid: blockIdx.y = oracle
+// (0 witness, 1 stage 2, 2 quotient, 3 setup, 4 + l = FRI layer l), blockIdx.x * 64 + lane = chain of that oracle over the whole
+// batch, 64 lanes per workgroup: the lanes of a wave work on ONE oracle, so leaf width and path depth — the number of
+// permutations — are wave-uniform; the oracle table is the key's and therefore the batch's.  The (proof, query) a chain belongs to
+// comes out of a table of per-proof records in device memory (VerifyBatchProof, ordered by first chain) by a binary search of at
+// most 17 steps (none for one record) — a few dozen cached loads in front of ~200 dependent permutations, against a chain ->
+// proof array of up to 2^16 x queries words that would have to be built and uploaded per call.  Chains of different proofs share
+// waves.  A chain reads its own query's words (a few hundred, uncoalesced: a proof's query section is under 2 MB) and writes one
+// status word; nothing here traps, whatever the words are.
 #pragma once
 #include "gl.h"
 #include "verify_batch_plan.h"
@@ -32,23 +31,14 @@ struct VerifyOracle {
     uint32_t cap_off;    // words from d_caps to this oracle's cap
 };
 struct VerifyOpenArgs {
-    const u64 *queries;     // [n_queries][query_words]: the query section of the proof
-    const u64 *indices;     // [n_queries]: the index of the LDE domain query c is judged at
-    const u64 *caps;
-    uint32_t *status;       // [n_oracles][n_queries]: 1 = the path leads to the cap, 0 = it does not
-    uint32_t n_queries, query_words, n_oracles;
-    VerifyOracle oracle[VERIFY_MAX_ORACLES];
-};
-
-struct VerifyOpenBatchArgs {
-    const u64 *base;
+    const u64 *base;                  // the batch's scratch: every offset of a record is in words from here
     const VerifyBatchProof *proofs;   // [n_proofs], chain0 ascending
-    uint32_t *status;                 // [n_oracles][n_chains]
+    uint32_t *status;                 // [n_oracles][n_chains]: 1 = the path leads to the cap, 0 = it does not
     uint32_t n_proofs, n_chains, query_words, n_oracles;
     VerifyOracle oracle[VERIFY_MAX_ORACLES];
 };
 
-// the record chain g of a batch belongs to: the last one with chain0 <= g (records without queries never own a chain)
+// the record chain g of a launch belongs to: the last one with chain0 <= g (records without queries never own a chain)
 __device__ __forceinline__ unsigned verify_batch_proof_of(const VerifyBatchProof *proofs, unsigned n_proofs, unsigned g) {
     unsigned lo = 0, hi = n_proofs;
     while (hi - lo > 1) {
@@ -100,19 +90,12 @@ __device__ __forceinline__ bool verify_chain_sponge(const u64 *query, u64 index,
 }
 template <void (*PERMUTE)(u64 (&)[12])>
 __device__ __forceinline__ void verify_open_sponge(const VerifyOpenArgs &A) {
-    const unsigned c = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
-    if (c >= A.n_queries) return;
-    const bool ok = verify_chain_sponge<PERMUTE>(A.queries + (size_t)c * A.query_words, A.indices[c], A.oracle[o], A.caps);
-    A.status[(size_t)o * A.n_queries + c] = ok ? 1u : 0u;
-}
-template <void (*PERMUTE)(u64 (&)[12])>
-__device__ __forceinline__ void verify_open_sponge_batch(const VerifyOpenBatchArgs &A) {
     const unsigned g = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
     if (g >= A.n_chains) return;
     const VerifyBatchProof &P = A.proofs[verify_batch_proof_of(A.proofs, A.n_proofs, g)];
     const unsigned c = g - P.chain0;
     if (c >= P.nq) return;
-    // three values per lane where the single-proof kernel has three wave-uniform ones: nothing else of the record stays live
+    // query base, cap base and index are per-lane values (a wave may span proofs): nothing else of the record stays live
     const u64 *query = A.base + P.queries + (size_t)c * A.query_words, *caps = A.base + P.caps;
     const u64 index = A.base[P.indices + c];
     const bool ok = verify_chain_sponge<PERMUTE>(query, index, A.oracle[o], caps);
@@ -147,13 +130,6 @@ __device__ __forceinline__ bool verify_chain_bytes(const u64 *query, u64 index, 
 }
 template <typename H>
 __device__ __forceinline__ void verify_open_bytes(const VerifyOpenArgs &A) {
-    const unsigned c = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
-    if (c >= A.n_queries) return;
-    const bool ok = verify_chain_bytes<H>(A.queries + (size_t)c * A.query_words, A.indices[c], A.oracle[o], A.caps);
-    A.status[(size_t)o * A.n_queries + c] = ok ? 1u : 0u;
-}
-template <typename H>
-__device__ __forceinline__ void verify_open_bytes_batch(const VerifyOpenBatchArgs &A) {
     const unsigned g = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
     if (g >= A.n_chains) return;
     const VerifyBatchProof &P = A.proofs[verify_batch_proof_of(A.proofs, A.n_proofs, g)];

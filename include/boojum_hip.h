@@ -848,6 +848,7 @@ typedef struct bj_verify_report {
  * the DEEP and FRI challenges, the proof of work, the query indices.  Device, two kernels over the query section uploaded once:
  * every Merkle chain (query x {4 base oracles, FRI layers}), and per query the DEEP value from the four opened leaves
  * (verifier.rs:2233-2290), the fold chain through the schedule and the final monomials at the point.
+ * This is the path of bj_verify_batch below with one proof: the same two kernels, the same layout in the context's scratch.
  * Per-query failures: the smallest failing query and, inside it, the reference's order — the four base oracles, then per FRI
  * layer the carried value and the layer's path, then the final check.  So one changed word of layer l's opened leaf is
  * BJ_VERIFY_FRI_VALUE at l where it is one of the two words (c0, c1) of the carried slot and BJ_VERIFY_FRI_MERKLE at l anywhere

@@ -1,6 +1,8 @@
 """bj_verify_batch (csrc/verifier.hip, csrc/verify_open.h, csrc/verify_batch_plan.h): many proofs of one key in one call.  The
-yardstick is bj_verify on each proof alone — every report of a batch equals it field for field — and every proof a test left
-untouched must be BJ_VERIFY_OK, so that two equally wrong implementations cannot agree on rejecting good proofs."""
+contract is bj_verify on each proof alone — every report of a batch equals it field for field.  bj_verify is the batch path with
+one proof, so both sides of that comparison share the kernels and the judge: it pins the contract (a record table of N against N
+tables of one), and the absolute expectations beside it carry the weight — every proof a test left untouched must be
+BJ_VERIFY_OK with all its queries checked, and every edited one must fail at the (stage, query, oracle) the edit dictates."""
 import copy
 import dataclasses
 
@@ -17,7 +19,8 @@ pytestmark = pytest.mark.gpu
 
 
 def _batch_equals_loop(vk, proofs, untouched=(), partial=False):
-    """verify_batch against bj_verify proof by proof; the proofs at the positions `untouched` must be valid.  Returns the reports."""
+    """verify_batch against bj_verify proof by proof (a contract check: both run the same device path, see the module docstring);
+    the proofs at the positions `untouched` must be valid, which no shared fault can fake.  Returns the reports."""
     got = vk.verify_batch(ctx(), proofs, partial_queries=partial)
     want = [vk.verify(ctx(), p, partial=partial) for p in proofs]
     assert got == want, "\n".join("%d: batch %s | alone %s" % (i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w)

@@ -13,7 +13,10 @@ the same witness (median of 3).
 
 adds the batch leg: per N, bj_verify_batch over N copies-with-distinct-buffers of the proof next to N looped bj_verify calls on the
 same buffers, alternating the two for 5 rounds after one warm-up of each (proofs/s from the median wall time), and the four
-phase times of bj_verify_batch_ms of the median batch.  `--batch N` with one number is the same for that N alone."""
+phase times of bj_verify_batch_ms of the median batch.  `--batch N` with one number is the same for that N alone.
+
+`--transcript` / `--tree-hasher` go to ProverSetup (default: Poseidon2 for both) and into every result row, e.g. `--transcript
+poseidon --tree-hasher poseidon` for Poseidon (v1) trees, `--transcript keccak256` for Keccak ones."""
 import argparse
 import json
 import os
@@ -30,6 +33,9 @@ def main():
     ap.add_argument("--shapes", default="sha16,sha20,rec16")
     ap.add_argument("--out", default=None)
     ap.add_argument("--batch", default=None, help="comma-separated batch sizes for the bj_verify_batch leg, e.g. 1,8,64,512")
+    ap.add_argument("--transcript", default="poseidon2", choices=["poseidon2", "poseidon", "blake2s", "keccak256"])
+    ap.add_argument("--tree-hasher", default=None, choices=["poseidon2", "poseidon", "blake2s", "keccak256"],
+                    help="default: the transcript's usual hasher")
     args = ap.parse_args()
     try:
         import torch
@@ -50,7 +56,7 @@ def main():
             log_n = int(shape[3:])
             c = S.recursion_like_circuit(log_n, seed=3)
             cfg = (2, 16, 100)
-        setup = E.ProverSetup(ctx, c, *cfg)
+        setup = E.ProverSetup(ctx, c, *cfg, transcript=args.transcript, tree_hasher=args.tree_hasher)
         v = np.ascontiguousarray(c.variables, dtype=np.uint64)
         if setup.num_witness_cols:
             v = np.ascontiguousarray(np.concatenate([v, c.witness], axis=0))
@@ -74,7 +80,7 @@ def main():
             a, b = vk.kernel_ms(ctx)
             k_open.append(a)
             k_deep.append(b)
-        res = {"shape": shape, "log_n": c.log_n, "num_vars": c.num_vars, "fri_lde_factor": cfg[0], "cap_size": cfg[1], "security_level": cfg[2],
+        res = {"shape": shape, "transcript": args.transcript, "tree_hasher": args.tree_hasher, "log_n": c.log_n, "num_vars": c.num_vars, "fri_lde_factor": cfg[0], "cap_size": cfg[1], "security_level": cfg[2],
                "queries": int(buf[9]), "proof_words": int(buf.size), "verify_ms": statistics.median(whole), "verify_runs_ms": whole,
                "verify_openings_kernel_ms": statistics.median(k_open), "verify_deep_fri_kernel_ms": statistics.median(k_deep),
                "prove_dev_ms": statistics.median(prove), "prove_dev_runs_ms": prove,
