@@ -1,7 +1,7 @@
 // Internal: what the op-list interpreter (gate_program.hip), the build-time generated straight-line kernels (gate_aot.hip) and
 // the kernels compiled at run time from a host's own op lists (gate_jit.hip) share on the device side — launch arguments, the
-// lazy alpha accumulator, the in-kernel inversion, the per-point drivers around a straight-line body.  Depends on gl.h only,
-// so that hiprtc can compile it from the copy embedded in the library (jit_headers.inc).
+// in-kernel inversion, the per-point drivers around a straight-line body (their lazy alpha accumulators are gl::Acc160).  Depends
+// on gl.h only, so that hiprtc can compile it from the copy embedded in the library (jit_headers.inc).
 #pragma once
 #include "gl.h"
 
@@ -12,29 +12,6 @@ struct DevRelation {
 namespace gpdev {
 using gl::u32;
 using gl::u64;
-
-struct Acc160g {   // same lazy accumulator as quotient.hip
-    u32 w[5];
-    __host__ __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int i = 0; i < 5; i++) w[i] = 0;
-    }
-    __host__ __device__ __forceinline__ void fma(u64 a, u64 b) {
-        u32 hh, hl;
-        u64 lo;
-        gl::mul_limbs(a, b, hh, hl, lo);
-        u32 c;
-        w[0] = __builtin_addc(w[0], gl::lo32(lo), 0u, &c);
-        w[1] = __builtin_addc(w[1], gl::hi32(lo), c, &c);
-        w[2] = __builtin_addc(w[2], hl, c, &c);
-        w[3] = __builtin_addc(w[3], hh, c, &c);
-        w[4] += c;
-    }
-    __host__ __device__ __forceinline__ u64 reduce() const {
-        u64 r = gl::reduce_limbs(w[3], w[2], gl::pack(w[0], w[1]));
-        return gl::sub(r, (u64)w[4] << 32);
-    }
-};
 
 __host__ __device__ inline u64 inv_pow(u64 x) {   // x^(p-2); inverse of 0 is 0 like the reference's batch inversion never sees
     u64 r = 1, b = x;
@@ -107,7 +84,7 @@ __host__ __device__ __forceinline__ u64 selector_at(const ProgArgs &a, size_t I)
 template <class B>
 __host__ __device__ __forceinline__ void aot_point(const ProgArgs &a, size_t I) {
     const u64 sel = selector_at(a, I);
-    Acc160g acc0, acc1;
+    gl::Acc160 acc0, acc1;
     acc0.clear();
     acc1.clear();
     for (unsigned r = 0; r < a.reps; r++) {
@@ -130,8 +107,8 @@ __host__ __device__ __forceinline__ void aot_point(const ProgArgs &a, size_t I) 
 
 // repetitions [r_lo, r_hi) of one gate inside a fused sweep: (sel * term) * alpha into the shared accumulators
 template <class B>
-__host__ __device__ __forceinline__ void fused_reps(const ProgArgs &a, size_t I, unsigned r_lo, unsigned r_hi, u64 sel, Acc160g &acc0,
-                                                    Acc160g &acc1) {
+__host__ __device__ __forceinline__ void fused_reps(const ProgArgs &a, size_t I, unsigned r_lo, unsigned r_hi, u64 sel, gl::Acc160 &acc0,
+                                                    gl::Acc160 &acc1) {
     for (unsigned r = r_lo; r < r_hi; r++) {
         u64 term[B::NT];
         B::run(a, I, r, term);

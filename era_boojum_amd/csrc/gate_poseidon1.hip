@@ -7,7 +7,7 @@
 // `w_hat`), then four full rounds whose first adds no constants.  Tables: poseidon1_fused.inc
 // (tools/gen_poseidon1_fused_constants.py).  The op-list interpreter (gate_program.hip) runs the same gate as the 3 457
 // operations on 34 slots of the capture's canonical form (3 980 recorded relations), its temporaries in scratch memory; here
-// the state stays in registers and the terms go straight into the alpha-weighted 160-bit accumulators.  Same terms (as
+// the state stays in registers and the terms go straight into the alpha-weighted gl::Acc160 accumulators.  Same terms (as
 // canonical residues), same order, same proof.  Round 26 is written out before the loop over rounds 27-29: a run-time
 // "constants or not" branch inside one loop over all four rounds took the kernel from 79 to 252 VGPRs.
 #include "gl.h"
@@ -27,34 +27,6 @@ __constant__ u64 P1G_DENSE[144] = BJ_P1_FUSED_DENSE;
 __constant__ u64 P1G_SBOX_RC[22] = BJ_P1_FUSED_SBOX_RC;
 __constant__ u64 P1G_VS[22 * 11] = BJ_P1_FUSED_VS;
 __constant__ u64 P1G_W_HATS[22 * 11] = BJ_P1_FUSED_W_HATS;
-
-struct Acc160q {   // sum of 128-bit products, reduced once (as gate_poseidon2.hip)
-    u32 w[5];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int i = 0; i < 5; i++) w[i] = 0;
-    }
-    __device__ __forceinline__ void fma(u64 a, u64 b) {
-        u32 hh, hl;
-        u64 lo;
-        gl::mul_limbs(a, b, hh, hl, lo);
-        u32 c;
-        w[0] = __builtin_addc(w[0], gl::lo32(lo), 0u, &c);
-        w[1] = __builtin_addc(w[1], gl::hi32(lo), c, &c);
-        w[2] = __builtin_addc(w[2], hl, c, &c);
-        w[3] = __builtin_addc(w[3], hh, c, &c);
-        w[4] += c;
-    }
-    __device__ __forceinline__ u64 reduce() const {
-        u64 r = gl::reduce_limbs(w[3], w[2], gl::pack(w[0], w[1]));
-        return gl::sub(r, (u64)w[4] << 32);
-    }
-};
-
-__device__ __forceinline__ u64 pow7(u64 x) {
-    u64 x2 = gl::sqr(x), x3 = gl::mul(x2, x), x4 = gl::sqr(x2);
-    return gl::mul(x4, x3);
-}
 
 // x * y + c on the 64-bit multiply-add, the power of two in an SGPR (as poseidon1.hip); callers bound the sums: no carry out
 __device__ __forceinline__ u64 p1g_mad(u32 x, u32 y, u64 c) {
@@ -99,7 +71,7 @@ quotient_poseidon_flattened_kernel(const u64 *vars, size_t var_stride, const u64
         u64 c = gl::canon(consts[(size_t)b * const_stride + I]);
         sel = gl::mul(sel, ((path_bits >> b) & 1u) ? c : gl::sub(1, c));
     }
-    Acc160q a0, a1;
+    gl::Acc160 a0, a1;
     a0.clear();
     a1.clear();
     unsigned term = 0, nxt = 24;
@@ -124,7 +96,7 @@ quotient_poseidon_flattened_kernel(const u64 *vars, size_t var_stride, const u64
     for (int rnd = 0; rnd < 4; rnd++) {   // full rounds 0-3; the MDS of round 3 is fused with the first partial round
         if (rnd) reset(s);
 #pragma unroll
-        for (int i = 0; i < 12; i++) s[i] = pow7(gl::add(s[i], P1G_RC[12 * rnd + i]));
+        for (int i = 0; i < 12; i++) s[i] = gl::pow7(gl::add(s[i], P1G_RC[12 * rnd + i]));
         if (rnd != 3) p1g_mds(s);
     }
     {
@@ -133,7 +105,7 @@ quotient_poseidon_flattened_kernel(const u64 *vars, size_t var_stride, const u64
         for (int i = 0; i < 12; i++) t[i] = gl::add(s[i], P1G_FUSED_RC[i]);
 #pragma unroll 1
         for (int r = 0; r < 12; r++) {
-            Acc160q acc;
+            gl::Acc160 acc;
             acc.clear();
 #pragma unroll
             for (int k = 0; k < 12; k++) acc.fma(t[k], P1G_DENSE[12 * r + k]);
@@ -147,8 +119,8 @@ quotient_poseidon_flattened_kernel(const u64 *vars, size_t var_stride, const u64
     for (int rnd = 0; rnd < 22; rnd++) {
         const u64 v = var(nxt++);
         push(gl::sub(s[0], v));
-        const u64 s0 = gl::add(pow7(v), P1G_SBOX_RC[rnd]);
-        Acc160q acc;
+        const u64 s0 = gl::add(gl::pow7(v), P1G_SBOX_RC[rnd]);
+        gl::Acc160 acc;
         acc.clear();
 #pragma unroll
         for (int k = 1; k < 12; k++) acc.fma(s[k], P1G_VS[11 * rnd + k - 1]);
@@ -158,13 +130,13 @@ quotient_poseidon_flattened_kernel(const u64 *vars, size_t var_stride, const u64
     }
     reset(s);   // round 26: its constants were propagated into the partial rounds
 #pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = pow7(s[i]);
+    for (int i = 0; i < 12; i++) s[i] = gl::pow7(s[i]);
     p1g_mds(s);
 #pragma unroll 1
     for (int r = 27; r < 30; r++) {
         reset(s);
 #pragma unroll
-        for (int i = 0; i < 12; i++) s[i] = pow7(gl::add(s[i], P1G_RC[12 * r + i]));
+        for (int i = 0; i < 12; i++) s[i] = gl::pow7(gl::add(s[i], P1G_RC[12 * r + i]));
         p1g_mds(s);
     }
 #pragma unroll

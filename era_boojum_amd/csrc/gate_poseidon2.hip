@@ -16,33 +16,6 @@ namespace {
 
 __constant__ u64 P2G_RC[BJ_POSEIDON_NUM_RC] = BJ_POSEIDON_RC_TABLE;
 
-struct Acc160p {   // sum of 128-bit products, reduced once
-    u32 w[5];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int i = 0; i < 5; i++) w[i] = 0;
-    }
-    __device__ __forceinline__ void fma(u64 a, u64 b) {
-        u32 hh, hl;
-        u64 lo;
-        gl::mul_limbs(a, b, hh, hl, lo);
-        u32 c;
-        w[0] = __builtin_addc(w[0], gl::lo32(lo), 0u, &c);
-        w[1] = __builtin_addc(w[1], gl::hi32(lo), c, &c);
-        w[2] = __builtin_addc(w[2], hl, c, &c);
-        w[3] = __builtin_addc(w[3], hh, c, &c);
-        w[4] += c;
-    }
-    __device__ __forceinline__ u64 reduce() const {
-        u64 r = gl::reduce_limbs(w[3], w[2], gl::pack(w[0], w[1]));
-        return gl::sub(r, (u64)w[4] << 32);
-    }
-};
-
-__device__ __forceinline__ u64 pow7(u64 x) {
-    u64 x2 = gl::sqr(x), x3 = gl::mul(x2, x), x4 = gl::sqr(x2);
-    return gl::mul(x4, x3);
-}
 __device__ __forceinline__ void m4(u64 *x) {   // [[5,7,1,3],[4,6,1,1],[1,3,5,7],[1,1,4,6]] (suggested_mds.rs:21-56)
     u64 t0 = gl::add(x[0], x[1]), t1 = gl::add(x[2], x[3]);
     u64 t2 = gl::add(gl::dbl(x[1]), t1), t3 = gl::add(gl::dbl(x[3]), t0);
@@ -69,7 +42,7 @@ quotient_poseidon2_flattened_kernel(const u64 *vars, size_t var_stride, const u6
         u64 c = gl::canon(consts[(size_t)b * const_stride + I]);
         sel = gl::mul(sel, ((path_bits >> b) & 1u) ? c : gl::sub(1, c));
     }
-    Acc160p a0, a1;
+    gl::Acc160 a0, a1;
     a0.clear();
     a1.clear();
     unsigned term = 0, nxt = 24;
@@ -95,7 +68,7 @@ quotient_poseidon2_flattened_kernel(const u64 *vars, size_t var_stride, const u6
             }
         }
 #pragma unroll
-        for (int i = 0; i < 12; i++) s[i] = pow7(gl::add(s[i], P2G_RC[12 * rnd + i]));
+        for (int i = 0; i < 12; i++) s[i] = gl::pow7(gl::add(s[i], P2G_RC[12 * rnd + i]));
         ext_mds(s);
     }
 #pragma unroll 1
@@ -103,7 +76,7 @@ quotient_poseidon2_flattened_kernel(const u64 *vars, size_t var_stride, const u6
         s[0] = gl::add(s[0], P2G_RC[12 * (4 + rnd)]);
         const u64 v = var(nxt++);
         push(gl::sub(s[0], v));
-        s[0] = pow7(v);
+        s[0] = gl::pow7(v);
         u64 tot = s[0];
 #pragma unroll
         for (int i = 1; i < 12; i++) tot = gl::add(tot, s[i]);
@@ -119,7 +92,7 @@ quotient_poseidon2_flattened_kernel(const u64 *vars, size_t var_stride, const u6
             s[i] = v;
         }
 #pragma unroll
-        for (int i = 0; i < 12; i++) s[i] = pow7(gl::add(s[i], P2G_RC[12 * (26 + k) + i]));
+        for (int i = 0; i < 12; i++) s[i] = gl::pow7(gl::add(s[i], P2G_RC[12 * (26 + k) + i]));
         ext_mds(s);
     }
 #pragma unroll

@@ -52,9 +52,8 @@ __global__ void __launch_bounds__(256) gate_program_kernel(ProgArgs a) {
         u64 c = gl::canon(a.consts[(size_t)b * a.const_stride + I]);
         sel = gl::mul(sel, a.path[b] ? c : gl::sub(1, c));
     }
-    Acc160g s0, s1;
-    s0.clear();
-    s1.clear();
+    gl::Acc160x2 s;
+    s.clear();
     for (unsigned r = 0; r < a.reps; r++) {
         const size_t vb = (size_t)r * a.rep_var_stride, cb = (size_t)a.path_len + (size_t)r * a.rep_const_stride;
         wb = (size_t)r * a.rep_wit_stride;
@@ -73,10 +72,7 @@ __global__ void __launch_bounds__(256) gate_program_kernel(ProgArgs a) {
                 default: {   // canon::OP_WRITE: x is term R.dst of this repetition
                     const size_t k = (size_t)r * a.n_writes + R.dst;
                     if (a.terms) a.terms[k * a.Q + I] = x;
-                    if (a.alphas) {
-                        s0.fma(x, a.alphas[2 * k]);
-                        s1.fma(x, a.alphas[2 * k + 1]);
-                    }
+                    if (a.alphas) s.fma_base(x, a.alphas + 2 * k);
                     continue;
                 }
             }
@@ -84,8 +80,8 @@ __global__ void __launch_bounds__(256) gate_program_kernel(ProgArgs a) {
         }
     }
     if (a.alphas) {
-        a.out0[I] = gl::add(gl::canon(a.out0[I]), gl::mul(s0.reduce(), sel));
-        a.out1[I] = gl::add(gl::canon(a.out1[I]), gl::mul(s1.reduce(), sel));
+        a.out0[I] = gl::add(gl::canon(a.out0[I]), gl::mul(s.s0.reduce(), sel));
+        a.out1[I] = gl::add(gl::canon(a.out1[I]), gl::mul(s.s1.reduce(), sel));
     }
 }
 }  // namespace

@@ -325,6 +325,14 @@ __host__ __device__ __forceinline__ u64 mul_pow2(u64 a, unsigned k) {
     return (c2 | c4) ? pack(q0, q1) : pack(r0, r1);
 }
 
+// 7 * a, canonical (7 = the non-residue of F_p^2 = the LDE coset shift)
+__host__ __device__ __forceinline__ u64 mul7(u64 a) { return sub(mul_pow2(a, 3), a); }
+// a^7, canonical: the Poseidon S-box of the gate evaluators and the host transcript
+__host__ __device__ __forceinline__ u64 pow7(u64 x) {
+    u64 x2 = sqr(x), x3 = mul(x2, x), x4 = sqr(x2);
+    return mul(x4, x3);
+}
+
 __host__ __device__ inline u64 pow(u64 a, u64 e) {
     u64 r = 1;
     while (e) {
@@ -335,6 +343,26 @@ __host__ __device__ inline u64 pow(u64 a, u64 e) {
     return r;
 }
 __host__ __device__ inline u64 inv(u64 a) { return pow(a, P - 2); }
+// the same x^(p-2) with an addition chain, for the kernels that invert per point:
+// p - 2 = (2^32 - 2) * 2^32 + (2^32 - 1)   (~72 multiplications)
+__host__ __device__ inline u64 inv_chain(u64 x) {
+    auto sqn = [](u64 v, int n) {
+        for (int i = 0; i < n; i++) v = sqr(v);
+        return v;
+    };
+    u64 a1 = x;                      // 2^1 - 1
+    u64 a2 = mul(sqn(a1, 1), a1);    // 2^2 - 1
+    u64 a4 = mul(sqn(a2, 2), a2);
+    u64 a8 = mul(sqn(a4, 4), a4);
+    u64 a16 = mul(sqn(a8, 8), a8);
+    u64 a24 = mul(sqn(a16, 8), a8);
+    u64 a28 = mul(sqn(a24, 4), a4);
+    u64 a30 = mul(sqn(a28, 2), a2);
+    u64 a31 = mul(sqn(a30, 1), a1);  // 2^31 - 1
+    u64 b = sqr(a31);                // 2^32 - 2
+    u64 a32 = mul(b, x);             // 2^32 - 1
+    return mul(sqn(b, 32), a32);
+}
 
 // domain_generator_for_size (cs/implementations/utils.rs:13-28); radix_2_subgroup_generator = 0x185629dcda58878c
 __host__ __device__ inline u64 omega(unsigned log_n) {
@@ -352,8 +380,7 @@ __host__ __device__ __forceinline__ e2 e2_sub(e2 a, e2 b) { return {sub(a.c0, b.
 __host__ __device__ __forceinline__ e2 e2_mul(e2 a, e2 b) {  // Karatsuba, field.rs:407-426
     u64 v0 = mul(a.c0, b.c0), v1 = mul(a.c1, b.c1);
     u64 c1 = sub(sub(mul(add(a.c0, a.c1), add(b.c0, b.c1)), v0), v1);
-    u64 seven_v1 = sub(mul_pow2(v1, 3), v1);
-    return {add(v0, seven_v1), c1};
+    return {add(v0, mul7(v1)), c1};
 }
 // the same product on weak residues, schoolbook: four weak products, two weak sums, 7 * a1 b1 through mul7_weak — no
 // canonicalisation anywhere (Karatsuba's three products cost five canonical additions / subtractions on this VALU)
@@ -366,6 +393,11 @@ __host__ __device__ __forceinline__ e2 e2_mul_base(e2 a, u64 s) { return {mul(a.
 __host__ __device__ inline e2 e2_inv(e2 a) {  // field.rs:484-512
     u64 n = sub(sqr(a.c0), mul(GEN, sqr(a.c1)));
     u64 ni = inv(n);
+    return {mul(a.c0, ni), neg(mul(a.c1, ni))};
+}
+__host__ __device__ __forceinline__ e2 e2_inv_chain(e2 a) {  // the same on inv_chain
+    u64 seven_c1sq = mul7(sqr(a.c1));
+    u64 ni = inv_chain(sub(sqr(a.c0), seven_c1sq));
     return {mul(a.c0, ni), neg(mul(a.c1, ni))};
 }
 
@@ -381,5 +413,72 @@ __host__ __device__ __forceinline__ u32 bitrev32(u32 x, unsigned bits) {
     return r;
 #endif
 }
+
+// ---- the bit-reversed forward twiddle table of a domain of size n = 2^log_n:  T[j] = omega_n^bitrev(j, log_n - 1), j < n/2 ----
+// omega_n^r for a natural index r < n
+__host__ __device__ __forceinline__ u64 omega_pow_nat(const u64 *tw, unsigned log_n, u32 r) {
+    if (log_n == 0) return 1;
+    u32 half = 1u << (log_n - 1);
+    u64 w = tw[bitrev32(r & (half - 1), log_n - 1)];
+    return (r & half) ? neg(w) : w;
+}
+// point j of the domain in bit-reversed enumeration:  omega_n^bitrev(j, log_n) = T[j>>1] * (-1)^(j&1)
+__host__ __device__ __forceinline__ u64 domain_point(const u64 *tw, size_t j) {
+    u64 wi = tw[j >> 1];
+    if (j & 1) wi = neg(wi);
+    return wi;
+}
+
+// ---- sums of products, accumulated UNREDUCED: each 64 x 64 product is added as a 128-bit integer into five 32-bit words
+// (carry chain) and the sum is reduced mod p once — four mads + five add-with-carry per term instead of a modular reduction
+// and a modular add ----
+struct Acc160 {
+    u32 w[5];
+    __host__ __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int i = 0; i < 5; i++) w[i] = 0;
+    }
+    // += a * b  (any u64 operands)
+    __host__ __device__ __forceinline__ void fma(u64 a, u64 b) {
+        u32 hh, hl;
+        u64 lo;
+        mul_limbs(a, b, hh, hl, lo);
+        u32 c;
+        w[0] = __builtin_addc(w[0], lo32(lo), 0u, &c);
+        w[1] = __builtin_addc(w[1], hi32(lo), c, &c);
+        w[2] = __builtin_addc(w[2], hl, c, &c);
+        w[3] = __builtin_addc(w[3], hh, c, &c);
+        w[4] += c;
+    }
+    // canonical residue of the accumulated integer: 2^64 = 2^32-1, 2^96 = -1, 2^128 = -2^32 (mod p)
+    __host__ __device__ __forceinline__ u64 reduce() const {
+        u64 r = reduce_limbs(w[3], w[2], pack(w[0], w[1]));
+        // at most 2^32 terms: each is below 2^128, so w[4], the count of 2^128s, does not wrap; and (w[4] << 32) <= 2^64 - 2^32
+        // = p - 1 whatever w[4] holds, a canonical operand for sub
+        return sub(r, (u64)w[4] << 32);
+    }
+};
+// The pair every term kernel keeps: sum_k term_k * alpha_k for alpha_k in F_p^2, one accumulator per component of the sum
+struct Acc160x2 {
+    Acc160 s1, s0;   // s0: the c0 component.  Declared in this order because the kernels' register assignment follows it: with s0 first
+                     // the same instructions come out on other VGPRs than with the two separate accumulators the kernels had
+    __host__ __device__ __forceinline__ void clear() {
+        s0.clear();
+        s1.clear();
+    }
+    // += term * (alpha[0] + alpha[1] u), term in F_p
+    __host__ __device__ __forceinline__ void fma_base(u64 term, const u64 *alpha) {
+        s0.fma(term, alpha[0]);
+        s1.fma(term, alpha[1]);
+    }
+    // += (t0 + t1 u)(a0 + a1 u) = (t0 a0 + 7 t1 a1) + (t0 a1 + t1 a0) u;  a1 canonical (mul7), the rest any u64
+    __host__ __device__ __forceinline__ void fma_e2(e2 t, u64 a0, u64 a1) {
+        s0.fma(t.c0, a0);
+        s0.fma(t.c1, mul7(a1));
+        s1.fma(t.c0, a1);
+        s1.fma(t.c1, a0);
+    }
+    __host__ __device__ __forceinline__ e2 reduce() const { return {s0.reduce(), s1.reduce()}; }
+};
 
 }  // namespace gl

@@ -20,10 +20,6 @@ inline const u64 *rc_table() {
     return RC;
 }
 
-inline u64 pow7(u64 x) {
-    u64 x2 = gl::sqr(x), x3 = gl::mul(x2, x), x4 = gl::sqr(x2);
-    return gl::mul(x4, x3);
-}
 inline void m4(u64 *x) {
     u64 t0 = gl::add(x[0], x[1]), t1 = gl::add(x[2], x[3]);
     u64 t2 = gl::add(gl::dbl(x[1]), t1), t3 = gl::add(gl::dbl(x[3]), t0);
@@ -44,17 +40,17 @@ inline void poseidon2_permutation(u64 *s) {
     ext_mds(s);
     int r = 0;
     for (int i = 0; i < 4; i++, r++) {
-        for (int k = 0; k < 12; k++) s[k] = pow7(gl::add(s[k], RC[12 * r + k]));
+        for (int k = 0; k < 12; k++) s[k] = gl::pow7(gl::add(s[k], RC[12 * r + k]));
         ext_mds(s);
     }
     for (int i = 0; i < 22; i++, r++) {
-        s[0] = pow7(gl::add(s[0], RC[12 * r]));
+        s[0] = gl::pow7(gl::add(s[0], RC[12 * r]));
         u64 sum = 0;
         for (int k = 0; k < 12; k++) sum = gl::add(sum, s[k]);
         for (int k = 0; k < 12; k++) s[k] = gl::add(gl::mul_pow2(s[k], SH[k]), sum);
     }
     for (int i = 0; i < 4; i++, r++) {
-        for (int k = 0; k < 12; k++) s[k] = pow7(gl::add(s[k], RC[12 * r + k]));
+        for (int k = 0; k < 12; k++) s[k] = gl::pow7(gl::add(s[k], RC[12 * r + k]));
         ext_mds(s);
     }
 }
@@ -71,7 +67,7 @@ inline void poseidon1_permutation(u64 *s) {
     for (int r = 0; r < 30; r++) {
         const bool full = r < 4 || r >= 26;
         for (int k = 0; k < 12; k++) s[k] = gl::add(s[k], RC[12 * r + k]);
-        for (int k = 0; k < (full ? 12 : 1); k++) s[k] = pow7(s[k]);
+        for (int k = 0; k < (full ? 12 : 1); k++) s[k] = gl::pow7(s[k]);
         // out[row] = sum_col s[col] << EXPS[(col - row) mod 12] = sum_d s[(row + d) mod 12] << EXPS[d]: for a fixed d
         // the twelve rows read a rotated copy of the state and shift by one constant, so the loops over rows vectorise.
         // Low and high words accumulate apart (each sum < 12 * 2^48), no 128-bit arithmetic.

@@ -10,9 +10,9 @@
 //   DEEP:         dst[I]  += ( sum_k coef_k * f_k[I]  -  C ) / (x_I - at)   (reduction over the columns)
 // A column is base-field, so coef * f is two base multiplications; an F_p^2 column (c0, c1) is presented by the host
 // as two base columns with coefficients (ch0, ch1) and (7*ch1, ch0) — same residues, no special case on the device.
-// The sums are accumulated UNREDUCED: each 64x64 product is added as a 128-bit integer into a 160-bit accumulator
-// (five 32-bit words, carry chain) and reduced mod p once at the end, which replaces a modular reduction + modular add
-// per term (~28 VALU ops) by the four mads + five add-with-carry (~10 ops).  HBM: every column value is read once.
+// The sums are accumulated UNREDUCED in gl::Acc160 (gl.h): each 64x64 product is added as a 128-bit integer into a 160-bit
+// accumulator (five 32-bit words, carry chain) and reduced mod p once at the end, which replaces a modular reduction + modular
+// add per term (~28 VALU ops) by the four mads + five add-with-carry (~10 ops).  HBM: every column value is read once.
 #include "gl.h"
 #include "kernels.h"
 
@@ -20,53 +20,6 @@ using gl::u64;
 using gl::u32;
 
 namespace bj {
-
-struct Acc160 {
-    u32 w[5];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int i = 0; i < 5; i++) w[i] = 0;
-    }
-    // += a * b  (any u64 operands)
-    __device__ __forceinline__ void fma(u64 a, u64 b) {
-        u32 hh, hl;
-        u64 lo;
-        gl::mul_limbs(a, b, hh, hl, lo);
-        u32 c;
-        w[0] = __builtin_addc(w[0], gl::lo32(lo), 0u, &c);
-        w[1] = __builtin_addc(w[1], gl::hi32(lo), c, &c);
-        w[2] = __builtin_addc(w[2], hl, c, &c);
-        w[3] = __builtin_addc(w[3], hh, c, &c);
-        w[4] += c;
-    }
-    // canonical residue of the accumulated integer: 2^64 = 2^32-1, 2^96 = -1, 2^128 = -2^32 (mod p)
-    __device__ __forceinline__ u64 reduce() const {
-        u64 r = gl::reduce_limbs(w[3], w[2], gl::pack(w[0], w[1]));
-        return gl::sub(r, (u64)w[4] << 32);  // w[4] < 2^31 terms, so (w4 << 32) < p
-    }
-};
-
-// x^(p-2) with an addition chain: p - 2 = (2^32 - 2) * 2^32 + (2^32 - 1)   (~72 multiplications)
-__device__ inline u64 inv_chain(u64 x) {
-    auto sqn = [](u64 v, int n) {
-        for (int i = 0; i < n; i++) v = gl::sqr(v);
-        return v;
-    };
-    u64 a1 = x;                          // 2^1 - 1
-    u64 a2 = gl::mul(sqn(a1, 1), a1);    // 2^2 - 1
-    u64 a4 = gl::mul(sqn(a2, 2), a2);
-    u64 a8 = gl::mul(sqn(a4, 4), a4);
-    u64 a16 = gl::mul(sqn(a8, 8), a8);
-    u64 a24 = gl::mul(sqn(a16, 8), a8);
-    u64 a28 = gl::mul(sqn(a24, 4), a4);
-    u64 a30 = gl::mul(sqn(a28, 2), a2);
-    u64 a31 = gl::mul(sqn(a30, 1), a1);  // 2^31 - 1
-    u64 b = gl::sqr(a31);                // 2^32 - 2
-    u64 a32 = gl::mul(b, x);             // 2^32 - 1
-    return gl::mul(sqn(b, 32), a32);
-}
-
-__device__ __forceinline__ u64 mul7(u64 a) { return gl::sub(gl::mul_pow2(a, 3), a); }
 
 // ---------------------------------------------------------------------------------------------------------
 // barycentric weights, stored bit-reversed:  w[j] = cf * omega^i / (z - coset*omega^i),  i = bitrev(j)
@@ -77,13 +30,12 @@ __global__ void barycentric_weights_kernel(u64 *w0, u64 *w1, const u64 *tw, unsi
     size_t n = (size_t)1 << log_n;
     size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
-    u64 wi = tw[j >> 1];
-    if (j & 1) wi = gl::neg(wi);
+    u64 wi = gl::domain_point(tw, j);
     u64 x = gl::mul(coset, wi);
-    // 1 / (z - x) in F_p^2
+    // 1 / (z - x) in F_p^2: gl::e2_inv_chain with the norm's two squares taken in the other order
     u64 d0 = gl::sub(z0, x), d1 = z1;
-    u64 norm = gl::sub(gl::sqr(d0), mul7(gl::sqr(d1)));
-    u64 ni = inv_chain(norm);
+    u64 norm = gl::sub(gl::sqr(d0), gl::mul7(gl::sqr(d1)));
+    u64 ni = gl::inv_chain(norm);
     gl::e2 inv{gl::mul(d0, ni), gl::neg(gl::mul(d1, ni))};
     gl::e2 c{gl::mul(cf0, wi), gl::mul(cf1, wi)};
     gl::e2 r = gl::e2_mul(inv, c);
@@ -138,7 +90,7 @@ barycentric_partial_kernel(const u64 *const *cols, unsigned n_cols, size_t n, co
     const u64 *f[BARY_COLS];
 #pragma unroll
     for (int c = 0; c < BARY_COLS; c++) f[c] = cols[c0 + c < n_cols ? c0 + c : c0];   // a short last group re-reads its first column; the surplus sums are dropped
-    Acc160 s0[BARY_COLS], s1[BARY_COLS];
+    gl::Acc160 s0[BARY_COLS], s1[BARY_COLS];
 #pragma unroll
     for (int c = 0; c < BARY_COLS; c++) {
         s0[c].clear();
@@ -240,7 +192,7 @@ __global__ void __launch_bounds__(256)
 linear_combination_kernel(const u64 *const *cols, const u64 *coefs /*[n_cols][2]*/, unsigned n_cols, size_t n, u64 *out0,
                           u64 *out1) {
     const size_t base = (size_t)blockIdx.x * (256 * PTS) + threadIdx.x;
-    Acc160 s0[PTS], s1[PTS];
+    gl::Acc160 s0[PTS], s1[PTS];
 #pragma unroll
     for (int k = 0; k < PTS; k++) {
         s0[k].clear();
@@ -310,7 +262,7 @@ __global__ void __launch_bounds__(256)
 deep_accumulate_kernel(const u64 *const *cols, const u64 *coefs /*[n][2]*/, unsigned n_cols, size_t N, size_t I0,
                        const u64 *tw, u64 c0, u64 c1, u64 at0, u64 at1, u64 *dst0, u64 *dst1, int accumulate) {
     const size_t base = (size_t)blockIdx.x * (256 * DEEP_PTS) + threadIdx.x;
-    Acc160 s0[DEEP_PTS], s1[DEEP_PTS];
+    gl::Acc160 s0[DEEP_PTS], s1[DEEP_PTS];
 #pragma unroll
     for (int k = 0; k < DEEP_PTS; k++) {
         s0[k].clear();
@@ -330,21 +282,19 @@ deep_accumulate_kernel(const u64 *const *cols, const u64 *coefs /*[n][2]*/, unsi
     // denominators x_I - at, inverted together
     u64 d0[DEEP_PTS], norm[DEEP_PTS], pref[DEEP_PTS];
     const u64 d1 = gl::neg(at1);
-    const u64 seven_d1sq = mul7(gl::sqr(d1));
+    const u64 seven_d1sq = gl::mul7(gl::sqr(d1));
     u64 run = 1;
 #pragma unroll
     for (int k = 0; k < DEEP_PTS; k++) {
         size_t I = base + (size_t)k * 256;
         size_t Ic = I0 + (I < N ? I : 0);   // global LDE index of the point
-        u64 wi = tw[Ic >> 1];
-        if (Ic & 1) wi = gl::neg(wi);
-        u64 x = mul7(wi);
+        u64 x = gl::mul7(gl::domain_point(tw, Ic));
         d0[k] = gl::sub(x, at0);
         norm[k] = gl::sub(gl::sqr(d0[k]), seven_d1sq);
         pref[k] = run;
         run = gl::mul(run, norm[k]);
     }
-    u64 inv_run = inv_chain(run);
+    u64 inv_run = gl::inv_chain(run);
 #pragma unroll
     for (int k = DEEP_PTS - 1; k >= 0; k--) {
         u64 ni = gl::mul(inv_run, pref[k]);
@@ -387,16 +337,14 @@ deep_accumulate_multi_kernel(DeepSetsDev S, size_t N, size_t I0, const u64 *tw, 
     for (int k = 0; k < DEEP_PTS; k++) {
         const size_t I = base + (size_t)k * 256;
         const size_t Ic = I0 + (I < N ? I : 0);
-        u64 wi = tw[Ic >> 1];
-        if (Ic & 1) wi = gl::neg(wi);
-        x[k] = mul7(wi);
+        x[k] = gl::mul7(gl::domain_point(tw, Ic));
     }
     u64 norm[DEEP_MAX_SETS][DEEP_PTS], pref[DEEP_MAX_SETS][DEEP_PTS];
     u64 run = 1;
 #pragma unroll
     for (int t = 0; t < DEEP_MAX_SETS; t++) {
         if (t >= S.n) break;
-        const u64 seven_d1sq = mul7(gl::sqr(S.s[t].at1));   // (-at1)^2 = at1^2
+        const u64 seven_d1sq = gl::mul7(gl::sqr(S.s[t].at1));   // (-at1)^2 = at1^2
 #pragma unroll
         for (int k = 0; k < DEEP_PTS; k++) {
             const u64 d0 = gl::sub(x[k], S.s[t].at0);
@@ -405,7 +353,7 @@ deep_accumulate_multi_kernel(DeepSetsDev S, size_t N, size_t I0, const u64 *tw, 
             run = gl::mul(run, norm[t][k]);
         }
     }
-    u64 inv_run = inv_chain(run);
+    u64 inv_run = gl::inv_chain(run);
     gl::e2 acc[DEEP_PTS];
 #pragma unroll
     for (int k = 0; k < DEEP_PTS; k++) {
@@ -415,7 +363,7 @@ deep_accumulate_multi_kernel(DeepSetsDev S, size_t N, size_t I0, const u64 *tw, 
 #pragma unroll
     for (int t = DEEP_MAX_SETS - 1; t >= 0; t--) {
         if (t >= S.n) continue;
-        Acc160 s0[DEEP_PTS], s1[DEEP_PTS];
+        gl::Acc160 s0[DEEP_PTS], s1[DEEP_PTS];
 #pragma unroll
         for (int k = 0; k < DEEP_PTS; k++) {
             s0[k].clear();

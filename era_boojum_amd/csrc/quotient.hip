@@ -23,45 +23,8 @@ using gl::u32;
 
 namespace bj {
 
-struct Acc160q {
-    u32 w[5];
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int i = 0; i < 5; i++) w[i] = 0;
-    }
-    __device__ __forceinline__ void fma(u64 a, u64 b) {
-        u32 hh, hl;
-        u64 lo;
-        gl::mul_limbs(a, b, hh, hl, lo);
-        u32 c;
-        w[0] = __builtin_addc(w[0], gl::lo32(lo), 0u, &c);
-        w[1] = __builtin_addc(w[1], gl::hi32(lo), c, &c);
-        w[2] = __builtin_addc(w[2], hl, c, &c);
-        w[3] = __builtin_addc(w[3], hh, c, &c);
-        w[4] += c;
-    }
-    __device__ __forceinline__ u64 reduce() const {
-        u64 r = gl::reduce_limbs(w[3], w[2], gl::pack(w[0], w[1]));
-        return gl::sub(r, (u64)w[4] << 32);
-    }
-};
-
-__device__ inline u64 inv_chain3(u64 x) {
-    auto sqn = [](u64 v, int n) { for (int i = 0; i < n; i++) v = gl::sqr(v); return v; };
-    u64 a1 = x, a2 = gl::mul(sqn(a1, 1), a1), a4 = gl::mul(sqn(a2, 2), a2), a8 = gl::mul(sqn(a4, 4), a4);
-    u64 a16 = gl::mul(sqn(a8, 8), a8), a24 = gl::mul(sqn(a16, 8), a8), a28 = gl::mul(sqn(a24, 4), a4);
-    u64 a30 = gl::mul(sqn(a28, 2), a2), a31 = gl::mul(sqn(a30, 1), a1);
-    u64 b = gl::sqr(a31), a32 = gl::mul(b, x);
-    return gl::mul(sqn(b, 32), a32);
-}
-__device__ __forceinline__ u64 mul7q(u64 a) { return gl::sub(gl::mul_pow2(a, 3), a); }
-
 // x_I = 7 * w_{qn}^{bitrev(I)} = 7 * T[I>>1] * (-1)^(I&1)
-__device__ __forceinline__ u64 lde_point(const u64 *tw, size_t I) {
-    u64 wi = tw[I >> 1];
-    if (I & 1) wi = gl::neg(wi);
-    return mul7q(wi);
-}
+__device__ __forceinline__ u64 lde_point(const u64 *tw, size_t I) { return gl::mul7(gl::domain_point(tw, I)); }
 
 struct GateDev {
     int kind, path_len, reps, var_stride, const_stride, num_terms;
@@ -93,9 +56,8 @@ quotient_gates_kernel(const u64 *vars, size_t var_stride, const u64 *consts, siz
             u64 c = gl::canon(consts[(size_t)b * const_stride + I]);
             sel = gl::mul(sel, G.path[b] ? c : gl::sub(1, c));
         }
-        Acc160q s0, s1;
-        s0.clear();
-        s1.clear();
+        gl::Acc160x2 s;
+        s.clear();
         const size_t cb0 = (size_t)G.path_len;
         u64 k0 = 0, k1 = 0, k2 = 0, k3 = 0;
         if (G.kind == 2) {
@@ -118,7 +80,7 @@ quotient_gates_kernel(const u64 *vars, size_t var_stride, const u64 *consts, siz
                 u64 a = VARQ(0), b = VARQ(1), c = VARQ(2), d = VARQ(3);
                 term = gl::sub(gl::add(gl::mul(c, k1), gl::mul(k0, gl::mul(a, b))), d);
             } else {                    // Reduction<4>: sum c_i v_i - r
-                Acc160q t;
+                gl::Acc160 t;
                 t.clear();
                 t.fma(VARQ(0), k0);
                 t.fma(VARQ(1), k1);
@@ -127,12 +89,11 @@ quotient_gates_kernel(const u64 *vars, size_t var_stride, const u64 *consts, siz
                 term = gl::sub(t.reduce(), VARQ(4));
             }
 #undef VARQ
-            s0.fma(term, alphas[2 * aoff]);
-            s1.fma(term, alphas[2 * aoff + 1]);
+            s.fma_base(term, alphas + 2 * aoff);
             aoff++;
         }
-        acc.c0 = gl::add(acc.c0, gl::mul(s0.reduce(), sel));
-        acc.c1 = gl::add(acc.c1, gl::mul(s1.reduce(), sel));
+        acc.c0 = gl::add(acc.c0, gl::mul(s.s0.reduce(), sel));
+        acc.c1 = gl::add(acc.c1, gl::mul(s.s1.reduce(), sel));
     }
     out0[I] = acc.c0;
     out1[I] = acc.c1;
@@ -186,7 +147,7 @@ quotient_gates_windowed_kernel(const u64 *vars, size_t var_stride, const u64 *co
 #pragma unroll
         for (int j = 0; j < 4; j++) k3[j] = gl::canon(consts[(size_t)(gw.path_len[3] + j) * const_stride + I]);
     }
-    Acc160q s0[4], s1[4];
+    gl::Acc160 s0[4], s1[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         s0[k].clear();
@@ -228,7 +189,7 @@ quotient_gates_windowed_kernel(const u64 *vars, size_t var_stride, const u64 *co
             for (int i = 0; i < GW_WINDOW / 5; i++) {
                 const int r = w * (GW_WINDOW / 5) + i;
                 if (r < gw.reps[3]) {
-                    Acc160q t;
+                    gl::Acc160 t;
                     t.clear();
                     t.fma(v[5 * i], k3[0]);
                     t.fma(v[5 * i + 1], k3[1]);
@@ -263,9 +224,8 @@ quotient_lookup_kernel(const u64 *lvars, size_t var_stride, const u64 *table_id,
                        LookupQArgs la, const u64 *alphas /* [reps+1][2] */, size_t Q, u64 *out0, u64 *out1) {
     const size_t I = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (I >= Q) return;
-    Acc160q s0, s1;
-    s0.clear();
-    s1.clear();
+    gl::Acc160x2 s;
+    s.clear();
     // table_id == nullptr: the table id is the last of the w + 1 variable columns of every sub-argument
     // (UseSpecializedColumnsWithTableIdAsVariable, lookup_argument_in_ext.rs:949-1000: capacity = w + 1, no constant column)
     const unsigned cps = table_id ? w : w + 1;
@@ -292,15 +252,10 @@ quotient_lookup_kernel(const u64 *lvars, size_t var_stride, const u64 *table_id,
         }
         gl::e2 t = gl::e2_mul(poly, d);
         t.c0 = gl::sub(t.c0, minus);
-        // (t0 + t1 u)(a0 + a1 u) = (t0 a0 + 7 t1 a1) + (t0 a1 + t1 a0) u
-        const u64 a0 = alphas[2 * i], a1 = alphas[2 * i + 1];
-        s0.fma(t.c0, a0);
-        s0.fma(t.c1, mul7q(a1));
-        s1.fma(t.c0, a1);
-        s1.fma(t.c1, a0);
+        s.fma_e2(t, alphas[2 * i], alphas[2 * i + 1]);
     }
-    out0[I] = gl::add(gl::canon(out0[I]), s0.reduce());
-    out1[I] = gl::add(gl::canon(out1[I]), s1.reduce());
+    out0[I] = gl::add(gl::canon(out0[I]), s.s0.reduce());
+    out1[I] = gl::add(gl::canon(out1[I]), s.s1.reduce());
 }
 
 // T = (T + alpha_L1 * (z - 1) * L1~(x) + copy-permutation chain) / (x^n - 1)
@@ -335,17 +290,16 @@ quotient_copy_perm_kernel(const u64 *vars, size_t var_stride, const u64 *sigmas,
     const u32 i_br = (u32)(I & (n - 1));
     const u64 x = lde_point(tw, I0 + I);
     const gl::e2 xb = SMALLK ? gl::e2{gl::mul_weak(x, ca.beta.c0), gl::mul_weak(x, ca.beta.c1)} : gl::e2{0, 0};   // x * beta, once per point
-    Acc160q s0, s1;
-    s0.clear();
-    s1.clear();
+    gl::Acc160x2 s;
+    s.clear();
     const gl::e2 zv{gl::canon(stage2[I]), gl::canon(stage2[s2_stride + I])};
     {   // (z - 1) * (x^n - 1) / (x - 1) * alpha
-        u64 l1 = gl::mul(ca.xn_minus_one[coset], inv_xm1 ? inv_xm1[I] : inv_chain3(gl::sub(x, 1)));
+        u64 l1 = gl::mul(ca.xn_minus_one[coset], inv_xm1 ? inv_xm1[I] : gl::inv_chain(gl::sub(x, 1)));
         gl::e2 t{gl::mul(gl::sub(zv.c0, 1), l1), gl::mul(zv.c1, l1)};
-        s0.fma(t.c0, ca.alpha_l1.c0);
-        s0.fma(t.c1, mul7q(ca.alpha_l1.c1));
-        s1.fma(t.c0, ca.alpha_l1.c1);
-        s1.fma(t.c1, ca.alpha_l1.c0);
+        s.s0.fma(t.c0, ca.alpha_l1.c0);
+        s.s0.fma(t.c1, gl::mul7(ca.alpha_l1.c1));
+        s.s1.fma(t.c0, ca.alpha_l1.c1);
+        s.s1.fma(t.c1, ca.alpha_l1.c0);
     }
     // z(omega * x): next natural index inside the coset
     const u32 i_next = gl::bitrev32((gl::bitrev32(i_br, log_n) + 1) & (u32)(n - 1), log_n);
@@ -372,14 +326,10 @@ quotient_copy_perm_kernel(const u64 *vars, size_t var_stride, const u64 *sigmas,
             rhs = gl::e2_mul_weak(rhs, nm);
         }
         const gl::e2 t{gl::sub_weak(lhs.c0, rhs.c0), gl::sub_weak(lhs.c1, rhs.c1)};
-        const u64 a0 = alphas[2 * j], a1 = alphas[2 * j + 1];
-        s0.fma(t.c0, a0);
-        s0.fma(t.c1, mul7q(a1));
-        s1.fma(t.c0, a1);
-        s1.fma(t.c1, a0);
+        s.fma_e2(t, alphas[2 * j], alphas[2 * j + 1]);
     }
-    u64 r0 = gl::add(gl::canon(out0[I]), s0.reduce());
-    u64 r1 = gl::add(gl::canon(out1[I]), s1.reduce());
+    u64 r0 = gl::add(gl::canon(out0[I]), s.s0.reduce());
+    u64 r1 = gl::add(gl::canon(out1[I]), s.s1.reduce());
     const u64 vi = ca.vanishing_inv[coset];
     out0[I] = gl::mul(r0, vi);
     out1[I] = gl::mul(r1, vi);
@@ -389,7 +339,7 @@ quotient_copy_perm_kernel(const u64 *vars, size_t var_stride, const u64 *sigmas,
 // fixed exponentiation is ~75 products per point, 3 % of quotient_copy_perm's arithmetic at 92 columns)
 __global__ void __launch_bounds__(256) inv_x_minus_one_kernel(const u64 *tw, size_t Q, size_t I0, u64 *out) {
     const size_t I = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I < Q) out[I] = inv_chain3(gl::sub(lde_point(tw, I0 + I), 1));
+    if (I < Q) out[I] = gl::inv_chain(gl::sub(lde_point(tw, I0 + I), 1));
 }
 
 // Sharded quotient: rank i has evaluated the quotient terms on the first E = q n / W points of its own LDE range
@@ -407,7 +357,7 @@ combine_residues_kernel(const u64 *__restrict__ residues, unsigned W, size_t E, 
     u64 r[8];
     for (unsigned i = 0; i < W; i++) r[i] = residues[((size_t)i * n_cols + col) * E + k];
     for (unsigned j = 0; j < W; j++) {
-        Acc160q acc;
+        gl::Acc160 acc;
         acc.clear();
         for (unsigned i = 0; i < W; i++) acc.fma(r[i], ca.vinv[j * W + i]);
         out[(size_t)col * W * E + (size_t)j * E + k] = acc.reduce();

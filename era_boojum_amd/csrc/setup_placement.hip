@@ -47,15 +47,8 @@ __global__ void __launch_bounds__(256) iota_kernel(u32 *out, size_t count) {
     if (i < count) out[i] = (u32)i;
 }
 
-// omega_n^r from the bit-reversed forward twiddle table, as stage2.hip::omega_pow_nat
-__device__ __forceinline__ u64 omega_pow_nat(const u64 *tw, unsigned log_n, u32 r) {
-    if (log_n == 0) return 1;
-    const u32 half = 1u << (log_n - 1);
-    const u64 w = tw[gl::bitrev32(r & (half - 1), log_n - 1)];
-    return (r & half) ? gl::neg(w) : w;
-}
 __device__ __forceinline__ u64 cell_id(const u64 *tw, const u64 *non_res, unsigned log_n, u32 cell) {
-    return gl::mul(non_res[cell >> log_n], omega_pow_nat(tw, log_n, cell & ((1u << log_n) - 1)));
+    return gl::mul(non_res[cell >> log_n], gl::omega_pow_nat(tw, log_n, cell & ((1u << log_n) - 1)));
 }
 
 __global__ void __launch_bounds__(256)

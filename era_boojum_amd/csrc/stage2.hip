@@ -15,27 +15,6 @@ using gl::u32;
 
 namespace bj {
 
-__device__ inline u64 inv_chain2(u64 x) {   // x^(p-2), p - 2 = (2^32 - 2) * 2^32 + (2^32 - 1)
-    auto sqn = [](u64 v, int n) { for (int i = 0; i < n; i++) v = gl::sqr(v); return v; };
-    u64 a1 = x, a2 = gl::mul(sqn(a1, 1), a1), a4 = gl::mul(sqn(a2, 2), a2), a8 = gl::mul(sqn(a4, 4), a4);
-    u64 a16 = gl::mul(sqn(a8, 8), a8), a24 = gl::mul(sqn(a16, 8), a8), a28 = gl::mul(sqn(a24, 4), a4);
-    u64 a30 = gl::mul(sqn(a28, 2), a2), a31 = gl::mul(sqn(a30, 1), a1);
-    u64 b = gl::sqr(a31), a32 = gl::mul(b, x);
-    return gl::mul(sqn(b, 32), a32);
-}
-__device__ __forceinline__ gl::e2 e2_inv_dev(gl::e2 a) {
-    u64 seven = gl::sub(gl::mul_pow2(gl::sqr(a.c1), 3), gl::sqr(a.c1));
-    u64 ni = inv_chain2(gl::sub(gl::sqr(a.c0), seven));
-    return {gl::mul(a.c0, ni), gl::neg(gl::mul(a.c1, ni))};
-}
-// omega_n^r for a natural index r from the bit-reversed forward twiddle table (T[j] = w^bitrev(j), j < n/2)
-__device__ __forceinline__ u64 omega_pow_nat(const u64 *tw, unsigned log_n, u32 r) {
-    if (log_n == 0) return 1;
-    u32 half = 1u << (log_n - 1);
-    u64 w = tw[gl::bitrev32(r & (half - 1), log_n - 1)];
-    return (r & half) ? gl::neg(w) : w;
-}
-
 // P[j][row] = prod_{i in chunk j} (w_i + beta*k_i*x + gamma) / (w_i + beta*sigma_i + gamma);  out: [n_chunks][2][n]
 // A lane handles RAT_PTS rows (256 apart, so every access stays coalesced) of one chunk and inverts their denominators
 // together (Montgomery's trick: one F_p^2 inversion = one x^(p-2) chain per RAT_PTS rows instead of per row — the inversion
@@ -55,7 +34,7 @@ copy_perm_rational_kernel(const u64 *vars, size_t var_stride, const u64 *sigmas,
 #pragma unroll
     for (int k = 0; k < RAT_PTS; k++) {
         const size_t r = base + (size_t)k * 256;
-        const u64 x = r < n ? omega_pow_nat(tw, log_n, (u32)r) : 0;
+        const u64 x = r < n ? gl::omega_pow_nat(tw, log_n, (u32)r) : 0;
         xb0[k] = gl::mul_weak(x, beta.c0);
         xb1[k] = gl::mul_weak(x, beta.c1);
         num[k] = {1, 0};
@@ -91,7 +70,7 @@ copy_perm_rational_kernel(const u64 *vars, size_t var_stride, const u64 *sigmas,
         pre[k] = run;
         run = gl::e2_mul(run, den[k]);
     }
-    gl::e2 inv_run = e2_inv_dev(run);
+    gl::e2 inv_run = gl::e2_inv_chain(run);
 #pragma unroll
     for (int k = RAT_PTS - 1; k >= 0; k--) {
         const gl::e2 inv_k = gl::e2_mul(inv_run, pre[k]);
@@ -271,7 +250,7 @@ lookup_polys_kernel(const u64 *lvars, size_t var_stride, const u64 *table_id, co
             pre[k] = run;
             run = gl::e2_mul(run, acc);
         }
-        gl::e2 inv_run = e2_inv_dev(run);
+        gl::e2 inv_run = gl::e2_inv_chain(run);
 #pragma unroll
         for (int k = (int)LK_GROUP - 1; k >= 0; k--) {
             if ((unsigned)k >= cnt) continue;
