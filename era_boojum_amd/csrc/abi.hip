@@ -2,6 +2,7 @@
 // Public contract: include/boojum_hip.h.  No CPU fallback anywhere in this file: every entry point either
 // enqueues HIP work on the context's device or returns an error.
 #include "ctx.h"
+#include "ntt_plan.h"
 
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -454,32 +455,51 @@ int bj_ntt_forward_batch(bj_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, uns
     return BJ_OK;
 }
 
-int bj_intt_batch(bj_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log_n, unsigned n_cols,
-                  size_t col_stride, uint64_t coset) {
-    if (int rc = bind(ctx)) return rc;
+// ifft_natural_to_natural (fft/mod.rs:464-491): butterflies with the inverse twiddles into scratch (bit-reversed), then one of two
+// endings into d_out.  Natural order: un-reverse and scale by 1/n and coset^-i.  Tiled (main domain, where the two-pass plan runs,
+// columns on 16-byte boundaries; d_in may equal d_out): ntt_local12_pair_tiled in place of the plan's last pass stores the
+// bit-reversed, 1/n-scaled positions directly, two HBM passes and no bit-reversal pass.  Columns go in groups whose scratch stays
+// below 1 GiB (the groups of a wide batch run back to back on the stream; a 2^23-row witness would otherwise keep 6 GB of scratch
+// per context: eight sharded ranks on one device could not afford it).
+static int intt_groups(bj_ctx *ctx, const u64 *d_in, size_t in_col_stride, u64 *d_out, size_t out_col_stride, unsigned log_n,
+                       unsigned n_cols, u64 coset, bool to_tiled) {
     if (n_cols == 0) return BJ_OK;
-    if (int rc = check_ntt_args(ctx, "bj_intt_batch", d_in, d_out, log_n, n_cols, col_stride)) return rc;
+    if (to_tiled && !(bj::mono_tiled(log_n) && bj::ntt_aligned16(d_in, d_out, in_col_stride, out_col_stride)))
+        return fail(ctx, BJ_ERR_UNSUPPORTED, "inverse transform into the tiled layout: 2^22-word columns on 16-byte boundaries only");
     if (int rc = ensure_twiddles(ctx, log_n, true)) return rc;
     coset = gl::canon(coset);
     if (coset == 0) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_intt_batch: coset shift must be non-zero");
     const size_t n = (size_t)1 << log_n;
-    // butterflies with inverse twiddles into scratch (bit-reversed), then un-reverse + scale into d_out — in groups of columns whose
-    // scratch stays below 1 GiB (the groups of a wide batch run back to back on the stream; a 2^23-row witness would otherwise
-    // keep 6 GB of scratch per context: eight sharded ranks on one device could not afford it)
     const size_t cap_elems = (size_t)1 << 27;
     unsigned group = n >= cap_elems ? 1u : (unsigned)(cap_elems / n);
     if (group > n_cols) group = n_cols;
     if (int rc = ensure_scratch(ctx, (size_t)group * n)) return rc;
     const u64 n_inv = log_n ? gl::inv(gl::canon((u64)n % gl::P)) : 1;
     const u64 step = coset == 1 ? 1 : gl::inv(coset);
+    if (to_tiled && !ctx->tw_inv_scaled22) {   // a table for 2^22 is a prefix of every larger one: built once per context, whatever tw_inv grows to
+        BJ_HIP(ctx, hipMalloc((void **)&ctx->tw_inv_scaled22, (n / 2) * sizeof(u64)));
+        bj::launch_scale_table(ctx->tw_inv, ctx->tw_inv_scaled22, n / 2, n_inv, ctx->stream);
+    }
     for (unsigned c0 = 0; c0 < n_cols; c0 += group) {
         const unsigned nc = n_cols - c0 < group ? n_cols - c0 : group;
-        bj::launch_ntt_passes(d_in + (size_t)c0 * col_stride, ctx->d_scratch, ctx->tw_inv, nullptr, log_n, nc, 1, col_stride, n, ctx->stream,
-                              bj::front_table(ctx));
-        bj::launch_bitrev_scale(ctx->d_scratch, d_out + (size_t)c0 * col_stride, log_n, nc, n, col_stride, n_inv, step, ctx->stream);
+        u64 *out = d_out + (size_t)c0 * out_col_stride;
+        bj::launch_ntt_passes(d_in + (size_t)c0 * in_col_stride, ctx->d_scratch, ctx->tw_inv, nullptr, log_n, nc, 1, in_col_stride, n, ctx->stream,
+                              bj::front_table(ctx), false, to_tiled);
+        if (to_tiled)
+            bj::launch_ntt_local12_pair_tiled(ctx->d_scratch, out, ctx->tw_inv, ctx->tw_inv_scaled22, n_inv, nc, n, out_col_stride, ctx->stream);
+        else
+            bj::launch_bitrev_scale(ctx->d_scratch, out, log_n, nc, n, out_col_stride, n_inv, step, ctx->stream);
     }
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
+}
+
+int bj_intt_batch(bj_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsigned log_n, unsigned n_cols,
+                  size_t col_stride, uint64_t coset) {
+    if (int rc = bind(ctx)) return rc;
+    if (n_cols == 0) return BJ_OK;
+    if (int rc = check_ntt_args(ctx, "bj_intt_batch", d_in, d_out, log_n, n_cols, col_stride)) return rc;
+    return intt_groups(ctx, d_in, col_stride, d_out, col_stride, log_n, n_cols, coset, false);
 }
 
 extern "C++" {
@@ -489,7 +509,7 @@ namespace bj {
 int lde_cosets_strided(bj_ctx *ctx, const u64 *d_mono, size_t in_col_stride, u64 *d_out, size_t out_col_stride,
                        unsigned log_n, unsigned n_cols, unsigned log_lde, unsigned coset_begin, unsigned coset_count, bool tiled_in) {
     if (int rc = ensure_twiddles(ctx, log_n, false)) return rc;
-    if (tiled_in && !bj::ntt_two_pass_applies(d_mono, d_out, log_n, coset_count, in_col_stride, out_col_stride))
+    if (tiled_in && !bj::ntt_two_pass_applies(d_mono, d_out, log_n, in_col_stride, out_col_stride))
         return fail(ctx, BJ_ERR_UNSUPPORTED, "LDE of tiled monomials: 2^22-word columns on 16-byte boundaries with the two-pass plan enabled only");
     u64 shifts[64];
     u64 w = gl::omega(log_n + log_lde);
@@ -503,34 +523,10 @@ int lde_cosets_strided(bj_ctx *ctx, const u64 *d_mono, size_t in_col_stride, u64
 }
 
 // The monomial layout bj_prove keeps for 2^log_n-row columns: tiled (ntt_r16.hip) where the two-pass plan runs, natural elsewhere.
-bool mono_tiled(unsigned log_n) { return log_n == 22 && bj::env().ntt_two_pass && bj::env().mono_tiled; }
+bool mono_tiled(unsigned log_n) { return bj::env().mono_tiled && bj::ntt_plan_is_two_pass({log_n, true, bj::env().ntt_two_pass}); }
 
-// ifft_natural_to_natural (fft/mod.rs:464-491) on the main domain with the result left in the TILED layout: front pass into scratch,
-// last pass storing the bit-reversed, 1/n-scaled positions directly — two HBM passes, no bit-reversal pass.  Columns on 16-byte
-// boundaries; d_in may equal d_out.
 int intt_to_tiled(bj_ctx *ctx, const u64 *d_in, size_t in_col_stride, u64 *d_out, size_t out_col_stride, unsigned log_n, unsigned n_cols) {
-    if (n_cols == 0) return BJ_OK;
-    if (!mono_tiled(log_n) || ((uintptr_t)d_in % 16) || ((uintptr_t)d_out % 16) || in_col_stride % 2 || out_col_stride % 2)
-        return fail(ctx, BJ_ERR_UNSUPPORTED, "inverse transform into the tiled layout: 2^22-word columns on 16-byte boundaries only");
-    if (int rc = ensure_twiddles(ctx, log_n, true)) return rc;
-    const size_t n = (size_t)1 << log_n;
-    const size_t cap_elems = (size_t)1 << 27;
-    unsigned group = (unsigned)(cap_elems / n);
-    if (group > n_cols) group = n_cols;
-    if (int rc = ensure_scratch(ctx, (size_t)group * n)) return rc;
-    const u64 n_inv = gl::inv(gl::canon((u64)n % gl::P));
-    if (!ctx->tw_inv_scaled22) {   // a table for 2^22 is a prefix of every larger one: built once per context, whatever tw_inv grows to
-        BJ_HIP(ctx, hipMalloc((void **)&ctx->tw_inv_scaled22, (n / 2) * sizeof(u64)));
-        bj::launch_scale_table(ctx->tw_inv, ctx->tw_inv_scaled22, n / 2, n_inv, ctx->stream);
-    }
-    for (unsigned c0 = 0; c0 < n_cols; c0 += group) {
-        const unsigned nc = n_cols - c0 < group ? n_cols - c0 : group;
-        bj::launch_ntt_front10(d_in + (size_t)c0 * in_col_stride, ctx->d_scratch, ctx->tw_inv, nullptr, bj::front_table(ctx), log_n, nc, 1,
-                               in_col_stride, n, ctx->stream);
-        bj::launch_ntt_local12_pair_tiled(ctx->d_scratch, d_out + (size_t)c0 * out_col_stride, ctx->tw_inv, ctx->tw_inv_scaled22, n_inv, nc, n, out_col_stride, ctx->stream);
-    }
-    BJ_CHECK_LAUNCH(ctx);
-    return BJ_OK;
+    return intt_groups(ctx, d_in, in_col_stride, d_out, out_col_stride, log_n, n_cols, 1, true);
 }
 }  // namespace bj
 }  // extern "C++"

@@ -14,7 +14,7 @@ typedef uint64_t u64;
 // setenv, no per-proof lookups, and every context of a process (one per GPU, each on its own host thread) sees the same plan.
 // bj_env_reload() re-reads them for tests that exercise both sides of a switch in one process (not thread-safe by contract).
 struct EnvConfig {
-    bool ntt_two_pass = true;           // BJ_NTT_TWO_PASS=0: 2^22-point transforms as 4 + 8 + 10 rounds (rounds 3-5) instead of 10 + 12
+    bool ntt_two_pass = true;           // BJ_NTT_TWO_PASS=0: 2^22-point transforms as 4 + 8 + 10 rounds instead of 10 + 12
     bool mono_tiled = true;             // BJ_MONO_TILED=0: bj_prove keeps 2^22-row monomials in natural order (inverse transforms end in a bit-reversal pass)
     bool gate_no_aot = false, gate_no_fuse = false, gate_no_jit = false;
     bool gates_windowed = true;         // BJ_GATES_WINDOWED=0: per-gate kernel for the hand-written kinds
@@ -38,39 +38,43 @@ void env_reload();
 // ntt.hip
 void launch_twiddles(u64 *d_out, unsigned log_n, bool inverse, hipStream_t s);
 void launch_round_scales(u64 *d_out, const u64 *h_shifts, unsigned n_cosets, unsigned log_n, hipStream_t s);
-// d_front_table: BJ_FRONT_TABLE_WORDS words of device scratch for the twiddle table of the two-pass plan (nullptr: never that plan)
+// What every NTT pass launcher is given: the columns it reads and writes, the twiddle table and the shape of the batch.
+struct NttIo {
+    const u64 *in;
+    u64 *out;
+    const u64 *tw;            // bit-reversed twiddle table
+    const u64 *round_scale;   // [n_cosets][32] per-round twiddle scale, or nullptr (plain subgroup transform)
+    unsigned log_n, n_cols, n_cosets;
+    size_t in_col_stride;     // elements between input columns
+    size_t in_coset_stride;   // 0 when every coset reads the same input column (the first pass), n when in place
+    size_t out_col_stride;    // elements between output columns (each column holds n_cosets * n outputs)
+};
+// Runs the plan of ntt_plan.h for 1..64 cosets.  d_front_table: BJ_FRONT_TABLE_WORDS words of device scratch for the twiddle table
+// of the two-pass plan; tiled_in: the caller's columns are in the tiled layout (two-pass plan only); skip_last: stop in front of
+// the plan's last pass (the caller runs its own in its place)
 constexpr size_t BJ_FRONT_TABLE_WORDS = 64 * 1024;
 void launch_ntt_passes(const u64 *d_in, u64 *d_out, const u64 *d_tw, const u64 *d_round_scale, unsigned log_n,
                        unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t out_col_stride, hipStream_t s,
-                       u64 *d_front_table = nullptr, bool tiled_in = false);
+                       u64 *d_front_table, bool tiled_in = false, bool skip_last = false);
 // true when launch_ntt_passes would take the two-pass plan for these arguments (the only plan that reads the tiled layout)
-bool ntt_two_pass_applies(const u64 *d_in, const u64 *d_out, unsigned log_n, unsigned n_cosets, size_t in_col_stride, size_t out_col_stride);
+bool ntt_two_pass_applies(const u64 *d_in, const u64 *d_out, unsigned log_n, size_t in_col_stride, size_t out_col_stride);
 void launch_bitrev_scale(const u64 *d_in, u64 *d_out, unsigned log_n, unsigned n_cols, size_t in_col_stride,
                          size_t out_col_stride, u64 scale, u64 step, hipStream_t s);
 void launch_canonicalize(u64 *d, size_t n, hipStream_t s);
 void launch_field_op(int op, const u64 *a, const u64 *b, u64 *out, size_t n, hipStream_t s);
 
 // ntt_r16.hip (register-radix-16 passes)
-void launch_ntt_local12(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, unsigned log_n,
-                        unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride,
-                        size_t out_col_stride, unsigned rounds /* 12, or 10 / 9 behind launch_ntt_first4 / first5 */, hipStream_t s);
-void launch_ntt_front10(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, u64 *d_table, unsigned log_n, unsigned n_cols,
-                        unsigned n_cosets, size_t in_col_stride, size_t out_col_stride, hipStream_t s, bool tiled_in = false);
+void launch_ntt_local12(const NttIo &io, unsigned rounds /* 12, or 10 / 9 behind launch_ntt_first4 / first5 */, hipStream_t s);
+void launch_ntt_strided(const NttIo &io, unsigned r0, unsigned rounds /* 8 or 4 */, hipStream_t s);
+void launch_ntt_first4(const NttIo &io, hipStream_t s);   // 16-byte accesses: ntt_aligned16 columns only
+void launch_ntt_first5(const NttIo &io, hipStream_t s);
+// first ten rounds of all cosets (log_n == 22, ntt_aligned16 columns); d_table: n_cosets * 1024 words of device scratch
+void launch_ntt_front10(const NttIo &io, u64 *d_table, bool tiled_in, hipStream_t s);
 // 2^22-word columns in the tiled layout (ntt_r16.hip: tiled_index): last pass of an inverse transform storing it, re-layout kernel
 void launch_ntt_local12_pair_tiled(const u64 *in, u64 *out, const u64 *tw, const u64 *tw_scaled /* tw[j] * scale, j < 2^21 */, u64 scale,
                                    unsigned n_cols, size_t in_col_stride, size_t out_col_stride, hipStream_t s);
 void launch_scale_table(const u64 *in, u64 *out, size_t count, u64 scale, hipStream_t s);
 void launch_tiled_permute(const u64 *in, u64 *out, unsigned n_cols, size_t in_col_stride, size_t out_col_stride, bool to_tiled, hipStream_t s);
-void launch_ntt_first5(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, unsigned log_n, unsigned n_cols,
-                       unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride, size_t out_col_stride, hipStream_t s);
-void launch_ntt_first4(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, unsigned log_n, unsigned n_cols,
-                       unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride, size_t out_col_stride, hipStream_t s);
-void launch_ntt_strided8(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, unsigned log_n, unsigned r0,
-                         unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride,
-                         size_t out_col_stride, hipStream_t s);
-void launch_ntt_strided4(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, unsigned log_n, unsigned r0,
-                         unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride,
-                         size_t out_col_stride, hipStream_t s);
 
 // tree_hash.hip: the Merkle-tree entry points, dispatched on hasher = BJ_HASHER_* (what each hasher contributes: tree_plan.h)
 void launch_tree_leaves(int hasher, const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,

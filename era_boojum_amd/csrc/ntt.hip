@@ -16,9 +16,11 @@
 // multiplying the round-r twiddle by shift^(n/2^(r+1)) (the factor shift^(i mod n/2^(r+1)) commutes through the
 // butterfly), so the kernel takes a per-round scale table instead.  Same residues, one HBM pass fewer.
 #include "gl.h"
+#include <cassert>
 #include <cstdint>
 #include <cstdlib>
 #include "kernels.h"
+#include "ntt_plan.h"
 
 using gl::u64;
 using gl::u32;
@@ -46,8 +48,8 @@ void launch_twiddles(u64 *d_out, unsigned log_n, bool inverse, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// generic LDS pass (any R + Wl <= 13).  v0 kernel: correct for every shape, used for small sizes and as the
-// fallback; the specialised register-radix kernels below take over for the big shapes.
+// generic LDS pass (any R + Wl <= 13).  v0 kernel: correct for every shape, run for columns shorter than 2^12 (one pass
+// of log_n rounds, Wl = 0); the specialised register-radix kernels of ntt_r16.hip take over for the big shapes.
 // ---------------------------------------------------------------------------------------------------------
 struct PassArgs {
     const u64 *in;
@@ -130,7 +132,7 @@ void launch_round_scales(u64 *d_out, const u64 *h_shifts, unsigned n_cosets, uns
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Remainder pass: the first R = 1..3 rounds (largest strides) of a transform whose round count is not 12 + 4k.
+// Remainder pass: the first round (largest stride) of a transform of 13 + 4k rounds; the kernel is written for R = 1..3.
 // A thread owns the 2^R elements {i + m * n/2^R} of one column, reads them ONCE and produces every coset from them
 // (an LDE reads its monomials once per column instead of once per coset); all twiddles are uniform per coset
 // (T[g] * sc[r], g < 2^r) and are staged in LDS by the first lanes.  No tile, no barrier in the data path: every access
@@ -213,166 +215,58 @@ __global__ void __launch_bounds__(256) ntt_first_rounds_kernel(PassArgs a, unsig
     }
 }
 
-static void launch_first_rounds(const u64 *src, u64 *d_out, const u64 *d_tw, const u64 *d_round_scale, unsigned log_n,
-                                unsigned R, unsigned n_cols, unsigned n_cosets, size_t src_col_stride,
-                                size_t src_coset_stride, size_t out_col_stride, hipStream_t s) {
-    PassArgs a{src, d_out, d_tw, d_round_scale, log_n, 0, R, 0, src_col_stride, src_coset_stride, out_col_stride};
-    const size_t quarter = ((size_t)1 << log_n) >> R;
+static void launch_first_round(const NttIo &io, hipStream_t s) {
+    PassArgs a{io.in, io.out, io.tw, io.round_scale, io.log_n, 0, 1, 0, io.in_col_stride, io.in_coset_stride, io.out_col_stride};
+    const size_t half = ((size_t)1 << io.log_n) >> 1;
     // two indices per lane need 16-byte aligned columns and an even slice
-    const bool wide = quarter % 512 == 0 && src_col_stride % 2 == 0 && src_coset_stride % 2 == 0 && out_col_stride % 2 == 0 &&
-                      ((uintptr_t)src % 16) == 0 && ((uintptr_t)d_out % 16) == 0;
-    dim3 grid((unsigned)((quarter / (wide ? 2 : 1) + 255) / 256), n_cols, 1);
-    if (wide) {
-        if (R == 1)
-            hipLaunchKernelGGL((ntt_first_rounds_kernel<1, 2>), grid, dim3(256), 0, s, a, n_cosets);
-        else if (R == 2)
-            hipLaunchKernelGGL((ntt_first_rounds_kernel<2, 2>), grid, dim3(256), 0, s, a, n_cosets);
-        else
-            hipLaunchKernelGGL((ntt_first_rounds_kernel<3, 2>), grid, dim3(256), 0, s, a, n_cosets);
-    } else if (R == 1)
-        hipLaunchKernelGGL((ntt_first_rounds_kernel<1, 1>), grid, dim3(256), 0, s, a, n_cosets);
-    else if (R == 2)
-        hipLaunchKernelGGL((ntt_first_rounds_kernel<2, 1>), grid, dim3(256), 0, s, a, n_cosets);
+    const bool wide = half % 512 == 0 && io.in_coset_stride % 2 == 0 && ntt_aligned16(io.in, io.out, io.in_col_stride, io.out_col_stride);
+    dim3 grid((unsigned)((half / (wide ? 2 : 1) + 255) / 256), io.n_cols, 1);
+    if (wide)
+        hipLaunchKernelGGL((ntt_first_rounds_kernel<1, 2>), grid, dim3(256), 0, s, a, io.n_cosets);
     else
-        hipLaunchKernelGGL((ntt_first_rounds_kernel<3, 1>), grid, dim3(256), 0, s, a, n_cosets);
+        hipLaunchKernelGGL((ntt_first_rounds_kernel<1, 1>), grid, dim3(256), 0, s, a, io.n_cosets);
 }
 
-// Plan: last pass local with up to LOCAL_MAX rounds; earlier rounds in strided passes of <= STRIDED_MAX rounds.
-static constexpr unsigned LOCAL_MAX = 12, STRIDED_MAX = 8, TILE_LOG = 12;
-
-static void launch_generic_pass(const u64 *src, u64 *d_out, const u64 *d_tw, const u64 *d_round_scale,
-                                unsigned log_n, unsigned r0, unsigned R, unsigned Wl, unsigned n_cols,
-                                unsigned n_cosets, size_t src_col_stride, size_t src_coset_stride,
-                                size_t out_col_stride, hipStream_t s) {
-    PassArgs a{src, d_out, d_tw, d_round_scale, log_n, r0, R, Wl, src_col_stride, src_coset_stride, out_col_stride};
-    unsigned tiles = 1u << (log_n - R - Wl);
-    size_t lds = ((size_t)8) << (R + Wl);
-    unsigned tpb = (1u << (R + Wl)) / 2;
+// the whole transform of a column shorter than 2^12 in one workgroup per column and coset (log_n = 0: the canonicalising copy)
+static void launch_generic_pass(const NttIo &io, hipStream_t s) {
+    const unsigned R = io.log_n;
+    PassArgs a{io.in, io.out, io.tw, io.round_scale, io.log_n, 0, R, 0, io.in_col_stride, io.in_coset_stride, io.out_col_stride};
+    size_t lds = ((size_t)8) << R;
+    unsigned tpb = (1u << R) / 2;
     if (tpb > 256) tpb = 256;
     if (tpb < 64) tpb = 64;
-    hipLaunchKernelGGL(ntt_pass_generic_kernel, dim3(tiles, n_cols, n_cosets), dim3(tpb), lds, s, a);
+    hipLaunchKernelGGL(ntt_pass_generic_kernel, dim3(1, io.n_cols, io.n_cosets), dim3(tpb), lds, s, a);
 }
 
-// Pass plan.  log_n < 12: generic LDS passes.  Otherwise the last 12, 10 or 9 rounds run in ntt_local12 and the rounds in front
-// of it in radix-16 strided passes of 8 or 4 rounds, behind a front pass that reads the caller's column once for every coset
-// (up to 64 cosets):
-//   2^22, 16-byte columns   ntt_front10 + ntt_local12: two passes (BJ_NTT_TWO_PASS=0: the 14 + 4k plan below)
-//   14 + 4k rounds          ntt_first4, the local pass runs 10 (ntt_first5 and 9 when the columns are not on 16-byte boundaries)
-//   15 + 4k rounds          ntt_first5, the local pass runs 10
-//   13 + 4k rounds          ntt_first_rounds for the one remainder round
-// Above 64 cosets the 1..3 remainder rounds of a transform not of the form 12 + 4k take one generic strided pass at the front.
-bool ntt_two_pass_applies(const u64 *d_in, const u64 *d_out, unsigned log_n, unsigned n_cosets, size_t in_col_stride, size_t out_col_stride) {
-    const bool io16 = ((uintptr_t)d_out % 16) == 0 && out_col_stride % 2 == 0 && ((uintptr_t)d_in % 16) == 0 && in_col_stride % 2 == 0;
-    return log_n == 22 && n_cosets <= 64 && io16 && bj::env().ntt_two_pass;
+bool ntt_two_pass_applies(const u64 *d_in, const u64 *d_out, unsigned log_n, size_t in_col_stride, size_t out_col_stride) {
+    return ntt_plan_is_two_pass({log_n, ntt_aligned16(d_in, d_out, in_col_stride, out_col_stride), env().ntt_two_pass});
 }
+
+// The plan is ntt_plan.h's; this runs it.  The first pass reads the caller's column (shared by all cosets), later passes run in
+// place on d_out.
 void launch_ntt_passes(const u64 *d_in, u64 *d_out, const u64 *d_tw, const u64 *d_round_scale, unsigned log_n,
                        unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t out_col_stride,
-                       hipStream_t s, u64 *d_front_table, bool tiled_in) {
-    const size_t n = (size_t)1 << log_n;
-    if (log_n == 0) {  // size-1 transform: canonicalising copy
-        launch_generic_pass(d_in, d_out, d_tw, nullptr, 0, 0, 0, 0, n_cols, n_cosets, in_col_stride, 0,
-                            out_col_stride, s);
-        return;
-    }
-    // the first pass reads the caller's column (shared by all cosets); later passes run in place on d_out
-    const u64 *src = d_in;
-    size_t src_col_stride = in_col_stride, src_coset_stride = 0;
-    unsigned r0 = 0;
-    auto advance = [&](unsigned R) {
-        r0 += R;
-        src = d_out;
-        src_col_stride = out_col_stride;
-        src_coset_stride = n;
-    };
-    if (log_n < 12) {
-        unsigned local = log_n < LOCAL_MAX ? log_n : LOCAL_MAX;
-        unsigned rest = log_n - local;
-        unsigned n_strided = (rest + STRIDED_MAX - 1) / STRIDED_MAX;
-        for (unsigned p = 0; p < n_strided; p++) {
-            unsigned R = rest / n_strided + (p < rest % n_strided ? 1 : 0);
-            unsigned rem_log = log_n - r0 - R;
-            unsigned Wl = TILE_LOG - R;
-            if (Wl > rem_log) Wl = rem_log;
-            launch_generic_pass(src, d_out, d_tw, d_round_scale, log_n, r0, R, Wl, n_cols, n_cosets, src_col_stride,
-                                src_coset_stride, out_col_stride, s);
-            advance(R);
+                       hipStream_t s, u64 *d_front_table, bool tiled_in, bool skip_last) {
+    assert(n_cosets >= 1 && n_cosets <= 64);   // ShiftArgs, the front passes' LDS twiddles and the front table hold 64
+    const NttPlan plan = ntt_plan({log_n, ntt_aligned16(d_in, d_out, in_col_stride, out_col_stride), env().ntt_two_pass});
+    assert(!tiled_in || plan.pass[0].kind == NttPassKind::Front10);
+    NttIo io{d_in, d_out, d_tw, d_round_scale, log_n, n_cols, n_cosets, in_col_stride, 0, out_col_stride};
+    for (unsigned i = 0; i < plan.n_passes - (skip_last ? 1 : 0); i++) {
+        const NttPass &p = plan.pass[i];
+        switch (p.kind) {
+        case NttPassKind::Generic: launch_generic_pass(io, s); break;
+        case NttPassKind::FirstRound: launch_first_round(io, s); break;
+        case NttPassKind::First4: launch_ntt_first4(io, s); break;
+        case NttPassKind::First5: launch_ntt_first5(io, s); break;
+        case NttPassKind::Front10: launch_ntt_front10(io, d_front_table, tiled_in, s); break;
+        case NttPassKind::Strided4:
+        case NttPassKind::Strided8: launch_ntt_strided(io, p.r0, p.rounds, s); break;
+        case NttPassKind::Local: launch_ntt_local12(io, p.rounds, s); break;
         }
-        launch_generic_pass(src, d_out, d_tw, d_round_scale, log_n, r0, local, 0, n_cols, n_cosets, src_col_stride,
-                            src_coset_stride, out_col_stride, s);
-        return;
+        io.in = d_out;
+        io.in_col_stride = out_col_stride;
+        io.in_coset_stride = (size_t)1 << log_n;
     }
-    unsigned front = log_n - 12;
-    // 22 rounds in two passes: ten in ntt_front10 (every coset from one tile of the caller's column), twelve in ntt_local12
-    // (the front pass moves 16 bytes per lane on both sides: columns on 16-byte boundaries)
-    if (d_front_table && ntt_two_pass_applies(d_in, d_out, log_n, n_cosets, in_col_stride, out_col_stride)) {
-        launch_ntt_front10(src, d_out, d_tw, d_round_scale, d_front_table, log_n, n_cols, n_cosets, src_col_stride, out_col_stride, s, tiled_in);
-        advance(10);
-        launch_ntt_local12(src, d_out, d_tw, d_round_scale, log_n, n_cols, n_cosets, src_col_stride, src_coset_stride,
-                           out_col_stride, 12, s);
-        return;
-    }
-    // 14 + 4k and 15 + 4k rounds: the coset-expanding front pass is bound by its traffic whatever it computes, so it takes four
-    // or five rounds (ntt_first4 / ntt_first5) and the local pass runs ten or nine instead of twelve — the same number of passes,
-    // butterflies moved into idle VALU slots.  13 + 4k rounds keep the remainder pass of one round.
-    const bool aligned16 = ((uintptr_t)d_in % 16) == 0 && ((uintptr_t)d_out % 16) == 0 && in_col_stride % 2 == 0 &&
-                           out_col_stride % 2 == 0;
-    unsigned F = 0, Lr = 12;
-    if (n_cosets <= 64) {
-        if (front % 4 == 2) {          // 2^22: 4 + 8 + 10 measured 283.5 ms per proof, 5 + 8 + 9 284.5 (2 + 8 + 12: 284.7)
-            if (aligned16) F = 4, Lr = 10;
-            else F = 5, Lr = 9;
-        } else if (front % 4 == 3) {   // 2^23: 5 + 8 + 10 measured 560.0 ms per proof against 565.4 for 3 + 8 + 12
-            F = 5, Lr = 10;
-        }
-    }
-    if (F) {
-        if (F == 5)
-            launch_ntt_first5(src, d_out, d_tw, d_round_scale, log_n, n_cols, n_cosets, src_col_stride, src_coset_stride,
-                              out_col_stride, s);
-        else
-            launch_ntt_first4(src, d_out, d_tw, d_round_scale, log_n, n_cols, n_cosets, src_col_stride, src_coset_stride,
-                              out_col_stride, s);
-        advance(F);
-        front = log_n - F - Lr;
-        while (front >= 8) {
-            launch_ntt_strided8(src, d_out, d_tw, d_round_scale, log_n, r0, n_cols, n_cosets, src_col_stride,
-                                src_coset_stride, out_col_stride, s);
-            advance(8);
-            front -= 8;
-        }
-        if (front == 4) {
-            launch_ntt_strided4(src, d_out, d_tw, d_round_scale, log_n, r0, n_cols, n_cosets, src_col_stride,
-                                src_coset_stride, out_col_stride, s);
-            advance(4);
-        }
-        launch_ntt_local12(src, d_out, d_tw, d_round_scale, log_n, n_cols, n_cosets, src_col_stride, src_coset_stride,
-                           out_col_stride, Lr, s);
-        return;
-    }
-    if (front % 4) {
-        unsigned R = front % 4;
-        if (n_cosets <= 64)
-            launch_first_rounds(src, d_out, d_tw, d_round_scale, log_n, R, n_cols, n_cosets, src_col_stride,
-                                src_coset_stride, out_col_stride, s);
-        else
-            launch_generic_pass(src, d_out, d_tw, d_round_scale, log_n, r0, R, TILE_LOG - R, n_cols, n_cosets,
-                                src_col_stride, src_coset_stride, out_col_stride, s);
-        advance(R);
-        front -= R;
-    }
-    while (front >= 8) {
-        launch_ntt_strided8(src, d_out, d_tw, d_round_scale, log_n, r0, n_cols, n_cosets, src_col_stride,
-                            src_coset_stride, out_col_stride, s);
-        advance(8);
-        front -= 8;
-    }
-    if (front == 4) {
-        launch_ntt_strided4(src, d_out, d_tw, d_round_scale, log_n, r0, n_cols, n_cosets, src_col_stride,
-                            src_coset_stride, out_col_stride, s);
-        advance(4);
-    }
-    launch_ntt_local12(src, d_out, d_tw, d_round_scale, log_n, n_cols, n_cosets, src_col_stride, src_coset_stride,
-                       out_col_stride, 12, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -797,24 +797,23 @@ static unsigned pick_cols_per_block(unsigned tiles, unsigned n_cols, unsigned n_
     return cpb;
 }
 
-void launch_ntt_local12(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, unsigned log_n,
-                        unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride,
-                        size_t out_col_stride, unsigned rounds, hipStream_t s) {
-    unsigned tiles = 1u << (log_n - 12);
-    unsigned cpb = pick_cols_per_block(tiles, n_cols, n_cosets);
-    R16Args a{in, out, tw, round_scale, log_n, log_n - 12, n_cols, cpb, in_col_stride, in_coset_stride, out_col_stride};
-    dim3 grid(tiles, (n_cols + cpb - 1) / cpb, n_cosets);
+void launch_ntt_local12(const NttIo &io, unsigned rounds, hipStream_t s) {
+    unsigned tiles = 1u << (io.log_n - 12);
+    unsigned cpb = pick_cols_per_block(tiles, io.n_cols, io.n_cosets);
+    // r0 = log_n - 12 whatever the round count: the kernel skips the rounds the front pass has run
+    R16Args a{io.in, io.out, io.tw, io.round_scale, io.log_n, io.log_n - 12, io.n_cols, cpb, io.in_col_stride, io.in_coset_stride, io.out_col_stride};
+    dim3 grid(tiles, (io.n_cols + cpb - 1) / cpb, io.n_cosets);
     if (rounds == 10) {
-        if (round_scale)
+        if (io.round_scale)
             hipLaunchKernelGGL((ntt_local12_kernel<true, 10>), grid, dim3(256), 0, s, a);
         else
             hipLaunchKernelGGL((ntt_local12_kernel<false, 10>), grid, dim3(256), 0, s, a);
     } else if (rounds == 9) {
-        if (round_scale)
+        if (io.round_scale)
             hipLaunchKernelGGL((ntt_local12_kernel<true, 9>), grid, dim3(256), 0, s, a);
         else
             hipLaunchKernelGGL((ntt_local12_kernel<false, 9>), grid, dim3(256), 0, s, a);
-    } else if (round_scale)
+    } else if (io.round_scale)
         hipLaunchKernelGGL((ntt_local12_kernel<true, 12>), grid, dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL((ntt_local12_kernel<false, 12>), grid, dim3(256), 0, s, a);
@@ -839,79 +838,56 @@ void launch_tiled_permute(const u64 *in, u64 *out, unsigned n_cols, size_t in_co
     hipLaunchKernelGGL(tiled_permute_kernel, dim3((4096u >> TILED_LB) * 16, n_cols), dim3(256), 0, s, in, out, in_col_stride, out_col_stride, to_tiled ? 1 : 0);
 }
 
-void launch_ntt_strided8(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, unsigned log_n, unsigned r0,
-                         unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride,
-                         size_t out_col_stride, hipStream_t s) {
-    unsigned tiles = 1u << (log_n - 12);
-    unsigned cpb = pick_cols_per_block(tiles, n_cols, n_cosets);
-    R16Args a{in, out, tw, round_scale, log_n, r0, n_cols, cpb, in_col_stride, in_coset_stride, out_col_stride};
-    dim3 grid(tiles, (n_cols + cpb - 1) / cpb, n_cosets);
-    if (round_scale)
-        hipLaunchKernelGGL((ntt_strided8_kernel<true, false>), grid, dim3(256), 0, s, a);
-    else if (r0 == 0)
-        hipLaunchKernelGGL((ntt_strided8_kernel<false, true>), grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((ntt_strided8_kernel<false, false>), grid, dim3(256), 0, s, a);
+void launch_ntt_strided(const NttIo &io, unsigned r0, unsigned rounds, hipStream_t s) {
+    unsigned tiles = 1u << (io.log_n - 12);
+    unsigned cpb = pick_cols_per_block(tiles, io.n_cols, io.n_cosets);
+    R16Args a{io.in, io.out, io.tw, io.round_scale, io.log_n, r0, io.n_cols, cpb, io.in_col_stride, io.in_coset_stride, io.out_col_stride};
+    dim3 grid(tiles, (io.n_cols + cpb - 1) / cpb, io.n_cosets);
+    const bool scaled = io.round_scale != nullptr, unit_first = !scaled && r0 == 0;
+    void (*k8)(R16Args) = scaled ? ntt_strided8_kernel<true, false> : unit_first ? ntt_strided8_kernel<false, true> : ntt_strided8_kernel<false, false>;
+    void (*k4)(R16Args) = scaled ? ntt_strided4_kernel<true, false> : unit_first ? ntt_strided4_kernel<false, true> : ntt_strided4_kernel<false, false>;
+    hipLaunchKernelGGL(rounds == 8 ? k8 : k4, grid, dim3(256), 0, s, a);
 }
 
-void launch_ntt_strided4(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, unsigned log_n, unsigned r0,
-                         unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride,
-                         size_t out_col_stride, hipStream_t s) {
-    unsigned tiles = 1u << (log_n - 12);
-    unsigned cpb = pick_cols_per_block(tiles, n_cols, n_cosets);
-    R16Args a{in, out, tw, round_scale, log_n, r0, n_cols, cpb, in_col_stride, in_coset_stride, out_col_stride};
-    dim3 grid(tiles, (n_cols + cpb - 1) / cpb, n_cosets);
-    if (round_scale)
-        hipLaunchKernelGGL((ntt_strided4_kernel<true, false>), grid, dim3(256), 0, s, a);
-    else if (r0 == 0)
-        hipLaunchKernelGGL((ntt_strided4_kernel<false, true>), grid, dim3(256), 0, s, a);
+void launch_ntt_first4(const NttIo &io, hipStream_t s) {
+    R16Args a{io.in, io.out, io.tw, io.round_scale, io.log_n, 0, io.n_cols, 1, io.in_col_stride, io.in_coset_stride, io.out_col_stride};
+    const size_t sl = ((size_t)1 << io.log_n) >> 4;
+    dim3 grid((unsigned)((sl / 2 + 255) / 256), io.n_cols, 1);   // two adjacent indices per lane
+    if (io.round_scale)
+        hipLaunchKernelGGL(ntt_first4_kernel<true>, grid, dim3(256), 0, s, a, io.n_cosets);
     else
-        hipLaunchKernelGGL((ntt_strided4_kernel<false, false>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(ntt_first4_kernel<false>, grid, dim3(256), 0, s, a, io.n_cosets);
 }
 
-// first four rounds of all cosets; the caller has checked first4_applicable()
-void launch_ntt_first4(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, unsigned log_n, unsigned n_cols,
-                       unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride, size_t out_col_stride, hipStream_t s) {
-    R16Args a{in, out, tw, round_scale, log_n, 0, n_cols, 1, in_col_stride, in_coset_stride, out_col_stride};
-    const size_t sl = ((size_t)1 << log_n) >> 4;
-    dim3 grid((unsigned)((sl / 2 + 255) / 256), n_cols, 1);   // two adjacent indices per lane
-    if (round_scale)
-        hipLaunchKernelGGL(ntt_first4_kernel<true>, grid, dim3(256), 0, s, a, n_cosets);
+void launch_ntt_first5(const NttIo &io, hipStream_t s) {
+    R16Args a{io.in, io.out, io.tw, io.round_scale, io.log_n, 0, io.n_cols, 1, io.in_col_stride, io.in_coset_stride, io.out_col_stride};
+    const size_t sl = ((size_t)1 << io.log_n) >> 5;
+    dim3 grid((unsigned)((sl + 255) / 256), io.n_cols, 1);
+    if (io.round_scale)
+        hipLaunchKernelGGL(ntt_first5_kernel<true>, grid, dim3(256), 0, s, a, io.n_cosets);
     else
-        hipLaunchKernelGGL(ntt_first4_kernel<false>, grid, dim3(256), 0, s, a, n_cosets);
+        hipLaunchKernelGGL(ntt_first5_kernel<false>, grid, dim3(256), 0, s, a, io.n_cosets);
 }
 
-void launch_ntt_first5(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, unsigned log_n, unsigned n_cols,
-                       unsigned n_cosets, size_t in_col_stride, size_t in_coset_stride, size_t out_col_stride, hipStream_t s) {
-    R16Args a{in, out, tw, round_scale, log_n, 0, n_cols, 1, in_col_stride, in_coset_stride, out_col_stride};
-    const size_t sl = ((size_t)1 << log_n) >> 5;
-    dim3 grid((unsigned)((sl + 255) / 256), n_cols, 1);
-    if (round_scale)
-        hipLaunchKernelGGL(ntt_first5_kernel<true>, grid, dim3(256), 0, s, a, n_cosets);
-    else
-        hipLaunchKernelGGL(ntt_first5_kernel<false>, grid, dim3(256), 0, s, a, n_cosets);
-}
-
-// first ten rounds of all cosets (log_n == 22); d_table: n_cosets * 1024 words of device scratch for the twiddle table
-void launch_ntt_front10(const u64 *in, u64 *out, const u64 *tw, const u64 *round_scale, u64 *d_table, unsigned log_n, unsigned n_cols,
-                        unsigned n_cosets, size_t in_col_stride, size_t out_col_stride, hipStream_t s, bool tiled_in) {
-    hipLaunchKernelGGL(front10_table_kernel, dim3(n_cosets * 4), dim3(256), 0, s, d_table, tw, round_scale, n_cosets);
+void launch_ntt_front10(const NttIo &io, u64 *d_table, bool tiled_in, hipStream_t s) {
+    const unsigned n_cols = io.n_cols, n_cosets = io.n_cosets;
+    hipLaunchKernelGGL(front10_table_kernel, dim3(n_cosets * 4), dim3(256), 0, s, d_table, io.tw, io.round_scale, n_cosets);
     constexpr int LBN = 4;   // natural-order input: lo values per tile = 2^LB: 3 -> 64-byte runs, 512 threads, two workgroups per CU; 4 -> full lines, 1024 threads, one
     const int lb = tiled_in ? TILED_LB : LBN;
-    const unsigned tiles = 1u << (log_n - 10 - lb);
-    const size_t n = (size_t)1 << log_n;
+    const unsigned tiles = 1u << (io.log_n - 10 - lb);
+    const size_t n = (size_t)1 << io.log_n;
     for (unsigned c0 = 0; c0 < n_cosets; c0 += 8) {   // at most eight cosets per launch: a tile's workgroups are one dispatch window on one XCD
         const unsigned nc = n_cosets - c0 < 8 ? n_cosets - c0 : 8;
         unsigned cpb = 8;
         while (cpb > 1 && (size_t)tiles * nc * ((n_cols + cpb - 1) / cpb) < 4096) cpb >>= 1;
-        F10Args a{in, out + (size_t)c0 * n, d_table + (size_t)c0 * 1024, log_n, n_cols, cpb, nc, in_col_stride, out_col_stride};
+        F10Args a{io.in, io.out + (size_t)c0 * n, d_table + (size_t)c0 * 1024, io.log_n, n_cols, cpb, nc, io.in_col_stride, io.out_col_stride};
         dim3 grid(tiles * nc, (n_cols + cpb - 1) / cpb, 1);
         if (tiled_in) {
-            if (round_scale)
+            if (io.round_scale)
                 hipLaunchKernelGGL((ntt_front10_kernel<false, TILED_LB, true>), grid, dim3(64u << TILED_LB), 0, s, a);
             else
                 hipLaunchKernelGGL((ntt_front10_kernel<true, TILED_LB, true>), grid, dim3(64u << TILED_LB), 0, s, a);
-        } else if (round_scale)
+        } else if (io.round_scale)
             hipLaunchKernelGGL((ntt_front10_kernel<false, LBN>), grid, dim3(64u << LBN), 0, s, a);
         else
             hipLaunchKernelGGL((ntt_front10_kernel<true, LBN>), grid, dim3(64u << LBN), 0, s, a);

@@ -27,6 +27,21 @@ def test_forward_matches_oracle(log_n, coset):
     d_in.free(); d_out.free()
 
 
+def test_forward_two_strided_passes_matches_oracle():
+    """2^24 is the smallest size whose plan (csrc/ntt_plan.h) chains two strided passes of different radix in front of the local
+    pass (S8 S4 L12): the one place where the executor's round bookkeeping crosses two of them.  One column (128 MiB),
+    non-canonical inputs, coset 7, out of place, every value against the oracle.  Sizes 2^28..2^30 (S8 S8) are not run on the
+    GPU: a column there is 2-8 GiB; their plans are checked on the host by tests/test_ntt_plan_host.py."""
+    log_n = 24
+    a = rand_gl(np.random.default_rng(1024), (1, 1 << log_n), noncanonical=True)
+    want = O.fft_batch(a, 7, threads=16)
+    d_in, d_out = DevBuf(a), DevBuf(nelems=a.size)
+    ctx().ntt_forward_batch(d_in.ptr, d_out.ptr, log_n, 1, coset=7)
+    got = d_out.get(a.shape)
+    d_in.free(); d_out.free()
+    assert np.array_equal(got, want)
+
+
 def test_forward_random_coset_and_strided_columns():
     log_n, n_cols, stride = 11, 5, (1 << 11) + 64
     rng = np.random.default_rng(5)
