@@ -124,9 +124,7 @@ int check_impl(bj_ctx *ctx, const bj_setup *S, const u64 *d_variables, const u64
     const u64 *d_consts = S->d_nat + (size_t)V * n, *d_tables = S->d_nat + (size_t)(V + nC) * n;
 
     // terms in evaluator order: (gate, repetition, term), general-purpose gates first
-    unsigned n_gate_terms = 0;
-    for (unsigned g = 0; g < S->n_gates; g++) n_gate_terms += (unsigned)(S->gates_flat[12 * g + 2] * S->gates_flat[12 * g + 5]);
-    const unsigned n_spec_terms = S->n_spec_terms, n_terms = n_gate_terms + n_spec_terms;
+    const unsigned n_gate_terms = S->gates.n_general_terms, n_spec_terms = S->gates.n_spec_terms, n_terms = n_gate_terms + n_spec_terms;
     const unsigned M = (n_gate_terms > n_spec_terms ? n_gate_terms : n_spec_terms) + 1;
 
     // scratch layout (words)
@@ -243,23 +241,15 @@ int check_impl(bj_ctx *ctx, const bj_setup *S, const u64 *d_variables, const u64
         unsigned k, gate, rep, term;   // k: position among the weights of its category
     };
     std::vector<Term> todo;
-    if (kind == BJ_UNSAT_GATE) {
-        unsigned k = 0;
-        for (unsigned g = 0; g < S->n_gates; g++) {
-            const int *f = S->gates_flat.data() + 12 * g;
-            bool deselected = false;   // a path constant that is exactly the other bit makes this gate's selector 0 on the row
-            for (int b = 0; b < f[1]; b++) deselected = deselected || h_consts[b] == (f[6 + b] ? 0u : 1u);
-            for (int r = 0; r < f[2]; r++)
-                for (int t = 0; t < f[5]; t++, k++)
-                    if (!deselected) todo.push_back({k, g, (unsigned)r, (unsigned)t});
-        }
-    } else {
-        unsigned k = 0, g = 0;
-        for (const auto &sg : S->spec) {
-            for (unsigned r = 0; r < sg.reps; r++)
-                for (unsigned t = 0; t < sg.terms; t++, k++) todo.push_back({k, g, r, t});
-            g++;
-        }
+    const std::vector<bj::GateShape> &shapes = kind == BJ_UNSAT_GATE ? S->gates.general : S->gates.spec;
+    for (unsigned g = 0; g < shapes.size(); g++) {
+        const bj::GateShape &G = shapes[g];
+        bool deselected = false;   // a path constant that is exactly the other bit makes this gate's selector 0 on the row
+        for (unsigned b = 0; b < G.path_len; b++) deselected = deselected || h_consts[b] == (G.path[b] ? 0u : 1u);
+        for (unsigned r = 0; r < G.reps && !deselected; r++)
+            for (unsigned t = 0; t < G.num_terms; t++) todo.push_back({G.first_term + r * G.num_terms + t, g, r, t});
+    }
+    if (kind != BJ_UNSAT_GATE) {   // the specialized evaluators ADD
         BJ_HIP(ctx, hipMemsetAsync(tb, 0, todo.size() * 2 * B * 8, st));
     }
     for (size_t i = 0; i < todo.size(); i++) {

@@ -86,7 +86,10 @@ int probe_begin(bj_ctx *ctx, const char *name, double algorithmic_bytes);
 void probe_end(bj_ctx *ctx, int idx);
 int fail(bj_ctx *ctx, int code, const char *fmt, ...);   // ctx == nullptr (host-only calls): the message goes to the calling thread's slot
 // setup.hip: what bj_setup_create refuses about a circuit description and a proof config (no device work); `who` starts the messages
-int circuit_check(bj_ctx *ctx, const char *who, const bj_circuit *c, const bj_proof_config *cfg, bool has_tables, const bj_comm *comm);
+// *gates: the resolved gate list (gate_list.h)
+struct GateList;
+int circuit_check(bj_ctx *ctx, const char *who, const bj_circuit *c, const bj_proof_config *cfg, bool has_tables, const bj_comm *comm,
+                  GateList *gates);
 int bind(bj_ctx *ctx);
 // host block -> device, ordered on ctx->stream like a kernel launch; returns without waiting (h_src may be reused at once)
 int h2d_async(bj_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);

@@ -86,24 +86,6 @@ __global__ void __launch_bounds__(256) gate_program_kernel(ProgArgs a) {
 }
 }  // namespace
 
-void gate_program_extent(const bj_gate_program *p, unsigned *var_extent, unsigned *const_extent, unsigned *wit_extent) {
-    unsigned v = 0, c = 0, w = 0;
-    auto see = [&](const bj_gate_index &ix) {
-        if (ix.kind == BJ_IDX_VARIABLE_POLY && ix.index + 1 > v) v = ix.index + 1;
-        if (ix.kind == BJ_IDX_CONSTANT_POLY && ix.index + 1 > c) c = ix.index + 1;
-        if (ix.kind == BJ_IDX_WITNESS_POLY && ix.index + 1 > w) w = ix.index + 1;
-    };
-    for (uint32_t i = 0; p && p->relations && i < p->num_relations; i++) {
-        const bj_gate_relation &R = p->relations[i];
-        see(R.a);
-        if (R.op == BJ_OP_ADD || R.op == BJ_OP_SUB || R.op == BJ_OP_MUL) see(R.b);
-    }
-    for (uint32_t t = 0; p && p->writes && t < p->num_writes; t++) see(p->writes[t]);
-    *var_extent = v;
-    *const_extent = c;
-    if (wit_extent) *wit_extent = w;
-}
-
 // Whatever numbering and order the host's list has (the reference hands over one fresh temporary per operation from a
 // process-wide counter, gpu_synthesizer/mod.rs:210-352), the device sees the canonical schedule of gate_canon.h: slots by
 // live range, and a fingerprint of the evaluator's function that finds a generated kernel or names the one compiled here.
@@ -178,16 +160,17 @@ static ProgArgs make_prog_args(const DevProgram &P, const u64 *d_vars, size_t va
 
 // the op-list gates of one circuit, quotient mode: the ones with a generated body go out as ONE fused launch when there are
 // at least two of them (they all sweep the same general-purpose columns), everything else one launch per gate as before
-void launch_gate_programs(const GateLaunch *gates, unsigned n, const u64 *d_vars, size_t var_stride, const u64 *d_consts,
-                          size_t const_stride, size_t Q, u64 *d_out0, u64 *d_out1, hipStream_t s, const u64 *d_wits) {
-    if (!Q || !n) return;
+void launch_gate_programs(const GateShape *gates, const DevProgram *programs, unsigned n, const u64 *d_vars, size_t var_stride,
+                          const u64 *d_consts, size_t const_stride, const u64 *d_alphas, size_t Q, u64 *d_out0, u64 *d_out1, hipStream_t s,
+                          const u64 *d_wits) {
+    if (!Q) return;
     const bool no_aot = bj::env().gate_no_aot, no_fuse = bj::env().gate_no_fuse;
     std::vector<unsigned> fused;
     if (!no_aot && !no_fuse)
         for (unsigned i = 0; i < n; i++) {
-            const GateLaunch &G = gates[i];
-            if (gate_aot_fusable(G.program->fp[0], G.program->fp[1]) && !G.program->reads_witness && G.rep_var_stride && G.reps &&
-                fused.size() < (size_t)gpdev::BJ_FUSED_MAX)
+            const GateShape &G = gates[i];
+            if (G.kind == BJ_GATE_PROGRAM && gate_aot_fusable(programs[i].fp[0], programs[i].fp[1]) && !programs[i].reads_witness &&
+                G.var_stride && G.reps && fused.size() < (size_t)gpdev::BJ_FUSED_MAX)
                 fused.push_back(i);
         }
     bool done_fused = false;
@@ -195,19 +178,19 @@ void launch_gate_programs(const GateLaunch *gates, unsigned n, const u64 *d_vars
         std::vector<ProgArgs> args;
         std::vector<uint64_t> hs, cs;
         for (unsigned i : fused) {
-            const GateLaunch &G = gates[i];
-            args.push_back(make_prog_args(*G.program, d_vars, var_stride, d_consts, const_stride, G.path_len, G.path, G.reps,
-                                          G.rep_var_stride, G.rep_const_stride, G.d_alphas, Q, d_out0, d_out1, nullptr, nullptr, 0));
-            hs.push_back(G.program->fp[0]);
-            cs.push_back(G.program->fp[1]);
+            const GateShape &G = gates[i];
+            args.push_back(make_prog_args(programs[i], d_vars, var_stride, d_consts, const_stride, G.path_len, G.path, G.reps, G.var_stride,
+                                          G.const_stride, d_alphas + 2 * (size_t)G.first_term, Q, d_out0, d_out1, nullptr, nullptr, 0));
+            hs.push_back(programs[i].fp[0]);
+            cs.push_back(programs[i].fp[1]);
         }
         done_fused = launch_gate_aot_fused(hs.data(), cs.data(), args.data(), (unsigned)args.size(), (unsigned)((Q + 255) / 256), s);
     }
     for (unsigned i = 0; i < n; i++) {
-        if (done_fused && std::find(fused.begin(), fused.end(), i) != fused.end()) continue;
-        const GateLaunch &G = gates[i];
-        launch_gate_program(*G.program, d_vars, var_stride, d_consts, const_stride, G.path_len, G.path, G.reps, G.rep_var_stride,
-                            G.rep_const_stride, G.d_alphas, Q, d_out0, d_out1, nullptr, s, d_wits, G.rep_wit_stride);
+        const GateShape &G = gates[i];
+        if (G.kind != BJ_GATE_PROGRAM || (done_fused && std::find(fused.begin(), fused.end(), i) != fused.end())) continue;
+        launch_gate_program(programs[i], d_vars, var_stride, d_consts, const_stride, G.path_len, G.path, G.reps, G.var_stride, G.const_stride,
+                            d_alphas + 2 * (size_t)G.first_term, Q, d_out0, d_out1, nullptr, s, d_wits, G.wit_stride);
     }
 }
 

@@ -106,10 +106,10 @@ void launch_copy_perm_stage2(const u64 *d_vars, size_t var_stride, const u64 *d_
 void launch_lookup_polys(const u64 *d_lvars, size_t var_stride, const u64 *d_table_id, const u64 *d_tables,
                          size_t tab_stride, const u64 *d_mult, unsigned reps, unsigned w, unsigned log_n,
                          const u64 *beta, const u64 *gamma, u64 *d_A, u64 *d_B, hipStream_t s);
-// quotient.hip
-void launch_quotient_gates(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
-                           const int *h_gates_flat, unsigned n_gates, const u64 *d_alphas, size_t Q, u64 *d_out0,
-                           u64 *d_out1, hipStream_t s);
+// quotient.hip: the hand-written kinds of a gate list (gate_list.h) in one launch; the other kinds only keep their alpha powers
+struct GateShape;
+void launch_quotient_gates(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride, const GateShape *gates,
+                           unsigned n_gates, const u64 *d_alphas, size_t Q, u64 *d_out0, u64 *d_out1, hipStream_t s);
 void launch_quotient_lookup(const u64 *d_lvars, size_t var_stride, const u64 *d_table_id, const u64 *d_tables,
                             size_t tab_stride, const u64 *d_mult, const u64 *d_A, const u64 *d_B, size_t s2_stride,
                             unsigned reps, unsigned w, const u64 *lbeta, const u64 *lgamma, const u64 *d_alphas,

@@ -177,66 +177,23 @@ int bj_proof_stage_ms(const bj_proof *p, float *out8) {
 }  // extern "C"
 
 namespace bj {
-// the selector path of a gate descriptor (12 ints of bj_setup::gates_flat) as the bytes the evaluators take
-static void selector_path(const int *f, unsigned char *path) {
-    for (int b = 0; b < f[1]; b++) path[b] = (unsigned char)f[6 + b];
-}
-
 // Every gate evaluator of the circuit over `points` points of caller-given columns (the quotient stage runs it on the LDE, the
 // satisfiability check on the trace itself): GATES_GENERAL OVERWRITES (t0, t1) with the hand-written kinds' sum and adds the
 // Poseidon evaluators and the op-list gates over general-purpose columns; GATES_SPECIALIZED ADDS the gates over specialized
 // columns.  a_gates / a_spec: one F_p^2 power per (gate, repetition, term) in evaluator order.
 void launch_circuit_gates(bj_ctx *ctx, const bj_setup *S, const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
                           size_t points, const u64 *a_gates, const u64 *a_spec, u64 *t0, u64 *t1, hipStream_t st, unsigned parts) {
-    if (parts & GATES_GENERAL) {
-        // gate evaluation, SURVEY §8d: 8 (V + consts) qn + 16 qn — V = the general-purpose columns the gates read
-        const int pg = bj::probe_begin(ctx, "quotient_gates", 8.0 * (S->num_gp_vars + S->nC) * (double)points + 16.0 * (double)points);
-        bj::launch_quotient_gates(d_vars, var_stride, d_consts, const_stride, S->gates_flat.data(), S->n_gates, a_gates, points, t0, t1, st);
-        bj::probe_end(ctx, pg);
-        unsigned aoff = 0;   // op-list gates (seam S3) add their contribution on top, with their own slice of alpha powers
-        std::vector<bj::GateLaunch> prog_gates;
-        for (unsigned g = 0; g < S->n_gates; g++) {
-            const int *f = S->gates_flat.data() + 12 * g;
-            if (f[0] == BJ_GATE_POSEIDON2_FLATTENED) {
-                unsigned char path[8] = {0};
-                selector_path(f, path);
-                bj::launch_quotient_poseidon2_flattened(d_vars, var_stride, d_consts, const_stride, (unsigned)f[1], path,
-                                                        a_gates + 2 * (size_t)aoff, points, t0, t1, st);
-            }
-            if (f[0] == BJ_GATE_POSEIDON_FLATTENED) {
-                unsigned char path[8] = {0};
-                selector_path(f, path);
-                bj::launch_quotient_poseidon_flattened(d_vars, var_stride, d_consts, const_stride, (unsigned)f[1], path,
-                                                       a_gates + 2 * (size_t)aoff, points, t0, t1, st);
-            }
-            if (f[0] == BJ_GATE_PROGRAM) {
-                bj::GateLaunch L{};
-                L.program = &S->programs[g];
-                L.path_len = (unsigned)f[1];
-                selector_path(f, L.path);
-                L.reps = (unsigned)f[2];
-                L.rep_var_stride = (unsigned)f[3];
-                L.rep_const_stride = (unsigned)f[4];
-                L.rep_wit_stride = S->gate_wit_stride[g];
-                L.d_alphas = a_gates + 2 * (size_t)aoff;
-                prog_gates.push_back(L);
-            }
-            aoff += (unsigned)(f[2] * f[5]);
+    if (parts & GATES_GENERAL)   // gate evaluation, SURVEY §8d: 8 (V + consts) qn + 16 qn — V = the general-purpose columns the gates read
+        bj::launch_general_gates(ctx, S->gates.general.data(), S->programs.data(), (unsigned)S->gates.general.size(), d_vars, var_stride,
+                                 d_consts, const_stride, S->Wc ? d_vars + (size_t)S->V * var_stride : nullptr, a_gates, points, t0, t1, st,
+                                 8.0 * (S->num_gp_vars + S->nC) * (double)points + 16.0 * (double)points);
+    if (parts & GATES_SPECIALIZED)   // gates over specialized columns: every row, no selector
+        for (size_t g = 0; g < S->gates.spec.size(); g++) {
+            const bj::GateShape &G = S->gates.spec[g];
+            bj::launch_gate_program(S->spec_programs[g], d_vars + (size_t)G.first_col * var_stride, var_stride,
+                                    d_consts + (size_t)G.first_const * const_stride, const_stride, 0, G.path, G.reps, G.var_stride,
+                                    G.const_stride, a_spec + 2 * (size_t)G.first_term, points, t0, t1, nullptr, st);
         }
-        // the op-list gates: one fused launch for those with generated bodies (they all sweep the general-purpose columns)
-        bj::launch_gate_programs(prog_gates.data(), (unsigned)prog_gates.size(), d_vars, var_stride, d_consts, const_stride, points, t0, t1, st,
-                                 S->Wc ? d_vars + (size_t)S->V * var_stride : nullptr);
-    }
-    if (parts & GATES_SPECIALIZED) {
-        unsigned soff = 0;   // gates over specialized columns: every row, no selector
-        const unsigned char no_path[8] = {0};
-        for (const auto &sg : S->spec) {
-            bj::launch_gate_program(sg.program, d_vars + (size_t)sg.first_col * var_stride, var_stride,
-                                    d_consts + (size_t)sg.first_const * const_stride, const_stride, 0, no_path, sg.reps, sg.width,
-                                    sg.const_width, a_spec + 2 * (size_t)soff, points, t0, t1, nullptr, st);
-            soff += sg.reps * sg.terms;
-        }
-    }
 }
 }  // namespace bj
 
@@ -577,9 +534,7 @@ int Proving::round3_quotient() {
     u64 alpha[2];
     challenge2(alpha);
     const unsigned n_lookup_terms = has_lookup ? S->lookup_reps + 1 : 0;
-    unsigned n_gate_terms = 0;
-    for (unsigned g = 0; g < S->n_gates; g++) n_gate_terms += (unsigned)(S->gates_flat[12 * g + 2] * S->gates_flat[12 * g + 5]);
-    const unsigned n_spec_terms = S->n_spec_terms;   // lookup | specialized | general | L1 | copy-permutation (prover.rs:599-625)
+    const unsigned n_gate_terms = S->gates.n_general_terms, n_spec_terms = S->gates.n_spec_terms;   // lookup | specialized | general | L1 | copy-permutation (prover.rs:599-625)
     const unsigned total_terms = n_lookup_terms + n_spec_terms + n_gate_terms + 1 + n_chunks;
     const std::vector<u64> alphas = e2_powers(alpha, total_terms);
     ArenaBuf d_alphas;

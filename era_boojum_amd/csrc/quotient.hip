@@ -12,6 +12,7 @@
 //   1 / (x^n - 1) per coset                         divide_by_vanishing_for_bitreversed_coset_enumeration utils.rs:770-817
 // One lane = one LDE point; consecutive lanes read consecutive addresses of every column (coalesced).  Sums of
 // challenge * term products are accumulated unreduced in 160-bit accumulators and reduced once.
+#include "gate_program.h"
 #include "gl.h"
 #include "kernels.h"
 
@@ -403,41 +404,29 @@ void launch_inv_x_minus_one(const u64 *d_tw_fwd, size_t Q, size_t I0, u64 *d_out
     if (Q) hipLaunchKernelGGL(inv_x_minus_one_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, d_tw_fwd, Q, I0, d_out);
 }
 
-void launch_quotient_gates(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
-                           const int *h_gates_flat /* 12 ints per gate */, unsigned n_gates, const u64 *d_alphas,
-                           size_t Q, u64 *d_out0, u64 *d_out1, hipStream_t s) {
-    GateSet gs;
-    gs.n_gates = (int)n_gates;
-    for (unsigned g = 0; g < n_gates && g < (unsigned)BJ_MAX_GATES; g++) {
-        const int *f = h_gates_flat + 12 * g;
-        gs.g[g] = GateDev{f[0], f[1], f[2], f[3], f[4], f[5], {f[6], f[7], f[8], f[9], f[10], f[11]}};
-    }
-    {   // the windowed kernel when the hand-written kinds appear at most once each with their principal widths
-        const bool windowed_on = bj::env().gates_windowed;   // BJ_GATES_WINDOWED=0 selects the per-gate kernel (the tests run both)
+void launch_quotient_gates(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride, const GateShape *gates,
+                           unsigned n_gates, const u64 *d_alphas, size_t Q, u64 *d_out0, u64 *d_out1, hipStream_t s) {
+    if (bj::env().gates_windowed && n_gates <= (unsigned)BJ_MAX_GATES) {   // BJ_GATES_WINDOWED=0 selects the per-gate kernel (the tests run both)
+        // the windowed kernel when the hand-written kinds appear at most once each with their principal widths
         GateWindows gw{};
-        const int width[4] = {0, 1, 4, 5};
-        bool ok = windowed_on && n_gates <= (unsigned)BJ_MAX_GATES;
-        int aoff = 0, span = 0, n_hand = 0;
+        bool ok = true;
+        int span = 0, n_hand = 0;
         for (unsigned g = 0; ok && g < n_gates; g++) {
-            const GateDev &G = gs.g[g];
-            if (G.num_terms == 0) continue;
-            if (G.kind >= 5) {   // evaluated by its own kernel: only the alpha powers are skipped (as in quotient_gates_kernel)
-                aoff += G.reps * G.num_terms;
-                continue;
-            }
-            if (G.kind < 1 || G.kind > 3 || gw.present[G.kind] || G.var_stride != width[G.kind] || G.num_terms != 1 || G.path_len > 6 ||
+            const GateShape &G = gates[g];
+            if (G.num_terms == 0 || G.kind >= 5) continue;   // no terms, or evaluated by its own kernel
+            const int width = (int)gate_kind_extent(G.kind).var_extent;
+            if (G.kind < 1 || G.kind > 3 || gw.present[G.kind] || (int)G.var_stride != width || G.num_terms != 1 || G.path_len > 6 ||
                 (G.kind != 1 && G.const_stride != 0)) {
                 ok = false;
                 break;
             }
             gw.present[G.kind] = 1;
-            gw.path_len[G.kind] = G.path_len;
+            gw.path_len[G.kind] = (int)G.path_len;
             for (int b = 0; b < 6; b++) gw.path[G.kind][b] = G.path[b];
-            gw.reps[G.kind] = G.reps;
-            gw.const_stride[G.kind] = G.const_stride;
-            gw.aoff[G.kind] = aoff;
-            aoff += G.reps;
-            if (G.reps * width[G.kind] > span) span = G.reps * width[G.kind];
+            gw.reps[G.kind] = (int)G.reps;
+            gw.const_stride[G.kind] = (int)G.const_stride;
+            gw.aoff[G.kind] = (int)G.first_term;
+            if ((int)G.reps * width > span) span = (int)G.reps * width;
             n_hand++;
         }
         if (ok && n_hand > 0) {
@@ -448,8 +437,37 @@ void launch_quotient_gates(const u64 *d_vars, size_t var_stride, const u64 *d_co
             return;
         }
     }
+    GateSet gs;   // the kernel walks the alpha powers itself, in list order
+    gs.n_gates = (int)n_gates;
+    for (unsigned g = 0; g < n_gates && g < (unsigned)BJ_MAX_GATES; g++) {
+        const GateShape &G = gates[g];
+        gs.g[g] = GateDev{G.kind, (int)G.path_len, (int)G.reps, (int)G.var_stride, (int)G.const_stride, (int)G.num_terms,
+                          {G.path[0], G.path[1], G.path[2], G.path[3], G.path[4], G.path[5]}};
+    }
     hipLaunchKernelGGL(quotient_gates_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, d_vars, var_stride,
                        d_consts, const_stride, gs, d_alphas, Q, d_out0, d_out1);
+}
+
+// Every evaluator over general-purpose columns at `points` points of caller-given columns: OVERWRITES (t0, t1) with the
+// hand-written kinds' sum, then the Poseidon evaluators and the op-list gates (seam S3) ADD theirs, each with its own slice of
+// d_alphas (one F_p^2 power per (gate, repetition, term) in evaluator order).  A proof's first call is the "quotient_gates" probe.
+void launch_general_gates(bj_ctx *ctx, const GateShape *gates, const DevProgram *programs, unsigned n_gates, const u64 *d_vars,
+                          size_t var_stride, const u64 *d_consts, size_t const_stride, const u64 *d_wits, const u64 *d_alphas,
+                          size_t points, u64 *t0, u64 *t1, hipStream_t st, double probe_bytes) {
+    const int pg = bj::probe_begin(ctx, "quotient_gates", probe_bytes);
+    launch_quotient_gates(d_vars, var_stride, d_consts, const_stride, gates, n_gates, d_alphas, points, t0, t1, st);
+    bj::probe_end(ctx, pg);
+    for (unsigned g = 0; g < n_gates; g++) {
+        const GateShape &G = gates[g];
+        if (G.kind == BJ_GATE_POSEIDON2_FLATTENED)
+            launch_quotient_poseidon2_flattened(d_vars, var_stride, d_consts, const_stride, G.path_len, G.path, d_alphas + 2 * (size_t)G.first_term,
+                                                points, t0, t1, st);
+        if (G.kind == BJ_GATE_POSEIDON_FLATTENED)
+            launch_quotient_poseidon_flattened(d_vars, var_stride, d_consts, const_stride, G.path_len, G.path, d_alphas + 2 * (size_t)G.first_term,
+                                               points, t0, t1, st);
+    }
+    // the op-list gates: one fused launch for those with generated bodies (they all sweep the general-purpose columns)
+    launch_gate_programs(gates, programs, n_gates, d_vars, var_stride, d_consts, const_stride, d_alphas, points, t0, t1, st, d_wits);
 }
 
 void launch_quotient_lookup(const u64 *d_lvars, size_t var_stride, const u64 *d_table_id, const u64 *d_tables,

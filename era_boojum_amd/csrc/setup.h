@@ -1,5 +1,6 @@
 // Internal: the setup object behind the opaque `bj_setup` of include/boojum_hip.h, shared by setup.hip (which creates it),
-// prover.hip (which proves with it) and check_satisfied.hip (which only reads the replicated natural-order columns and the gate list).
+// prover.hip (which proves with it), check_satisfied.hip (which only reads the replicated natural-order columns and the gate list)
+// and verifier.hip (bj_vk_from_setup copies the gate list and the packed op lists).
 #pragma once
 #include "ctx.h"
 #include "fri_types.h"
@@ -14,17 +15,8 @@ struct bj_setup {
     unsigned Wc = 0;               // non-copiable witness columns (behind the V variable columns in the witness oracle)
     bool tid_var = false;          // UseSpecializedColumnsWithTableIdAsVariable: the table id is the last of lookup_cps = lookup_w + 1
     unsigned lookup_cps = 0;       // variable columns of a sub-argument (specialized_columns_per_subargument, cs/mod.rs:300-312)
-    std::vector<unsigned> gate_wit_stride;   // per general-purpose gate: per_chunk_offset.witnesses_offset
-    std::vector<int> gates_flat;   // 12 ints per gate
-    std::vector<bj::DevProgram> programs;   // per gate; empty (block == nullptr) unless kind == BJ_GATE_PROGRAM
-    unsigned n_gates = 0;
-    struct SpecGate {                        // a gate over specialized columns: op list, no selector, own columns
-        bj::DevProgram program;
-        unsigned reps = 0, width = 0, terms = 0, first_col = 0;
-        unsigned first_const = 0, const_width = 0;   // its constant columns: reps * const_width of them from first_const on
-    };
-    std::vector<SpecGate> spec;
-    unsigned n_spec_terms = 0;
+    bj::GateList gates;            // as bj::resolve_gates (gate_list.h) made it from the circuit's description
+    std::vector<bj::DevProgram> programs, spec_programs;   // beside gates.general / gates.spec; empty (block == nullptr) unless kind == BJ_GATE_PROGRAM
     std::vector<gl::u64> non_residues;
     bool small_non_residues = false;   // every k_c < 2^32 (canonical): quotient_copy_perm multiplies by them as 32-bit integers
     std::vector<unsigned> pub_cols, pub_rows;

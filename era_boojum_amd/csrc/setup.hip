@@ -35,7 +35,7 @@ void bj_setup_destroy(bj_setup *s) {
     if (s->d_inv_xm1) (void)hipFree(s->d_inv_xm1);
     if (s->d_placement) (void)hipFree(s->d_placement);
     for (auto &p : s->programs) p.release();
-    for (auto &g : s->spec) g.program.release();
+    for (auto &p : s->spec_programs) p.release();
     delete s;
 }
 
@@ -55,9 +55,9 @@ void bj::setup_adopt_placement(bj_setup *s, uint32_t *d_placement) { s->d_placem
 const uint32_t *bj::setup_placement(const bj_setup *s) { return s->d_placement; }
 
 // Everything bj_setup_create refuses about a circuit description and a proof config, without touching a device: the geometry,
-// the config, the sharding requirements (comm != nullptr), every gate descriptor with the column ranges it will form, and the op
-// lists, which are brought into canonical form here (a malformed list is refused with the canonicaliser's message).  bj_vk_create
-// runs the same function, so a key is refused exactly where a setup is, in the same words after the caller's name.
+// the config, the sharding requirements (comm != nullptr), and what bj::resolve_gates (gate_list.h) refuses about the gates, whose
+// resolved list goes to *gates.  bj_vk_create runs the same function, so a key is refused exactly where a setup is, in the same
+// words after the caller's name.
 #define BJ_WHO "%s: "
 #define BJ_WHO_SHARDED "%s_sharded: "
 static int check_program(bj_ctx *ctx, const bj_gate_program *p) {
@@ -69,7 +69,8 @@ static int check_program(bj_ctx *ctx, const bj_gate_program *p) {
     return BJ_OK;
 }
 
-int bj::circuit_check(bj_ctx *ctx, const char *who, const bj_circuit *c, const bj_proof_config *cfg, bool has_tables, const bj_comm *comm) {
+int bj::circuit_check(bj_ctx *ctx, const char *who, const bj_circuit *c, const bj_proof_config *cfg, bool has_tables, const bj_comm *comm,
+                      bj::GateList *gates) {
     if (c->log_n < 1 || c->log_n > 26) return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "log_n out of range", who);
     if (c->num_gates == 0 || c->num_gates > 16 || !c->gates) return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "1..16 gates expected", who);
     if (!bj::is_pow2(c->quotient_degree) || !bj::is_pow2(cfg->fri_lde_factor) || cfg->fri_lde_factor < 2 ||
@@ -122,89 +123,11 @@ int bj::circuit_check(bj_ctx *ctx, const char *who, const bj_circuit *c, const b
         if (Qe_rank < 2 || !bj::is_pow2(Qe_rank))                              // and inverse-transforms them: a power of two
             return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO_SHARDED "q n / world = %zu quotient points per rank (a power of two >= 2 is needed)", who, Qe_rank);
     }
-    if (c->num_gates > 16)
-        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, BJ_WHO "%u gate types over general-purpose columns (at most 16)", who, c->num_gates);
-    for (unsigned g = 0; g < c->num_gates; g++) {
-        const bj_gate_desc &G = c->gates[g];
-        const bool p2 = G.kind == BJ_GATE_POSEIDON2_FLATTENED || G.kind == BJ_GATE_POSEIDON_FLATTENED;
-        if (G.kind < 1 || G.kind > BJ_GATE_POSEIDON_FLATTENED || G.path_len > 6 || (G.kind == BJ_GATE_PROGRAM && !G.program) ||
-            (p2 && (G.num_terms != 118 || G.num_repetitions != 1 || c->num_gp_vars < 130)) ||
-            (G.kind != BJ_GATE_PROGRAM && G.kind != BJ_GATE_NOP && !p2 && G.num_terms != 1))
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "bad gate descriptor %u", who, g);
-        {   // every column index the evaluator will form must exist: (reps - 1) * stride + the widest operand, after the selector path
-            unsigned var_extent = 0, const_extent = 0, wit_extent = 0;
-            bool const_per_rep = true;
-            switch (G.kind) {
-                case BJ_GATE_CONSTANT_ALLOCATOR: var_extent = 1; const_extent = 1; break;
-                case BJ_GATE_FMA_NO_CONSTANT: var_extent = 4; const_extent = 2; const_per_rep = false; break;
-                case BJ_GATE_REDUCTION4: var_extent = 5; const_extent = 4; const_per_rep = false; break;
-                case BJ_GATE_POSEIDON2_FLATTENED: var_extent = 130; break;
-                case BJ_GATE_POSEIDON_FLATTENED: var_extent = 130; break;
-                case BJ_GATE_PROGRAM: bj::gate_program_extent(G.program, &var_extent, &const_extent, &wit_extent); break;
-                default: break;
-            }
-            if (wit_extent && (size_t)(G.num_repetitions ? G.num_repetitions - 1 : 0) * G.wit_stride + wit_extent > c->num_witness_cols)
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "gate %u reads witness column %zu of %u", who, g,
-                                (size_t)(G.num_repetitions - 1) * G.wit_stride + wit_extent, c->num_witness_cols);
-            const size_t last = G.num_repetitions ? G.num_repetitions - 1 : 0;
-            const size_t var_end = var_extent ? last * G.var_stride + var_extent : 0;
-            const size_t const_end = G.path_len + (const_extent ? (const_per_rep ? last * G.const_stride : 0) + const_extent : 0);
-            if (G.kind != BJ_GATE_NOP && (G.num_repetitions == 0 || var_end > c->num_gp_vars || const_end > c->num_constant_cols))
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "gate %u reads variable column %zu / constant column %zu of %u / %u "
-                                "(repetitions x stride + operand index, after a selector path of %u)", who, g, var_end, const_end,
-                                c->num_gp_vars, c->num_constant_cols, G.path_len);
-            if (G.path_len > c->num_constant_cols)
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "gate %u: selector path longer than the constant columns", who, g);
-        }
-        if (G.kind == BJ_GATE_PROGRAM) {
-            if (G.program->num_writes != G.num_terms)
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "gate %u: program writes %u terms, descriptor says %u", who, g,
-                                G.program->num_writes, G.num_terms);
-            if (int prc = check_program(ctx, G.program)) return prc;
-        }
-    }
-    {   // gates over specialized columns (evaluator_data.rs:124-240, prover.rs:635-800): their variable columns follow the lookup ones
-        // in declaration order; their constant columns follow the general-purpose gates' ones and the table-id column (which is the
-        // first "special purpose" constant: setup.rs:963-1010), num_repetitions * const_stride columns each — every repetition its
-        // own principal_width.num_constants columns (share_constants = false, per_repetition_offset.constants_offset = that width)
-        // (64-bit sums: the sizes are the caller's, a wrapped 32-bit total must not pass the range checks)
-        uint64_t col = (uint64_t)c->num_gp_vars + (uint64_t)lookup_cps * c->lookup_reps;
-        uint64_t spec_consts = 0;
-        for (unsigned g = 0; c->specialized_gates && g < c->num_specialized_gates; g++) {
-            const uint64_t per_gate = (uint64_t)c->specialized_gates[g].num_repetitions * c->specialized_gates[g].const_stride;
-            if (per_gate > c->num_constant_cols) { spec_consts = (uint64_t)c->num_constant_cols + 1; break; }
-            spec_consts += per_gate;
-        }
-        if (spec_consts > c->num_constant_cols ||
-            (c->lookup_reps && !tid_var && (uint64_t)c->table_id_col + 1 + spec_consts != c->num_constant_cols))
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "%u constant columns declared; the specialized gates' %llu must be the "
-                            "last ones, right behind the table-id column", who, c->num_constant_cols, (unsigned long long)spec_consts);
-        for (unsigned g = 0; g < c->num_specialized_gates; g++) {
-            const bj_gate_desc &G = c->specialized_gates[g];
-            bool ok = c->specialized_gates && G.kind == BJ_GATE_PROGRAM && G.program && G.path_len == 0 && G.num_repetitions &&
-                      G.var_stride && G.program->num_writes == G.num_terms;
-            unsigned ve = 0, ce = 0, we = 0;
-            if (ok) {
-                bj::gate_program_extent(G.program, &ve, &ce, &we);
-                // a repetition reads its own var_stride variable columns and its own const_stride constant columns, no witness column.
-                // Constants SHARED by the repetitions (share_constants = true with constants) are refused: the reference itself hands
-                // such an evaluator an empty constant range (per_repetition_offset.constants_offset = 0, prover.rs:748-772)
-                ok = ve <= G.var_stride && we == 0 && ce <= G.const_stride;
-            }
-            if (!ok)
-                return bj::fail(ctx, BJ_ERR_UNSUPPORTED, BJ_WHO "specialized gate %u must be an op list without a selector path "
-                                "whose repetitions each read their own var_stride variable and const_stride constant columns "
-                                "(share_constants = false) and no witness column", who, g);
-            if (int prc = check_program(ctx, G.program)) return prc;
-            if (col + (uint64_t)G.num_repetitions * G.var_stride > c->num_vars)
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "specialized gate %u runs past the %u declared variable columns", who, g,
-                                c->num_vars);
-            col += (uint64_t)G.num_repetitions * G.var_stride;
-        }
-        if (col != c->num_vars)
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "%u variable columns declared, geometry + lookups + "
-                            "specialized gates make %llu", who, c->num_vars, (unsigned long long)col);
-    }
+    // every gate descriptor with the column ranges it will form, and the layout of the specialized columns (gate_list.h); the op
+    // lists are canonicalised at their place in that order, and a malformed one is refused in the canonicaliser's own words
+    std::string err;
+    if (int rc = bj::resolve_gates(*c, lookup_cps, gates, &err, [ctx](const bj_gate_program *p) { return check_program(ctx, p); }))
+        return err.empty() ? rc : bj::fail(ctx, rc, BJ_WHO "%s", who, err.c_str());
     return BJ_OK;
 }
 #undef BJ_WHO
@@ -217,7 +140,8 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
     if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: null out pointer");
     *out = nullptr;
     if (!c || !cfg || (!h_sigmas && !fill_sigmas) || !h_constants) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: null argument");
-    if (int rc = bj::circuit_check(ctx, "bj_setup_create", c, cfg, h_tables != nullptr, comm)) return rc;
+    bj::GateList gates;
+    if (int rc = bj::circuit_check(ctx, "bj_setup_create", c, cfg, h_tables != nullptr, comm, &gates)) return rc;
     const bool tid_var = c->lookup_reps && c->table_id_col == BJ_TABLE_ID_AS_VARIABLE;
     const unsigned lookup_cps = c->lookup_width + (tid_var ? 1u : 0u);
     bj_setup *s = new bj_setup();
@@ -234,43 +158,19 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
     s->lookup_w = c->lookup_width; s->lookup_reps = c->lookup_reps; s->table_id_col = tid_var ? 0 : c->table_id_col;
     s->tid_var = tid_var; s->lookup_cps = lookup_cps;
     s->q = c->quotient_degree;
-    s->n_gates = c->num_gates;
-    for (unsigned g = 0; g < c->num_gates; g++) {
-        const bj_gate_desc &G = c->gates[g];
-        s->gate_wit_stride.push_back(G.wit_stride);
-        s->programs.emplace_back();
-        if (G.kind == BJ_GATE_PROGRAM) {
-            if (int prc = s->programs.back().upload(ctx, G.program)) {
-                bj_setup_destroy(s);
-                return prc;
-            }
-        }
-        int f[12] = {G.kind, (int)G.path_len, (int)G.num_repetitions, (int)G.var_stride, (int)G.const_stride,
-                     (int)G.num_terms, 0, 0, 0, 0, 0, 0};
-        for (unsigned b = 0; b < G.path_len; b++) f[6 + b] = G.path[b] ? 1 : 0;
-        s->gates_flat.insert(s->gates_flat.end(), f, f + 12);
-    }
-    {   // gates over specialized columns: their variable columns follow the lookup ones in declaration order, their constant columns
-        // are the last ones (the layout bj::circuit_check has verified)
-        uint64_t col = (uint64_t)c->num_gp_vars + (uint64_t)lookup_cps * c->lookup_reps;
-        uint64_t spec_consts = 0;
-        for (unsigned g = 0; g < c->num_specialized_gates; g++)
-            spec_consts += (uint64_t)c->specialized_gates[g].num_repetitions * c->specialized_gates[g].const_stride;
-        unsigned ccol = c->num_constant_cols - (unsigned)spec_consts;
-        s->spec.resize(c->num_specialized_gates);
-        for (unsigned g = 0; g < c->num_specialized_gates; g++) {
-            const bj_gate_desc &G = c->specialized_gates[g];
-            bj_setup::SpecGate &sg = s->spec[g];
-            if (int prc = sg.program.upload(ctx, G.program)) {
-                bj_setup_destroy(s);
-                return prc;
-            }
-            sg.reps = G.num_repetitions; sg.width = G.var_stride; sg.terms = G.num_terms; sg.first_col = (unsigned)col;
-            sg.first_const = ccol; sg.const_width = G.const_stride;
-            col += (uint64_t)sg.reps * sg.width;
-            ccol += sg.reps * sg.const_width;
-            s->n_spec_terms += sg.reps * sg.terms;
-        }
+    s->gates = std::move(gates);
+    auto upload = [ctx](std::vector<bj::DevProgram> &to, const bj_gate_desc *from, unsigned n) {
+        to.resize(n);
+        for (unsigned g = 0; g < n; g++)
+            if (from[g].kind == BJ_GATE_PROGRAM)
+                if (int prc = to[g].upload(ctx, from[g].program)) return prc;
+        return (int)BJ_OK;
+    };
+    int prc = upload(s->programs, c->gates, c->num_gates);
+    if (!prc) prc = upload(s->spec_programs, c->specialized_gates, c->num_specialized_gates);
+    if (prc) {
+        bj_setup_destroy(s);
+        return prc;
     }
     s->non_residues.assign(c->non_residues, c->non_residues + c->num_vars);
     s->small_non_residues = true;

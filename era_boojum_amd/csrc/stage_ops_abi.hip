@@ -5,7 +5,7 @@
 #include "ctx.h"
 #include "gate_program.h"
 
-#include <memory>
+#include <string>
 #include <vector>
 
 using gl::u64;
@@ -84,101 +84,51 @@ int bj_quotient_gates(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, un
     if (num_gates == 0 || num_gates > 16) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: 1..16 gate types");
     if (var_stride < num_points || const_stride < num_points)
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: column stride below the number of points");
-    std::vector<int> flat;
-    std::vector<std::unique_ptr<bj::DevProgram>> programs(num_gates);   // op-list gates, uploaded below
-    size_t n_terms = 0;
+    // the rules of a circuit's gates (gate_list.h) over the columns given here, and two refusals of this operator's own
+    const bj::GateColumns cols{num_gp_vars, num_constant_cols, ~0u};
+    bj::GateList L;
+    std::string err;
     for (unsigned g = 0; g < num_gates; g++) {
         const bj_gate_desc &G = gates[g];
-        if (G.kind == BJ_GATE_PROGRAM) {   // an op list in quotient mode, as bj_prove launches it (generated, compiled or interpreted)
-            unsigned ve = 0, ce = 0, we = 0;
-            if (G.program) bj::gate_program_extent(G.program, &ve, &ce, &we);
-            if (!G.program || G.path_len > 6 || G.num_repetitions == 0 || G.num_terms != G.program->num_writes)
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: bad gate descriptor %u", g);
-            if (we) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_quotient_gates: gate %u reads witness columns", g);
-            const size_t last_rep = G.num_repetitions - 1;
-            if (last_rep * G.var_stride + ve > num_gp_vars || G.path_len + last_rep * G.const_stride + ce > num_constant_cols)
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: gate %u reads past the given columns", g);
-            int f[12] = {G.kind, (int)G.path_len, (int)G.num_repetitions, (int)G.var_stride, (int)G.const_stride, (int)G.num_terms,
-                         0, 0, 0, 0, 0, 0};
-            for (unsigned b = 0; b < G.path_len; b++) f[6 + b] = G.path[b] ? 1 : 0;
-            flat.insert(flat.end(), f, f + 12);
-            n_terms += (size_t)G.num_repetitions * G.num_terms;
-            continue;
-        }
-        if (G.kind == BJ_GATE_POSEIDON_FLATTENED) {   // the hand-written v1 evaluator: one repetition over the first 130 columns
-            if (G.path_len > 6 || G.num_terms != 118 || G.num_repetitions != 1 || num_gp_vars < 130 || G.path_len > num_constant_cols)
-                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: bad gate descriptor %u", g);
-            int f[12] = {G.kind, (int)G.path_len, 1, 130, 0, 118, 0, 0, 0, 0, 0, 0};
-            for (unsigned b = 0; b < G.path_len; b++) f[6 + b] = G.path[b] ? 1 : 0;
-            flat.insert(flat.end(), f, f + 12);
-            n_terms += 118;
-            continue;
-        }
-        if (G.kind < BJ_GATE_CONSTANT_ALLOCATOR || G.kind > BJ_GATE_NOP)
+        if (G.kind != BJ_GATE_PROGRAM && G.kind != BJ_GATE_POSEIDON_FLATTENED && (G.kind < BJ_GATE_CONSTANT_ALLOCATOR || G.kind > BJ_GATE_NOP))
             return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_quotient_gates: gate %u: kind %d is not evaluated here", g, G.kind);
-        if (G.path_len > 6 || (G.kind != BJ_GATE_NOP && G.num_terms != 1))
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: bad gate descriptor %u", g);
-        static const unsigned width[5] = {0, 1, 4, 5, 0};
-        const size_t last_rep = G.num_repetitions ? G.num_repetitions - 1 : 0;
-        // ConstantsAllocator reads one constant per repetition, the other two evaluators row-shared constants after the path
-        const size_t const_end = G.kind == BJ_GATE_CONSTANT_ALLOCATOR ? G.path_len + last_rep * G.const_stride + 1
-                                 : G.kind == BJ_GATE_FMA_NO_CONSTANT  ? G.path_len + 2
-                                 : G.kind == BJ_GATE_REDUCTION4       ? G.path_len + 4 : G.path_len;
-        if (G.kind != BJ_GATE_NOP && G.num_repetitions &&
-            (last_rep * G.var_stride + width[G.kind] > num_gp_vars || const_end > num_constant_cols))
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: gate %u reads past the given columns", g);
-        if (G.path_len > num_constant_cols)
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: gate %u: selector path longer than the constant columns", g);
-        int f[12] = {G.kind, (int)G.path_len, (int)G.num_repetitions, (int)G.var_stride, (int)G.const_stride, (int)G.num_terms,
-                     0, 0, 0, 0, 0, 0};
-        for (unsigned b = 0; b < G.path_len; b++) f[6 + b] = G.path[b] ? 1 : 0;
-        flat.insert(flat.end(), f, f + 12);
-        n_terms += (size_t)G.num_repetitions * G.num_terms;
+        bj::GateShape shape;
+        if (int rc = bj::resolve_gate(G, g, cols, &shape, &err, "reads past the given columns"))
+            return bj::fail(ctx, rc, "bj_quotient_gates: %s", err.c_str());
+        unsigned ve = 0, ce = 0, we = 0;
+        if (G.kind == BJ_GATE_PROGRAM) bj::gate_program_extent(G.program, &ve, &ce, &we);
+        if (we) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_quotient_gates: gate %u reads witness columns", g);
+        L.push_general(shape);
     }
+    const size_t n_terms = L.n_general_terms;
     if (n_terms && !h_alphas) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_gates: null alpha powers");
+    std::vector<bj::DevProgram> programs(num_gates);   // op-list gates; their device copies live until their kernels are done
+    auto release = [&]() {
+        bool synced = false;
+        for (auto &p : programs)
+            if (p.block) {
+                if (!synced) (void)hipStreamSynchronize(ctx->stream);
+                synced = true;
+                p.release();
+            }
+    };
     for (unsigned g = 0; g < num_gates; g++)
-        if (gates[g].kind == BJ_GATE_PROGRAM) {
-            programs[g].reset(new bj::DevProgram);
-            if (int rc = programs[g]->upload(ctx, gates[g].program)) {
-                for (auto &p : programs)
-                    if (p) p->release();
+        if (gates[g].kind == BJ_GATE_PROGRAM)
+            if (int rc = programs[g].upload(ctx, gates[g].program)) {
+                release();
                 return rc;
             }
-        }
     Tmp al(ctx);
-    if (int rc = al.alloc(16 * (n_terms + 1))) return rc;
-    if (n_terms)
-        if (int rc = bj::h2d_async(ctx, al.p, h_alphas, 16 * n_terms)) return rc;
-    bj::launch_quotient_gates(d_vars, var_stride, d_consts, const_stride, flat.data(), num_gates, (const u64 *)al.p, num_points,
-                              d_out0, d_out1, ctx->stream);
-    size_t aoff = 0;   // gates with a kernel of their own add their terms on top, with their slice of the alpha powers
-    for (unsigned g = 0; g < num_gates; g++) {
-        const int *f = flat.data() + 12 * g;
-        if (f[0] == BJ_GATE_POSEIDON_FLATTENED) {
-            unsigned char path[8] = {0};
-            for (int b = 0; b < f[1]; b++) path[b] = (unsigned char)f[6 + b];
-            bj::launch_quotient_poseidon_flattened(d_vars, var_stride, d_consts, const_stride, (unsigned)f[1], path,
-                                                   (const u64 *)al.p + 2 * aoff, num_points, d_out0, d_out1, ctx->stream);
-        }
-        if (f[0] == BJ_GATE_PROGRAM) {
-            unsigned char path[8] = {0};
-            for (int b = 0; b < f[1]; b++) path[b] = (unsigned char)f[6 + b];
-            bj::launch_gate_program(*programs[g], d_vars, var_stride, d_consts, const_stride, (unsigned)f[1], path, (unsigned)f[2],
-                                    (unsigned)f[3], (unsigned)f[4], (const u64 *)al.p + 2 * aoff, num_points, d_out0, d_out1, nullptr,
-                                    ctx->stream);
-        }
-        aoff += (size_t)f[2] * f[5];
+    int rc = al.alloc(16 * (n_terms + 1));
+    if (!rc && n_terms) rc = bj::h2d_async(ctx, al.p, h_alphas, 16 * n_terms);
+    if (!rc) {
+        bj::launch_general_gates(ctx, L.general.data(), programs.data(), num_gates, d_vars, var_stride, d_consts, const_stride, nullptr,
+                                 (const u64 *)al.p, num_points, d_out0, d_out1, ctx->stream, 0.0);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = bj::fail(ctx, BJ_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     }
-    const hipError_t e = hipGetLastError();
-    bool synced = false;
-    for (auto &p : programs)
-        if (p) {   // the programs' device copies live until their kernels are done
-            if (!synced) (void)hipStreamSynchronize(ctx->stream);
-            synced = true;
-            p->release();
-        }
-    if (e != hipSuccess) return bj::fail(ctx, BJ_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return BJ_OK;
+    release();
+    return rc;
 }
 
 int bj_quotient_lookup(bj_ctx *ctx, const uint64_t *d_lookup_vars, size_t var_stride, const uint64_t *d_table_id,

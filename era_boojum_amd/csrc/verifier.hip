@@ -45,14 +45,11 @@ struct bj_vk {
         std::vector<u64> values;
         unsigned n_slots = 0;
     };
-    struct Gate {
-        int kind = 0;
-        unsigned path_len = 0, reps = 0, var_stride = 0, wit_stride = 0, const_stride = 0, num_terms = 0;
-        unsigned char path[8] = {};
-        unsigned first_col = 0, first_const = 0;   // gates over specialized columns: where their columns start
+    struct Gate : bj::GateShape {   // gate_list.h
         Program prog;
     };
     std::vector<Gate> gates, spec;
+    unsigned n_gate_terms = 0, n_spec_terms = 0;
     std::vector<u64> non_residues;
     std::vector<unsigned> pub_cols, pub_rows;
     unsigned fri_lde = 0, cap_size = 0, security = 0, pow_bits = 0, transcript = BJ_TRANSCRIPT_POSEIDON2, hasher = BJ_HASHER_POSEIDON2,
@@ -581,13 +578,13 @@ e2 lookup_terms(const bj_vk *K, const Challenges &C, const Openings &O, const e2
 e2 specialized_gate_terms(const bj_vk *K, const Openings &O, const e2 *a_spec, bool *well_formed) {
     e2 T = ZERO2;
     std::vector<e2> slots, terms;
-    size_t off = 0;
     for (const auto &g : K->spec) {
         terms.assign(g.num_terms ? g.num_terms : 1, ZERO2);
         for (unsigned r = 0; r < g.reps; r++) {
             const size_t vb = g.first_col + (size_t)r * g.var_stride, cb = g.first_const + (size_t)r * g.const_stride;
             *well_formed = program_terms(g.prog, O.var_z + vb, g.var_stride, O.con_z + cb, g.const_stride, nullptr, 0, slots, terms.data(), g.num_terms) && *well_formed;
-            for (unsigned k = 0; k < g.num_terms; k++) T = gl::e2_add(T, gl::e2_mul(terms[k], a_spec[off++]));
+            const e2 *a = a_spec + g.first_term + (size_t)r * g.num_terms;
+            for (unsigned k = 0; k < g.num_terms; k++) T = gl::e2_add(T, gl::e2_mul(terms[k], a[k]));
         }
     }
     return T;
@@ -599,7 +596,6 @@ e2 general_gate_terms(const bj_vk *K, const ProofView &P, const Openings &O, con
     const e2 *var_z = O.var_z, *wit_z = O.wit_z, *con_z = O.con_z;
     e2 T = ZERO2;
     std::vector<e2> slots, terms;
-    size_t off = 0;
     for (const auto &g : K->gates) {
         if (!g.num_terms) continue;
         e2 sel = ONE2;
@@ -632,7 +628,8 @@ e2 general_gate_terms(const bj_vk *K, const ProofView &P, const Openings &O, con
                                                  Wc - (size_t)r * g.wit_stride, slots, terms.data(), g.num_terms) && *well_formed;
                     break;
             }
-            for (unsigned k = 0; k < g.num_terms; k++) acc = gl::e2_add(acc, gl::e2_mul(terms[k], a_gates[off++]));
+            const e2 *a = a_gates + g.first_term + (size_t)r * g.num_terms;
+            for (unsigned k = 0; k < g.num_terms; k++) acc = gl::e2_add(acc, gl::e2_mul(terms[k], a[k]));
         }
         T = gl::e2_add(T, gl::e2_mul(acc, sel));
     }
@@ -658,9 +655,7 @@ e2 copy_permutation_terms(const bj_vk *K, const ProofView &P, const Challenges &
 // The lookup sum and the quotient identity at z (verifier.rs:1090-1810): BJ_VERIFY_OK, or the stage that fails.  Challenge
 // powers in the order lookup | specialized | general | L1 | chunks (prover.rs:599-625, verifier.rs:1000-1060).
 uint32_t quotient_identity(const bj_vk *K, const ProofView &P, const Challenges &C, const Openings &O) {
-    size_t n_gate_terms = 0, n_spec_terms = 0;
-    for (const auto &g : K->gates) n_gate_terms += (size_t)g.reps * g.num_terms;
-    for (const auto &g : K->spec) n_spec_terms += (size_t)g.reps * g.num_terms;
+    const size_t n_gate_terms = K->n_gate_terms, n_spec_terms = K->n_spec_terms;
     const size_t total_terms = P.n_lookup_terms + n_spec_terms + n_gate_terms + 1 + P.n_chunks;
     std::vector<e2> alphas(total_terms);
     alphas[0] = ONE2;
@@ -1032,12 +1027,20 @@ int verify_impl(bj_ctx *ctx, const bj_vk *K, const u64 *W, size_t n_words, unsig
     return judge(ctx, K, &R, 1, out, &ctx->verify_timing);
 }
 
-void take_gate(bj_vk::Gate &g, const bj_gate_desc &G) {
-    g.kind = G.kind;
-    g.path_len = G.path_len;
-    for (unsigned b = 0; b < G.path_len && b < 8; b++) g.path[b] = G.path[b] ? 1 : 0;
-    g.reps = G.num_repetitions; g.var_stride = G.var_stride; g.wit_stride = G.wit_stride; g.const_stride = G.const_stride;
-    g.num_terms = G.num_terms;
+// the key's gates: the shapes of a resolved list, each op-list gate with its packed program from program_of(spec, g, &program)
+template <class ProgramOf>
+void take_gates(bj_vk *k, const bj::GateList &L, ProgramOf program_of) {
+    k->n_gate_terms = L.n_general_terms;
+    k->n_spec_terms = L.n_spec_terms;
+    for (bool spec : {false, true}) {
+        const std::vector<bj::GateShape> &shapes = spec ? L.spec : L.general;
+        std::vector<bj_vk::Gate> &to = spec ? k->spec : k->gates;
+        to.resize(shapes.size());
+        for (size_t g = 0; g < shapes.size(); g++) {
+            static_cast<bj::GateShape &>(to[g]) = shapes[g];
+            if (shapes[g].kind == BJ_GATE_PROGRAM) program_of(spec, g, &to[g].prog);
+        }
+    }
 }
 
 void finish_config(bj_vk *k, unsigned fri_lde, unsigned cap_size, unsigned security, unsigned pow_bits, unsigned transcript, unsigned hasher,
@@ -1057,39 +1060,22 @@ int bj_vk_create(const bj_circuit *c, const uint64_t *setup_cap, const bj_proof_
     if (!out) return bj::fail(nullptr, BJ_ERR_INVALID_ARG, "bj_vk_create: null out pointer");
     *out = nullptr;
     if (!c || !cfg || !setup_cap) return bj::fail(nullptr, BJ_ERR_INVALID_ARG, "bj_vk_create: null argument");
-    if (int rc = bj::circuit_check(nullptr, "bj_vk_create", c, cfg, true, nullptr)) return rc;
+    bj::GateList L;
+    if (int rc = bj::circuit_check(nullptr, "bj_vk_create", c, cfg, true, nullptr, &L)) return rc;
     bj_vk *k = new bj_vk();
     k->log_n = c->log_n; k->V = c->num_vars; k->num_gp_vars = c->num_gp_vars; k->Wc = c->num_witness_cols; k->nC = c->num_constant_cols;
     k->lookup_w = c->lookup_width; k->lookup_reps = c->lookup_reps; k->q = c->quotient_degree;
     k->tid_var = c->lookup_reps && c->table_id_col == BJ_TABLE_ID_AS_VARIABLE;
     k->table_id_col = k->tid_var ? 0 : c->table_id_col;
     k->lookup_cps = c->lookup_width + (k->tid_var ? 1u : 0u);
-    auto take_program = [](bj_vk::Program &P, const bj_gate_program *p) {   // circuit_check has canonicalised it once: it cannot fail here
+    auto take_program = [](const bj_gate_program *p, bj_vk::Program *P) {   // circuit_check has canonicalised it once: it cannot fail here
         bj::canon::Program C;
         std::string err;
         if (bj::canon::canonicalize(p, &C, &err)) return;
-        bj::pack_program(C, &P.rel, &P.values);
-        P.n_slots = C.num_slots;
+        bj::pack_program(C, &P->rel, &P->values);
+        P->n_slots = C.num_slots;
     };
-    k->gates.resize(c->num_gates);
-    for (unsigned g = 0; g < c->num_gates; g++) {
-        take_gate(k->gates[g], c->gates[g]);
-        if (c->gates[g].kind == BJ_GATE_PROGRAM) take_program(k->gates[g].prog, c->gates[g].program);
-    }
-    uint64_t col = (uint64_t)c->num_gp_vars + (uint64_t)k->lookup_cps * c->lookup_reps, spec_consts = 0;
-    for (unsigned g = 0; g < c->num_specialized_gates; g++)
-        spec_consts += (uint64_t)c->specialized_gates[g].num_repetitions * c->specialized_gates[g].const_stride;
-    unsigned ccol = c->num_constant_cols - (unsigned)spec_consts;
-    k->spec.resize(c->num_specialized_gates);
-    for (unsigned g = 0; g < c->num_specialized_gates; g++) {
-        bj_vk::Gate &sg = k->spec[g];
-        take_gate(sg, c->specialized_gates[g]);
-        take_program(sg.prog, c->specialized_gates[g].program);
-        sg.first_col = (unsigned)col;
-        sg.first_const = ccol;
-        col += (uint64_t)sg.reps * sg.var_stride;
-        ccol += sg.reps * sg.const_stride;
-    }
+    take_gates(k, L, [&](bool spec, size_t g, bj_vk::Program *P) { take_program((spec ? c->specialized_gates : c->gates)[g].program, P); });
     k->non_residues.assign(c->non_residues, c->non_residues + c->num_vars);
     for (unsigned i = 0; i < c->num_public_inputs; i++) {
         k->pub_cols.push_back(c->public_input_cols[i]);
@@ -1109,29 +1095,12 @@ int bj_vk_from_setup(const bj_setup *S, bj_vk **out) {
     k->log_n = S->log_n; k->V = S->V; k->num_gp_vars = S->num_gp_vars; k->Wc = S->Wc; k->nC = S->nC;
     k->lookup_w = S->lookup_w; k->lookup_reps = S->lookup_reps; k->q = S->q;
     k->tid_var = S->tid_var; k->table_id_col = S->table_id_col; k->lookup_cps = S->lookup_cps;
-    auto take_program = [](bj_vk::Program &P, const bj::DevProgram &d) {
-        P.rel = d.h_rel;
-        P.values = d.h_values;
-        P.n_slots = slots_of(P.rel);
+    auto take_program = [](const bj::DevProgram &d, bj_vk::Program *P) {
+        P->rel = d.h_rel;
+        P->values = d.h_values;
+        P->n_slots = slots_of(P->rel);
     };
-    k->gates.resize(S->n_gates);
-    for (unsigned g = 0; g < S->n_gates; g++) {
-        const int *f = S->gates_flat.data() + 12 * g;
-        bj_vk::Gate &G = k->gates[g];
-        G.kind = f[0]; G.path_len = (unsigned)f[1]; G.reps = (unsigned)f[2]; G.var_stride = (unsigned)f[3]; G.const_stride = (unsigned)f[4];
-        G.num_terms = (unsigned)f[5];
-        for (unsigned b = 0; b < G.path_len && b < 6; b++) G.path[b] = (unsigned char)f[6 + b];
-        G.wit_stride = S->gate_wit_stride[g];
-        if (G.kind == BJ_GATE_PROGRAM) take_program(G.prog, S->programs[g]);
-    }
-    k->spec.resize(S->spec.size());
-    for (size_t g = 0; g < S->spec.size(); g++) {
-        const bj_setup::SpecGate &sg = S->spec[g];
-        bj_vk::Gate &G = k->spec[g];
-        G.kind = BJ_GATE_PROGRAM; G.reps = sg.reps; G.var_stride = sg.width; G.const_stride = sg.const_width; G.num_terms = sg.terms;
-        G.first_col = sg.first_col; G.first_const = sg.first_const;
-        take_program(G.prog, sg.program);
-    }
+    take_gates(k, S->gates, [&](bool spec, size_t g, bj_vk::Program *P) { take_program((spec ? S->spec_programs : S->programs)[g], P); });
     k->non_residues = S->non_residues;
     k->pub_cols = S->pub_cols;
     k->pub_rows = S->pub_rows;

@@ -190,6 +190,57 @@ def test_quotient_term_kernels_one_by_one_and_together(log_n, kw):
         b.free()
 
 
+def test_quotient_gates_fused_op_list_launch_equals_the_per_gate_launches_and_the_definition():
+    """bj_quotient_gates sends its op-list gates through the dispatcher of a proof: those with generated bodies go out as one fused
+    launch once there are two of them.  The smallest such input — three generated op lists under selector paths of lengths 1, 3
+    and 5 next to one FMA gate, 2^8 points at a stride of 2^8 + 8 — once as it is and once with BJ_GATE_NO_FUSE=1 (one launch
+    per gate): the same words both ways, the words of tests/quotient_ref.py's python-integer definition, and the eight words
+    behind the points of either output column untouched."""
+    import ctypes
+    import os
+
+    import quotient_cases as QC
+    import quotient_ref as R
+    from era_boojum_amd import gate_program as GP
+
+    def op_list(program, width, reps, path):
+        return S.GateDesc(S.GATE_PROGRAM, "op list", 2, 0, width, reps, width, 0, program.num_terms, True, path=path, program=program)
+
+    points, stride = 1 << 8, (1 << 8) + 8
+    gates = [op_list(GP.boolean_program(), 1, 5, [True]),
+             S.GateDesc(S.GATE_FMA, "FmaGateInBaseFieldWithoutConstant", 3, 2, 4, 2, 4, 0, 1, True, path=[False, True]),
+             op_list(GP.selection_program(), 4, 3, [False, False, True]),
+             op_list(GP.u32_add_program(), 5, 3, [False, True, False, False, True])]
+    assert all(E.load_library().bj_gate_program_generated(ctypes.byref(g.program.struct)) == 1 for g in gates if g.program is not None)
+    rng = np.random.default_rng(20260607)
+    variables = QC.raw_columns(rng, 15, stride, points, salt=2)      # 3 repetitions of 5 columns are the widest
+    constants = QC.raw_columns(rng, 5, stride, points, salt=4)       # the longest path; the FMA gate reads constants 2 and 3
+    alphas = QC.raw_alphas(rng, sum(g.reps * g.num_terms for g in gates), False)
+    init = QC.raw_columns(rng, 2, stride, points, salt=1)
+    want = R.to_words(*R.gates_term(variables, constants, gates, alphas, points))
+    dv, dc, do = DevBuf(variables), DevBuf(constants), DevBuf(init)
+    got = {}
+    try:
+        for no_fuse in (False, True):
+            if no_fuse:
+                os.environ["BJ_GATE_NO_FUSE"] = "1"      # the switches are read once per process: bj_env_reload re-reads them
+            try:
+                E.load_library().bj_env_reload()
+                ctx().h2d(do.ptr, init)
+                ctx().quotient_gates(dv.ptr, stride, 15, dc.ptr, stride, 5, gates, alphas, points, do.ptr, do.ptr + 8 * stride)
+                got[no_fuse] = do.get((2, stride))
+            finally:
+                os.environ.pop("BJ_GATE_NO_FUSE", None)
+                E.load_library().bj_env_reload()
+    finally:
+        for b in (dv, dc, do):
+            b.free()
+    assert np.array_equal(got[False], got[True])
+    for out in got.values():
+        assert np.array_equal(out[:, :points], want)
+        assert np.array_equal(out[:, points:], init[:, points:])
+
+
 def test_stage_operators_report_bad_arguments():
     import era_boojum_amd as E
     d = DevBuf(nelems=64)
