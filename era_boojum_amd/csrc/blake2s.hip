@@ -7,11 +7,13 @@
 // elements, i.e. 8 coalesced column loads.  Pure 32-bit add/xor/rotate (v_alignbit) work: ~1.3 k VALU instructions per
 // 64-byte block against ~14 k for one Poseidon2 permutation over the same 8 elements.
 // Digests are stored as four little-endian u64 words = the 32 digest bytes in memory order (never canonicalised).
-// Where a lane finds its words, the launch helper and the entry this file contributes to the hasher dispatch of tree_hash.hip
-// (which also walks the node layers): tree_plan.h.  The block loops (8 words + the byte counter t) are this file's own.
+// The per-lane kernel bodies (tree leaves through their three doors, node layers, proof of work) are the plan of byte_tree.h,
+// shared with keccak.hip; the fetches, the launch helpers and the entry this file contributes to the hasher dispatch of
+// tree_hash.hip are in tree_plan.h.  Here: the compression, the policy with the ONE block loop (8 words + the byte counter t),
+// the entry points.
 #include "gl.h"
 #include "kernels.h"
-#include "tree_plan.h"
+#include "byte_tree.h"
 #include "verify_open.h"
 
 using gl::u64;
@@ -74,90 +76,17 @@ struct B2s {
 #pragma unroll
         for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[8 + i];
     }
-    __device__ __forceinline__ void store(u64 *dst) const {
-        ulonglong2 *d = reinterpret_cast<ulonglong2 *>(dst);
-        d[0] = make_ulonglong2(gl::pack(h[0], h[1]), gl::pack(h[2], h[3]));
-        d[1] = make_ulonglong2(gl::pack(h[4], h[5]), gl::pack(h[6], h[7]));
+    __device__ __forceinline__ void digest(u64 (&d)[4]) const {
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = gl::pack(h[2 * k], h[2 * k + 1]);
     }
 };
 
-// leaf I = Blake2s over the canonical little-endian bytes of cols[0][I], cols[1][I], ...
-__global__ void __launch_bounds__(256)
-blake2s_leaves_kernel(const u64 *base, size_t col_stride, const u64 *const *col_ptrs, unsigned n_cols, size_t num_leaves,
-                      u64 *digests) {
-    const size_t I = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= num_leaves) return;
-    B2s st;
-    st.init();
-    const unsigned n_blocks = n_cols ? (n_cols + 7) / 8 : 1;   // an empty message is one (final) zero block
-    for (unsigned b = 0; b < n_blocks; b++) {
-        u32 m[16];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const unsigned c = b * 8 + k;
-            const u64 v = c < n_cols ? gl::canon(leaf_word(base, col_stride, col_ptrs, c, I)) : 0;
-            m[2 * k] = gl::lo32(v);
-            m[2 * k + 1] = gl::hi32(v);
-        }
-        const bool last = b + 1 == n_blocks;
-        const u64 t = last ? (u64)n_cols * 8 : (u64)(b + 1) * 64;
-        st.compress(m, t, last);
-    }
-    st.store(digests + 4 * I);
-}
-
-// leaf j = Blake2s( src0[jE..(j+1)E) || src1[jE..(j+1)E) )   (FRI oracles, merkle_tree.rs:176-386)
-__global__ void __launch_bounds__(256)
-blake2s_leaves_chunked_kernel(const u64 *src0, const u64 *src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
-                              u64 *digests) {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= num_leaves) return;
-    const unsigned E = 1u << log_e, total = n_srcs * E;
-    B2s st;
-    st.init();
-    const unsigned n_blocks = (total + 7) / 8;
-    for (unsigned b = 0; b < n_blocks; b++) {
-        u32 m[16];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const unsigned e = b * 8 + k;
-            const u64 v = e < total ? gl::canon(chunk_word(src0, src1, log_e, E, j, e)) : 0;
-            m[2 * k] = gl::lo32(v);
-            m[2 * k + 1] = gl::hi32(v);
-        }
-        const bool last = b + 1 == n_blocks;
-        st.compress(m, last ? (u64)total * 8 : (u64)(b + 1) * 64, last);
-    }
-    st.store(digests + 4 * j);
-}
-
-// next[i] = Blake2s( prev[2i] || prev[2i+1] ): exactly one 64-byte block
-__global__ void __launch_bounds__(256) blake2s_nodes_kernel(const u64 *prev, u64 *next, size_t n_nodes) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_nodes) return;
-    const ulonglong2 *p = reinterpret_cast<const ulonglong2 *>(prev + 8 * i);
-    u32 m[16];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        ulonglong2 w = p[k];
-        m[4 * k] = gl::lo32(w.x);
-        m[4 * k + 1] = gl::hi32(w.x);
-        m[4 * k + 2] = gl::lo32(w.y);
-        m[4 * k + 3] = gl::hi32(w.y);
-    }
-    B2s st;
-    st.init();
-    st.compress(m, 64, true);
-    st.store(next + 4 * i);
-}
-
-// bj_verify / bj_verify_batch: what a (query, oracle) Merkle chain (verify_open.h) takes from the leaf and node hashes above
-struct B2sVerifyHasher {
-    static __device__ __forceinline__ void digest(const B2s &st, u64 (&d)[4]) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) d[k] = gl::pack(st.h[2 * k], st.h[2 * k + 1]);
-    }
-    static __device__ __forceinline__ void leaf(const u64 *w, unsigned n, u64 (&d)[4]) {
+// the hash policy of byte_tree.h / verify_open.h
+struct Blake2sTree {
+    // 8 canonical words per 64-byte block; an empty message is one (final) zero block
+    template <typename W>
+    static __device__ __forceinline__ void leaf(W word, unsigned n, u64 (&d)[4]) {
         B2s st;
         st.init();
         const unsigned n_blocks = n ? (n + 7) / 8 : 1;
@@ -166,15 +95,16 @@ struct B2sVerifyHasher {
 #pragma unroll
             for (int k = 0; k < 8; k++) {
                 const unsigned c = b * 8 + k;
-                const u64 v = c < n ? gl::canon(w[c]) : 0;
+                const u64 v = c < n ? gl::canon(word(c)) : 0;
                 m[2 * k] = gl::lo32(v);
                 m[2 * k + 1] = gl::hi32(v);
             }
             const bool last = b + 1 == n_blocks;
             st.compress(m, last ? (u64)n * 8 : (u64)(b + 1) * 64, last);
         }
-        digest(st, d);
+        st.digest(d);
     }
+    // exactly one 64-byte block
     static __device__ __forceinline__ void node(const u64 (&l)[4], const u64 (&r)[4], u64 (&d)[4]) {
         u32 m[16];
 #pragma unroll
@@ -187,64 +117,53 @@ struct B2sVerifyHasher {
         B2s st;
         st.init();
         st.compress(m, 64, true);
-        digest(st, d);
+        st.digest(d);
+    }
+    // seed = 5 field elements = 40 bytes, so seed || nonce is one 48-byte block
+    static __device__ __forceinline__ u64 pow_word(const u64 (&seed)[5], u64 nonce) {
+        u32 m[16];
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            m[2 * k] = gl::lo32(seed[k]);
+            m[2 * k + 1] = gl::hi32(seed[k]);
+        }
+        m[10] = gl::lo32(nonce);
+        m[11] = gl::hi32(nonce);
+        m[12] = m[13] = m[14] = m[15] = 0;
+        B2s st;
+        st.init();
+        st.compress(m, 48, true);
+        return gl::pack(st.h[0], st.h[1]);
     }
 };
 
-// Proof of work (impl PoWRunner for Blake2s256, src/cs/implementations/pow.rs:50-133): the smallest nonce such that the
-// first 8 digest bytes of Blake2s(seed || le64(nonce)), read as a little-endian u64, have >= pow_bits trailing zeros.
-// seed = 5 field elements = 40 bytes, so seed || nonce is one 48-byte block.  lane = nonce; the minimum over the launch.
-struct PowSeed {
-    u32 w[10];
-};
+// the plan of byte_tree.h around this hash
+__global__ void __launch_bounds__(256)
+blake2s_leaves_kernel(const u64 *base, size_t col_stride, const u64 *const *col_ptrs, unsigned n_cols, size_t num_leaves,
+                      u64 *digests) {
+    byte_leaves<Blake2sTree>(base, col_stride, col_ptrs, n_cols, num_leaves, digests);
+}
+__global__ void __launch_bounds__(256)
+blake2s_leaves_chunked_kernel(const u64 *src0, const u64 *src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
+                              u64 *digests) {
+    byte_leaves_chunked<Blake2sTree>(src0, src1, n_srcs, log_e, num_leaves, digests);
+}
+__global__ void __launch_bounds__(256) blake2s_nodes_kernel(const u64 *children, u64 *parents, size_t num_parents) {
+    byte_nodes<Blake2sTree>(children, parents, num_parents);
+}
 __global__ void __launch_bounds__(256) blake2s_pow_kernel(PowSeed seed, unsigned pow_bits, u64 base, u64 count, unsigned long long *result) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const u64 nonce = base + i;
-    u32 m[16];
-#pragma unroll
-    for (int k = 0; k < 10; k++) m[k] = seed.w[k];
-    m[10] = gl::lo32(nonce);
-    m[11] = gl::hi32(nonce);
-    m[12] = m[13] = m[14] = m[15] = 0;
-    B2s st;
-    st.init();
-    st.compress(m, 48, true);
-    const u64 first = gl::pack(st.h[0], st.h[1]);
-    const unsigned tz = first ? (unsigned)__builtin_ctzll(first) : 64u;
-    if (tz >= pow_bits) atomicMin(result, (unsigned long long)nonce);
+    byte_pow<Blake2sTree>(seed, pow_bits, base, count, result);
 }
 
 }  // namespace
 
-void launch_blake2s_pow(const u64 *seed5, unsigned pow_bits, u64 base, u64 count, u64 *d_result, hipStream_t s) {
-    PowSeed ps;
-    for (int k = 0; k < 5; k++) {
-        ps.w[2 * k] = gl::lo32(seed5[k]);
-        ps.w[2 * k + 1] = gl::hi32(seed5[k]);
-    }
-    launch_1d(blake2s_pow_kernel, count, s, ps, pow_bits, base, count, (unsigned long long *)d_result);
-}
-
-static void launch_blake2s_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
-                                  size_t num_leaves, u64 *d_digests, hipStream_t s) {
-    launch_1d(blake2s_leaves_kernel, num_leaves, s, d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests);
-}
-static void launch_blake2s_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
-                                          u64 *d_digests, hipStream_t s) {
-    launch_1d(blake2s_leaves_chunked_kernel, num_leaves, s, d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests);
-}
-static void launch_blake2s_nodes(const u64 *d_children, u64 *d_parents, size_t num_parents, hipStream_t s) {
-    launch_1d(blake2s_nodes_kernel, num_parents, s, d_children, d_parents, num_parents);
-}
 // bj_verify / bj_verify_batch: one (query, oracle) Merkle chain per lane over every proof of the launch, chain -> (proof, query)
 // through the record table (verify_open.h)
-__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) blake2s_verify_openings_kernel(VerifyOpenArgs A) { verify_open_bytes<B2sVerifyHasher>(A); }
-static void launch_blake2s_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
-    hipLaunchKernelGGL(blake2s_verify_openings_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
-}
+__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) blake2s_verify_openings_kernel(VerifyOpenArgs A) { verify_open<verify_chain_bytes<Blake2sTree>>(A); }
+
 TreeHasher blake2s_tree_hasher() {
-    return {launch_blake2s_leaves, launch_blake2s_leaves_chunked, launch_blake2s_nodes, nullptr, launch_blake2s_verify_openings};
+    return {tree_leaves<blake2s_leaves_kernel>, tree_leaves_chunked<blake2s_leaves_chunked_kernel>, tree_nodes<blake2s_nodes_kernel>, nullptr,
+            tree_verify_openings<blake2s_verify_openings_kernel>, tree_pow<blake2s_pow_kernel>};
 }
 
 }  // namespace bj

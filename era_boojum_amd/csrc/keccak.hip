@@ -3,11 +3,12 @@
 //   leaf = Keccak256( le64(canonical(e_0)) || le64(canonical(e_1)) || ... ),   node = Keccak256( left[32] || right[32] )
 // lane = leaf / node; the 25-lane state lives in VGPRs (50 registers); a rate block is 17 field elements = 17 state lanes,
 // so absorbing is 17 coalesced column loads XORed straight into the state.  Digests: state lanes 0..3 (little endian).
-// Where a lane finds its words, the launch helper and the entry this file contributes to the hasher dispatch of tree_hash.hip
-// (which also walks the node layers): tree_plan.h.  The block loops (17 words + pad10*1) are this file's own.
+// The per-lane kernel bodies (tree leaves through their three doors, node layers, proof of work) are the plan of byte_tree.h,
+// shared with blake2s.hip; the fetches, the launch helpers and the entry this file contributes to the hasher dispatch of
+// tree_hash.hip are in tree_plan.h.  Here: the permutation, the policy with the ONE block loop (17 words + pad10*1), the entry points.
 #include "gl.h"
 #include "kernels.h"
-#include "tree_plan.h"
+#include "byte_tree.h"
 #include "verify_open.h"
 
 using gl::u64;
@@ -72,100 +73,31 @@ struct Keccak {
         a[16] ^= last;
         keccak_f(a);
     }
-    __device__ __forceinline__ void store(u64 *dst) const {
-        ulonglong2 *d = reinterpret_cast<ulonglong2 *>(dst);
-        d[0] = make_ulonglong2(a[0], a[1]);
-        d[1] = make_ulonglong2(a[2], a[3]);
+    __device__ __forceinline__ void digest(u64 (&d)[4]) const {
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = a[k];
     }
 };
 
-__global__ void __launch_bounds__(256)
-keccak_leaves_kernel(const u64 *base, size_t col_stride, const u64 *const *col_ptrs, unsigned n_cols, size_t num_leaves,
-                     u64 *digests) {
-    const size_t I = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= num_leaves) return;
-    Keccak st;
-    st.init();
-    unsigned c = 0;
-    for (; c + 17 <= n_cols; c += 17) {   // full rate blocks
-#pragma unroll
-        for (int k = 0; k < 17; k++) {
-            st.a[k] ^= gl::canon(leaf_word(base, col_stride, col_ptrs, c + k, I));
-        }
-        keccak_f(st.a);
-    }
-    const unsigned rem = n_cols - c;     // 0..16 words in the last block, then the padding
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        if ((unsigned)k < rem) {
-            st.a[k] ^= gl::canon(leaf_word(base, col_stride, col_ptrs, c + k, I));
-        }
-    }
-    st.pad_and_permute(rem);
-    st.store(digests + 4 * I);
-}
-
-__global__ void __launch_bounds__(256)
-keccak_leaves_chunked_kernel(const u64 *src0, const u64 *src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
-                             u64 *digests) {
-    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= num_leaves) return;
-    const unsigned E = 1u << log_e, total = n_srcs * E;
-    Keccak st;
-    st.init();
-    unsigned e0 = 0;
-    for (; e0 + 17 <= total; e0 += 17) {
-#pragma unroll
-        for (int k = 0; k < 17; k++) {
-            st.a[k] ^= gl::canon(chunk_word(src0, src1, log_e, E, j, e0 + k));
-        }
-        keccak_f(st.a);
-    }
-    const unsigned rem = total - e0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        if ((unsigned)k < rem) {
-            st.a[k] ^= gl::canon(chunk_word(src0, src1, log_e, E, j, e0 + k));
-        }
-    }
-    st.pad_and_permute(rem);
-    st.store(digests + 4 * j);
-}
-
-__global__ void __launch_bounds__(256) keccak_nodes_kernel(const u64 *prev, u64 *next, size_t n_nodes) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_nodes) return;
-    const ulonglong2 *p = reinterpret_cast<const ulonglong2 *>(prev + 8 * i);
-    Keccak st;
-    st.init();
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        ulonglong2 w = p[k];
-        st.a[2 * k] = w.x;
-        st.a[2 * k + 1] = w.y;
-    }
-    st.pad_and_permute(8);   // 64 message bytes = 8 lanes
-    st.store(next + 4 * i);
-}
-
-// bj_verify / bj_verify_batch: what a (query, oracle) Merkle chain (verify_open.h) takes from the leaf and node hashes above
-struct KeccakVerifyHasher {
-    static __device__ __forceinline__ void leaf(const u64 *w, unsigned n, u64 (&d)[4]) {
+// the hash policy of byte_tree.h / verify_open.h.  Every index into the state is a constant after unrolling (a run-time index
+// would send the 25 lanes to scratch): the tail is selected by k < rem, the padding lane inside pad_and_permute
+struct KeccakTree {
+    template <typename W>
+    static __device__ __forceinline__ void leaf(W word, unsigned n, u64 (&d)[4]) {
         Keccak st;
         st.init();
         unsigned c = 0;
-        for (; c + 17 <= n; c += 17) {
+        for (; c + 17 <= n; c += 17) {   // full rate blocks
 #pragma unroll
-            for (int k = 0; k < 17; k++) st.a[k] ^= gl::canon(w[c + k]);
+            for (int k = 0; k < 17; k++) st.a[k] ^= gl::canon(word(c + k));
             keccak_f(st.a);
         }
-        const unsigned rem = n - c;
+        const unsigned rem = n - c;      // 0..16 words in the last block, then the padding
 #pragma unroll
         for (int k = 0; k < 16; k++)
-            if ((unsigned)k < rem) st.a[k] ^= gl::canon(w[c + k]);
+            if ((unsigned)k < rem) st.a[k] ^= gl::canon(word(c + k));
         st.pad_and_permute(rem);
-#pragma unroll
-        for (int k = 0; k < 4; k++) d[k] = st.a[k];
+        st.digest(d);
     }
     static __device__ __forceinline__ void node(const u64 (&l)[4], const u64 (&r)[4], u64 (&d)[4]) {
         Keccak st;
@@ -175,60 +107,48 @@ struct KeccakVerifyHasher {
             st.a[k] = l[k];
             st.a[4 + k] = r[k];
         }
-        st.pad_and_permute(8);
+        st.pad_and_permute(8);   // 64 message bytes = 8 lanes
+        st.digest(d);
+    }
+    // seed = 5 field elements = 40 bytes, so seed || nonce is six lanes of one rate block
+    static __device__ __forceinline__ u64 pow_word(const u64 (&seed)[5], u64 nonce) {
+        Keccak st;
+        st.init();
 #pragma unroll
-        for (int k = 0; k < 4; k++) d[k] = st.a[k];
+        for (int k = 0; k < 5; k++) st.a[k] = seed[k];
+        st.a[5] = nonce;
+        st.pad_and_permute(6);   // 48 message bytes = 6 lanes
+        return st.a[0];
     }
 };
 
-// Proof of work (impl PoWRunner for Keccak256, src/cs/implementations/pow.rs:139-230): the smallest nonce such that the first
-// 8 digest bytes of Keccak256(seed || le64(nonce)), read as a little-endian u64, have >= pow_bits trailing zeros.  seed = 5 field
-// elements = 40 bytes, so seed || nonce is six lanes of one rate block; lane = nonce, the minimum over the launch.
-struct KeccakPowSeed {
-    u64 w[5];
-};
-__global__ void __launch_bounds__(256) keccak_pow_kernel(KeccakPowSeed seed, unsigned pow_bits, u64 base, u64 count, unsigned long long *result) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const u64 nonce = base + i;
-    Keccak st;
-    st.init();
-#pragma unroll
-    for (int k = 0; k < 5; k++) st.a[k] = seed.w[k];
-    st.a[5] = nonce;
-    st.pad_and_permute(6);   // 48 message bytes = 6 lanes
-    const u64 first = st.a[0];
-    const unsigned tz = first ? (unsigned)__builtin_ctzll(first) : 64u;
-    if (tz >= pow_bits) atomicMin(result, (unsigned long long)nonce);
+// the plan of byte_tree.h around this hash
+__global__ void __launch_bounds__(256)
+keccak_leaves_kernel(const u64 *base, size_t col_stride, const u64 *const *col_ptrs, unsigned n_cols, size_t num_leaves,
+                     u64 *digests) {
+    byte_leaves<KeccakTree>(base, col_stride, col_ptrs, n_cols, num_leaves, digests);
+}
+__global__ void __launch_bounds__(256)
+keccak_leaves_chunked_kernel(const u64 *src0, const u64 *src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
+                             u64 *digests) {
+    byte_leaves_chunked<KeccakTree>(src0, src1, n_srcs, log_e, num_leaves, digests);
+}
+__global__ void __launch_bounds__(256) keccak_nodes_kernel(const u64 *children, u64 *parents, size_t num_parents) {
+    byte_nodes<KeccakTree>(children, parents, num_parents);
+}
+__global__ void __launch_bounds__(256) keccak_pow_kernel(PowSeed seed, unsigned pow_bits, u64 base, u64 count, unsigned long long *result) {
+    byte_pow<KeccakTree>(seed, pow_bits, base, count, result);
 }
 
 }  // namespace
 
-void launch_keccak_pow(const u64 *seed5, unsigned pow_bits, u64 base, u64 count, u64 *d_result, hipStream_t s) {
-    KeccakPowSeed ps;
-    for (int k = 0; k < 5; k++) ps.w[k] = seed5[k];
-    launch_1d(keccak_pow_kernel, count, s, ps, pow_bits, base, count, (unsigned long long *)d_result);
-}
-
-static void launch_keccak_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
-                                 size_t num_leaves, u64 *d_digests, hipStream_t s) {
-    launch_1d(keccak_leaves_kernel, num_leaves, s, d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests);
-}
-static void launch_keccak_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e, size_t num_leaves,
-                                         u64 *d_digests, hipStream_t s) {
-    launch_1d(keccak_leaves_chunked_kernel, num_leaves, s, d_src0, d_src1, n_srcs, log_e, num_leaves, d_digests);
-}
-static void launch_keccak_nodes(const u64 *d_children, u64 *d_parents, size_t num_parents, hipStream_t s) {
-    launch_1d(keccak_nodes_kernel, num_parents, s, d_children, d_parents, num_parents);
-}
 // bj_verify / bj_verify_batch: one (query, oracle) Merkle chain per lane over every proof of the launch, chain -> (proof, query)
 // through the record table (verify_open.h)
-__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) keccak_verify_openings_kernel(VerifyOpenArgs A) { verify_open_bytes<KeccakVerifyHasher>(A); }
-static void launch_keccak_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
-    hipLaunchKernelGGL(keccak_verify_openings_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
-}
+__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) keccak_verify_openings_kernel(VerifyOpenArgs A) { verify_open<verify_chain_bytes<KeccakTree>>(A); }
+
 TreeHasher keccak_tree_hasher() {
-    return {launch_keccak_leaves, launch_keccak_leaves_chunked, launch_keccak_nodes, nullptr, launch_keccak_verify_openings};
+    return {tree_leaves<keccak_leaves_kernel>, tree_leaves_chunked<keccak_leaves_chunked_kernel>, tree_nodes<keccak_nodes_kernel>, nullptr,
+            tree_verify_openings<keccak_verify_openings_kernel>, tree_pow<keccak_pow_kernel>};
 }
 
 }  // namespace bj

@@ -89,10 +89,9 @@ void launch_tree_leaves_absorb(int hasher, const u64 *d_base, size_t col_stride,
 // poseidon2.hip, poseidon1.hip: the bare permutation on n_states 12-word states
 void launch_poseidon2_permute_states(u64 *d_states, size_t n_states, hipStream_t s);
 void launch_poseidon1_permute_states(u64 *d_states, size_t n_states, hipStream_t s);
-// keccak.hip, blake2s.hip
-void launch_keccak_pow(const u64 *seed5, unsigned pow_bits, u64 base, u64 count, u64 *d_result, hipStream_t s);
-// Blake2s proof of work over nonces [base, base + count): atomicMin of the valid ones into *d_result (pre-set to ~0)
-void launch_blake2s_pow(const u64 *seed5, unsigned pow_bits, u64 base, u64 count, u64 *d_result, hipStream_t s);
+// tree_hash.hip: proof of work of runner BJ_POW_* over nonces [base, base + count): atomicMin of the valid ones into *d_result
+// (pre-set to ~0)
+void launch_pow(int pow_runner, const u64 *seed5, unsigned pow_bits, u64 base, u64 count, u64 *d_result, hipStream_t s);
 
 // fri.hip
 void launch_fri_fold(const u64 *d_c0, const u64 *d_c1, size_t len, u64 *d_o0, u64 *d_o1, const u64 *d_roots,

@@ -382,19 +382,12 @@ poseidon2_leaves_chunked_lanepar_kernel(const u64 *src0, const u64 *src1, unsign
 
 // bj_verify / bj_verify_batch: one (query, oracle) Merkle chain per lane over every proof of the launch, chain -> (proof, query)
 // through the record table (verify_open.h)
-__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) poseidon2_verify_openings_kernel(VerifyOpenArgs A) { verify_open_sponge<poseidon2_permutation>(A); }
-static void launch_poseidon2_verify_openings(const VerifyOpenArgs &A, hipStream_t s) {
-    hipLaunchKernelGGL(poseidon2_verify_openings_kernel, dim3((A.n_chains + VERIFY_OPEN_BLOCK - 1) / VERIFY_OPEN_BLOCK, A.n_oracles), dim3(VERIFY_OPEN_BLOCK), 0, s, A);
-}
+__global__ void __launch_bounds__(VERIFY_OPEN_BLOCK) poseidon2_verify_openings_kernel(VerifyOpenArgs A) { verify_open<verify_chain_sponge<poseidon2_permutation>>(A); }
 
 __global__ void poseidon2_permute_states_kernel(u64 *states, size_t n_states) { sponge_permute_states<poseidon2_permutation>(states, n_states); }
 
 // layers and oracles of up to bj::env().nodes_lanepar_max items are latency-bound: the lane-parallel kernels, one item per
 // 16 lanes (BJ_NODES_LANEPAR_MAX=0: never)
-static void launch_poseidon2_leaves(const u64 *d_base, size_t col_stride, const u64 *const *d_col_ptrs, unsigned n_cols,
-                                    size_t num_leaves, u64 *d_digests, hipStream_t s) {
-    launch_1d(poseidon2_leaves_kernel, num_leaves, s, d_base, col_stride, d_col_ptrs, n_cols, num_leaves, d_digests);
-}
 static void launch_poseidon2_leaves_chunked(const u64 *d_src0, const u64 *d_src1, unsigned n_srcs, unsigned log_e,
                                             size_t num_leaves, u64 *d_digests, hipStream_t s) {
     if (num_leaves <= bj::env().nodes_lanepar_max)
@@ -410,14 +403,9 @@ static void launch_poseidon2_nodes(const u64 *d_children, u64 *d_parents, size_t
     else
         launch_1d(poseidon2_nodes_kernel, num_parents, s, d_children, d_parents, num_parents);
 }
-static void launch_poseidon2_leaves_absorb(const u64 *d_base, size_t col_stride, unsigned n_cols, size_t num_leaves, u64 *d_capacity,
-                                           u64 *d_digests, bool first, bool last, hipStream_t s) {
-    launch_1d(poseidon2_leaves_absorb_kernel, num_leaves, s, d_base, col_stride, n_cols, num_leaves, d_capacity, d_digests,
-              first, last);
-}
 TreeHasher poseidon2_tree_hasher() {
-    return {launch_poseidon2_leaves, launch_poseidon2_leaves_chunked, launch_poseidon2_nodes, launch_poseidon2_leaves_absorb,
-            launch_poseidon2_verify_openings};
+    return {tree_leaves<poseidon2_leaves_kernel>, launch_poseidon2_leaves_chunked, launch_poseidon2_nodes,
+            tree_leaves_absorb<poseidon2_leaves_absorb_kernel>, tree_verify_openings<poseidon2_verify_openings_kernel>, nullptr};
 }
 
 void launch_poseidon2_permute_states(u64 *d_states, size_t n_states, hipStream_t s) {

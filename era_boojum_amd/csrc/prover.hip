@@ -881,8 +881,7 @@ int Proving::round5b_fri() {
         u64 found = none;
         for (u64 base = 0; found == none; base += batch) {   // batches in order + minimum inside a batch = the smallest nonce,
             if ((rc = bj::h2d_async(ctx, d_res.p, &none, 8))) return rc;   // i.e. what the reference's serial search returns
-            if (S->pow_runner == BJ_POW_KECCAK256) bj::launch_keccak_pow(seed, new_pow, base, batch, d_res.p, st);
-            else bj::launch_blake2s_pow(seed, new_pow, base, batch, d_res.p, st);
+            bj::launch_pow((int)S->pow_runner, seed, new_pow, base, batch, d_res.p, st);
             BJ_CHECK_LAUNCH(ctx);
             if ((rc = bj_memcpy_d2h(ctx, &found, d_res.p, 8))) return rc;
             if (base > ((u64)1 << 40)) return bj::fail(ctx, BJ_ERR_HIP, "bj_prove: proof of work did not terminate");

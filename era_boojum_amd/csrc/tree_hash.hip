@@ -39,5 +39,11 @@ void launch_tree_leaves_absorb(int hasher, const u64 *d_base, size_t col_stride,
     (h.leaves_absorb ? h : tree_hasher(BJ_HASHER_POSEIDON2)).leaves_absorb(d_base, col_stride, n_cols, num_leaves, d_capacity, d_digests, first, last, s);
 }
 void launch_verify_openings(int hasher, const VerifyOpenArgs &args, hipStream_t s) { tree_hasher(hasher).verify_openings(args, s); }
+// pow_runner = BJ_POW_*; 0 is Blake2s, the reference's default runner
+void launch_pow(int pow_runner, const u64 *seed5, unsigned pow_bits, u64 base, u64 count, u64 *d_result, hipStream_t s) {
+    PowSeed seed;
+    for (int k = 0; k < 5; k++) seed.w[k] = seed5[k];
+    tree_hasher(pow_runner == BJ_POW_KECCAK256 ? BJ_HASHER_KECCAK256 : BJ_HASHER_BLAKE2S).pow(seed, pow_bits, base, count, d_result, s);
+}
 
 }  // namespace bj

@@ -1,8 +1,8 @@
 // bj_verify / bj_verify_batch, the Merkle half of the per-query work (verifier.rs:2150-2232 for the base oracles, :2387-2519 for
 // the FRI layers): one chain per (query, oracle) — hash the opened leaf, walk the sibling path with the bits of the leaf's index,
-// compare with the cap entry the walk ends at.  The bodies here are templates over what each tree hasher brings (the sponge
-// permutation of poseidon2.hip / poseidon1.hip, the leaf and node functions of blake2s.hip / keccak.hip); every hasher file
-// wraps one in a __global__ kernel of its own and adds its launcher to the dispatch of tree_hash.hip.
+// compare with the cap entry the walk ends at.  The chain bodies here are templates over what each tree hasher brings (the sponge
+// permutation of poseidon2.hip / poseidon1.hip, the hash policy of blake2s.hip / keccak.hip); every hasher file wraps
+// verify_open around one in a __global__ kernel of its own and adds its launcher to the dispatch of tree_hash.hip.
 //
 // One launch runs the chains of every proof of a batch under ONE key; bj_verify is the batch of one.  Grid: blockIdx.y = oracle
 // (0 witness, 1 stage 2, 2 quotient, 3 setup, 4 + l = FRI layer l), blockIdx.x * 64 + lane = chain of that oracle over the whole
@@ -88,28 +88,15 @@ __device__ __forceinline__ bool verify_chain_sponge(const u64 *query, u64 index,
     for (int k = 0; k < 4; k++) ok = ok && gl::canon(s[k]) == cap[k];
     return ok;
 }
-template <void (*PERMUTE)(u64 (&)[12])>
-__device__ __forceinline__ void verify_open_sponge(const VerifyOpenArgs &A) {
-    const unsigned g = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
-    if (g >= A.n_chains) return;
-    const VerifyBatchProof &P = A.proofs[verify_batch_proof_of(A.proofs, A.n_proofs, g)];
-    const unsigned c = g - P.chain0;
-    if (c >= P.nq) return;
-    // query base, cap base and index are per-lane values (a wave may span proofs): nothing else of the record stays live
-    const u64 *query = A.base + P.queries + (size_t)c * A.query_words, *caps = A.base + P.caps;
-    const u64 index = A.base[P.indices + c];
-    const bool ok = verify_chain_sponge<PERMUTE>(query, index, A.oracle[o], caps);
-    A.status[(size_t)o * A.n_chains + g] = ok ? 1u : 0u;
-}
 
-// the byte hashers: H::leaf(words, n, digest) hashes the canonical little-endian bytes of n field elements, H::node(l, r, digest)
-// the 64 bytes of two digests; digests are four raw words
+// the byte hashers (the policy of byte_tree.h): H::leaf(word, n, digest) hashes the canonical little-endian bytes of the n field
+// elements word(0..n), H::node(l, r, digest) the 64 bytes of two digests; digests are four raw words
 template <typename H>
 __device__ __forceinline__ bool verify_chain_bytes(const u64 *query, u64 index, const VerifyOracle &O, const u64 *caps) {
     const u64 *leaf = query + O.leaf_off, *path = leaf + O.width;
     u64 ti = index >> O.shift;
     u64 d[4];
-    H::leaf(leaf, O.width, d);
+    H::leaf([=](unsigned c) { return leaf[c]; }, O.width, d);
     for (unsigned j = 0; j < O.depth; j++) {
         const u64 *sib = path + 4 * j;
         const bool right = ti & 1;
@@ -128,16 +115,20 @@ __device__ __forceinline__ bool verify_chain_bytes(const u64 *query, u64 index, 
     for (int k = 0; k < 4; k++) ok = ok && d[k] == cap[k];
     return ok;
 }
-template <typename H>
-__device__ __forceinline__ void verify_open_bytes(const VerifyOpenArgs &A) {
+
+// one chain of a launch: which (proof, query) it belongs to, the chain body CHAIN (verify_chain_sponge<PERMUTE> or
+// verify_chain_bytes<H>), its status word
+template <bool (*CHAIN)(const u64 *, u64, const VerifyOracle &, const u64 *)>
+__device__ __forceinline__ void verify_open(const VerifyOpenArgs &A) {
     const unsigned g = blockIdx.x * VERIFY_OPEN_BLOCK + threadIdx.x, o = blockIdx.y;
     if (g >= A.n_chains) return;
     const VerifyBatchProof &P = A.proofs[verify_batch_proof_of(A.proofs, A.n_proofs, g)];
     const unsigned c = g - P.chain0;
     if (c >= P.nq) return;
+    // query base, cap base and index are per-lane values (a wave may span proofs): nothing else of the record stays live
     const u64 *query = A.base + P.queries + (size_t)c * A.query_words, *caps = A.base + P.caps;
     const u64 index = A.base[P.indices + c];
-    const bool ok = verify_chain_bytes<H>(query, index, A.oracle[o], caps);
+    const bool ok = CHAIN(query, index, A.oracle[o], caps);
     A.status[(size_t)o * A.n_chains + g] = ok ? 1u : 0u;
 }
 

@@ -38,7 +38,7 @@ def test_tree_matches_oracle(n_cols, num_leaves, cap):
     d_cols.free(); d_tree.free()
 
 
-@pytest.mark.parametrize("log_e", [1, 2, 3])
+@pytest.mark.parametrize("log_e", [1, 2, 3, 4, 5, 6])     # 6 is the ABI's bound; from 4 on a leaf holds full rate blocks (1 / 3 / 7)
 def test_chunked_tree_matches_oracle(log_e):
     rng = np.random.default_rng(log_e)
     n, cap = 2048, 4
@@ -49,6 +49,40 @@ def test_chunked_tree_matches_oracle(log_e):
     d_tree = DevBuf(nelems=4 * nd)
     ctx().merkle_tree_build_chunked(d0.ptr, d1.ptr, n, log_e, cap, d_tree.ptr)
     assert np.array_equal(d_tree.get((nd, 4)), L.merkle_construct_chunked([c0, c1], 1 << log_e, cap))
+
+
+@pytest.mark.parametrize("elems", [1, 16])
+def test_one_leaf_through_the_chunked_and_the_column_door(elems):
+    """Leaf j of a chunked tree over (c0, c1) is leaf j of a column tree over the 2 * elems columns c0[j * elems + k], c1[j * elems + k]: the same
+    message, so the leaf layers are equal word for word (non-canonical input words in both sources)."""
+    leaves, cap, log_e = 128, 4, elems.bit_length() - 1
+    rng = np.random.default_rng(700 + elems)
+    c0, c1 = rand_gl(rng, (leaves * elems,), noncanonical=True), rand_gl(rng, (leaves * elems,), noncanonical=True)
+    cols = np.ascontiguousarray(np.concatenate([c0.reshape(leaves, elems), c1.reshape(leaves, elems)], axis=1).T)
+    d0, d1, d_cols = DevBuf(c0), DevBuf(c1), DevBuf(cols)
+    nd = ctx().merkle_tree_digests(leaves, cap)
+    d_a, d_b = DevBuf(nelems=4 * nd), DevBuf(nelems=4 * nd)
+    ctx().merkle_tree_build_chunked(d0.ptr, d1.ptr, leaves * elems, log_e, cap, d_a.ptr)
+    ctx().merkle_tree_build(d_cols.ptr, leaves, 2 * elems, leaves, cap, d_b.ptr)
+    a, b = d_a.get((nd, 4)), d_b.get((nd, 4))
+    assert np.array_equal(a[:leaves], b[:leaves])
+    assert np.array_equal(a[0], L.hash_leaf(cols[:, 0])) and np.array_equal(a, b)
+    for d in (d0, d1, d_cols, d_a, d_b):
+        d.free()
+
+
+@pytest.mark.parametrize("n_cols", [17, 18])    # one full rate block (the padding gets a block of its own), one block and a word
+def test_tree_from_column_pointers_matches_oracle(n_cols):
+    num_leaves, cap = 64, 4
+    rng = np.random.default_rng(800 + n_cols)
+    cols = rand_gl(rng, (n_cols, num_leaves), noncanonical=True)
+    d_cols = DevBuf(cols)
+    nd = ctx().merkle_tree_digests(num_leaves, cap)
+    d_tree = DevBuf(nelems=4 * nd)
+    perm = list(reversed(range(n_cols)))
+    ctx().merkle_tree_build_ptrs([d_cols.ptr + 8 * num_leaves * c for c in perm], num_leaves, cap, d_tree.ptr)
+    assert np.array_equal(d_tree.get((nd, 4)), L.merkle_construct(cols[perm], cap))
+    d_cols.free(); d_tree.free()
 
 
 def test_keccak_proof_equals_oracle_proof():

@@ -1,5 +1,5 @@
 """bj_verify / bj_verify_batch, the direction the other verifier tests only sample: EVERY word of a query's openings is bound, for
-every tree hasher; leaf widths on the block edges of each leaf function (csrc/verify_open.h, B2sVerifyHasher, KeccakVerifyHasher,
+every tree hasher; leaf widths on the block edges of each leaf function (csrc/verify_open.h: the Blake2sTree and KeccakTree policies,
 the two sponge instantiations); the carried-value status of deep_fri_status (csrc/verifier.hip) at every FRI layer; every word of
 the final monomials.  What each edit must be rejected as comes from the field class of the word and the order the header
 documents (verify_util.expected_rejection), never from the code under test; every proof a test left untouched must be

@@ -20,6 +20,23 @@ def test_sponge_equals_hashlib_sha3_with_fips_domain_byte():
             assert d[i].astype("<u8").tobytes() == hashlib.sha3_256(w[i].astype("<u8").tobytes()).digest(), n
 
 
+def test_chunked_leaves_of_full_rate_blocks_equal_the_byte_path():
+    """What the GPU's chunked trees are compared with at 16 / 32 / 64 elements per leaf and source (1 / 3 / 7 full rate blocks and a
+    tail): leaf 0 of the oracle's chunked tree is the hash of the concatenated canonical bytes, by the byte path, and the word path
+    at these lengths is pinned through hashlib as above."""
+    L, P = K.layer(), 2**64 - 2**32 + 1
+    rng = np.random.default_rng(5)
+    for log_e in (4, 5, 6):
+        E, n = 1 << log_e, 2048
+        c0, c1 = (rng.integers(0, 2**64 - 1, size=n, dtype=np.uint64, endpoint=True) for _ in range(2))
+        c0[0], c1[E - 1] = np.uint64(P), np.uint64(2**64 - 1)          # words >= p inside leaf 0
+        tree = L.merkle_construct_chunked([c0, c1], E, 4)
+        msg = b"".join((int(w) % P).to_bytes(8, "little") for w in list(c0[:E]) + list(c1[:E]))
+        assert tree[0].astype("<u8").tobytes() == K.keccak256_bytes(msg), log_e
+        w = np.frombuffer(msg, dtype="<u8").reshape(1, -1)
+        assert K.hash_words(w, domain=0x06)[0].astype("<u8").tobytes() == hashlib.sha3_256(msg).digest(), log_e
+
+
 def test_keccak256_known_answers():
     assert K.keccak256_bytes(b"").hex() == "c5d2460186f7233c927e7db2dcc703c0e500b653ca82273b7bfad8045d85a470"
     assert K.keccak256_bytes(b"abc").hex() == "4e03657aea45a94fc7d47ba826c8d667c0d1e6e33a64a036ec44f58fa12d6c45"
