@@ -411,19 +411,32 @@ class Context:
         self._check(self._lib.bj_combine_residues(self._h, d_residues, world, residue_len, num_cols, _np_ptr(a), d_out))
 
     FIELD_OPS = {"add": 0, "sub": 1, "mul": 2, "mul_lazy": 3, "square": 4, "inverse": 5, "ext2_mul": 6, "butterfly": 7, "addsub": 8,
-                 "add_lazy": 9, "sub_lazy": 10, "ext2_mul_lazy": 11}
+                 "add_lazy": 9, "sub_lazy": 10, "ext2_mul_lazy": 11, "reduce128": 12, "acc160": 13, "acc_ext2": 14, "mul7_lazy": 15,
+                 "mul_u32_lazy": 16, "mul_pow2": 17, "mul7": 18, "pow7": 19, "inverse_chain": 20, "ext2_inverse": 21,
+                 "ext2_inverse_chain": 22, "bitrev": 23}
+    # operator -> (parts of n words in d_a, in d_b (0: unused), in d_out); every other operator is (1, 1, 1) or unary (1, 0, 1)
+    FIELD_OP_PARTS = {"ext2_mul": (2, 2, 2), "ext2_mul_lazy": (2, 2, 2), "butterfly": (2, 1, 2), "addsub": (2, 0, 2), "acc160": (3, 2, 1),
+                      "acc_ext2": (2, 2, 2), "ext2_inverse": (2, 0, 2), "ext2_inverse_chain": (2, 0, 2)}
 
     def field_op(self, op, a, b=None):
-        """bj_field_op_batch on host arrays (uploads, runs, downloads): elementwise Goldilocks / F_p^2 operators."""
+        """bj_field_op_batch on host arrays (uploads, runs, downloads): elementwise Goldilocks / F_p^2 operators.  An operand of
+        several parts is [parts][n] (or flat); the result has the operand's shape, for acc160 (three parts in, one out) it is [n]."""
         a = np.ascontiguousarray(a, dtype=np.uint64)
-        n = a.size // 2 if op in ("ext2_mul", "ext2_mul_lazy", "butterfly", "addsub") else a.size
+        pa, pb, po = self.FIELD_OP_PARTS.get(op, (1, 1, 1))
+        n = a.size // pa
+        if a.size != n * pa:
+            raise ValueError("field_op %s: the first operand holds %d parts of n words" % (op, pa))
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.uint64)
+            if pb and b.size != n * pb:     # the kernel reads pb parts of n words: a short operand would be read past its end
+                raise ValueError("field_op %s: the second operand holds %d parts of %d words" % (op, pb, n))
         da = self.upload(a)
-        db = self.upload(np.ascontiguousarray(b, dtype=np.uint64)) if b is not None else None
+        db = self.upload(b) if b is not None else None
         do = self.malloc(a.nbytes)
         try:
             self._check(self._lib.bj_field_op_batch(self._h, self.FIELD_OPS[op], C.c_void_p(da), C.c_void_p(db) if db else None,
                                                     C.c_void_p(do), n))
-            return self.d2h(do, a.shape)
+            return self.d2h(do, a.shape if po == pa else (n,))
         finally:
             for p in (da, db, do):
                 if p:

@@ -409,9 +409,63 @@ __global__ void field_op_kernel(int op, const u64 *a, const u64 *b, u64 *out, si
     }
     out[i] = r;
 }
+// operators 12-23: the gl.h helpers whose device compile differs from the host's (the inline-assembly reduction and product limbs
+// under gl::Acc160, __brev) or that the kernels reach on random columns only (weak small-constant products, the inversion chains).
+// A kernel of its own: field_op_kernel's code stays what its tests pin.  Parts of a / b / out are n words each.
+//   12 reduce128(hi = a, lo = b);  13 Acc160 loaded from a = [w1:w0 | w3:w2 | w4], += b[i] * b[n + i], reduced;
+//   14 Acc160x2: cleared, fma_e2((a[i], a[n + i]), b[i], canon b[n + i]) twice, reduced;  15 mul7_weak;  16 mul_u32_weak(a, (u32)b);
+//   17 mul_pow2(canon a, b & 31);  18 mul7(canon a);  19 pow7;  20 inv_chain;  21 / 22 e2_inv / e2_inv_chain;  23 bitrev32((u32)a, b)
+__global__ void field_helper_kernel(int op, const u64 *a, const u64 *b, u64 *out, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (op == 13) {
+        gl::Acc160 acc;
+        const u64 w10 = a[i], w32 = a[n + i];
+        acc.w[0] = gl::lo32(w10); acc.w[1] = gl::hi32(w10); acc.w[2] = gl::lo32(w32); acc.w[3] = gl::hi32(w32);
+        acc.w[4] = gl::lo32(a[2 * n + i]);
+        acc.fma(b[i], b[n + i]);
+        out[i] = acc.reduce();
+        return;
+    }
+    if (op == 14) {
+        const gl::e2 t = {a[i], a[n + i]};
+        const u64 a0 = b[i], a1 = gl::canon(b[n + i]);
+        gl::Acc160x2 acc;
+        acc.clear();
+        acc.fma_e2(t, a0, a1);
+        acc.fma_e2(t, a0, a1);
+        const gl::e2 r = acc.reduce();
+        out[i] = r.c0;
+        out[n + i] = r.c1;
+        return;
+    }
+    if (op == 21 || op == 22) {
+        const gl::e2 x = {gl::canon(a[i]), gl::canon(a[n + i])};
+        const gl::e2 r = op == 21 ? gl::e2_inv(x) : gl::e2_inv_chain(x);
+        out[i] = r.c0;
+        out[n + i] = r.c1;
+        return;
+    }
+    const u64 x = a[i], y = b ? b[i] : 0;
+    u64 r;
+    switch (op) {
+    case 12: r = gl::reduce128(x, y); break;
+    case 15: r = gl::canon(gl::mul7_weak(x)); break;
+    case 16: r = gl::canon(gl::mul_u32_weak(x, (gl::u32)y)); break;
+    case 17: r = gl::mul_pow2(gl::canon(x), (unsigned)(y & 31)); break;
+    case 18: r = gl::mul7(gl::canon(x)); break;
+    case 19: r = gl::pow7(x); break;
+    case 20: r = gl::inv_chain(x); break;
+    default: r = gl::bitrev32((gl::u32)x, (unsigned)y); break;
+    }
+    out[i] = r;
+}
 void launch_field_op(int op, const u64 *a, const u64 *b, u64 *out, size_t n, hipStream_t s) {
     if (n == 0) return;
-    hipLaunchKernelGGL(field_op_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op, a, b, out, n);
+    if (op >= 12)
+        hipLaunchKernelGGL(field_helper_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op, a, b, out, n);
+    else
+        hipLaunchKernelGGL(field_op_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, op, a, b, out, n);
 }
 
 }  // namespace bj

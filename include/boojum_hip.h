@@ -157,7 +157,23 @@ enum { BJ_FIELD_ADD = 0, BJ_FIELD_SUB = 1, BJ_FIELD_MUL = 2, BJ_FIELD_MUL_LAZY =
        BJ_FIELD_ADDSUB = 8,    /* the same with twiddle 1: d_a = [u | v], d_b unused; out = [u + v | u - v] */
        BJ_FIELD_ADD_LAZY = 9, BJ_FIELD_SUB_LAZY = 10, /* sum / difference of the RAW words as weak residues (what the quotient's product
                                 * chains run between their weak products), canonicalised only for the store */
-       BJ_FIELD_EXT2_MUL_LAZY = 11 /* the F_p^2 product on weak residues: raw words in (second halves at +n) */ };
+       BJ_FIELD_EXT2_MUL_LAZY = 11, /* the F_p^2 product on weak residues: raw words in (second halves at +n) */
+       /* 12-23: the helpers under the lazy accumulators and the per-point inversions, which the kernels reach only on random
+        * columns.  Raw words in unless stated, canonical words out; parts of n words each, one after the other. */
+       BJ_FIELD_REDUCE128 = 12,    /* (d_a[i] * 2^64 + d_b[i]) mod p, any two u64 */
+       BJ_FIELD_ACC160 = 13,       /* the 160-bit accumulator: d_a = [w1:w0 | w3:w2 | w4 (low 32 bits)], d_b = [x | y]; the five words are
+                                    * loaded, x * y is added once, the sum is reduced: (state + x*y) mod p for state + x*y < 2^160 */
+       BJ_FIELD_ACC160X2_E2 = 14,  /* the pair of accumulators: d_a = [t0 | t1], d_b = [a0 | a1] (a1 canonicalised first); cleared, t * alpha
+                                    * added twice, reduced: out = [c0 | c1] = 2 t alpha in F_p^2 */
+       BJ_FIELD_MUL7_LAZY = 15,    /* 7 a on the raw word as a weak residue, canonicalised for the store; d_b unused */
+       BJ_FIELD_MUL_U32_LAZY = 16, /* a * (uint32_t)b on the raw word as a weak residue, canonicalised for the store */
+       BJ_FIELD_MUL_POW2 = 17,     /* canon(a) * 2^(b & 31) */
+       BJ_FIELD_MUL7 = 18,         /* 7 * canon(a); d_b unused */
+       BJ_FIELD_POW7 = 19,         /* a^7; d_b unused */
+       BJ_FIELD_INVERSE_CHAIN = 20, /* a^(p-2) by the addition chain of the per-point kernels, 0 -> 0; d_b unused */
+       BJ_FIELD_EXT2_INVERSE = 21, BJ_FIELD_EXT2_INVERSE_CHAIN = 22, /* the F_p^2 inverse of (canon d_a[i], canon d_a[n+i]) on the square-and-
+                                    * multiply / the addition-chain base inversion; out = [c0 | c1], (0, 0) -> (0, 0); d_b unused */
+       BJ_FIELD_BITREV = 23        /* the low b bits of (uint32_t)a reversed, b in 0..32 */ };
 int bj_field_op_batch(bj_ctx *ctx, int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n);
 
 /* Host-memory convenience for single-polynomial plumbing (what a Rust `impl PrimeFieldLikeVectorized` would call);

@@ -1,5 +1,5 @@
 // Host check of the shared field helpers of csrc/gl.h — gl::Acc160, Acc160x2, inv_chain, e2_inv_chain, mul7, pow7, omega_pow_nat,
-// domain_point — against unsigned __int128 arithmetic mod p and against gl::pow / gl::inv / gl::e2_mul / gl::e2_inv.  They are
+// domain_point, reduce128 — against unsigned __int128 arithmetic mod p and against gl::pow / gl::inv / gl::e2_mul / gl::e2_inv.  They are
 // __host__ __device__; tests/test_gl_toolbox_host.py builds this file for the host with the address and undefined-behaviour
 // sanitizers and runs it.  The kernels that use the helpers are compared with independent references by the GPU tests.
 #include "gl.h"
@@ -38,6 +38,37 @@ static u64 rnd_word() {   // any u64; a quarter of them in [p, 2^64)
 }
 static u64 mulmod(u64 a, u64 b) { return (u64)((u128)a * b % gl::P); }
 static u64 addmod(u64 a, u64 b) { return (u64)(((u128)a + b) % gl::P); }
+
+// gl::reduce128 on the grid that tests/field_helper_cases.py gives the device: both limbs of the high word on their edges, the
+// low word on the edge words and where the intermediate sum r lands on p - 1, p, p + 1, 2^64 - 1 and wraps to 0 and 1 (with
+// and without the first step's borrow)
+static void check_reduce128_grid() {
+    const u64 P = gl::P, E = gl::EPS;
+    const u64 limbs[] = {0, 1, 2, 0x7FFFFFFFULL, 0x80000000ULL, 0xFFFFFFFEULL, 0xFFFFFFFFULL};
+    const u64 words[] = {0, 1, 2, 7, 1ULL << 16, E, E + 1, E + 2, 1ULL << 48, (1ULL << 48) - 1, P - 2, P - 1, P, P + 1, ~0ULL - E, ~0ULL - 1,
+                         ~0ULL, 1ULL << 63, (1ULL << 63) - 1, 0xFFFFFFFF00000000ULL, 0xFFFFFFFEFFFFFFFFULL, 0xFFFFFFFE00000001ULL,
+                         0x8000000080000000ULL, 0x00000001FFFFFFFFULL};
+    const u64 targets[] = {P - 1, P, P + 1, ~0ULL, 0, 1};   // mod 2^64
+    for (u64 hh : limbs)
+        for (u64 hl : limbs) {
+            std::vector<u64> los(words, words + sizeof(words) / sizeof(words[0]));
+            for (u64 t : targets) {
+                los.push_back(t - hl * E + hh);
+                los.push_back(t - hl * E + hh + E);
+            }
+            for (u64 lo : los) {
+                const u64 hi = (hh << 32) | hl, got = gl::reduce128(hi, lo);
+                const u64 want = (u64)((((u128)hi << 64) | lo) % P);
+                CHECK(got == want, "reduce128(%016llx, %016llx) = %016llx, not %016llx", (unsigned long long)hi, (unsigned long long)lo,
+                      (unsigned long long)got, (unsigned long long)want);
+                CHECK(gl::reduce_limbs((u32)hh, (u32)hl, lo) == want, "reduce_limbs(%08x, %08x, %016llx)", (u32)hh, (u32)hl, (unsigned long long)lo);
+            }
+        }
+    for (int i = 0; i < 20000; i++) {
+        const u64 hi = rnd(), lo = rnd();
+        CHECK(gl::reduce128(hi, lo) == (u64)((((u128)hi << 64) | lo) % P), "reduce128(%016llx, %016llx)", (unsigned long long)hi, (unsigned long long)lo);
+    }
+}
 
 static void check_acc160() {
     const int ks[] = {1, 2, 5, 118, 4096};
@@ -171,6 +202,7 @@ int main() {
     check_inversion();
     check_mul7_pow7();
     check_twiddle_table_readers();
+    check_reduce128_grid();
     printf("gl toolbox == 128-bit arithmetic (%d checks)\n", checks);
     return 0;
 }

@@ -1,7 +1,9 @@
 """The shared field helpers of csrc/gl.h on the host: gl::Acc160 / Acc160x2 (the 160-bit lazy accumulator and the pair of
 them the term kernels keep), inv_chain / e2_inv_chain, mul7, pow7, omega_pow_nat and domain_point are __host__ __device__, so
 one stand-alone program (tests/gl_toolbox_check.cpp) compares them with unsigned __int128 arithmetic mod p and with gl::pow /
-gl::inv / gl::e2_mul / gl::e2_inv under the address and undefined-behaviour sanitizers.  The kernels built on them are compared
+gl::inv / gl::e2_mul / gl::e2_inv under the address and undefined-behaviour sanitizers, and gl::reduce128 on the edge grid of
+tests/field_helper_cases.py.  The device compile of the helpers is compared with Python integers through bj_field_op_batch
+(tests/test_gpu_field_helpers.py); the kernels built on them are compared
 word for word with independent references by the -m gpu tests (quotient terms, stage ops, openings, gate programs, Poseidon
 gates, setup placement, whole proofs)."""
 import os

@@ -1,6 +1,6 @@
 // Host check of the weak-residue helpers of csrc/gl.h (the host halves of the __host__ __device__ functions share every line
 // with the device code except gl::mul_weak, whose device form is inline assembly and is checked on the GPU through
-// bj_field_op_batch): add_weak, sub_weak, mul7_weak, e2_mul_weak, mul_pow2 and the canonical operators on extreme words and
+// bj_field_op_batch): add_weak, sub_weak, mul7_weak, mul_u32_weak, e2_mul_weak, mul_pow2 and the canonical operators on extreme words and
 // random ones, against unsigned __int128 arithmetic.      hipcc --cuda-host-only -x hip tools/gl_weak_host_check.cpp
 #include "gl.h"
 
@@ -36,10 +36,22 @@ int main() {
         }
     };
     const size_t n = w.size();
+    // 32-bit multipliers of mul_u32_weak: the copy-permutation non-residues are small, the function takes any
+    std::vector<gl::u32> ks = {0, 1, 7, 11, 13, 0x80000000u, 0xFFFFFFFEu, 0xFFFFFFFFu};
+    for (int i = 0; i < 8; i++) ks.push_back((gl::u32)splitmix(seed));
     for (size_t i = 0; i < n; i++) {
         const u64 a = w[i];
         expect("mul7_weak", gl::mul7_weak(a), red((u128)a * 7), a, 7);
         for (unsigned k = 0; k < 32; k += 5) expect("mul_pow2", gl::mul_pow2(gl::canon(a), k), red((u128)gl::canon(a) << k), a, k);
+        for (size_t j = 0; j < ks.size(); j++) {
+            const gl::u32 k = ks[j];
+            expect("mul_u32_weak", gl::mul_u32_weak(a, k), red((u128)a * k), a, k);
+            // k a = c 2^64 + 0xFFFFFFFF'........: the packed low words sit within 2^32 of 2^64 and the fold of c wraps them
+            const u64 c = k > 1 ? 1 + (a ^ j) % (k - 1) : 0;
+            const u128 near = ((u128)c << 64) + 0xFFFFFFFF00000000ULL + (gl::u32)(a >> 7);
+            const u64 b = k ? (u64)((near + k - 1) / k) : 0;
+            expect("mul_u32_weak", gl::mul_u32_weak(b, k), red((u128)b * k), b, k);
+        }
         for (size_t j = (i * 7) % 13; j < n; j += 13) {
             const u64 b = w[j];
             expect("add_weak", gl::add_weak(a, b), red((u128)a + b), a, b);
