@@ -413,10 +413,10 @@ class Context:
     FIELD_OPS = {"add": 0, "sub": 1, "mul": 2, "mul_lazy": 3, "square": 4, "inverse": 5, "ext2_mul": 6, "butterfly": 7, "addsub": 8,
                  "add_lazy": 9, "sub_lazy": 10, "ext2_mul_lazy": 11, "reduce128": 12, "acc160": 13, "acc_ext2": 14, "mul7_lazy": 15,
                  "mul_u32_lazy": 16, "mul_pow2": 17, "mul7": 18, "pow7": 19, "inverse_chain": 20, "ext2_inverse": 21,
-                 "ext2_inverse_chain": 22, "bitrev": 23}
+                 "ext2_inverse_chain": 22, "bitrev": 23, "w16_butterfly": 32}
     # operator -> (parts of n words in d_a, in d_b (0: unused), in d_out); every other operator is (1, 1, 1) or unary (1, 0, 1)
     FIELD_OP_PARTS = {"ext2_mul": (2, 2, 2), "ext2_mul_lazy": (2, 2, 2), "butterfly": (2, 1, 2), "addsub": (2, 0, 2), "acc160": (3, 2, 1),
-                      "acc_ext2": (2, 2, 2), "ext2_inverse": (2, 0, 2), "ext2_inverse_chain": (2, 0, 2)}
+                      "acc_ext2": (2, 2, 2), "w16_butterfly": (2, 1, 2), "ext2_inverse": (2, 0, 2), "ext2_inverse_chain": (2, 0, 2)}
 
     def field_op(self, op, a, b=None):
         """bj_field_op_batch on host arrays (uploads, runs, downloads): elementwise Goldilocks / F_p^2 operators.  An operand of

@@ -484,7 +484,7 @@ static int intt_groups(bj_ctx *ctx, const u64 *d_in, size_t in_col_stride, u64 *
         const unsigned nc = n_cols - c0 < group ? n_cols - c0 : group;
         u64 *out = d_out + (size_t)c0 * out_col_stride;
         bj::launch_ntt_passes(d_in + (size_t)c0 * in_col_stride, ctx->d_scratch, ctx->tw_inv, nullptr, log_n, nc, 1, in_col_stride, n, ctx->stream,
-                              bj::front_table(ctx), false, to_tiled);
+                              bj::front_table(ctx), false, to_tiled, true);
         if (to_tiled)
             bj::launch_ntt_local12_pair_tiled(ctx->d_scratch, out, ctx->tw_inv, ctx->tw_inv_scaled22, n_inv, nc, n, out_col_stride, ctx->stream);
         else
@@ -619,8 +619,8 @@ int bj_bitreverse_batch(bj_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsi
 int bj_field_op_batch(bj_ctx *ctx, int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n) {
     if (int rc = bind(ctx)) return rc;
     if (n == 0) return BJ_OK;
-    if (op < BJ_FIELD_ADD || op > BJ_FIELD_BITREV) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_field_op_batch: unknown operator");
-    if ((op == BJ_FIELD_BUTTERFLY || op == BJ_FIELD_ADDSUB) && (n & 1))
+    if (op < BJ_FIELD_ADD || (op > BJ_FIELD_BITREV && op != BJ_FIELD_W16_BUTTERFLY)) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_field_op_batch: unknown operator");
+    if ((op == BJ_FIELD_BUTTERFLY || op == BJ_FIELD_ADDSUB || op == BJ_FIELD_W16_BUTTERFLY) && (n & 1))
         return fail(ctx, BJ_ERR_INVALID_ARG, "bj_field_op_batch: the butterfly operators take an even number of pairs");
     const bool unary = op == BJ_FIELD_SQUARE || op == BJ_FIELD_INVERSE || op == BJ_FIELD_ADDSUB || op == BJ_FIELD_MUL7_LAZY ||
                        op == BJ_FIELD_MUL7 || op == BJ_FIELD_POW7 || op == BJ_FIELD_INVERSE_CHAIN || op == BJ_FIELD_EXT2_INVERSE ||

@@ -264,7 +264,7 @@ __host__ __device__ __forceinline__ u64 mul_u32_weak(u64 a, u32 k) {
 }
 
 }  // namespace gl
-#include "gl_asm.inc"   // generated: butterfly2_weak_asm, addsub2_weak_asm (tools/gen_gl_asm.py)
+#include "gl_asm.inc"   // generated: butterfly2_weak_asm, addsub2_weak_asm, shiftbf2_weak_asm (tools/gen_gl_asm.py)
 namespace gl {
 #if defined(__HIP_DEVICE_COMPILE__)
 // Lazy radix-2 butterflies of the NTT kernels, two at a time (the two chains fill each other's SGPR wait states):
@@ -308,6 +308,90 @@ __host__ __forceinline__ void addsub2_weak(u64 &ua, u64 &va, u64 &ub, u64 &vb) {
     ua = add(ca, ta); va = sub(ca, ta); ub = add(cb, tb); vb = sub(cb, tb);
 }
 #endif
+
+// ---- products by compile-time powers of two: the 16th roots of unity ----
+// 2 has order 192 in F_p and 2^96 = -1, so the subgroup of order 16 is generated by 2^12: every 16th root of unity is +-2^S with
+// S in {0, 12, ..., 84}, and a butterfly whose twiddle is one of them needs shifts and one fold, no 32 x 32 products.
+constexpr u64 cx_mul(u64 a, u64 b) { return (u64)((unsigned __int128)a * b % P); }
+constexpr u64 cx_pow(u64 a, u64 e) {
+    u64 r = 1;
+    for (; e; e >>= 1, a = cx_mul(a, a))
+        if (e & 1) r = cx_mul(r, a);
+    return r;
+}
+// the root of the twiddle tables, omega(4), is 2^(12 t) for the odd t the generator of gl_asm.inc found
+static_assert(cx_pow(0x185629dcda58878cULL, 1ULL << 28) == cx_pow(2, 12 * OMEGA16_LOG2_DIV12) && OMEGA16_LOG2_DIV12 % 2 == 1,
+              "omega(4) is not the power of 2^12 the generated sequences were made for: rerun tools/gen_gl_asm.py");
+// omega(4)^E (INV: its inverse) = (-1)^NEG * 2^S
+template <int E, bool INV>
+struct w16 {
+    static constexpr int X = (12 * (INV ? 16 - OMEGA16_LOG2_DIV12 : OMEGA16_LOG2_DIV12) * E) % 192;
+    static constexpr int S = X % 96;
+    static constexpr bool NEG = X >= 96;
+};
+// v * 2^S on weak residues (any u64 in, any u64 congruent to the product out), 0 < S < 96, S not a multiple of 32.  With k = S mod 32
+// the product v * 2^S has three 32-bit limbs a = lo32(v) << k, b = (v >> (32 - k)) mod 2^32, c = hi32(v) >> (32 - k) < 2^k at the
+// weights 2^(S-k), 2^(S-k+32), 2^(S-k+64); with 2^64 = EPS, 2^96 = -1, 2^128 = -2^32 (mod p):
+//   S < 32:  (b : a) + c EPS.       c EPS < 2^56: where the sum wraps it is below 2^56 and takes the EPS of the wrap without a second one.
+//   S < 64:  (a : 0) + b EPS - c.   R = (a : 0) + b EPS mod 2^64 (carry cy), D = R - c mod 2^64 (borrow bw), value = D + (cy - bw) 2^64:
+//            cy = bw: D.  cy alone: R <= 2^64 - 3 * 2^32 + 1 and D <= R, so D + EPS does not wrap.  bw alone: D >= 2^64 - 2^28, so
+//            D - EPS does not borrow.
+//   S > 64:  a EPS - (c : b).       a EPS < 2^64 does not wrap; where the difference borrows D >= 2^64 - 2^52, and D - EPS does not.
+// The device butterflies (gl_asm.inc: shiftbf2_weak_asm) run the same limbs; for S < 64 they leave the carry cy to the sum and the
+// difference of the butterfly, which add (wrap + cy) EPS and take off (borrow + cy) EPS in the instruction that handled the wrap
+// alone before, and send bw (R < c: about 2^-36 per product) to the canonical path with the double wraps.
+template <int S>
+__host__ __device__ __forceinline__ u64 mul_pow2_weak(u64 v) {
+    static_assert(S > 0 && S < 96 && S % 32 != 0, "shift out of range");
+    constexpr int k = S % 32;
+    const u32 a = lo32(v) << k, b = (u32)(v >> (32 - k)), c = hi32(v) >> (32 - k);
+    if (S < 32) {
+        const u64 t = (u64)c * EPS, r = pack(a, b) + t;
+        return r < t ? r + EPS : r;
+    }
+    if (S < 64) {
+        const u64 t = (u64)b * EPS, r = pack(0, a) + t, d = r - c;
+        const bool cy = r < t, bw = r < c;
+        return cy == bw ? d : cy ? d + EPS : d - EPS;
+    }
+    const u64 r = (u64)a * EPS, bc = pack(b, c), d = r - bc;
+    return r < bc ? d - EPS : d;
+}
+// (u, v) <- (u + v w, u - v w) for w = omega(4)^E (its inverse with INV), on weak residues.  A negative root swaps the two outputs.
+template <int E, bool INV>
+__host__ __device__ __forceinline__ void w16_butterfly_weak(u64 &u, u64 &v) {
+    typedef w16<E, INV> W;
+    u64 t = v;
+    if constexpr (W::S != 0) t = mul_pow2_weak<W::S>(v);
+    const u64 s = add_weak(u, t), d = sub_weak(u, t);
+    u = W::NEG ? d : s;
+    v = W::NEG ? s : d;
+}
+// two of them side by side, as the NTT kernels run them: the generated sequences on the device (the wave-uniform slow path recomputes
+// all four results canonically, as in butterfly2_weak), the helpers above on the host
+template <int EA, int EB, bool INV>
+__host__ __device__ __forceinline__ void w16_butterfly2_weak(u64 &ua, u64 &va, u64 &ub, u64 &vb) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef w16<EA, INV> WA;
+    typedef w16<EB, INV> WB;
+    u64 sa, da, sb, db;
+    if constexpr (WA::S == 0 && WB::S == 0) {
+        sa = ua; da = va; sb = ub; db = vb;
+        addsub2_weak(sa, da, sb, db);
+    } else {
+        const u64 rare = shiftbf2_weak_asm<WA::S, WB::S>(ua, va, ub, vb, sa, da, sb, db);
+        if (__builtin_expect(rare != 0, 0)) {
+            const bfly4 r = butterfly2_canonical(ua, va, cx_pow(2, WA::S), ub, vb, cx_pow(2, WB::S));
+            sa = r.sa; da = r.da; sb = r.sb; db = r.db;
+        }
+    }
+    ua = WA::NEG ? da : sa; va = WA::NEG ? sa : da;
+    ub = WB::NEG ? db : sb; vb = WB::NEG ? sb : db;
+#else
+    w16_butterfly_weak<EA, INV>(ua, va);
+    w16_butterfly_weak<EB, INV>(ub, vb);
+#endif
+}
 
 // a * 2^k mod p for 0 <= k < 32 (shift instead of multiply; used by Poseidon2's internal matrix): the part shifted
 // out is < 2^32, so the reduction is  lo + out*(2^32-1)  with one wrap/canonicalisation fix

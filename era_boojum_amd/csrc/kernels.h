@@ -48,14 +48,15 @@ struct NttIo {
     size_t in_col_stride;     // elements between input columns
     size_t in_coset_stride;   // 0 when every coset reads the same input column (the first pass), n when in place
     size_t out_col_stride;    // elements between output columns (each column holds n_cosets * n outputs)
+    bool inverse;             // tw is the inverse root's table: the register steps run the inverse 16th roots of unity
 };
 // Runs the plan of ntt_plan.h for 1..64 cosets.  d_front_table: BJ_FRONT_TABLE_WORDS words of device scratch for the twiddle table
 // of the two-pass plan; tiled_in: the caller's columns are in the tiled layout (two-pass plan only); skip_last: stop in front of
-// the plan's last pass (the caller runs its own in its place)
+// the plan's last pass (the caller runs its own in its place); inverse: d_tw is the table of the inverse root (launch_twiddles)
 constexpr size_t BJ_FRONT_TABLE_WORDS = 64 * 1024;
 void launch_ntt_passes(const u64 *d_in, u64 *d_out, const u64 *d_tw, const u64 *d_round_scale, unsigned log_n,
                        unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t out_col_stride, hipStream_t s,
-                       u64 *d_front_table, bool tiled_in = false, bool skip_last = false);
+                       u64 *d_front_table, bool tiled_in = false, bool skip_last = false, bool inverse = false);
 // true when launch_ntt_passes would take the two-pass plan for these arguments (the only plan that reads the tiled layout)
 bool ntt_two_pass_applies(const u64 *d_in, const u64 *d_out, unsigned log_n, size_t in_col_stride, size_t out_col_stride);
 void launch_bitrev_scale(const u64 *d_in, u64 *d_out, unsigned log_n, unsigned n_cols, size_t in_col_stride,

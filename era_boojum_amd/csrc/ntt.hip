@@ -246,11 +246,11 @@ bool ntt_two_pass_applies(const u64 *d_in, const u64 *d_out, unsigned log_n, siz
 // place on d_out.
 void launch_ntt_passes(const u64 *d_in, u64 *d_out, const u64 *d_tw, const u64 *d_round_scale, unsigned log_n,
                        unsigned n_cols, unsigned n_cosets, size_t in_col_stride, size_t out_col_stride,
-                       hipStream_t s, u64 *d_front_table, bool tiled_in, bool skip_last) {
+                       hipStream_t s, u64 *d_front_table, bool tiled_in, bool skip_last, bool inverse) {
     assert(n_cosets >= 1 && n_cosets <= 64);   // ShiftArgs, the front passes' LDS twiddles and the front table hold 64
     const NttPlan plan = ntt_plan({log_n, ntt_aligned16(d_in, d_out, in_col_stride, out_col_stride), env().ntt_two_pass});
     assert(!tiled_in || plan.pass[0].kind == NttPassKind::Front10);
-    NttIo io{d_in, d_out, d_tw, d_round_scale, log_n, n_cols, n_cosets, in_col_stride, 0, out_col_stride};
+    NttIo io{d_in, d_out, d_tw, d_round_scale, log_n, n_cols, n_cosets, in_col_stride, 0, out_col_stride, inverse};
     for (unsigned i = 0; i < plan.n_passes - (skip_last ? 1 : 0); i++) {
         const NttPass &p = plan.pass[i];
         switch (p.kind) {
@@ -415,6 +415,30 @@ __global__ void field_op_kernel(int op, const u64 *a, const u64 *b, u64 *out, si
 //   12 reduce128(hi = a, lo = b);  13 Acc160 loaded from a = [w1:w0 | w3:w2 | w4], += b[i] * b[n + i], reduced;
 //   14 Acc160x2: cleared, fma_e2((a[i], a[n + i]), b[i], canon b[n + i]) twice, reduced;  15 mul7_weak;  16 mul_u32_weak(a, (u32)b);
 //   17 mul_pow2(canon a, b & 31);  18 mul7(canon a);  19 pow7;  20 inv_chain;  21 / 22 e2_inv / e2_inv_chain;  23 bitrev32((u32)a, b)
+//   32 w16_butterfly2_weak on a = [u | v]: the butterflies by the 16th roots of unity (signed powers of two), pair and direction from b
+template <bool INV>
+__device__ void w16_butterfly2_pair(unsigned pair, u64 &ua, u64 &va, u64 &ub, u64 &vb) {
+    switch (pair) {
+    case 0: gl::w16_butterfly2_weak<0, 0, INV>(ua, va, ub, vb); break;
+    case 1: gl::w16_butterfly2_weak<1, 1, INV>(ua, va, ub, vb); break;
+    case 2: gl::w16_butterfly2_weak<2, 2, INV>(ua, va, ub, vb); break;
+    case 3: gl::w16_butterfly2_weak<3, 3, INV>(ua, va, ub, vb); break;
+    case 4: gl::w16_butterfly2_weak<4, 4, INV>(ua, va, ub, vb); break;
+    case 5: gl::w16_butterfly2_weak<5, 5, INV>(ua, va, ub, vb); break;
+    case 6: gl::w16_butterfly2_weak<6, 6, INV>(ua, va, ub, vb); break;
+    case 7: gl::w16_butterfly2_weak<7, 7, INV>(ua, va, ub, vb); break;
+    case 8: gl::w16_butterfly2_weak<0, 4, INV>(ua, va, ub, vb); break;
+    case 9: gl::w16_butterfly2_weak<2, 6, INV>(ua, va, ub, vb); break;
+    case 10: gl::w16_butterfly2_weak<1, 5, INV>(ua, va, ub, vb); break;
+    default: gl::w16_butterfly2_weak<3, 7, INV>(ua, va, ub, vb); break;
+    }
+}
+__device__ void w16_butterfly2_select(unsigned sel, u64 &ua, u64 &va, u64 &ub, u64 &vb) {
+    if (sel & 16u)
+        w16_butterfly2_pair<true>(sel & 15u, ua, va, ub, vb);
+    else
+        w16_butterfly2_pair<false>(sel & 15u, ua, va, ub, vb);
+}
 __global__ void field_helper_kernel(int op, const u64 *a, const u64 *b, u64 *out, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -444,6 +468,14 @@ __global__ void field_helper_kernel(int op, const u64 *a, const u64 *b, u64 *out
         const gl::e2 r = op == 21 ? gl::e2_inv(x) : gl::e2_inv_chain(x);
         out[i] = r.c0;
         out[n + i] = r.c1;
+        return;
+    }
+    if (op == 32) {   // two shift butterflies per thread, exactly as the radix-16 steps run them (n even); b[i] names the exponent pair
+        const size_t h = n / 2;
+        if (i >= h) return;
+        u64 ua = a[i], va = a[n + i], ub = a[i + h], vb = a[n + i + h];
+        w16_butterfly2_select((unsigned)b[i], ua, va, ub, vb);
+        out[i] = gl::canon(ua); out[n + i] = gl::canon(va); out[i + h] = gl::canon(ub); out[n + i + h] = gl::canon(vb);
         return;
     }
     const u64 x = a[i], y = b ? b[i] : 0;

@@ -8,14 +8,20 @@
 //   ntt_strided8_kernel  8 rounds at stride 2^rem_log, tile = 256 x 16 elems (2 steps, 1 LDS transpose; every HBM
 //                        access is a 128-byte run)
 //   ntt_strided4_kernel  4 rounds at stride 2^rem_log, tile = 16 x 256 elems (1 step, no LDS)
-// Twiddles: round r of group k needs T[k] * shift^(n/2^(r+1)).  Per step a thread needs 15 of them
-// (1 + 2 + 4 + 8); they are fetched (and coset-scaled) ONCE per workgroup and reused for every column the
-// workgroup loops over: the block-uniform ones are staged in LDS, the per-thread ones stay in VGPRs.
+// Twiddles: round r of group k needs T[k] * shift^(n/2^(r+1)).  The 15 twiddles (1 + 2 + 4 + 8) of a step all come from ONE value:
+// with beta = T[8 kb] * sc[r + 3] (the last round's first twiddle) round s of group g needs beta^(8 >> s) * omega_16^((8 >> s) bitrev(g, s)),
+// because T[2 j] is the principal square root of T[j], T[(j << s) + g] = T[j << s] * omega_(2^(s+1))^bitrev(g, s), and sc[r + 1]^2 = sc[r].
+// So a step is: x[m] *= beta^m for m = 1..15 (15 generic products), then a DFT-16 whose twiddles are 16th roots of unity — signed
+// powers of two (gl.h: w16), butterflies of shifts and one fold, no product: 15 of the 32 butterflies are plain sums and differences,
+// 17 shift.  Per step a thread needs the 15 powers beta^1..beta^15; they are built (and coset-scaled) ONCE per workgroup and reused for
+// every column the workgroup loops over: the block-uniform ones are staged in LDS, the per-thread ones stay in VGPRs.  The inverse
+// transform's table holds the inverse roots: the same step with the inverse root of unity (template parameter INV).
 // All LDS indices go through pad(l) = l + l/16, which makes every transpose below bank-conflict free for
 // ds_read_b64 / ds_write_b64 (64 x 4-byte banks).
 #include "gl.h"
 #include "kernels.h"
 
+#include <cstdio>
 #include <cstdlib>
 
 using gl::u64;
@@ -90,58 +96,80 @@ __device__ __forceinline__ void st_off(u64 *base, u32 byte_off, u64 v) {
     *reinterpret_cast<u64 *>(reinterpret_cast<char *>(base) + byte_off) = v;
 }
 
-// tw[(1<<s)-1+g] = T[(kb<<s)+g] * sc[r+s],  s = 0..3, g < 2^s
+// the base of a step's powers: beta = T[8 kb] * sc[r + 3]  (r: the step's first round, kb: its group in that round)
 template <bool SCALED>
-__device__ __forceinline__ void load_step_twiddles(u64 (&tw)[15], const u64 *__restrict__ T, u32 kb, unsigned r,
+__device__ __forceinline__ u64 step_base(const u64 *__restrict__ T, size_t kb, unsigned r, const u64 *__restrict__ sc) {
+    u64 b = T[kb << 3];
+    if (SCALED) b = gl::mul(b, sc[r + 3]);
+    return b;
+}
+// pw[m - 1] = beta^m, m = 1..15
+template <bool SCALED>
+__device__ __forceinline__ void load_step_twiddles(u64 (&pw)[15], const u64 *__restrict__ T, u32 kb, unsigned r,
                                                    const u64 *__restrict__ sc) {
+    pw[0] = step_base<SCALED>(T, kb, r, sc);
 #pragma unroll
-    for (int s = 0; s < 4; s++) {
-        u64 scale = SCALED ? sc[r + s] : 1;
-#pragma unroll
-        for (int g = 0; g < (1 << s); g++) {
-            u64 t = T[((size_t)kb << s) + g];
-            if (SCALED) t = gl::mul(t, scale);
-            tw[(1 << s) - 1 + g] = t;
-        }
-    }
+    for (int m = 2; m <= 15; m++) pw[m - 1] = gl::mul(pw[m / 2 - 1], pw[m - m / 2 - 1]);
 }
 
-// 4 rounds on 16 register-resident elements; round s pairs x[i], x[i + (8>>s)] inside groups of 16>>s.  The elements are WEAK
-// residues (any u64) from the load of the first pass to the store of the last one: butterflies run two at a time through
-// gl::butterfly2_weak, nothing is canonicalised in between (the last pass does it once per element when it stores).
-// tw: the step's 15 twiddles, in registers (array) or in LDS (pointer) — indexed by constants after unrolling either way.
-// FIRST_S = 2 runs only the last two of the four rounds (the local pass after a front pass that has already done the other two).
+// One radix-16 step = 4 rounds on 16 register-resident elements; round s pairs x[i], x[i + (8>>s)] inside groups of 16>>s.  The
+// elements are WEAK residues (any u64) from the load of the first pass to the store of the last one: nothing is canonicalised in
+// between (the last pass does it once per element when it stores).
+// pw: the step's 15 powers beta^1..beta^15, in registers (array) or in LDS (pointer) — indexed by constants either way.  The step
+// multiplies x[m] by beta^m (gl::mul_weak) and runs the shift-only DFT-16: round s of group g has the twiddle omega_16^((8 >> s) bitrev(g, s)),
+// butterflies two at a time through gl::w16_butterfly2_weak.
+// UNIT_FIRST: beta = 1 (group 0 of an unscaled transform's first rounds): no products at all.
+// FIRST_S = 2 runs only the last two of the four rounds (the local pass after a front pass that has already done the other two): four
+// DFT-4 with a base of their own each, pw[3 g + m - 1] = beta_g^m for m = 1..3, beta_g = T[8 kb + 2 g] * sc[r + 3].  FIRST_S = 3 runs the
+// last round alone, generic butterflies on its eight twiddles pw[7 + g] = T[8 kb + g] * sc[r + 3] (nothing to factor in one round).
 // PRIO: the wave lowers its issue priority round by round (3, 2, 1, 0): the SIMD's arbiter serves the oldest wave first, so the waves
 // of a workgroup would reach the barrier behind the step one after the other and the last one would compute alone; with the
 // priority falling as a wave advances, the wave that is behind is served first and they arrive together (ntt_front10)
-template <bool UNIT_FIRST, int FIRST_S = 0, bool PRIO = false>
-__device__ __forceinline__ void radix16(u64 (&x)[16], const u64 *tw) {
+template <bool UNIT_FIRST, int FIRST_S = 0, bool PRIO = false, bool INV = false>
+__device__ __forceinline__ void radix16(u64 (&x)[16], const u64 *pw) {
+    if constexpr (FIRST_S == 3) {
 #pragma unroll
-    for (int s = FIRST_S; s < 3; s++) {
-        if (PRIO) set_prio(3 - s);
-        const int half = 8 >> s;
+        for (int g = 0; g < 8; g += 2) gl::butterfly2_weak(x[2 * g], x[2 * g + 1], pw[7 + g], x[2 * g + 2], x[2 * g + 3], pw[8 + g]);
+    } else if constexpr (FIRST_S == 2) {
 #pragma unroll
-        for (int g = 0; g < (1 << s); g++) {
-            const u64 w = (UNIT_FIRST && s == 0) ? 1 : tw[(1 << s) - 1 + g];
+        for (int g = 0; g < 4; g++)
 #pragma unroll
-            for (int j = 0; j < half; j += 2) {
-                const int iu = g * 2 * half + j, iv = iu + half;
-                if (UNIT_FIRST && s == 0)
-                    gl::addsub2_weak(x[iu], x[iv], x[iu + 1], x[iv + 1]);
-                else
-                    gl::butterfly2_weak(x[iu], x[iv], w, x[iu + 1], x[iv + 1], w);
-            }
+            for (int m = 1; m < 4; m++) x[4 * g + m] = gl::mul_weak(x[4 * g + m], pw[3 * g + m - 1]);
+#pragma unroll
+        for (int g = 0; g < 4; g++) gl::w16_butterfly2_weak<0, 0, INV>(x[4 * g], x[4 * g + 2], x[4 * g + 1], x[4 * g + 3]);
+#pragma unroll
+        for (int g = 0; g < 4; g++) gl::w16_butterfly2_weak<0, 4, INV>(x[4 * g], x[4 * g + 1], x[4 * g + 2], x[4 * g + 3]);
+    } else {
+        static_assert(FIRST_S == 0, "a step runs four, two or one of its rounds");
+        if (PRIO) set_prio(3);
+        if (!UNIT_FIRST) {
+#pragma unroll
+            for (int m = 1; m < 16; m++) x[m] = gl::mul_weak(x[m], pw[m - 1]);
         }
-    }
-    if (PRIO) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
-    for (int g = 0; g < 8; g += 2)   // last round: neighbours, one twiddle per pair
-        gl::butterfly2_weak(x[2 * g], x[2 * g + 1], tw[7 + g], x[2 * g + 2], x[2 * g + 3], tw[8 + g]);
+        for (int j = 0; j < 8; j += 2) gl::w16_butterfly2_weak<0, 0, INV>(x[j], x[j + 8], x[j + 1], x[j + 9]);
+        if (PRIO) set_prio(2);
+#pragma unroll
+        for (int j = 0; j < 4; j += 2) {
+            gl::w16_butterfly2_weak<0, 0, INV>(x[j], x[j + 4], x[j + 1], x[j + 5]);
+            gl::w16_butterfly2_weak<4, 4, INV>(x[j + 8], x[j + 12], x[j + 9], x[j + 13]);
+        }
+        if (PRIO) set_prio(1);
+        gl::w16_butterfly2_weak<0, 0, INV>(x[0], x[2], x[1], x[3]);
+        gl::w16_butterfly2_weak<4, 4, INV>(x[4], x[6], x[5], x[7]);
+        gl::w16_butterfly2_weak<2, 2, INV>(x[8], x[10], x[9], x[11]);
+        gl::w16_butterfly2_weak<6, 6, INV>(x[12], x[14], x[13], x[15]);
+        if (PRIO) __builtin_amdgcn_s_setprio(0);
+        gl::w16_butterfly2_weak<0, 4, INV>(x[0], x[1], x[2], x[3]);      // last round: neighbours, exponents bitrev3(g), bitrev3(g + 1)
+        gl::w16_butterfly2_weak<2, 6, INV>(x[4], x[5], x[6], x[7]);
+        gl::w16_butterfly2_weak<1, 5, INV>(x[8], x[9], x[10], x[11]);
+        gl::w16_butterfly2_weak<3, 7, INV>(x[12], x[13], x[14], x[15]);
+    }
 }
-template <bool UNIT_FIRST>
-__device__ __forceinline__ void radix16_lds(u64 (&x)[16], const u64 *tw) { radix16<UNIT_FIRST>(x, tw); }
-// the same four rounds with every output multiplied by s: the last round runs (s u + (s w) v, s u - (s w) v) — the caller passes its
-// eight twiddles tw[7..14] already multiplied by s — so the factor costs one product per butterfly, half a product per element
+// Four rounds of GENERIC butterflies on the step's 15 twiddles tw[(1<<s)-1+g] = T[(kb<<s)+g], every output multiplied by s: the last round
+// runs (s u + (s w) v, s u - (s w) v) — the caller passes its eight twiddles tw[7..14] already multiplied by s — so the factor costs one
+// product per butterfly.  Step C of ntt_local12_pair_tiled alone: it fetches its per-lane twiddles again for every chunk of every
+// column (no room for them in registers), and fifteen loads are cheaper there than one load and fourteen products for the powers.
 __device__ __forceinline__ void radix16_scaled(u64 (&x)[16], const u64 *tw, u64 s) {
 #pragma unroll
     for (int st = 0; st < 3; st++) {
@@ -164,24 +192,27 @@ __device__ __forceinline__ void radix16_scaled(u64 (&x)[16], const u64 *tw, u64 
     }
 }
 
-// block-uniform step twiddles: 15 lanes compute them once, everyone reads them back as LDS broadcasts
+// block-uniform step powers: 15 lanes compute them once, everyone reads them back as LDS broadcasts
 template <bool SCALED>
 __device__ __forceinline__ void stage_uniform_twiddles(u64 *lds_tw, const u64 *__restrict__ T, u32 kb, unsigned r,
                                                        const u64 *__restrict__ sc) {
     const u32 t = threadIdx.x;
-    if (t < 15) {
-        const int s = 31 - __clz(t + 1);          // 0,1,1,2,2,2,2,3...
-        const int g = (int)(t + 1) - (1 << s);
-        u64 v = T[((size_t)kb << s) + g];
-        if (SCALED) v = gl::mul(v, sc[r + s]);
-        lds_tw[t] = v;
+    if (t < 15) lds_tw[t] = gl::pow(step_base<SCALED>(T, kb, r, sc), t + 1);
+}
+// the powers of sixteen consecutive groups kb0 .. kb0 + 15 of one step: tab[m * 16 + i] = beta_m^(i + 1), 240 lanes
+template <bool SCALED>
+__device__ __forceinline__ void stage_group_twiddles(u64 *tab, const u64 *__restrict__ T, size_t kb0, unsigned r, const u64 *__restrict__ sc) {
+    const u32 t = threadIdx.x;
+    if (t < 240) {
+        const u32 m = t / 15, i = t % 15;
+        tab[m * 16 + i] = gl::pow(step_base<SCALED>(T, kb0 + m, r, sc), i + 1);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // ROUNDS = 12, or 10 / 9: the same kernel without the first two / three rounds of step A (a 4096-element chunk is then four /
 // eight independent sub-transforms; the rounds that remain are exactly the last ROUNDS rounds, with the twiddle indices unchanged)
-template <bool SCALED, int ROUNDS = 12>
+template <bool SCALED, int ROUNDS = 12, bool INV = false>
 __global__ void __launch_bounds__(256, R16_WAVES) ntt_local12_kernel(R16Args a) {
     __shared__ u64 lds[LDS_ELEMS + 16 + 16 * 16];
     u64 *lds_tw = lds + LDS_ELEMS;
@@ -195,15 +226,20 @@ __global__ void __launch_bounds__(256, R16_WAVES) ntt_local12_kernel(R16Args a) 
 
     u64 twC[15];
     load_step_twiddles<SCALED>(twC, a.tw, b * 256 + t, r0 + 8, sc);
-    stage_uniform_twiddles<SCALED>(lds_tw, a.tw, b, r0, sc);
-    if (t < 240) {
-        const u32 m = t / 15, i = t % 15;
-        const int s = 31 - __clz(i + 1);
-        const int g = (int)(i + 1) - (1 << s);
-        u64 v = a.tw[(((size_t)b * 16 + m) << s) + g];
-        if (SCALED) v = gl::mul(v, sc[r0 + 4 + s]);
-        lds_twB[m * 16 + i] = v;
+    if (ROUNDS == 12) {
+        stage_uniform_twiddles<SCALED>(lds_tw, a.tw, b, r0, sc);
+    } else if (ROUNDS == 10) {   // four DFT-4: lds_tw[3 g + m - 1] = (T[8 b + 2 g] * sc[r0 + 3])^m
+        if (t < 12) {
+            u64 v = a.tw[(size_t)b * 8 + 2 * (t / 3)];
+            if (SCALED) v = gl::mul(v, sc[r0 + 3]);
+            lds_tw[t] = gl::pow(v, t % 3 + 1);
+        }
+    } else if (t < 8) {          // the last round of step A alone: its eight twiddles
+        u64 v = a.tw[(size_t)b * 8 + t];
+        if (SCALED) v = gl::mul(v, sc[r0 + 3]);
+        lds_tw[7 + t] = v;
     }
+    stage_group_twiddles<SCALED>(lds_twB, a.tw, (size_t)b * 16, r0 + 4, sc);
     __syncthreads();
 
     const unsigned col0 = blockIdx.y * a.cols_per_block;
@@ -218,21 +254,21 @@ __global__ void __launch_bounds__(256, R16_WAVES) ntt_local12_kernel(R16Args a) 
         const gcptr src = uniform_gptr(a.in + (size_t)col * a.in_col_stride + (size_t)coset * a.in_coset_stride + (size_t)b * TILE);
 #pragma unroll
         for (int j = 0; j < 16; j++) x[j] = ld_off(src + j * 256, t * 8u);
-        radix16<false, 12 - ROUNDS>(x, lds_tw);   // step A: bits 11..8 in registers, twiddles uniform (LDS broadcasts at the point of use)
+        radix16<false, 12 - ROUNDS, false, INV>(x, lds_tw);   // step A: bits 11..8 in registers, twiddles uniform (LDS broadcasts at the point of use)
 #pragma unroll
         for (int j = 0; j < 16; j++) lds[pad(j * 256 + t)] = x[j];
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 16; j++) x[j] = lds[pad(ta * 256 + j * 16 + tc)];
         __syncthreads();
-        radix16_lds<false>(x, lds_twB + ta * 16);   // step B: bits 7..4
+        radix16<false, 0, false, INV>(x, lds_twB + ta * 16);   // step B: bits 7..4
 #pragma unroll
         for (int j = 0; j < 16; j++) lds[pad(ta * 256 + j * 16 + tc)] = x[j];
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 16; j++) x[j] = lds[pad(t * 16 + j)];
         __syncthreads();
-        radix16<false>(x, twC);   // step C: bits 3..0
+        radix16<false, 0, false, INV>(x, twC);   // step C: bits 3..0
 #pragma unroll
         for (int j = 0; j < 16; j++) lds[pad(t * 16 + j)] = gl::canon(x[j]);   // the transform's output: canonical residues
         __syncthreads();
@@ -248,7 +284,7 @@ __global__ void __launch_bounds__(256, R16_WAVES) ntt_local12_kernel(R16Args a) 
 
 // ---------------------------------------------------------------------------------------------------------
 static constexpr int S8_WAVES = 3;   // tuned: 3 -> 7.6 ms, 4 -> 9.7 ms (spills) per 93 x 2^20 x 8 LDE
-template <bool SCALED, bool UNIT_FIRST>
+template <bool SCALED, bool UNIT_FIRST, bool INV>
 __global__ void __launch_bounds__(256, S8_WAVES) ntt_strided8_kernel(R16Args a) {
     __shared__ u64 lds[LDS_ELEMS + 16 + 16 * 16];
     u64 *lds_tw = lds + LDS_ELEMS;            // 15 block-uniform twiddles of the first step
@@ -264,14 +300,7 @@ __global__ void __launch_bounds__(256, S8_WAVES) ntt_strided8_kernel(R16Args a) 
     const u32 tm = t >> 4, tl = t & 15;
 
     stage_uniform_twiddles<SCALED>(lds_tw, a.tw, hi, a.r0, sc);
-    if (t < 240) {   // second-step twiddles: T[((hi*16 + m) << s) + g] * sc[r0 + 4 + s] for m < 16
-        const u32 m = t / 15, i = t % 15;
-        const int s = 31 - __clz(i + 1);
-        const int g = (int)(i + 1) - (1 << s);
-        u64 v = a.tw[(((size_t)hi * 16 + m) << s) + g];
-        if (SCALED) v = gl::mul(v, sc[a.r0 + 4 + s]);
-        lds_tw2[m * 16 + i] = v;
-    }
+    stage_group_twiddles<SCALED>(lds_tw2, a.tw, (size_t)hi * 16, a.r0 + 4, sc);   // second step: groups hi * 16 + m, m < 16
     __syncthreads();
 
     // addressing: a wave-uniform pointer per access (SGPR pair, advanced by scalar adds) + ONE 32-bit per-lane offset for the
@@ -286,14 +315,14 @@ __global__ void __launch_bounds__(256, S8_WAVES) ntt_strided8_kernel(R16Args a) 
         const gcptr src = uniform_gptr(a.in + (size_t)col * a.in_col_stride + (size_t)coset * a.in_coset_stride + tile_base);
 #pragma unroll
         for (int j = 0; j < 16; j++) x[j] = ld_off(src + ((size_t)(j * 16) << rem_log), off_ld);
-        radix16_lds<UNIT_FIRST>(x, lds_tw);    // mid bits 7..4
+        radix16<UNIT_FIRST, 0, false, INV>(x, lds_tw);    // mid bits 7..4
 #pragma unroll
         for (int j = 0; j < 16; j++) lds[pad(j * 256 + t)] = x[j];
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 16; j++) x[j] = lds[pad(tm * 256 + j * 16 + tl)];
         __syncthreads();
-        radix16_lds<false>(x, lds_tw2 + tm * 16);   // mid bits 3..0
+        radix16<false, 0, false, INV>(x, lds_tw2 + tm * 16);   // mid bits 3..0
 #pragma unroll
         for (int j = 0; j < 16; j++) st_off(dst + ((size_t)j << rem_log), off_st, x[j]);
     };
@@ -304,7 +333,7 @@ __global__ void __launch_bounds__(256, S8_WAVES) ntt_strided8_kernel(R16Args a) 
 }
 
 // ---------------------------------------------------------------------------------------------------------
-template <bool SCALED, bool UNIT_FIRST>
+template <bool SCALED, bool UNIT_FIRST, bool INV>
 __global__ void __launch_bounds__(256) ntt_strided4_kernel(R16Args a) {
     __shared__ u64 lds_tw[16];
     const u32 t = threadIdx.x;
@@ -328,7 +357,7 @@ __global__ void __launch_bounds__(256) ntt_strided4_kernel(R16Args a) {
         u64 x[16];
 #pragma unroll
         for (int j = 0; j < 16; j++) x[j] = ld_off(src + ((size_t)j << rem_log), t * 8u);
-        radix16<UNIT_FIRST>(x, tw1);
+        radix16<UNIT_FIRST, 0, false, INV>(x, tw1);
 #pragma unroll
         for (int j = 0; j < 16; j++) st_off(dst + ((size_t)j << rem_log), t * 8u, x[j]);
     }
@@ -344,17 +373,13 @@ __global__ void __launch_bounds__(256) ntt_strided4_kernel(R16Args a) {
 // it then runs 10 rounds instead of 12 (ntt_local12_kernel<., 10>).
 // The 2 x 16 input words of a lane stay in registers across the coset loop when every coset reads the same column (206 VGPRs: two
 // waves per SIMD); with a coset stride they are read per coset.
-template <bool SCALED>
+template <bool SCALED, bool INV>
 __global__ void __launch_bounds__(256, 1) ntt_first4_kernel(R16Args a, unsigned n_cosets) {
     __shared__ u64 tws[64 * 16];                          // [coset][15 (+1 pad)]
     const size_t n = (size_t)1 << a.log_n, sl = n >> 4;
     for (u32 t = threadIdx.x; t < n_cosets * 15; t += blockDim.x) {
         const u32 c = t / 15, i = t % 15;
-        const int r = 31 - __clz(i + 1);
-        const int g = (int)(i + 1) - (1 << r);
-        u64 v = a.tw[g];
-        if (SCALED) v = gl::mul(v, a.round_scale[(size_t)c * 32 + r]);
-        tws[c * 16 + i] = v;
+        tws[c * 16 + i] = gl::pow(step_base<SCALED>(a.tw, 0, 0, SCALED ? a.round_scale + (size_t)c * 32 : nullptr), i + 1);
     }
     __syncthreads();
     const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 2;
@@ -385,8 +410,8 @@ __global__ void __launch_bounds__(256, 1) ntt_first4_kernel(R16Args a, unsigned 
             }
         }
         const u64 *tw = tws + c * 16;
-        radix16<!SCALED>(x0, tw);   // unscaled: T[0] = 1, the first round is additions only
-        radix16<!SCALED>(x1, tw);
+        radix16<!SCALED, 0, false, INV>(x0, tw);   // unscaled: beta = T[0] = 1, no products
+        radix16<!SCALED, 0, false, INV>(x1, tw);
         u64 *o = dst + (size_t)c * n;
 #pragma unroll
         for (int m = 0; m < 16; m++) *reinterpret_cast<ulonglong2 *>(o + (size_t)m * sl) = make_ulonglong2(x0[m], x1[m]);
@@ -395,21 +420,20 @@ __global__ void __launch_bounds__(256, 1) ntt_first4_kernel(R16Args a, unsigned 
 
 // The first FIVE rounds the same way, one index per lane (32 elements {i + m * n/32} in registers): round 0 pairs the two
 // halves of the register file, rounds 1..4 are one radix-16 step on each half with that half's twiddles.
-template <bool SCALED>
+template <bool SCALED, bool INV>
 __global__ void __launch_bounds__(256) ntt_first5_kernel(R16Args a, unsigned n_cosets) {
-    __shared__ u64 tws[64 * 40];                          // [coset]: [0] round 0; [8 + 16 h + i] step twiddles of half h
+    __shared__ u64 tws[64 * 40];                          // [coset]: [0] round 0; [8 + 16 h + i] step powers of half h (rounds 1..4, group h)
     const size_t n = (size_t)1 << a.log_n, sl = n >> 5;
     for (u32 t = threadIdx.x; t < n_cosets * 31; t += blockDim.x) {
         const u32 c = t / 31, i = t % 31;
-        const int r = 31 - __clz(i + 1);
-        const int g = (int)(i + 1) - (1 << r);
-        u64 v = a.tw[g];
-        if (SCALED) v = gl::mul(v, a.round_scale[(size_t)c * 32 + r]);
-        if (r == 0) {
+        const u64 *sc = SCALED ? a.round_scale + (size_t)c * 32 : nullptr;
+        if (i == 0) {
+            u64 v = a.tw[0];
+            if (SCALED) v = gl::mul(v, sc[0]);
             tws[c * 40] = v;
         } else {
-            const int st = r - 1, h = g >> st, gg = g & ((1 << st) - 1);
-            tws[c * 40 + 8 + 16 * h + (1 << st) - 1 + gg] = v;
+            const u32 h = (i - 1) / 15, m = (i - 1) % 15;
+            tws[c * 40 + 8 + 16 * h + m] = gl::pow(step_base<SCALED>(a.tw, h, 1, sc), m + 1);
         }
     }
     __syncthreads();
@@ -443,8 +467,8 @@ __global__ void __launch_bounds__(256) ntt_first5_kernel(R16Args a, unsigned n_c
             else
                 gl::addsub2_weak(lo[j], hi[j], lo[j + 1], hi[j + 1]);      // T[0] = 1
         }
-        radix16<false>(lo, tw + 8);
-        radix16<false>(hi, tw + 24);
+        radix16<false, 0, false, INV>(lo, tw + 8);
+        radix16<false, 0, false, INV>(hi, tw + 24);
         u64 *o = dst + (size_t)c * n;
 #pragma unroll
         for (int m = 0; m < 16; m++) {
@@ -465,9 +489,9 @@ __global__ void __launch_bounds__(256) ntt_first5_kernel(R16Args a, unsigned n_c
 // transposes through LDS in between.  LDS indices are XOR-swizzled instead of padded (tools/lds_conflicts.py: every ds_read_b64 /
 // ds_write_b64 below is conflict-free), which keeps the tile at exactly 64 KB.
 // Twiddles: round r < 10 of group k < 2^r needs T[k] * sc_c[r]; all of them are uniform over the tiles, so they come from a
-// table tw[coset][2^r - 1 + k] (1023 entries per coset, front10_table_kernel) instead of being rebuilt by every workgroup:
-// step A's fifteen per coset sit in LDS for the whole kernel, step B's 16 x 15 are re-staged per coset, step C's three per lane
-// are loaded into registers.  The inputs of a tile are read again for every coset (no room for them in 128 VGPRs): seven of the
+// table per coset (1023 entries, front10_table_kernel) instead of being rebuilt by every workgroup: [0, 15) step A's fifteen powers,
+// [15, 255) step B's 16 x 15 powers, [255, 1023) the twiddles of rounds 8 and 9 at [2^r - 1 + k], of which step C loads three per
+// lane into registers.  The inputs of a tile are read again for every coset (no room for them in 128 VGPRs): seven of the
 // eight reads are L2 / Infinity-Cache hits.
 struct F10Args {
     const u64 *in;
@@ -498,10 +522,18 @@ __global__ void front10_table_kernel(u64 *out, const u64 *__restrict__ T, const 
         out[idx] = 0;
         return;
     }
-    const int r = 31 - __clz(e + 1);
-    const u32 k = e + 1 - (1u << r);
-    u64 v = T[k];
-    if (round_scale) v = gl::mul(v, round_scale[(size_t)c * 32 + r]);
+    const u64 *sc = round_scale ? round_scale + (size_t)c * 32 : nullptr;
+    u64 v;
+    if (e < 15u) {            // step A (rounds 0..3, group 0): beta^(e + 1)
+        v = gl::pow(sc ? step_base<true>(T, 0, 0, sc) : step_base<false>(T, 0, 0, sc), e + 1);
+    } else if (e < 255u) {    // step B (rounds 4..7, groups mh < 16): [15 + 15 mh + m - 1] = beta_mh^m
+        const u32 mh = (e - 15u) / 15u, m = (e - 15u) % 15u + 1u;
+        v = gl::pow(sc ? step_base<true>(T, mh, 4, sc) : step_base<false>(T, mh, 4, sc), m);
+    } else {                  // step C (rounds 8, 9): the twiddles themselves, [2^r - 1 + k] = T[k] * sc[r]
+        const int r = 31 - __clz(e + 1);
+        v = T[e + 1 - (1u << r)];
+        if (sc) v = gl::mul(v, sc[r]);
+    }
     out[idx] = gl::canon(v);
 }
 // The B -> C index map is LINEAR over GF(2) in the bits of (lane, register): index(lane, i) = index(lane, 0) ^ index(0, i), so a lane
@@ -513,32 +545,6 @@ __host__ __device__ constexpr u32 f10_bc(u32 m, u32 l) {
     return LB == 3 ? x ^ (((x >> 3) ^ (x >> 5)) & 31u) : x ^ (((x >> 2) ^ (x >> 4)) & 31u);
 }
 __device__ __forceinline__ u64 &f10_at(u64 *lds, u32 byte_index) { return *reinterpret_cast<u64 *>(reinterpret_cast<char *>(lds) + byte_index); }
-// four rounds on 16 registers, stage s reading its 2^s twiddles at tw[off_s + g] (one table for all ten rounds of a coset)
-template <bool UNIT_FIRST, bool PRIO>
-__device__ __forceinline__ void radix16_tab(u64 (&x)[16], const u64 *tw, u32 o0, u32 o1, u32 o2, u32 o3) {
-    const u32 off[4] = {o0, o1, o2, o3};
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-        if (PRIO) set_prio(3 - s);
-        const int half = 8 >> s;
-#pragma unroll
-        for (int g = 0; g < (1 << s); g++) {
-            const u64 w = (UNIT_FIRST && s == 0) ? 1 : tw[off[s] + g];
-#pragma unroll
-            for (int j = 0; j < half; j += 2) {
-                const int iu = g * 2 * half + j, iv = iu + half;
-                if (UNIT_FIRST && s == 0)
-                    gl::addsub2_weak(x[iu], x[iv], x[iu + 1], x[iv + 1]);
-                else
-                    gl::butterfly2_weak(x[iu], x[iv], w, x[iu + 1], x[iv + 1], w);
-            }
-        }
-    }
-    if (PRIO) __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-    for (int g = 0; g < 8; g += 2)
-        gl::butterfly2_weak(x[2 * g], x[2 * g + 1], tw[off[3] + g], x[2 * g + 2], x[2 * g + 3], tw[off[3] + g + 1]);
-}
 typedef const void __attribute__((address_space(1))) *f10_gsrc;
 typedef void __attribute__((address_space(3))) *f10_ldst;
 // A workgroup (8 waves) owns ONE (tile, coset) and loops over columns.  The eight cosets of a tile are eight workgroups that the
@@ -554,7 +560,7 @@ typedef void __attribute__((address_space(3))) *f10_ldst;
 //   registers, region w is dead: it requests the next column's pieces at once, then computes step C and stores.
 // The coset's twiddle table (8 KB) is fetched once per workgroup, by LDS-DMA as well.  The butterflies run under falling issue
 // priorities (radix16's PRIO).
-template <bool UNIT_FIRST, int LB, bool TILED_IN = false>
+template <bool UNIT_FIRST, int LB, bool TILED_IN = false, bool INV = false>
 __global__ void __launch_bounds__(64 << LB, 4) ntt_front10_kernel(F10Args a) {
     static_assert(!TILED_IN || LB == TILED_LB, "the tiled layout is defined for one tile width");
     constexpr u32 NT = 64u << LB, TILE_E = 1024u << LB, ROWS = 128u >> LB;   // threads, elements per tile, mid rows per 1-KB DMA piece
@@ -618,13 +624,13 @@ __global__ void __launch_bounds__(64 << LB, 4) ntt_front10_kernel(F10Args a) {
         u64 x[16];
 #pragma unroll
         for (int i = 0; i < 16; i++) x[i] = lds[i * NT + t];
-        radix16<UNIT_FIRST, 0, true>(x, lds_tw);
+        radix16<UNIT_FIRST, 0, true, INV>(x, lds_tw);
 #pragma unroll
         for (int i = 0; i < 16; i++) lds[i * NT + t] = x[i];          // in place: no barrier between the read and this write
         lds_barrier();
 #pragma unroll
         for (int i = 0; i < 16; i++) x[i] = f10_at(lds, jB1 + i * (32u << LB));
-        radix16_tab<false, true>(x, lds_tw, 15u + mhB, 31u + 2u * mhB, 63u + 4u * mhB, 127u + 8u * mhB);
+        radix16<false, 0, true, INV>(x, lds_tw + 15u + 15u * mhB);
 #pragma unroll
         for (int i = 0; i < 16; i++) f10_at(lds, jB2 ^ (f10_bc<LB>(i * 4u, 0) * 8u)) = x[i];      // inside this wave's region
         const u64 w8 = lds_tw[255u + m92], w9a = lds_tw[511u + 2u * m92], w9b = lds_tw[512u + 2u * m92];
@@ -663,8 +669,9 @@ __global__ void __launch_bounds__(64 << LB, 4) ntt_front10_kernel(F10Args a) {
 // choose WHICH sixteen-word group a lane takes: lane t takes group pi(t) = t with its low six bits reversed, so that m = rev4(j) * 64
 // + (t & 63) and the lanes of a store are in address order (in lane order rev6 the same kilobyte leaves as 64 separate 16-byte
 // writes: measured, the pass is then bound by them).  The twiddles of steps
-// A and B of both chunks stay in LDS (2 x (16 + 256) words); step C's fifteen per lane are fetched again for every chunk of every
-// column (L2 hits, issued with the chunk's sixteen data loads) — resident for both chunks they cost 60 VGPRs and the third wave of a SIMD.
+// A and B of both chunks stay in LDS (2 x (16 + 256) words, as powers: radix16); step C's fifteen per lane are fetched again for every chunk
+// of every column (L2 hits, issued with the chunk's sixteen data loads) — resident for both chunks they cost 60 VGPRs and the third wave
+// of a SIMD — so step C keeps the generic butterflies on the twiddles themselves, with 1 / n in the last round's (radix16_scaled).
 struct PairArgs {
     const u64 *in;
     u64 *out;
@@ -686,17 +693,8 @@ __global__ void __launch_bounds__(256, PAIR_WAVES) ntt_local12_pair_tiled_kernel
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const u32 b = bp + 512u * h;
-        if (t < 15) {
-            const int s = 31 - __clz(t + 1);
-            const int g = (int)(t + 1) - (1 << s);
-            lds_twA[h * 16 + t] = a.tw[((size_t)b << s) + g];
-        }
-        if (t < 240) {
-            const u32 m = t / 15, i = t % 15;
-            const int s = 31 - __clz(i + 1);
-            const int g = (int)(i + 1) - (1 << s);
-            lds_twB[h * 256 + m * 16 + i] = a.tw[(((size_t)b * 16 + m) << s) + g];
-        }
+        stage_uniform_twiddles<false>(lds_twA + h * 16, a.tw, b, 0, nullptr);
+        stage_group_twiddles<false>(lds_twB + h * 256, a.tw, (size_t)b * 16, 0, nullptr);
     }
     __syncthreads();
     const unsigned col0 = blockIdx.y * a.cols_per_block;
@@ -726,14 +724,14 @@ __global__ void __launch_bounds__(256, PAIR_WAVES) ntt_local12_pair_tiled_kernel
 #pragma unroll
                     for (int g = 0; g < (1 << st); g++) twC[(1 << st) - 1 + g] = (st == 3 ? a.tw_scaled : a.tw)[((size_t)kb << st) + g];
             }
-            radix16<false>(x, lds_twA + h * 16);
+            radix16<false, 0, false, true>(x, lds_twA + h * 16);      // the inverse root's table: INV
 #pragma unroll
             for (int j = 0; j < 16; j++) lds[pad(j * 256 + t)] = x[j];
             __syncthreads();
 #pragma unroll
             for (int j = 0; j < 16; j++) x[j] = lds[pad(ta * 256 + j * 16 + tc)];
             __syncthreads();
-            radix16_lds<false>(x, lds_twB + h * 256 + ta * 16);
+            radix16<false, 0, false, true>(x, lds_twB + h * 256 + ta * 16);
 #pragma unroll
             for (int j = 0; j < 16; j++) lds[pad(ta * 256 + j * 16 + tc)] = x[j];
             __syncthreads();
@@ -797,26 +795,29 @@ static unsigned pick_cols_per_block(unsigned tiles, unsigned n_cols, unsigned n_
     return cpb;
 }
 
+// which instance of a pass serves io: 0 plain forward, 1 forward on a coset (per-round scales), 2 inverse (the inverse root's table; the
+// coset factors of an inverse transform are applied behind it, never as per-round scales)
+static int step_mode(const NttIo &io) {
+    if (io.inverse && io.round_scale) {
+        fprintf(stderr, "ntt: an inverse transform takes no per-round scales\n");
+        abort();
+    }
+    return io.inverse ? 2 : io.round_scale ? 1 : 0;
+}
+
 void launch_ntt_local12(const NttIo &io, unsigned rounds, hipStream_t s) {
     unsigned tiles = 1u << (io.log_n - 12);
     unsigned cpb = pick_cols_per_block(tiles, io.n_cols, io.n_cosets);
     // r0 = log_n - 12 whatever the round count: the kernel skips the rounds the front pass has run
     R16Args a{io.in, io.out, io.tw, io.round_scale, io.log_n, io.log_n - 12, io.n_cols, cpb, io.in_col_stride, io.in_coset_stride, io.out_col_stride};
     dim3 grid(tiles, (io.n_cols + cpb - 1) / cpb, io.n_cosets);
-    if (rounds == 10) {
-        if (io.round_scale)
-            hipLaunchKernelGGL((ntt_local12_kernel<true, 10>), grid, dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL((ntt_local12_kernel<false, 10>), grid, dim3(256), 0, s, a);
-    } else if (rounds == 9) {
-        if (io.round_scale)
-            hipLaunchKernelGGL((ntt_local12_kernel<true, 9>), grid, dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL((ntt_local12_kernel<false, 9>), grid, dim3(256), 0, s, a);
-    } else if (io.round_scale)
-        hipLaunchKernelGGL((ntt_local12_kernel<true, 12>), grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((ntt_local12_kernel<false, 12>), grid, dim3(256), 0, s, a);
+    void (*k)(R16Args);
+    switch (step_mode(io)) {
+    case 1: k = rounds == 10 ? ntt_local12_kernel<true, 10, false> : rounds == 9 ? ntt_local12_kernel<true, 9, false> : ntt_local12_kernel<true, 12, false>; break;
+    case 2: k = rounds == 10 ? ntt_local12_kernel<false, 10, true> : rounds == 9 ? ntt_local12_kernel<false, 9, true> : ntt_local12_kernel<false, 12, true>; break;
+    default: k = rounds == 10 ? ntt_local12_kernel<false, 10, false> : rounds == 9 ? ntt_local12_kernel<false, 9, false> : ntt_local12_kernel<false, 12, false>; break;
+    }
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, a);
 }
 
 // last pass of a 2^22-point inverse transform into the tiled layout (in: the front pass's output, chunk b at b * 4096)
@@ -843,9 +844,19 @@ void launch_ntt_strided(const NttIo &io, unsigned r0, unsigned rounds, hipStream
     unsigned cpb = pick_cols_per_block(tiles, io.n_cols, io.n_cosets);
     R16Args a{io.in, io.out, io.tw, io.round_scale, io.log_n, r0, io.n_cols, cpb, io.in_col_stride, io.in_coset_stride, io.out_col_stride};
     dim3 grid(tiles, (io.n_cols + cpb - 1) / cpb, io.n_cosets);
-    const bool scaled = io.round_scale != nullptr, unit_first = !scaled && r0 == 0;
-    void (*k8)(R16Args) = scaled ? ntt_strided8_kernel<true, false> : unit_first ? ntt_strided8_kernel<false, true> : ntt_strided8_kernel<false, false>;
-    void (*k4)(R16Args) = scaled ? ntt_strided4_kernel<true, false> : unit_first ? ntt_strided4_kernel<false, true> : ntt_strided4_kernel<false, false>;
+    const int mode = step_mode(io);
+    const bool unit_first = mode != 1 && r0 == 0;
+    void (*k8)(R16Args), (*k4)(R16Args);
+    if (mode == 1) {
+        k8 = ntt_strided8_kernel<true, false, false>;
+        k4 = ntt_strided4_kernel<true, false, false>;
+    } else if (mode == 2) {
+        k8 = unit_first ? ntt_strided8_kernel<false, true, true> : ntt_strided8_kernel<false, false, true>;
+        k4 = unit_first ? ntt_strided4_kernel<false, true, true> : ntt_strided4_kernel<false, false, true>;
+    } else {
+        k8 = unit_first ? ntt_strided8_kernel<false, true, false> : ntt_strided8_kernel<false, false, false>;
+        k4 = unit_first ? ntt_strided4_kernel<false, true, false> : ntt_strided4_kernel<false, false, false>;
+    }
     hipLaunchKernelGGL(rounds == 8 ? k8 : k4, grid, dim3(256), 0, s, a);
 }
 
@@ -853,24 +864,33 @@ void launch_ntt_first4(const NttIo &io, hipStream_t s) {
     R16Args a{io.in, io.out, io.tw, io.round_scale, io.log_n, 0, io.n_cols, 1, io.in_col_stride, io.in_coset_stride, io.out_col_stride};
     const size_t sl = ((size_t)1 << io.log_n) >> 4;
     dim3 grid((unsigned)((sl / 2 + 255) / 256), io.n_cols, 1);   // two adjacent indices per lane
-    if (io.round_scale)
-        hipLaunchKernelGGL(ntt_first4_kernel<true>, grid, dim3(256), 0, s, a, io.n_cosets);
-    else
-        hipLaunchKernelGGL(ntt_first4_kernel<false>, grid, dim3(256), 0, s, a, io.n_cosets);
+    const int mode = step_mode(io);
+    void (*k)(R16Args, unsigned);
+    if (mode == 1) k = ntt_first4_kernel<true, false>;
+    else if (mode == 2) k = ntt_first4_kernel<false, true>;
+    else k = ntt_first4_kernel<false, false>;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, a, io.n_cosets);
 }
 
 void launch_ntt_first5(const NttIo &io, hipStream_t s) {
     R16Args a{io.in, io.out, io.tw, io.round_scale, io.log_n, 0, io.n_cols, 1, io.in_col_stride, io.in_coset_stride, io.out_col_stride};
     const size_t sl = ((size_t)1 << io.log_n) >> 5;
     dim3 grid((unsigned)((sl + 255) / 256), io.n_cols, 1);
-    if (io.round_scale)
-        hipLaunchKernelGGL(ntt_first5_kernel<true>, grid, dim3(256), 0, s, a, io.n_cosets);
-    else
-        hipLaunchKernelGGL(ntt_first5_kernel<false>, grid, dim3(256), 0, s, a, io.n_cosets);
+    const int mode = step_mode(io);
+    void (*k)(R16Args, unsigned);
+    if (mode == 1) k = ntt_first5_kernel<true, false>;
+    else if (mode == 2) k = ntt_first5_kernel<false, true>;
+    else k = ntt_first5_kernel<false, false>;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, a, io.n_cosets);
 }
 
 void launch_ntt_front10(const NttIo &io, u64 *d_table, bool tiled_in, hipStream_t s) {
     const unsigned n_cols = io.n_cols, n_cosets = io.n_cosets;
+    const int mode = step_mode(io);
+    if (tiled_in && mode == 2) {
+        fprintf(stderr, "ntt: the tiled layout is read by forward transforms only\n");
+        abort();
+    }
     hipLaunchKernelGGL(front10_table_kernel, dim3(n_cosets * 4), dim3(256), 0, s, d_table, io.tw, io.round_scale, n_cosets);
     constexpr int LBN = 4;   // natural-order input: lo values per tile = 2^LB: 3 -> 64-byte runs, 512 threads, two workgroups per CU; 4 -> full lines, 1024 threads, one
     const int lb = tiled_in ? TILED_LB : LBN;
@@ -882,15 +902,12 @@ void launch_ntt_front10(const NttIo &io, u64 *d_table, bool tiled_in, hipStream_
         while (cpb > 1 && (size_t)tiles * nc * ((n_cols + cpb - 1) / cpb) < 4096) cpb >>= 1;
         F10Args a{io.in, io.out + (size_t)c0 * n, d_table + (size_t)c0 * 1024, io.log_n, n_cols, cpb, nc, io.in_col_stride, io.out_col_stride};
         dim3 grid(tiles * nc, (n_cols + cpb - 1) / cpb, 1);
-        if (tiled_in) {
-            if (io.round_scale)
-                hipLaunchKernelGGL((ntt_front10_kernel<false, TILED_LB, true>), grid, dim3(64u << TILED_LB), 0, s, a);
-            else
-                hipLaunchKernelGGL((ntt_front10_kernel<true, TILED_LB, true>), grid, dim3(64u << TILED_LB), 0, s, a);
-        } else if (io.round_scale)
-            hipLaunchKernelGGL((ntt_front10_kernel<false, LBN>), grid, dim3(64u << LBN), 0, s, a);
+        void (*k)(F10Args);
+        if (tiled_in)   // the tiled layout holds monomials: forward only
+            k = mode == 1 ? ntt_front10_kernel<false, TILED_LB, true, false> : ntt_front10_kernel<true, TILED_LB, true, false>;
         else
-            hipLaunchKernelGGL((ntt_front10_kernel<true, LBN>), grid, dim3(64u << LBN), 0, s, a);
+            k = mode == 1 ? ntt_front10_kernel<false, LBN, false, false> : mode == 2 ? ntt_front10_kernel<true, LBN, false, true> : ntt_front10_kernel<true, LBN, false, false>;
+        hipLaunchKernelGGL(k, grid, dim3(64u << (tiled_in ? TILED_LB : LBN)), 0, s, a);
     }
 }
 

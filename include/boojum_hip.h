@@ -173,7 +173,12 @@ enum { BJ_FIELD_ADD = 0, BJ_FIELD_SUB = 1, BJ_FIELD_MUL = 2, BJ_FIELD_MUL_LAZY =
        BJ_FIELD_INVERSE_CHAIN = 20, /* a^(p-2) by the addition chain of the per-point kernels, 0 -> 0; d_b unused */
        BJ_FIELD_EXT2_INVERSE = 21, BJ_FIELD_EXT2_INVERSE_CHAIN = 22, /* the F_p^2 inverse of (canon d_a[i], canon d_a[n+i]) on the square-and-
                                     * multiply / the addition-chain base inversion; out = [c0 | c1], (0, 0) -> (0, 0); d_b unused */
-       BJ_FIELD_BITREV = 23        /* the low b bits of (uint32_t)a reversed, b in 0..32 */ };
+       BJ_FIELD_BITREV = 23,       /* the low b bits of (uint32_t)a reversed, b in 0..32 */
+       /* 32: the butterflies of the NTT register steps that have no generic form */
+       BJ_FIELD_W16_BUTTERFLY = 32 /* the butterflies of the shift-only DFT-16, two per thread as the NTT kernels run them (n even): d_a = [u | v],
+                                    * (u, v) <- (u + v w, u - v w) on the raw words, w = omega_16^e a signed power of two, no product.  b = d_b[i]
+                                    * of the FIRST pair (i < n/2) names the exponents of pairs i and i + n/2: b & 15 = 0..7: (e, e) = (b, b);
+                                    * 8..11: (0, 4), (2, 6), (1, 5), (3, 7); b & 16: the inverse root */ };
 int bj_field_op_batch(bj_ctx *ctx, int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n);
 
 /* Host-memory convenience for single-polynomial plumbing (what a Rust `impl PrimeFieldLikeVectorized` would call);

@@ -141,6 +141,113 @@ def gen_addsub2():
     return lines, clobbers(B, B + 12)
 
 
+# ---- multiplication by a compile-time power of two, and the butterfly around it (the shift-only DFT-16 of ntt_r16.hip) ----
+P = 2**64 - 2**32 + 1
+ROOT_2_32 = 0x185629DCDA58878C        # radix_2_subgroup_generator (gl.h: omega)
+OMEGA16 = pow(ROOT_2_32, 1 << 28, P)  # gl::omega(4)
+OMEGA16_T = [t for t in range(16) if pow(2, 12 * t, P) == OMEGA16][0]   # omega_16 = 2^(12 t), t odd
+
+
+def w16_shift(e, inverse):
+    """omega_16^(+-e) = (-1)^neg * 2^S: (S, neg)"""
+    x = (12 * ((16 - OMEGA16_T) if inverse else OMEGA16_T) * e) % 192
+    return x % 96, x >= 96
+
+
+def shift_pairs():
+    """the (S_a, S_b) pairs a radix-16 step runs side by side: equal exponents in the first three rounds, the exponent pairs
+    (bitrev3(g), bitrev3(g + 1)) of the last one, forward and inverse; (0, 0) is addsub2"""
+    pairs = set()
+    for inverse in (False, True):
+        for e in range(8):
+            pairs.add((w16_shift(e, inverse)[0],) * 2)
+        for ea, eb in ((0, 4), (2, 6), (1, 5), (3, 7)):
+            pairs.add((w16_shift(ea, inverse)[0], w16_shift(eb, inverse)[0]))
+    pairs.discard((0, 0))
+    return sorted(pairs)
+
+
+def shift_chain(ch, S, v0, v1, base, ct, bq):
+    """X = v[base+2 : base+3] <- v * 2^S folded to 64 bits with 2^64 = 2^32 - 1, 2^96 = -1 (gl.h: mul_pow2_weak has the argument).
+    With k = S mod 32 the product has three 32-bit limbs a = v0 << k, b = (v >> (32 - k)) & (2^32 - 1), c = v1 >> (32 - k) < 2^k at
+    weights 2^S', 2^(S'+32), 2^(S'+64), S' = S - k.  Returns True when `ct` holds a carry the caller still owes: value = X + ct * 2^64."""
+    T, X, C, E = base, base + 2, base + 4, base + 5
+    k = S % 32
+    if S < 32:        # a + b 2^32 + c 2^64 = (b : a) + c EPS
+        ch.add("v_lshlrev_b32 v%d, %d, %s" % (T, k, v0))
+        ch.add("v_alignbit_b32 v%d, %s, %s, %d" % (T + 1, v1, v0, 32 - k))
+        ch.add("v_lshrrev_b32 v%d, %d, %s" % (C, 32 - k, v1))
+        ch.add("v_mad_u64_u32 %s, %s, v%d, -1, %s" % (pair(X), ct, C, pair(T)), defs=[ct])
+        return True
+    if S < 64:        # a 2^32 + b 2^64 + c 2^96 = (a : 0) + b EPS - c;  a borrow of the subtraction (X < c < 2^28) goes to the slow path
+        ch.add("v_mov_b32 v%d, 0" % T)
+        ch.add("v_lshlrev_b32 v%d, %d, %s" % (T + 1, k, v0))
+        ch.add("v_alignbit_b32 v%d, %s, %s, %d" % (E, v1, v0, 32 - k))
+        ch.add("v_lshrrev_b32 v%d, %d, %s" % (C, 32 - k, v1))
+        ch.add("v_mad_u64_u32 %s, %s, v%d, -1, %s" % (pair(X), ct, E, pair(T)), defs=[ct])
+        ch.add("v_sub_co_u32 v%d, %s, v%d, v%d" % (X, bq, X, C), defs=[bq])
+        ch.add("v_subb_co_u32 v%d, %s, v%d, 0, %s" % (X + 1, bq, X + 1, bq), defs=[bq], uses=[bq])
+        return True
+    # a 2^64 + b 2^96 + c 2^128 = a EPS - (c : b): no wrap in a EPS; where the difference borrows, D >= 2^64 - 2^52 and the
+    # value is D - 2^64 = D - EPS = D - 2^32 + 1 (mod p), exact: the high word cannot borrow, the sum cannot wrap
+    ch.add("v_lshlrev_b32 v%d, %d, %s" % (E, k, v0))
+    ch.add("v_alignbit_b32 v%d, %s, %s, %d" % (T, v1, v0, 32 - k))
+    ch.add("v_lshrrev_b32 v%d, %d, %s" % (T + 1, 32 - k, v1))
+    ch.add("v_mad_u64_u32 %s, vcc, v%d, -1, 0" % (pair(X), E))
+    ch.add("v_sub_co_u32 v%d, %s, v%d, v%d" % (X, bq, X, T), defs=[bq])
+    ch.add("v_subb_co_u32 v%d, %s, v%d, v%d, %s" % (X + 1, bq, X + 1, T + 1, bq), defs=[bq], uses=[bq])
+    ch.add("v_subb_co_u32 v%d, %s, v%d, 0, %s" % (X + 1, ct, X + 1, bq), defs=[ct], uses=[bq])     # - 2^32 where it borrowed (ct: no borrow out)
+    ch.add("v_addc_co_u32 v%d, %s, v%d, 0, %s" % (X, bq, X, bq), defs=[bq], uses=[bq])             # + 1 where it borrowed
+    ch.add("v_addc_co_u32 v%d, %s, v%d, 0, %s" % (X + 1, bq, X + 1, bq), defs=[bq], uses=[bq])
+    return False
+
+
+def addsub_carry_chain(ch, u0, u1, base, ct, out_s, out_d, sA, sB, sC, sD):
+    """out_s <- weak(u + t), out_d <- weak(u - t) for t = X + ct * 2^64 (X = v[base+2 : base+3]): the owed carry joins the wrap of the
+    sum and the borrow of the difference — (sA + ct) EPS is added, (sB + ct) EPS taken off — so it costs one instruction, not a
+    correction of its own; a wrap of either correction goes to sC / sD (slow path), as in addsub_chain."""
+    T, X, C, E, D = base, base + 2, base + 4, base + 5, base + 6
+    ch.add("v_cndmask_b32 v%d, 0, 1, %s" % (E, ct), uses=[ct])
+    ch.add("v_add_co_u32 v%d, %s, %s, v%d" % (T, sA, u0, X), defs=[sA])
+    ch.add("v_sub_co_u32 v%d, %s, %s, v%d" % (D, sB, u0, X), defs=[sB])
+    ch.add("v_addc_co_u32 v%d, %s, %s, v%d, %s" % (T + 1, sA, u1, X + 1, sA), defs=[sA], uses=[sA])
+    ch.add("v_subb_co_u32 v%d, %s, %s, v%d, %s" % (D + 1, sB, u1, X + 1, sB), defs=[sB], uses=[sB])
+    ch.add("v_addc_co_u32 v%d, vcc, v%d, 0, %s" % (C, E, sA), uses=[sA])
+    ch.add("v_addc_co_u32 v%d, vcc, v%d, 0, %s" % (X, E, sB), uses=[sB])
+    ch.add("v_mad_u64_u32 %s, %s, v%d, -1, %s" % (out_s, sC, C, pair(T)), defs=[sC])
+    ch.add("v_sub_co_u32 v%d, %s, v%d, v%d" % (D + 1, sD, D + 1, X), defs=[sD])
+    ch.add("v_mad_u64_u32 %s, vcc, v%d, 1, %s" % (out_d, X, pair(D)))
+
+
+def gen_shiftbf2(SA, SB):
+    B = TEMP_BASE
+    chains = []
+    rare = []
+    for k, (S, base) in enumerate(((SA, B), (SB, B + 8))):
+        ch = Chain("sb%d" % k)
+        sfx = "ab"[k]
+        o = lambda n: "%%[%s%s]" % (n, sfx)
+        if S == 0:
+            addsub_chain(ch, "%%[u%s0]" % sfx, "%%[u%s1]" % sfx, "%%[v%s0]" % sfx, "%%[v%s1]" % sfx, base, base + 2, base + 4, base + 5,
+                         o("s"), o("d"), o("p"), o("q"), o("c"), o("e"))
+        else:
+            owed = shift_chain(ch, S, "%%[v%s0]" % sfx, "%%[v%s1]" % sfx, base, o("t"), o("r"))
+            if owed:
+                addsub_carry_chain(ch, "%%[u%s0]" % sfx, "%%[u%s1]" % sfx, base, o("t"), o("s"), o("d"), o("p"), o("q"), o("c"), o("e"))
+            else:   # raw sum in T, raw difference in D, flags in C and X.lo (read by the first two instructions only)
+                addsub_chain(ch, "%%[u%s0]" % sfx, "%%[u%s1]" % sfx, "v%d" % (base + 2), "v%d" % (base + 3), base, base + 6, base + 4, base + 2,
+                             o("s"), o("d"), o("p"), o("q"), o("c"), o("e"))
+            if 32 < S < 64:
+                rare.append(o("r"))
+        chains.append(ch)
+    lines = interleave(chains)
+    # SALU: the masks written last are read last (as in gen_butterfly2)
+    for r in rare:
+        lines.append("s_or_b64 %%[ca], %%[ca], %s" % r)
+    lines += ["s_or_b64 %[ca], %[ca], %[cb]", "s_or_b64 %[ea], %[ea], %[eb]", "s_or_b64 %[ca], %[ca], %[ea]"]
+    return lines, clobbers(B, B + 16)
+
+
 HEADER = '''// GENERATED by tools/gen_gl_asm.py — do not edit.  Hand-scheduled gfx950 sequences for lazy Goldilocks arithmetic.
 // Values are "weak" residues: any u64 congruent to the field element.  Every function returns a wave-uniform mask of the
 // lanes (probability ~2^-32 per operation on random data) whose result the straight-line sequence did NOT finish: a
@@ -153,6 +260,22 @@ HEADER = '''// GENERATED by tools/gen_gl_asm.py — do not edit.  Hand-scheduled
 def main():
     b2, b2c = gen_butterfly2()
     a2, a2c = gen_addsub2()
+
+    sh = ""
+    for SA, SB in shift_pairs():
+        lines, clob = gen_shiftbf2(SA, SB)
+        sh += '''template <> __device__ __forceinline__ u64 shiftbf2_weak_asm<%d, %d>(u64 ua, u64 va, u64 ub, u64 vb, u64 &sa, u64 &da, u64 &sb, u64 &db) {
+    u64 ta, ra, pa, qa, ca, ea, tb, rb, pb, qb, cb, eb;
+    asm(
+%s
+        : [sa] "=&v"(sa), [da] "=&v"(da), [sb] "=&v"(sb), [db] "=&v"(db), [ta] "=&s"(ta), [ra] "=&s"(ra), [pa] "=&s"(pa), [qa] "=&s"(qa),
+          [ca] "=&s"(ca), [ea] "=&s"(ea), [tb] "=&s"(tb), [rb] "=&s"(rb), [pb] "=&s"(pb), [qb] "=&s"(qb), [cb] "=&s"(cb), [eb] "=&s"(eb)
+        : [ua0] "v"(lo32(ua)), [ua1] "v"(hi32(ua)), [va0] "v"(lo32(va)), [va1] "v"(hi32(va)),
+          [ub0] "v"(lo32(ub)), [ub1] "v"(hi32(ub)), [vb0] "v"(lo32(vb)), [vb1] "v"(hi32(vb))
+        : "vcc", "scc", %s);
+    return ca;
+}
+''' % (SA, SB, asm_block(lines), clob)
     src = HEADER % TEMP_BASE
     src += '''
 namespace gl {
@@ -181,9 +304,14 @@ __device__ __forceinline__ u64 addsub2_weak_asm(u64 ua, u64 va, u64 ub, u64 vb, 
         : "vcc", "scc", %s);
     return ra;
 }
-#endif
+// two butterflies by compile-time powers of two side by side:  (u, v) <- (u + v * 2^S, u - v * 2^S)  on weak residues, for the pairs
+// (SA, SB) the shift-only DFT-16 of ntt_r16.hip runs (S = 0: no product)
+template <int SA, int SB> __device__ __forceinline__ u64 shiftbf2_weak_asm(u64 ua, u64 va, u64 ub, u64 vb, u64 &sa, u64 &da, u64 &sb, u64 &db);
+%s#endif
+// gl::omega(4) = 2^(12 t): the 16th root of unity of the twiddle tables as a power of two (checked in gl.h)
+static constexpr int OMEGA16_LOG2_DIV12 = %d;
 }  // namespace gl
-''' % (asm_block(b2), b2c, asm_block(a2), a2c)
+''' % (asm_block(b2), b2c, asm_block(a2), a2c, sh, OMEGA16_T)
     old = open(OUT).read() if os.path.exists(OUT) else None
     if old != src:
         with open(OUT, "w") as f:
