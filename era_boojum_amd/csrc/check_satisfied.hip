@@ -120,8 +120,9 @@ int check_impl(bj_ctx *ctx, const bj_setup *S, const u64 *d_variables, const u64
     std::memset(out, 0, sizeof(*out));
     hipStream_t st = ctx->stream;
     const size_t n = (size_t)1 << S->log_n, B = CHECK_BLOCK;
-    const unsigned V = S->V, VW = V + S->Wc, nC = S->nC;
-    const u64 *d_consts = S->d_nat + (size_t)V * n, *d_tables = S->d_nat + (size_t)(V + nC) * n;
+    const bj::ProofLayout &PL = S->layout;
+    const unsigned VW = S->V + S->Wc, nC = S->nC;
+    const u64 *d_consts = S->d_nat + (size_t)PL.constant(0) * n;
 
     // terms in evaluator order: (gate, repetition, term), general-purpose gates first
     const unsigned n_gate_terms = S->gates.n_general_terms, n_spec_terms = S->gates.n_spec_terms, n_terms = n_gate_terms + n_spec_terms;
@@ -180,9 +181,9 @@ int check_impl(bj_ctx *ctx, const bj_setup *S, const u64 *d_variables, const u64
         BJ_HIP(ctx, hipMemsetAsync(d_lo, 0, n * 8, st));
         BJ_HIP(ctx, hipMemsetAsync(d_hi, 0, n * 4, st));
         LookupShape L;
-        L.tables = d_tables;
-        L.lvars = d_variables + (size_t)S->num_gp_vars * n;
-        L.table_id = S->tid_var ? nullptr : d_consts + (size_t)S->table_id_col * n;
+        L.tables = S->d_nat + (size_t)PL.table(0) * n;
+        L.lvars = d_variables + (size_t)PL.lookup_var(0, 0) * n;
+        L.table_id = S->tid_var ? nullptr : S->d_nat + (size_t)PL.table_id() * n;
         L.n = L.tstride = L.vstride = n;
         L.w = S->lookup_w;
         L.reps = S->lookup_reps;

@@ -106,9 +106,9 @@ int lookup_multiplicities(bj_ctx *ctx, const char *who, const u64 *d_lvars, size
 
 int setup_lookup_multiplicities(bj_ctx *ctx, const char *who, const bj_setup *S, const u64 *d_variables, u64 *d_out) {
     const size_t n = (size_t)1 << S->log_n;
-    const u64 *d_consts = S->d_nat + (size_t)S->V * n, *d_tables = S->d_nat + (size_t)(S->V + S->nC) * n;
-    return lookup_multiplicities(ctx, who, d_variables + (size_t)S->num_gp_vars * n, n, S->tid_var ? nullptr : d_consts + (size_t)S->table_id_col * n,
-                                 d_tables, n, S->lookup_reps, S->lookup_w, S->log_n, d_out);
+    const bj::ProofLayout &L = S->layout;
+    return lookup_multiplicities(ctx, who, d_variables + (size_t)L.lookup_var(0, 0) * n, n, S->tid_var ? nullptr : S->d_nat + (size_t)L.table_id() * n,
+                                 S->d_nat + (size_t)L.table(0) * n, n, S->lookup_reps, S->lookup_w, S->log_n, d_out);
 }
 
 }  // namespace bj

@@ -221,17 +221,18 @@ struct Proving {
     hipStream_t st;
     const u64 *d_variables, *d_multiplicities, *h_public_values;
     const HostWitness *hw;   // nullptr: the witness is resident (bj_prove_dev)
+    const bj::ProofLayout &L;   // proof_layout.h: the columns of every oracle, the opening order, the proof's words
     bool has_lookup;
     bool count_mult;         // no multiplicity column was supplied: round 1 counts it (count_multiplicities)
-    unsigned log_n, V, q, nC;
+    unsigned log_n, V, q;
     // N / Ln: leaves / column stride HELD BY THIS GPU (the whole domain on one GPU); Q: points of the quotient domain
     size_t n, N, Q, Ln, I0, capl;
     // quotient evaluation: the q n points are split evenly, rank r evaluates on the first Qe = q n / W points of ITS OWN range of
     // the LDE (they form the coset x_{I0} * H_Qe in bit-reversed order, whether Qe is several cosets of H_n, one, or a fraction
     // of one), inverse-transforms them to T mod (x^Qe - x_{I0}^Qe), and the residues are all-gathered and combined (round 3)
     size_t Qe;            // points this rank evaluates
-    unsigned VW;          // variables, then the non-copiable witness columns (prover.rs:317-343)
-    unsigned nW, n_chunks, n_part, nS2, nT;
+    unsigned VW;          // variables, then the non-copiable witness columns (prover.rs:317-343): the columns in front of the multiplicities
+    unsigned nW, nS2;     // leaf widths of the witness and the stage-2 oracle
     bj_proof *proof = nullptr;
     bj::host::Transcript tr;
     u64 beta[2], gamma[2], lbeta[2] = {0, 0}, lgamma[2] = {0, 0}, z[2], zo[2];   // challenges of rounds 2 and 4 (zo = z * omega)
@@ -249,17 +250,14 @@ struct Proving {
     u64 pow_challenge = 0;
 
     Proving(bj_ctx *c, const bj_setup *s, const u64 *d_vars, const u64 *d_mult, const u64 *h_pub, const HostWitness *h, bool count)
-        : ctx(c), S(s), sh(s->sh), st(c->stream), d_variables(d_vars), d_multiplicities(d_mult), h_public_values(h_pub), hw(h) {
-        has_lookup = S->lookup_reps > 0;
+        : ctx(c), S(s), sh(s->sh), st(c->stream), d_variables(d_vars), d_multiplicities(d_mult), h_public_values(h_pub), hw(h), L(s->layout) {
+        has_lookup = L.has_lookup;
         count_mult = has_lookup && count;
-        log_n = S->log_n, V = S->V, q = S->q, nC = S->nC;
+        log_n = S->log_n, V = S->V, q = S->q;
         n = (size_t)1 << log_n, N = S->Nl, Q = n * q, Ln = S->Ls, I0 = (size_t)S->c0 * n, capl = S->cap_l;
         Qe = Q / sh.world;
-        VW = V + S->Wc;
-        nW = VW + (has_lookup ? 1 : 0);
-        n_chunks = (V + q - 1) / q, n_part = n_chunks - 1;
-        nS2 = 2 * (1 + n_part) + (has_lookup ? 2 * (S->lookup_reps + 1) : 0);
-        nT = has_lookup ? S->lookup_w + 1 : 0;
+        VW = L.multiplicity();
+        nW = L.widths[bj::ORACLE_WITNESS], nS2 = L.widths[bj::ORACLE_STAGE2];
     }
     int reserve_workspace();
     int check_public_inputs();
@@ -272,6 +270,8 @@ struct Proving {
     int exchange_residues(u64 *Tl);
     int round4_openings();
     void list_opened_columns();
+    Src lde_src(const bj::Opened &o) const;
+    Src mono_src(const bj::Opened &o) const;
     int evaluate_at(u64 *w, u64 open_shift, const std::vector<Src> &ss, const u64 *at, std::vector<u64> &vals);
     int round5a_deep();
     int deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector<Src> &ms, const u64 *vals, const u64 *at);
@@ -280,7 +280,7 @@ struct Proving {
     int round6_queries(Queries &qr);
     int gather_base_queries(Queries &qr);
     int gather_fri_queries(Queries &qr);
-    void serialise(const Queries &qr);
+    int serialise(const Queries &qr);
     void read_back_stats();
 
     size_t tree_elems() const { return bj_merkle_tree_digests(N, capl) * 4; }   // words of a tree over this GPU's leaves
@@ -314,7 +314,7 @@ int Proving::reserve_workspace() {
     // sizes mirror the allocations; +1 MiB slack per buffer for alignment
     const size_t tree_elems = this->tree_elems(), slack = (size_t)1 << 17;
     size_t need = (size_t)nW * Ln + (size_t)(nW + nS2) * n + tree_elems                        // wit_lde, monomials, wit_tree
-                + (size_t)nS2 * n + ((size_t)2 * n_chunks * n + 2 * ((n + 1023) / 1024) + 16)   // s2_nat, tmp
+                + (size_t)nS2 * n + ((size_t)2 * L.n_chunks * n + 2 * ((n + 1023) / 1024) + 16)   // s2_nat, tmp
                 + (size_t)nS2 * Ln + tree_elems                                                // s2_lde, s2_tree
                 + 2 * Q + (sh.world > 1 ? 2 * Ln * (sh.world + 1) : 0) + (size_t)2 * q * N + tree_elems + 4 * n + 4 * N                       // T (+ gather staging), q_lde, q_tree, w, deep
                 + (size_t)4096 * 1024 * (sh.world > 1 ? 1 + sh.world : 1) + 64 * slack        // alphas, query gathers
@@ -407,7 +407,7 @@ int Proving::witness_from_host(bool *hashed_in_groups) {
         BJ_HIP(ctx, hipStreamWaitEvent(st, ctx->copy_ev[g], 0));
         if (count_mult && c1 == nW && (rc = count_multiplicities())) break;   // the last group: every lookup column has landed
         if (c0 < v1) rc = intt_cols(d_variables + (size_t)c0 * n, mono.p + (size_t)c0 * n, v1 - c0);
-        if (!rc && has_lookup && c1 == nW) rc = intt_cols(d_multiplicities, mono.p + (size_t)VW * n, 1);
+        if (!rc && has_lookup && c1 == nW) rc = intt_cols(d_multiplicities, mono.p + (size_t)L.multiplicity() * n, 1);
         if (!rc) rc = lde_cols(mono.p + (size_t)c0 * n, wit_lde.p + (size_t)c0 * Ln, Ln, c1 - c0, S->log_L, S->c0, S->cl);
         if (absorb && !rc && plan[g].absorb_from != bj::NO_ABSORB) {
             const unsigned a0 = plan[g].absorb_from;
@@ -444,7 +444,7 @@ int Proving::round1_witness() {
     if ((rc = mono_s2.alloc(ctx, (size_t)nS2 * n))) return rc;
     if (!hw) {
         rc = intt_cols(d_variables, mono.p, VW);
-        if (!rc && has_lookup) rc = intt_cols(d_multiplicities, mono.p + (size_t)VW * n, 1);
+        if (!rc && has_lookup) rc = intt_cols(d_multiplicities, mono.p + (size_t)L.multiplicity() * n, 1);
         if (!rc) rc = lde_cols(mono.p, wit_lde.p, Ln, nW, S->log_L, S->c0, S->cl);
     } else {
         rc = witness_from_host(&hashed_in_groups);
@@ -477,16 +477,15 @@ int Proving::round2_stage2() {
     challenge2(gamma);
     ArenaBuf s2_nat, tmp;
     if ((rc = s2_nat.alloc(ctx, (size_t)nS2 * n))) return rc;
-    if ((rc = tmp.alloc(ctx, (size_t)2 * n_chunks * n + 2 * ((n + 1023) / 1024) + 16))) return rc;
-    const u64 *d_sig_nat = S->d_nat, *d_con_nat = S->d_nat + (size_t)V * n, *d_tab_nat = S->d_nat + (size_t)(V + nC) * n;
-    bj::launch_copy_perm_stage2(d_variables, n, d_sig_nat, n, S->d_non_res, V, q, log_n, ctx->tw_fwd, beta, gamma, tmp.p,
-                                s2_nat.p, s2_nat.p + 2 * n, st, S->small_non_residues);
+    if ((rc = tmp.alloc(ctx, (size_t)2 * L.n_chunks * n + 2 * ((n + 1023) / 1024) + 16))) return rc;
+    bj::launch_copy_perm_stage2(d_variables, n, S->d_nat + (size_t)L.sigma(0) * n, n, S->d_non_res, V, q, log_n, ctx->tw_fwd, beta, gamma, tmp.p,
+                                s2_nat.p + (size_t)L.z() * n, s2_nat.p + (size_t)L.partial(0) * n, st, S->small_non_residues);
     if (has_lookup) {
         challenge2(lbeta);
         challenge2(lgamma);
-        u64 *dA = s2_nat.p + (size_t)(2 + 2 * n_part) * n, *dB = dA + (size_t)2 * S->lookup_reps * n;
-        bj::launch_lookup_polys(d_variables + (size_t)S->num_gp_vars * n, n, S->tid_var ? nullptr : d_con_nat + (size_t)S->table_id_col * n, d_tab_nat,
-                                n, d_multiplicities, S->lookup_reps, S->lookup_w, log_n, lbeta, lgamma, dA, dB, st);
+        u64 *dA = s2_nat.p + (size_t)L.lookup_a(0) * n, *dB = s2_nat.p + (size_t)L.lookup_b() * n;
+        bj::launch_lookup_polys(d_variables + (size_t)L.lookup_var(0, 0) * n, n, S->tid_var ? nullptr : S->d_nat + (size_t)L.table_id() * n,
+                                S->d_nat + (size_t)L.table(0) * n, n, d_multiplicities, S->lookup_reps, S->lookup_w, log_n, lbeta, lgamma, dA, dB, st);
     }
     BJ_CHECK_LAUNCH(ctx);
     if ((rc = s2_lde.alloc(ctx, (size_t)nS2 * Ln))) return rc;
@@ -533,9 +532,9 @@ int Proving::round3_quotient() {
     int rc = BJ_OK;
     u64 alpha[2];
     challenge2(alpha);
-    const unsigned n_lookup_terms = has_lookup ? S->lookup_reps + 1 : 0;
+    const unsigned n_lookup_terms = L.n_lookup_terms;
     const unsigned n_gate_terms = S->gates.n_general_terms, n_spec_terms = S->gates.n_spec_terms;   // lookup | specialized | general | L1 | copy-permutation (prover.rs:599-625)
-    const unsigned total_terms = n_lookup_terms + n_spec_terms + n_gate_terms + 1 + n_chunks;
+    const unsigned total_terms = n_lookup_terms + n_spec_terms + n_gate_terms + 1 + L.n_chunks;
     const std::vector<u64> alphas = e2_powers(alpha, total_terms);
     ArenaBuf d_alphas;
     if ((rc = d_alphas.alloc(ctx, alphas.size()))) return rc;
@@ -548,19 +547,19 @@ int Proving::round3_quotient() {
     u64 *t0 = Tl.p, *t1 = Tl.p + Qe;
     const u64 *a_lookup = d_alphas.p, *a_spec = d_alphas.p + 2 * n_lookup_terms, *a_gates = a_spec + 2 * n_spec_terms,
               *a_l1 = a_gates + 2 * n_gate_terms;
-    const u64 *d_sig_lde = S->d_lde, *d_con_lde = S->d_lde + (size_t)V * Ln, *d_tab_lde = S->d_lde + (size_t)(V + nC) * Ln;
+    const u64 *d_sig_lde = S->d_lde + (size_t)L.sigma(0) * Ln, *d_con_lde = S->d_lde + (size_t)L.constant(0) * Ln;
     if (Qe)
         bj::launch_circuit_gates(ctx, S, wit_lde.p, Ln, d_con_lde, Ln, Qe, a_gates, a_spec, t0, t1, st,
                                  bj::GATES_GENERAL | bj::GATES_SPECIALIZED);
     if (has_lookup && Qe) {
-        const u64 *dA = s2_lde.p + (size_t)(2 + 2 * n_part) * Ln, *dB = dA + (size_t)2 * S->lookup_reps * Ln;
-        bj::launch_quotient_lookup(wit_lde.p + (size_t)S->num_gp_vars * Ln, Ln, S->tid_var ? nullptr : d_con_lde + (size_t)S->table_id_col * Ln, d_tab_lde,
-                                   Ln, wit_lde.p + (size_t)VW * Ln, dA, dB, Ln, S->lookup_reps, S->lookup_w, lbeta, lgamma,
+        const u64 *dA = s2_lde.p + (size_t)L.lookup_a(0) * Ln, *dB = s2_lde.p + (size_t)L.lookup_b() * Ln;
+        bj::launch_quotient_lookup(wit_lde.p + (size_t)L.lookup_var(0, 0) * Ln, Ln, S->tid_var ? nullptr : S->d_lde + (size_t)L.table_id() * Ln,
+                                   S->d_lde + (size_t)L.table(0) * Ln, Ln, wit_lde.p + (size_t)L.multiplicity() * Ln, dA, dB, Ln, S->lookup_reps, S->lookup_w, lbeta, lgamma,
                                    a_lookup, Qe, t0, t1, st);
     }
     if (Qe) {
         // variables + sigmas + z and the partial products + 1/(x - 1), accumulators read and written
-        const int pc = bj::probe_begin(ctx, "quotient_copy_perm", 8.0 * (2.0 * V + 2 + 2 * n_part + 1) * (double)Qe + 32.0 * (double)Qe);
+        const int pc = bj::probe_begin(ctx, "quotient_copy_perm", 8.0 * (2.0 * V + 2 * (1 + L.n_partials) + 1) * (double)Qe + 32.0 * (double)Qe);
         bj::launch_quotient_copy_perm(wit_lde.p, Ln, d_sig_lde, Ln, s2_lde.p, Ln, S->d_non_res, V, q, log_n, S->log_L, ctx->tw_fwd,
                                       beta, gamma, alphas.data() + 2 * (n_lookup_terms + n_spec_terms + n_gate_terms), a_l1 + 2, Qe, I0, S->d_inv_xm1, t0, t1, st,
                                       S->small_non_residues);
@@ -601,37 +600,28 @@ int Proving::round3_quotient() {
     return BJ_OK;
 }
 
+// An opened polynomial of the layout as its columns in the LDE arrays / in the monomial arrays (chunk j of the quotient:
+// coefficients [j*n, (j+1)*n) of T's two monomial forms, which lie Q apart instead of side by side).
+Src Proving::lde_src(const bj::Opened &o) const {
+    const u64 *bases[4] = {wit_lde.p, s2_lde.p, q_lde.p, S->d_lde};
+    const size_t strides[4] = {Ln, Ln, N, Ln};
+    const u64 *b = bases[o.oracle];
+    return {b + o.col0 * strides[o.oracle], o.col1 == bj::NO_COLUMN ? nullptr : b + o.col1 * strides[o.oracle]};
+}
+Src Proving::mono_src(const bj::Opened &o) const {
+    if (o.oracle == bj::ORACLE_QUOTIENT) return {Tm + (size_t)(o.col0 / 2) * n, Tm + Q + (size_t)(o.col0 / 2) * n};
+    const u64 *bases[4] = {mono.p, mono_s2.p, nullptr, S->d_mono};
+    const u64 *b = bases[o.oracle];
+    return {b + (size_t)o.col0 * n, o.col1 == bj::NO_COLUMN ? nullptr : b + (size_t)o.col1 * n};
+}
+
 // Reads wit_lde, mono, s2_lde, mono_s2, q_lde, Tm and the setup's LDE and monomials.  Adds srcs / msrcs and the two small sets
 // opened elsewhere than at z: zsrc / mz and (with lookups) lsrc / ml.  F_p^2 polys contribute two columns.
 void Proving::list_opened_columns() {
-    const u64 *d_sig_lde = S->d_lde, *d_con_lde = S->d_lde + (size_t)V * Ln, *d_tab_lde = S->d_lde + (size_t)(V + nC) * Ln;
-    const u64 *m_sig = S->d_mono, *m_con = S->d_mono + (size_t)V * n, *m_tab = S->d_mono + (size_t)(V + nC) * n;
-    for (unsigned i = 0; i < VW; i++) srcs.push_back({wit_lde.p + (size_t)i * Ln, nullptr}), msrcs.push_back({mono.p + (size_t)i * n, nullptr});   // variables, witness
-    for (unsigned i = 0; i < nC; i++) srcs.push_back({d_con_lde + (size_t)i * Ln, nullptr}), msrcs.push_back({m_con + (size_t)i * n, nullptr});
-    for (unsigned i = 0; i < V; i++) srcs.push_back({d_sig_lde + (size_t)i * Ln, nullptr}), msrcs.push_back({m_sig + (size_t)i * n, nullptr});
-    for (unsigned j = 0; j < 1 + n_part; j++) {
-        srcs.push_back({s2_lde.p + (size_t)(2 * j) * Ln, s2_lde.p + (size_t)(2 * j + 1) * Ln});
-        msrcs.push_back({mono_s2.p + (size_t)(2 * j) * n, mono_s2.p + (size_t)(2 * j + 1) * n});
-    }
-    if (has_lookup) {
-        srcs.push_back({wit_lde.p + (size_t)VW * Ln, nullptr});
-        msrcs.push_back({mono.p + (size_t)VW * n, nullptr});
-        for (unsigned i = 0; i < S->lookup_reps + 1; i++) {
-            size_t o = (size_t)(2 + 2 * n_part + 2 * i);
-            srcs.push_back({s2_lde.p + o * Ln, s2_lde.p + (o + 1) * Ln});
-            msrcs.push_back({mono_s2.p + o * n, mono_s2.p + (o + 1) * n});
-        }
-        for (unsigned i = 0; i < nT; i++) srcs.push_back({d_tab_lde + (size_t)i * Ln, nullptr}), msrcs.push_back({m_tab + (size_t)i * n, nullptr});
-    }
-    for (unsigned j = 0; j < q; j++) {   // chunk j of the quotient: coefficients [j*n, (j+1)*n) of T's monomial form
-        srcs.push_back({q_lde.p + (size_t)(2 * j) * N, q_lde.p + (size_t)(2 * j + 1) * N});
-        msrcs.push_back({Tm + (size_t)j * n, Tm + Q + (size_t)j * n});
-    }
-    const size_t iz = VW + nC + V, il = iz + 1 + n_part + 1;   // z(x); the first lookup sum
-    zsrc = {srcs[iz]};
-    mz = {msrcs[iz]};
-    if (has_lookup)
-        for (unsigned i = 0; i < S->lookup_reps + 1; i++) lsrc.push_back(srcs[il + i]), ml.push_back(msrcs[il + i]);
+    for (const bj::Opened &o : L.opened) srcs.push_back(lde_src(o)), msrcs.push_back(mono_src(o));
+    zsrc = {srcs[L.at_z]};
+    mz = {msrcs[L.at_z]};
+    for (unsigned i = 0; i < L.n_lookup_terms; i++) lsrc.push_back(srcs[L.at_a + i]), ml.push_back(msrcs[L.at_a + i]);   // the A_i, then B
 }
 
 // The polynomials `ss` at the point `at`, by barycentric evaluation on this GPU's first coset (shift open_shift); w: 2 n words
@@ -814,46 +804,34 @@ int Proving::deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector
 // codeword FRI folds.
 int Proving::round5a_deep() {
     int rc = BJ_OK;
-    struct PubSet { u64 at; std::vector<unsigned> cols; std::vector<u64> vals; };
-    std::vector<PubSet> pubs;
-    {
-        u64 om = gl::omega(log_n);
-        for (size_t i = 0; i < S->pub_cols.size(); i++) {
-            u64 at = gl::pow(om, S->pub_rows[i]);
-            size_t pos = 0;
-            for (; pos < pubs.size(); pos++)
-                if (pubs[pos].at == at) break;
-            if (pos == pubs.size()) pubs.push_back({at, {}, {}});
-            pubs[pos].cols.push_back(S->pub_cols[i]);
-            pubs[pos].vals.push_back(gl::canon(h_public_values[i]));
-        }
-    }
+    const std::vector<bj::OpeningSet> sets = L.opening_sets(S->pub_cols.data(), S->pub_rows.data(), S->pub_cols.size());
     u64 cch[2];
     challenge2(cch);
-    size_t total_ch = srcs.size() + 1 + lsrc.size();
-    for (auto &p : pubs) total_ch += p.cols.size();
+    size_t total_ch = 0;
+    for (auto &set : sets) total_ch += set.polys.size();
     DeepSets D;
     D.chs = e2_powers(cch, total_ch);
     if ((rc = deep.alloc(ctx, 2 * N))) return rc;
     if ((rc = D.num_mono.alloc(ctx, 2 * n))) return rc;
     if (sh.world > 1 && (rc = D.num_slice.alloc(ctx, 2 * n / sh.world + 16))) return rc;
-    if ((rc = deep_set(D, srcs, msrcs, vz.data(), z))) return rc;
-    if ((rc = deep_set(D, zsrc, mz, vzo.data(), zo))) return rc;   // z(x) at z*omega
-    if (has_lookup) {
-        u64 zero2[2] = {0, 0};
-        if ((rc = deep_set(D, lsrc, ml, v0.data(), zero2))) return rc;
-    }
-    for (auto &p : pubs) {
-        std::vector<Src> ps, pl;
-        std::vector<u64> pv;
-        for (size_t i = 0; i < p.cols.size(); i++) {
-            pl.push_back({wit_lde.p + (size_t)p.cols[i] * Ln, nullptr});
-            ps.push_back({mono.p + (size_t)p.cols[i] * n, nullptr});
-            pv.push_back(p.vals[i]);
-            pv.push_back(0);
+    const u64 zero2[2] = {0, 0};
+    for (auto &set : sets) {   // in the order the challenges are handed out
+        if (set.point == bj::OPEN_AT_Z) rc = deep_set(D, srcs, msrcs, vz.data(), z);
+        else if (set.point == bj::OPEN_AT_Z_OMEGA) rc = deep_set(D, zsrc, mz, vzo.data(), zo);
+        else if (set.point == bj::OPEN_AT_ZERO) rc = deep_set(D, lsrc, ml, v0.data(), zero2);
+        else {
+            std::vector<Src> ps, pl;
+            std::vector<u64> pv;
+            for (size_t i = 0; i < set.polys.size(); i++) {
+                pl.push_back(lde_src(set.polys[i]));
+                ps.push_back(mono_src(set.polys[i]));
+                pv.push_back(gl::canon(h_public_values[set.value[i]]));
+                pv.push_back(0);
+            }
+            const u64 at2[2] = {gl::pow(gl::omega(log_n), set.row), 0};
+            rc = deep_set(D, pl, ps, pv.data(), at2);
         }
-        u64 at2[2] = {p.at, 0};
-        if ((rc = deep_set(D, pl, ps, pv.data(), at2))) return rc;
+        if (rc) return rc;
     }
     return flush_deep(D);
 }
@@ -896,7 +874,7 @@ int Proving::round5b_fri() {
 // What round 6 hands to the serialiser
 struct Queries {
     std::vector<u64> idxs;               // the queried leaves of the whole LDE domain
-    unsigned depth = 0, widths[4] = {};   // the base oracles (witness, stage 2, quotient, setup): path length, leaf widths
+    unsigned depth = 0;                  // path length of the base oracles (witness, stage 2, quotient, setup)
     size_t block = 0;                    // words one rank gathered for the base oracles
     std::vector<u64> gathered;           // [rank][block]; query qi reads the block of rank idxs[qi] / N
     std::vector<std::vector<u64>> fri_leaves, fri_paths;   // per FRI oracle
@@ -904,18 +882,18 @@ struct Queries {
 };
 
 // Round 6, the base oracles: leaves and Merkle paths of the witness, stage-2, quotient and setup trees.
-// Reads qr.idxs, qr.depth, the four LDEs and trees; adds qr.widths, qr.block, qr.gathered.
+// Reads qr.idxs, qr.depth, the four LDEs and trees; adds qr.block, qr.gathered.
 int Proving::gather_base_queries(Queries &qr) {
     const unsigned W = sh.world, depth = qr.depth;
     // a leaf lives on rank index / N; every rank gathers at (index mod N) and the owner's answer is kept
-    const unsigned widths[4] = {nW, nS2, 2 * q, S->n_cols};
+    const unsigned *widths = L.widths;
     const u64 *bases[4] = {wit_lde.p, s2_lde.p, q_lde.p, S->d_lde};
     const size_t strides[4] = {Ln, Ln, N, Ln};
     const u64 *trees[4] = {wit_tree.p, s2_tree.p, q_tree.p, S->d_tree};
     int rc = BJ_OK;
     ArenaBuf d_idx, d_g;
     size_t per_query = 0;
-    for (int o = 0; o < 4; o++) per_query += (qr.widths[o] = widths[o]) + (size_t)depth * 4;
+    for (int o = 0; o < 4; o++) per_query += widths[o] + (size_t)depth * 4;
     const size_t G = qr.block = per_query * num_queries;
     if ((rc = d_idx.alloc(ctx, num_queries))) return rc;
     if ((rc = d_g.alloc(ctx, G))) return rc;
@@ -1010,49 +988,54 @@ int Proving::round6_queries(Queries &qr) {
 }
 
 // ---------------- serialise ----------------
-// Reads the caps, the opened values, the FRI object and the query answers; fills proof->data (layout: proof_format.py).
-void Proving::serialise(const Queries &qr) {
-    const size_t cap = S->cap_size;
-    const unsigned depth = qr.depth;
+// Reads the caps, the opened values, the FRI object and the query answers; fills proof->data (word order: proof_layout.h; parsed by proof_format.py).
+int Proving::serialise(const Queries &qr) {
+    const size_t cap = S->cap_size, n_pub = S->pub_cols.size();
+    const bj::SerialLayout SL = bj::serial_layout(L, sched, sched_len, final_degree, num_queries, n_pub);
+    if (!SL.ok) return bj::fail(ctx, BJ_ERR_HIP, "bj_prove: internal error: the proof's own schedule has no serialised layout");
+    const size_t depth4 = (size_t)SL.depth * 4;
     std::vector<u64> &D = proof->data;
-    auto put = [&](const u64 *p, size_t k) { D.insert(D.end(), p, p + k); };
-    const u64 header[] = {0x424A5046ULL, 2, S->pub_cols.size(), cap, vz.size() / 2, vzo.size() / 2, v0.size() / 2, sched_len,
-                          final_degree, num_queries, nW, nS2, 2 * q, S->n_cols, depth, log_n, S->fri_lde, S->pow_bits, pow_challenge};
-    put(header, sizeof(header) / 8);
-    for (size_t i = 0; i < sched_len; i++) D.push_back(sched[i]);
-    for (size_t i = 0; i < S->pub_cols.size(); i++) D.push_back(gl::canon(h_public_values[i]));
-    put(wit_cap.data(), wit_cap.size());
-    put(s2_cap.data(), s2_cap.size());
-    put(q_cap.data(), q_cap.size());
-    put(vz.data(), vz.size());
-    put(vzo.data(), vzo.size());
-    put(v0.data(), v0.size());
+    D.assign(SL.total, 0);
+    auto put = [&](size_t at, const u64 *p, size_t k) { std::copy(p, p + k, D.begin() + at); };
+    bj::ProofHeader header;
+    header.fill(L, n_pub, sched_len, final_degree, num_queries, SL.depth, S->pow_bits, pow_challenge);
+    put(SL.header, header.w, bj::ProofHeader::WORDS);
+    for (size_t i = 0; i < sched_len; i++) D[SL.schedule + i] = sched[i];
+    for (size_t i = 0; i < n_pub; i++) D[SL.public_inputs + i] = gl::canon(h_public_values[i]);
+    put(SL.witness_cap, wit_cap.data(), wit_cap.size());
+    put(SL.stage2_cap, s2_cap.data(), s2_cap.size());
+    put(SL.quotient_cap, q_cap.data(), q_cap.size());
+    put(SL.values_at_z, vz.data(), vz.size());
+    put(SL.values_at_z_omega, vzo.data(), vzo.size());
+    put(SL.values_at_0, v0.data(), v0.size());
     {
         std::vector<u64> c(4 * cap);
         for (size_t i = 0; i < sched_len; i++) {
             bj_fri_cap(fri, i, c.data());
-            put(c.data(), c.size());
+            put(SL.fri_caps + i * c.size(), c.data(), c.size());
         }
         std::vector<u64> f0(final_degree), f1(final_degree);
         bj_fri_final_monomials(fri, f0.data(), f1.data());
-        put(f0.data(), final_degree);
-        put(f1.data(), final_degree);
+        put(SL.final_c0, f0.data(), final_degree);
+        put(SL.final_c1, f1.data(), final_degree);
     }
     for (size_t qi = 0; qi < num_queries; qi++) {
-        D.push_back(qr.idxs[qi]);
-        size_t off = (qr.idxs[qi] / N) * qr.block;
+        const size_t at = SL.queries + qi * SL.query_words;
+        D[at] = qr.idxs[qi];
+        size_t off = (qr.idxs[qi] / N) * qr.block;   // the block of the rank that owns the leaf: per oracle [leaves][paths]
         for (int o = 0; o < 4; o++) {
-            put(qr.gathered.data() + off + qi * qr.widths[o], qr.widths[o]);
-            off += (size_t)qr.widths[o] * num_queries;
-            put(qr.gathered.data() + off + qi * (size_t)depth * 4, (size_t)depth * 4);
-            off += (size_t)depth * 4 * num_queries;
+            put(at + SL.leaf_off[o], qr.gathered.data() + off + qi * L.widths[o], L.widths[o]);
+            off += (size_t)L.widths[o] * num_queries;
+            put(at + SL.path_off[o], qr.gathered.data() + off + qi * depth4, depth4);
+            off += depth4 * num_queries;
         }
         for (size_t i = 0; i < sched_len; i++) {
             const size_t E2 = (size_t)2 << sched[i];
-            put(qr.fri_leaves[i].data() + qi * E2, E2);
-            put(qr.fri_paths[i].data() + qi * (size_t)qr.fri_depth[i] * 4, (size_t)qr.fri_depth[i] * 4);
+            put(at + SL.fri_leaf_off[i], qr.fri_leaves[i].data() + qi * E2, E2);
+            put(at + SL.fri_path_off[i], qr.fri_paths[i].data() + qi * (size_t)SL.fri_depth[i] * 4, (size_t)SL.fri_depth[i] * 4);
         }
     }
+    return BJ_OK;
 }
 
 // The proof has drained (its bytes are on the host): the collectives' event pairs and the kernel probes can be read.
@@ -1148,7 +1131,7 @@ int prove_impl(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, cons
     stage_ms[5] = timer.lap();
     Queries qr;
     if ((rc = P.round6_queries(qr))) return rc;
-    P.serialise(qr);
+    if ((rc = P.serialise(qr))) return rc;
     stage_ms[6] = timer.lap();
     P.read_back_stats();
     guard.ok = true;
@@ -1161,7 +1144,7 @@ int prove_impl(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, cons
 extern "C" {
 
 static int stage_witness(bj_ctx *ctx, const bj_setup *S) {
-    const size_t n = (size_t)1 << S->log_n, need = (size_t)(S->V + S->Wc + 1) * n;
+    const size_t n = (size_t)1 << S->log_n, need = (size_t)(S->layout.multiplicity() + 1) * n;   // the multiplicity column behind the others
     if (ctx->wit_stage_elems < need) {   // device staging of the witness, kept for the next proof (no 3 GB hipMalloc per proof)
         if (ctx->wit_stage) BJ_HIP(ctx, hipFree(ctx->wit_stage));
         ctx->wit_stage = nullptr;
@@ -1186,7 +1169,7 @@ int bj_prove(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_variables, const 
     const unsigned group = bj::env().prove_h2d_group;
     const HostWitness hw{h_variables, h_multiplicities, group, false};
     // the copies are queued inside the proof (after the workspace is reserved); a previous proof on this context has drained
-    return prove_impl(ctx, S, ctx->wit_stage, ctx->wit_stage + (size_t)(S->V + S->Wc) * n, h_public_values, out, &hw, h_multiplicities == nullptr);
+    return prove_impl(ctx, S, ctx->wit_stage, ctx->wit_stage + (size_t)S->layout.multiplicity() * n, h_public_values, out, &hw, h_multiplicities == nullptr);
 }
 
 }  // extern "C"
@@ -1200,7 +1183,7 @@ int prove_host_copy_first(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_vari
     if (int rc = bind(ctx)) return rc;
     if (!S || !h_variables || !out) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove: null argument");
     if (int rc = stage_witness(ctx, S)) return rc;
-    const size_t n = (size_t)1 << S->log_n, vw = (size_t)(S->V + S->Wc) * n;
+    const size_t n = (size_t)1 << S->log_n, vw = (size_t)S->layout.multiplicity() * n;
     if (mode == 2) {   // transfer and transform in groups as bj_prove does, but ONE leaf kernel at the end: the sibling lane's kernels
                        // cover the transfer, so nothing is gained by absorbing group by group (extra launches, capacity round trips)
         const HostWitness hw{h_variables, h_multiplicities, env().prove_h2d_group, true};

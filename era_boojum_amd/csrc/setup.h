@@ -1,40 +1,37 @@
 // Internal: the setup object behind the opaque `bj_setup` of include/boojum_hip.h, shared by setup.hip (which creates it),
 // prover.hip (which proves with it), check_satisfied.hip (which only reads the replicated natural-order columns and the gate list)
-// and verifier.hip (bj_vk_from_setup copies the gate list and the packed op lists).
+// and verifier.hip (bj_vk_from_setup copies the shape, the gate list and the packed op lists).  The circuit's shape and every
+// column position are proof_layout.h's: that header is the definition of what an oracle holds and of a proof's word order.
 #pragma once
 #include "ctx.h"
 #include "fri_types.h"
 #include "gate_program.h"
+#include "proof_layout.h"
 
 #include <vector>
 
-struct bj_setup {
+struct bj_setup : bj::CircuitShape {   // proof_layout.h: bj::circuit_shape fills the base
     int device = 0;
-    // circuit
-    unsigned log_n = 0, V = 0, num_gp_vars = 0, nC = 0, lookup_w = 0, lookup_reps = 0, table_id_col = 0, q = 0;
-    unsigned Wc = 0;               // non-copiable witness columns (behind the V variable columns in the witness oracle)
-    bool tid_var = false;          // UseSpecializedColumnsWithTableIdAsVariable: the table id is the last of lookup_cps = lookup_w + 1
-    unsigned lookup_cps = 0;       // variable columns of a sub-argument (specialized_columns_per_subargument, cs/mod.rs:300-312)
+    bj::ProofLayout layout;        // of this shape: column positions, leaf widths, opening order
     bj::GateList gates;            // as bj::resolve_gates (gate_list.h) made it from the circuit's description
     std::vector<bj::DevProgram> programs, spec_programs;   // beside gates.general / gates.spec; empty (block == nullptr) unless kind == BJ_GATE_PROGRAM
     std::vector<gl::u64> non_residues;
     bool small_non_residues = false;   // every k_c < 2^32 (canonical): quotient_copy_perm multiplies by them as 32-bit integers
     std::vector<unsigned> pub_cols, pub_rows;
     // proof config
-    unsigned fri_lde = 0, cap_size = 0, security = 0, pow_bits = 0, transcript = BJ_TRANSCRIPT_POSEIDON2, hasher = BJ_HASHER_POSEIDON2;
+    unsigned fri_lde = 0, security = 0, pow_bits = 0, transcript = BJ_TRANSCRIPT_POSEIDON2, hasher = BJ_HASHER_POSEIDON2;
     unsigned pow_runner = BJ_POW_BLAKE2S256;   // the POW type parameter of prove_cpu_basic (pow.rs:6-31)
-    unsigned L = 0, log_L = 0, log_fri = 0, log_q = 0;
-    unsigned n_cols = 0;           // V sigmas + nC constants + (w+1) tables
+    unsigned L = 0, log_L = 0, log_q = 0;
     // shard of the LDE domain held by this GPU: cosets [c0, c0 + cl), i.e. flat indices [c0*n, (c0+cl)*n)
     bj::Shard sh;
     unsigned c0 = 0, cl = 0;
     size_t Ls = 0;                 // column stride of every LDE array = cl * n
     size_t Nl = 0;                 // Merkle leaves held here (n * fri_lde / world)
     size_t cap_l = 0;              // cap nodes of the local subtree (cap_size / world)
-    gl::u64 *d_nat = nullptr;          // [n_cols][n] natural-order values (replicated)
-    gl::u64 *d_mono = nullptr;         // [n_cols][n] monomial forms (replicated; the DEEP numerator is combined on them)
+    gl::u64 *d_nat = nullptr;          // [setup width][n] natural-order values (replicated)
+    gl::u64 *d_mono = nullptr;         // [setup width][n] monomial forms (replicated; the DEEP numerator is combined on them)
     bool tiled = false;            // monomials (these and every proof's) in the tiled layout of ntt_r16.hip: 2^22-row traces
-    gl::u64 *d_lde = nullptr;          // [n_cols][cl][n]
+    gl::u64 *d_lde = nullptr;          // [setup width][cl][n]
     gl::u64 *d_tree = nullptr;         // local subtree
     gl::u64 *d_non_res = nullptr;
     gl::u64 *d_inv_xm1 = nullptr;      // 1 / (x - 1) on the points this GPU evaluates the quotient on (a property of the domain)

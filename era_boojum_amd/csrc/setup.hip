@@ -97,10 +97,9 @@ int bj::circuit_check(bj_ctx *ctx, const char *who, const bj_circuit *c, const b
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "pow_bits must be <= 32 and below the security level (pow.rs:53, prover.rs:2293)", who);
     if (cfg->pow_runner > BJ_POW_KECCAK256)
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "pow_runner %u (0 / BJ_POW_BLAKE2S256 / BJ_POW_KECCAK256)", who, cfg->pow_runner);
-    // LookupParameters::UseSpecializedColumnsWithTableIdAsVariable (cs/mod.rs:237-241): table_ids_column_idxes is empty (setup.rs:970-971)
-    // and a sub-argument owns width + 1 variable columns, the last one the table id (lookup_argument_in_ext.rs:354-366, 949-1000)
-    const bool tid_var = c->lookup_reps && c->table_id_col == BJ_TABLE_ID_AS_VARIABLE;
-    const unsigned lookup_cps = c->lookup_width + (tid_var ? 1u : 0u);
+    const bj::CircuitShape shape = bj::circuit_shape(c, cfg);   // proof_layout.h: the table id as a constant or as a variable
+    const bool tid_var = shape.tid_var;
+    const unsigned lookup_cps = shape.lookup_cps;
     if (c->lookup_reps && (!has_tables || c->lookup_width == 0 || c->lookup_width > 8 || (!tid_var && c->table_id_col >= c->num_constant_cols)))
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, BJ_WHO "bad lookup parameters", who);
     if ((uint64_t)c->num_vars < (uint64_t)c->num_gp_vars + (uint64_t)lookup_cps * c->lookup_reps || !c->non_residues)
@@ -142,9 +141,9 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
     if (!c || !cfg || (!h_sigmas && !fill_sigmas) || !h_constants) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: null argument");
     bj::GateList gates;
     if (int rc = bj::circuit_check(ctx, "bj_setup_create", c, cfg, h_tables != nullptr, comm, &gates)) return rc;
-    const bool tid_var = c->lookup_reps && c->table_id_col == BJ_TABLE_ID_AS_VARIABLE;
-    const unsigned lookup_cps = c->lookup_width + (tid_var ? 1u : 0u);
     bj_setup *s = new bj_setup();
+    static_cast<bj::CircuitShape &>(*s) = bj::circuit_shape(c, cfg);
+    s->layout = bj::proof_layout(*s);
     s->device = ctx->device;
     bj::HasherGuard hasher_guard{ctx, ctx->hasher};
     ctx->hasher = cfg->tree_hasher ? (int)cfg->tree_hasher : BJ_HASHER_POSEIDON2;
@@ -153,11 +152,6 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
         s->sh.world = comm->world;
         s->sh.comm = *comm;
     }
-    s->log_n = c->log_n; s->V = c->num_vars; s->num_gp_vars = c->num_gp_vars; s->nC = c->num_constant_cols;
-    s->Wc = c->num_witness_cols;
-    s->lookup_w = c->lookup_width; s->lookup_reps = c->lookup_reps; s->table_id_col = tid_var ? 0 : c->table_id_col;
-    s->tid_var = tid_var; s->lookup_cps = lookup_cps;
-    s->q = c->quotient_degree;
     s->gates = std::move(gates);
     auto upload = [ctx](std::vector<bj::DevProgram> &to, const bj_gate_desc *from, unsigned n) {
         to.resize(n);
@@ -179,15 +173,15 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
         s->pub_cols.push_back(c->public_input_cols[i]);
         s->pub_rows.push_back(c->public_input_rows[i]);
     }
-    s->fri_lde = cfg->fri_lde_factor; s->cap_size = cfg->cap_size; s->security = cfg->security_level; s->pow_bits = cfg->pow_bits;
+    s->fri_lde = cfg->fri_lde_factor; s->security = cfg->security_level; s->pow_bits = cfg->pow_bits;
     s->pow_runner = cfg->pow_runner ? cfg->pow_runner : BJ_POW_BLAKE2S256;
     s->transcript = cfg->transcript ? cfg->transcript : BJ_TRANSCRIPT_POSEIDON2;
     s->hasher = cfg->tree_hasher ? cfg->tree_hasher : BJ_HASHER_POSEIDON2;
     s->L = s->fri_lde > s->q ? s->fri_lde : s->q;   // used_lde_degree (prover.rs:313)
-    s->log_L = bj::log2_exact(s->L); s->log_fri = bj::log2_exact(s->fri_lde); s->log_q = bj::log2_exact(s->q);
+    s->log_L = bj::log2_exact(s->L); s->log_q = bj::log2_exact(s->q);
     const size_t n = (size_t)1 << s->log_n;
-    const unsigned nT = s->lookup_reps ? s->lookup_w + 1 : 0;
-    s->n_cols = s->V + s->nC + nT;
+    const bj::ProofLayout &L = s->layout;
+    const unsigned n_cols = L.widths[bj::ORACLE_SETUP], nT = n_cols - L.table(0);
     s->cl = s->L / s->sh.world;
     s->c0 = s->sh.rank * s->cl;
     s->Ls = (size_t)s->cl * n;
@@ -198,23 +192,23 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
         bj_setup_destroy(s);
         return code;
     };
-    if (hipMalloc((void **)&s->d_nat, (size_t)s->n_cols * n * 8) != hipSuccess ||
-        hipMalloc((void **)&s->d_lde, (size_t)s->n_cols * s->Ls * 8) != hipSuccess ||
+    if (hipMalloc((void **)&s->d_nat, (size_t)n_cols * n * 8) != hipSuccess ||
+        hipMalloc((void **)&s->d_lde, (size_t)n_cols * s->Ls * 8) != hipSuccess ||
         hipMalloc((void **)&s->d_non_res, s->V * 8) != hipSuccess)
         return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_setup_create: device allocation failed"));
     // leaf order of the setup oracle: sigma || constants || tables (polynomial_storage.rs:667-676)
     rc = fill_sigmas ? fill_sigmas(s, s->d_nat) : bj_memcpy_h2d(ctx, s->d_nat, h_sigmas, (size_t)s->V * n * 8);
-    if (!rc) rc = bj_memcpy_h2d(ctx, s->d_nat + (size_t)s->V * n, h_constants, (size_t)s->nC * n * 8);
-    if (!rc && nT) rc = bj_memcpy_h2d(ctx, s->d_nat + (size_t)(s->V + s->nC) * n, h_tables, (size_t)nT * n * 8);
+    if (!rc) rc = bj_memcpy_h2d(ctx, s->d_nat + (size_t)L.constant(0) * n, h_constants, (size_t)s->nC * n * 8);
+    if (!rc && nT) rc = bj_memcpy_h2d(ctx, s->d_nat + (size_t)L.table(0) * n, h_tables, (size_t)nT * n * 8);
     if (!rc) rc = bj_memcpy_h2d(ctx, s->d_non_res, s->non_residues.data(), s->V * 8);
     if (rc) return bail(rc);
     {   // monomials (kept), LDE into d_lde
-        if (hipMalloc((void **)&s->d_mono, (size_t)s->n_cols * n * 8) != hipSuccess)
+        if (hipMalloc((void **)&s->d_mono, (size_t)n_cols * n * 8) != hipSuccess)
             return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_setup_create: device allocation failed"));
         s->tiled = bj::mono_tiled(s->log_n);
-        rc = s->tiled ? bj::intt_to_tiled(ctx, s->d_nat, n, s->d_mono, n, s->log_n, s->n_cols)
-                      : bj_intt_batch(ctx, s->d_nat, s->d_mono, s->log_n, s->n_cols, n, 1);
-        if (!rc) rc = bj::lde_cosets_strided(ctx, s->d_mono, n, s->d_lde, s->Ls, s->log_n, s->n_cols, s->log_L, s->c0, s->cl, s->tiled);
+        rc = s->tiled ? bj::intt_to_tiled(ctx, s->d_nat, n, s->d_mono, n, s->log_n, n_cols)
+                      : bj_intt_batch(ctx, s->d_nat, s->d_mono, s->log_n, n_cols, n, 1);
+        if (!rc) rc = bj::lde_cosets_strided(ctx, s->d_mono, n, s->d_lde, s->Ls, s->log_n, n_cols, s->log_L, s->c0, s->cl, s->tiled);
         if (!rc) rc = bj_sync(ctx);
         if (rc) return bail(rc);
     }
@@ -230,7 +224,7 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
     }
     if (hipMalloc((void **)&s->d_tree, bj_merkle_tree_digests(s->Nl, s->cap_l) * 32) != hipSuccess)
         return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_setup_create: tree allocation failed"));
-    rc = bj_merkle_tree_build(ctx, s->d_lde, s->Ls, s->n_cols, s->Nl, s->cap_l, s->d_tree);
+    rc = bj_merkle_tree_build(ctx, s->d_lde, s->Ls, n_cols, s->Nl, s->cap_l, s->d_tree);
     s->cap.resize(4 * s->cap_size);
     if (!rc) rc = bj::gather_cap(ctx, s->sh, s->d_tree, s->Nl, s->cap_size, s->cap.data());
     if (rc) return bail(rc);
@@ -258,10 +252,11 @@ int bj_setup_cap(const bj_setup *s, uint64_t *h_cap) {
 int bj_setup_device_bytes(const bj_setup *s, size_t *bytes) {
     if (!s || !bytes) return BJ_ERR_INVALID_ARG;
     const size_t n = (size_t)1 << s->log_n;
+    const unsigned n_cols = s->layout.widths[bj::ORACLE_SETUP];
     size_t b = 0;
-    if (s->d_nat) b += (size_t)s->n_cols * n * 8;
-    if (s->d_mono) b += (size_t)s->n_cols * n * 8;
-    if (s->d_lde) b += (size_t)s->n_cols * s->Ls * 8;
+    if (s->d_nat) b += (size_t)n_cols * n * 8;
+    if (s->d_mono) b += (size_t)n_cols * n * 8;
+    if (s->d_lde) b += (size_t)n_cols * s->Ls * 8;
     if (s->d_tree) b += bj_merkle_tree_digests(s->Nl, s->cap_l) * 32;
     if (s->d_non_res) b += (size_t)s->V * 8;
     if (s->d_inv_xm1) b += (n * s->q) / s->sh.world * 8;

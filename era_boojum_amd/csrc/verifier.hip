@@ -37,9 +37,8 @@ void launch_verify_openings(int hasher, const VerifyOpenArgs &args, hipStream_t 
 const std::vector<u64> &proof_words(const bj_proof *p);   // prover.hip: the serialised words a proof handle holds
 }
 
-struct bj_vk {
-    unsigned log_n = 0, V = 0, num_gp_vars = 0, Wc = 0, nC = 0, lookup_w = 0, lookup_reps = 0, table_id_col = 0, q = 0, lookup_cps = 0;
-    bool tid_var = false;
+struct bj_vk : bj::CircuitShape {   // proof_layout.h
+    bj::ProofLayout layout;         // of this shape
     struct Program {   // canonical op list, packed as the interpreter kernels take it (gate_program.h: pack_program)
         std::vector<bj::DevRelation> rel;
         std::vector<u64> values;
@@ -52,8 +51,8 @@ struct bj_vk {
     unsigned n_gate_terms = 0, n_spec_terms = 0;
     std::vector<u64> non_residues;
     std::vector<unsigned> pub_cols, pub_rows;
-    unsigned fri_lde = 0, cap_size = 0, security = 0, pow_bits = 0, transcript = BJ_TRANSCRIPT_POSEIDON2, hasher = BJ_HASHER_POSEIDON2,
-             pow_runner = BJ_POW_BLAKE2S256, log_fri = 0;
+    unsigned fri_lde = 0, security = 0, pow_bits = 0, transcript = BJ_TRANSCRIPT_POSEIDON2, hasher = BJ_HASHER_POSEIDON2,
+             pow_runner = BJ_POW_BLAKE2S256;
     std::vector<u64> cap;
 };
 
@@ -409,10 +408,10 @@ struct Prepared {
 
 // The counts the key dictates and where the sections of one proof lie (pointers into the caller's buffer).
 struct ProofView {
-    unsigned log_n, V, Wc, nC, q, log_fri, LOGN, depth, n_chunks, n_partials, n_lookup_terms, n_lookup_polys, total_folds;
+    bj::SerialLayout at;   // proof_layout.h: the sections, the words of a query
+    unsigned log_n, V, Wc, nC, q, log_fri, LOGN, n_chunks, n_lookup_terms;
     bool has_lookup;
-    size_t N, cap, nz, n_pub, nq, query_words, sched_len, final_degree;
-    unsigned widths[4], fri_depth[32];
+    size_t N, cap, nz, n_pub, nq, sched_len, final_degree;
     uint32_t sched[32], new_pow;
     u64 pow_challenge;
     const u64 *pub, *wit_cap, *s2_cap, *q_cap, *vz_w, *vzo_w, *v0_w, *fri_caps, *fm0, *fm1, *queries;
@@ -431,9 +430,8 @@ struct Draw {
     std::vector<u64> indices;   // [nq] drawn, then [nq] stored: the proof's claim
     int first_mismatch = -1;
 };
-// The DEEP sources in opening order as the kernel reads them (VerifyDeepArgs: terms, sets), and the leaf offsets they rest on.
+// The DEEP sources in opening order as the kernel reads them (VerifyDeepArgs: terms, sets).
 struct DeepTables {
-    uint32_t leaf_off[4] = {};
     std::vector<u64> term_words, set_words;
     size_t n_sets = 0;
 };
@@ -446,70 +444,47 @@ e2 challenge2(bj::host::Transcript &t) {
 // shape: every count is the key's before it sizes anything
 bool parse_proof(const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, Prepared *R, ProofView *P) {
     bj_verify_report *out = &R->report;
-    const unsigned V = P->V = K->V, Wc = P->Wc = K->Wc, nC = P->nC = K->nC, q = P->q = K->q;
-    const unsigned log_n = P->log_n = K->log_n, log_fri = P->log_fri = K->log_fri, LOGN = P->LOGN = log_n + log_fri;
-    const size_t n = (size_t)1 << log_n, N = P->N = n << log_fri, cap = P->cap = K->cap_size;
-    const bool has_lookup = P->has_lookup = K->lookup_reps > 0;
-    P->n_chunks = (V + q - 1) / q;
-    const unsigned n_partials = P->n_partials = P->n_chunks - 1;
-    const unsigned n_lookup_terms = P->n_lookup_terms = has_lookup ? K->lookup_reps + 1 : 0;
-    const unsigned n_lookup_polys = P->n_lookup_polys = has_lookup ? K->lookup_reps + 2 + K->lookup_w + 1 : 0;
-    const size_t nz = P->nz = (size_t)V + Wc + nC + V + 1 + n_partials + n_lookup_polys + q;
-    const unsigned widths[4] = {V + Wc + (has_lookup ? 1u : 0u), 2 * (1 + n_partials) + (has_lookup ? 2 * (K->lookup_reps + 1) : 0u), 2 * q,
-                                V + nC + (has_lookup ? K->lookup_w + 1 : 0u)};
-    std::memcpy(P->widths, widths, sizeof widths);
+    const bj::ProofLayout &L = K->layout;
+    P->V = K->V, P->Wc = K->Wc, P->nC = K->nC, P->q = K->q;
+    const unsigned log_n = P->log_n = K->log_n, log_fri = P->log_fri = K->log_fri;
+    P->LOGN = log_n + log_fri;
+    P->N = (size_t)1 << P->LOGN, P->cap = K->cap_size;
+    P->has_lookup = L.has_lookup;
+    P->n_chunks = L.n_chunks, P->n_lookup_terms = L.n_lookup_terms, P->nz = L.nz;
     uint32_t *sched = P->sched;
     size_t num_queries = 0, sched_len = 0, final_degree = 0;
-    if (bj_fri_schedule(K->security, cap, K->pow_bits, log_fri, log_n, &P->new_pow, &num_queries, sched, &sched_len, &final_degree) || sched_len > 32) {
+    if (bj_fri_schedule(K->security, P->cap, K->pow_bits, log_fri, log_n, &P->new_pow, &num_queries, sched, &sched_len, &final_degree) || sched_len > 32) {
         R->refuse(BJ_ERR_INVALID_ARG, "bj_verify: compute_fri_schedule failed for the key's config");
         return false;
     }
     P->sched_len = sched_len;
     P->final_degree = final_degree;
     auto shape = [&]() { verdict(out, BJ_VERIFY_SHAPE); return false; };
-    if (N < cap || LOGN > 32) return shape();
-    const unsigned depth = P->depth = bj::log2_exact(N / cap);
-    if (!W || n_words < 19 || W[0] != 0x424A5046ULL || W[1] != 2) return shape();
     const size_t n_pub = P->n_pub = K->pub_cols.size();
-    const u64 nq64 = W[9];
+    if (!W || n_words < bj::ProofHeader::WORDS) return shape();
+    const u64 nq64 = W[bj::ProofHeader::N_QUERIES];
     const bool partial = (flags & BJ_VERIFY_PARTIAL_QUERIES) != 0;
-    if (W[2] != n_pub || W[3] != cap || W[4] != nz || W[5] != 1 || W[6] != n_lookup_terms || W[7] != sched_len || W[8] != final_degree ||
-        !(nq64 == num_queries || (partial && nq64 > 0 && nq64 < num_queries)) || W[10] != widths[0] || W[11] != widths[1] ||
-        W[12] != widths[2] || W[13] != widths[3] || W[14] != depth || W[15] != log_n || W[16] != K->fri_lde || W[17] != K->pow_bits)
-        return shape();
+    if (!(nq64 == num_queries || (partial && nq64 > 0 && nq64 < num_queries))) return shape();
     const size_t nq = P->nq = (size_t)nq64;
-    size_t query_words = 1;
-    for (int o = 0; o < 4; o++) query_words += widths[o] + (size_t)depth * 4;
-    {
-        size_t ln = N;
-        for (size_t l = 0; l < sched_len; l++) {
-            const unsigned k = sched[l];
-            if (k < 1 || k > 3 || (ln >> k) < cap) return shape();   // a schedule the prover cannot emit
-            P->fri_depth[l] = bj::log2_exact((ln >> k) / cap);
-            query_words += ((size_t)2 << k) + (size_t)P->fri_depth[l] * 4;
-            ln >>= k;
-            P->total_folds += k;
-        }
-    }
-    P->query_words = query_words;
-    const size_t fixed = 19 + sched_len + n_pub + 3 * cap * 4 + 2 * (nz + 1 + n_lookup_terms) + sched_len * cap * 4 + 2 * final_degree;
-    if (n_words != fixed + nq * query_words) return shape();
-    P->pow_challenge = W[18];
-    const u64 *p = W + 19;
+    const bj::SerialLayout &at = P->at = bj::serial_layout(L, sched, sched_len, final_degree, nq, n_pub);
+    if (!at.ok) return shape();   // a domain below the cap, a schedule the prover cannot emit
+    bj::ProofHeader header;
+    header.fill(L, n_pub, sched_len, final_degree, nq, at.depth, K->pow_bits, 0);
+    if (!header.matches(W) || n_words != at.total) return shape();
+    P->pow_challenge = W[bj::ProofHeader::POW_CHALLENGE];
     for (size_t l = 0; l < sched_len; l++)
-        if (p[l] != sched[l]) return shape();
-    p += sched_len;
-    P->pub = p; p += n_pub;
-    P->wit_cap = p; p += cap * 4;
-    P->s2_cap = p; p += cap * 4;
-    P->q_cap = p; p += cap * 4;
-    P->vz_w = p; p += 2 * nz;
-    P->vzo_w = p; p += 2;
-    P->v0_w = p; p += 2 * (size_t)n_lookup_terms;
-    P->fri_caps = p; p += sched_len * cap * 4;
-    P->fm0 = p; p += final_degree;
-    P->fm1 = p; p += final_degree;
-    P->queries = p;
+        if (W[at.schedule + l] != sched[l]) return shape();
+    P->pub = W + at.public_inputs;
+    P->wit_cap = W + at.witness_cap;
+    P->s2_cap = W + at.stage2_cap;
+    P->q_cap = W + at.quotient_cap;
+    P->vz_w = W + at.values_at_z;
+    P->vzo_w = W + at.values_at_z_omega;
+    P->v0_w = W + at.values_at_0;
+    P->fri_caps = W + at.fri_caps;
+    P->fm0 = W + at.final_c0;
+    P->fm1 = W + at.final_c1;
+    P->queries = W + at.queries;
     return true;
 }
 
@@ -543,18 +518,19 @@ void split_openings(const bj_vk *K, const ProofView &P, Openings *O) {
     for (size_t i = 0; i < P.nz; i++) O->vz[i] = e2c(P.vz_w + 2 * i);
     for (size_t i = 0; i < P.n_lookup_terms; i++) O->v0[i] = e2c(P.v0_w + 2 * i);
     O->z_at_zo = e2c(P.vzo_w);
-    O->var_z = O->vz.data();
-    O->wit_z = O->var_z + P.V;
-    O->con_z = O->wit_z + P.Wc;
-    O->sig_z = O->con_z + P.nC;
-    O->z_at_z = O->sig_z[P.V];
-    O->part_z = O->sig_z + P.V + 1;
-    const e2 *lk = O->part_z + P.n_partials;
-    O->mult_z = lk;
-    O->A_z = lk + (P.has_lookup ? 1 : 0);
-    O->B_z = O->A_z + K->lookup_reps;
-    O->tab_z = O->B_z + (P.has_lookup ? 1 : 0);
-    O->qch_z = lk + P.n_lookup_polys;
+    const bj::ProofLayout &L = K->layout;
+    const e2 *vz = O->vz.data();
+    O->var_z = vz + L.at_var;
+    O->wit_z = vz + L.at_wit;
+    O->con_z = vz + L.at_const;
+    O->sig_z = vz + L.at_sigma;
+    O->z_at_z = vz[L.at_z];
+    O->part_z = vz + L.at_partial;
+    O->mult_z = vz + L.at_mult;
+    O->A_z = vz + L.at_a;
+    O->B_z = vz + L.at_b;
+    O->tab_z = vz + L.at_table;
+    O->qch_z = vz + L.at_chunk;
 }
 
 // the lookup sub-arguments at z (verifier.rs:1397-1470)
@@ -565,7 +541,7 @@ e2 lookup_terms(const bj_vk *K, const Challenges &C, const Openings &O, const e2
     for (unsigned j = 1; j <= K->lookup_w; j++) gp[j] = gl::e2_mul(gp[j - 1], C.lgamma);
     for (unsigned i = 0; i < K->lookup_reps; i++) {
         e2 d = C.lbeta;
-        for (unsigned j = 0; j < K->lookup_cps; j++) d = gl::e2_add(d, gl::e2_mul(gp[j], O.var_z[K->num_gp_vars + i * K->lookup_cps + j]));
+        for (unsigned j = 0; j < K->lookup_cps; j++) d = gl::e2_add(d, gl::e2_mul(gp[j], O.var_z[K->layout.lookup_var(i, j)]));
         if (!K->tid_var) d = gl::e2_add(d, gl::e2_mul(gp[K->lookup_w], O.con_z[K->table_id_col]));
         T = gl::e2_add(T, gl::e2_mul(gl::e2_sub(gl::e2_mul(O.A_z[i], d), ONE2), a_lookup[i]));
     }
@@ -711,7 +687,7 @@ bool draw_challenges_and_indices(const bj_vk *K, const ProofView &P, bj::host::T
     bools.max_needed = P.LOGN;
     for (size_t i = 0; i < nq; i++) {
         D->indices[i] = bools.query_index(t, P.log_n, P.log_fri);
-        const u64 stored = P.queries[i * P.query_words];
+        const u64 stored = P.queries[i * P.at.query_words];
         if (stored >= P.N) return stop(BJ_VERIFY_SHAPE, i);   // not an index of the domain at all
         D->indices[nq + i] = stored;
         if (stored != D->indices[i] && D->first_mismatch < 0) D->first_mismatch = (int)i;
@@ -721,52 +697,20 @@ bool draw_challenges_and_indices(const bj_vk *K, const ProofView &P, bj::host::T
 
 // the DEEP sources in opening order (verifier.rs:2233-2290) as words of a query's block
 bool deep_tables(const bj_vk *K, const ProofView &P, const Challenges &C, const Openings &O, const Draw &D, Prepared *R, DeepTables *DT) {
-    const unsigned V = P.V, Wc = P.Wc, nC = P.nC, n_partials = P.n_partials, n_lookup_terms = P.n_lookup_terms, log_n = P.log_n;
+    const bj::ProofLayout &L = K->layout;
+    const unsigned n_lookup_terms = P.n_lookup_terms, log_n = P.log_n;
     const size_t nz = P.nz, n_pub = P.n_pub;
-    const bool has_lookup = P.has_lookup;
-    uint32_t *leaf_off = DT->leaf_off;
-    {
-        uint32_t o = 1;
-        for (int k = 0; k < 4; k++) {
-            leaf_off[k] = o;
-            o += P.widths[k] + P.depth * 4;
-        }
-    }
-    const uint32_t oW = leaf_off[0], oS2 = leaf_off[1], oQ = leaf_off[2], oSU = leaf_off[3];
     struct Term { uint32_t o0, o1; };
-    std::vector<Term> src;
-    auto base_run = [&](uint32_t at, size_t count) { for (size_t i = 0; i < count; i++) src.push_back({at + (uint32_t)i, NO_C1}); };
-    auto ext_run = [&](uint32_t at, size_t pairs) { for (size_t i = 0; i < pairs; i++) src.push_back({at + 2 * (uint32_t)i, at + 2 * (uint32_t)i + 1}); };
-    base_run(oW, V + Wc);             // variables, witness columns
-    base_run(oSU + V, nC);            // constants
-    base_run(oSU, V);                 // sigmas
-    ext_run(oS2, 1 + n_partials);     // z, partial products
-    const uint32_t oLk = oS2 + 2 * (1 + n_partials);
-    if (has_lookup) {
-        base_run(oW + V + Wc, 1);             // multiplicities
-        ext_run(oLk, K->lookup_reps + 1);     // A_i, B
-        base_run(oSU + V + nC, K->lookup_w + 1);
-    }
-    ext_run(oQ, P.q);
-    if (src.size() != nz) {
-        R->refuse(BJ_ERR_HIP, "bj_verify: internal error: %zu DEEP sources for %zu openings", src.size(), nz);
+    auto term_of = [&](const bj::Opened &o) {   // the words of a query's block that hold the polynomial's leaf elements
+        const uint32_t leaf = P.at.leaf_off[o.oracle];
+        return Term{leaf + o.col0, o.col1 == bj::NO_COLUMN ? NO_C1 : leaf + o.col1};
+    };
+    if (L.opened.size() != nz) {
+        R->refuse(BJ_ERR_HIP, "bj_verify: internal error: %zu DEEP sources for %zu openings", L.opened.size(), nz);
         return false;
     }
-    struct PubSet { u64 at; std::vector<uint32_t> cols; std::vector<u64> vals; };
-    std::vector<PubSet> pubs;
-    {
-        const u64 om = gl::omega(log_n);
-        for (size_t i = 0; i < n_pub; i++) {
-            const u64 at = gl::pow(om, K->pub_rows[i]);
-            size_t pos = 0;
-            for (; pos < pubs.size(); pos++)
-                if (pubs[pos].at == at) break;
-            if (pos == pubs.size()) pubs.push_back({at, {}, {}});
-            pubs[pos].cols.push_back(K->pub_cols[i]);
-            pubs[pos].vals.push_back(gl::canon(P.pub[i]));
-        }
-    }
-    const size_t n_sets = DT->n_sets = 2 + (has_lookup ? 1 : 0) + pubs.size();
+    const std::vector<bj::OpeningSet> sets = L.opening_sets(K->pub_cols.data(), K->pub_rows.data(), n_pub);
+    const size_t n_sets = DT->n_sets = sets.size();
     const size_t n_terms = nz + 1 + n_lookup_terms + n_pub;
     std::vector<u64> &term_words = DT->term_words, &set_words = DT->set_words;
     term_words.assign(3 * n_terms, 0);
@@ -787,20 +731,25 @@ bool deep_tables(const bj_vk *K, const ProofView &P, const Challenges &C, const 
         chp = gl::e2_mul(chp, D.cch);
     };
     auto close_set = [&]() { set_words[6 * sno++ + 1] = tno; };
-    open_set(C.z);
-    for (size_t i = 0; i < nz; i++) add_term(src[i], O.vz[i]);
-    close_set();
-    open_set(gl::e2_mul_base(C.z, gl::omega(log_n)));
-    add_term({oS2, oS2 + 1}, O.z_at_zo);
-    close_set();
-    if (has_lookup) {
-        open_set(ZERO2);
-        for (unsigned i = 0; i < n_lookup_terms; i++) add_term({oLk + 2 * i, oLk + 2 * i + 1}, O.v0[i]);
-        close_set();
-    }
-    for (const auto &ps : pubs) {
-        open_set(e2{ps.at, 0});
-        for (size_t i = 0; i < ps.cols.size(); i++) add_term({oW + ps.cols[i], NO_C1}, e2{ps.vals[i], 0});
+    auto point_of = [&](const bj::OpeningSet &set) {
+        switch (set.point) {
+            case bj::OPEN_AT_Z: return C.z;
+            case bj::OPEN_AT_Z_OMEGA: return gl::e2_mul_base(C.z, gl::omega(log_n));
+            case bj::OPEN_AT_ZERO: return ZERO2;
+            default: return e2{gl::pow(gl::omega(log_n), set.row), 0};
+        }
+    };
+    auto value_of = [&](const bj::OpeningSet &set, size_t i) {
+        switch (set.point) {
+            case bj::OPEN_AT_Z: return O.vz[set.value[i]];
+            case bj::OPEN_AT_Z_OMEGA: return O.z_at_zo;
+            case bj::OPEN_AT_ZERO: return O.v0[set.value[i]];
+            default: return e2{gl::canon(P.pub[set.value[i]]), 0};
+        }
+    };
+    for (const bj::OpeningSet &set : sets) {
+        open_set(point_of(set));
+        for (size_t i = 0; i < set.polys.size(); i++) add_term(term_of(set.polys[i]), value_of(set, i));
         close_set();
     }
     return true;
@@ -809,9 +758,10 @@ bool deep_tables(const bj_vk *K, const ProofView &P, const Challenges &C, const 
 // what the judge needs: the geometry, and the tables in the block layout of verify_tables
 void fill_device_tables(const bj_vk *K, const ProofView &P, const Draw &D, const DeepTables &DT, Prepared *R) {
     const size_t sched_len = P.sched_len, final_degree = P.final_degree, nq = P.nq, n_oracles = 4 + sched_len, cap_words = P.cap * 4;
-    const unsigned depth = P.depth;
+    const bj::SerialLayout &at_q = P.at;
+    const unsigned *widths = K->layout.widths;
     Geometry &G = R->geo;
-    G.sizes.query_words = P.query_words;
+    G.sizes.query_words = at_q.query_words;
     G.sizes.n_oracles = n_oracles;
     G.sizes.cap_words = cap_words;
     G.sizes.term_words = DT.term_words.size();
@@ -821,17 +771,14 @@ void fill_device_tables(const bj_vk *K, const ProofView &P, const Draw &D, const
     G.LOGN = P.LOGN;
     G.n_sets = (unsigned)DT.n_sets;
     G.n_fri = (unsigned)sched_len;
-    G.total_folds = P.total_folds;
-    for (int o = 0; o < 4; o++) G.oracle[o] = bj::VerifyOracle{DT.leaf_off[o], P.widths[o], depth, 0, (uint32_t)(o * cap_words)};
-    {
-        uint32_t o = DT.leaf_off[3] + P.widths[3] + depth * 4, shift = 0;
-        for (size_t l = 0; l < sched_len; l++) {
-            shift += P.sched[l];
-            G.oracle[4 + l] = bj::VerifyOracle{o, 2u << P.sched[l], P.fri_depth[l], shift, (uint32_t)((4 + l) * cap_words)};
-            G.fri_off[l] = o;
-            G.sched[l] = (unsigned char)P.sched[l];
-            o += (2u << P.sched[l]) + P.fri_depth[l] * 4;
-        }
+    G.total_folds = at_q.total_folds;
+    for (int o = 0; o < 4; o++) G.oracle[o] = bj::VerifyOracle{at_q.leaf_off[o], widths[o], at_q.depth, 0, (uint32_t)(o * cap_words)};
+    uint32_t shift = 0;
+    for (size_t l = 0; l < sched_len; l++) {
+        shift += P.sched[l];
+        G.oracle[4 + l] = bj::VerifyOracle{at_q.fri_leaf_off[l], 2u << P.sched[l], at_q.fri_depth[l], shift, (uint32_t)((4 + l) * cap_words)};
+        G.fri_off[l] = at_q.fri_leaf_off[l];
+        G.sched[l] = (unsigned char)P.sched[l];
     }
     const bj::VerifyTables at = bj::verify_tables(G.sizes, nq);
     R->tables.assign(at.words, 0);
@@ -1043,13 +990,12 @@ void take_gates(bj_vk *k, const bj::GateList &L, ProgramOf program_of) {
     }
 }
 
-void finish_config(bj_vk *k, unsigned fri_lde, unsigned cap_size, unsigned security, unsigned pow_bits, unsigned transcript, unsigned hasher,
-                   unsigned pow_runner) {
-    k->fri_lde = fri_lde; k->cap_size = cap_size; k->security = security; k->pow_bits = pow_bits;
+void finish_config(bj_vk *k, unsigned fri_lde, unsigned security, unsigned pow_bits, unsigned transcript, unsigned hasher, unsigned pow_runner) {
+    k->layout = bj::proof_layout(*k);
+    k->fri_lde = fri_lde; k->security = security; k->pow_bits = pow_bits;
     k->transcript = transcript ? transcript : BJ_TRANSCRIPT_POSEIDON2;
     k->hasher = hasher ? hasher : BJ_HASHER_POSEIDON2;
     k->pow_runner = pow_runner ? pow_runner : BJ_POW_BLAKE2S256;
-    k->log_fri = bj::log2_exact(fri_lde);
 }
 
 }  // namespace
@@ -1063,11 +1009,7 @@ int bj_vk_create(const bj_circuit *c, const uint64_t *setup_cap, const bj_proof_
     bj::GateList L;
     if (int rc = bj::circuit_check(nullptr, "bj_vk_create", c, cfg, true, nullptr, &L)) return rc;
     bj_vk *k = new bj_vk();
-    k->log_n = c->log_n; k->V = c->num_vars; k->num_gp_vars = c->num_gp_vars; k->Wc = c->num_witness_cols; k->nC = c->num_constant_cols;
-    k->lookup_w = c->lookup_width; k->lookup_reps = c->lookup_reps; k->q = c->quotient_degree;
-    k->tid_var = c->lookup_reps && c->table_id_col == BJ_TABLE_ID_AS_VARIABLE;
-    k->table_id_col = k->tid_var ? 0 : c->table_id_col;
-    k->lookup_cps = c->lookup_width + (k->tid_var ? 1u : 0u);
+    static_cast<bj::CircuitShape &>(*k) = bj::circuit_shape(c, cfg);
     auto take_program = [](const bj_gate_program *p, bj_vk::Program *P) {   // circuit_check has canonicalised it once: it cannot fail here
         bj::canon::Program C;
         std::string err;
@@ -1081,7 +1023,7 @@ int bj_vk_create(const bj_circuit *c, const uint64_t *setup_cap, const bj_proof_
         k->pub_cols.push_back(c->public_input_cols[i]);
         k->pub_rows.push_back(c->public_input_rows[i]);
     }
-    finish_config(k, cfg->fri_lde_factor, cfg->cap_size, cfg->security_level, cfg->pow_bits, cfg->transcript, cfg->tree_hasher, cfg->pow_runner);
+    finish_config(k, cfg->fri_lde_factor, cfg->security_level, cfg->pow_bits, cfg->transcript, cfg->tree_hasher, cfg->pow_runner);
     k->cap.assign(setup_cap, setup_cap + 4 * (size_t)cfg->cap_size);
     *out = k;
     return BJ_OK;
@@ -1092,9 +1034,7 @@ int bj_vk_from_setup(const bj_setup *S, bj_vk **out) {
     *out = nullptr;
     if (!S) return bj::fail(nullptr, BJ_ERR_INVALID_ARG, "bj_vk_from_setup: null setup");
     bj_vk *k = new bj_vk();
-    k->log_n = S->log_n; k->V = S->V; k->num_gp_vars = S->num_gp_vars; k->Wc = S->Wc; k->nC = S->nC;
-    k->lookup_w = S->lookup_w; k->lookup_reps = S->lookup_reps; k->q = S->q;
-    k->tid_var = S->tid_var; k->table_id_col = S->table_id_col; k->lookup_cps = S->lookup_cps;
+    static_cast<bj::CircuitShape &>(*k) = *S;
     auto take_program = [](const bj::DevProgram &d, bj_vk::Program *P) {
         P->rel = d.h_rel;
         P->values = d.h_values;
@@ -1104,7 +1044,7 @@ int bj_vk_from_setup(const bj_setup *S, bj_vk **out) {
     k->non_residues = S->non_residues;
     k->pub_cols = S->pub_cols;
     k->pub_rows = S->pub_rows;
-    finish_config(k, S->fri_lde, S->cap_size, S->security, S->pow_bits, S->transcript, S->hasher, S->pow_runner);
+    finish_config(k, S->fri_lde, S->security, S->pow_bits, S->transcript, S->hasher, S->pow_runner);
     k->cap = S->cap;
     *out = k;
     return BJ_OK;

@@ -1,7 +1,8 @@
 """Parser (and its inverse) of the flat u64 proof serialisation produced by bj_proof_serialize (csrc/prover.hip) into a dict with the field
 names of the reference's `Proof` (src/cs/implementations/proof.rs:121-136).
 
-Layout (all u64, little endian):
+Layout (all u64, little endian; the definition of the word order is csrc/proof_layout.h — bj::ProofHeader and bj::SerialLayout, which
+the prover writes through and the verifier reads through; this parser reads the header words, it does not derive them):
   header[19] = magic 'BJPF', version (2), n_public, cap_size, n_values_at_z, n_values_at_z_omega, n_values_at_0, n_fri_oracles,
                final_degree, n_queries, witness leaf width, stage-2 leaf width, quotient leaf width, setup leaf width,
                base-oracle path depth, log_n, fri_lde_factor, pow_bits, pow_challenge      (version 1: the first 17 only)
