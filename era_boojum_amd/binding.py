@@ -1366,8 +1366,8 @@ class ProverSetup:
         self.last_workspace = {"reserved_bytes": int(res.value), "high_water_bytes": int(hw.value), "overflow_slabs": int(slabs.value)}
         self._lib.bj_proof_destroy(h)
         if slabs.value and not os.environ.get("BJ_ALLOW_WORKSPACE_OVERFLOW"):
-            # the proof is right, but the reservation of reserve_workspace was not an upper bound for this geometry: every proof the test
-            # suite makes passes through here, so the list of buffers in csrc/prover.hip cannot drift away from the allocations
+            # the proof is right, but an allowance of its workspace plan (csrc/workspace_plan.h) was no upper bound for this geometry:
+            # every proof the test suite makes passes through here
             raise BoojumHipError("the proof needed %d overflow slab(s): reserved %d bytes, high-water mark %d bytes"
                                  % (slabs.value, res.value, hw.value))
         stages = dict(zip(STAGE_NAMES, [float(x) for x in ms][:7]))

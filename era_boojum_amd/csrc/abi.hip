@@ -3,6 +3,7 @@
 // enqueues HIP work on the context's device or returns an error.
 #include "ctx.h"
 #include "ntt_plan.h"
+#include "workspace_plan.h"
 
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -96,21 +97,46 @@ int arena_reset(bj_ctx *ctx, size_t need_elems) {
     return BJ_OK;
 }
 
-void *tmp_alloc(bj_ctx *ctx, size_t bytes, bool *from_arena) {
-    *from_arena = false;
-    if (ctx->in_proof) {
-        if (u64 *p = arena_alloc(ctx, (bytes + 7) / 8)) {
-            *from_arena = true;
-            return p;
-        }
+int TmpBuf::alloc(bj_ctx *c, size_t words) {
+    ctx = c;
+    from_arena = false;
+    if (c->in_proof && (p = arena_alloc(c, words))) {
+        from_arena = true;
+        return BJ_OK;
     }
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) return nullptr;
-    return p;
+    if (hipMalloc((void **)&p, words ? words * 8 : 8) != hipSuccess) {
+        p = nullptr;
+        return fail(c, BJ_ERR_OOM, "out of device memory (%zu MiB)", words * 8 >> 20);
+    }
+    return BJ_OK;
 }
-void tmp_free(bj_ctx *ctx, void *p, bool from_arena) {
-    (void)ctx;
-    if (p && !from_arena) (void)hipFree(p);
+int TmpBuf::take(bj_ctx *c, unsigned id, size_t words) {
+    const WorkspacePlan *plan = c->ws_plan;
+    if (!plan) return alloc(c, words);
+    while (c->ws_next < plan->entries.size() && !plan->entries[c->ws_next].exact) c->ws_next++;
+    if (c->ws_next == plan->entries.size())
+        return fail(c, BJ_ERR_HIP, "bj_prove: internal error: the workspace plan ends before %s", ws_name(id));
+    const WorkspaceEntry &e = plan->entries[c->ws_next];
+    if (e.id != id) return fail(c, BJ_ERR_HIP, "bj_prove: internal error: the workspace plan holds %s where the proof takes %s", ws_name(e.id), ws_name(id));
+    if (words && words != e.words)
+        return fail(c, BJ_ERR_HIP, "bj_prove: internal error: %s is planned with %zu words and taken with %zu", ws_name(id), e.words, words);
+    c->ws_next++;
+    ctx = c;
+    if (!(p = arena_alloc(c, e.words))) return fail(c, BJ_ERR_OOM, "workspace reservation too small for %zu MiB", e.words * 8 >> 20);
+    from_arena = true;   // never freed: a planned buffer may outlive the scope that took it
+    return BJ_OK;
+}
+TmpBuf::~TmpBuf() {
+    if (!p || from_arena) return;
+    if (drain) (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(p);
+}
+int workspace_all_taken(bj_ctx *ctx) {
+    const WorkspacePlan *plan = ctx->ws_plan;
+    for (size_t i = ctx->ws_next; plan && i < plan->entries.size(); i++)
+        if (plan->entries[i].exact)
+            return fail(ctx, BJ_ERR_HIP, "bj_prove: internal error: the proof ends without taking %s of its workspace plan", ws_name(plan->entries[i].id));
+    return BJ_OK;
 }
 
 constexpr size_t RING_BYTES = (size_t)1 << 20, RING_MAX_BLOCK = (size_t)128 << 10;

@@ -14,7 +14,8 @@
 #define BJ_MAX_KERNEL_PROBES 12
 
 namespace bj {
-struct Pipeline;   // prove_async.hip: the two lanes of bj_prove_async
+struct Pipeline;        // prove_async.hip: the two lanes of bj_prove_async
+struct WorkspacePlan;   // workspace_plan.h: the buffers of a proof, in the order it takes them
 }
 
 struct bj_ctx {
@@ -37,13 +38,16 @@ struct bj_ctx {
     size_t arena_elems = 0, arena_off = 0;
     // A proof whose buffers outgrow the reservation does not fail: further blocks come out of overflow slabs (hipMalloc in the
     // middle of a proof — slow, once), the proof reports its high-water mark (bj_proof_workspace_bytes) and the next reservation
-    // on this context is at least that large.  The suite asserts that no proof needed a slab (the reservation is an upper bound).
+    // on this context is at least that large.  The reservation is the total of the proof's plan and every buffer is taken from
+    // that plan, so only an allowance that was no upper bound can lead here; the suite asserts that no proof needed a slab.
     std::vector<std::pair<gl::u64 *, size_t>> arena_slabs;   // (base, elems), each slab bump-allocated like the arena
     size_t slab_off = 0;                 // elements used in the last slab
     size_t arena_high_water = 0;         // elements the proof in flight has taken (arena + slabs)
     size_t arena_learned = 0;            // largest high-water mark seen on this context
     int hasher = BJ_HASHER_POSEIDON2;   // tree hasher of the bj_merkle_tree_* calls (bj_ctx_set_tree_hasher / bj_prove)
     bool in_proof = false;       // bj_prove_dev is running: temporaries come out of the arena instead of hipMalloc
+    const bj::WorkspacePlan *ws_plan = nullptr;   // of the proof in flight (it owns the plan), and the entry TmpBuf::take expects next
+    size_t ws_next = 0;
     // pinned staging ring for the small host->device blocks between kernels (challenges, pointer tables, query indices):
     // a copy out of pageable memory costs a blocking staging pass plus a stream synchronisation, ~35 us of idle GPU each
     unsigned char *h_ring = nullptr;
@@ -105,9 +109,29 @@ int pipeline_release_workspace(bj_ctx *ctx);    // bj_ctx_release_workspace on e
 int arena_reset(bj_ctx *ctx, size_t need_elems);
 int arena_drop_slabs(bj_ctx *ctx);
 gl::u64 *arena_alloc(bj_ctx *ctx, size_t elems);   // nullptr if the reservation was too small
-// short-lived device memory: from the arena inside a proof (no hipMalloc/hipFree, no implicit syncs), hipMalloc otherwise
-void *tmp_alloc(bj_ctx *ctx, size_t bytes, bool *from_arena);
-void tmp_free(bj_ctx *ctx, void *p, bool from_arena);
+// A block of device memory for the scope that holds it: out of the arena inside a proof (no hipMalloc / hipFree, no implicit
+// synchronisation; the arena is a bump allocator and gives nothing back before the next proof), hipMalloc'ed and freed otherwise.
+struct TmpBuf {
+    gl::u64 *p = nullptr;
+    bool from_arena = false;
+    bool drain = false;          // a hipMalloc'ed block is freed after the stream has drained (the stand-alone operators)
+    bj_ctx *ctx = nullptr;
+    TmpBuf() = default;
+    explicit TmpBuf(bool drain_before_free) : drain(drain_before_free) {}
+    TmpBuf(const TmpBuf &) = delete;
+    TmpBuf &operator=(const TmpBuf &) = delete;
+    ~TmpBuf();
+    int alloc(bj_ctx *c, size_t words);   // a temporary of the callee's own: inside a proof, covered by an allowance of the plan
+    // a named buffer of the proof in flight: `id` (a WsId) must be the next exact entry of its plan and `words`, unless 0, that
+    // entry's size — anything else is an internal error and nothing is allocated.  No proof in flight: alloc(words)
+    int take(bj_ctx *c, unsigned id, size_t words = 0);
+    gl::u64 *release() {   // the caller keeps the block (bj_fri lists its hipMalloc'ed ones)
+        gl::u64 *q = p;
+        p = nullptr;
+        return q;
+    }
+};
+int workspace_all_taken(bj_ctx *ctx);   // the proof in flight has taken every exact entry of its plan, or an internal error
 int lde_cosets_strided(bj_ctx *ctx, const gl::u64 *d_mono, size_t in_col_stride, gl::u64 *d_out, size_t out_col_stride,
                        unsigned log_n, unsigned n_cols, unsigned log_lde, unsigned coset_begin, unsigned coset_count,
                        bool tiled_in = false);

@@ -6,6 +6,7 @@
 #include "ctx.h"
 #include "host_transcript.hpp"
 #include "fri_types.h"
+#include "workspace_plan.h"
 
 #include <cstring>
 #include <vector>
@@ -132,13 +133,14 @@ int bj::fri_prove_sharded(bj_ctx *ctx, const bj::Shard &sh, const u64 *d_c0, con
         bj_fri_destroy(f);
         return code;
     };
-    // layers and trees live as long as the bj_fri object: arena blocks inside a proof (released with the arena), hipMalloc
-    // blocks (listed in f->owned) for the stand-alone bj_fri_prove
-    auto alloc = [&](size_t elems) -> u64 * {
-        bool from_arena = false;
-        u64 *p = (u64 *)bj::tmp_alloc(ctx, elems * sizeof(u64), &from_arena);
-        if (p && !from_arena) f->owned.push_back(p);
-        return p;
+    // layers and trees live as long as the bj_fri object: inside a proof entries of its workspace plan (released with the
+    // arena), hipMalloc blocks (listed in f->owned) for the stand-alone bj_fri_prove
+    auto take = [&](bj::WsId id, size_t elems, u64 **out) {
+        bj::TmpBuf b;
+        if (int rc = b.take(ctx, id, elems)) return rc;
+        if (!b.from_arena) f->owned.push_back(b.p);
+        *out = b.release();
+        return (int)BJ_OK;
     };
     for (size_t step = 0; step < schedule_len; step++) {
         const unsigned k = schedule[step];
@@ -154,7 +156,7 @@ int bj::fri_prove_sharded(bj_ctx *ctx, const bj::Shard &sh, const u64 *d_c0, con
         if (o.num_leaves < loc_cap || loc_cap == 0)
             return bail(bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_fri_prove: oracle smaller than cap"));
         size_t nd = 2 * o.num_leaves - loc_cap;
-        if (!(o.d_tree = alloc(nd * 4))) return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_fri_prove: tree allocation failed"));
+        if ((rc = take(bj::WS_FRI_TREE, nd * 4, &o.d_tree))) return bail(rc);
         f->oracles.push_back(o);
         bj_fri::Oracle &oo = f->oracles.back();
         // oracle: 2^k values of c0 then of c1 per leaf (merkle_tree.rs:176-386)
@@ -171,8 +173,8 @@ int bj::fri_prove_sharded(bj_ctx *ctx, const bj::Shard &sh, const u64 *d_c0, con
         oo.ch1 = tr->t.challenge();
         // fold by 2^k in one fused launch; alpha and kappa are squared per inner fold inside the kernel
         const size_t out_len = cur_len >> k, loc_out = loc_len >> k;
-        u64 *nxt = alloc(2 * out_len);
-        if (!nxt) return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_fri_prove: layer allocation failed"));
+        u64 *nxt = nullptr, *part = nullptr;
+        if ((rc = take(bj::WS_FRI_LAYER, 2 * out_len, &nxt))) return bail(rc);
         // FRI fold by 2^k over m F_p^2 inputs, SURVEY §8d: 16 m + 16 m / 2^k
         const int pf = bj::probe_begin(ctx, "fri_fold_first", 16.0 * (double)loc_len * (1.0 + 1.0 / (double)(1u << k)));
         if (parts == 1) {
@@ -180,8 +182,7 @@ int bj::fri_prove_sharded(bj_ctx *ctx, const bj::Shard &sh, const u64 *d_c0, con
                                      ctx->stream);
             bj::probe_end(ctx, pf);
         } else {
-            u64 *part = alloc(2 * loc_out);   // [2][loc_out] of this rank, gathered into nxt = [2][out_len]
-            if (!part) return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_fri_prove: layer allocation failed"));
+            if ((rc = take(bj::WS_FRI_PART, 2 * loc_out, &part))) return bail(rc);   // [2][loc_out] of this rank, gathered into nxt = [2][out_len]
             bj::launch_fri_fold_step(cur0, cur1, loc_len, k, part, part + loc_out, ctx->tw_inv, kappa, oo.ch0, oo.ch1,
                                      ctx->stream, (size_t)sh.rank * loc_out);
             bj::probe_end(ctx, pf);
@@ -201,8 +202,8 @@ int bj::fri_prove_sharded(bj_ctx *ctx, const bj::Shard &sh, const u64 *d_c0, con
     }
     // final interpolation: bit-reverse, iNTT on coset kappa^-1, keep len/lde coefficients (fri/mod.rs:312-343)
     const unsigned log_m = bj::log2_exact(cur_len);
-    u64 *fin = alloc(2 * cur_len);
-    if (!fin) return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_fri_prove: final buffer allocation failed"));
+    u64 *fin = nullptr;
+    if ((rc = take(bj::WS_FRI_FINAL, 2 * cur_len, &fin))) return bail(rc);
     rc = bj_bitreverse_batch(ctx, cur0, fin, log_m, 2, cur_len);
     if (!rc) rc = bj_intt_batch(ctx, fin, fin, log_m, 2, cur_len, gl::inv(kappa));
     f->final_c0.resize(cur_len);

@@ -2,6 +2,7 @@
 // Not part of the public boundary (that is include/boojum_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "callee_words.h"
 #include <stddef.h>
 #include <stdint.h>
 #include <string>
@@ -99,7 +100,7 @@ void launch_fri_fold(const u64 *d_c0, const u64 *d_c1, size_t len, u64 *d_o0, u6
                      u64 coset_inv, u64 ch0, u64 ch1, hipStream_t s);
 void launch_fri_fold_step(const u64 *d_c0, const u64 *d_c1, size_t len, unsigned k, u64 *d_o0, u64 *d_o1,
                           const u64 *d_roots, u64 coset_inv, u64 ch0, u64 ch1, hipStream_t s, size_t j0 = 0);
-// stage2.hip
+// stage2.hip.  d_tmp: copy_perm_stage2_scratch_words(ceil(V / chunk), n) words
 void launch_copy_perm_stage2(const u64 *d_vars, size_t var_stride, const u64 *d_sigmas, size_t sig_stride,
                              const u64 *d_non_res, unsigned V, unsigned chunk, unsigned log_n, const u64 *d_tw_fwd,
                              const u64 *beta, const u64 *gamma, u64 *d_tmp, u64 *d_z, u64 *d_partials, hipStream_t s, bool small_non_residues);
@@ -137,7 +138,6 @@ void launch_quotient_poseidon_flattened(const u64 *d_vars, size_t var_stride, co
 // openings.hip
 void launch_barycentric_weights(u64 *d_w0, u64 *d_w1, const u64 *d_tw_fwd, unsigned log_n, u64 coset, const u64 *at,
                                 hipStream_t s);
-unsigned barycentric_num_blocks(size_t n);
 void launch_barycentric_eval(const u64 *const *d_col_ptrs, unsigned n_cols, size_t n, const u64 *d_w0, const u64 *d_w1,
                              u64 *d_partials, u64 *d_out, hipStream_t s);
 void launch_linear_combination(const u64 *const *d_col_ptrs, const u64 *d_coefs, unsigned n_cols, size_t n, u64 *d_out0,
@@ -145,8 +145,7 @@ void launch_linear_combination(const u64 *const *d_col_ptrs, const u64 *d_coefs,
 void launch_deep_accumulate(const u64 *const *d_col_ptrs, const u64 *d_coefs, unsigned n_cols, size_t N, size_t I0,
                             const u64 *d_tw_fwd, u64 c0, u64 c1, u64 at0, u64 at1, u64 *d_dst0, u64 *d_dst1,
                             int accumulate, hipStream_t s);
-// several DEEP opening sets in one launch (device-side argument pointers, canonical scalars)
-constexpr int DEEP_MAX_SETS = 3;
+// several DEEP opening sets in one launch, at most DEEP_MAX_SETS (device-side argument pointers, canonical scalars)
 struct DeepSetHostArgs {
     const u64 *const *d_cols;
     const u64 *d_coefs;     // [n_cols][2]

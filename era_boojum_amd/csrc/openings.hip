@@ -73,7 +73,7 @@ void launch_barycentric_weights(u64 *d_w0, u64 *d_w1, const u64 *d_tw_fwd, unsig
 // ---------------------------------------------------------------------------------------------------------
 // barycentric evaluation of a batch of base columns:  partial[col][block] = sum over the block's points of f * w
 // ---------------------------------------------------------------------------------------------------------
-static constexpr int BARY_PTS = 32;   // points per lane: a workgroup covers 256 * BARY_PTS consecutive points
+// BARY_PTS (callee_words.h): points per lane, a workgroup covers 256 * BARY_PTS consecutive points
 static constexpr int BARY_STEP = 4;   // points in flight per column
 static constexpr int BARY_COLS = 8;   // columns sharing one read of the weights
 
@@ -168,8 +168,6 @@ __global__ void barycentric_final_kernel(const u64 *partials, unsigned n_blocks,
         out[2 * c + 1] = red[1][0];
     }
 }
-
-unsigned barycentric_num_blocks(size_t n) { return (unsigned)((n + 256 * BARY_PTS - 1) / (256 * BARY_PTS)); }
 
 void launch_barycentric_eval(const u64 *const *d_col_ptrs, unsigned n_cols, size_t n, const u64 *d_w0, const u64 *d_w1,
                              u64 *d_partials, u64 *d_out, hipStream_t s) {

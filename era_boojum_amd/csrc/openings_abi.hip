@@ -6,20 +6,6 @@
 using gl::u64;
 
 namespace {
-// device-side argument block: [ptrs (n_cols)] [coefs (2*n_cols)] in one temporary allocation
-struct DevArgs {
-    bj_ctx *ctx = nullptr;
-    void *d = nullptr;
-    bool from_arena = false;
-    int alloc(bj_ctx *c, size_t bytes) {
-        ctx = c;
-        d = bj::tmp_alloc(c, bytes, &from_arena);
-        return d ? BJ_OK : bj::fail(c, BJ_ERR_OOM, "argument block allocation failed");
-    }
-    ~DevArgs() {
-        if (d) bj::tmp_free(ctx, d, from_arena);
-    }
-};
 // [first, first + count) must lie inside the LDE domain: the kernels index the twiddle table by first + i
 int check_deep_range(bj_ctx *ctx, const char *who, unsigned log_n, unsigned log_lde, size_t first, size_t count) {
     const unsigned log_full = log_n + log_lde;
@@ -58,10 +44,9 @@ int bj_barycentric_eval_batch(bj_ctx *ctx, const uint64_t *const *h_col_ptrs, un
         if (!h_col_ptrs[c]) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_barycentric_eval_batch: null column %u", c);
     const size_t n = (size_t)1 << log_n;
     const unsigned nb = bj::barycentric_num_blocks(n);
-    DevArgs args;
-    size_t bytes = (size_t)n_cols * sizeof(u64 *) + ((size_t)n_cols * nb * 2 + (size_t)n_cols * 2) * sizeof(u64);
-    if (int rc = args.alloc(ctx, bytes)) return rc;
-    const u64 **d_ptrs = (const u64 **)args.d;
+    bj::TmpBuf args;   // [pointers][partial sums per block][values]
+    if (int rc = args.alloc(ctx, bj::barycentric_arg_words(n_cols, n))) return rc;
+    const u64 **d_ptrs = (const u64 **)args.p;
     u64 *d_partials = (u64 *)(d_ptrs + n_cols);
     u64 *d_out = d_partials + (size_t)n_cols * nb * 2;
     if (int rc = bj::h2d_async(ctx, (void *)d_ptrs, h_col_ptrs, n_cols * sizeof(u64 *))) return rc;
@@ -141,9 +126,9 @@ int combine_monomials(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64
         }
     }
     const unsigned n_cols = (unsigned)ptrs.size();
-    DevArgs args;
-    if (int rc = args.alloc(ctx, n_cols * sizeof(u64 *) + coefs.size() * sizeof(u64))) return rc;
-    const u64 **d_ptrs = (const u64 **)args.d;
+    bj::TmpBuf args;   // [pointers][F_p^2 coefficients]
+    if (int rc = args.alloc(ctx, bj::column_list_arg_words(n_cols))) return rc;
+    const u64 **d_ptrs = (const u64 **)args.p;
     u64 *d_coefs = (u64 *)(d_ptrs + n_cols);
     if (int rc = bj::h2d_async(ctx, (void *)d_ptrs, ptrs.data(), n_cols * sizeof(u64 *))) return rc;
     if (int rc = bj::h2d_async(ctx, d_coefs, coefs.data(), coefs.size() * sizeof(u64))) return rc;
@@ -185,9 +170,9 @@ int deep_accumulate_range(bj_ctx *ctx, const uint64_t *const *h_src_c0, const ui
         }
     }
     const unsigned n_cols = (unsigned)ptrs.size();
-    DevArgs args;
-    if (int rc = args.alloc(ctx, n_cols * sizeof(u64 *) + coefs.size() * sizeof(u64))) return rc;
-    const u64 **d_ptrs = (const u64 **)args.d;
+    bj::TmpBuf args;   // [pointers][F_p^2 coefficients]
+    if (int rc = args.alloc(ctx, bj::column_list_arg_words(n_cols))) return rc;
+    const u64 **d_ptrs = (const u64 **)args.p;
     u64 *d_coefs = (u64 *)(d_ptrs + n_cols);
     if (int rc = bj::h2d_async(ctx, (void *)d_ptrs, ptrs.data(), n_cols * sizeof(u64 *))) return rc;
     if (int rc = bj::h2d_async(ctx, d_coefs, coefs.data(), coefs.size() * sizeof(u64))) return rc;
@@ -238,9 +223,9 @@ int deep_accumulate_multi(bj_ctx *ctx, const DeepSetHost *sets, unsigned n_sets,
         a[t].at0 = gl::canon(S.at2[0]);
         a[t].at1 = gl::canon(S.at2[1]);
     }
-    DevArgs args;
-    if (int rc = args.alloc(ctx, ptrs.size() * sizeof(u64 *) + coefs.size() * sizeof(u64))) return rc;
-    const u64 **d_ptrs = (const u64 **)args.d;
+    bj::TmpBuf args;   // [pointers][F_p^2 coefficients]
+    if (int rc = args.alloc(ctx, bj::column_list_arg_words(ptrs.size()))) return rc;
+    const u64 **d_ptrs = (const u64 **)args.p;
     u64 *d_coefs = (u64 *)(d_ptrs + ptrs.size());
     if (int rc = bj::h2d_async(ctx, (void *)d_ptrs, ptrs.data(), ptrs.size() * sizeof(u64 *))) return rc;
     if (int rc = bj::h2d_async(ctx, d_coefs, coefs.data(), coefs.size() * sizeof(u64))) return rc;

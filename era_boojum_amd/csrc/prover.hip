@@ -14,7 +14,9 @@
 #include "gate_program.h"
 #include "setup.h"
 #include "witness_plan.h"
+#include "workspace_plan.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <deque>
@@ -38,17 +40,6 @@ struct bj_proof {
 };
 
 namespace {
-
-
-// workspace buffer carved out of the context's arena (no hipMalloc/hipFree inside a proof)
-struct ArenaBuf {
-    u64 *p = nullptr;
-    int alloc(bj_ctx *ctx, size_t elems) {
-        p = bj::arena_alloc(ctx, elems ? elems : 1);
-        if (!p) return bj::fail(ctx, BJ_ERR_OOM, "workspace reservation too small for %zu MiB", elems * 8 >> 20);
-        return BJ_OK;
-    }
-};
 
 gl::e2 e2c(const u64 *p) { return {gl::canon(p[0]), gl::canon(p[1])}; }
 
@@ -110,10 +101,10 @@ int all_gather(bj_ctx *ctx, const Shard &sh, const u64 *d_send, u64 *d_recv, siz
 int all_gather_columns(bj_ctx *ctx, const Shard &sh, const u64 *d_send, u64 *d_dst, unsigned parts, size_t part_len) {
     if (sh.world == 1) return all_gather(ctx, sh, d_send, d_dst, (size_t)parts * part_len);
     const size_t per = (size_t)parts * part_len;
-    bool from_arena = false;
-    u64 *tmp = (u64 *)tmp_alloc(ctx, per * sh.world * 8, &from_arena);
-    if (!tmp) return fail(ctx, BJ_ERR_OOM, "all_gather_columns: staging allocation failed");
-    int rc = all_gather(ctx, sh, d_send, tmp, per);
+    TmpBuf staging;
+    if (int rc = staging.alloc(ctx, gather_columns_staging_words(sh.world, parts, part_len))) return rc;
+    const u64 *tmp = staging.p;
+    int rc = all_gather(ctx, sh, d_send, staging.p, per);
     if (!rc) {
         // tmp[r][p][part_len] -> dst[p][r][part_len]: for each rank one strided 2-D copy
         for (unsigned r = 0; r < sh.world && !rc; r++)
@@ -122,7 +113,6 @@ int all_gather_columns(bj_ctx *ctx, const Shard &sh, const u64 *d_send, u64 *d_d
                 rc = fail(ctx, BJ_ERR_HIP, "all_gather_columns: device copy failed");
         (void)hipStreamSynchronize(ctx->stream);
     }
-    tmp_free(ctx, tmp, from_arena);
     return rc;
 }
 
@@ -213,7 +203,7 @@ struct Queries;
 
 // A proof in the making: what lives from one round to the next, and the rounds in the order prove_impl runs them.  Each says
 // above its definition what it reads from this object and what it adds to it.  Arena buffers are never given back (bump
-// allocator): the order of the alloc calls IS the layout of the workspace.
+// allocator): the order of the takes IS the layout of the workspace, and `plan` (workspace_plan.h) is that order written down.
 struct Proving {
     bj_ctx *ctx;
     const bj_setup *S;
@@ -224,6 +214,7 @@ struct Proving {
     const bj::ProofLayout &L;   // proof_layout.h: the columns of every oracle, the opening order, the proof's words
     bool has_lookup;
     bool count_mult;         // no multiplicity column was supplied: round 1 counts it (count_multiplicities)
+    bool absorb;             // host witness: the leaves absorb every column group as it lands (witness_from_host)
     unsigned log_n, V, q;
     // N / Ln: leaves / column stride HELD BY THIS GPU (the whole domain on one GPU); Q: points of the quotient domain
     size_t n, N, Q, Ln, I0, capl;
@@ -236,15 +227,17 @@ struct Proving {
     bj_proof *proof = nullptr;
     bj::host::Transcript tr;
     u64 beta[2], gamma[2], lbeta[2] = {0, 0}, lgamma[2] = {0, 0}, z[2], zo[2];   // challenges of rounds 2 and 4 (zo = z * omega)
-    ArenaBuf wit_lde, wit_tree, mono, mono_s2;   // mono: witness monomials, mono_s2: stage-2 monomials (both kept for DEEP)
-    ArenaBuf s2_lde, s2_tree, T, q_lde, q_tree, deep;
+    bj::WorkspacePlan plan;
+    bj::TmpBuf wit_lde, wit_tree, mono, mono_s2;   // mono: witness monomials, mono_s2: stage-2 monomials (both kept for DEEP)
+    bj::TmpBuf s2_lde, s2_tree, T, q_lde, q_tree, deep;
     const u64 *Tm = nullptr;   // the 2 q chunks of n coefficients each of the quotient, in the monomial layout of this trace length
     std::vector<u64> wit_cap, s2_cap, q_cap;
     // base columns whose coset 0 is evaluated, in the order of prover.rs:1550-1683; msrcs: the monomial forms of the same
     // polynomials, same order (for the DEEP numerator).  zsrc / mz: z(x), opened at z * omega; lsrc / ml: the lookup sums, at 0
     std::vector<Src> srcs, msrcs, zsrc, mz, lsrc, ml;
     std::vector<u64> vz, vzo, v0;   // the opened values
-    uint32_t sched[32];             // FRI folding schedule
+    uint32_t sched[32];             // FRI folding schedule (bj_fri_schedule, before the workspace is reserved)
+    uint32_t new_pow = 0;           // proof-of-work bits left once the query count is rounded
     size_t sched_len = 0, num_queries = 0, final_degree = 0;
     bj_fri *fri = nullptr;
     u64 pow_challenge = 0;
@@ -258,6 +251,7 @@ struct Proving {
         Qe = Q / sh.world;
         VW = L.multiplicity();
         nW = L.widths[bj::ORACLE_WITNESS], nS2 = L.widths[bj::ORACLE_STAGE2];
+        absorb = hw && (S->hasher == BJ_HASHER_POSEIDON2 || S->hasher == BJ_HASHER_POSEIDON) && !bj::env().prove_no_absorb && !hw->no_absorb;
     }
     int reserve_workspace();
     int check_public_inputs();
@@ -283,7 +277,6 @@ struct Proving {
     int serialise(const Queries &qr);
     void read_back_stats();
 
-    size_t tree_elems() const { return bj_merkle_tree_digests(N, capl) * 4; }   // words of a tree over this GPU's leaves
     void challenge2(u64 *o) {
         o[0] = tr.challenge();
         o[1] = tr.challenge();
@@ -309,27 +302,17 @@ std::vector<u64> e2_powers(const u64 *x, size_t count) {
     return out;
 }
 
-// Reads the sizes.  Resets the context's arena to one reservation for every buffer of the proof; adds proof->ws_reserved.
+// Reads the setup's parameters and the sizes.  Adds the FRI schedule and the workspace plan; resets the context's arena to one
+// reservation for every buffer of the proof (a context that has seen a larger proof keeps its size); adds proof->ws_reserved.
 int Proving::reserve_workspace() {
-    // sizes mirror the allocations; +1 MiB slack per buffer for alignment
-    const size_t tree_elems = this->tree_elems(), slack = (size_t)1 << 17;
-    size_t need = (size_t)nW * Ln + (size_t)(nW + nS2) * n + tree_elems                        // wit_lde, monomials, wit_tree
-                + (size_t)nS2 * n + ((size_t)2 * L.n_chunks * n + 2 * ((n + 1023) / 1024) + 16)   // s2_nat, tmp
-                + (size_t)nS2 * Ln + tree_elems                                                // s2_lde, s2_tree
-                + 2 * Q + (sh.world > 1 ? 2 * Ln * (sh.world + 1) : 0) + (size_t)2 * q * N + tree_elems + 4 * n + 4 * N                       // T (+ gather staging), q_lde, q_tree, w, deep
-                + (size_t)4096 * 1024 * (sh.world > 1 ? 1 + sh.world : 1) + 64 * slack        // alphas, query gathers
-                + 4 * N + (N * sh.world) / 2                                                   // FRI layers + trees, DEEP argument blocks
-                + (sh.world > 1 ? 10 * n : 0)                                                  // sharded DEEP numerators: slices + gather staging
-                + 4 * N                                                                        // host witness hashed in groups: the leaves' capacity words — reserved whichever
-                                                                                               // entry point the proof came through: a context that alternates between bj_prove and
-                                                                                               // bj_prove_dev (the lanes of bj_prove_async do) must not re-allocate its arena (1.8 s for 64 GB)
-                + (size_t)2 * N * (1 + S->pub_cols.size())                                     // DEEP: one extended numerator per large opening set beyond the first
-                + (S->tiled ? 2 * Q : 0)                                                       // the quotient's chunks once more, in the tiled layout
-                + (count_mult && !d_multiplicities ? n + slack : 0);                           // the counted multiplicity column of a resident witness
-    // `need` is an upper bound by construction of the list above — checked on every proof the test suite makes (the binding
-    // raises when a proof had to take an overflow slab) — and a context that has seen a larger proof keeps its size
-    if (need < ctx->arena_learned) need = ctx->arena_learned;
-    if (int rc = bj::arena_reset(ctx, need)) return rc;
+    if (int rc = bj_fri_schedule(S->security, S->cap_size, S->pow_bits, S->log_fri, log_n, &new_pow, &num_queries, sched, &sched_len, &final_degree))
+        return bj::fail(ctx, rc, "bj_prove: compute_fri_schedule failed");
+    const unsigned alpha_terms = L.n_lookup_terms + S->gates.n_spec_terms + S->gates.n_general_terms + 1 + L.n_chunks;
+    plan = bj::workspace_plan(bj::workspace_shape(L, sh.world, S->tiled, alpha_terms, S->pub_cols.data(), S->pub_rows.data(), S->pub_cols.size(),
+                                                  count_mult && !d_multiplicities,
+                                                  !hw ? bj::WS_HOST_NONE : absorb ? bj::WS_HOST_ABSORBING : bj::WS_HOST_NOT_ABSORBING, new_pow != 0,
+                                                  sched, sched_len, num_queries));
+    if (int rc = bj::arena_reset(ctx, std::max(plan.total(), ctx->arena_learned))) return rc;
     proof->ws_reserved = ctx->arena_elems * 8;
     return BJ_OK;
 }
@@ -377,15 +360,13 @@ int Proving::witness_from_host(bool *hashed_in_groups) {
     // kernel — runs under the transfer of the later groups instead of after the last one has landed.
     unsigned G = hw->group;
     if ((nW + G - 1) / G > 64) G = (nW + 63) / 64;
-    const bool algebraic = ctx->hasher == BJ_HASHER_POSEIDON2 || ctx->hasher == BJ_HASHER_POSEIDON;
-    const bool absorb = algebraic && !bj::env().prove_no_absorb && !hw->no_absorb;
     if (absorb) G = (G + 7) / 8 * 8;
     const std::vector<bj::WitnessGroup> plan = bj::host_witness_plan(nW, G, absorb, bj::env().prove_uniform_groups);
     const unsigned n_groups = (unsigned)plan.size();
-    ArenaBuf capacity;
+    bj::TmpBuf capacity;
     if (absorb) {
-        if ((rc = wit_tree.alloc(ctx, tree_elems()))) return rc;
-        if ((rc = capacity.alloc(ctx, 4 * N))) return rc;
+        if ((rc = wit_tree.take(ctx, bj::WS_WIT_TREE))) return rc;
+        if ((rc = capacity.take(ctx, bj::WS_CAPACITY))) return rc;
         *hashed_in_groups = true;
     }
     for (unsigned g = 0; g < n_groups; g++) {
@@ -425,8 +406,8 @@ int Proving::witness_from_host(bool *hashed_in_groups) {
 // Reads d_variables; sets d_multiplicities where it was nullptr.
 int Proving::count_multiplicities() {
     if (!d_multiplicities) {
-        ArenaBuf col;
-        if (int rc = col.alloc(ctx, n)) return rc;
+        bj::TmpBuf col;
+        if (int rc = col.take(ctx, bj::WS_MULTIPLICITY)) return rc;
         d_multiplicities = col.p;
     }
     return bj::setup_lookup_multiplicities(ctx, hw ? "bj_prove" : "bj_prove_dev", S, d_variables, const_cast<u64 *>(d_multiplicities));
@@ -439,9 +420,9 @@ int Proving::round1_witness() {
     int rc = BJ_OK;
     bool hashed_in_groups = false;               // bj_prove: the witness leaves were absorbed group by group under the transfer
     if (count_mult && !hw && (rc = count_multiplicities())) return rc;   // before any proof work
-    if ((rc = wit_lde.alloc(ctx, (size_t)nW * Ln))) return rc;
-    if ((rc = mono.alloc(ctx, (size_t)nW * n))) return rc;
-    if ((rc = mono_s2.alloc(ctx, (size_t)nS2 * n))) return rc;
+    if ((rc = wit_lde.take(ctx, bj::WS_WIT_LDE))) return rc;
+    if ((rc = mono.take(ctx, bj::WS_MONO))) return rc;
+    if ((rc = mono_s2.take(ctx, bj::WS_MONO_S2))) return rc;
     if (!hw) {
         rc = intt_cols(d_variables, mono.p, VW);
         if (!rc && has_lookup) rc = intt_cols(d_multiplicities, mono.p + (size_t)L.multiplicity() * n, 1);
@@ -450,7 +431,7 @@ int Proving::round1_witness() {
         rc = witness_from_host(&hashed_in_groups);
     }
     if (rc) return rc;
-    if (!hashed_in_groups && (rc = wit_tree.alloc(ctx, tree_elems()))) return rc;
+    if (!hashed_in_groups && (rc = wit_tree.take(ctx, bj::WS_WIT_TREE))) return rc;
     // witness tree; the leaf kernel (the dominant kernel of a proof) is bracketed by HIP events on the launch stream (with a
     // host witness hashed in groups the bracket spans the groups' transforms too: the roofline figure comes from bj_prove_dev)
     if (!hashed_in_groups) {
@@ -475,9 +456,9 @@ int Proving::round2_stage2() {
     int rc = BJ_OK;
     challenge2(beta);
     challenge2(gamma);
-    ArenaBuf s2_nat, tmp;
-    if ((rc = s2_nat.alloc(ctx, (size_t)nS2 * n))) return rc;
-    if ((rc = tmp.alloc(ctx, (size_t)2 * L.n_chunks * n + 2 * ((n + 1023) / 1024) + 16))) return rc;
+    bj::TmpBuf s2_nat, tmp;
+    if ((rc = s2_nat.take(ctx, bj::WS_S2_NAT))) return rc;
+    if ((rc = tmp.take(ctx, bj::WS_S2_SCRATCH))) return rc;
     bj::launch_copy_perm_stage2(d_variables, n, S->d_nat + (size_t)L.sigma(0) * n, n, S->d_non_res, V, q, log_n, ctx->tw_fwd, beta, gamma, tmp.p,
                                 s2_nat.p + (size_t)L.z() * n, s2_nat.p + (size_t)L.partial(0) * n, st, S->small_non_residues);
     if (has_lookup) {
@@ -488,11 +469,11 @@ int Proving::round2_stage2() {
                                 S->d_nat + (size_t)L.table(0) * n, n, d_multiplicities, S->lookup_reps, S->lookup_w, log_n, lbeta, lgamma, dA, dB, st);
     }
     BJ_CHECK_LAUNCH(ctx);
-    if ((rc = s2_lde.alloc(ctx, (size_t)nS2 * Ln))) return rc;
+    if ((rc = s2_lde.take(ctx, bj::WS_S2_LDE))) return rc;
     rc = intt_cols(s2_nat.p, mono_s2.p, nS2);
     if (!rc) rc = lde_cols(mono_s2.p, s2_lde.p, Ln, nS2, S->log_L, S->c0, S->cl);
     if (rc) return rc;
-    if ((rc = s2_tree.alloc(ctx, tree_elems()))) return rc;
+    if ((rc = s2_tree.take(ctx, bj::WS_S2_TREE))) return rc;
     rc = bj_merkle_tree_build(ctx, s2_lde.p, Ln, nS2, N, capl, s2_tree.p);
     if (!rc) rc = bj::gather_cap(ctx, sh, s2_tree.p, N, S->cap_size, s2_cap.data());
     if (rc) return rc;
@@ -513,8 +494,8 @@ int Proving::exchange_residues(u64 *Tl) {
     int rc = bj_bitreverse_batch(ctx, Tl, Tl, log_E, 2, Qe);
     if (!rc) rc = bj_intt_batch(ctx, Tl, Tl, log_E, 2, Qe, rank_shift(sh.rank));
     if (rc) return rc;
-    ArenaBuf all;
-    if ((rc = all.alloc(ctx, (size_t)2 * Q))) return rc;
+    bj::TmpBuf all;
+    if ((rc = all.take(ctx, bj::WS_RESIDUES))) return rc;
     if ((rc = bj::all_gather(ctx, sh, Tl, all.p, 2 * Qe))) return rc;
     u64 a[8];
     for (unsigned r = 0; r < sh.world; r++) a[r] = gl::pow(rank_shift(r), Qe);
@@ -536,15 +517,13 @@ int Proving::round3_quotient() {
     const unsigned n_gate_terms = S->gates.n_general_terms, n_spec_terms = S->gates.n_spec_terms;   // lookup | specialized | general | L1 | copy-permutation (prover.rs:599-625)
     const unsigned total_terms = n_lookup_terms + n_spec_terms + n_gate_terms + 1 + L.n_chunks;
     const std::vector<u64> alphas = e2_powers(alpha, total_terms);
-    ArenaBuf d_alphas;
-    if ((rc = d_alphas.alloc(ctx, alphas.size()))) return rc;
+    bj::TmpBuf d_alphas, T_local;
+    if ((rc = d_alphas.take(ctx, bj::WS_ALPHAS, alphas.size()))) return rc;
     if ((rc = bj::h2d_async(ctx, d_alphas.p, alphas.data(), alphas.size() * 8))) return rc;
-    if ((rc = T.alloc(ctx, 2 * Q))) return rc;
-    ArenaBuf Tl;   // this rank's evaluations [2][Qe] (T itself when nothing has to be gathered)
-    if (q_local)
-        Tl.p = T.p;
-    else if ((rc = Tl.alloc(ctx, 2 * Qe))) return rc;
-    u64 *t0 = Tl.p, *t1 = Tl.p + Qe;
+    if ((rc = T.take(ctx, bj::WS_T))) return rc;
+    if (!q_local && (rc = T_local.take(ctx, bj::WS_T_LOCAL))) return rc;
+    u64 *const Tl = q_local ? T.p : T_local.p;   // this rank's evaluations [2][Qe] (T itself when nothing has to be gathered)
+    u64 *t0 = Tl, *t1 = Tl + Qe;
     const u64 *a_lookup = d_alphas.p, *a_spec = d_alphas.p + 2 * n_lookup_terms, *a_gates = a_spec + 2 * n_spec_terms,
               *a_l1 = a_gates + 2 * n_gate_terms;
     const u64 *d_sig_lde = S->d_lde + (size_t)L.sigma(0) * Ln, *d_con_lde = S->d_lde + (size_t)L.constant(0) * Ln;
@@ -572,7 +551,7 @@ int Proving::round3_quotient() {
         rc = bj_bitreverse_batch(ctx, T.p, T.p, log_Q, 2, Q);
         if (!rc) rc = bj_intt_batch(ctx, T.p, T.p, log_Q, 2, Q, gl::GEN);
     } else {
-        rc = exchange_residues(Tl.p);
+        rc = exchange_residues(Tl);
     }
     u64 top[2] = {1, 1};
     if (!rc) rc = bj_memcpy_d2h(ctx, &top[0], T.p + Q - 1, 8);
@@ -582,17 +561,17 @@ int Proving::round3_quotient() {
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove: constraint system is not satisfied (quotient is not a polynomial; prover.rs:1425-1438)");
     Tm = T.p;
     if (S->tiled) {   // the chunks come out of a transform of another size: one re-layout pass over 2 q n words
-        ArenaBuf Tt;
-        if ((rc = Tt.alloc(ctx, 2 * Q))) return rc;
+        bj::TmpBuf Tt;
+        if ((rc = Tt.take(ctx, bj::WS_T_TILED))) return rc;
         bj::launch_tiled_permute(T.p, Tt.p, 2 * q, n, n, true, st);
         BJ_CHECK_LAUNCH(ctx);
         Tm = Tt.p;
     }
-    if ((rc = q_lde.alloc(ctx, (size_t)2 * q * N))) return rc;
+    if ((rc = q_lde.take(ctx, bj::WS_Q_LDE))) return rc;
     for (unsigned e = 0; e < 2 && !rc; e++)   // chunk j of c_e -> column 2j+e (prover.rs:1445-1467)
         rc = lde_cols(Tm + (size_t)e * Q, q_lde.p + (size_t)e * N, 2 * N, q, S->log_fri, sh.world > 1 ? S->c0 : 0, sh.world > 1 ? S->cl : S->fri_lde);
     if (rc) return rc;
-    if ((rc = q_tree.alloc(ctx, tree_elems()))) return rc;
+    if ((rc = q_tree.take(ctx, bj::WS_Q_TREE))) return rc;
     rc = bj_merkle_tree_build(ctx, q_lde.p, N, 2 * q, N, capl, q_tree.p);
     if (!rc) rc = bj::gather_cap(ctx, sh, q_tree.p, N, S->cap_size, q_cap.data());
     if (rc) return rc;
@@ -677,8 +656,8 @@ int Proving::evaluate_at(u64 *w, u64 open_shift, const std::vector<Src> &ss, con
 int Proving::round4_openings() {
     int rc = BJ_OK;
     challenge2(z);
-    ArenaBuf w;
-    if ((rc = w.alloc(ctx, 2 * n))) return rc;
+    bj::TmpBuf w;
+    if ((rc = w.take(ctx, bj::WS_BARY_W))) return rc;
     list_opened_columns();
     // every rank evaluates from ITS first coset (shift 7*w^bitrev(c0)): the polynomials have degree < n, so the value
     // is the same field element whichever coset it is interpolated from — no exchange, identical transcripts
@@ -713,7 +692,7 @@ struct PendingDeep {
 struct DeepSets {
     std::vector<u64> chs;   // powers of the DEEP challenge, one per opened polynomial over all sets
     size_t choff = 0;       // challenges handed out so far
-    ArenaBuf num_mono, num_slice;
+    bj::TmpBuf num_mono, num_slice;
     std::deque<PendingDeep> pending;
     bool written = false;   // deep holds the sets flushed so far
 };
@@ -746,7 +725,7 @@ int Proving::deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector
     std::vector<const u64 *> p0, p1;
     size_t n_base = 0;
     for (auto &m : ms) n_base += m.c1 ? 2 : 1;
-    if (n_base < 16) {   // a handful of columns: streaming them over the FRI domain is cheaper than an extra LDE pass
+    if (n_base < bj::WS_LARGE_SET) {   // a handful of columns: streaming them over the FRI domain is cheaper than an extra LDE pass
         PendingDeep pd;
         for (auto &l : ls) {
             pd.p0.push_back(l.c0);
@@ -760,8 +739,8 @@ int Proving::deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector
         D.choff += ls.size();
         return BJ_OK;
     }
-    ArenaBuf num_lde;   // this set's extended numerator: alive until the sets are flushed
-    if (int ra = num_lde.alloc(ctx, 2 * N)) return ra;
+    bj::TmpBuf num_lde;   // this set's extended numerator: alive until the sets are flushed
+    if (int ra = num_lde.take(ctx, bj::WS_NUM_LDE)) return ra;
     for (auto &m : ms) {
         p0.push_back(m.c0);
         p1.push_back(m.c1);
@@ -811,9 +790,9 @@ int Proving::round5a_deep() {
     for (auto &set : sets) total_ch += set.polys.size();
     DeepSets D;
     D.chs = e2_powers(cch, total_ch);
-    if ((rc = deep.alloc(ctx, 2 * N))) return rc;
-    if ((rc = D.num_mono.alloc(ctx, 2 * n))) return rc;
-    if (sh.world > 1 && (rc = D.num_slice.alloc(ctx, 2 * n / sh.world + 16))) return rc;
+    if ((rc = deep.take(ctx, bj::WS_DEEP))) return rc;
+    if ((rc = D.num_mono.take(ctx, bj::WS_NUM_MONO))) return rc;
+    if (sh.world > 1 && (rc = D.num_slice.take(ctx, bj::WS_NUM_SLICE))) return rc;
     const u64 zero2[2] = {0, 0};
     for (auto &set : sets) {   // in the order the challenges are handed out
         if (set.point == bj::OPEN_AT_Z) rc = deep_set(D, srcs, msrcs, vz.data(), z);
@@ -837,13 +816,10 @@ int Proving::round5a_deep() {
 }
 
 // ---------------- round 5b: FRI (prover.rs:2075-2105) ----------------
-// Reads deep.  Adds the schedule (sched, sched_len, num_queries, final_degree), the FRI object (its caps went through the
-// transcript) and pow_challenge, absorbed as well.
+// Reads deep and the schedule (sched, sched_len, new_pow).  Adds the FRI object (its caps went through the transcript) and
+// pow_challenge, absorbed as well.
 int Proving::round5b_fri() {
     int rc = BJ_OK;
-    uint32_t new_pow = 0;
-    if ((rc = bj_fri_schedule(S->security, S->cap_size, S->pow_bits, S->log_fri, log_n, &new_pow, &num_queries, sched, &sched_len, &final_degree)))
-        return bj::fail(ctx, rc, "bj_prove: compute_fri_schedule failed");
     bj_transcript trw;   // bj_fri_prove drives a bj_transcript; hand our state over and take it back
     trw.t = tr;
     rc = bj::fri_prove_sharded(ctx, sh, deep.p, deep.p + N, log_n, S->log_fri, sched, sched_len, S->cap_size, &trw, &fri);
@@ -853,8 +829,8 @@ int Proving::round5b_fri() {
     if (new_pow) {
         u64 seed[5];   // 256 / CHAR_BITS = 4, "+1 if not a multiple of CHAR_BITS" -> 5 challenges = 40 seed bytes
         for (int i = 0; i < 5; i++) seed[i] = gl::canon(tr.challenge());
-        ArenaBuf d_res;
-        if ((rc = d_res.alloc(ctx, 8))) return rc;
+        bj::TmpBuf d_res;
+        if ((rc = d_res.take(ctx, bj::WS_POW))) return rc;
         const u64 none = ~(u64)0, batch = (u64)1 << 24;
         u64 found = none;
         for (u64 base = 0; found == none; base += batch) {   // batches in order + minimum inside a batch = the smallest nonce,
@@ -891,12 +867,12 @@ int Proving::gather_base_queries(Queries &qr) {
     const size_t strides[4] = {Ln, Ln, N, Ln};
     const u64 *trees[4] = {wit_tree.p, s2_tree.p, q_tree.p, S->d_tree};
     int rc = BJ_OK;
-    ArenaBuf d_idx, d_g;
+    bj::TmpBuf d_idx, d_g;
     size_t per_query = 0;
     for (int o = 0; o < 4; o++) per_query += widths[o] + (size_t)depth * 4;
     const size_t G = qr.block = per_query * num_queries;
-    if ((rc = d_idx.alloc(ctx, num_queries))) return rc;
-    if ((rc = d_g.alloc(ctx, G))) return rc;
+    if ((rc = d_idx.take(ctx, bj::WS_QUERY_IDX, num_queries))) return rc;
+    if ((rc = d_g.take(ctx, bj::WS_QUERY_BLOCK, G))) return rc;
     {
         std::vector<u64> loc(num_queries);
         for (size_t i = 0; i < num_queries; i++) loc[i] = qr.idxs[i] % N;
@@ -912,9 +888,9 @@ int Proving::gather_base_queries(Queries &qr) {
     }
     BJ_CHECK_LAUNCH(ctx);
     const u64 *src = d_g.p;
-    ArenaBuf all;
+    bj::TmpBuf all;
     if (W > 1) {
-        if ((rc = all.alloc(ctx, G * W))) return rc;
+        if ((rc = all.take(ctx, bj::WS_QUERY_ALL, G * W))) return rc;
         if ((rc = bj::all_gather(ctx, sh, d_g.p, all.p, G))) return rc;
         src = all.p;
     }
@@ -929,8 +905,8 @@ int Proving::gather_fri_queries(Queries &qr) {
     const std::vector<u64> &idxs = qr.idxs;
     int rc = BJ_OK;
     qr.fri_leaves.resize(sched_len), qr.fri_paths.resize(sched_len), qr.fri_depth.resize(sched_len);
-    ArenaBuf d_li, d_fo;
-    if ((rc = d_li.alloc(ctx, num_queries))) return rc;
+    bj::TmpBuf d_li, d_fo;
+    if ((rc = d_li.take(ctx, bj::WS_FRI_QUERY_IDX, num_queries))) return rc;
     size_t max_out = 0;
     for (size_t i = 0; i < sched_len; i++) {
         const bj_fri::Oracle &o = fri->oracles[i];
@@ -938,7 +914,7 @@ int Proving::gather_fri_queries(Queries &qr) {
         size_t need = ((size_t)2 << o.log_e) + (size_t)qr.fri_depth[i] * 4;
         if (need > max_out) max_out = need;
     }
-    if ((rc = d_fo.alloc(ctx, max_out * num_queries * (W + 1)))) return rc;
+    if ((rc = d_fo.take(ctx, bj::WS_FRI_QUERY_BLOCK, max_out * num_queries * (W + 1)))) return rc;
     std::vector<u64> li(num_queries), host_all;
     unsigned shift = 0;
     for (size_t i = 0; i < sched_len; i++) {
@@ -1058,7 +1034,10 @@ void Proving::read_back_stats() {
     }
     proof->ws_high_water = ctx->arena_high_water * 8;
     proof->ws_overflow_slabs = ctx->arena_slabs.size();
-    if (ctx->arena_high_water + ((size_t)1 << 17) > ctx->arena_learned) ctx->arena_learned = ctx->arena_high_water + ((size_t)1 << 17);
+    // the context learns from a proof that outgrew its reservation; one that stayed inside it (every proof whose plan holds: the
+    // reservation of a single-GPU proof IS its high-water mark) leaves the arena as it is, so the next proof re-allocates nothing
+    if (proof->ws_overflow_slabs && ctx->arena_high_water + ((size_t)1 << 17) > ctx->arena_learned)
+        ctx->arena_learned = ctx->arena_high_water + ((size_t)1 << 17);
 }
 
 // Scope guards of a proof.  prove_impl declares them in this order, so they end in the reverse one: the FRI object first,
@@ -1075,14 +1054,19 @@ struct ProofGuard {
 };
 struct InProof {   // temporaries of the ABI calls of the rounds come out of the arena while this is alive
     bj_ctx *c;
-    explicit InProof(bj_ctx *x) : c(x) {
+    InProof(bj_ctx *x, const bj::WorkspacePlan *plan) : c(x) {
         c->in_proof = true;
+        c->ws_plan = plan;
+        c->ws_next = 0;
         c->comm_n = 0;
         c->comm_bytes = 0;
         c->comm_host_ms = 0;
         c->probe_n = 0;
     }
-    ~InProof() { c->in_proof = false; }
+    ~InProof() {
+        c->in_proof = false;
+        c->ws_plan = nullptr;
+    }
 };
 struct CopyDrain {   // bj_prove: whatever way the proof ends, no queued copy may still read the caller's witness afterwards
     bj_ctx *c;
@@ -1108,7 +1092,7 @@ int prove_impl(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, cons
     P.proof = new bj_proof();
     ProofGuard guard{P.proof};
     if ((rc = P.reserve_workspace())) return rc;
-    InProof in_proof(ctx);
+    InProof in_proof(ctx, &P.plan);
     bj::HasherGuard hasher_guard{ctx, ctx->hasher};
     CopyDrain copy_drain{ctx, hw != nullptr};
     ctx->hasher = (int)S->hasher;
@@ -1132,6 +1116,7 @@ int prove_impl(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, cons
     Queries qr;
     if ((rc = P.round6_queries(qr))) return rc;
     if ((rc = P.serialise(qr))) return rc;
+    if ((rc = bj::workspace_all_taken(ctx))) return rc;
     stage_ms[6] = timer.lap();
     P.read_back_stats();
     guard.ok = true;

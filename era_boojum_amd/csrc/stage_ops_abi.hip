@@ -10,25 +10,6 @@
 
 using gl::u64;
 
-namespace {
-struct Tmp {   // short-lived device block; freed after the stream has drained (these are test / plumbing entry points)
-    bj_ctx *ctx;
-    void *p = nullptr;
-    bool arena = false;
-    explicit Tmp(bj_ctx *c) : ctx(c) {}
-    int alloc(size_t bytes) {
-        p = bj::tmp_alloc(ctx, bytes, &arena);
-        return p ? BJ_OK : bj::fail(ctx, BJ_ERR_OOM, "out of device memory (%zu bytes)", bytes);
-    }
-    ~Tmp() {
-        if (p) {
-            (void)hipStreamSynchronize(ctx->stream);
-            bj::tmp_free(ctx, p, arena);
-        }
-    }
-};
-}  // namespace
-
 extern "C" {
 
 int bj_copy_perm_stage2(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, const uint64_t *d_sigmas, size_t sig_stride,
@@ -43,19 +24,19 @@ int bj_copy_perm_stage2(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, 
     const unsigned n_chunks = (num_vars + chunk - 1) / chunk;
     if (n_chunks > 1 && !d_partials) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_copy_perm_stage2: null partial-product buffer");
     if (int rc = bj::ensure_twiddles(ctx, log_n, false)) return rc;
-    Tmp nr(ctx), tmp(ctx), dummy(ctx);
-    if (int rc = nr.alloc(8 * (size_t)num_vars)) return rc;
-    if (int rc = tmp.alloc(8 * ((size_t)2 * n_chunks * n + 2 * ((n + 1023) / 1024) + 16))) return rc;
+    bj::TmpBuf nr(true), tmp(true), dummy(true);   // freed after the stream has drained: these are test / plumbing entry points
+    if (int rc = nr.alloc(ctx, num_vars)) return rc;
+    if (int rc = tmp.alloc(ctx, bj::copy_perm_stage2_scratch_words(n_chunks, n))) return rc;
     u64 *partials = d_partials;
     if (!partials) {   // one chunk: the kernel still wants a valid pointer
-        if (int rc = dummy.alloc(64)) return rc;
-        partials = (u64 *)dummy.p;
+        if (int rc = dummy.alloc(ctx, 8)) return rc;
+        partials = dummy.p;
     }
     if (int rc = bj::h2d_async(ctx, nr.p, h_non_residues, 8 * (size_t)num_vars)) return rc;
     bool small_k = true;
     for (unsigned c = 0; c < num_vars; c++) small_k = small_k && gl::canon(h_non_residues[c]) < ((u64)1 << 32);
-    bj::launch_copy_perm_stage2(d_vars, var_stride, d_sigmas, sig_stride, (const u64 *)nr.p, num_vars, chunk, log_n, ctx->tw_fwd,
-                                h_beta, h_gamma, (u64 *)tmp.p, d_z, partials, ctx->stream, small_k);
+    bj::launch_copy_perm_stage2(d_vars, var_stride, d_sigmas, sig_stride, nr.p, num_vars, chunk, log_n, ctx->tw_fwd,
+                                h_beta, h_gamma, tmp.p, d_z, partials, ctx->stream, small_k);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }
@@ -118,12 +99,12 @@ int bj_quotient_gates(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, un
                 release();
                 return rc;
             }
-    Tmp al(ctx);
-    int rc = al.alloc(16 * (n_terms + 1));
+    bj::TmpBuf al(true);
+    int rc = al.alloc(ctx, 2 * (n_terms + 1));
     if (!rc && n_terms) rc = bj::h2d_async(ctx, al.p, h_alphas, 16 * n_terms);
     if (!rc) {
         bj::launch_general_gates(ctx, L.general.data(), programs.data(), num_gates, d_vars, var_stride, d_consts, const_stride, nullptr,
-                                 (const u64 *)al.p, num_points, d_out0, d_out1, ctx->stream, 0.0);
+                                 al.p, num_points, d_out0, d_out1, ctx->stream, 0.0);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = bj::fail(ctx, BJ_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     }
@@ -142,11 +123,11 @@ int bj_quotient_lookup(bj_ctx *ctx, const uint64_t *d_lookup_vars, size_t var_st
     if (reps == 0 || width == 0 || width > 8) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_lookup: bad geometry (width 1..8)");
     if (var_stride < num_points || table_stride < num_points || stage2_stride < num_points)
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_lookup: column stride below the number of points");
-    Tmp al(ctx);
-    if (int rc = al.alloc(16 * ((size_t)reps + 1))) return rc;
+    bj::TmpBuf al(true);
+    if (int rc = al.alloc(ctx, 2 * ((size_t)reps + 1))) return rc;
     if (int rc = bj::h2d_async(ctx, al.p, h_alphas, 16 * ((size_t)reps + 1))) return rc;
     bj::launch_quotient_lookup(d_lookup_vars, var_stride, d_table_id, d_tables, table_stride, d_multiplicities, d_A, d_B,
-                               stage2_stride, reps, width, h_beta, h_gamma, (const u64 *)al.p, num_points, d_out0, d_out1,
+                               stage2_stride, reps, width, h_beta, h_gamma, al.p, num_points, d_out0, d_out1,
                                ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
@@ -170,15 +151,15 @@ int bj_quotient_copy_perm(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_quotient_copy_perm: column stride below the number of points rounded up to whole cosets");
     if (int rc = bj::ensure_twiddles(ctx, log_n + log_lde, false)) return rc;
     const unsigned n_chunks = (num_vars + chunk - 1) / chunk;
-    Tmp nr(ctx), al(ctx);
-    if (int rc = nr.alloc(8 * (size_t)num_vars)) return rc;
-    if (int rc = al.alloc(16 * ((size_t)n_chunks + 1))) return rc;
+    bj::TmpBuf nr(true), al(true);
+    if (int rc = nr.alloc(ctx, num_vars)) return rc;
+    if (int rc = al.alloc(ctx, 2 * ((size_t)n_chunks + 1))) return rc;
     if (int rc = bj::h2d_async(ctx, nr.p, h_non_residues, 8 * (size_t)num_vars)) return rc;
     if (int rc = bj::h2d_async(ctx, al.p, h_alphas + 2, 16 * (size_t)n_chunks)) return rc;
     bool small_k = true;
     for (unsigned c = 0; c < num_vars; c++) small_k = small_k && gl::canon(h_non_residues[c]) < ((u64)1 << 32);
-    bj::launch_quotient_copy_perm(d_vars, var_stride, d_sigmas, sig_stride, d_stage2, stage2_stride, (const u64 *)nr.p, num_vars,
-                                  chunk, log_n, log_lde, ctx->tw_fwd, h_beta, h_gamma, h_alphas, (const u64 *)al.p, num_points,
+    bj::launch_quotient_copy_perm(d_vars, var_stride, d_sigmas, sig_stride, d_stage2, stage2_stride, nr.p, num_vars,
+                                  chunk, log_n, log_lde, ctx->tw_fwd, h_beta, h_gamma, h_alphas, al.p, num_points,
                                   first_point, nullptr, d_out0, d_out1, ctx->stream, small_k);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;

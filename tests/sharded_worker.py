@@ -1,7 +1,8 @@
 """Worker of tests/test_gpu_sharded_prover.py: one rank of a coset-sharded proof (launched by torch.distributed.run).
 
 Several ranks may share one GPU (backend gloo): the sharding logic is the same, only the transport differs.
-Writes this rank's proof to <out>/proof_<rank>.npy."""
+Writes this rank's proof to <out>/proof_<rank>.npy and what bj_proof_workspace_bytes says of it to <out>/workspace_<rank>.json."""
+import json
 import os
 import sys
 
@@ -40,11 +41,12 @@ def main():
     proof, _ = setup.prove()
     np.save(os.path.join(out_dir, "proof_%d.npy" % rank), proof)
     np.save(os.path.join(out_dir, "cap_%d.npy" % rank), setup.cap())
+    with open(os.path.join(out_dir, "workspace_%d.json" % rank), "w") as f:
+        json.dump(setup.last_workspace, f)
     if rank == 0:
         with open(os.path.join(out_dir, "comm.txt"), "w") as f:
             f.write("%d %d\n" % (comm.calls, comm.bytes))
     if comm is not base:
-        import json
         with open(os.path.join(out_dir, "peer_%d.json" % rank), "w") as f:
             json.dump(comm.stats(), f)
         proof2, _ = setup.prove()          # a second proof reuses the mapped allocations
