@@ -204,14 +204,12 @@ void launch_gate_program(const DevProgram &P, const u64 *d_vars, size_t var_stri
     const dim3 grid((unsigned)((Q + 255) / 256)), block(256);
     const bool no_aot = bj::env().gate_no_aot;
     if (!no_aot && launch_gate_aot(P.fp[0], P.fp[1], a, grid.x, s)) return;   // a build-time generated straight-line kernel
-    // the reference's own capture of the Poseidon2 flattened gate: the hand-written evaluator (quotient mode, one repetition)
-    if (!no_aot && d_alphas && !d_terms && reps == 1 && gate_is_poseidon2_flattened(P.fp[0], P.fp[1])) {
-        launch_quotient_poseidon2_flattened(d_vars, var_stride, d_consts, const_stride, path_len, path, d_alphas, Q, d_out0, d_out1, s);
-        return;
-    }
-    // the same for the Poseidon (v1) flattened gate (csrc/gate_poseidon1.hip)
-    if (!no_aot && d_alphas && !d_terms && reps == 1 && gate_is_poseidon_flattened(P.fp[0], P.fp[1])) {
-        launch_quotient_poseidon_flattened(d_vars, var_stride, d_consts, const_stride, path_len, path, d_alphas, Q, d_out0, d_out1, s);
+    // the reference's own captures of the two flattened Poseidon gates: the hand-written evaluators of gate_poseidon.hip
+    // (quotient mode, one repetition)
+    const int poseidon = gate_is_poseidon2_flattened(P.fp[0], P.fp[1]) ? BJ_GATE_POSEIDON2_FLATTENED
+                         : gate_is_poseidon_flattened(P.fp[0], P.fp[1]) ? BJ_GATE_POSEIDON_FLATTENED : 0;
+    if (!no_aot && d_alphas && !d_terms && reps == 1 && poseidon) {
+        launch_quotient_poseidon_gate(poseidon, d_vars, var_stride, d_consts, const_stride, path_len, path, d_alphas, Q, d_out0, d_out1, s);
         return;
     }
     if (P.jit && launch_jit_gate(P.jit, a, grid.x, s)) return;                // compiled from this very op list at upload

@@ -13,7 +13,7 @@ bool launch_gate_aot(uint64_t fp0, uint64_t fp1, const gpdev::ProgArgs &a, unsig
 bool gate_aot_known(uint64_t fp0, uint64_t fp1);
 bool gate_aot_fusable(uint64_t fp0, uint64_t fp1);   // known AND light enough for the fused sweep
 // the fingerprint of the reference's own capture of Poseidon2FlattenedGate<8,12,4> without witness columns
-// (src/cs/gates/poseidon2.rs:166-391): such a program is run by the hand-written evaluator of gate_poseidon2.hip
+// (src/cs/gates/poseidon2.rs:166-391): such a program is run by the hand-written evaluator of gate_poseidon.hip
 bool gate_is_poseidon2_flattened(uint64_t fp0, uint64_t fp1);
 bool gate_is_poseidon_flattened(uint64_t fp0, uint64_t fp1);
 // a fingerprint hit is believed only with the structural summary recorded at build time for that body (gate_aot.hip)

@@ -6,7 +6,7 @@
 //   BoolsBuffer   src/cs/implementations/transcript.rs:369-417; index split prover.rs:2161-2182
 #pragma once
 #include "gl.h"
-#include "poseidon_rc.inc"
+#include "poseidon_gate_terms.h"
 #include <cstdint>
 #include <vector>
 
@@ -15,26 +15,9 @@ namespace host {
 
 using gl::u64;
 
-inline const u64 *rc_table() {
-    static const u64 RC[BJ_POSEIDON_NUM_RC] = BJ_POSEIDON_RC_TABLE;
-    return RC;
-}
-
-inline void m4(u64 *x) {
-    u64 t0 = gl::add(x[0], x[1]), t1 = gl::add(x[2], x[3]);
-    u64 t2 = gl::add(gl::dbl(x[1]), t1), t3 = gl::add(gl::dbl(x[3]), t0);
-    u64 t4 = gl::add(gl::dbl(gl::dbl(t1)), t3), t5 = gl::add(gl::dbl(gl::dbl(t0)), t2);
-    x[0] = gl::add(t3, t5); x[1] = t5; x[2] = gl::add(t2, t4); x[3] = t4;
-}
-inline void ext_mds(u64 *s) {
-    m4(s); m4(s + 4); m4(s + 8);
-    for (int j = 0; j < 4; j++) {
-        u64 sum = gl::add(gl::add(s[j], s[4 + j]), s[8 + j]);
-        s[j] = gl::add(s[j], sum); s[4 + j] = gl::add(s[4 + j], sum); s[8 + j] = gl::add(s[8 + j], sum);
-    }
-}
+// rc_table(), the external layer, P2_SH and P1_EXPS are those of the gate evaluators (poseidon_gate_terms.h)
+inline void ext_mds(u64 *s) { bj::ext_mds<GateU64>(s); }
 inline void poseidon2_permutation(u64 *s) {
-    static const unsigned SH[12] = {4, 14, 11, 8, 0, 5, 2, 9, 13, 6, 3, 12};
     const u64 *RC = rc_table();
     for (int i = 0; i < 12; i++) s[i] = gl::canon(s[i]);
     ext_mds(s);
@@ -47,7 +30,7 @@ inline void poseidon2_permutation(u64 *s) {
         s[0] = gl::pow7(gl::add(s[0], RC[12 * r]));
         u64 sum = 0;
         for (int k = 0; k < 12; k++) sum = gl::add(sum, s[k]);
-        for (int k = 0; k < 12; k++) s[k] = gl::add(gl::mul_pow2(s[k], SH[k]), sum);
+        for (int k = 0; k < 12; k++) s[k] = gl::add(gl::mul_pow2(s[k], P2_SH[k]), sum);
     }
     for (int i = 0; i < 4; i++, r++) {
         for (int k = 0; k < 12; k++) s[k] = gl::pow7(gl::add(s[k], RC[12 * r + k]));
@@ -61,7 +44,6 @@ inline void poseidon2_permutation(u64 *s) {
 // element 0 (partial), then the circulant MDS with power-of-two entries, here as shift-and-add on 128-bit integers.
 // The reference has no known-answer vector for it: checked against two independent restatements only.
 inline void poseidon1_permutation(u64 *s) {
-    static const unsigned EXPS[12] = {0, 0, 1, 0, 3, 5, 1, 8, 12, 3, 16, 10};
     const u64 *RC = rc_table();
     for (int i = 0; i < 12; i++) s[i] = gl::canon(s[i]);
     for (int r = 0; r < 30; r++) {
@@ -77,7 +59,7 @@ inline void poseidon1_permutation(u64 *s) {
             hi2[k] = hi2[k + 12] = s[k] >> 32;
         }
         for (int d = 0; d < 12; d++) {
-            const unsigned e = EXPS[d];
+            const unsigned e = P1_EXPS[d];
             for (int row = 0; row < 12; row++) {
                 acc_lo[row] += lo2[row + d] << e;
                 acc_hi[row] += hi2[row + d] << e;

@@ -128,13 +128,10 @@ void launch_merkle_paths(const u64 *d_tree, size_t num_leaves, unsigned depth, c
                          u64 *d_out, hipStream_t s);
 void launch_gather_fri_leaves(const u64 *d_c0, const u64 *d_c1, unsigned log_e, const u64 *d_leaf_idx, unsigned n_idx,
                               u64 *d_out, hipStream_t s);
-// gate_poseidon2.hip, gate_poseidon1.hip
-void launch_quotient_poseidon2_flattened(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
-                                         unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q,
-                                         u64 *d_out0, u64 *d_out1, hipStream_t s);
-void launch_quotient_poseidon_flattened(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
-                                        unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q,
-                                        u64 *d_out0, u64 *d_out1, hipStream_t s);
+// gate_poseidon.hip; kind: BJ_GATE_POSEIDON2_FLATTENED or BJ_GATE_POSEIDON_FLATTENED
+void launch_quotient_poseidon_gate(int kind, const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
+                                   unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q, u64 *d_out0,
+                                   u64 *d_out1, hipStream_t s);
 // openings.hip
 void launch_barycentric_weights(u64 *d_w0, u64 *d_w1, const u64 *d_tw_fwd, unsigned log_n, u64 coset, const u64 *at,
                                 hipStream_t s);

@@ -459,12 +459,9 @@ void launch_general_gates(bj_ctx *ctx, const GateShape *gates, const DevProgram 
     bj::probe_end(ctx, pg);
     for (unsigned g = 0; g < n_gates; g++) {
         const GateShape &G = gates[g];
-        if (G.kind == BJ_GATE_POSEIDON2_FLATTENED)
-            launch_quotient_poseidon2_flattened(d_vars, var_stride, d_consts, const_stride, G.path_len, G.path, d_alphas + 2 * (size_t)G.first_term,
-                                                points, t0, t1, st);
-        if (G.kind == BJ_GATE_POSEIDON_FLATTENED)
-            launch_quotient_poseidon_flattened(d_vars, var_stride, d_consts, const_stride, G.path_len, G.path, d_alphas + 2 * (size_t)G.first_term,
-                                               points, t0, t1, st);
+        if (G.kind == BJ_GATE_POSEIDON2_FLATTENED || G.kind == BJ_GATE_POSEIDON_FLATTENED)
+            launch_quotient_poseidon_gate(G.kind, d_vars, var_stride, d_consts, const_stride, G.path_len, G.path,
+                                          d_alphas + 2 * (size_t)G.first_term, points, t0, t1, st);
     }
     // the op-list gates: one fused launch for those with generated bodies (they all sweep the general-purpose columns)
     launch_gate_programs(gates, programs, n_gates, d_vars, var_stride, d_consts, const_stride, d_alphas, points, t0, t1, st, d_wits);

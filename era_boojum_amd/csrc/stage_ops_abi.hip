@@ -71,7 +71,7 @@ int bj_quotient_gates(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, un
     std::string err;
     for (unsigned g = 0; g < num_gates; g++) {
         const bj_gate_desc &G = gates[g];
-        if (G.kind != BJ_GATE_PROGRAM && G.kind != BJ_GATE_POSEIDON_FLATTENED && (G.kind < BJ_GATE_CONSTANT_ALLOCATOR || G.kind > BJ_GATE_NOP))
+        if (G.kind < BJ_GATE_CONSTANT_ALLOCATOR || G.kind > BJ_GATE_POSEIDON_FLATTENED)
             return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_quotient_gates: gate %u: kind %d is not evaluated here", g, G.kind);
         bj::GateShape shape;
         if (int rc = bj::resolve_gate(G, g, cols, &shape, &err, "reads past the given columns"))

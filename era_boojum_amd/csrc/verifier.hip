@@ -3,7 +3,7 @@
 // Host (tiny data, order-critical, on top of host_transcript.hpp): the transcript replay (:924-1076), the split of the openings
 // (:1150-1206), the challenge powers in the order lookup | specialized | general | L1 | chunks (:1000-1060), the lookup sum
 // (:1236-1256), the quotient identity at z (:1090-1810) — hand-written kinds by formula, op lists interpreted over F_p^2 in the
-// canonical form of gate_canon.h, the two flattened Poseidon gates by the F_p^2 restatement of their evaluators below — the DEEP
+// canonical form of gate_canon.h, the two flattened Poseidon gates by the walks of poseidon_gate_terms.h over F_p^2 — the DEEP
 // and FRI challenges (:1819-1955), the proof of work (:1957-1983), the public-input tuples and the query indices.
 // Device (the verifier's only volume, ~200 dependent permutations per query): verify_openings (verify_open.h, one kernel per tree
 // hasher) walks every Merkle chain; verify_deep_fri_kernel here, one wave per (proof, query), simulates the DEEP value from the four
@@ -16,7 +16,6 @@
 #include "ctx.h"
 #include "gate_program.h"
 #include "host_transcript.hpp"
-#include "poseidon1_fused.inc"
 #include "setup.h"
 #include "verify_open.h"
 
@@ -62,10 +61,6 @@ const e2 ZERO2{0, 0}, ONE2{1, 0};
 e2 e2c(const u64 *p) { return {gl::canon(p[0]), gl::canon(p[1])}; }
 e2 base2(u64 x) { return {gl::canon(x), 0}; }
 bool eq2(e2 a, e2 b) { return a.c0 == b.c0 && a.c1 == b.c1; }
-e2 pow7(e2 x) {
-    const e2 x2 = gl::e2_sqr(x), x3 = gl::e2_mul(x2, x), x4 = gl::e2_sqr(x2);
-    return gl::e2_mul(x4, x3);
-}
 
 unsigned slots_of(const std::vector<bj::DevRelation> &rel) {
     unsigned n = 0;
@@ -115,121 +110,6 @@ bool program_terms(const bj_vk::Program &P, const e2 *var, size_t n_var, const e
         else ok = false;
     }
     return ok;
-}
-
-// ---- the flattened Poseidon gates over F_p^2: the evaluators of gate_poseidon2.hip / gate_poseidon1.hip with every base-field
-// operation replaced by its F_p^2 counterpart (matrix entries and round constants stay base-field scalars); 118 terms each ----
-void ext_mds2(e2 *s) {   // circ(2 M4, M4, M4), M4 = [[5,7,1,3],[4,6,1,1],[1,3,5,7],[1,1,4,6]] (suggested_mds.rs:21-103)
-    auto m4 = [](e2 *x) {
-        auto dbl = [](e2 a) { return gl::e2_add(a, a); };
-        const e2 t0 = gl::e2_add(x[0], x[1]), t1 = gl::e2_add(x[2], x[3]);
-        const e2 t2 = gl::e2_add(dbl(x[1]), t1), t3 = gl::e2_add(dbl(x[3]), t0);
-        const e2 t4 = gl::e2_add(dbl(dbl(t1)), t3), t5 = gl::e2_add(dbl(dbl(t0)), t2);
-        x[0] = gl::e2_add(t3, t5); x[1] = t5; x[2] = gl::e2_add(t2, t4); x[3] = t4;
-    };
-    m4(s); m4(s + 4); m4(s + 8);
-    for (int j = 0; j < 4; j++) {
-        const e2 sum = gl::e2_add(gl::e2_add(s[j], s[4 + j]), s[8 + j]);
-        s[j] = gl::e2_add(s[j], sum); s[4 + j] = gl::e2_add(s[4 + j], sum); s[8 + j] = gl::e2_add(s[8 + j], sum);
-    }
-}
-e2 add_rc(e2 x, u64 rc) { return {gl::add(x.c0, gl::canon(rc)), x.c1}; }
-
-void poseidon2_flattened_terms(const e2 *var, e2 *terms) {   // src/cs/gates/poseidon2.rs:165-410
-    static const unsigned SH[12] = {4, 14, 11, 8, 0, 5, 2, 9, 13, 6, 3, 12};
-    const u64 *RC = bj::host::rc_table();
-    unsigned t = 0, nxt = 24;
-    e2 s[12];
-    for (int i = 0; i < 12; i++) s[i] = var[i];
-    ext_mds2(s);
-    for (int rnd = 0; rnd < 4; rnd++) {
-        if (rnd)
-            for (int i = 0; i < 12; i++) {
-                const e2 v = var[nxt++];
-                terms[t++] = gl::e2_sub(s[i], v);
-                s[i] = v;
-            }
-        for (int i = 0; i < 12; i++) s[i] = pow7(add_rc(s[i], RC[12 * rnd + i]));
-        ext_mds2(s);
-    }
-    for (int rnd = 0; rnd < 22; rnd++) {
-        s[0] = add_rc(s[0], RC[12 * (4 + rnd)]);
-        const e2 v = var[nxt++];
-        terms[t++] = gl::e2_sub(s[0], v);
-        s[0] = pow7(v);
-        e2 tot = s[0];
-        for (int i = 1; i < 12; i++) tot = gl::e2_add(tot, s[i]);
-        for (int i = 0; i < 12; i++) s[i] = gl::e2_add(gl::e2_mul_base(s[i], (u64)1 << SH[i]), tot);
-    }
-    for (int k = 0; k < 4; k++) {
-        for (int i = 0; i < 12; i++) {
-            const e2 v = var[nxt++];
-            terms[t++] = gl::e2_sub(s[i], v);
-            s[i] = v;
-        }
-        for (int i = 0; i < 12; i++) s[i] = pow7(add_rc(s[i], RC[12 * (26 + k) + i]));
-        ext_mds2(s);
-    }
-    for (int i = 0; i < 12; i++) terms[t++] = gl::e2_sub(var[12 + i], s[i]);
-}
-
-void poseidon1_flattened_terms(const e2 *var, e2 *terms) {   // src/cs/gates/poseidon.rs:199-464, fused form (poseidon_goldilocks.rs:374-420)
-    static const unsigned EXPS[12] = {0, 0, 1, 0, 3, 5, 1, 8, 12, 3, 16, 10};
-    static const u64 FUSED_RC[12] = BJ_P1_FUSED_RC, DENSE[144] = BJ_P1_FUSED_DENSE, SBOX_RC[22] = BJ_P1_FUSED_SBOX_RC,
-                     VS[22 * 11] = BJ_P1_FUSED_VS, W_HATS[22 * 11] = BJ_P1_FUSED_W_HATS;
-    const u64 *RC = bj::host::rc_table();
-    unsigned t = 0, nxt = 24;
-    e2 s[12];
-    auto mds = [&]() {   // M[row][col] = 2^EXPS[(col - row) mod 12]
-        e2 out[12];
-        for (int row = 0; row < 12; row++) {
-            e2 acc = ZERO2;
-            for (int col = 0; col < 12; col++) acc = gl::e2_add(acc, gl::e2_mul_base(s[col], (u64)1 << EXPS[(col + 12 - row) % 12]));
-            out[row] = acc;
-        }
-        for (int k = 0; k < 12; k++) s[k] = out[k];
-    };
-    auto reset = [&]() {
-        for (int i = 0; i < 12; i++) {
-            const e2 v = var[nxt++];
-            terms[t++] = gl::e2_sub(s[i], v);
-            s[i] = v;
-        }
-    };
-    for (int i = 0; i < 12; i++) s[i] = var[i];
-    for (int rnd = 0; rnd < 4; rnd++) {
-        if (rnd) reset();
-        for (int i = 0; i < 12; i++) s[i] = pow7(add_rc(s[i], RC[12 * rnd + i]));
-        if (rnd != 3) mds();
-    }
-    {
-        e2 tt[12], out[12];
-        for (int i = 0; i < 12; i++) tt[i] = add_rc(s[i], FUSED_RC[i]);
-        for (int r = 0; r < 12; r++) {
-            e2 acc = ZERO2;
-            for (int k = 0; k < 12; k++) acc = gl::e2_add(acc, gl::e2_mul_base(tt[k], gl::canon(DENSE[12 * r + k])));
-            out[r] = acc;
-        }
-        for (int i = 0; i < 12; i++) s[i] = out[i];
-    }
-    for (int rnd = 0; rnd < 22; rnd++) {
-        const e2 v = var[nxt++];
-        terms[t++] = gl::e2_sub(s[0], v);
-        const e2 s0 = add_rc(pow7(v), SBOX_RC[rnd]);
-        e2 acc = ZERO2;
-        for (int k = 1; k < 12; k++) acc = gl::e2_add(acc, gl::e2_mul_base(s[k], gl::canon(VS[11 * rnd + k - 1])));
-        s[0] = gl::e2_add(acc, s0);
-        for (int k = 1; k < 12; k++) s[k] = gl::e2_add(s[k], gl::e2_mul_base(s0, gl::canon(W_HATS[11 * rnd + k - 1])));
-    }
-    reset();   // round 26: its constants were propagated into the partial rounds
-    for (int i = 0; i < 12; i++) s[i] = pow7(s[i]);
-    mds();
-    for (int r = 27; r < 30; r++) {
-        reset();
-        for (int i = 0; i < 12; i++) s[i] = pow7(add_rc(s[i], RC[12 * r + i]));
-        mds();
-    }
-    for (int i = 0; i < 12; i++) terms[t++] = gl::e2_sub(var[12 + i], s[i]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -582,6 +462,9 @@ e2 general_gate_terms(const bj_vk *K, const ProofView &P, const Openings &O, con
         for (unsigned r = 0; r < g.reps; r++) {
             const size_t vb = (size_t)r * g.var_stride, cb = d + (size_t)r * g.const_stride;
             const e2 *v = var_z + vb;
+            unsigned n_pushed = 0;   // the walks of poseidon_gate_terms.h read variables and hand over their terms in order
+            auto var_at = [&](unsigned k) { return v[k]; };
+            auto push_term = [&](e2 t) { terms[n_pushed++] = t; };
             switch (g.kind) {
                 case BJ_GATE_CONSTANT_ALLOCATOR: terms[0] = gl::e2_sub(v[0], con_z[cb]); break;
                 case BJ_GATE_FMA_NO_CONSTANT:
@@ -593,8 +476,8 @@ e2 general_gate_terms(const bj_vk *K, const ProofView &P, const Openings &O, con
                     terms[0] = gl::e2_sub(s, v[4]);
                     break;
                 }
-                case BJ_GATE_POSEIDON2_FLATTENED: poseidon2_flattened_terms(v, terms.data()); break;
-                case BJ_GATE_POSEIDON_FLATTENED: poseidon1_flattened_terms(v, terms.data()); break;
+                case BJ_GATE_POSEIDON2_FLATTENED: bj::poseidon2_flattened_terms<bj::GateE2>(var_at, push_term); break;
+                case BJ_GATE_POSEIDON_FLATTENED: bj::poseidon1_flattened_terms<bj::GateE2>(var_at, push_term); break;
                 default:   // BJ_GATE_PROGRAM
                     if (vb > K->num_gp_vars || cb > nC || (size_t)r * g.wit_stride > Wc) {
                         *well_formed = false;

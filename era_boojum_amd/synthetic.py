@@ -26,8 +26,8 @@ from .gate_program import EvaluatorContext
 P = F.P
 
 GATE_CONSTANT_ALLOCATOR, GATE_FMA, GATE_REDUCTION4, GATE_NOP = 1, 2, 3, 4
-GATE_POSEIDON2_FLATTENED = 6   # the hand-written evaluator of Poseidon2FlattenedGate (csrc/gate_poseidon2.hip)
-GATE_POSEIDON_FLATTENED = 7    # the hand-written evaluator of PoseidonFlattenedGate, Poseidon v1 (csrc/gate_poseidon1.hip)
+GATE_POSEIDON2_FLATTENED = 6   # the hand-written evaluator of Poseidon2FlattenedGate (csrc/gate_poseidon.hip)
+GATE_POSEIDON_FLATTENED = 7    # the hand-written evaluator of PoseidonFlattenedGate, Poseidon v1 (csrc/gate_poseidon.hip)
 GATE_PROGRAM = 5     # evaluated from an op list (seam S3): GateDesc.program is an era_boojum_amd.gate_program.GateProgram
 
 

@@ -495,7 +495,7 @@ int bj_lookup_multiplicities(bj_ctx *ctx, const uint64_t *d_lookup_vars, size_t 
                              uint64_t *d_multiplicities);
 /* Gate terms of the quotient numerator at num_points LDE points (prover.rs:1031-1080 with buffering_source.rs:133-362 and
  * the selectors of prover.rs:2775-2916): out = sum_g selector_g * sum_t alpha_t * term_t for the hand-written evaluators
- * (kinds 1..4, and BJ_GATE_POSEIDON_FLATTENED over the first 130 columns) and for op lists without witness columns
+ * (kinds 1..4, and the two flattened Poseidon kinds over the first 130 columns) and for op lists without witness columns
  * (BJ_GATE_PROGRAM: the kernel bj_prove would launch for it — generated, hand-written by fingerprint, run-time compiled or
  * interpreted).  h_alphas: one F_p^2 power per (gate, repetition, term) in evaluator order.  OVERWRITES d_out0 / d_out1. */
 int bj_quotient_gates(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, unsigned num_gp_vars, const uint64_t *d_consts,

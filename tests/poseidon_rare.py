@@ -7,7 +7,7 @@ a chosen S-box input, in python integers.
     logs every S-box input.
   * v1 tree leaves and nodes (capacity words 0): round 0 through the rate words (`tree_round0_word`), round 1 by solving one
     row of the MDS for one rate word (`tree_round1_words`).
-  * flattened gates (csrc/gate_poseidon1.hip, gate_poseidon2.hip): every reset variable feeds an S-box, through + RC or
+  * flattened gates (csrc/gate_poseidon.hip): every reset variable feeds an S-box, through + RC or
     directly; round 0 comes from the 12 inputs (+ RC for v1, Poseidon2's external matrix first, then + RC).
 """
 import json

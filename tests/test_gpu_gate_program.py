@@ -283,7 +283,7 @@ def test_circuit_of_the_golden_proofs_class_proves_and_verifies(fri_lde, cap):
 
 
 def test_hand_written_poseidon2_gate_gives_the_same_proof_as_its_op_list():
-    """BJ_GATE_POSEIDON2_FLATTENED (csrc/gate_poseidon2.hip) against the same gate through the op-list interpreter: the two
+    """BJ_GATE_POSEIDON2_FLATTENED (csrc/gate_poseidon.hip) against the same gate through the op-list interpreter: the two
     proofs of the same recursion-class circuit are identical bytes."""
     a = S.recursion_like_circuit(10, seed=9)
     b = S.recursion_like_circuit(10, seed=9, poseidon2_as_op_list=True)

@@ -1,5 +1,5 @@
 """-m gpu: PoseidonFlattenedGate<8, 12, 4, PoseidonGoldilocks>, the Poseidon (v1) round-function gate: the hand-written evaluator
-(csrc/gate_poseidon1.hip, BJ_GATE_POSEIDON_FLATTENED) against the op-list interpreter on arbitrary LDE inputs, and whole proofs of
+(csrc/gate_poseidon.hip, BJ_GATE_POSEIDON_FLATTENED) against the op-list interpreter on arbitrary LDE inputs, and whole proofs of
 the recursion-class circuit with the v1 gate — hand-written kind, op list (build-time routed, interpreter), with witness
 columns — against each other and against the oracle prover, under the default Poseidon2 pairing and the v1 tree hasher."""
 import os

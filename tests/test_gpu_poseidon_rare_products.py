@@ -316,7 +316,7 @@ def test_flattened_gate_at_rare_sbox_products(gate, form, cls):
 
 @pytest.mark.timeout(300)
 def test_hand_written_poseidon2_quotient_equals_the_interpreter_on_random_points():
-    """As test_gpu_poseidon1_gate.py's v1 test, for gate_poseidon2.hip: unsatisfying random LDE inputs (not reduced); the
+    """As test_gpu_poseidon1_gate.py's v1 test, for gate_poseidon.hip: unsatisfying random LDE inputs (not reduced); the
     kernel's selector * sum alpha_t * term_t equals the same sum over the interpreter's raw terms at every point, and those
     terms equal the golden-pinned oracle evaluator at every point."""
     n, path = 1500, [True, False]

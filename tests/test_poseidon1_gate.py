@@ -1,7 +1,7 @@
 """PoseidonFlattenedGate<F, 8, 12, 4, PoseidonGoldilocks> (src/cs/gates/poseidon.rs:12-500), the Poseidon (v1) round-function gate:
 the fused partial-round constants (tools/gen_poseidon1_fused_constants.py) against the plain permutation, the traced evaluator
 (gate_program.evaluate_poseidon_flattened) against a second restatement written here, the synthetic witness fill, and the
-routing of its capture to the hand-written evaluator (csrc/gate_poseidon1.hip) by fingerprint."""
+routing of its capture to the hand-written evaluator (csrc/gate_poseidon.hip) by fingerprint."""
 import ctypes as C
 import random
 
@@ -150,7 +150,7 @@ def test_fingerprint_routes_the_capture_to_the_hand_written_evaluator():
     from era_boojum_amd import gate_codegen as GC
     lib = E.load_library()
     prog = G.poseidon_flattened_program()
-    assert lib.bj_gate_program_generated(C.byref(prog.struct)) == 1                       # -> csrc/gate_poseidon1.hip
+    assert lib.bj_gate_program_generated(C.byref(prog.struct)) == 1                       # -> csrc/gate_poseidon.hip
     assert lib.bj_gate_program_generated(C.byref(G.poseidon_flattened_program(12).struct)) == 0     # witness cells: op list
     assert lib.bj_gate_program_generated(C.byref(G.poseidon_flattened_compact_program().struct)) == 0
     fp = GC.program_fingerprint(prog)

@@ -4,7 +4,7 @@
  * tools/find_rare_mul_vectors.c's; every product is checked against 128-bit integers.  x^7 is taken in two chains:
  *   weak:      poseidon1.hip p1_pow7, mul_weak results passed on unreduced.  x is a residue >= 2^32 - 1, so its only u64
  *              representative is x itself and the device sees exactly that word whatever p1_add_rc did before;
- *   canonical: the flattened gates' pow7 (gate_poseidon1.hip, gate_poseidon2.hip), gl::mul = canon(mul_weak) after every product.
+ *   canonical: the flattened gates' pow7 (gate_poseidon.hip), gl::mul = canon(mul_weak) after every product.
  * Products: 0 = x*x, 1 = x2*x, 2 = x2*x2, 3 = x4*x3.  Class 1 comes from structured inputs (k * 2^48, 2^24, 2^14); class 3 from a
  * search (~2^-33 per product).  Class 1 at x2*x has no known construction: that cell stays empty.
  *   gcc -O3 -fopenmp tools/find_poseidon_sbox_rare.c -o /tmp/find_sbox && /tmp/find_sbox > tests/golden/poseidon_sbox_rare.json */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Derive the fused partial-round constants of Poseidon (v1) over Goldilocks and emit them as a C data table
 (era_boojum_amd/csrc/poseidon1_fused.inc), which the gate trace (gate_program.py) and the hand-written gate evaluator
-(csrc/gate_poseidon1.hip) both read.
+(csrc/gate_poseidon.hip) both read.
 
 The reference computes these tables at compile time (src/implementations/poseidon_goldilocks.rs:620-1010) by rewriting the
 plain round sequence — AddRoundConstants / FullSBox / MulByMDS x 4, AddRoundConstants / PartialSBox / MulByMDSInPartialRound

@@ -2,7 +2,7 @@
 """Quotient launch of the Poseidon (v1) flattened gate (PoseidonFlattenedGate<8,12,4>) on one MI355X: every arm is ONE
 bj_quotient_gates call in quotient mode (selector path of 2, alpha-weighted sum of the 118 terms) over the same --log-points
 points (default 2^22 rows x LDE 8 = 2^25):
-  hand_written     kind BJ_GATE_POSEIDON_FLATTENED (csrc/gate_poseidon1.hip)
+  hand_written     kind BJ_GATE_POSEIDON_FLATTENED (csrc/gate_poseidon.hip)
   capture_routed   the reference's op-list capture as kind BJ_GATE_PROGRAM: its fingerprint selects the same kernel
   hiprtc           gate_program.poseidon_flattened_compact_program() as an op list: the same 118 terms, a fingerprint no table
                    knows, so its kernel is compiled at run time (checked: bj_gate_jit_status counts one more kernel)
