@@ -5,163 +5,22 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 P = (1 << 64) - (1 << 32) + 1
 u64p = C.POINTER(C.c_uint64)
 
-# every symbol include/boojum_hip.h declares (checked by tests/test_abi_symbols.py against the header text)
-_SIGNATURES = {
-    "bj_abi_version": (C.c_int, []),
-    "bj_gate_kind_supported": (C.c_int, [C.c_int]),
-    "bj_env_reload": (None, []),
-    "bj_device_count": (C.c_int, []),
-    "bj_status_string": (C.c_char_p, [C.c_int]),
-    "bj_ctx_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
-    "bj_ctx_destroy": (None, [C.c_void_p]),
-    "bj_ctx_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "bj_last_error": (C.c_char_p, [C.c_void_p]),
-    "bj_sync": (C.c_int, [C.c_void_p]),
-    "bj_malloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
-    "bj_free": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "bj_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
-    "bj_memcpy_d2h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
-    "bj_memcpy_d2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
-    "bj_timer_start": (C.c_int, [C.c_void_p]),
-    "bj_timer_stop_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
-    "bj_ntt_forward_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_size_t, C.c_uint64]),
-    "bj_intt_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_size_t, C.c_uint64]),
-    "bj_lde_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
-    "bj_lde_cosets_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
-    "bj_trace_to_lde_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint, C.c_uint]),
-    "bj_bitreverse_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_size_t]),
-    "bj_monomials_tiled": (C.c_int, [C.c_uint]),
-    "bj_intt_batch_tiled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_size_t]),
-    "bj_lde_cosets_batch_tiled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
-    "bj_tiled_permute_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_size_t, C.c_int]),
-    "bj_canonicalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
-    "bj_field_op_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
-    "bj_ntt_forward_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint64]),
-    "bj_intt_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint64]),
-    "bj_merkle_tree_digests": (C.c_size_t, [C.c_size_t, C.c_size_t]),
-    "bj_merkle_tree_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_size_t, C.c_size_t, C.c_void_p]),
-    "bj_merkle_tree_build_ptrs": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint, C.c_size_t, C.c_size_t, C.c_void_p]),
-    "bj_merkle_tree_build_chunked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_size_t, C.c_void_p]),
-    "bj_merkle_tree_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]),
-    "bj_merkle_tree_cap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
-    "bj_merkle_tree_proof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "bj_poseidon2_permute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
-    "bj_poseidon_permute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
-    "bj_fri_fold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint64, C.c_uint64, C.c_uint64]),
-    "bj_barycentric_weights": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_barycentric_eval_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_deep_quotient_accumulate": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_int]),
-    "bj_deep_quotient_accumulate_range": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p,
-                                                    C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_size_t, C.c_size_t, C.c_void_p,
-                                                    C.c_void_p, C.c_int]),
-    "bj_deep_quotient_accumulate_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_size_t, C.c_size_t,
-                                                   C.c_void_p, C.c_void_p, C.c_int]),
-    "bj_linear_combination": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t,
-                                        C.c_void_p, C.c_void_p]),
-    "bj_copy_perm_stage2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_uint,
-                                      C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_sigmas_from_placement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t]),
-    "bj_lookup_polys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint,
-                                  C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_lookup_multiplicities": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint,
-                                           C.c_void_p]),
-    "bj_setup_lookup_multiplicities": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_quotient_gates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p,
-                                    C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "bj_quotient_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                     C.c_void_p, C.c_void_p]),
-    "bj_quotient_copy_perm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                        C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
-    "bj_combine_residues": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p]),
-    "bj_rccl_available": (C.c_int, []),
-    "bj_rccl_unique_id": (C.c_int, [C.c_void_p]),
-    "bj_comm_rccl_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p]),
-    "bj_comm_rccl_destroy": (None, [C.c_void_p]),
-    "bj_comm_rccl_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
-    "bj_setup_set_comm": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "bj_comm_replay_create": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]),
-    "bj_comm_replay_destroy": (None, [C.c_void_p]),
-    "bj_comm_replay_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
-    "bj_comm_replay_capture": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
-    "bj_comm_replay_captured": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
-    "bj_gate_program_generated": (C.c_int, [C.c_void_p]),
-    "bj_gate_program_canonical_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_gate_program_emit_body": (C.c_size_t, [C.c_void_p, C.c_char_p, C.c_size_t]),
-    "bj_gate_program_jit_source": (C.c_size_t, [C.c_void_p, C.c_char_p, C.c_size_t]),
-    "bj_gate_program_jit_compile_check": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t]),
-    "bj_gate_jit_status": (C.c_int, [C.c_char_p, C.c_size_t]),
-    "bj_gate_program_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint,
-                                       C.c_uint, C.c_size_t, C.c_void_p]),
-    "bj_setup_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "bj_setup_create_sharded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.POINTER(C.c_void_p)]),
-    "bj_setup_destroy": (None, [C.c_void_p]),
-    "bj_setup_cap": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "bj_setup_device_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
-    "bj_prove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "bj_comm_peer_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bj_comm_peer_destroy": (None, [C.c_void_p]),
-    "bj_comm_peer_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
-    "bj_prove_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "bj_proof_wait": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
-    "bj_proof_poll": (C.c_int, [C.c_void_p]),
-    "bj_prove_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "bj_proof_destroy": (None, [C.c_void_p]),
-    "bj_proof_size_u64": (C.c_size_t, [C.c_void_p]),
-    "bj_proof_serialize": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "bj_setup_shape": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_setup_dump_info": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p]),
-    "bj_setup_create_from_dump": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "bj_setup_create_from_placement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.POINTER(C.c_void_p)]),
-    "bj_prove_from_dumps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
-                                      C.POINTER(C.c_void_p)]),
-    "bj_check_satisfied": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_check_satisfied_from_dumps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
-                                                C.c_void_p]),
-    "bj_sigma_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t,
-                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
-    "bj_check_copy_constraints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_vk_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "bj_vk_from_setup": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
-    "bj_vk_destroy": (None, [C.c_void_p]),
-    "bj_verify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p]),
-    "bj_verify_proof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_verify_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
-    "bj_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_uint, C.c_void_p]),
-    "bj_verify_batch_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
-    "bj_proof_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "bj_proof_workspace_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
-    "bj_proof_kernel_stats": (C.c_int, [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_proof_comm_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_fri_fold_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint64, C.c_uint64, C.c_uint64]),
-    "bj_transcript_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
-    "bj_transcript_destroy": (None, [C.c_void_p]),
-    "bj_transcript_absorb_cap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
-    "bj_ctx_set_tree_hasher": (C.c_int, [C.c_void_p, C.c_int]),
-    "bj_ctx_release_workspace": (C.c_int, [C.c_void_p]),
-    "bj_transcript_absorb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
-    "bj_transcript_challenge": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
-    "bj_transcript_query_index": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint, C.POINTER(C.c_uint64)]),
-    "bj_fri_schedule": (C.c_int, [C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
-                                  C.POINTER(C.c_size_t), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
-    "bj_fri_prove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.POINTER(C.c_uint32), C.c_size_t,
-                               C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "bj_fri_destroy": (None, [C.c_void_p]),
-    "bj_fri_num_oracles": (C.c_size_t, [C.c_void_p]),
-    "bj_fri_final_degree": (C.c_size_t, [C.c_void_p]),
-    "bj_fri_cap": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bj_fri_challenge": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "bj_fri_final_monomials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bj_fri_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
-}
+# era_boojum_amd/_abi.py is generated from include/boojum_hip.h (tools/gen_py_abi.py): every symbol the header declares as
+# name -> (restype, argtypes), its structs, callback types, enumerators and defines.  The names below are the binding's own.
+_SIGNATURES = _abi.SIGNATURES
+ABI_VERSION = _abi.BJ_ABI_VERSION
+RCCL_UNIQUE_ID_BYTES = _abi.BJ_RCCL_UNIQUE_ID_BYTES
+DeepSet = _abi.bj_deep_set                 # one opening set of bj_deep_quotient_accumulate_sets
+_GateDesc, _Circuit, _ProofConfig = _abi.bj_gate_desc, _abi.bj_circuit, _abi.bj_proof_config
+_Comm, _ALL_GATHER_FN, _ALL_GATHER_STREAM_FN = _abi.bj_comm, _abi.bj_comm_all_gather, _abi.bj_comm_all_gather_stream
+_HOST_EXCHANGE_FN = _abi.bj_host_exchange_fn
+_VerifyReport, _UnsatReport, _CopyReport = _abi.bj_verify_report, _abi.bj_unsat_report, _abi.bj_copy_report
 
 
 class BoojumHipError(RuntimeError):
@@ -180,9 +39,6 @@ def exported_symbols():
 _lib = None
 
 
-ABI_VERSION = 6
-
-
 def load_library():
     """dlopen libboojum_hip.so; raises (never falls back) if it has not been built."""
     global _lib
@@ -196,17 +52,11 @@ def load_library():
             fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
             fn.restype = res
             fn.argtypes = args
-        if lib.bj_abi_version() != ABI_VERSION:     # struct layouts below are those of BJ_ABI_VERSION in include/boojum_hip.h
-            raise BoojumHipError("%s has ABI version %d, this binding was written for %d: rebuild (python -m era_boojum_amd.build)"
+        if lib.bj_abi_version() != ABI_VERSION:     # a library built from another header than the one _abi.py was generated from
+            raise BoojumHipError("%s has ABI version %d, this binding was generated for %d: rebuild (python -m era_boojum_amd.build)"
                                  % (path, lib.bj_abi_version(), ABI_VERSION))
         _lib = lib
     return _lib
-
-
-class DeepSet(C.Structure):
-    """bj_deep_set: one opening set of bj_deep_quotient_accumulate_sets."""
-    _fields_ = [("src_c0", C.POINTER(C.c_void_p)), ("src_c1", C.POINTER(C.c_void_p)), ("n_src", C.c_size_t),
-                ("values", C.c_void_p), ("challenges", C.c_void_p), ("at2", C.c_void_p)]
 
 
 def _np_ptr(a):
@@ -253,8 +103,8 @@ class Context:
 
     # -- plumbing
     def set_tree_hasher(self, hasher):
-        """1 = Poseidon2 (default), 2 = Blake2s-256, 3 = Keccak-256, 4 = Poseidon (v1): hasher of the merkle_tree_* / fri calls
-        on this context (BJ_HASHER_*)."""
+        """BJ_HASHER_POSEIDON2 (default), BJ_HASHER_BLAKE2S, BJ_HASHER_KECCAK256 or BJ_HASHER_POSEIDON (v1): hasher of the
+        merkle_tree_* / fri calls on this context."""
         self._check(self._lib.bj_ctx_set_tree_hasher(self._h, int(hasher)))
 
     def set_stream(self, stream_handle):
@@ -410,10 +260,9 @@ class Context:
         a = np.ascontiguousarray(np.array([int(v) for v in moduli], dtype=np.uint64))
         self._check(self._lib.bj_combine_residues(self._h, d_residues, world, residue_len, num_cols, _np_ptr(a), d_out))
 
-    FIELD_OPS = {"add": 0, "sub": 1, "mul": 2, "mul_lazy": 3, "square": 4, "inverse": 5, "ext2_mul": 6, "butterfly": 7, "addsub": 8,
-                 "add_lazy": 9, "sub_lazy": 10, "ext2_mul_lazy": 11, "reduce128": 12, "acc160": 13, "acc_ext2": 14, "mul7_lazy": 15,
-                 "mul_u32_lazy": 16, "mul_pow2": 17, "mul7": 18, "pow7": 19, "inverse_chain": 20, "ext2_inverse": 21,
-                 "ext2_inverse_chain": 22, "bitrev": 23, "w16_butterfly": 32}
+    # every BJ_FIELD_* operator of the header under its name in lower case ("add", ..., "w16_butterfly"), in header order
+    FIELD_OPS = {{"acc160x2_e2": "acc_ext2"}.get(name, name): value for name, value in
+                 ((k[len("BJ_FIELD_"):].lower(), v) for k, v in vars(_abi).items() if k.startswith("BJ_FIELD_"))}
     # operator -> (parts of n words in d_a, in d_b (0: unused), in d_out); every other operator is (1, 1, 1) or unary (1, 0, 1)
     FIELD_OP_PARTS = {"ext2_mul": (2, 2, 2), "ext2_mul_lazy": (2, 2, 2), "butterfly": (2, 1, 2), "addsub": (2, 0, 2), "acc160": (3, 2, 1),
                       "acc_ext2": (2, 2, 2), "w16_butterfly": (2, 1, 2), "ext2_inverse": (2, 0, 2), "ext2_inverse_chain": (2, 0, 2)}
@@ -538,7 +387,7 @@ class Context:
         keep = [self._deep_args(*s) for s in sets]
         arr = (DeepSet * max(len(sets), 1))()
         for t, (p0, p1, k, v, ch, a) in enumerate(keep):
-            arr[t] = DeepSet(p0, p1, k, _np_ptr(v), _np_ptr(ch), _np_ptr(a))
+            arr[t] = DeepSet(p0, p1, k, v.ctypes.data_as(u64p), ch.ctypes.data_as(u64p), a.ctypes.data_as(u64p))
         self._check(self._lib.bj_deep_quotient_accumulate_sets(self._h, C.cast(arr, C.c_void_p), len(sets), log_n, log_lde, first,
                                                                count, d_dst0, d_dst1, int(bool(accumulate))))
 
@@ -565,8 +414,8 @@ class Context:
 class Transcript:
     """Host-side Poseidon2 Fiat–Shamir transcript of the product (bj_transcript_*); needs no GPU."""
 
-    def __init__(self, kind=1):
-        """kind 1 = Poseidon2 (BJ_TRANSCRIPT_POSEIDON2), 2 = Poseidon v1 (BJ_TRANSCRIPT_POSEIDON)."""
+    def __init__(self, kind=_abi.BJ_TRANSCRIPT_POSEIDON2):
+        """kind: BJ_TRANSCRIPT_POSEIDON2 (the default) or BJ_TRANSCRIPT_POSEIDON (Poseidon v1)."""
         self._lib = load_library()
         h = C.c_void_p()
         rc = self._lib.bj_transcript_create(int(kind), C.byref(h))
@@ -672,15 +521,9 @@ class FriProof:
         return leaf, path[:depth]
 
 
-class _GateDesc(C.Structure):
-    _fields_ = [("kind", C.c_int), ("path_len", C.c_uint), ("path", C.c_ubyte * 8), ("num_repetitions", C.c_uint),
-                ("var_stride", C.c_uint), ("wit_stride", C.c_uint), ("const_stride", C.c_uint), ("num_terms", C.c_uint),
-                ("program", C.c_void_p)]
-
-
 def gate_desc_array(gates):
     """bj_gate_desc[] for gates with the attributes of synthetic.Gate (kind, path, reps, var_stride, const_stride, num_terms); an
-    op-list gate (kind 5) points at its program, which the caller keeps alive for the call."""
+    op-list gate (BJ_GATE_PROGRAM) points at its program, which the caller keeps alive for the call."""
     arr = (_GateDesc * len(gates))()
     for i, g in enumerate(gates):
         arr[i].kind, arr[i].path_len = int(g.kind), len(g.path)
@@ -688,39 +531,13 @@ def gate_desc_array(gates):
             arr[i].path[b] = 1 if bit else 0
         arr[i].num_repetitions, arr[i].var_stride, arr[i].const_stride = int(g.reps), int(g.var_stride), int(g.const_stride)
         arr[i].num_terms, arr[i].program = int(g.num_terms), None
-        if int(g.kind) == 5 and getattr(g, "program", None) is not None:
-            arr[i].program = C.cast(C.pointer(g.program.struct), C.c_void_p)
+        if int(g.kind) == _abi.BJ_GATE_PROGRAM and getattr(g, "program", None) is not None:
+            arr[i].program = C.pointer(g.program.struct)
     return arr
-
-
-class _Circuit(C.Structure):
-    _fields_ = [("log_n", C.c_uint), ("num_vars", C.c_uint), ("num_gp_vars", C.c_uint), ("num_witness_cols", C.c_uint),
-                ("num_constant_cols", C.c_uint), ("lookup_width", C.c_uint), ("lookup_reps", C.c_uint),
-                ("table_id_col", C.c_uint), ("quotient_degree", C.c_uint), ("num_gates", C.c_uint),
-                ("gates", C.POINTER(_GateDesc)), ("non_residues", C.POINTER(C.c_uint64)), ("num_public_inputs", C.c_uint),
-                ("public_input_cols", C.POINTER(C.c_uint)), ("public_input_rows", C.POINTER(C.c_uint)),
-                ("num_specialized_gates", C.c_uint), ("specialized_gates", C.POINTER(_GateDesc))]
-
-
-class _ProofConfig(C.Structure):
-    _fields_ = [("fri_lde_factor", C.c_uint), ("cap_size", C.c_uint), ("security_level", C.c_uint), ("pow_bits", C.c_uint),
-                ("transcript", C.c_uint), ("tree_hasher", C.c_uint), ("pow_runner", C.c_uint)]
 
 
 STAGE_NAMES = ["witness_lde_and_tree", "second_stage", "quotient_work_and_lde", "openings_at_z",
                "batched_fri_opening_computation", "fri", "queries"]
-
-
-_ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
-_ALL_GATHER_STREAM_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
-
-
-class _Comm(C.Structure):  # bj_comm
-    _fields_ = [("rank", C.c_uint), ("world", C.c_uint), ("all_gather", _ALL_GATHER_FN), ("user", C.c_void_p),
-                ("all_gather_stream", _ALL_GATHER_STREAM_FN)]
-
-
-RCCL_UNIQUE_ID_BYTES = 128
 
 
 def rccl_unique_id():
@@ -935,9 +752,6 @@ class TorchComm:
             return 1
 
 
-_HOST_EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
-
-
 class PeerComm:
     """bj_comm_peer_create: full-mesh peer copies for the bulk exchanges of a sharded proof (every rank writes its contribution
     straight into every peer's receive buffer, mapped through HIP IPC), everything smaller through `base` (a TorchComm or RcclComm).
@@ -1019,15 +833,15 @@ def circuit_struct(c, from_dump=False):
             g.reps, g.var_stride, g.const_stride, g.num_terms
         gates[i].wit_stride = getattr(g, "wit_stride", 0)
         prog = getattr(g, "program", None)       # seam S3: evaluate this gate from its op list (gate_program.py)
-        if prog is not None and g.kind != 7:     # BJ_GATE_POSEIDON_FLATTENED: its program serves the host-side checks only
-            gates[i].kind = 5
-            gates[i].program = C.cast(C.pointer(prog.struct), C.c_void_p)
+        if prog is not None and g.kind != _abi.BJ_GATE_POSEIDON_FLATTENED:     # whose program serves the host-side checks only
+            gates[i].kind = _abi.BJ_GATE_PROGRAM
+            gates[i].program = C.pointer(prog.struct)
     spec_list = list(getattr(c, "specialized_gates", []) or [])
     spec = (_GateDesc * max(1, len(spec_list)))()
     for i, g in enumerate(spec_list):                # gates over specialized columns: op lists, no selector
-        spec[i].kind, spec[i].path_len = 5, 0
+        spec[i].kind, spec[i].path_len = _abi.BJ_GATE_PROGRAM, 0
         spec[i].num_repetitions, spec[i].var_stride, spec[i].const_stride, spec[i].num_terms = g.reps, g.var_stride, g.const_stride, g.num_terms
-        spec[i].program = C.cast(C.pointer(g.program.struct), C.c_void_p)
+        spec[i].program = C.pointer(g.program.struct)
     nr = np.array(c.non_residues, dtype=np.uint64)
     cols = (C.c_uint * max(1, len(c.public_inputs)))(*[p[0] for p in c.public_inputs])
     rows = (C.c_uint * max(1, len(c.public_inputs)))(*[p[1] for p in c.public_inputs])
@@ -1040,22 +854,23 @@ def circuit_struct(c, from_dump=False):
 
 def proof_config_struct(fri_lde_factor, cap_size, security_level, pow_bits, transcript="poseidon2", tree_hasher=None, pow_runner="blake2s"):
     """bj_proof_config; tree_hasher None pairs the transcript with its usual hasher (Transcript::CompatibleCap = TreeHasher::Output)."""
-    transcript_kind = {"poseidon2": 1, "poseidon": 2, "blake2s": 3, "keccak256": 4}[transcript]
+    transcript_kind = TRANSCRIPT_KINDS[transcript]
     if tree_hasher is None:
-        hasher_kind = {"blake2s": 2, "keccak256": 3}.get(transcript, 1)
-    else:
-        hasher_kind = {"poseidon2": 1, "blake2s": 2, "keccak256": 3, "poseidon": 4}[tree_hasher]
-    return _ProofConfig(fri_lde_factor, cap_size, security_level, pow_bits, transcript_kind, hasher_kind, {"blake2s": 1, "keccak256": 2}[pow_runner])
+        tree_hasher = transcript if transcript in ("blake2s", "keccak256") else "poseidon2"
+    return _ProofConfig(fri_lde_factor, cap_size, security_level, pow_bits, transcript_kind, HASHER_KINDS[tree_hasher], POW_KINDS[pow_runner])
 
 
-class _VerifyReport(C.Structure):  # bj_verify_report
-    _fields_ = [("stage", C.c_uint32), ("query", C.c_uint32), ("oracle", C.c_uint32), ("queries_checked", C.c_uint32)]
+TRANSCRIPT_KINDS = {"poseidon2": _abi.BJ_TRANSCRIPT_POSEIDON2, "poseidon": _abi.BJ_TRANSCRIPT_POSEIDON,
+                    "blake2s": _abi.BJ_TRANSCRIPT_BLAKE2S, "keccak256": _abi.BJ_TRANSCRIPT_KECCAK256}
+HASHER_KINDS = {"poseidon2": _abi.BJ_HASHER_POSEIDON2, "blake2s": _abi.BJ_HASHER_BLAKE2S, "keccak256": _abi.BJ_HASHER_KECCAK256,
+                "poseidon": _abi.BJ_HASHER_POSEIDON}
+POW_KINDS = {"blake2s": _abi.BJ_POW_BLAKE2S256, "keccak256": _abi.BJ_POW_KECCAK256}
 
-
-(VERIFY_OK, VERIFY_SHAPE, VERIFY_LOOKUP_SUM, VERIFY_QUOTIENT, VERIFY_POW, VERIFY_MERKLE, VERIFY_FRI_VALUE, VERIFY_FRI_MERKLE,
- VERIFY_FINAL) = range(9)     # bj_verify_stage
+(VERIFY_OK, VERIFY_SHAPE, VERIFY_LOOKUP_SUM, VERIFY_QUOTIENT, VERIFY_POW, VERIFY_MERKLE, VERIFY_FRI_VALUE, VERIFY_FRI_MERKLE, VERIFY_FINAL) = (
+    _abi.BJ_VERIFY_OK, _abi.BJ_VERIFY_SHAPE, _abi.BJ_VERIFY_LOOKUP_SUM, _abi.BJ_VERIFY_QUOTIENT, _abi.BJ_VERIFY_POW, _abi.BJ_VERIFY_MERKLE,
+    _abi.BJ_VERIFY_FRI_VALUE, _abi.BJ_VERIFY_FRI_MERKLE, _abi.BJ_VERIFY_FINAL)     # bj_verify_stage
 VERIFY_STAGE_NAMES = ["ok", "shape", "lookup_sum", "quotient", "pow", "merkle", "fri_value", "fri_merkle", "final"]
-VERIFY_PARTIAL_QUERIES = 1
+VERIFY_PARTIAL_QUERIES = _abi.BJ_VERIFY_PARTIAL_QUERIES
 
 
 @dataclass
@@ -1144,12 +959,8 @@ class Verifier:
         return float(a.value), float(b.value)
 
 
-class _UnsatReport(C.Structure):  # bj_unsat_report
-    _fields_ = [("kind", C.c_uint32), ("gate", C.c_uint32), ("repetition", C.c_uint32), ("term", C.c_uint32), ("row", C.c_uint64),
-                ("value", C.c_uint64), ("expected", C.c_uint64), ("failures", C.c_uint64 * 5)]
-
-
-SAT, UNSAT_GATE, UNSAT_SPECIALIZED_GATE, UNSAT_LOOKUP, UNSAT_MULTIPLICITY = range(5)     # bj_unsat_kind
+SAT, UNSAT_GATE, UNSAT_SPECIALIZED_GATE, UNSAT_LOOKUP, UNSAT_MULTIPLICITY = (
+    _abi.BJ_SAT, _abi.BJ_UNSAT_GATE, _abi.BJ_UNSAT_SPECIALIZED_GATE, _abi.BJ_UNSAT_LOOKUP, _abi.BJ_UNSAT_MULTIPLICITY)     # bj_unsat_kind
 
 
 @dataclass
@@ -1180,12 +991,8 @@ class SatisfiabilityReport:
         return "Unsatisfied at table row %d: multiplicities sum to %d, %d lookups" % (self.row, self.expected, self.value)
 
 
-class _CopyReport(C.Structure):  # bj_copy_report
-    _fields_ = [("kind", C.c_uint32), ("column", C.c_uint32), ("partner_column", C.c_uint32), ("row", C.c_uint64), ("partner_row", C.c_uint64),
-                ("value", C.c_uint64), ("partner_value", C.c_uint64), ("variable", C.c_uint32), ("failures", C.c_uint64 * 4)]
-
-
-COPY_OK, COPY_SIGMA_INVALID, COPY_SIGMA_NOT_PERMUTATION, COPY_VALUE_MISMATCH = range(4)     # bj_copy_kind
+COPY_OK, COPY_SIGMA_INVALID, COPY_SIGMA_NOT_PERMUTATION, COPY_VALUE_MISMATCH = (
+    _abi.BJ_COPY_OK, _abi.BJ_COPY_SIGMA_INVALID, _abi.BJ_COPY_SIGMA_NOT_PERMUTATION, _abi.BJ_COPY_VALUE_MISMATCH)     # bj_copy_kind
 NO_CELL = 0xFFFFFFFF                # bj_sigma_cells: a word in no coset; bj_copy_report.variable: no placement index
 NO_CELL_KEY = (1 << 64) - 1         # bj_sigma_cells: *first_invalid when every word is valid
 

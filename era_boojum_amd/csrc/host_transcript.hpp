@@ -5,6 +5,7 @@
 //   transcript    src/cs/implementations/transcript.rs:48-131 (AlgebraicSpongeBasedTranscript), :144-151 (Poseidon2)
 //   BoolsBuffer   src/cs/implementations/transcript.rs:369-417; index split prover.rs:2161-2182
 #pragma once
+#include "../../include/boojum_hip.h"
 #include "gl.h"
 #include "poseidon_gate_terms.h"
 #include <cstdint>
@@ -204,15 +205,15 @@ struct Keccak256 {
 };
 
 struct Transcript {
-    int kind = 1;   // BJ_TRANSCRIPT_POSEIDON2 = 1, BJ_TRANSCRIPT_POSEIDON = 2, BJ_TRANSCRIPT_BLAKE2S = 3, BJ_TRANSCRIPT_KECCAK256 = 4
-    bool is_bytes() const { return kind == 3 || kind == 4; }
+    int kind = BJ_TRANSCRIPT_POSEIDON2;   // BJ_TRANSCRIPT_*
+    bool is_bytes() const { return kind == BJ_TRANSCRIPT_BLAKE2S || kind == BJ_TRANSCRIPT_KECCAK256; }
     // --- byte transcripts (Blake2sTranscript / Keccak256Transcript, transcript.rs:155-372)
     Blake2s inner;
     Keccak256 inner_k;
     std::vector<unsigned char> bytes, avail_bytes;
     void reseed() {
         unsigned char out[32];
-        if (kind == 4) {
+        if (kind == BJ_TRANSCRIPT_KECCAK256) {
             inner_k.finalize_reset(out);
             inner_k.update(out, 32);
         } else {
@@ -223,7 +224,7 @@ struct Transcript {
     }
     void flush_bytes() {
         if (!bytes.empty()) {
-            if (kind == 4)
+            if (kind == BJ_TRANSCRIPT_KECCAK256)
                 inner_k.update(bytes.data(), bytes.size());
             else
                 inner.update(bytes.data(), bytes.size());
@@ -248,7 +249,7 @@ struct Transcript {
             for (int b = 0; b < 8; b++) bytes.push_back((unsigned char)(digest_words[i] >> (8 * b)));
     }
     void permute() {
-        if (kind == 2) poseidon1_permutation(state);
+        if (kind == BJ_TRANSCRIPT_POSEIDON) poseidon1_permutation(state);
         else poseidon2_permutation(state);
     }
     u64 state[12] = {0};

@@ -31,6 +31,8 @@ struct GateDev {
     int kind, path_len, reps, var_stride, const_stride, num_terms;
     int path[6];
 };
+// the kinds the two kernels below evaluate themselves (bj_gate_kind); every kind from BJ_GATE_PROGRAM on has a kernel of its own
+constexpr int K_ALLOC = BJ_GATE_CONSTANT_ALLOCATOR, K_FMA = BJ_GATE_FMA_NO_CONSTANT, K_RED4 = BJ_GATE_REDUCTION4;
 constexpr int BJ_MAX_GATES = 16;   // evaluators over general-purpose columns per circuit (the golden proof's circuit has 11)
 struct GateSet {
     GateDev g[BJ_MAX_GATES];
@@ -48,7 +50,7 @@ quotient_gates_kernel(const u64 *vars, size_t var_stride, const u64 *consts, siz
     for (int gi = 0; gi < gs.n_gates; gi++) {
         const GateDev &G = gs.g[gi];
         if (G.num_terms == 0) continue;
-        if (G.kind >= 5) {   // op-list gate (seam S3) or the Poseidon2 flattened gate: evaluated by their own kernels, only the alpha powers are skipped here
+        if (G.kind >= BJ_GATE_PROGRAM) {   // op-list gate (seam S3) or the Poseidon2 flattened gate: evaluated by their own kernels, only the alpha powers are skipped here
             aoff += G.reps * G.num_terms;
             continue;
         }
@@ -61,10 +63,10 @@ quotient_gates_kernel(const u64 *vars, size_t var_stride, const u64 *consts, siz
         s.clear();
         const size_t cb0 = (size_t)G.path_len;
         u64 k0 = 0, k1 = 0, k2 = 0, k3 = 0;
-        if (G.kind == 2) {
+        if (G.kind == K_FMA) {
             k0 = gl::canon(consts[cb0 * const_stride + I]);
             k1 = gl::canon(consts[(cb0 + 1) * const_stride + I]);
-        } else if (G.kind == 3) {
+        } else if (G.kind == K_RED4) {
             k0 = gl::canon(consts[cb0 * const_stride + I]);
             k1 = gl::canon(consts[(cb0 + 1) * const_stride + I]);
             k2 = gl::canon(consts[(cb0 + 2) * const_stride + I]);
@@ -74,10 +76,10 @@ quotient_gates_kernel(const u64 *vars, size_t var_stride, const u64 *consts, siz
             const size_t vb = (size_t)r * G.var_stride;
 #define VARQ(k) gl::canon(vars[(vb + (k)) * var_stride + I])
             u64 term;
-            if (G.kind == 1) {          // ConstantsAllocator: a - c_r
+            if (G.kind == K_ALLOC) {    // ConstantsAllocator: a - c_r
                 u64 c = gl::canon(consts[(cb0 + (size_t)r * G.const_stride) * const_stride + I]);
                 term = gl::sub(VARQ(0), c);
-            } else if (G.kind == 2) {   // FMA: q*a*b + l*c - d
+            } else if (G.kind == K_FMA) { // FMA: q*a*b + l*c - d
                 u64 a = VARQ(0), b = VARQ(1), c = VARQ(2), d = VARQ(3);
                 term = gl::sub(gl::add(gl::mul(c, k1), gl::mul(k0, gl::mul(a, b))), d);
             } else {                    // Reduction<4>: sum c_i v_i - r
@@ -107,9 +109,9 @@ quotient_gates_kernel(const u64 *vars, size_t var_stride, const u64 *consts, siz
 // gate (PMC: 2.05 x the algorithmic bytes); this one reads them once.
 constexpr int GW_WINDOW = 20;
 struct GateWindows {
-    int present[4];         // by kind (1, 2, 3)
-    int path_len[4], path[4][6];
-    int reps[4], const_stride[4], aoff[4];
+    int present[BJ_GATE_NOP];   // by kind (K_ALLOC, K_FMA, K_RED4)
+    int path_len[BJ_GATE_NOP], path[BJ_GATE_NOP][6];
+    int reps[BJ_GATE_NOP], const_stride[BJ_GATE_NOP], aoff[BJ_GATE_NOP];
     int n_windows, n_vars;
 };
 __global__ void __launch_bounds__(256)
@@ -117,21 +119,21 @@ quotient_gates_windowed_kernel(const u64 *vars, size_t var_stride, const u64 *co
                                const u64 *alphas /* [n_terms][2] */, size_t Q, u64 *out0, u64 *out1) {
     const size_t I = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (I >= Q) return;
-    u64 sel[4] = {0, 0, 0, 0};
+    u64 sel[BJ_GATE_NOP] = {0, 0, 0, 0};
     u64 pc[6];              // the selector path columns (shared by all gates), read once
 #pragma unroll
     for (int b = 0; b < 6; b++) pc[b] = 0;
     {
         int max_path = 0;
 #pragma unroll
-        for (int k = 1; k <= 3; k++)
+        for (int k = K_ALLOC; k < BJ_GATE_NOP; k++)
             if (gw.present[k] && gw.path_len[k] > max_path) max_path = gw.path_len[k];
 #pragma unroll
         for (int b = 0; b < 6; b++)
             if (b < max_path) pc[b] = gl::canon(consts[(size_t)b * const_stride + I]);
     }
 #pragma unroll
-    for (int k = 1; k <= 3; k++) {
+    for (int k = K_ALLOC; k < BJ_GATE_NOP; k++) {
         if (!gw.present[k]) continue;
         u64 sv = 1;
 #pragma unroll
@@ -140,17 +142,17 @@ quotient_gates_windowed_kernel(const u64 *vars, size_t var_stride, const u64 *co
         sel[k] = sv;
     }
     u64 k2[2] = {0, 0}, k3[4] = {0, 0, 0, 0};
-    if (gw.present[2]) {
+    if (gw.present[K_FMA]) {
 #pragma unroll
-        for (int j = 0; j < 2; j++) k2[j] = gl::canon(consts[(size_t)(gw.path_len[2] + j) * const_stride + I]);
+        for (int j = 0; j < 2; j++) k2[j] = gl::canon(consts[(size_t)(gw.path_len[K_FMA] + j) * const_stride + I]);
     }
-    if (gw.present[3]) {
+    if (gw.present[K_RED4]) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) k3[j] = gl::canon(consts[(size_t)(gw.path_len[3] + j) * const_stride + I]);
+        for (int j = 0; j < 4; j++) k3[j] = gl::canon(consts[(size_t)(gw.path_len[K_RED4] + j) * const_stride + I]);
     }
-    gl::Acc160 s0[4], s1[4];
+    gl::Acc160 s0[BJ_GATE_NOP], s1[BJ_GATE_NOP];
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < BJ_GATE_NOP; k++) {
         s0[k].clear();
         s1[k].clear();
     }
@@ -162,34 +164,34 @@ quotient_gates_windowed_kernel(const u64 *vars, size_t var_stride, const u64 *co
             const int col = w * GW_WINDOW + c;
             v[c] = gl::canon(vars[(size_t)(col < gw.n_vars ? col : 0) * var_stride + I]);   // past the last column: a valid address, never used
         }
-        if (gw.present[1]) {    // ConstantsAllocator: a - c_r
+        if (gw.present[K_ALLOC]) {    // ConstantsAllocator: a - c_r
 #pragma unroll
             for (int i = 0; i < GW_WINDOW; i++) {
                 const int r = w * GW_WINDOW + i;
-                if (r < gw.reps[1]) {
-                    const u64 c = gl::canon(consts[(size_t)(gw.path_len[1] + r * gw.const_stride[1]) * const_stride + I]);
+                if (r < gw.reps[K_ALLOC]) {
+                    const u64 c = gl::canon(consts[(size_t)(gw.path_len[K_ALLOC] + r * gw.const_stride[K_ALLOC]) * const_stride + I]);
                     const u64 term = gl::sub(v[i], c);
-                    s0[1].fma(term, alphas[2 * (gw.aoff[1] + r)]);
-                    s1[1].fma(term, alphas[2 * (gw.aoff[1] + r) + 1]);
+                    s0[K_ALLOC].fma(term, alphas[2 * (gw.aoff[K_ALLOC] + r)]);
+                    s1[K_ALLOC].fma(term, alphas[2 * (gw.aoff[K_ALLOC] + r) + 1]);
                 }
             }
         }
-        if (gw.present[2]) {    // FMA: q*a*b + l*c - d
+        if (gw.present[K_FMA]) {    // FMA: q*a*b + l*c - d
 #pragma unroll
             for (int i = 0; i < GW_WINDOW / 4; i++) {
                 const int r = w * (GW_WINDOW / 4) + i;
-                if (r < gw.reps[2]) {
+                if (r < gw.reps[K_FMA]) {
                     const u64 term = gl::sub(gl::add(gl::mul(v[4 * i + 2], k2[1]), gl::mul(k2[0], gl::mul(v[4 * i], v[4 * i + 1]))), v[4 * i + 3]);
-                    s0[2].fma(term, alphas[2 * (gw.aoff[2] + r)]);
-                    s1[2].fma(term, alphas[2 * (gw.aoff[2] + r) + 1]);
+                    s0[K_FMA].fma(term, alphas[2 * (gw.aoff[K_FMA] + r)]);
+                    s1[K_FMA].fma(term, alphas[2 * (gw.aoff[K_FMA] + r) + 1]);
                 }
             }
         }
-        if (gw.present[3]) {    // Reduction<4>: sum c_i v_i - r
+        if (gw.present[K_RED4]) {    // Reduction<4>: sum c_i v_i - r
 #pragma unroll
             for (int i = 0; i < GW_WINDOW / 5; i++) {
                 const int r = w * (GW_WINDOW / 5) + i;
-                if (r < gw.reps[3]) {
+                if (r < gw.reps[K_RED4]) {
                     gl::Acc160 t;
                     t.clear();
                     t.fma(v[5 * i], k3[0]);
@@ -197,15 +199,15 @@ quotient_gates_windowed_kernel(const u64 *vars, size_t var_stride, const u64 *co
                     t.fma(v[5 * i + 2], k3[2]);
                     t.fma(v[5 * i + 3], k3[3]);
                     const u64 term = gl::sub(t.reduce(), v[5 * i + 4]);
-                    s0[3].fma(term, alphas[2 * (gw.aoff[3] + r)]);
-                    s1[3].fma(term, alphas[2 * (gw.aoff[3] + r) + 1]);
+                    s0[K_RED4].fma(term, alphas[2 * (gw.aoff[K_RED4] + r)]);
+                    s1[K_RED4].fma(term, alphas[2 * (gw.aoff[K_RED4] + r) + 1]);
                 }
             }
         }
     }
     gl::e2 acc{0, 0};
 #pragma unroll
-    for (int k = 1; k <= 3; k++) {
+    for (int k = K_ALLOC; k < BJ_GATE_NOP; k++) {
         if (!gw.present[k]) continue;
         acc.c0 = gl::add(acc.c0, gl::mul(s0[k].reduce(), sel[k]));
         acc.c1 = gl::add(acc.c1, gl::mul(s1[k].reduce(), sel[k]));
@@ -413,10 +415,10 @@ void launch_quotient_gates(const u64 *d_vars, size_t var_stride, const u64 *d_co
         int span = 0, n_hand = 0;
         for (unsigned g = 0; ok && g < n_gates; g++) {
             const GateShape &G = gates[g];
-            if (G.num_terms == 0 || G.kind >= 5) continue;   // no terms, or evaluated by its own kernel
+            if (G.num_terms == 0 || G.kind >= BJ_GATE_PROGRAM) continue;   // no terms, or evaluated by its own kernel
             const int width = (int)gate_kind_extent(G.kind).var_extent;
-            if (G.kind < 1 || G.kind > 3 || gw.present[G.kind] || (int)G.var_stride != width || G.num_terms != 1 || G.path_len > 6 ||
-                (G.kind != 1 && G.const_stride != 0)) {
+            if (G.kind < K_ALLOC || G.kind >= BJ_GATE_NOP || gw.present[G.kind] || (int)G.var_stride != width || G.num_terms != 1 || G.path_len > 6 ||
+                (G.kind != K_ALLOC && G.const_stride != 0)) {
                 ok = false;
                 break;
             }

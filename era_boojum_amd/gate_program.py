@@ -14,23 +14,15 @@ library does not depend on: csrc/gate_canon.h).  gate_codegen.py generates the b
 A formula can also be written with `+ - *` on the traced values (tests do that for independent restatements)."""
 import ctypes as C
 
-OP_ADD, OP_DOUBLE, OP_SUB, OP_NEGATE, OP_MUL, OP_SQUARE, OP_INVERSE = 1, 2, 3, 4, 5, 6, 7
-IDX_VARIABLE, IDX_WITNESS, IDX_CONSTANT_POLY, IDX_TEMPORARY, IDX_VALUE = 0, 1, 2, 3, 4
+from . import _abi
+
+# bj_gate_op, bj_index_kind and the three structs of a program, as _abi.py generates them from the header
+OP_ADD, OP_DOUBLE, OP_SUB, OP_NEGATE, OP_MUL, OP_SQUARE, OP_INVERSE = (
+    _abi.BJ_OP_ADD, _abi.BJ_OP_DOUBLE, _abi.BJ_OP_SUB, _abi.BJ_OP_NEGATE, _abi.BJ_OP_MUL, _abi.BJ_OP_SQUARE, _abi.BJ_OP_INVERSE)
+IDX_VARIABLE, IDX_WITNESS, IDX_CONSTANT_POLY, IDX_TEMPORARY, IDX_VALUE = (
+    _abi.BJ_IDX_VARIABLE_POLY, _abi.BJ_IDX_WITNESS_POLY, _abi.BJ_IDX_CONSTANT_POLY, _abi.BJ_IDX_TEMPORARY, _abi.BJ_IDX_CONSTANT_VALUE)
+_GateIndex, _GateRelation, _GateProgram = _abi.bj_gate_index, _abi.bj_gate_relation, _abi.bj_gate_program
 P = (1 << 64) - (1 << 32) + 1
-
-
-class _GateIndex(C.Structure):
-    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32)]
-
-
-class _GateRelation(C.Structure):
-    _fields_ = [("op", C.c_uint32), ("dst", C.c_uint32), ("a", _GateIndex), ("b", _GateIndex)]
-
-
-class _GateProgram(C.Structure):
-    _fields_ = [("relations", C.POINTER(_GateRelation)), ("num_relations", C.c_uint32), ("values", C.POINTER(C.c_uint64)),
-                ("num_values", C.c_uint32), ("writes", C.POINTER(_GateIndex)), ("num_writes", C.c_uint32),
-                ("num_temporaries", C.c_uint32)]
 
 
 class _Val:

@@ -19,16 +19,19 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from . import _abi
 from . import field_np as F
 from . import gate_program as GP
 from .gate_program import EvaluatorContext
 
 P = F.P
 
-GATE_CONSTANT_ALLOCATOR, GATE_FMA, GATE_REDUCTION4, GATE_NOP = 1, 2, 3, 4
-GATE_POSEIDON2_FLATTENED = 6   # the hand-written evaluator of Poseidon2FlattenedGate (csrc/gate_poseidon.hip)
-GATE_POSEIDON_FLATTENED = 7    # the hand-written evaluator of PoseidonFlattenedGate, Poseidon v1 (csrc/gate_poseidon.hip)
-GATE_PROGRAM = 5     # evaluated from an op list (seam S3): GateDesc.program is an era_boojum_amd.gate_program.GateProgram
+# bj_gate_kind (include/boojum_hip.h)
+GATE_CONSTANT_ALLOCATOR, GATE_FMA, GATE_REDUCTION4, GATE_NOP = (
+    _abi.BJ_GATE_CONSTANT_ALLOCATOR, _abi.BJ_GATE_FMA_NO_CONSTANT, _abi.BJ_GATE_REDUCTION4, _abi.BJ_GATE_NOP)
+GATE_POSEIDON2_FLATTENED = _abi.BJ_GATE_POSEIDON2_FLATTENED   # the hand-written evaluator of Poseidon2FlattenedGate (csrc/gate_poseidon.hip)
+GATE_POSEIDON_FLATTENED = _abi.BJ_GATE_POSEIDON_FLATTENED     # the same for PoseidonFlattenedGate, Poseidon v1
+GATE_PROGRAM = _abi.BJ_GATE_PROGRAM     # evaluated from an op list (seam S3): GateDesc.program is an era_boojum_amd.gate_program.GateProgram
 
 
 @dataclass
@@ -247,7 +250,7 @@ def make_tables(bits):
     return [t.astype(np.uint64) for t in (tri, ch, maj, s1, s2)]
 
 
-TABLE_ID_AS_VARIABLE = 0xFFFFFFFF     # bj_circuit.table_id_col = BJ_TABLE_ID_AS_VARIABLE (include/boojum_hip.h)
+TABLE_ID_AS_VARIABLE = _abi.BJ_TABLE_ID_AS_VARIABLE     # bj_circuit.table_id_col: the table id is a variable column
 
 
 @dataclass

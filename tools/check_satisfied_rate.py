@@ -66,9 +66,9 @@ def main():
     setup.check_satisfied_dev(d_good, d_m)           # first call: the scratch allocation
     sat_ms, sat_all = median3(timed(lambda: reports.__setitem__("sat", setup.check_satisfied_dev(d_good, d_m))))
     bad_ms, bad_all = median3(timed(lambda: reports.__setitem__("bad", setup.check_satisfied_dev(d_bad, d_m))))
-    assert reports["sat"].kind == 0, str(reports["sat"])
+    assert reports["sat"].kind == E.binding.SAT, str(reports["sat"])
     r = reports["bad"]
-    assert (r.kind, r.gate, r.repetition, r.row) == (1, fma, g.reps - 1, row), str(r)
+    assert (r.kind, r.gate, r.repetition, r.row) == (E.binding.UNSAT_GATE, fma, g.reps - 1, row), str(r)
     stages = {}
     setup.prove_dev(d_good, d_m)                     # first proof: the workspace reservation
     prove_ms, prove_all = median3(timed(lambda: stages.update(setup.prove_dev(d_good, d_m)[1])))

@@ -72,14 +72,14 @@ def main():
     setup.check_copy_constraints(d_good)             # first call: the scratch allocation
     ok_ms, ok_all = median3(timed(lambda: reports.__setitem__("ok", setup.check_copy_constraints(d_good))))
     bad_ms, bad_all = median3(timed(lambda: reports.__setitem__("bad", setup.check_copy_constraints(d_bad))))
-    assert reports["ok"].kind == 0 and reports["ok"].failures == (0, 0, 0, 0), str(reports["ok"])
+    assert reports["ok"].kind == E.binding.COPY_OK and reports["ok"].failures == (0, 0, 0, 0), str(reports["ok"])
     r = reports["bad"]
-    assert r.kind == 3 and r.failures[3] == 2 and (0, row) in ((r.column, r.row), (r.partner_column, r.partner_row)), str(r)
+    assert r.kind == E.binding.COPY_VALUE_MISMATCH and r.failures[3] == 2 and (0, row) in ((r.column, r.row), (r.partner_column, r.partner_row)), str(r)
     decode_only()
     dec_ms, dec_all = median3(decode_only)
     setup.check_satisfied_dev(d_good, d_m)
     sat_ms, sat_all = median3(timed(lambda: reports.__setitem__("sat", setup.check_satisfied_dev(d_good, d_m))))
-    assert reports["sat"].kind == 0, str(reports["sat"])
+    assert reports["sat"].kind == E.binding.SAT, str(reports["sat"])
     rounds = [(i, min(4, log_n - i)) for i in range(0, log_n, 4)]
     products = log_n + 1 + sum(log_n - i - w + 1 for i, w in rounds)
     res = {"what": "bj_check_copy_constraints next to bj_check_satisfied, real SHA-256 circuit, witness resident, median of 3, measured on this run",

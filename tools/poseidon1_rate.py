@@ -25,8 +25,9 @@ import torch
 
 import era_boojum_amd as E
 
-VALU_PER_PERM = {1: 8588, 4: 20988}      # Poseidon2 (generated stream), v1 (poseidon1.hip): counted in the gfx950 ISA
-NAMES = {1: "poseidon2", 4: "poseidon"}
+P2, V1 = E.binding.HASHER_KINDS["poseidon2"], E.binding.HASHER_KINDS["poseidon"]      # BJ_HASHER_*
+VALU_PER_PERM = {P2: 8588, V1: 20988}      # Poseidon2 (generated stream), v1 (poseidon1.hip): counted in the gfx950 ISA
+NAMES = {P2: "poseidon2", V1: "poseidon"}
 
 
 def _stats(xs):
@@ -58,7 +59,7 @@ def trees(ctx, reps, log_leaves=25, width=93, cap=16):
             b, n = one(h)
             res[h]["build"].append(b)
             res[h]["nodes"].append(n)
-    ctx.set_tree_hasher(1)
+    ctx.set_tree_hasher(P2)
     out = {}
     perms_per_leaf = (width + 7) // 8
     for h, name in NAMES.items():
@@ -86,8 +87,8 @@ def proofs(ctx, reps):
     dev = torch.device("cuda", 0)
     d_v = torch.from_numpy(np.ascontiguousarray(c.variables).view(np.int64)).to(dev)
     d_m = torch.from_numpy(np.ascontiguousarray(c.multiplicities).view(np.int64)).to(dev)
-    setups = {1: E.ProverSetup(ctx, c, 8, 16, 100, transcript="poseidon2"),
-              4: E.ProverSetup(ctx, c, 8, 16, 100, transcript="poseidon", tree_hasher="poseidon")}
+    setups = {P2: E.ProverSetup(ctx, c, 8, 16, 100, transcript="poseidon2"),
+              V1: E.ProverSetup(ctx, c, 8, 16, 100, transcript="poseidon", tree_hasher="poseidon")}
     times = {h: [] for h in setups}
     last = None
     for h, s in setups.items():   # warm-up
@@ -98,14 +99,14 @@ def proofs(ctx, reps):
             t = time.perf_counter()
             buf, _ = s.prove_dev(d_v.data_ptr(), d_m.data_ptr())
             times[h].append((time.perf_counter() - t) * 1e3)
-            if h == 4:
+            if h == V1:
                 last = buf.copy()
     import poseidon1_layer as PL
     from oracle import prover as OP
     from oracle import verifier as OV
     layer = PL.poseidon1_layer()
     OP.hashing_layer = lambda hasher: layer
-    ok = bool(OV.verify(OV.VerificationKey(c, setups[4].cap(), 8, 16), proof_format.parse(last, security_level=100), transcript_kind=2))
+    ok = bool(OV.verify(OV.VerificationKey(c, setups[V1].cap(), 8, 16), proof_format.parse(last, security_level=100), transcript_kind=setups[V1].transcript_kind))
     n = 1 << c.log_n
     out = {"log_n": c.log_n, "synthesis_s": round(synth_s, 1), "v1_proof_verified": ok}
     for h, name in NAMES.items():
