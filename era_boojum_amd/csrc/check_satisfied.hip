@@ -157,13 +157,15 @@ int check_impl(bj_ctx *ctx, const bj_setup *S, const u64 *d_variables, const u64
     }
 
     // ---- gates, phase 1 ----
+    const bj::Cols trace_vars{d_variables, n}, trace_consts{d_consts, n};
+    const bj::TermSink general{d_alpha, n, t0, t1}, spec{d_alpha + 2 * (size_t)n_gate_terms, n, t0, t1};
     if (n_gate_terms) {
-        bj::launch_circuit_gates(ctx, S, d_variables, n, d_consts, n, n, d_alpha, nullptr, t0, t1, st, bj::GATES_GENERAL);
+        bj::launch_circuit_gates(ctx, S, trace_vars, trace_consts, &general, nullptr, st);
         hipLaunchKernelGGL(nonzero_rows_kernel, dim3(blocks_for(n)), dim3(CHECK_BLOCK), 0, st, t0, t1, n, ctr + 0, ctr + 1);
     }
     if (n_spec_terms) {
         BJ_HIP(ctx, hipMemsetAsync(t0, 0, 2 * n * 8, st));
-        bj::launch_circuit_gates(ctx, S, d_variables, n, d_consts, n, n, nullptr, d_alpha + 2 * (size_t)n_gate_terms, t0, t1, st, bj::GATES_SPECIALIZED);
+        bj::launch_circuit_gates(ctx, S, trace_vars, trace_consts, nullptr, &spec, st);
         hipLaunchKernelGGL(nonzero_rows_kernel, dim3(blocks_for(n)), dim3(CHECK_BLOCK), 0, st, t0, t1, n, ctr + 2, ctr + 3);
     }
     BJ_CHECK_LAUNCH(ctx);
@@ -254,12 +256,9 @@ int check_impl(bj_ctx *ctx, const bj_setup *S, const u64 *d_variables, const u64
         BJ_HIP(ctx, hipMemsetAsync(tb, 0, todo.size() * 2 * B * 8, st));
     }
     for (size_t i = 0; i < todo.size(); i++) {
-        const u64 *a = d_unit + 2 * ((size_t)M - todo[i].k);
-        u64 *o0 = tb + i * 2 * B, *o1 = o0 + B;
-        if (kind == BJ_UNSAT_GATE)
-            bj::launch_circuit_gates(ctx, S, row_v, B, row_c, B, B, a, nullptr, o0, o1, st, bj::GATES_GENERAL);
-        else
-            bj::launch_circuit_gates(ctx, S, row_v, B, row_c, B, B, nullptr, a, o0, o1, st, bj::GATES_SPECIALIZED);
+        const bj::TermSink one{d_unit + 2 * ((size_t)M - todo[i].k), B, tb + i * 2 * B, tb + i * 2 * B + B};   // the category's first power
+        const bool is_general = kind == BJ_UNSAT_GATE;
+        bj::launch_circuit_gates(ctx, S, bj::Cols{row_v, B}, bj::Cols{row_c, B}, is_general ? &one : nullptr, is_general ? nullptr : &one, st);
     }
     BJ_CHECK_LAUNCH(ctx);
     std::vector<u64> h_tb(todo.size() * 2 * B);

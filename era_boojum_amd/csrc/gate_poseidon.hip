@@ -5,7 +5,7 @@
 // recorded operations with their temporaries in scratch memory; here the state stays in registers and the terms go straight into
 // the alpha-weighted gl::Acc160 accumulators (~10x fewer instructions per LDE point).  Same terms (as canonical residues), same
 // order, same proof.
-#include "../../include/boojum_hip.h"
+#include "gate_launch.h"
 #include "gl.h"
 #include "kernels.h"
 #include "poseidon_gate_terms.h"
@@ -56,14 +56,10 @@ quotient_poseidon_flattened_kernel(const u64 *vars, size_t var_stride, const u64
 
 }  // namespace
 
-void launch_quotient_poseidon_gate(int kind, const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
-                                   unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q, u64 *d_out0,
-                                   u64 *d_out1, hipStream_t s) {
-    unsigned bits = 0;
-    for (unsigned b = 0; b < path_len; b++) bits |= (path[b] ? 1u : 0u) << b;
-    const auto kernel = kind == BJ_GATE_POSEIDON2_FLATTENED ? quotient_poseidon2_flattened_kernel : quotient_poseidon_flattened_kernel;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, d_vars, var_stride, d_consts, const_stride,
-                       path_len, bits, d_alphas, Q, d_out0, d_out1);
+void launch_quotient_poseidon_gate(const GateShape &G, const GateCols &cols, const TermSink &out, hipStream_t s) {
+    const auto kernel = G.kind == BJ_GATE_POSEIDON2_FLATTENED ? quotient_poseidon2_flattened_kernel : quotient_poseidon_flattened_kernel;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((out.points + 255) / 256)), dim3(256), 0, s, cols.vars.p, cols.vars.stride, cols.consts.p,
+                       cols.consts.stride, G.path_len, path_bits(G), out.powers(G.first_term), out.points, out.out0, out.out1);
 }
 
 }  // namespace bj

@@ -31,19 +31,15 @@ struct DevProgram {
 };
 // the canonical program in the interpreter's packed form (operands kind << 28 | slot or index, OP_WRITE pseudo relations)
 void pack_program(const canon::Program &C, std::vector<DevRelation> *rel, std::vector<gl::u64> *values);
-// quotient mode (d_alphas != nullptr): out += selector * sum alpha * term; stand-alone mode (d_terms != nullptr): raw terms
-void launch_gate_program(const DevProgram &P, const gl::u64 *d_vars, size_t var_stride, const gl::u64 *d_consts,
-                         size_t const_stride, unsigned path_len, const unsigned char *path, unsigned reps,
-                         unsigned rep_var_stride, unsigned rep_const_stride, const gl::u64 *d_alphas, size_t Q,
-                         gl::u64 *d_out0, gl::u64 *d_out1, gl::u64 *d_terms, hipStream_t s, const gl::u64 *d_wits = nullptr,
-                         unsigned rep_wit_stride = 0);
-// the op-list gates of a gate list (quotient mode); programs[g] belongs to gates[g], d_alphas is the list's first power
-void launch_gate_programs(const GateShape *gates, const DevProgram *programs, unsigned n, const gl::u64 *d_vars, size_t var_stride,
-                          const gl::u64 *d_consts, size_t const_stride, const gl::u64 *d_alphas, size_t Q, gl::u64 *d_out0,
-                          gl::u64 *d_out1, hipStream_t s, const gl::u64 *d_wits);
+// The launchers below take the columns and the destination as term_io.h's descriptors; out.d_alphas is the first power of the
+// gates' category, as everywhere (TermSink).
+// gate G with op list P.  Quotient mode (out.d_alphas != nullptr): out += selector * sum alpha * term; stand-alone mode
+// (d_terms != nullptr): raw terms [reps * n_writes][out.points]
+void launch_gate_program(const DevProgram &P, const GateShape &G, const GateCols &cols, const TermSink &out, gl::u64 *d_terms, hipStream_t s);
+// the op-list gates of a gate list (quotient mode); programs[g] belongs to gates[g]
+void launch_gate_programs(const GateShape *gates, const DevProgram *programs, unsigned n, const GateCols &cols, const TermSink &out, hipStream_t s);
 // quotient.hip: every evaluator of a list of gates over general-purpose columns; probe_bytes: algorithmic bytes of the
 // hand-written launch, for the kernel probe of a proof
-void launch_general_gates(bj_ctx *ctx, const GateShape *gates, const DevProgram *programs, unsigned n_gates, const gl::u64 *d_vars,
-                          size_t var_stride, const gl::u64 *d_consts, size_t const_stride, const gl::u64 *d_wits, const gl::u64 *d_alphas,
-                          size_t points, gl::u64 *t0, gl::u64 *t1, hipStream_t st, double probe_bytes);
+void launch_general_gates(bj_ctx *ctx, const GateShape *gates, const DevProgram *programs, unsigned n_gates, const GateCols &cols,
+                          const TermSink &out, hipStream_t st, double probe_bytes);
 }  // namespace bj

@@ -6,7 +6,7 @@
 #include "ctx.h"
 #include "gate_canon.h"
 #include "gate_jit.h"
-#include "gate_program.h"
+#include "gate_launch.h"
 #include "gate_program_dev.h"
 #include <algorithm>
 #include <cstdlib>
@@ -143,27 +143,10 @@ void DevProgram::release() {
     block = nullptr;
 }
 
-static ProgArgs make_prog_args(const DevProgram &P, const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
-                               unsigned path_len, const unsigned char *path, unsigned reps, unsigned rep_var_stride,
-                               unsigned rep_const_stride, const u64 *d_alphas, size_t Q, u64 *d_out0, u64 *d_out1, u64 *d_terms,
-                               const u64 *d_wits, unsigned rep_wit_stride) {
-    ProgArgs a{};
-    a.wits = d_wits; a.rep_wit_stride = rep_wit_stride;
-    a.vars = d_vars; a.var_stride = var_stride; a.consts = d_consts; a.const_stride = const_stride;
-    a.rel = P.d_rel; a.values = P.d_values; a.n_rel = P.n_rel; a.n_writes = P.n_writes;
-    a.path_len = path_len;
-    for (unsigned b = 0; b < 8; b++) a.path[b] = b < path_len ? path[b] : 0;
-    a.reps = reps; a.rep_var_stride = rep_var_stride; a.rep_const_stride = rep_const_stride;
-    a.alphas = d_alphas; a.Q = Q; a.out0 = d_out0; a.out1 = d_out1; a.terms = d_terms;
-    return a;
-}
-
 // the op-list gates of one circuit, quotient mode: the ones with a generated body go out as ONE fused launch when there are
 // at least two of them (they all sweep the same general-purpose columns), everything else one launch per gate as before
-void launch_gate_programs(const GateShape *gates, const DevProgram *programs, unsigned n, const u64 *d_vars, size_t var_stride,
-                          const u64 *d_consts, size_t const_stride, const u64 *d_alphas, size_t Q, u64 *d_out0, u64 *d_out1, hipStream_t s,
-                          const u64 *d_wits) {
-    if (!Q) return;
+void launch_gate_programs(const GateShape *gates, const DevProgram *programs, unsigned n, const GateCols &cols, const TermSink &out, hipStream_t s) {
+    if (!out.points) return;
     const bool no_aot = bj::env().gate_no_aot, no_fuse = bj::env().gate_no_fuse;
     std::vector<unsigned> fused;
     if (!no_aot && !no_fuse)
@@ -178,38 +161,31 @@ void launch_gate_programs(const GateShape *gates, const DevProgram *programs, un
         std::vector<ProgArgs> args;
         std::vector<uint64_t> hs, cs;
         for (unsigned i : fused) {
-            const GateShape &G = gates[i];
-            args.push_back(make_prog_args(programs[i], d_vars, var_stride, d_consts, const_stride, G.path_len, G.path, G.reps, G.var_stride,
-                                          G.const_stride, d_alphas + 2 * (size_t)G.first_term, Q, d_out0, d_out1, nullptr, nullptr, 0));
+            args.push_back(prog_args(programs[i], gates[i], cols, out, nullptr));
             hs.push_back(programs[i].fp[0]);
             cs.push_back(programs[i].fp[1]);
         }
-        done_fused = launch_gate_aot_fused(hs.data(), cs.data(), args.data(), (unsigned)args.size(), (unsigned)((Q + 255) / 256), s);
+        done_fused = launch_gate_aot_fused(hs.data(), cs.data(), args.data(), (unsigned)args.size(), (unsigned)((out.points + 255) / 256), s);
     }
-    for (unsigned i = 0; i < n; i++) {
-        const GateShape &G = gates[i];
-        if (G.kind != BJ_GATE_PROGRAM || (done_fused && std::find(fused.begin(), fused.end(), i) != fused.end())) continue;
-        launch_gate_program(programs[i], d_vars, var_stride, d_consts, const_stride, G.path_len, G.path, G.reps, G.var_stride, G.const_stride,
-                            d_alphas + 2 * (size_t)G.first_term, Q, d_out0, d_out1, nullptr, s, d_wits, G.wit_stride);
-    }
+    for (unsigned i = 0; i < n; i++)
+        if (gates[i].kind == BJ_GATE_PROGRAM && !(done_fused && std::find(fused.begin(), fused.end(), i) != fused.end()))
+            launch_gate_program(programs[i], gates[i], cols, out, nullptr, s);
 }
 
-void launch_gate_program(const DevProgram &P, const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
-                         unsigned path_len, const unsigned char *path, unsigned reps, unsigned rep_var_stride,
-                         unsigned rep_const_stride, const u64 *d_alphas, size_t Q, u64 *d_out0, u64 *d_out1, u64 *d_terms,
-                         hipStream_t s, const u64 *d_wits, unsigned rep_wit_stride) {
-    const ProgArgs a = make_prog_args(P, d_vars, var_stride, d_consts, const_stride, path_len, path, reps, rep_var_stride,
-                                      rep_const_stride, d_alphas, Q, d_out0, d_out1, d_terms, d_wits, rep_wit_stride);
-    if (!Q) return;
-    const dim3 grid((unsigned)((Q + 255) / 256)), block(256);
+void launch_gate_program(const DevProgram &P, const GateShape &G, const GateCols &cols, const TermSink &out, u64 *d_terms, hipStream_t s) {
+    if (!out.points) return;
+    const ProgArgs a = prog_args(P, G, cols, out, d_terms);
+    const dim3 grid((unsigned)((out.points + 255) / 256)), block(256);
     const bool no_aot = bj::env().gate_no_aot;
     if (!no_aot && launch_gate_aot(P.fp[0], P.fp[1], a, grid.x, s)) return;   // a build-time generated straight-line kernel
     // the reference's own captures of the two flattened Poseidon gates: the hand-written evaluators of gate_poseidon.hip
     // (quotient mode, one repetition)
     const int poseidon = gate_is_poseidon2_flattened(P.fp[0], P.fp[1]) ? BJ_GATE_POSEIDON2_FLATTENED
                          : gate_is_poseidon_flattened(P.fp[0], P.fp[1]) ? BJ_GATE_POSEIDON_FLATTENED : 0;
-    if (!no_aot && d_alphas && !d_terms && reps == 1 && poseidon) {
-        launch_quotient_poseidon_gate(poseidon, d_vars, var_stride, d_consts, const_stride, path_len, path, d_alphas, Q, d_out0, d_out1, s);
+    if (!no_aot && out.d_alphas && !d_terms && G.reps == 1 && poseidon) {
+        GateShape H = G;
+        H.kind = poseidon;
+        launch_quotient_poseidon_gate(H, cols, out, s);
         return;
     }
     if (P.jit && launch_jit_gate(P.jit, a, grid.x, s)) return;                // compiled from this very op list at upload
@@ -251,8 +227,11 @@ extern "C" int bj_gate_program_eval(bj_ctx *ctx, const bj_gate_program *program,
         P.release();
         return rc;
     }
-    bj::launch_gate_program(P, d_vars, var_stride, d_consts ? d_consts : d_vars, const_stride, 0, nullptr, num_repetitions,
-                            rep_var_stride, rep_const_stride, nullptr, n_points, nullptr, nullptr, d_terms, ctx->stream);
+    bj::GateShape G;   // no selector path, no alpha powers: the raw terms of every repetition
+    G.kind = BJ_GATE_PROGRAM;
+    G.reps = num_repetitions; G.var_stride = rep_var_stride; G.const_stride = rep_const_stride; G.num_terms = P.n_writes;
+    const bj::GateCols cols{{d_vars, var_stride}, {d_consts ? d_consts : d_vars, const_stride}, nullptr};
+    bj::launch_gate_program(P, G, cols, bj::TermSink{nullptr, n_points, nullptr, nullptr}, d_terms, ctx->stream);
     int rc = BJ_OK;
     if (hipGetLastError() != hipSuccess) rc = bj::fail(ctx, BJ_ERR_HIP, "bj_gate_program_eval: launch failed");
     (void)hipStreamSynchronize(ctx->stream);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "callee_words.h"
+#include "term_io.h"
 #include <stddef.h>
 #include <stdint.h>
 #include <string>
@@ -100,26 +101,20 @@ void launch_fri_fold(const u64 *d_c0, const u64 *d_c1, size_t len, u64 *d_o0, u6
                      u64 coset_inv, u64 ch0, u64 ch1, hipStream_t s);
 void launch_fri_fold_step(const u64 *d_c0, const u64 *d_c1, size_t len, unsigned k, u64 *d_o0, u64 *d_o1,
                           const u64 *d_roots, u64 coset_inv, u64 ch0, u64 ch1, hipStream_t s, size_t j0 = 0);
-// stage2.hip.  d_tmp: copy_perm_stage2_scratch_words(ceil(V / chunk), n) words
-void launch_copy_perm_stage2(const u64 *d_vars, size_t var_stride, const u64 *d_sigmas, size_t sig_stride,
-                             const u64 *d_non_res, unsigned V, unsigned chunk, unsigned log_n, const u64 *d_tw_fwd,
-                             const u64 *beta, const u64 *gamma, u64 *d_tmp, u64 *d_z, u64 *d_partials, hipStream_t s, bool small_non_residues);
-void launch_lookup_polys(const u64 *d_lvars, size_t var_stride, const u64 *d_table_id, const u64 *d_tables,
-                         size_t tab_stride, const u64 *d_mult, unsigned reps, unsigned w, unsigned log_n,
-                         const u64 *beta, const u64 *gamma, u64 *d_A, u64 *d_B, hipStream_t s);
-// quotient.hip: the hand-written kinds of a gate list (gate_list.h) in one launch; the other kinds only keep their alpha powers
+// stage2.hip and quotient.hip: the term kernels of rounds 2 and 3, given launch descriptors (term_io.h).
+// d_tmp: copy_perm_stage2_scratch_words(ceil(V / chunk), n) words; d_z [2][n], d_partials [(n_chunks - 1)][2][n]
+void launch_copy_perm_stage2(const CopyPermArg &cp, u64 *d_tmp, u64 *d_z, u64 *d_partials, hipStream_t s);
+void launch_lookup_polys(const LookupArg &l, unsigned log_n, u64 *d_A, u64 *d_B, hipStream_t s);
+// the hand-written kinds of a gate list (gate_list.h) in one launch, OVERWRITING out; the other kinds only keep their alpha powers
 struct GateShape;
-void launch_quotient_gates(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride, const GateShape *gates,
-                           unsigned n_gates, const u64 *d_alphas, size_t Q, u64 *d_out0, u64 *d_out1, hipStream_t s);
-void launch_quotient_lookup(const u64 *d_lvars, size_t var_stride, const u64 *d_table_id, const u64 *d_tables,
-                            size_t tab_stride, const u64 *d_mult, const u64 *d_A, const u64 *d_B, size_t s2_stride,
-                            unsigned reps, unsigned w, const u64 *lbeta, const u64 *lgamma, const u64 *d_alphas,
-                            size_t Q, u64 *d_out0, u64 *d_out1, hipStream_t s);
-void launch_quotient_copy_perm(const u64 *d_vars, size_t var_stride, const u64 *d_sigmas, size_t sig_stride,
-                               const u64 *d_stage2, size_t s2_stride, const u64 *d_non_res, unsigned V, unsigned chunk,
-                               unsigned log_n, unsigned log_L, const u64 *d_tw_fwd, const u64 *beta, const u64 *gamma,
-                               const u64 *alpha_l1, const u64 *d_alphas_cp, size_t Q_local, size_t I0, const u64 *d_inv_xm1, u64 *d_out0,
-                               u64 *d_out1, hipStream_t s, bool small_non_residues);
+void launch_quotient_gates(const GateCols &cols, const GateShape *gates, unsigned n_gates, const TermSink &out, hipStream_t s);
+// out += the lookup terms; d_A [2 * reps] and d_B [2] columns at s2_stride
+void launch_quotient_lookup(const LookupArg &l, const u64 *d_A, const u64 *d_B, size_t s2_stride, const TermSink &out, hipStream_t s);
+// out = (out + alpha_L1 * (z - 1) * L1~ + copy-permutation chain) / (x^n - 1) on points [I0, I0 + out.points) of the LDE of 2^log_L
+// cosets; stage2: z and the partial products; out.d_alphas: the chunk powers (the power behind h_alpha_l1's);
+// d_inv_xm1: 1 / (x - 1) per local point, or null (computed in the kernel)
+void launch_quotient_copy_perm(const CopyPermArg &cp, Cols stage2, unsigned log_L, const u64 *h_alpha_l1, const TermSink &out, size_t I0,
+                               const u64 *d_inv_xm1, hipStream_t s);
 void launch_inv_x_minus_one(const u64 *d_tw_fwd, size_t Q, size_t I0, u64 *d_out, hipStream_t s);
 bool launch_combine_residues(const u64 *d_residues, unsigned W, size_t E, unsigned n_cols, const u64 *h_a, u64 *d_out, hipStream_t s);
 void launch_gather_rows(const u64 *d_base, size_t col_stride, unsigned n_cols, const u64 *d_idx, unsigned n_idx,
@@ -128,10 +123,9 @@ void launch_merkle_paths(const u64 *d_tree, size_t num_leaves, unsigned depth, c
                          u64 *d_out, hipStream_t s);
 void launch_gather_fri_leaves(const u64 *d_c0, const u64 *d_c1, unsigned log_e, const u64 *d_leaf_idx, unsigned n_idx,
                               u64 *d_out, hipStream_t s);
-// gate_poseidon.hip; kind: BJ_GATE_POSEIDON2_FLATTENED or BJ_GATE_POSEIDON_FLATTENED
-void launch_quotient_poseidon_gate(int kind, const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
-                                   unsigned path_len, const unsigned char *path, const u64 *d_alphas, size_t Q, u64 *d_out0,
-                                   u64 *d_out1, hipStream_t s);
+// gate_poseidon.hip: out += the gate's terms; G.kind: BJ_GATE_POSEIDON2_FLATTENED or BJ_GATE_POSEIDON_FLATTENED.  Quotient mode only:
+// out.d_alphas must not be null (the kernels have no stand-alone term mode)
+void launch_quotient_poseidon_gate(const GateShape &G, const GateCols &cols, const TermSink &out, hipStream_t s);
 // openings.hip
 void launch_barycentric_weights(u64 *d_w0, u64 *d_w1, const u64 *d_tw_fwd, unsigned log_n, u64 coset, const u64 *at,
                                 hipStream_t s);

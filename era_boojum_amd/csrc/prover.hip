@@ -166,27 +166,6 @@ int bj_proof_stage_ms(const bj_proof *p, float *out8) {
 
 }  // extern "C"
 
-namespace bj {
-// Every gate evaluator of the circuit over `points` points of caller-given columns (the quotient stage runs it on the LDE, the
-// satisfiability check on the trace itself): GATES_GENERAL OVERWRITES (t0, t1) with the hand-written kinds' sum and adds the
-// Poseidon evaluators and the op-list gates over general-purpose columns; GATES_SPECIALIZED ADDS the gates over specialized
-// columns.  a_gates / a_spec: one F_p^2 power per (gate, repetition, term) in evaluator order.
-void launch_circuit_gates(bj_ctx *ctx, const bj_setup *S, const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride,
-                          size_t points, const u64 *a_gates, const u64 *a_spec, u64 *t0, u64 *t1, hipStream_t st, unsigned parts) {
-    if (parts & GATES_GENERAL)   // gate evaluation, SURVEY §8d: 8 (V + consts) qn + 16 qn — V = the general-purpose columns the gates read
-        bj::launch_general_gates(ctx, S->gates.general.data(), S->programs.data(), (unsigned)S->gates.general.size(), d_vars, var_stride,
-                                 d_consts, const_stride, S->Wc ? d_vars + (size_t)S->V * var_stride : nullptr, a_gates, points, t0, t1, st,
-                                 8.0 * (S->num_gp_vars + S->nC) * (double)points + 16.0 * (double)points);
-    if (parts & GATES_SPECIALIZED)   // gates over specialized columns: every row, no selector
-        for (size_t g = 0; g < S->gates.spec.size(); g++) {
-            const bj::GateShape &G = S->gates.spec[g];
-            bj::launch_gate_program(S->spec_programs[g], d_vars + (size_t)G.first_col * var_stride, var_stride,
-                                    d_consts + (size_t)G.first_const * const_stride, const_stride, 0, G.path, G.reps, G.var_stride,
-                                    G.const_stride, a_spec + 2 * (size_t)G.first_term, points, t0, t1, nullptr, st);
-        }
-}
-}  // namespace bj
-
 namespace {
 // bj_prove: the witness is still in host memory when the proof starts.  Its columns are copied in groups on a second stream,
 // every group followed by an event; the witness round below waits for a group right before it transforms it, so the PCIe
@@ -459,14 +438,15 @@ int Proving::round2_stage2() {
     bj::TmpBuf s2_nat, tmp;
     if ((rc = s2_nat.take(ctx, bj::WS_S2_NAT))) return rc;
     if ((rc = tmp.take(ctx, bj::WS_S2_SCRATCH))) return rc;
-    bj::launch_copy_perm_stage2(d_variables, n, S->d_nat + (size_t)L.sigma(0) * n, n, S->d_non_res, V, q, log_n, ctx->tw_fwd, beta, gamma, tmp.p,
-                                s2_nat.p + (size_t)L.z() * n, s2_nat.p + (size_t)L.partial(0) * n, st, S->small_non_residues);
+    const bj::Cols vars{d_variables, n}, nat{S->d_nat, n};
+    bj::launch_copy_perm_stage2(bj::CopyPermArg{vars, nat.at(L.sigma(0)), S->d_non_res, V, q, log_n, ctx->tw_fwd, beta, gamma, S->small_non_residues},
+                                tmp.p, s2_nat.p + (size_t)L.z() * n, s2_nat.p + (size_t)L.partial(0) * n, st);
     if (has_lookup) {
         challenge2(lbeta);
         challenge2(lgamma);
-        u64 *dA = s2_nat.p + (size_t)L.lookup_a(0) * n, *dB = s2_nat.p + (size_t)L.lookup_b() * n;
-        bj::launch_lookup_polys(d_variables + (size_t)L.lookup_var(0, 0) * n, n, S->tid_var ? nullptr : S->d_nat + (size_t)L.table_id() * n,
-                                S->d_nat + (size_t)L.table(0) * n, n, d_multiplicities, S->lookup_reps, S->lookup_w, log_n, lbeta, lgamma, dA, dB, st);
+        bj::launch_lookup_polys(bj::LookupArg{vars.at(L.lookup_var(0, 0)), nat.at(L.table(0)), S->tid_var ? nullptr : nat.at(L.table_id()).p,
+                                              d_multiplicities, S->lookup_reps, S->lookup_w, lbeta, lgamma},
+                                log_n, s2_nat.p + (size_t)L.lookup_a(0) * n, s2_nat.p + (size_t)L.lookup_b() * n, st);
     }
     BJ_CHECK_LAUNCH(ctx);
     if ((rc = s2_lde.take(ctx, bj::WS_S2_LDE))) return rc;
@@ -526,22 +506,22 @@ int Proving::round3_quotient() {
     u64 *t0 = Tl, *t1 = Tl + Qe;
     const u64 *a_lookup = d_alphas.p, *a_spec = d_alphas.p + 2 * n_lookup_terms, *a_gates = a_spec + 2 * n_spec_terms,
               *a_l1 = a_gates + 2 * n_gate_terms;
-    const u64 *d_sig_lde = S->d_lde + (size_t)L.sigma(0) * Ln, *d_con_lde = S->d_lde + (size_t)L.constant(0) * Ln;
-    if (Qe)
-        bj::launch_circuit_gates(ctx, S, wit_lde.p, Ln, d_con_lde, Ln, Qe, a_gates, a_spec, t0, t1, st,
-                                 bj::GATES_GENERAL | bj::GATES_SPECIALIZED);
-    if (has_lookup && Qe) {
-        const u64 *dA = s2_lde.p + (size_t)L.lookup_a(0) * Ln, *dB = s2_lde.p + (size_t)L.lookup_b() * Ln;
-        bj::launch_quotient_lookup(wit_lde.p + (size_t)L.lookup_var(0, 0) * Ln, Ln, S->tid_var ? nullptr : S->d_lde + (size_t)L.table_id() * Ln,
-                                   S->d_lde + (size_t)L.table(0) * Ln, Ln, wit_lde.p + (size_t)L.multiplicity() * Ln, dA, dB, Ln, S->lookup_reps, S->lookup_w, lbeta, lgamma,
-                                   a_lookup, Qe, t0, t1, st);
+    const bj::Cols wit{wit_lde.p, Ln}, setup{S->d_lde, Ln}, s2{s2_lde.p, Ln};
+    auto sink = [&](const u64 *d_powers) { return bj::TermSink{d_powers, Qe, t0, t1}; };
+    if (Qe) {
+        const bj::TermSink general = sink(a_gates), spec = sink(a_spec);
+        bj::launch_circuit_gates(ctx, S, wit, setup.at(L.constant(0)), &general, &spec, st);
     }
+    if (has_lookup && Qe)
+        bj::launch_quotient_lookup(bj::LookupArg{wit.at(L.lookup_var(0, 0)), setup.at(L.table(0)), S->tid_var ? nullptr : setup.at(L.table_id()).p,
+                                                 wit.at(L.multiplicity()).p, S->lookup_reps, S->lookup_w, lbeta, lgamma},
+                                   s2.at(L.lookup_a(0)).p, s2.at(L.lookup_b()).p, Ln, sink(a_lookup), st);
     if (Qe) {
         // variables + sigmas + z and the partial products + 1/(x - 1), accumulators read and written
         const int pc = bj::probe_begin(ctx, "quotient_copy_perm", 8.0 * (2.0 * V + 2 * (1 + L.n_partials) + 1) * (double)Qe + 32.0 * (double)Qe);
-        bj::launch_quotient_copy_perm(wit_lde.p, Ln, d_sig_lde, Ln, s2_lde.p, Ln, S->d_non_res, V, q, log_n, S->log_L, ctx->tw_fwd,
-                                      beta, gamma, alphas.data() + 2 * (n_lookup_terms + n_spec_terms + n_gate_terms), a_l1 + 2, Qe, I0, S->d_inv_xm1, t0, t1, st,
-                                      S->small_non_residues);
+        const u64 *h_alpha_l1 = alphas.data() + (a_l1 - d_alphas.p);   // the same power on the host: it goes into the kernel's arguments
+        bj::launch_quotient_copy_perm(bj::CopyPermArg{wit, setup.at(L.sigma(0)), S->d_non_res, V, q, log_n, ctx->tw_fwd, beta, gamma, S->small_non_residues},
+                                      s2, S->log_L, h_alpha_l1, sink(a_l1 + 2), I0, S->d_inv_xm1, st);
         bj::probe_end(ctx, pc);
     }
     BJ_CHECK_LAUNCH(ctx);

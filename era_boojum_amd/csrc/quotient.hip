@@ -12,9 +12,11 @@
 //   1 / (x^n - 1) per coset                         divide_by_vanishing_for_bitreversed_coset_enumeration utils.rs:770-817
 // One lane = one LDE point; consecutive lanes read consecutive addresses of every column (coalesced).  Sums of
 // challenge * term products are accumulated unreduced in 160-bit accumulators and reduced once.
-#include "gate_program.h"
+#include "gate_launch.h"
 #include "gl.h"
 #include "kernels.h"
+#include "lookup_challenges.h"
+#include "setup.h"
 
 #include <cstdlib>
 #include <utility>
@@ -27,18 +29,7 @@ namespace bj {
 // x_I = 7 * w_{qn}^{bitrev(I)} = 7 * T[I>>1] * (-1)^(I&1)
 __device__ __forceinline__ u64 lde_point(const u64 *tw, size_t I) { return gl::mul7(gl::domain_point(tw, I)); }
 
-struct GateDev {
-    int kind, path_len, reps, var_stride, const_stride, num_terms;
-    int path[6];
-};
-// the kinds the two kernels below evaluate themselves (bj_gate_kind); every kind from BJ_GATE_PROGRAM on has a kernel of its own
-constexpr int K_ALLOC = BJ_GATE_CONSTANT_ALLOCATOR, K_FMA = BJ_GATE_FMA_NO_CONSTANT, K_RED4 = BJ_GATE_REDUCTION4;
-constexpr int BJ_MAX_GATES = 16;   // evaluators over general-purpose columns per circuit (the golden proof's circuit has 11)
-struct GateSet {
-    GateDev g[BJ_MAX_GATES];
-    int n_gates;
-};
-
+// GateSet (gate_launch.h): the gates in list order
 // T = sum_g selector_g * sum_t alpha_t * term_t            (overwrites out)
 __global__ void __launch_bounds__(256)
 quotient_gates_kernel(const u64 *vars, size_t var_stride, const u64 *consts, size_t const_stride, GateSet gs,
@@ -107,13 +98,6 @@ quotient_gates_kernel(const u64 *vars, size_t var_stride, const u64 *consts, siz
 // Reduction<4> repetitions, twenty constant allocations), held in registers, and every gate evaluates its repetitions of the
 // window from there.  quotient_gates_kernel above reads the sixty general-purpose columns of the SHA-256 circuit once per
 // gate (PMC: 2.05 x the algorithmic bytes); this one reads them once.
-constexpr int GW_WINDOW = 20;
-struct GateWindows {
-    int present[BJ_GATE_NOP];   // by kind (K_ALLOC, K_FMA, K_RED4)
-    int path_len[BJ_GATE_NOP], path[BJ_GATE_NOP][6];
-    int reps[BJ_GATE_NOP], const_stride[BJ_GATE_NOP], aoff[BJ_GATE_NOP];
-    int n_windows, n_vars;
-};
 __global__ void __launch_bounds__(256)
 quotient_gates_windowed_kernel(const u64 *vars, size_t var_stride, const u64 *consts, size_t const_stride, GateWindows gw,
                                const u64 *alphas /* [n_terms][2] */, size_t Q, u64 *out0, u64 *out1) {
@@ -406,94 +390,61 @@ void launch_inv_x_minus_one(const u64 *d_tw_fwd, size_t Q, size_t I0, u64 *d_out
     if (Q) hipLaunchKernelGGL(inv_x_minus_one_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, d_tw_fwd, Q, I0, d_out);
 }
 
-void launch_quotient_gates(const u64 *d_vars, size_t var_stride, const u64 *d_consts, size_t const_stride, const GateShape *gates,
-                           unsigned n_gates, const u64 *d_alphas, size_t Q, u64 *d_out0, u64 *d_out1, hipStream_t s) {
-    if (bj::env().gates_windowed && n_gates <= (unsigned)BJ_MAX_GATES) {   // BJ_GATES_WINDOWED=0 selects the per-gate kernel (the tests run both)
-        // the windowed kernel when the hand-written kinds appear at most once each with their principal widths
-        GateWindows gw{};
-        bool ok = true;
-        int span = 0, n_hand = 0;
-        for (unsigned g = 0; ok && g < n_gates; g++) {
-            const GateShape &G = gates[g];
-            if (G.num_terms == 0 || G.kind >= BJ_GATE_PROGRAM) continue;   // no terms, or evaluated by its own kernel
-            const int width = (int)gate_kind_extent(G.kind).var_extent;
-            if (G.kind < K_ALLOC || G.kind >= BJ_GATE_NOP || gw.present[G.kind] || (int)G.var_stride != width || G.num_terms != 1 || G.path_len > 6 ||
-                (G.kind != K_ALLOC && G.const_stride != 0)) {
-                ok = false;
-                break;
-            }
-            gw.present[G.kind] = 1;
-            gw.path_len[G.kind] = (int)G.path_len;
-            for (int b = 0; b < 6; b++) gw.path[G.kind][b] = G.path[b];
-            gw.reps[G.kind] = (int)G.reps;
-            gw.const_stride[G.kind] = (int)G.const_stride;
-            gw.aoff[G.kind] = (int)G.first_term;
-            if ((int)G.reps * width > span) span = (int)G.reps * width;
-            n_hand++;
-        }
-        if (ok && n_hand > 0) {
-            gw.n_windows = (span + GW_WINDOW - 1) / GW_WINDOW;
-            gw.n_vars = span;
-            hipLaunchKernelGGL(quotient_gates_windowed_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, d_vars, var_stride,
-                               d_consts, const_stride, gw, d_alphas, Q, d_out0, d_out1);
-            return;
-        }
-    }
-    GateSet gs;   // the kernel walks the alpha powers itself, in list order
-    gs.n_gates = (int)n_gates;
-    for (unsigned g = 0; g < n_gates && g < (unsigned)BJ_MAX_GATES; g++) {
-        const GateShape &G = gates[g];
-        gs.g[g] = GateDev{G.kind, (int)G.path_len, (int)G.reps, (int)G.var_stride, (int)G.const_stride, (int)G.num_terms,
-                          {G.path[0], G.path[1], G.path[2], G.path[3], G.path[4], G.path[5]}};
-    }
-    hipLaunchKernelGGL(quotient_gates_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, d_vars, var_stride,
-                       d_consts, const_stride, gs, d_alphas, Q, d_out0, d_out1);
+void launch_quotient_gates(const GateCols &cols, const GateShape *gates, unsigned n_gates, const TermSink &out, hipStream_t s) {
+    const dim3 grid((unsigned)((out.points + 255) / 256)), block(256);
+    GateWindows gw;
+    // BJ_GATES_WINDOWED=0 selects the per-gate kernel (the tests run both)
+    if (bj::env().gates_windowed && n_gates <= (unsigned)BJ_MAX_GATES && gate_windows(gates, n_gates, &gw))
+        hipLaunchKernelGGL(quotient_gates_windowed_kernel, grid, block, 0, s, cols.vars.p, cols.vars.stride, cols.consts.p, cols.consts.stride, gw,
+                           out.d_alphas, out.points, out.out0, out.out1);
+    else
+        hipLaunchKernelGGL(quotient_gates_kernel, grid, block, 0, s, cols.vars.p, cols.vars.stride, cols.consts.p, cols.consts.stride,
+                           gate_set(gates, n_gates), out.d_alphas, out.points, out.out0, out.out1);
 }
 
-// Every evaluator over general-purpose columns at `points` points of caller-given columns: OVERWRITES (t0, t1) with the
-// hand-written kinds' sum, then the Poseidon evaluators and the op-list gates (seam S3) ADD theirs, each with its own slice of
-// d_alphas (one F_p^2 power per (gate, repetition, term) in evaluator order).  A proof's first call is the "quotient_gates" probe.
-void launch_general_gates(bj_ctx *ctx, const GateShape *gates, const DevProgram *programs, unsigned n_gates, const u64 *d_vars,
-                          size_t var_stride, const u64 *d_consts, size_t const_stride, const u64 *d_wits, const u64 *d_alphas,
-                          size_t points, u64 *t0, u64 *t1, hipStream_t st, double probe_bytes) {
+// Every evaluator over general-purpose columns: OVERWRITES out with the hand-written kinds' sum, then the Poseidon evaluators and
+// the op-list gates (seam S3) ADD theirs; out.d_alphas holds one F_p^2 power per (gate, repetition, term) in evaluator order.  A
+// proof's first call is the "quotient_gates" probe.
+void launch_general_gates(bj_ctx *ctx, const GateShape *gates, const DevProgram *programs, unsigned n_gates, const GateCols &cols,
+                          const TermSink &out, hipStream_t st, double probe_bytes) {
     const int pg = bj::probe_begin(ctx, "quotient_gates", probe_bytes);
-    launch_quotient_gates(d_vars, var_stride, d_consts, const_stride, gates, n_gates, d_alphas, points, t0, t1, st);
+    launch_quotient_gates(cols, gates, n_gates, out, st);
     bj::probe_end(ctx, pg);
-    for (unsigned g = 0; g < n_gates; g++) {
-        const GateShape &G = gates[g];
-        if (G.kind == BJ_GATE_POSEIDON2_FLATTENED || G.kind == BJ_GATE_POSEIDON_FLATTENED)
-            launch_quotient_poseidon_gate(G.kind, d_vars, var_stride, d_consts, const_stride, G.path_len, G.path,
-                                          d_alphas + 2 * (size_t)G.first_term, points, t0, t1, st);
-    }
+    for (unsigned g = 0; g < n_gates; g++)
+        if (gates[g].kind == BJ_GATE_POSEIDON2_FLATTENED || gates[g].kind == BJ_GATE_POSEIDON_FLATTENED)
+            launch_quotient_poseidon_gate(gates[g], cols, out, st);
     // the op-list gates: one fused launch for those with generated bodies (they all sweep the general-purpose columns)
-    launch_gate_programs(gates, programs, n_gates, d_vars, var_stride, d_consts, const_stride, d_alphas, points, t0, t1, st, d_wits);
+    launch_gate_programs(gates, programs, n_gates, cols, out, st);
 }
 
-void launch_quotient_lookup(const u64 *d_lvars, size_t var_stride, const u64 *d_table_id, const u64 *d_tables,
-                            size_t tab_stride, const u64 *d_mult, const u64 *d_A, const u64 *d_B, size_t s2_stride,
-                            unsigned reps, unsigned w, const u64 *lbeta, const u64 *lgamma, const u64 *d_alphas,
-                            size_t Q, u64 *d_out0, u64 *d_out1, hipStream_t s) {
-    LookupQArgs la;
-    la.beta = {gl::canon(lbeta[0]), gl::canon(lbeta[1])};
-    gl::e2 g{gl::canon(lgamma[0]), gl::canon(lgamma[1])};
-    la.gpow[0] = {1, 0};
-    for (unsigned j = 1; j <= w && j < 9; j++) la.gpow[j] = gl::e2_mul(la.gpow[j - 1], g);
-    hipLaunchKernelGGL(quotient_lookup_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, d_lvars, var_stride,
-                       d_table_id, d_tables, tab_stride, d_mult, d_A, d_B, s2_stride, reps, w, la, d_alphas, Q, d_out0,
-                       d_out1);
+// Every gate evaluator of the setup's circuit on caller-given columns (the quotient stage runs it on the LDE, the satisfiability
+// check on the trace itself).  general (null: skipped): launch_general_gates over the general-purpose columns, OVERWRITING; spec
+// (null: skipped): the gates over specialized columns ADD theirs — every row, no selector.
+void launch_circuit_gates(bj_ctx *ctx, const bj_setup *S, Cols vars, Cols consts, const TermSink *general, const TermSink *spec, hipStream_t st) {
+    if (general)   // 8 (V + consts) qn + 16 qn — V = the general-purpose columns the gates read
+        launch_general_gates(ctx, S->gates.general.data(), S->programs.data(), (unsigned)S->gates.general.size(),
+                             GateCols{vars, consts, S->Wc ? vars.at(S->V).p : nullptr}, *general, st,
+                             8.0 * (S->num_gp_vars + S->nC) * (double)general->points + 16.0 * (double)general->points);
+    for (size_t g = 0; spec && g < S->gates.spec.size(); g++) {
+        const GateShape &G = S->gates.spec[g];
+        launch_gate_program(S->spec_programs[g], G, GateCols{vars.at(G.first_col), consts.at(G.first_const), nullptr}, *spec, nullptr, st);
+    }
 }
 
-void launch_quotient_copy_perm(const u64 *d_vars, size_t var_stride, const u64 *d_sigmas, size_t sig_stride,
-                               const u64 *d_stage2, size_t s2_stride, const u64 *d_non_res, unsigned V, unsigned chunk,
-                               unsigned log_n, unsigned log_L, const u64 *d_tw_fwd, const u64 *beta, const u64 *gamma,
-                               const u64 *alpha_l1, const u64 *d_alphas_cp, size_t Q_local, size_t I0, const u64 *d_inv_xm1, u64 *d_out0,
-                               u64 *d_out1, hipStream_t s, bool small_non_residues) {
-    const size_t n = (size_t)1 << log_n, Q = Q_local;
+void launch_quotient_lookup(const LookupArg &l, const u64 *d_A, const u64 *d_B, size_t s2_stride, const TermSink &out, hipStream_t s) {
+    hipLaunchKernelGGL(quotient_lookup_kernel, dim3((unsigned)((out.points + 255) / 256)), dim3(256), 0, s, l.lvars.p, l.lvars.stride,
+                       l.d_table_id, l.tables.p, l.tables.stride, l.d_mult, d_A, d_B, s2_stride, l.reps, l.w, lookup_challenges<LookupQArgs>(l),
+                       out.d_alphas, out.points, out.out0, out.out1);
+}
+
+void launch_quotient_copy_perm(const CopyPermArg &cp, Cols stage2, unsigned log_L, const u64 *h_alpha_l1, const TermSink &out, size_t I0,
+                               const u64 *d_inv_xm1, hipStream_t s) {
+    const size_t n = (size_t)1 << cp.log_n;
     const unsigned L = 1u << log_L;   // cosets of the whole LDE domain; a GPU may hold any contiguous range of them
     CopyPermQArgs ca;
-    ca.beta = {gl::canon(beta[0]), gl::canon(beta[1])};
-    ca.gamma = {gl::canon(gamma[0]), gl::canon(gamma[1])};
-    ca.alpha_l1 = {gl::canon(alpha_l1[0]), gl::canon(alpha_l1[1])};
+    ca.beta = {gl::canon(cp.h_beta[0]), gl::canon(cp.h_beta[1])};
+    ca.gamma = {gl::canon(cp.h_gamma[0]), gl::canon(cp.h_gamma[1])};
+    ca.alpha_l1 = {gl::canon(h_alpha_l1[0]), gl::canon(h_alpha_l1[1])};
     // x^n on coset c: (7 * w_{Ln}^{bitrev_L(c)})^n = 7^n * w_L^{bitrev_L(c)}   (for c < q this is w_q^{bitrev_q(c)})
     const u64 g_n = gl::pow(gl::GEN, n);
     const u64 wq = gl::omega(log_L);
@@ -507,15 +458,12 @@ void launch_quotient_copy_perm(const u64 *d_vars, size_t var_stride, const u64 *
             ca.vanishing_inv[c] = 0;
         }
     }
-    const unsigned n_chunks = (V + chunk - 1) / chunk;
-    if (small_non_residues && !env().copy_perm_wide_k)
-        hipLaunchKernelGGL(quotient_copy_perm_kernel<true>, dim3((unsigned)((Q + 255) / 256)), dim3(256), (size_t)V * 8, s, d_vars, var_stride,
-                           d_sigmas, sig_stride, d_stage2, s2_stride, d_non_res, V, chunk, n_chunks, log_n, d_tw_fwd, ca,
-                           d_alphas_cp, Q, I0, d_inv_xm1, d_out0, d_out1);
-    else
-        hipLaunchKernelGGL(quotient_copy_perm_kernel<false>, dim3((unsigned)((Q + 255) / 256)), dim3(256), (size_t)V * 16, s, d_vars, var_stride,
-                           d_sigmas, sig_stride, d_stage2, s2_stride, d_non_res, V, chunk, n_chunks, log_n, d_tw_fwd, ca,
-                           d_alphas_cp, Q, I0, d_inv_xm1, d_out0, d_out1);
+    const unsigned n_chunks = (cp.V + cp.chunk - 1) / cp.chunk;
+    const bool small_k = cp.small_non_residues && !env().copy_perm_wide_k;   // LDS: [V] words of k_c, or [V][2] of k_c * beta
+    const auto kernel = small_k ? quotient_copy_perm_kernel<true> : quotient_copy_perm_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((out.points + 255) / 256)), dim3(256), (size_t)cp.V * (small_k ? 8 : 16), s, cp.vars.p, cp.vars.stride,
+                       cp.sigmas.p, cp.sigmas.stride, stage2.p, stage2.stride, cp.d_non_res, cp.V, cp.chunk, n_chunks, cp.log_n, cp.d_tw, ca,
+                       out.d_alphas, out.points, I0, d_inv_xm1, out.out0, out.out1);
 }
 
 // ----------------------------------------------------------------------------------------------- query gathers

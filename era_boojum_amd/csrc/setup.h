@@ -48,9 +48,7 @@ struct HasherGuard {
     ~HasherGuard() { c->hasher = saved; }
 };
 
-enum : unsigned { GATES_GENERAL = 1, GATES_SPECIALIZED = 2 };
-// prover.hip: every gate evaluator of the setup's circuit over `points` points of caller-given columns
-void launch_circuit_gates(bj_ctx *ctx, const bj_setup *S, const gl::u64 *d_vars, size_t var_stride, const gl::u64 *d_consts,
-                          size_t const_stride, size_t points, const gl::u64 *a_gates, const gl::u64 *a_spec, gl::u64 *t0, gl::u64 *t1,
-                          hipStream_t st, unsigned parts);
+// quotient.hip: every gate evaluator of the setup's circuit on caller-given columns; general OVERWRITES its sink with the gates over
+// general-purpose columns, spec ADDS the gates over specialized columns to its own; a null sink skips that part
+void launch_circuit_gates(bj_ctx *ctx, const bj_setup *S, Cols vars, Cols consts, const TermSink *general, const TermSink *spec, hipStream_t st);
 }  // namespace bj

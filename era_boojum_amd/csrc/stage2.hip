@@ -9,6 +9,7 @@
 // any association order: per-row products, a three-phase device-wide exclusive scan under F_p^2 multiplication.
 #include "gl.h"
 #include "kernels.h"
+#include "lookup_challenges.h"
 
 using gl::u64;
 using gl::u32;
@@ -184,22 +185,16 @@ scan_apply_partials_kernel(u64 *z0, u64 *z1, const u64 *block_pre, const u64 *Q,
 }
 
 // Driver.  d_tmp must hold 2*n_chunks*n + 2*ceil(n/1024) elements.  Outputs: d_z [2][n], d_partials [(n_chunks-1)][2][n].
-void launch_copy_perm_stage2(const u64 *d_vars, size_t var_stride, const u64 *d_sigmas, size_t sig_stride,
-                             const u64 *d_non_res, unsigned V, unsigned chunk, unsigned log_n, const u64 *d_tw_fwd,
-                             const u64 *beta, const u64 *gamma, u64 *d_tmp, u64 *d_z, u64 *d_partials, hipStream_t s,
-                             bool small_non_residues) {
-    const size_t n = (size_t)1 << log_n;
-    const unsigned n_chunks = (V + chunk - 1) / chunk;
-    gl::e2 b{gl::canon(beta[0]), gl::canon(beta[1])}, g{gl::canon(gamma[0]), gl::canon(gamma[1])};
+void launch_copy_perm_stage2(const CopyPermArg &cp, u64 *d_tmp, u64 *d_z, u64 *d_partials, hipStream_t s) {
+    const size_t n = (size_t)1 << cp.log_n;
+    const unsigned n_chunks = (cp.V + cp.chunk - 1) / cp.chunk;
+    gl::e2 b{gl::canon(cp.h_beta[0]), gl::canon(cp.h_beta[1])}, g{gl::canon(cp.h_gamma[0]), gl::canon(cp.h_gamma[1])};
     u64 *P = d_tmp;
     u64 *block_tot = d_tmp + (size_t)2 * n_chunks * n;
     const unsigned rb = (unsigned)((n + 255) / 256);
-    if (small_non_residues && !env().copy_perm_wide_k)
-        hipLaunchKernelGGL(copy_perm_rational_kernel<true>, dim3((unsigned)((n + 256 * RAT_PTS - 1) / (256 * RAT_PTS)), n_chunks), dim3(256), 0, s, d_vars, var_stride,
-                           d_sigmas, sig_stride, d_non_res, V, chunk, log_n, d_tw_fwd, b, g, P);
-    else
-        hipLaunchKernelGGL(copy_perm_rational_kernel<false>, dim3((unsigned)((n + 256 * RAT_PTS - 1) / (256 * RAT_PTS)), n_chunks), dim3(256), 0, s, d_vars, var_stride,
-                           d_sigmas, sig_stride, d_non_res, V, chunk, log_n, d_tw_fwd, b, g, P);
+    const auto kernel = cp.small_non_residues && !env().copy_perm_wide_k ? copy_perm_rational_kernel<true> : copy_perm_rational_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 256 * RAT_PTS - 1) / (256 * RAT_PTS)), n_chunks), dim3(256), 0, s, cp.vars.p, cp.vars.stride,
+                       cp.sigmas.p, cp.sigmas.stride, cp.d_non_res, cp.V, cp.chunk, cp.log_n, cp.d_tw, b, g, P);
     hipLaunchKernelGGL(chunk_prefix_kernel, dim3(rb), dim3(256), 0, s, P, n_chunks, n);
     const u64 *a0 = P + ((size_t)2 * (n_chunks - 1)) * n, *a1 = a0 + n;
     const size_t n_blocks = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
@@ -269,17 +264,10 @@ lookup_polys_kernel(const u64 *lvars, size_t var_stride, const u64 *table_id, co
     }
 }
 
-void launch_lookup_polys(const u64 *d_lvars, size_t var_stride, const u64 *d_table_id, const u64 *d_tables,
-                         size_t tab_stride, const u64 *d_mult, unsigned reps, unsigned w, unsigned log_n,
-                         const u64 *beta, const u64 *gamma, u64 *d_A, u64 *d_B, hipStream_t s) {
+void launch_lookup_polys(const LookupArg &l, unsigned log_n, u64 *d_A, u64 *d_B, hipStream_t s) {
     const size_t n = (size_t)1 << log_n;
-    LookupArgs a;
-    a.beta = {gl::canon(beta[0]), gl::canon(beta[1])};
-    gl::e2 g{gl::canon(gamma[0]), gl::canon(gamma[1])};
-    a.gpow[0] = {1, 0};
-    for (unsigned j = 1; j <= w && j < 9; j++) a.gpow[j] = gl::e2_mul(a.gpow[j - 1], g);
-    hipLaunchKernelGGL(lookup_polys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_lvars, var_stride,
-                       d_table_id, d_tables, tab_stride, d_mult, reps, w, n, a, d_A, d_B);
+    hipLaunchKernelGGL(lookup_polys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, l.lvars.p, l.lvars.stride,
+                       l.d_table_id, l.tables.p, l.tables.stride, l.d_mult, l.reps, l.w, n, lookup_challenges<LookupArgs>(l), d_A, d_B);
 }
 
 }  // namespace bj

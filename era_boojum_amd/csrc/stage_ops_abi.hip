@@ -35,8 +35,8 @@ int bj_copy_perm_stage2(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, 
     if (int rc = bj::h2d_async(ctx, nr.p, h_non_residues, 8 * (size_t)num_vars)) return rc;
     bool small_k = true;
     for (unsigned c = 0; c < num_vars; c++) small_k = small_k && gl::canon(h_non_residues[c]) < ((u64)1 << 32);
-    bj::launch_copy_perm_stage2(d_vars, var_stride, d_sigmas, sig_stride, nr.p, num_vars, chunk, log_n, ctx->tw_fwd,
-                                h_beta, h_gamma, tmp.p, d_z, partials, ctx->stream, small_k);
+    const bj::CopyPermArg cp{{d_vars, var_stride}, {d_sigmas, sig_stride}, nr.p, num_vars, chunk, log_n, ctx->tw_fwd, h_beta, h_gamma, small_k};
+    bj::launch_copy_perm_stage2(cp, tmp.p, d_z, partials, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }
@@ -51,8 +51,8 @@ int bj_lookup_polys(bj_ctx *ctx, const uint64_t *d_lookup_vars, size_t var_strid
     if (reps == 0 || width == 0 || width > 8 || log_n > 30) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_lookup_polys: bad geometry (width 1..8)");
     const size_t n = (size_t)1 << log_n;
     if (var_stride < n || table_stride < n) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_lookup_polys: column stride below n");
-    bj::launch_lookup_polys(d_lookup_vars, var_stride, d_table_id, d_tables, table_stride, d_multiplicities, reps, width, log_n,
-                            h_beta, h_gamma, d_A, d_B, ctx->stream);
+    const bj::LookupArg l{{d_lookup_vars, var_stride}, {d_tables, table_stride}, d_table_id, d_multiplicities, reps, width, h_beta, h_gamma};
+    bj::launch_lookup_polys(l, log_n, d_A, d_B, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }
@@ -103,8 +103,8 @@ int bj_quotient_gates(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, un
     int rc = al.alloc(ctx, 2 * (n_terms + 1));
     if (!rc && n_terms) rc = bj::h2d_async(ctx, al.p, h_alphas, 16 * n_terms);
     if (!rc) {
-        bj::launch_general_gates(ctx, L.general.data(), programs.data(), num_gates, d_vars, var_stride, d_consts, const_stride, nullptr,
-                                 al.p, num_points, d_out0, d_out1, ctx->stream, 0.0);
+        bj::launch_general_gates(ctx, L.general.data(), programs.data(), num_gates, bj::GateCols{{d_vars, var_stride}, {d_consts, const_stride}, nullptr},
+                                 bj::TermSink{al.p, num_points, d_out0, d_out1}, ctx->stream, 0.0);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = bj::fail(ctx, BJ_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     }
@@ -126,9 +126,8 @@ int bj_quotient_lookup(bj_ctx *ctx, const uint64_t *d_lookup_vars, size_t var_st
     bj::TmpBuf al(true);
     if (int rc = al.alloc(ctx, 2 * ((size_t)reps + 1))) return rc;
     if (int rc = bj::h2d_async(ctx, al.p, h_alphas, 16 * ((size_t)reps + 1))) return rc;
-    bj::launch_quotient_lookup(d_lookup_vars, var_stride, d_table_id, d_tables, table_stride, d_multiplicities, d_A, d_B,
-                               stage2_stride, reps, width, h_beta, h_gamma, al.p, num_points, d_out0, d_out1,
-                               ctx->stream);
+    const bj::LookupArg l{{d_lookup_vars, var_stride}, {d_tables, table_stride}, d_table_id, d_multiplicities, reps, width, h_beta, h_gamma};
+    bj::launch_quotient_lookup(l, d_A, d_B, stage2_stride, bj::TermSink{al.p, num_points, d_out0, d_out1}, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }
@@ -158,9 +157,9 @@ int bj_quotient_copy_perm(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride
     if (int rc = bj::h2d_async(ctx, al.p, h_alphas + 2, 16 * (size_t)n_chunks)) return rc;
     bool small_k = true;
     for (unsigned c = 0; c < num_vars; c++) small_k = small_k && gl::canon(h_non_residues[c]) < ((u64)1 << 32);
-    bj::launch_quotient_copy_perm(d_vars, var_stride, d_sigmas, sig_stride, d_stage2, stage2_stride, nr.p, num_vars,
-                                  chunk, log_n, log_lde, ctx->tw_fwd, h_beta, h_gamma, h_alphas, al.p, num_points,
-                                  first_point, nullptr, d_out0, d_out1, ctx->stream, small_k);
+    const bj::CopyPermArg cp{{d_vars, var_stride}, {d_sigmas, sig_stride}, nr.p, num_vars, chunk, log_n, ctx->tw_fwd, h_beta, h_gamma, small_k};
+    bj::launch_quotient_copy_perm(cp, bj::Cols{d_stage2, stage2_stride}, log_lde, h_alphas /* the L1 power; al: the chunks' that follow it */,
+                                  bj::TermSink{al.p, num_points, d_out0, d_out1}, first_point, nullptr, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }
