@@ -818,8 +818,7 @@ int bj_fri_fold(bj_ctx *ctx, const uint64_t *d_c0, const uint64_t *d_c1, size_t 
     if (log_full > 32 || len > ((size_t)1 << log_full))
         return fail(ctx, BJ_ERR_INVALID_ARG, "bj_fri_fold: array longer than the initial domain");
     if (int rc = ensure_twiddles(ctx, log_full, true)) return rc;
-    (void)log2_exact;
-    bj::launch_fri_fold(d_c0, d_c1, len, d_o0, d_o1, ctx->tw_inv, coset_inv, ch0, ch1, ctx->stream);
+    bj::launch_fri_fold_step(d_c0, d_c1, len, 1, d_o0, d_o1, ctx->tw_inv, coset_inv, ch0, ch1, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }

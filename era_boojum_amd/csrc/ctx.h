@@ -155,20 +155,10 @@ int placement_narrow(bj_ctx *ctx, const PlacementWorkspace &w, const gl::u64 *d_
 int placement_check(bj_ctx *ctx, const PlacementWorkspace &w);   // synchronises; BJ_ERR_UNSUPPORTED if the flag was raised
 int sigmas_from_keys(bj_ctx *ctx, const PlacementWorkspace &w, unsigned num_vars, unsigned log_n, const gl::u64 *h_non_residues,
                      gl::u64 *d_sigmas, size_t sig_stride);      // sorts keys[0] (destroyed) and scatters
-// openings_abi.hip: the DEEP stage on host-side lists of device columns
-int combine_monomials(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1, size_t n_src,
-                      const uint64_t *h_challenges, size_t n, uint64_t *d_out0, uint64_t *d_out1);
-int deep_accumulate_range(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1, size_t n_src,
-                          const uint64_t *h_values, const uint64_t *h_challenges, const uint64_t *at2, unsigned log_n,
-                          unsigned log_lde, size_t N_local, size_t I0, uint64_t *d_dst_c0, uint64_t *d_dst_c1,
-                          int accumulate);
-struct DeepSetHost {   // one opening set, host side: sources (device pointers), values and challenges as F_p^2 pairs, the point
-    const uint64_t *const *src_c0, *const *src_c1;
-    size_t n_src;
-    const uint64_t *values, *challenges, *at2;
-};
-int deep_accumulate_multi(bj_ctx *ctx, const DeepSetHost *sets, unsigned n_sets, unsigned log_n, unsigned log_lde, size_t N_local,
-                          size_t I0, uint64_t *d_dst_c0, uint64_t *d_dst_c1, int accumulate);
+// openings_abi.hip: the DEEP stage on column lists (opening_args.h); one argument block of L.words() words per call
+int combine_monomials(bj_ctx *ctx, const ColumnList &L, size_t n, uint64_t *d_out0, uint64_t *d_out1);
+int deep_accumulate_multi(bj_ctx *ctx, const ColumnList &L, unsigned log_n, unsigned log_lde, size_t N_local, size_t I0,
+                          uint64_t *d_dst_c0, uint64_t *d_dst_c1, int accumulate);
 // setup.hip: bj_setup_create[_sharded] with the sigma columns either from the host or written on the device by `fill_sigmas`
 // ([num_vars][n] at d_sigmas, called once the setup's buffers exist); a placement handed over is freed with the setup
 int setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const std::function<int(bj_setup *, gl::u64 *)> &fill_sigmas,

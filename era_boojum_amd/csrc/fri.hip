@@ -13,24 +13,6 @@ using gl::u64;
 
 namespace bj {
 
-__global__ void __launch_bounds__(256)
-fri_fold_kernel(const u64 *c0, const u64 *c1, u64 *o0, u64 *o1, const u64 *roots, size_t half, u64 coset_inv, u64 ch0,
-                u64 ch1) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    size_t stride = (size_t)gridDim.x * blockDim.x;
-    const gl::e2 alpha{ch0, ch1};
-    for (; i < half; i += stride) {
-        ulonglong2 p0 = reinterpret_cast<const ulonglong2 *>(c0)[i];
-        ulonglong2 p1 = reinterpret_cast<const ulonglong2 *>(c1)[i];
-        u64 a0 = gl::canon(p0.x), b0 = gl::canon(p0.y), a1 = gl::canon(p1.x), b1 = gl::canon(p1.y);
-        u64 r = gl::mul(gl::canon(roots[i]), coset_inv);
-        gl::e2 diff{gl::mul(gl::sub(a0, b0), r), gl::mul(gl::sub(a1, b1), r)};
-        gl::e2 m = gl::e2_mul(diff, alpha);
-        o0[i] = gl::add(gl::add(m.c0, a0), b0);
-        o1[i] = gl::add(gl::add(m.c1, a1), b1);
-    }
-}
-
 // K consecutive folds (one schedule step of 2^K) fused in registers: a lane reads 2^K adjacent values of c0 and of
 // c1 (64-512 contiguous bytes), folds them pairwise K times with challenges alpha, alpha^2, alpha^4 and coset
 // factors kappa, kappa^2, kappa^4, and writes ONE output.  Intermediate arrays never touch HBM.
@@ -87,17 +69,6 @@ void launch_fri_fold_step(const u64 *d_c0, const u64 *d_c1, size_t len, unsigned
         hipLaunchKernelGGL(fri_fold_fused_kernel<2>, dim3((unsigned)blocks), dim3(tpb), 0, s, d_c0, d_c1, d_o0, d_o1, d_roots, out_len, j0, coset_inv, ch0, ch1);
     else
         hipLaunchKernelGGL(fri_fold_fused_kernel<3>, dim3((unsigned)blocks), dim3(tpb), 0, s, d_c0, d_c1, d_o0, d_o1, d_roots, out_len, j0, coset_inv, ch0, ch1);
-}
-
-void launch_fri_fold(const u64 *d_c0, const u64 *d_c1, size_t len, u64 *d_o0, u64 *d_o1, const u64 *d_roots,
-                     u64 coset_inv, u64 ch0, u64 ch1, hipStream_t s) {
-    size_t half = len / 2;
-    if (!half) return;
-    unsigned tpb = 256;
-    size_t blocks = (half + tpb - 1) / tpb;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(fri_fold_kernel, dim3((unsigned)blocks), dim3(tpb), 0, s, d_c0, d_c1, d_o0, d_o1, d_roots, half,
-                       gl::canon(coset_inv), gl::canon(ch0), gl::canon(ch1));
 }
 
 }  // namespace bj

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "callee_words.h"
+#include "opening_args.h"
 #include "term_io.h"
 #include <stddef.h>
 #include <stdint.h>
@@ -97,8 +98,7 @@ void launch_poseidon1_permute_states(u64 *d_states, size_t n_states, hipStream_t
 void launch_pow(int pow_runner, const u64 *seed5, unsigned pow_bits, u64 base, u64 count, u64 *d_result, hipStream_t s);
 
 // fri.hip
-void launch_fri_fold(const u64 *d_c0, const u64 *d_c1, size_t len, u64 *d_o0, u64 *d_o1, const u64 *d_roots,
-                     u64 coset_inv, u64 ch0, u64 ch1, hipStream_t s);
+// fold by 2^k (k = 1..3) in one launch; j0: the global output index of local output 0 (a shard's part of an oracle)
 void launch_fri_fold_step(const u64 *d_c0, const u64 *d_c1, size_t len, unsigned k, u64 *d_o0, u64 *d_o1,
                           const u64 *d_roots, u64 coset_inv, u64 ch0, u64 ch1, hipStream_t s, size_t j0 = 0);
 // stage2.hip and quotient.hip: the term kernels of rounds 2 and 3, given launch descriptors (term_io.h).
@@ -133,18 +133,10 @@ void launch_barycentric_eval(const u64 *const *d_col_ptrs, unsigned n_cols, size
                              u64 *d_partials, u64 *d_out, hipStream_t s);
 void launch_linear_combination(const u64 *const *d_col_ptrs, const u64 *d_coefs, unsigned n_cols, size_t n, u64 *d_out0,
                                u64 *d_out1, hipStream_t s);
-void launch_deep_accumulate(const u64 *const *d_col_ptrs, const u64 *d_coefs, unsigned n_cols, size_t N, size_t I0,
-                            const u64 *d_tw_fwd, u64 c0, u64 c1, u64 at0, u64 at1, u64 *d_dst0, u64 *d_dst1,
-                            int accumulate, hipStream_t s);
-// several DEEP opening sets in one launch, at most DEEP_MAX_SETS (device-side argument pointers, canonical scalars)
-struct DeepSetHostArgs {
-    const u64 *const *d_cols;
-    const u64 *d_coefs;     // [n_cols][2]
-    unsigned n_cols;
-    u64 c0, c1, at0, at1;
-};
-void launch_deep_accumulate_multi(const DeepSetHostArgs *sets, unsigned n_sets, size_t N, size_t I0, const u64 *d_tw_fwd,
-                                  u64 *d_dst0, u64 *d_dst1, int accumulate, hipStream_t s);
+// the opening sets of a column list (opening_args.h; at most DEEP_MAX_SETS) in one launch; d_ptrs / d_coefs: the list's two parts
+// on the device
+void launch_deep_accumulate_multi(const ColumnSet *sets, unsigned n_sets, const u64 *const *d_ptrs, const u64 *d_coefs, size_t N,
+                                  size_t I0, const u64 *d_tw_fwd, u64 *d_dst0, u64 *d_dst1, int accumulate, hipStream_t s);
 // copy_check.hip: sigma words -> cell numbers with the decoding table of that file (d_table); the one-pass check of a setup's
 // sigma columns against the variables (both [num_vars][n] at stride n) and its second pass for a sigma that is no permutation
 void launch_sigma_cells(const u64 *d_sigmas, size_t sig_stride, unsigned num_vars, unsigned log_n, const u64 *d_table, uint32_t *d_cells,

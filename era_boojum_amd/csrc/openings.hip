@@ -256,67 +256,11 @@ void launch_linear_combination(const u64 *const *d_col_ptrs, const u64 *d_coefs,
 // ---------------------------------------------------------------------------------------------------------
 static constexpr int DEEP_PTS = 4;
 
-__global__ void __launch_bounds__(256)
-deep_accumulate_kernel(const u64 *const *cols, const u64 *coefs /*[n][2]*/, unsigned n_cols, size_t N, size_t I0,
-                       const u64 *tw, u64 c0, u64 c1, u64 at0, u64 at1, u64 *dst0, u64 *dst1, int accumulate) {
-    const size_t base = (size_t)blockIdx.x * (256 * DEEP_PTS) + threadIdx.x;
-    gl::Acc160 s0[DEEP_PTS], s1[DEEP_PTS];
-#pragma unroll
-    for (int k = 0; k < DEEP_PTS; k++) {
-        s0[k].clear();
-        s1[k].clear();
-    }
-    for (unsigned c = 0; c < n_cols; c++) {
-        const u64 *f = cols[c];
-        const u64 a = coefs[2 * c], b = coefs[2 * c + 1];
-#pragma unroll
-        for (int k = 0; k < DEEP_PTS; k++) {
-            size_t I = base + (size_t)k * 256;
-            u64 v = I < N ? f[I] : 0;
-            s0[k].fma(v, a);
-            s1[k].fma(v, b);
-        }
-    }
-    // denominators x_I - at, inverted together
-    u64 d0[DEEP_PTS], norm[DEEP_PTS], pref[DEEP_PTS];
-    const u64 d1 = gl::neg(at1);
-    const u64 seven_d1sq = gl::mul7(gl::sqr(d1));
-    u64 run = 1;
-#pragma unroll
-    for (int k = 0; k < DEEP_PTS; k++) {
-        size_t I = base + (size_t)k * 256;
-        size_t Ic = I0 + (I < N ? I : 0);   // global LDE index of the point
-        u64 x = gl::mul7(gl::domain_point(tw, Ic));
-        d0[k] = gl::sub(x, at0);
-        norm[k] = gl::sub(gl::sqr(d0[k]), seven_d1sq);
-        pref[k] = run;
-        run = gl::mul(run, norm[k]);
-    }
-    u64 inv_run = gl::inv_chain(run);
-#pragma unroll
-    for (int k = DEEP_PTS - 1; k >= 0; k--) {
-        u64 ni = gl::mul(inv_run, pref[k]);
-        inv_run = gl::mul(inv_run, norm[k]);
-        size_t I = base + (size_t)k * 256;
-        if (I < N) {
-            gl::e2 den{gl::mul(d0[k], ni), gl::neg(gl::mul(d1, ni))};
-            gl::e2 num{gl::sub(s0[k].reduce(), c0), gl::sub(s1[k].reduce(), c1)};
-            gl::e2 r = gl::e2_mul(num, den);
-            if (accumulate) {
-                r.c0 = gl::add(r.c0, gl::canon(dst0[I]));
-                r.c1 = gl::add(r.c1, gl::canon(dst1[I]));
-            }
-            dst0[I] = r.c0;
-            dst1[I] = r.c1;
-        }
-    }
-}
-
-// Several opening sets in one pass (the prover's z, z*omega and 0): dst (+)= sum_t (sum_k coef_tk f_tk - C_t) / (x - at_t).
-// One inversion serves DEEP_PTS * n_sets denominators instead of DEEP_PTS, and the destination is written once instead of
-// being re-read and re-written per set.  Phase 1 walks (set, point) forward building the prefix products of the norms,
+// One to DEEP_MAX_SETS opening sets in one pass (the prover's z, z*omega and 0): dst (+)= sum_t (sum_k coef_tk f_tk - C_t) / (x - at_t).
+// One inversion serves DEEP_PTS * n_sets denominators, and the destination is written once instead of being re-read and
+// re-written per set.  Phase 1 walks (set, point) forward building the prefix products of the norms,
 // phase 2 walks backward: it unwinds the inverses and computes each set's numerators only then, so that one set's
-// accumulators are live at a time.  Exact arithmetic: the same values as deep_accumulate_kernel applied set by set.
+// accumulators are live at a time.  Exact arithmetic: the same values as one pass per set.
 struct DeepSetDev {
     const u64 *const *cols;
     const u64 *coefs;       // [n_cols][2]
@@ -398,22 +342,15 @@ deep_accumulate_multi_kernel(DeepSetsDev S, size_t N, size_t I0, const u64 *tw, 
         }
     }
 }
-void launch_deep_accumulate_multi(const DeepSetHostArgs *sets, unsigned n_sets, size_t N, size_t I0, const u64 *d_tw_fwd,
-                                  u64 *d_dst0, u64 *d_dst1, int accumulate, hipStream_t s) {
+void launch_deep_accumulate_multi(const ColumnSet *sets, unsigned n_sets, const u64 *const *d_ptrs, const u64 *d_coefs, size_t N,
+                                  size_t I0, const u64 *d_tw_fwd, u64 *d_dst0, u64 *d_dst1, int accumulate, hipStream_t s) {
     DeepSetsDev S{};
     S.n = (int)n_sets;
     for (unsigned t = 0; t < n_sets && t < (unsigned)DEEP_MAX_SETS; t++)
-        S.s[t] = DeepSetDev{sets[t].d_cols, sets[t].d_coefs, sets[t].n_cols, sets[t].c0, sets[t].c1, sets[t].at0, sets[t].at1};
+        S.s[t] = DeepSetDev{d_ptrs + sets[t].first_col, d_coefs + 2 * sets[t].first_col, sets[t].n_cols, sets[t].C[0], sets[t].C[1],
+                            sets[t].at[0], sets[t].at[1]};
     const unsigned blocks = (unsigned)((N + 256 * DEEP_PTS - 1) / (256 * DEEP_PTS));
     hipLaunchKernelGGL(deep_accumulate_multi_kernel, dim3(blocks), dim3(256), 0, s, S, N, I0, d_tw_fwd, d_dst0, d_dst1, accumulate);
-}
-
-void launch_deep_accumulate(const u64 *const *d_col_ptrs, const u64 *d_coefs, unsigned n_cols, size_t N, size_t I0,
-                            const u64 *d_tw_fwd, u64 c0, u64 c1, u64 at0, u64 at1, u64 *d_dst0, u64 *d_dst1,
-                            int accumulate, hipStream_t s) {
-    unsigned blocks = (unsigned)((N + 256 * DEEP_PTS - 1) / (256 * DEEP_PTS));
-    hipLaunchKernelGGL(deep_accumulate_kernel, dim3(blocks), dim3(256), 0, s, d_col_ptrs, d_coefs, n_cols, N, I0,
-                       d_tw_fwd, c0, c1, at0, at1, d_dst0, d_dst1, accumulate);
 }
 
 }  // namespace bj

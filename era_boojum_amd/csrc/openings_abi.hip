@@ -1,21 +1,39 @@
 // C-ABI entry points for the opening stage (barycentric evaluation at z, DEEP quotient).  Kernels: openings.hip.
 #include "ctx.h"
 
-#include <vector>
-
 using gl::u64;
 
 namespace {
-// [first, first + count) must lie inside the LDE domain: the kernels index the twiddle table by first + i
-int check_deep_range(bj_ctx *ctx, const char *who, unsigned log_n, unsigned log_lde, size_t first, size_t count) {
+// a caller's sources as one set of L
+int add_sources(bj_ctx *ctx, const char *who, bj::ColumnList &L, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1,
+                size_t n_src, const uint64_t *h_challenges, const uint64_t *h_values, const uint64_t *at2) {
+    if (n_src == 0 || n_src > (1u << 20)) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: bad source count", who);
+    if (!L.add_set(bj::open_srcs(h_src_c0, h_src_c1, n_src).data(), n_src, h_challenges, h_values, at2))
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: null source %zu of set %zu", who, L.bad_src, L.bad_set);
+    return BJ_OK;
+}
+
+// The three DEEP entry points: the caller's sets, checked, as one column list and one launch.  [first, first + count) must lie
+// inside the LDE domain (the kernel indexes the twiddle table by first + i)
+int deep_sets(bj_ctx *ctx, const char *who, const bj_deep_set *sets, unsigned n_sets, unsigned log_n, unsigned log_lde, size_t first,
+               size_t count, uint64_t *d_dst_c0, uint64_t *d_dst_c1, int accumulate) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!sets || !d_dst_c0 || !d_dst_c1) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (n_sets == 0 || n_sets > (unsigned)bj::DEEP_MAX_SETS)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: %u opening sets, one call takes 1..%d", who, n_sets, bj::DEEP_MAX_SETS);
     const unsigned log_full = log_n + log_lde;
-    if (log_n > 32 || log_lde > 32 || log_full == 0 || log_full > 32)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: bad domain", who);
+    if (log_n > 32 || log_lde > 32 || log_full == 0 || log_full > 32) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: bad domain", who);
     const size_t N = (size_t)1 << log_full;
     if (count == 0 || count > N || first > N - count)
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: range [%zu, %zu + %zu) is empty or passes the 2^%u-point domain", who, first,
                         first, count, log_full);
-    return BJ_OK;
+    bj::ColumnList L;
+    for (unsigned t = 0; t < n_sets; t++) {
+        const bj_deep_set &S = sets[t];
+        if (!S.src_c0 || !S.values || !S.challenges || !S.at2) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: null pointer in set %u", who, t);
+        if (int rc = add_sources(ctx, who, L, S.src_c0, S.src_c1, S.n_src, S.challenges, S.values, S.at2)) return rc;
+    }
+    return bj::deep_accumulate_multi(ctx, L, log_n, log_lde, count, first, d_dst_c0, d_dst_c1, accumulate);
 }
 }  // namespace
 
@@ -62,34 +80,24 @@ int bj_deep_quotient_accumulate(bj_ctx *ctx, const uint64_t *const *h_src_c0, co
                                 size_t n_src, const uint64_t *h_values, const uint64_t *h_challenges,
                                 const uint64_t *at2, unsigned log_n, unsigned log_lde, uint64_t *d_dst_c0,
                                 uint64_t *d_dst_c1, int accumulate) {
-    return bj::deep_accumulate_range(ctx, h_src_c0, h_src_c1, n_src, h_values, h_challenges, at2, log_n, log_lde,
-                                     (size_t)1 << (log_n + log_lde), 0, d_dst_c0, d_dst_c1, accumulate);
+    const bj_deep_set one{h_src_c0, h_src_c1, n_src, h_values, h_challenges, at2};
+    const unsigned log_full = log_n + log_lde;   // the whole domain; a bad one is refused before the range is looked at
+    return deep_sets(ctx, "bj_deep_quotient_accumulate", &one, 1, log_n, log_lde, 0, log_full <= 32 ? (size_t)1 << log_full : 0, d_dst_c0,
+                     d_dst_c1, accumulate);
 }
 
 int bj_deep_quotient_accumulate_range(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1,
                                       size_t n_src, const uint64_t *h_values, const uint64_t *h_challenges,
                                       const uint64_t *at2, unsigned log_n, unsigned log_lde, size_t first, size_t count,
                                       uint64_t *d_dst_c0, uint64_t *d_dst_c1, int accumulate) {
-    if (int rc = bj::bind(ctx)) return rc;
-    if (int rc = check_deep_range(ctx, "bj_deep_quotient_accumulate_range", log_n, log_lde, first, count)) return rc;
-    return bj::deep_accumulate_range(ctx, h_src_c0, h_src_c1, n_src, h_values, h_challenges, at2, log_n, log_lde, count, first,
-                                     d_dst_c0, d_dst_c1, accumulate);
+    const bj_deep_set one{h_src_c0, h_src_c1, n_src, h_values, h_challenges, at2};
+    return deep_sets(ctx, "bj_deep_quotient_accumulate_range", &one, 1, log_n, log_lde, first, count, d_dst_c0, d_dst_c1, accumulate);
 }
 
 int bj_deep_quotient_accumulate_sets(bj_ctx *ctx, const bj_deep_set *sets, unsigned n_sets, unsigned log_n,
                                      unsigned log_lde, size_t first, size_t count, uint64_t *d_dst_c0,
                                      uint64_t *d_dst_c1, int accumulate) {
-    if (int rc = bj::bind(ctx)) return rc;
-    if (!sets || !d_dst_c0 || !d_dst_c1)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_deep_quotient_accumulate_sets: null pointer");
-    if (n_sets == 0 || n_sets > (unsigned)bj::DEEP_MAX_SETS)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_deep_quotient_accumulate_sets: %u opening sets, one call takes 1..%d", n_sets,
-                        bj::DEEP_MAX_SETS);
-    if (int rc = check_deep_range(ctx, "bj_deep_quotient_accumulate_sets", log_n, log_lde, first, count)) return rc;
-    bj::DeepSetHost hs[bj::DEEP_MAX_SETS];
-    for (unsigned t = 0; t < n_sets; t++)
-        hs[t] = bj::DeepSetHost{sets[t].src_c0, sets[t].src_c1, sets[t].n_src, sets[t].values, sets[t].challenges, sets[t].at2};
-    return bj::deep_accumulate_multi(ctx, hs, n_sets, log_n, log_lde, count, first, d_dst_c0, d_dst_c1, accumulate);
+    return deep_sets(ctx, "bj_deep_quotient_accumulate_sets", sets, n_sets, log_n, log_lde, first, count, d_dst_c0, d_dst_c1, accumulate);
 }
 
 int bj_linear_combination(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1, size_t n_src,
@@ -97,145 +105,63 @@ int bj_linear_combination(bj_ctx *ctx, const uint64_t *const *h_src_c0, const ui
     if (int rc = bj::bind(ctx)) return rc;
     if (!h_src_c0 || !h_challenges || !d_out_c0 || !d_out_c1)
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_linear_combination: null pointer");
-    if (n_src == 0 || n_src > (1u << 20)) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_linear_combination: bad source count");
     if (n == 0) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_linear_combination: n = 0");
-    for (size_t k = 0; k < n_src; k++)
-        if (!h_src_c0[k]) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_linear_combination: null source %zu", k);
-    return bj::combine_monomials(ctx, h_src_c0, h_src_c1, n_src, h_challenges, n, d_out_c0, d_out_c1);
+    bj::ColumnList L;
+    if (int rc = add_sources(ctx, "bj_linear_combination", L, h_src_c0, h_src_c1, n_src, h_challenges, nullptr, nullptr)) return rc;
+    return bj::combine_monomials(ctx, L, n, d_out_c0, d_out_c1);
 }
 
 }  // extern "C"
 
 namespace bj {
-// out = sum_k ch_k * src_k over n entries (sources: base columns, or F_p^2 columns as (c0, c1) pairs) — same flattening
-// of F_p^2 sources into base columns with F_p^2 coefficients as the DEEP call below
-int combine_monomials(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1, size_t n_src,
-                      const uint64_t *h_challenges, size_t n, uint64_t *d_out0, uint64_t *d_out1) {
-    if (int rc = bj::bind(ctx)) return rc;
-    std::vector<const u64 *> ptrs;
-    std::vector<u64> coefs;
-    for (size_t k = 0; k < n_src; k++) {
-        gl::e2 ch{gl::canon(h_challenges[2 * k]), gl::canon(h_challenges[2 * k + 1])};
-        ptrs.push_back(h_src_c0[k]);
-        coefs.push_back(ch.c0);
-        coefs.push_back(ch.c1);
-        if (h_src_c1 && h_src_c1[k]) {
-            ptrs.push_back(h_src_c1[k]);
-            coefs.push_back(gl::mul(gl::GEN, ch.c1));
-            coefs.push_back(ch.c0);
-        }
-    }
-    const unsigned n_cols = (unsigned)ptrs.size();
-    bj::TmpBuf args;   // [pointers][F_p^2 coefficients]
-    if (int rc = args.alloc(ctx, bj::column_list_arg_words(n_cols))) return rc;
-    const u64 **d_ptrs = (const u64 **)args.p;
-    u64 *d_coefs = (u64 *)(d_ptrs + n_cols);
-    if (int rc = bj::h2d_async(ctx, (void *)d_ptrs, ptrs.data(), n_cols * sizeof(u64 *))) return rc;
-    if (int rc = bj::h2d_async(ctx, d_coefs, coefs.data(), coefs.size() * sizeof(u64))) return rc;
-    bj::launch_linear_combination(d_ptrs, d_coefs, n_cols, n, d_out0, d_out1, ctx->stream);
+namespace {
+// The two parts of a column list in device memory: one block `args` ([pointers][coefficients], L.words() words: out of the
+// proof's workspace inside a proof), filled by two copies on the context's stream
+struct DeviceColumns {
+    const u64 *const *ptrs;
+    const u64 *coefs;
+};
+int upload_columns(bj_ctx *ctx, const ColumnList &L, TmpBuf &args, DeviceColumns *d) {
+    if (int rc = args.alloc(ctx, L.words())) return rc;
+    u64 *d_ptrs = args.p + L.ptr_offset(), *d_coefs = args.p + L.coef_offset();
+    if (int rc = bj::h2d_async(ctx, d_ptrs, L.ptrs.data(), L.ptrs.size() * sizeof(u64 *))) return rc;
+    if (int rc = bj::h2d_async(ctx, d_coefs, L.coefs.data(), L.coefs.size() * sizeof(u64))) return rc;
+    *d = DeviceColumns{(const u64 *const *)d_ptrs, d_coefs};
+    return BJ_OK;
+}
+// after the launch that reads the block: a hipMalloc'ed one is freed when the caller returns
+int launched_on_columns(bj_ctx *ctx, const TmpBuf &args) {
     BJ_CHECK_LAUNCH(ctx);
     if (!args.from_arena) BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return BJ_OK;
 }
+}  // namespace
 
-// the same over the LOCAL index range [I0, I0 + N_local) of the LDE domain (a contiguous range of cosets owned by one GPU);
-// source and destination pointers address the local range
-int deep_accumulate_range(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1, size_t n_src,
-                          const uint64_t *h_values, const uint64_t *h_challenges, const uint64_t *at2, unsigned log_n,
-                          unsigned log_lde, size_t N_local, size_t I0, uint64_t *d_dst_c0, uint64_t *d_dst_c1,
-                          int accumulate) {
+// out = sum of the columns of L times their coefficients over n entries (L: one set, its values and point unused)
+int combine_monomials(bj_ctx *ctx, const ColumnList &L, size_t n, uint64_t *d_out0, uint64_t *d_out1) {
     if (int rc = bj::bind(ctx)) return rc;
-    if (!h_src_c0 || !h_values || !h_challenges || !at2 || !d_dst_c0 || !d_dst_c1)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_deep_quotient_accumulate: null pointer");
-    if (n_src == 0 || n_src > (1u << 20)) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_deep_quotient_accumulate: bad source count");
-    const unsigned log_full = log_n + log_lde;
-    if (log_full == 0 || log_full > 32) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_deep_quotient_accumulate: bad domain");
-    if (int rc = bj::ensure_twiddles(ctx, log_full, false)) return rc;
-    // flatten F_p^2 sources into base columns with F_p^2 coefficients; C = sum_k ch_k * v_k
-    std::vector<const u64 *> ptrs;
-    std::vector<u64> coefs;
-    gl::e2 C{0, 0};
-    for (size_t k = 0; k < n_src; k++) {
-        if (!h_src_c0[k]) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_deep_quotient_accumulate: null source %zu", k);
-        gl::e2 ch{gl::canon(h_challenges[2 * k]), gl::canon(h_challenges[2 * k + 1])};
-        gl::e2 v{gl::canon(h_values[2 * k]), gl::canon(h_values[2 * k + 1])};
-        C = gl::e2_add(C, gl::e2_mul(ch, v));
-        ptrs.push_back(h_src_c0[k]);
-        coefs.push_back(ch.c0);
-        coefs.push_back(ch.c1);
-        if (h_src_c1 && h_src_c1[k]) {  // (f0 + f1 u) * ch = ... + f1 * (7 ch1 + ch0 u)
-            ptrs.push_back(h_src_c1[k]);
-            coefs.push_back(gl::mul(gl::GEN, ch.c1));
-            coefs.push_back(ch.c0);
-        }
-    }
-    const unsigned n_cols = (unsigned)ptrs.size();
-    bj::TmpBuf args;   // [pointers][F_p^2 coefficients]
-    if (int rc = args.alloc(ctx, bj::column_list_arg_words(n_cols))) return rc;
-    const u64 **d_ptrs = (const u64 **)args.p;
-    u64 *d_coefs = (u64 *)(d_ptrs + n_cols);
-    if (int rc = bj::h2d_async(ctx, (void *)d_ptrs, ptrs.data(), n_cols * sizeof(u64 *))) return rc;
-    if (int rc = bj::h2d_async(ctx, d_coefs, coefs.data(), coefs.size() * sizeof(u64))) return rc;
-    bj::launch_deep_accumulate(d_ptrs, d_coefs, n_cols, N_local, I0, ctx->tw_fwd, C.c0, C.c1,
-                               gl::canon(at2[0]), gl::canon(at2[1]), d_dst_c0, d_dst_c1, accumulate, ctx->stream);
-    BJ_CHECK_LAUNCH(ctx);
-    if (!args.from_arena) BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a hipMalloc'ed argument block is freed on return
-    return BJ_OK;
+    if (!L.ok || L.n_cols() == 0) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "combine_monomials: unusable column list");
+    bj::TmpBuf args;
+    DeviceColumns d;
+    if (int rc = upload_columns(ctx, L, args, &d)) return rc;
+    bj::launch_linear_combination(d.ptrs, d.coefs, (unsigned)L.n_cols(), n, d_out0, d_out1, ctx->stream);
+    return launched_on_columns(ctx, args);
 }
 
-// up to DEEP_MAX_SETS opening sets at once (same argument meaning per set as deep_accumulate_range): one launch, one inversion
-// per lane for all of them, the destination written once
-int deep_accumulate_multi(bj_ctx *ctx, const DeepSetHost *sets, unsigned n_sets, unsigned log_n, unsigned log_lde, size_t N_local,
-                          size_t I0, uint64_t *d_dst_c0, uint64_t *d_dst_c1, int accumulate) {
+// The 1..DEEP_MAX_SETS opening sets of L over the LOCAL index range [I0, I0 + N_local) of the LDE domain (a contiguous range of
+// cosets owned by one GPU; source and destination pointers address the local range): one launch, one inversion per lane for all
+// of them, the destination written once
+int deep_accumulate_multi(bj_ctx *ctx, const ColumnList &L, unsigned log_n, unsigned log_lde, size_t N_local, size_t I0,
+                          uint64_t *d_dst_c0, uint64_t *d_dst_c1, int accumulate) {
     if (int rc = bj::bind(ctx)) return rc;
-    if (!sets || n_sets == 0 || n_sets > (unsigned)DEEP_MAX_SETS || !d_dst_c0 || !d_dst_c1)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "deep_accumulate_multi: bad arguments");
-    const unsigned log_full = log_n + log_lde;
-    if (log_full == 0 || log_full > 32) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "deep_accumulate_multi: bad domain");
-    if (int rc = bj::ensure_twiddles(ctx, log_full, false)) return rc;
-    std::vector<const u64 *> ptrs;
-    std::vector<u64> coefs;
-    DeepSetHostArgs a[DEEP_MAX_SETS];
-    size_t first_col[DEEP_MAX_SETS];
-    for (unsigned t = 0; t < n_sets; t++) {
-        const DeepSetHost &S = sets[t];
-        if (!S.src_c0 || !S.values || !S.challenges || !S.at2 || S.n_src == 0 || S.n_src > (1u << 20))
-            return bj::fail(ctx, BJ_ERR_INVALID_ARG, "deep_accumulate_multi: bad set %u", t);
-        first_col[t] = ptrs.size();
-        gl::e2 C{0, 0};
-        for (size_t k = 0; k < S.n_src; k++) {
-            if (!S.src_c0[k]) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "deep_accumulate_multi: null source %zu of set %u", k, t);
-            const gl::e2 ch{gl::canon(S.challenges[2 * k]), gl::canon(S.challenges[2 * k + 1])};
-            const gl::e2 v{gl::canon(S.values[2 * k]), gl::canon(S.values[2 * k + 1])};
-            C = gl::e2_add(C, gl::e2_mul(ch, v));
-            ptrs.push_back(S.src_c0[k]);
-            coefs.push_back(ch.c0);
-            coefs.push_back(ch.c1);
-            if (S.src_c1 && S.src_c1[k]) {
-                ptrs.push_back(S.src_c1[k]);
-                coefs.push_back(gl::mul(gl::GEN, ch.c1));
-                coefs.push_back(ch.c0);
-            }
-        }
-        a[t].n_cols = (unsigned)(ptrs.size() - first_col[t]);
-        a[t].c0 = C.c0;
-        a[t].c1 = C.c1;
-        a[t].at0 = gl::canon(S.at2[0]);
-        a[t].at1 = gl::canon(S.at2[1]);
-    }
-    bj::TmpBuf args;   // [pointers][F_p^2 coefficients]
-    if (int rc = args.alloc(ctx, bj::column_list_arg_words(ptrs.size()))) return rc;
-    const u64 **d_ptrs = (const u64 **)args.p;
-    u64 *d_coefs = (u64 *)(d_ptrs + ptrs.size());
-    if (int rc = bj::h2d_async(ctx, (void *)d_ptrs, ptrs.data(), ptrs.size() * sizeof(u64 *))) return rc;
-    if (int rc = bj::h2d_async(ctx, d_coefs, coefs.data(), coefs.size() * sizeof(u64))) return rc;
-    for (unsigned t = 0; t < n_sets; t++) {
-        a[t].d_cols = d_ptrs + first_col[t];
-        a[t].d_coefs = d_coefs + 2 * first_col[t];
-    }
-    bj::launch_deep_accumulate_multi(a, n_sets, N_local, I0, ctx->tw_fwd, d_dst_c0, d_dst_c1, accumulate, ctx->stream);
-    BJ_CHECK_LAUNCH(ctx);
-    if (!args.from_arena) BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return BJ_OK;
+    if (!L.ok || L.sets.empty() || L.sets.size() > (size_t)DEEP_MAX_SETS)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "deep_accumulate_multi: unusable column list");
+    if (int rc = bj::ensure_twiddles(ctx, log_n + log_lde, false)) return rc;
+    bj::TmpBuf args;
+    DeviceColumns d;
+    if (int rc = upload_columns(ctx, L, args, &d)) return rc;
+    bj::launch_deep_accumulate_multi(L.sets.data(), (unsigned)L.sets.size(), d.ptrs, d.coefs, N_local, I0, ctx->tw_fwd, d_dst_c0, d_dst_c1,
+                                     accumulate, ctx->stream);
+    return launched_on_columns(ctx, args);
 }
 }  // namespace bj

@@ -19,7 +19,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
-#include <deque>
 #include <vector>
 
 using gl::u64;
@@ -176,7 +175,7 @@ struct HostWitness {
     bool no_absorb;        // transfer and transform in groups, hash once at the end (a lane of bj_prove_async whose sibling is proving)
 };
 
-struct Src { const u64 *c0, *c1; };   // a base-field column (c1 == nullptr) or the two columns of an F_p^2 polynomial
+using Src = bj::OpenSrc;   // opening_args.h: a base-field column (c1 == nullptr) or the two columns of an F_p^2 polynomial
 struct DeepSets;
 struct Queries;
 
@@ -588,11 +587,7 @@ void Proving::list_opened_columns() {
 int Proving::evaluate_at(u64 *w, u64 open_shift, const std::vector<Src> &ss, const u64 *at, std::vector<u64> &vals) {
     int r = bj_barycentric_weights(ctx, log_n, open_shift, at, w, w + n);
     if (r) return r;
-    std::vector<const u64 *> ptrs;
-    for (auto &s : ss) {
-        ptrs.push_back(s.c0);
-        if (s.c1) ptrs.push_back(s.c1);
-    }
+    const std::vector<const u64 *> ptrs = bj::open_columns(ss.data(), ss.size());
     std::vector<u64> raw(2 * ptrs.size());
     const size_t np = ptrs.size(), per = (np + sh.world - 1) / sh.world;
     if (sh.world > 1 && np >= 8 * (size_t)sh.world && 2 * per * sh.world <= 2048) {
@@ -614,19 +609,8 @@ int Proving::evaluate_at(u64 *w, u64 open_shift, const std::vector<Src> &ss, con
         r = bj_barycentric_eval_batch(ctx, ptrs.data(), (unsigned)np, log_n, w, w + n, raw.data());
         if (r) return r;
     }
-    vals.clear();
-    size_t k = 0;
-    for (auto &s : ss) {
-        gl::e2 e0{raw[2 * k], raw[2 * k + 1]};
-        k++;
-        if (s.c1) {   // E(c0) + u * E(c1) = (a0 + 7 b1, a1 + b0)
-            gl::e2 e1{raw[2 * k], raw[2 * k + 1]};
-            k++;
-            e0 = {gl::add(e0.c0, gl::mul(gl::GEN, e1.c1)), gl::add(e0.c1, e1.c0)};
-        }
-        vals.push_back(e0.c0);
-        vals.push_back(e0.c1);
-    }
+    vals.resize(2 * ss.size());
+    bj::recombine_values(ss.data(), ss.size(), raw.data(), vals.data());
     return BJ_OK;
 }
 
@@ -664,37 +648,30 @@ int Proving::round4_openings() {
 // extended by one two-column LDE and divided by (x - at) pointwise.  Exact arithmetic: the same values as combining on the LDE.
 // The sets are prepared one after the other (a large one leaves its extended numerator in a buffer of its own) and divided
 // by their (x - at) TOGETHER, bj::DEEP_MAX_SETS per launch: one inversion per lane for all of them, the destination written once.
-struct PendingDeep {
-    std::vector<const u64 *> p0, p1;
-    std::vector<u64> vals, ch;
-    u64 at[2];
-};
 struct DeepSets {
     std::vector<u64> chs;   // powers of the DEEP challenge, one per opened polynomial over all sets
     size_t choff = 0;       // challenges handed out so far
     bj::TmpBuf num_mono, num_slice;
-    std::deque<PendingDeep> pending;
+    std::vector<bj::ColumnList> pending;   // the sets waiting for flush_deep, bj::DEEP_MAX_SETS per list = per launch
     bool written = false;   // deep holds the sets flushed so far
+
+    void queue(const std::vector<Src> &ss, const u64 *ch, const u64 *vals, const u64 *at) {   // a source without a column: refused at the flush
+        if (pending.empty() || pending.back().sets.size() == (size_t)bj::DEEP_MAX_SETS) pending.emplace_back();
+        pending.back().add_set(ss.data(), ss.size(), ch, vals, at);
+    }
 };
 
 // Divides the pending sets by their (x - at) into deep (accumulating once it has been written).
 int Proving::flush_deep(DeepSets &D) {
-    while (!D.pending.empty()) {
-        bj::DeepSetHost hs[bj::DEEP_MAX_SETS];
-        unsigned cnt = 0;
-        for (auto it = D.pending.begin(); it != D.pending.end() && cnt < (unsigned)bj::DEEP_MAX_SETS; ++it, ++cnt)
-            hs[cnt] = bj::DeepSetHost{it->p0.data(), it->p1.data(), it->p0.size(), it->vals.data(), it->ch.data(), it->at};
-        double deep_cols = 0;      // DEEP, SURVEY §8d: 8 (#base columns) Ln + 16 Ln (the destination pair)
-        for (unsigned k = 0; k < cnt; k++)
-            for (size_t j = 0; j < hs[k].n_src; j++) deep_cols += hs[k].src_c1 && hs[k].src_c1[j] ? 2 : 1;
-        const int pd = bj::probe_begin(ctx, "deep_accumulate_multi", 8.0 * deep_cols * (double)N + (D.written ? 32.0 : 16.0) * (double)N);
-        int r = bj::deep_accumulate_multi(ctx, hs, cnt, log_n, S->log_fri, N, sh.world > 1 ? I0 : 0, deep.p, deep.p + N,
-                                          D.written ? 1 : 0);
+    for (const bj::ColumnList &L : D.pending) {
+        // DEEP, SURVEY §8d: 8 (#base columns) Ln + 16 Ln (the destination pair)
+        const int pd = bj::probe_begin(ctx, "deep_accumulate_multi", 8.0 * (double)L.n_cols() * (double)N + (D.written ? 32.0 : 16.0) * (double)N);
+        int r = bj::deep_accumulate_multi(ctx, L, log_n, S->log_fri, N, sh.world > 1 ? I0 : 0, deep.p, deep.p + N, D.written ? 1 : 0);
         bj::probe_end(ctx, pd);
         if (r) return r;
         D.written = true;
-        for (unsigned k = 0; k < cnt; k++) D.pending.pop_front();
     }
+    D.pending.clear();
     return BJ_OK;
 }
 
@@ -702,41 +679,27 @@ int Proving::flush_deep(DeepSets &D) {
 // ms.size() challenges; a large set gets its extended numerator (an arena buffer of 2 N words); queues the set for flush_deep.
 int Proving::deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector<Src> &ms, const u64 *vals, const u64 *at) {
     const u64 *ch = D.chs.data() + 2 * D.choff;
-    std::vector<const u64 *> p0, p1;
-    size_t n_base = 0;
-    for (auto &m : ms) n_base += m.c1 ? 2 : 1;
-    if (n_base < bj::WS_LARGE_SET) {   // a handful of columns: streaming them over the FRI domain is cheaper than an extra LDE pass
-        PendingDeep pd;
-        for (auto &l : ls) {
-            pd.p0.push_back(l.c0);
-            pd.p1.push_back(l.c1);
-        }
-        pd.vals.assign(vals, vals + 2 * ls.size());
-        pd.ch.assign(ch, ch + 2 * ls.size());
-        pd.at[0] = at[0];
-        pd.at[1] = at[1];
-        D.pending.push_back(std::move(pd));
-        D.choff += ls.size();
+    D.choff += ms.size();
+    if (bj::open_columns(ms.data(), ms.size()).size() < bj::WS_LARGE_SET) {   // a handful of columns: streaming them over the FRI domain is cheaper than an extra LDE pass
+        D.queue(ls, ch, vals, at);
         return BJ_OK;
     }
     bj::TmpBuf num_lde;   // this set's extended numerator: alive until the sets are flushed
     if (int ra = num_lde.take(ctx, bj::WS_NUM_LDE)) return ra;
-    for (auto &m : ms) {
-        p0.push_back(m.c0);
-        p1.push_back(m.c1);
-    }
     int r;
+    bj::ColumnList num;   // the numerator's columns and coefficients, and C = sum_k ch_k * v_k; unusable: combine_monomials refuses it
     if (sh.world > 1 && n % sh.world == 0 && n / sh.world >= 256) {
         // the monomials are replicated: every rank combines its slice of the coefficient range, one all-gather of the
         // two result columns rebuilds the numerator everywhere (the combination is the replicated part of DEEP)
         const size_t per = n / sh.world, off = (size_t)sh.rank * per;
-        for (auto &q0 : p0) q0 += off;
-        for (auto &q1 : p1)
-            if (q1) q1 += off;
-        r = bj::combine_monomials(ctx, p0.data(), p1.data(), ms.size(), ch, per, D.num_slice.p, D.num_slice.p + per);
+        std::vector<Src> slice = ms;
+        for (Src &m : slice) m = {m.c0 + off, m.c1 ? m.c1 + off : nullptr};
+        num.add_set(slice.data(), slice.size(), ch, vals, at);
+        r = bj::combine_monomials(ctx, num, per, D.num_slice.p, D.num_slice.p + per);
         if (!r) r = bj::all_gather_columns(ctx, sh, D.num_slice.p, D.num_mono.p, 2, per);
     } else {
-        r = bj::combine_monomials(ctx, p0.data(), p1.data(), ms.size(), ch, n, D.num_mono.p, D.num_mono.p + n);
+        num.add_set(ms.data(), ms.size(), ch, vals, at);
+        r = bj::combine_monomials(ctx, num, n, D.num_mono.p, D.num_mono.p + n);
     }
     if (r) return r;
     if (sh.world > 1)
@@ -744,17 +707,8 @@ int Proving::deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector
     else
         r = lde_cols(D.num_mono.p, num_lde.p, N, 2, S->log_fri, 0, S->fri_lde);
     if (r) return r;
-    gl::e2 C{0, 0};   // sum_k ch_k * v_k
-    for (size_t k = 0; k < ms.size(); k++) C = gl::e2_add(C, gl::e2_mul(e2c(ch + 2 * k), e2c(vals + 2 * k)));
-    PendingDeep pd;   // one F_p^2 source (the extended numerator) with challenge 1 and "value" C
-    pd.p0.push_back(num_lde.p);
-    pd.p1.push_back(num_lde.p + N);
-    pd.vals = {C.c0, C.c1};
-    pd.ch = {1, 0};
-    pd.at[0] = at[0];
-    pd.at[1] = at[1];
-    D.pending.push_back(std::move(pd));
-    D.choff += ms.size();
+    const u64 one[2] = {1, 0};   // one F_p^2 source (the extended numerator) with challenge 1 and "value" C
+    D.queue({Src{num_lde.p, num_lde.p + N}}, one, num.sets[0].C, at);
     return BJ_OK;
 }
 

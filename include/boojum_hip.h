@@ -224,7 +224,8 @@ int bj_poseidon_permute(bj_ctx *ctx, uint64_t *d_states, size_t n_states);
  * ------------------------------------------------------------------------------------------------------------- */
 /* One fold by 2 of the bit-reversed F_p^2 array (c0, c1) of length len into (o0, o1) of length len/2:
  *   out[i] = (a + b) + (ch0 + ch1*u) * ((a - b) * roots[i] * coset_inv),  a = in[2i], b = in[2i+1].
- * roots = inverse bit-reversed twiddles of the initial LDE domain of size 2^log_full (cached in the context). */
+ * roots = inverse bit-reversed twiddles of the initial LDE domain of size 2^log_full (cached in the context).
+ * The same launch as bj_fri_fold_step with k = 1. */
 int bj_fri_fold(bj_ctx *ctx, const uint64_t *d_c0, const uint64_t *d_c1, size_t len, uint64_t *d_o0, uint64_t *d_o1,
                 unsigned log_full, uint64_t coset_inv, uint64_t ch0, uint64_t ch1);
 
@@ -250,7 +251,8 @@ int bj_barycentric_eval_batch(bj_ctx *ctx, const uint64_t *const *h_col_ptrs, un
 /* quotening_operation_in_extension (src/cs/implementations/prover.rs:2523-2706):
  *   dst[I] (+)= [ sum_k ch_k * (f_k[I] - v_k) ] / (x_I - at),  x_I = g*w_{nL}^{bitrev(I)}, I < 2^(log_n+log_lde).
  * Source k is the LDE column h_src_c0[k] (and h_src_c1[k] for an F_p^2 polynomial; NULL entry or NULL array = base
- * field).  h_values / h_challenges are [n_src][2].  accumulate = 0 overwrites dst, otherwise adds to it. */
+ * field).  h_values / h_challenges are [n_src][2].  accumulate = 0 overwrites dst, otherwise adds to it.
+ * The same launch as bj_deep_quotient_accumulate_sets with one set: the kernel a proof runs. */
 int bj_deep_quotient_accumulate(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1,
                                 size_t n_src, const uint64_t *h_values, const uint64_t *h_challenges,
                                 const uint64_t *at2, unsigned log_n, unsigned log_lde, uint64_t *d_dst_c0,

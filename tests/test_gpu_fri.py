@@ -25,6 +25,44 @@ def test_fold_matches_oracle(log_len):
     d_c.free(); d_o.free()
 
 
+GUARD = 16                                  # words around each output column
+GUARD_WORD = np.uint64(0xA5A5A5A5A5A5A5A5)
+
+
+@pytest.mark.parametrize("log_len", [1, 9, 23, 24])
+def test_fold_between_guard_cells(log_len):
+    """bj_fri_fold is the fused fold with k = 1.  Its launch is capped at 16 384 workgroups of 256 lanes, so the sizes are: one
+    output on one live lane (2), exactly one workgroup (512), the cap itself with no second trip of the grid-stride loop (2^23)
+    and a second trip for every lane (2^24).  Non-canonical words in; each output column lies between guard cells, which must
+    come back untouched."""
+    log_full = max(log_len, 4)
+    rng = np.random.default_rng(700 + log_len)
+    ln = 1 << log_len
+    half = ln // 2
+    c = rand_gl(rng, (2, ln), noncanonical=True)
+    ch = (int(rng.integers(0, P, dtype=np.uint64)), P + 5)                   # a non-canonical challenge word
+    kappa = pow(O.inv(7), 2, P)
+    w0, w1 = O.fri_fold(c[0], c[1], O.twiddles(log_full, inverse=True), kappa, (ch[0], 5))
+    d_c = DevBuf(c)
+    d_o = DevBuf(np.full(3 * GUARD + 2 * half, GUARD_WORD, dtype=np.uint64))
+    o0, o1 = d_o.ptr + 8 * GUARD, d_o.ptr + 8 * (2 * GUARD + half)
+    ctx().fri_fold(d_c.ptr, d_c.ptr + 8 * ln, ln, o0, o1, log_full, kappa, ch)
+    got = d_o.get()
+    d_c.free(); d_o.free()
+    assert np.array_equal(got[GUARD:GUARD + half], w0) and np.array_equal(got[2 * GUARD + half:2 * GUARD + 2 * half], w1)
+    for g in (got[:GUARD], got[GUARD + half:2 * GUARD + half], got[2 * GUARD + 2 * half:]):
+        assert (g == GUARD_WORD).all()
+
+
+def test_fold_refuses_a_length_that_is_no_power_of_two():
+    import era_boojum_amd as E
+    d = DevBuf(np.zeros(2 * 514 + 514, dtype=np.uint64))
+    with pytest.raises(E.BoojumHipError, match="bj_fri_fold: length must be a power of two >= 2"):
+        ctx().fri_fold(d.ptr, d.ptr + 8 * 514, 514, d.ptr + 8 * 1028, d.ptr + 8 * (1028 + 257), 10, 1, (3, 5))
+    assert not d.get().any()                                                 # nothing was launched
+    d.free()
+
+
 def test_fold_chain_equals_oracle_do_fri():
     """Drive a whole do_fri schedule with the HIP fold + HIP chunked trees and compare every oracle cap and the last
     folded layer with the CPU oracle's do_fri (fri/mod.rs:49-358)."""

@@ -90,7 +90,9 @@ def test_deep_quotient_at_a_trace_domain_point_2p25():
     """The opening set of a public input: at = (omega_n^row, 0) over the 2^25-point LDE domain.  In one thread of this launch
     the running product of the four denominators has a 2-power order, so the inversion chain squares 2^48 (2^96 = -1):
     the borrow-without-carry branch of gl::mul_weak, taken in the middle of a counted loop.  (Its s_andn2_b64 writes SCC;
-    with SCC missing from the asm clobbers the loop lost its exit test and ran 2^29 more trips.)"""
+    with SCC missing from the asm clobbers the loop lost its exit test and ran 2^29 more trips.)  The single-set operator
+    runs the multi-set kernel with one set: its running product is the same four norms in the same order, so this thread
+    still takes that branch."""
     log_n, log_lde = 22, 3
     N = 1 << (log_n + log_lde)
     rng = np.random.default_rng(2225)
