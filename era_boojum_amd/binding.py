@@ -1,4 +1,5 @@
 """ctypes binding of include/boojum_hip.h.  Device buffers are plain integer addresses (e.g. ``tensor.data_ptr()``)."""
+import contextlib
 import ctypes as C
 import os
 from dataclasses import dataclass
@@ -1034,6 +1035,26 @@ class _Ticket:
         self.handle, self.keep = handle, keep
 
 
+@contextlib.contextmanager
+def _setup_lean_switch(lib, on):
+    """BJ_SETUP_LEAN set (and read by the library) for the calls inside, then whatever the environment held before, read again.
+    `on` false: nothing is touched, the library keeps what it last read."""
+    if not on:
+        yield
+        return
+    before = os.environ.get("BJ_SETUP_LEAN")
+    os.environ["BJ_SETUP_LEAN"] = "1"
+    lib.bj_env_reload()
+    try:
+        yield
+    finally:
+        if before is None:
+            os.environ.pop("BJ_SETUP_LEAN", None)
+        else:
+            os.environ["BJ_SETUP_LEAN"] = before
+        lib.bj_env_reload()
+
+
 class ProverSetup:
     """Device-resident setup for a circuit of era_boojum_amd.synthetic.Circuit shape (bj_setup_create).
 
@@ -1042,8 +1063,13 @@ class ProverSetup:
     (bj_setup_create_sharded)."""
 
     def __init__(self, ctx, circuit, fri_lde_factor=8, cap_size=16, security_level=100, pow_bits=0, comm=None,
-                 transcript="poseidon2", setup_base_dump=None, pow_runner="blake2s", tree_hasher=None, variables_hint_dump=None):
-        """pow_runner: "blake2s" | "keccak256" — the PoWRunner (pow.rs), independent of the transcript as in the reference.
+                 transcript="poseidon2", setup_base_dump=None, pow_runner="blake2s", tree_hasher=None, variables_hint_dump=None, lean=False):
+        """lean: the setup keeps its monomials and its tree and drops the LDE of its columns once the tree stands (BJ_SETUP_LEAN,
+        DESIGN.md §3): `n_cols * L * n * 8` bytes less in HBM, the same cap and byte-identical proofs, each proof paying one coset
+        transform of the setup columns per quotient coset and an evaluation per queried leaf.  The switch is set for the creation
+        only and the value the environment held is put back, also when the creation raises; not thread-safe (bj_env_reload), so
+        never while a proof runs.  Single GPU only: refused together with `comm`.
+        pow_runner: "blake2s" | "keccak256" — the PoWRunner (pow.rs), independent of the transcript as in the reference.
         tree_hasher: None pairs the transcript with its usual hasher (Poseidon2 trees for "poseidon2" / "poseidon", the same byte
         hash for "blake2s" / "keccak256"); "poseidon2" | "poseidon" | "blake2s" | "keccak256" picks one (BJ_HASHER_*), e.g.
         "poseidon" with transcript="poseidon" for GoldilocksPoseidonSponge trees + GoldilocksPoisedonTranscript.
@@ -1055,6 +1081,15 @@ class ProverSetup:
         `prove_from_dumps(witness_vec_dump, None)` works.  See `from_placement`."""
         self._ctx, self._lib, self.circuit = ctx, ctx._lib, circuit
         self._comm = comm
+        self._lean = bool(lean)
+        if lean and comm is not None:
+            raise BoojumHipError("a lean setup is single-GPU: a shard already holds only its own cosets of the LDE")
+        with _setup_lean_switch(self._lib, self._lean):
+            self._create(ctx, circuit, fri_lde_factor, cap_size, security_level, pow_bits, comm, transcript, setup_base_dump, pow_runner,
+                         tree_hasher, variables_hint_dump)
+
+    def _create(self, ctx, circuit, fri_lde_factor, cap_size, security_level, pow_bits, comm, transcript, setup_base_dump, pow_runner,
+                tree_hasher, variables_hint_dump):
         self.fri_lde_factor, self.cap_size, self.security_level, self.pow_bits = fri_lde_factor, cap_size, security_level, pow_bits
         c = circuit
         from_dump = setup_base_dump is not None
@@ -1082,10 +1117,19 @@ class ProverSetup:
             ctx._check(self._lib.bj_setup_create_from_dump(ctx._h, C.byref(cc), blob, len(blob), C.byref(cfg), C.byref(h)))
             self._h = h
             return
-        ctx._check(self._lib.bj_setup_create_sharded(ctx._h, C.byref(cc), _np_ptr(sig), _np_ptr(con),
-                                                     _np_ptr(tab) if c.lookup_reps else None, C.byref(cfg),
-                                                     C.byref(comm.struct) if comm is not None else None, C.byref(h)))
+        if comm is None:
+            ctx._check(self._lib.bj_setup_create(ctx._h, C.byref(cc), _np_ptr(sig), _np_ptr(con), _np_ptr(tab) if c.lookup_reps else None,
+                                                 C.byref(cfg), C.byref(h)))
+        else:   # bj_setup_create_sharded does not look at BJ_SETUP_LEAN
+            ctx._check(self._lib.bj_setup_create_sharded(ctx._h, C.byref(cc), _np_ptr(sig), _np_ptr(con),
+                                                         _np_ptr(tab) if c.lookup_reps else None, C.byref(cfg), C.byref(comm.struct), C.byref(h)))
         self._h = h
+
+    @property
+    def lean(self):
+        """True for a setup created with lean=True.  (One created with lean=False while BJ_SETUP_LEAN was set by other means is lean
+        as well: `device_bytes` tells.)"""
+        return self._lean
 
     @classmethod
     def from_placement(cls, ctx, circuit, var_ids, *args, **kwargs):

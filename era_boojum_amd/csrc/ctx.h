@@ -162,7 +162,8 @@ int deep_accumulate_multi(bj_ctx *ctx, const ColumnList &L, unsigned log_n, unsi
 // setup.hip: bj_setup_create[_sharded] with the sigma columns either from the host or written on the device by `fill_sigmas`
 // ([num_vars][n] at d_sigmas, called once the setup's buffers exist); a placement handed over is freed with the setup
 int setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const std::function<int(bj_setup *, gl::u64 *)> &fill_sigmas,
-                      const uint64_t *h_constants, const uint64_t *h_tables, const bj_proof_config *cfg, const bj_comm *comm, bj_setup **out);
+                      const uint64_t *h_constants, const uint64_t *h_tables, const bj_proof_config *cfg, const bj_comm *comm, bj_setup **out,
+                      bool lean = false);   // lean: drop the LDE once the tree stands (single device only; the callers pass env().setup_lean)
 void setup_adopt_placement(bj_setup *s, uint32_t *d_placement);   // [num_vars][n] u32, hipMalloc'ed
 const uint32_t *setup_placement(const bj_setup *s);               // nullptr unless created from a placement
 // lookup_multiplicities.hip: the multiplicity column [n] counted from raw columns (the arguments of bj_lookup_multiplicities) or

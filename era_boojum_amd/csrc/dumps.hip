@@ -333,7 +333,7 @@ int bj_setup_create_from_placement(bj_ctx *ctx, const bj_circuit *circuit, const
         BJ_HIP(ctx, hipMemcpyAsync(w.keys[0], d_place, (size_t)V * n * 4, hipMemcpyDeviceToDevice, ctx->stream));
         return bj::sigmas_from_keys(ctx, w, V, log_n, circuit->non_residues, d_sigmas, n);
     };
-    return bj::setup_create_impl(ctx, circuit, nullptr, fill, h_constants, h_tables, config, nullptr, out);
+    return bj::setup_create_impl(ctx, circuit, nullptr, fill, h_constants, h_tables, config, nullptr, out, bj::env().setup_lean);
 }
 
 }  // extern "C"

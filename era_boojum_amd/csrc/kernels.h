@@ -22,6 +22,7 @@ struct EnvConfig {
     bool gate_no_aot = false, gate_no_fuse = false, gate_no_jit = false;
     bool gates_windowed = true;         // BJ_GATES_WINDOWED=0: per-gate kernel for the hand-written kinds
     bool prove_no_absorb = false;
+    bool setup_lean = false;            // BJ_SETUP_LEAN: a single-device setup created while it is set drops its LDE once the tree stands; sampled per setup
     bool copy_perm_wide_k = false;       // BJ_COPY_PERM_WIDE_K: quotient_copy_perm with 64-bit non-residue products even when they fit 32 bits (A/B, tests)
     bool prove_uniform_groups = false;   // BJ_PROVE_UNIFORM_GROUPS: equal groups of G columns, one multi-block absorption run per group (round 4's GROUPING only: its launches absorbed eight columns each)
     bool async_stagger = true;           // BJ_ASYNC_STAGGER=0: bj_prove_async lanes start whenever they are given work (A/B)
@@ -74,7 +75,7 @@ void launch_ntt_first4(const NttIo &io, hipStream_t s);   // 16-byte accesses: n
 void launch_ntt_first5(const NttIo &io, hipStream_t s);
 // first ten rounds of all cosets (log_n == 22, ntt_aligned16 columns); d_table: n_cosets * 1024 words of device scratch
 void launch_ntt_front10(const NttIo &io, u64 *d_table, bool tiled_in, hipStream_t s);
-// 2^22-word columns in the tiled layout (ntt_r16.hip: tiled_index): last pass of an inverse transform storing it, re-layout kernel
+// 2^22-word columns in the tiled layout (tiled_layout.h: tiled_index): last pass of an inverse transform storing it, re-layout kernel
 void launch_ntt_local12_pair_tiled(const u64 *in, u64 *out, const u64 *tw, const u64 *tw_scaled /* tw[j] * scale, j < 2^21 */, u64 scale,
                                    unsigned n_cols, size_t in_col_stride, size_t out_col_stride, hipStream_t s);
 void launch_scale_table(const u64 *in, u64 *out, size_t count, u64 scale, hipStream_t s);
@@ -133,6 +134,11 @@ void launch_barycentric_eval(const u64 *const *d_col_ptrs, unsigned n_cols, size
                              u64 *d_partials, u64 *d_out, hipStream_t s);
 void launch_linear_combination(const u64 *const *d_col_ptrs, const u64 *d_coefs, unsigned n_cols, size_t n, u64 *d_out0,
                                u64 *d_out1, hipStream_t s);
+// d_out[j][c] = sum_i mono_c[i] * x_j^i for every column c (n_cols of 2^log_n coefficients at col_stride; tiled: in the tiled
+// layout, 2^22 only) and every j < n_idx, x_j the LDE point of leaf I0 + d_idx[j] (the DEEP kernels' x_I): what gather_rows would
+// read at d_idx[j] from the columns' LDE, canonical, same order.  One launch for all queries
+void launch_eval_monomials_at(const u64 *d_mono, size_t col_stride, unsigned n_cols, unsigned log_n, bool tiled, const u64 *d_tw_fwd, size_t I0,
+                              const u64 *d_idx, unsigned n_idx, u64 *d_out, hipStream_t s);
 // the opening sets of a column list (opening_args.h; at most DEEP_MAX_SETS) in one launch; d_ptrs / d_coefs: the list's two parts
 // on the device
 void launch_deep_accumulate_multi(const ColumnSet *sets, unsigned n_sets, const u64 *const *d_ptrs, const u64 *d_coefs, size_t N,

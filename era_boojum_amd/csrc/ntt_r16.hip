@@ -20,6 +20,7 @@
 // ds_read_b64 / ds_write_b64 (64 x 4-byte banks).
 #include "gl.h"
 #include "kernels.h"
+#include "tiled_layout.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -500,20 +501,7 @@ struct F10Args {
     unsigned log_n, n_cols, cols_per_block, n_cosets;
     size_t in_col_stride, out_col_stride;
 };
-// TILED layout of a 2^22-word column (the monomial form between an inverse transform and the extensions that read it):
-// element e = m * 4096 + r * 2^LB + l (m: ten bits, r: 12 - LB, l: LB = TILED_LB bits) sits at word
-//     tiled(e) = r * (1024 * 2^LB) + (l >> 1) * 2048 + m * 2 + (l & 1)
-// — the 1024 * 2^LB words one front-pass tile reads are contiguous, ordered so that (a) the pair of 4096-word chunks (b, b + 512) of the
-// inverse transform's last pass, whose results are the words (m, l = 2k) and (m, l = 2k + 1) of FOUR tiles for every m, leaves them
-// as 16-byte words in runs of 1 KB per wave store — the bit reversal of ifft_natural_to_natural (fft/mod.rs:464-491) happens in the
-// store addresses, no pass of its own — and (b) the front pass fetches 16-byte words (m, l pair) for its LDS tile in [m][l] order as before.
-constexpr int TILED_LB = 3;   // lo values per front-pass tile of the tiled layout = 2^LB.  3: 1024 x 8 tiles (64 KB), 512-thread workgroups, TWO per CU —
-                              // their barrier phases interleave; the half-line stores of tiles 2u, 2u + 1 meet in one XCD's L2 (blocks b, b + 8).
-                              // Measured with tiled (contiguous) reads: LDE 93 x 2^22 x 8 27.10 ms against 27.76 ms for 4 (full-line tiles, one
-                              // 1024-thread workgroup per CU); with natural-order reads (64-byte runs) the half-line tiles had lost.
-__host__ __device__ constexpr size_t tiled_index(size_t e) {   // e = m * 4096 + r * 2^LB + l
-    return ((e & 4095u) >> TILED_LB) * ((size_t)1024 << TILED_LB) + ((e & ((1u << TILED_LB) - 1u)) >> 1) * 2048u + (e >> 12) * 2u + (e & 1u);
-}
+// the TILED layout of a 2^22-word column, TILED_LB and tiled_index: tiled_layout.h
 __global__ void front10_table_kernel(u64 *out, const u64 *__restrict__ T, const u64 *__restrict__ round_scale, unsigned n_cosets) {
     const u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n_cosets * 1024u) return;

@@ -15,6 +15,7 @@
 // add per term (~28 VALU ops) by the four mads + five add-with-carry (~10 ops).  HBM: every column value is read once.
 #include "gl.h"
 #include "kernels.h"
+#include "tiled_layout.h"
 
 using gl::u64;
 using gl::u32;
@@ -351,6 +352,107 @@ void launch_deep_accumulate_multi(const ColumnSet *sets, unsigned n_sets, const 
                             sets[t].at[0], sets[t].at[1]};
     const unsigned blocks = (unsigned)((N + 256 * DEEP_PTS - 1) / (256 * DEEP_PTS));
     hipLaunchKernelGGL(deep_accumulate_multi_kernel, dim3(blocks), dim3(256), 0, s, S, N, I0, d_tw_fwd, d_dst0, d_dst1, accumulate);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// out[j][c] = sum_i mono_c[i] * x_j^i,  x_j = 7 * w^bitrev(I0 + idx[j]): the words of leaf idx[j] of an oracle whose LDE is not kept,
+// from its monomial forms (a lean setup's query openings, prover.hip).  Canonical, in the [query][column] order of gather_rows.
+//
+// One workgroup per (query, column); the queries are the fast grid dimension, so the workgroups that stream one column run
+// together and all but the first read it out of L2 / Infinity Cache.  The exponent of a coefficient is split three ways,
+//     i = lane(t) + u * 2^inner_log + k * 2^outer_log,
+// so that for fixed (u, k) the 256 lanes read 256 consecutive words, and a lane's sum is
+//     x^lane(t) * sum_k (x^(2^outer_log))^k * sum_u mono[...] * W[u],      W[u] = (x^(2^inner_log))^u  in LDS (one broadcast read),
+// the inner sum UNREDUCED in gl::Acc160 (four mads and a carry chain per coefficient, one reduction per U of them), the outer one a
+// Horner step per U coefficients.  W and the lanes' own powers are built by doubling from the squares x^(2^j): log2 U + 7 products
+// per lane and as many barriers, no exponentiation loop per lane.  EvalWalk is the split for a layout: the natural order, and the
+// tiled one of 2^22-word columns read where it lies (tiled_layout.h), pairs (m, l & 1) across the lanes.
+// ---------------------------------------------------------------------------------------------------------
+static constexpr unsigned EVAL_TABLE = 2048;   // words of W: 16 KB of LDS
+struct EvalWalk {
+    unsigned lanes;                     // active lanes (fewer than 256 coefficients: one each)
+    unsigned lane_log;                  // lane t stands for the exponent (t >> 1) * 2^lane_log + (t & 1)
+    unsigned inner_log, log_U;          // inner step u < 2^log_U <= EVAL_TABLE stands for u * 2^inner_log and lies u * inner_stride words on
+    unsigned outer_log, K;              // outer step k < K stands for k * 2^outer_log and lies k * outer_stride words on
+    size_t inner_stride, outer_stride;
+};
+static EvalWalk eval_walk(unsigned log_n, bool tiled) {
+    if (tiled) {
+        // e = m * 4096 + 2 u + b  (u = r * 4 + (l >> 1) < 2048, b = l & 1) sits at u * 2048 + 2 m + b; 2 m + b = k * 256 + t
+        static_assert(TILED_LB == 3, "eval_walk spells the tiled layout out for 8-word tiles");
+        static_assert(tiled_index(0) == 0 && tiled_index(1) == 1 && tiled_index(2) == 2048 && tiled_index(8) == 4 * 2048 &&
+                      tiled_index(4096) == 2 && tiled_index((size_t)1023 * 4096 + 2 * 2047 + 1) == ((size_t)1 << 22) - 1 &&
+                      tiled_index((size_t)(3 * 128 + 77) * 4096 + 2 * 1234 + 1) == (size_t)1234 * 2048 + 3 * 256 + 2 * 77 + 1,
+                      "eval_walk does not follow tiled_index");
+        return {256, 12, 1, 11, 19, 8, 2048, 256};
+    }
+    if (log_n < 8) return {1u << log_n, 1, 8, 0, 8, 1, 256, 256};
+    const unsigned log_U = log_n - 8 < 11 ? log_n - 8 : 11;
+    return {256, 1, 8, log_U, 8 + log_U, 1u << (log_n - 8 - log_U), 256, (size_t)256 << log_U};
+}
+__global__ void __launch_bounds__(256)
+eval_monomials_at_kernel(const u64 *mono, size_t col_stride, unsigned n_cols, EvalWalk w, const u64 *tw, size_t I0, const u64 *idx, u64 *out) {
+    __shared__ u64 W[EVAL_TABLE];
+    __shared__ u64 red[256];
+    const unsigned t = threadIdx.x, qi = blockIdx.x, c = blockIdx.y;
+    const u64 x = gl::mul7(gl::domain_point(tw, I0 + idx[qi]));
+    u64 p_lane = 0, p_inner = 0, p_outer = x;   // x^(2^lane_log), x^(2^inner_log), x^(2^outer_log)
+    for (unsigned j = 0; j < w.outer_log; j++) {
+        if (j == w.lane_log) p_lane = p_outer;
+        if (j == w.inner_log) p_inner = p_outer;
+        p_outer = gl::sqr(p_outer);
+    }
+    // red[j] = p_lane^j, j < 128, and W[u] = p_inner^u, by doubling
+    if (t == 0) red[0] = W[0] = 1;
+    __syncthreads();
+    u64 ps = p_lane;
+    for (unsigned s = 0; s < 7; s++) {
+        if (t < (1u << s)) red[t + (1u << s)] = gl::mul(red[t], ps);
+        ps = gl::sqr(ps);
+        __syncthreads();
+    }
+    ps = p_inner;
+    for (unsigned s = 0; s < w.log_U; s++) {
+        for (unsigned j = t; j < (1u << s); j += 256) W[j + (1u << s)] = gl::mul(W[j], ps);
+        ps = gl::sqr(ps);
+        __syncthreads();
+    }
+    const u64 lane_power = (t & 1) ? gl::mul(red[t >> 1], x) : red[t >> 1];
+    __syncthreads();   // red is reused for the sums
+    u64 sum = 0;
+    if (t < w.lanes) {
+        const unsigned U = 1u << w.log_U;
+        const u64 *col = mono + (size_t)c * col_stride + t;
+        for (unsigned k = w.K; k-- > 0;) {
+            const u64 *p = col + (size_t)k * w.outer_stride;
+            gl::Acc160 acc;
+            acc.clear();
+            unsigned u = 0;
+            for (; u + 8 <= U; u += 8) {
+                u64 v[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) v[i] = p[(size_t)(u + i) * w.inner_stride];
+#pragma unroll
+                for (int i = 0; i < 8; i++) acc.fma(v[i], W[u + i]);
+            }
+            for (; u < U; u++) acc.fma(p[(size_t)u * w.inner_stride], W[u]);
+            sum = gl::add(gl::mul(sum, p_outer), acc.reduce());
+        }
+        sum = gl::mul(sum, lane_power);
+    }
+    red[t] = sum;
+    __syncthreads();
+    for (unsigned stride = 128; stride > 0; stride >>= 1) {
+        if (t < stride) red[t] = gl::add(red[t], red[t + stride]);
+        __syncthreads();
+    }
+    if (t == 0) out[(size_t)qi * n_cols + c] = red[0];
+}
+void launch_eval_monomials_at(const u64 *d_mono, size_t col_stride, unsigned n_cols, unsigned log_n, bool tiled, const u64 *d_tw_fwd, size_t I0,
+                              const u64 *d_idx, unsigned n_idx, u64 *d_out, hipStream_t s) {
+    if (!n_cols || !n_idx) return;
+    hipLaunchKernelGGL(eval_monomials_at_kernel, dim3(n_idx, n_cols), dim3(256), 0, s, d_mono, col_stride, n_cols,
+                       eval_walk(log_n, tiled && log_n == 22), d_tw_fwd, I0, d_idx, d_out);
 }
 
 }  // namespace bj

@@ -208,6 +208,7 @@ struct Proving {
     bj::WorkspacePlan plan;
     bj::TmpBuf wit_lde, wit_tree, mono, mono_s2;   // mono: witness monomials, mono_s2: stage-2 monomials (both kept for DEEP)
     bj::TmpBuf s2_lde, s2_tree, T, q_lde, q_tree, deep;
+    bj::TmpBuf setup_coset;    // lean setup: [setup width][n], one coset of its columns rebuilt from S->d_mono; after round 3 it holds coset 0
     const u64 *Tm = nullptr;   // the 2 q chunks of n coefficients each of the quotient, in the monomial layout of this trace length
     std::vector<u64> wit_cap, s2_cap, q_cap;
     // base columns whose coset 0 is evaluated, in the order of prover.rs:1550-1683; msrcs: the monomial forms of the same
@@ -246,7 +247,7 @@ struct Proving {
     Src mono_src(const bj::Opened &o) const;
     int evaluate_at(u64 *w, u64 open_shift, const std::vector<Src> &ss, const u64 *at, std::vector<u64> &vals);
     int round5a_deep();
-    int deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector<Src> &ms, const u64 *vals, const u64 *at);
+    int deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector<Src> &ms, const u64 *vals, const u64 *at, bool on_monomials = false);
     int flush_deep(DeepSets &D);
     int round5b_fri();
     int round6_queries(Queries &qr);
@@ -286,10 +287,12 @@ int Proving::reserve_workspace() {
     if (int rc = bj_fri_schedule(S->security, S->cap_size, S->pow_bits, S->log_fri, log_n, &new_pow, &num_queries, sched, &sched_len, &final_degree))
         return bj::fail(ctx, rc, "bj_prove: compute_fri_schedule failed");
     const unsigned alpha_terms = L.n_lookup_terms + S->gates.n_spec_terms + S->gates.n_general_terms + 1 + L.n_chunks;
-    plan = bj::workspace_plan(bj::workspace_shape(L, sh.world, S->tiled, alpha_terms, S->pub_cols.data(), S->pub_rows.data(), S->pub_cols.size(),
-                                                  count_mult && !d_multiplicities,
-                                                  !hw ? bj::WS_HOST_NONE : absorb ? bj::WS_HOST_ABSORBING : bj::WS_HOST_NOT_ABSORBING, new_pow != 0,
-                                                  sched, sched_len, num_queries));
+    bj::WorkspaceShape shape = bj::workspace_shape(L, sh.world, S->tiled, alpha_terms, S->pub_cols.data(), S->pub_rows.data(), S->pub_cols.size(),
+                                                   count_mult && !d_multiplicities,
+                                                   !hw ? bj::WS_HOST_NONE : absorb ? bj::WS_HOST_ABSORBING : bj::WS_HOST_NOT_ABSORBING, new_pow != 0,
+                                                   sched, sched_len, num_queries);
+    shape.lean = S->lean;
+    plan = bj::workspace_plan(shape);
     if (int rc = bj::arena_reset(ctx, std::max(plan.total(), ctx->arena_learned))) return rc;
     proof->ws_reserved = ctx->arena_elems * 8;
     return BJ_OK;
@@ -505,23 +508,37 @@ int Proving::round3_quotient() {
     u64 *t0 = Tl, *t1 = Tl + Qe;
     const u64 *a_lookup = d_alphas.p, *a_spec = d_alphas.p + 2 * n_lookup_terms, *a_gates = a_spec + 2 * n_spec_terms,
               *a_l1 = a_gates + 2 * n_gate_terms;
-    const bj::Cols wit{wit_lde.p, Ln}, setup{S->d_lde, Ln}, s2{s2_lde.p, Ln};
-    auto sink = [&](const u64 *d_powers) { return bj::TermSink{d_powers, Qe, t0, t1}; };
-    if (Qe) {
+    // Every term kernel on `points` points from local point `first` on, with the setup's columns there given as `setup`.  The
+    // accumulators are per point, so the whole range at once (the setup's LDE is resident) and one coset after the other (a lean
+    // setup) write the same words.
+    auto terms_on = [&](size_t first, size_t points, const bj::Cols setup) {
+        const bj::Cols wit{wit_lde.p + first, Ln}, s2{s2_lde.p + first, Ln};
+        auto sink = [&](const u64 *d_powers) { return bj::TermSink{d_powers, points, t0 + first, t1 + first}; };
         const bj::TermSink general = sink(a_gates), spec = sink(a_spec);
         bj::launch_circuit_gates(ctx, S, wit, setup.at(L.constant(0)), &general, &spec, st);
-    }
-    if (has_lookup && Qe)
-        bj::launch_quotient_lookup(bj::LookupArg{wit.at(L.lookup_var(0, 0)), setup.at(L.table(0)), S->tid_var ? nullptr : setup.at(L.table_id()).p,
-                                                 wit.at(L.multiplicity()).p, S->lookup_reps, S->lookup_w, lbeta, lgamma},
-                                   s2.at(L.lookup_a(0)).p, s2.at(L.lookup_b()).p, Ln, sink(a_lookup), st);
-    if (Qe) {
+        if (has_lookup)
+            bj::launch_quotient_lookup(bj::LookupArg{wit.at(L.lookup_var(0, 0)), setup.at(L.table(0)), S->tid_var ? nullptr : setup.at(L.table_id()).p,
+                                                     wit.at(L.multiplicity()).p, S->lookup_reps, S->lookup_w, lbeta, lgamma},
+                                       s2.at(L.lookup_a(0)).p, s2.at(L.lookup_b()).p, Ln, sink(a_lookup), st);
         // variables + sigmas + z and the partial products + 1/(x - 1), accumulators read and written
-        const int pc = bj::probe_begin(ctx, "quotient_copy_perm", 8.0 * (2.0 * V + 2 * (1 + L.n_partials) + 1) * (double)Qe + 32.0 * (double)Qe);
+        const int pc = bj::probe_begin(ctx, "quotient_copy_perm", 8.0 * (2.0 * V + 2 * (1 + L.n_partials) + 1) * (double)points + 32.0 * (double)points);
         const u64 *h_alpha_l1 = alphas.data() + (a_l1 - d_alphas.p);   // the same power on the host: it goes into the kernel's arguments
         bj::launch_quotient_copy_perm(bj::CopyPermArg{wit, setup.at(L.sigma(0)), S->d_non_res, V, q, log_n, ctx->tw_fwd, beta, gamma, S->small_non_residues},
-                                      s2, S->log_L, h_alpha_l1, sink(a_l1 + 2), I0, S->d_inv_xm1, st);
+                                      s2, S->log_L, h_alpha_l1, sink(a_l1 + 2), I0 + first, S->d_inv_xm1 + first, st);
         bj::probe_end(ctx, pc);
+    };
+    if (S->lean) {
+        // The setup kept no LDE: its columns are extended from the monomials one coset at a time into [width][n] words, and the
+        // terms of that coset's n points are taken before the next one overwrites them.  Highest coset first, so that coset 0 is
+        // what stays in the buffer: round 4 evaluates the setup's polynomials at z from it.  q == 0 cannot happen (a power of two).
+        if ((rc = setup_coset.take(ctx, bj::WS_SETUP_COSET))) return rc;
+        for (unsigned c = q; c-- > 0 && !rc;) {
+            rc = lde_cols(S->d_mono, setup_coset.p, n, L.widths[bj::ORACLE_SETUP], S->log_L, c, 1);
+            if (!rc) terms_on((size_t)c * n, n, bj::Cols{setup_coset.p, n});
+        }
+        if (rc) return rc;
+    } else if (Qe) {
+        terms_on(0, Qe, bj::Cols{S->d_lde, Ln});
     }
     BJ_CHECK_LAUNCH(ctx);
     // flatten (= bit-reversal of the evaluations), iNTT on their coset (prover.rs:1386-1422)
@@ -561,8 +578,10 @@ int Proving::round3_quotient() {
 // An opened polynomial of the layout as its columns in the LDE arrays / in the monomial arrays (chunk j of the quotient:
 // coefficients [j*n, (j+1)*n) of T's two monomial forms, which lie Q apart instead of side by side).
 Src Proving::lde_src(const bj::Opened &o) const {
-    const u64 *bases[4] = {wit_lde.p, s2_lde.p, q_lde.p, S->d_lde};
-    const size_t strides[4] = {Ln, Ln, N, Ln};
+    // a lean setup's columns exist on coset 0 only (setup_coset, stride n): enough for the evaluations of round 4, which read the
+    // first coset; DEEP never takes them from here (deep_set combines that set on the monomials)
+    const u64 *bases[4] = {wit_lde.p, s2_lde.p, q_lde.p, S->lean ? setup_coset.p : S->d_lde};
+    const size_t strides[4] = {Ln, Ln, N, S->lean ? n : Ln};
     const u64 *b = bases[o.oracle];
     return {b + o.col0 * strides[o.oracle], o.col1 == bj::NO_COLUMN ? nullptr : b + o.col1 * strides[o.oracle]};
 }
@@ -677,10 +696,11 @@ int Proving::flush_deep(DeepSets &D) {
 
 // One opening set: the polynomials ls (on the LDE) = ms (monomials) with the values vals at the point at.  Takes the next
 // ms.size() challenges; a large set gets its extended numerator (an arena buffer of 2 N words); queues the set for flush_deep.
-int Proving::deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector<Src> &ms, const u64 *vals, const u64 *at) {
+// on_monomials: the set goes that way whatever its size (its columns are on no FRI domain: the set at z under a lean setup).
+int Proving::deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector<Src> &ms, const u64 *vals, const u64 *at, bool on_monomials) {
     const u64 *ch = D.chs.data() + 2 * D.choff;
     D.choff += ms.size();
-    if (bj::open_columns(ms.data(), ms.size()).size() < bj::WS_LARGE_SET) {   // a handful of columns: streaming them over the FRI domain is cheaper than an extra LDE pass
+    if (!on_monomials && bj::open_columns(ms.data(), ms.size()).size() < bj::WS_LARGE_SET) {   // a handful of columns: streaming them over the FRI domain is cheaper than an extra LDE pass
         D.queue(ls, ch, vals, at);
         return BJ_OK;
     }
@@ -729,7 +749,7 @@ int Proving::round5a_deep() {
     if (sh.world > 1 && (rc = D.num_slice.take(ctx, bj::WS_NUM_SLICE))) return rc;
     const u64 zero2[2] = {0, 0};
     for (auto &set : sets) {   // in the order the challenges are handed out
-        if (set.point == bj::OPEN_AT_Z) rc = deep_set(D, srcs, msrcs, vz.data(), z);
+        if (set.point == bj::OPEN_AT_Z) rc = deep_set(D, srcs, msrcs, vz.data(), z, S->lean);
         else if (set.point == bj::OPEN_AT_Z_OMEGA) rc = deep_set(D, zsrc, mz, vzo.data(), zo);
         else if (set.point == bj::OPEN_AT_ZERO) rc = deep_set(D, lsrc, ml, v0.data(), zero2);
         else {
@@ -797,7 +817,7 @@ int Proving::gather_base_queries(Queries &qr) {
     const unsigned W = sh.world, depth = qr.depth;
     // a leaf lives on rank index / N; every rank gathers at (index mod N) and the owner's answer is kept
     const unsigned *widths = L.widths;
-    const u64 *bases[4] = {wit_lde.p, s2_lde.p, q_lde.p, S->d_lde};
+    const u64 *bases[4] = {wit_lde.p, s2_lde.p, q_lde.p, S->d_lde};   // the last is null under a lean setup: evaluated below
     const size_t strides[4] = {Ln, Ln, N, Ln};
     const u64 *trees[4] = {wit_tree.p, s2_tree.p, q_tree.p, S->d_tree};
     int rc = BJ_OK;
@@ -815,7 +835,10 @@ int Proving::gather_base_queries(Queries &qr) {
     qr.gathered.resize(G * W);
     size_t off = 0;
     for (int o = 0; o < 4; o++) {
-        bj::launch_gather_rows(bases[o], strides[o], widths[o], d_idx.p, (unsigned)num_queries, d_g.p + off, st);
+        if ((unsigned)o == bj::ORACLE_SETUP && S->lean)   // the leaf's words are the setup polynomials at the leaf's point; the paths come from the kept tree
+            bj::launch_eval_monomials_at(S->d_mono, n, widths[o], log_n, S->tiled, ctx->tw_fwd, I0, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
+        else
+            bj::launch_gather_rows(bases[o], strides[o], widths[o], d_idx.p, (unsigned)num_queries, d_g.p + off, st);
         off += (size_t)widths[o] * num_queries;
         bj::launch_merkle_paths(trees[o], N, depth, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
         off += (size_t)depth * 4 * num_queries;

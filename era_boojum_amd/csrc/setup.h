@@ -31,7 +31,9 @@ struct bj_setup : bj::CircuitShape {   // proof_layout.h: bj::circuit_shape fill
     gl::u64 *d_nat = nullptr;          // [setup width][n] natural-order values (replicated)
     gl::u64 *d_mono = nullptr;         // [setup width][n] monomial forms (replicated; the DEEP numerator is combined on them)
     bool tiled = false;            // monomials (these and every proof's) in the tiled layout of ntt_r16.hip: 2^22-row traces
-    gl::u64 *d_lde = nullptr;          // [setup width][cl][n]
+    gl::u64 *d_lde = nullptr;          // [setup width][cl][n]; null once a lean setup stands
+    bool lean = false;             // BJ_SETUP_LEAN as it stood when the setup was created: the LDE is not kept, a proof rebuilds the quotient's
+                                   // cosets from d_mono one at a time and evaluates the queried leaves (prover.hip); never set on a shard
     gl::u64 *d_tree = nullptr;         // local subtree
     gl::u64 *d_non_res = nullptr;
     gl::u64 *d_inv_xm1 = nullptr;      // 1 / (x - 1) on the points this GPU evaluates the quotient on (a property of the domain)

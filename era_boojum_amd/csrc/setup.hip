@@ -41,7 +41,7 @@ void bj_setup_destroy(bj_setup *s) {
 
 int bj_setup_create(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const uint64_t *h_constants,
                     const uint64_t *h_tables, const bj_proof_config *cfg, bj_setup **out) {
-    return bj_setup_create_sharded(ctx, c, h_sigmas, h_constants, h_tables, cfg, nullptr, out);
+    return bj::setup_create_impl(ctx, c, h_sigmas, nullptr, h_constants, h_tables, cfg, nullptr, out, bj::env().setup_lean);
 }
 
 int bj_setup_create_sharded(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const uint64_t *h_constants,
@@ -134,7 +134,7 @@ int bj::circuit_check(bj_ctx *ctx, const char *who, const bj_circuit *c, const b
 
 int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas, const std::function<int(bj_setup *, u64 *)> &fill_sigmas,
                           const uint64_t *h_constants, const uint64_t *h_tables, const bj_proof_config *cfg, const bj_comm *comm,
-                          bj_setup **out) {
+                          bj_setup **out, bool lean) {
     if (int rc = bj::bind(ctx)) return rc;
     if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_create: null out pointer");
     *out = nullptr;
@@ -228,6 +228,12 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
     s->cap.resize(4 * s->cap_size);
     if (!rc) rc = bj::gather_cap(ctx, s->sh, s->d_tree, s->Nl, s->cap_size, s->cap.data());
     if (rc) return bail(rc);
+    if (lean && s->sh.world == 1) {   // the tree and the cap stand: from here on nothing but a proof wants the LDE, and a lean proof rebuilds what it reads
+        if ((rc = bj_sync(ctx))) return bail(rc);
+        (void)hipFree(s->d_lde);
+        s->d_lde = nullptr;
+        s->lean = true;
+    }
     *out = s;
     return BJ_OK;
 }

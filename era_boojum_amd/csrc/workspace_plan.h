@@ -17,7 +17,7 @@ enum WsId : unsigned {
     // exact entries: the buffers the prover takes itself, in the order of the rounds
     WS_MULTIPLICITY, WS_WIT_LDE, WS_MONO, WS_MONO_S2, WS_WIT_TREE, WS_CAPACITY,
     WS_S2_NAT, WS_S2_SCRATCH, WS_S2_LDE, WS_S2_TREE,
-    WS_ALPHAS, WS_T, WS_T_LOCAL, WS_RESIDUES, WS_T_TILED, WS_Q_LDE, WS_Q_TREE,
+    WS_ALPHAS, WS_T, WS_T_LOCAL, WS_RESIDUES, WS_SETUP_COSET, WS_T_TILED, WS_Q_LDE, WS_Q_TREE,
     WS_BARY_W,
     WS_DEEP, WS_NUM_MONO, WS_NUM_SLICE, WS_NUM_LDE,
     WS_FRI_TREE, WS_FRI_LAYER, WS_FRI_PART, WS_FRI_FINAL,
@@ -31,7 +31,7 @@ inline const char *ws_name(unsigned id) {
     static const char *const names[WS_N_IDS] = {
         "multiplicity column", "wit_lde", "mono", "mono_s2", "wit_tree", "capacity words",
         "s2_nat", "stage-2 scratch", "s2_lde", "s2_tree",
-        "alphas", "T", "T of this rank", "residue gather", "tiled T", "q_lde", "q_tree",
+        "alphas", "T", "T of this rank", "residue gather", "setup coset", "tiled T", "q_lde", "q_tree",
         "barycentric w",
         "deep", "num_mono", "num_slice", "num_lde",
         "FRI tree", "FRI layer", "FRI part", "FRI final buffer",
@@ -54,6 +54,7 @@ struct WorkspaceShape {
     unsigned alpha_terms = 0;                // powers of the quotient challenge
     unsigned world = 1;
     bool tiled = false;
+    bool lean = false;                       // the setup keeps no LDE (bj_setup::lean): set by the prover, single device only
     size_t tree_words = 0;                   // bj_merkle_tree_digests(N, cap_size / world) * 4
     unsigned depth = 0;                      // path length of the base oracles: log2(N * world / cap_size)
     unsigned opened_cols = 0;                // base columns of the polynomials opened at z (an F_p^2 polynomial counts two)
@@ -145,6 +146,7 @@ inline WorkspacePlan workspace_plan(const WorkspaceShape &s) {
         P.take(WS_T_LOCAL, 2 * s.Qe);
         P.take(WS_RESIDUES, 2 * s.Q);
     }
+    if (s.lean) P.take(WS_SETUP_COSET, (size_t)s.n_setup * s.n);   // one coset of the setup columns at a time; round 4 reads the last one left in it
     if (s.tiled) P.take(WS_T_TILED, 2 * s.Q);
     P.take(WS_Q_LDE, (size_t)2 * s.q * s.N);
     P.take(WS_Q_TREE, s.tree_words);
@@ -161,7 +163,8 @@ inline WorkspacePlan workspace_plan(const WorkspaceShape &s) {
     if (s.has_lookup) sets.push_back(2 * (size_t)s.lookup_terms);
     sets.insert(sets.end(), s.pub_set_cols.begin(), s.pub_set_cols.end());
     for (size_t &cols : sets) {
-        if (cols < WS_LARGE_SET) continue;
+        // a lean setup has its columns on no FRI domain: the set opened at z, which holds them, always goes through its monomials
+        if (cols < WS_LARGE_SET && !(s.lean && &cols == &sets[0])) continue;
         P.take(WS_NUM_LDE, 2 * s.N);
         P.allow(WS_ARGS_COMBINE, column_list_arg_words(cols));
         if (sharded && s.n % W == 0 && s.n / W >= 256) P.allow(WS_GATHER_STAGING, gather_columns_staging_words(W, 2, s.n / W));

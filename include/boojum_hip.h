@@ -591,7 +591,16 @@ typedef struct bj_setup bj_setup; /* device-resident SetupStorage + setup Merkle
 typedef struct bj_proof bj_proof;
 
 /* h_sigmas [num_vars][n], h_constants [num_constant_cols][n], h_tables [lookup_width+1][n] (NULL without lookups):
- * natural-order values over the main domain (SetupBaseStorage, polynomial_storage.rs:48-75). */
+ * natural-order values over the main domain (SetupBaseStorage, polynomial_storage.rs:48-75).
+ * Lean setups: with BJ_SETUP_LEAN set in the environment (any value that does not start with '0'; read with the other switches,
+ * re-read by bj_env_reload) when this call, bj_setup_create_from_dump or bj_setup_create_from_placement runs, the setup keeps
+ * its natural-order columns, its monomials and its tree and frees the LDE of its columns once the tree stands: n_cols * L * n * 8
+ * bytes less in HBM (L = max(fri_lde_factor, quotient_degree)), the same cap, and proofs that are the resident setup's byte for
+ * byte.  Every proof then extends the setup columns over the quotient's cosets again, one coset at a time, and evaluates the
+ * setup words of the queried leaves from the monomials (cost: DESIGN.md §5); its workspace grows by one coset of the setup
+ * columns.  The mode is the setup's: what the switch says later changes nothing, lean and resident setups live side by side in one
+ * context.  Peak memory during the creation is that of a resident setup.  bj_setup_create_sharded does not look at the switch: a
+ * rank holds 1 / world of the LDE already. */
 int bj_setup_create(bj_ctx *ctx, const bj_circuit *circuit, const uint64_t *h_sigmas, const uint64_t *h_constants,
                     const uint64_t *h_tables, const bj_proof_config *config, bj_setup **out);
 /* ---- one proof across several GPUs ----------------------------------------------------------------
@@ -678,7 +687,8 @@ void bj_setup_destroy(bj_setup *s);
 int bj_setup_cap(const bj_setup *s, uint64_t *h_cap); /* vk.setup_merkle_tree_cap: cap_size*4 u64 */
 /* HBM held by a setup (its shard on a sharded setup): natural-order columns, monomials, the LDE of the cosets it owns, its
  * Merkle subtree, 1 / (x - 1) on its quotient points — the "per rank" column of DESIGN.md §6's memory table — and the u32
- * placement of a setup made by bj_setup_create_from_placement. */
+ * placement of a setup made by bj_setup_create_from_placement.  A lean setup (BJ_SETUP_LEAN, bj_setup_create) holds no LDE: it
+ * reports exactly n_cols * L * n * 8 bytes less than the same setup created resident. */
 int bj_setup_device_bytes(const bj_setup *s, size_t *bytes);
 int bj_setup_shape(const bj_setup *s, unsigned *log_n, unsigned *num_vars, unsigned *num_witness_cols,
                    unsigned *num_public_inputs); /* any out pointer may be NULL */
