@@ -400,6 +400,28 @@ class Context:
         ch = np.ascontiguousarray(np.array(challenges, dtype=np.uint64).reshape(-1))
         self._check(self._lib.bj_linear_combination(self._h, p0, p1, k, _np_ptr(ch), n, d_out0, d_out1))
 
+    def eval_monomials_at(self, d_mono, col_stride, n_cols, log_n, log_lde, d_idx, n_idx, d_out, tiled=False, first_leaf=0):
+        """bj_eval_monomials_at: d_out[j][c] = the polynomial of column c at the point of leaf first_leaf + d_idx[j] of the
+        2^(log_n + log_lde) LDE domain (d_idx: n_idx u64 on the device), from natural-order or tiled monomials."""
+        self._check(self._lib.bj_eval_monomials_at(self._h, d_mono, col_stride, n_cols, log_n, log_lde, 1 if tiled else 0, first_leaf,
+                                                   d_idx, n_idx, d_out))
+
+    def merkle_leaves_absorb(self, d_cols, col_stride, n_cols, num_leaves, d_capacity, d_digests, first, last):
+        """bj_merkle_leaves_absorb: one group of columns into the leaf sponges of the context's algebraic tree hasher; the capacity
+        words travel through d_capacity ([4][num_leaves]) between groups, the last group writes d_digests ([num_leaves][4])."""
+        self._check(self._lib.bj_merkle_leaves_absorb(self._h, d_cols, col_stride, n_cols, num_leaves, d_capacity, d_digests,
+                                                      1 if first else 0, 1 if last else 0))
+
+    def pow_search(self, pow_runner, seed5, pow_bits, base, count):
+        """bj_pow_search: the smallest nonce of [base, base + count) that the runner (BJ_POW_*) accepts for the five seed words at
+        pow_bits, or 2^64 - 1 when the window holds none."""
+        seed = np.ascontiguousarray(seed5, dtype=np.uint64)
+        if seed.size != 5:
+            raise ValueError("pow_search: the seed is five words")
+        out = C.c_uint64()
+        self._check(self._lib.bj_pow_search(self._h, int(pow_runner), _np_ptr(seed), pow_bits, base, count, C.byref(out)))
+        return int(out.value)
+
     def fri_fold_step(self, d_c0, d_c1, length, k, d_o0, d_o1, log_full, coset_inv, ch):
         self._check(self._lib.bj_fri_fold_step(self._h, d_c0, d_c1, length, k, d_o0, d_o1, log_full, coset_inv, ch[0], ch[1]))
 

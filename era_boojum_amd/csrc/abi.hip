@@ -809,6 +809,39 @@ int bj_poseidon_permute(bj_ctx *ctx, uint64_t *d_states, size_t n_states) {
     return BJ_OK;
 }
 
+int bj_merkle_leaves_absorb(bj_ctx *ctx, const uint64_t *d_cols, size_t col_stride, unsigned n_cols, size_t num_leaves,
+                            uint64_t *d_capacity, uint64_t *d_digests, int first, int last) {
+    if (int rc = bind(ctx)) return rc;
+    // launch_tree_leaves_absorb takes any other hasher for Poseidon2: a byte hasher has no absorption run and is refused here
+    if (ctx->hasher != BJ_HASHER_POSEIDON2 && ctx->hasher != BJ_HASHER_POSEIDON)
+        return fail(ctx, BJ_ERR_UNSUPPORTED, "bj_merkle_leaves_absorb: tree hasher %d is a byte hasher, it has no absorption run", ctx->hasher);
+    if (!d_cols || n_cols == 0) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_merkle_leaves_absorb: no columns");
+    if (!last && n_cols % 8 != 0)
+        return fail(ctx, BJ_ERR_INVALID_ARG, "bj_merkle_leaves_absorb: %u columns in a group that is not the last (a multiple of 8 is)", n_cols);
+    if (num_leaves == 0) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_merkle_leaves_absorb: no leaves");
+    if (col_stride < num_leaves) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_merkle_leaves_absorb: col_stride smaller than num_leaves");
+    if ((!d_capacity && !(first && last)) || (!d_digests && last)) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_merkle_leaves_absorb: null pointer");
+    bj::launch_tree_leaves_absorb(ctx->hasher, d_cols, col_stride, n_cols, num_leaves, d_capacity, d_digests, first != 0, last != 0, ctx->stream);
+    BJ_CHECK_LAUNCH(ctx);
+    return BJ_OK;
+}
+
+int bj_pow_search(bj_ctx *ctx, int pow_runner, const uint64_t *h_seed5, unsigned pow_bits, uint64_t base, uint64_t count,
+                  uint64_t *h_result) {
+    if (int rc = bind(ctx)) return rc;
+    if (!h_seed5 || !h_result) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_pow_search: null pointer");
+    if (pow_runner != BJ_POW_BLAKE2S256 && pow_runner != BJ_POW_KECCAK256) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_pow_search: unknown runner %d", pow_runner);
+    if (count == 0 || count > ((u64)1 << 24)) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_pow_search: count must be 1..2^24");
+    if (pow_bits > 64) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_pow_search: pow_bits above 64");
+    if (base >= ~(u64)0 - count + 1) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_pow_search: the window passes 2^64 - 1");
+    if (int rc = ensure_scratch(ctx, 1)) return rc;   // the result word lives in the context's scratch
+    const u64 none = ~(u64)0;
+    if (int rc = bj::h2d_async(ctx, ctx->d_scratch, &none, 8)) return rc;
+    bj::launch_pow(pow_runner, h_seed5, pow_bits, base, count, ctx->d_scratch, ctx->stream);
+    BJ_CHECK_LAUNCH(ctx);
+    return bj_memcpy_d2h(ctx, h_result, ctx->d_scratch, 8);
+}
+
 // --------------------------------------------------------------------------------------------------------- FRI
 
 int bj_fri_fold(bj_ctx *ctx, const uint64_t *d_c0, const uint64_t *d_c1, size_t len, uint64_t *d_o0, uint64_t *d_o1,

@@ -111,6 +111,24 @@ int bj_linear_combination(bj_ctx *ctx, const uint64_t *const *h_src_c0, const ui
     return bj::combine_monomials(ctx, L, n, d_out_c0, d_out_c1);
 }
 
+int bj_eval_monomials_at(bj_ctx *ctx, const uint64_t *d_mono, size_t col_stride, unsigned n_cols, unsigned log_n, unsigned log_lde,
+                         int tiled, size_t first_leaf, const uint64_t *d_idx, unsigned n_idx, uint64_t *d_out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!d_mono || !d_idx || !d_out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_eval_monomials_at: null pointer");
+    const unsigned log_full = log_n + log_lde;
+    if (log_n > 32 || log_lde > 32 || log_full == 0 || log_full > 32) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_eval_monomials_at: bad domain");
+    if (col_stride < ((size_t)1 << log_n)) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_eval_monomials_at: col_stride smaller than 2^log_n");
+    if (n_cols > 65535) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_eval_monomials_at: more than 65535 columns (one grid row each)");
+    if (tiled && log_n != 22)
+        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_eval_monomials_at: the tiled layout is defined for 2^22-word columns");
+    if (first_leaf >= ((size_t)1 << log_full))   // the indices themselves are on the device: the caller's obligation
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_eval_monomials_at: first_leaf %zu passes the 2^%u-point domain", first_leaf, log_full);
+    if (int rc = bj::ensure_twiddles(ctx, log_full, false)) return rc;
+    bj::launch_eval_monomials_at(d_mono, col_stride, n_cols, log_n, tiled != 0, ctx->tw_fwd, first_leaf, d_idx, n_idx, d_out, ctx->stream);
+    BJ_CHECK_LAUNCH(ctx);
+    return BJ_OK;
+}
+
 }  // extern "C"
 
 namespace bj {

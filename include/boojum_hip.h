@@ -46,7 +46,8 @@ typedef struct bj_ctx bj_ctx;
  * 4: bj_proof_config.pow_runner, bj_circuit.table_id_col = BJ_TABLE_ID_AS_VARIABLE (round 5); 5: bj_comm_replay_capture,
  * bj_proof_workspace_bytes, bj_setup_device_bytes; 6: bj_prove_async / bj_proof_wait, the tiled-monomial operators, bj_comm_peer_create (round 6);
  * entry points added within version 6 (no layout of an existing struct changes with them): bj_check_satisfied, bj_lookup_multiplicities, bj_vk_* / bj_verify,
- * bj_sigma_cells, bj_check_copy_constraints, bj_verify_batch / bj_verify_batch_ms */
+ * bj_sigma_cells, bj_check_copy_constraints, bj_verify_batch / bj_verify_batch_ms, bj_eval_monomials_at, bj_merkle_leaves_absorb,
+ * bj_pow_search */
 #define BJ_ABI_VERSION 6
 int bj_abi_version(void);
 /* 1 if bj_setup_create accepts bj_gate_desc.kind == kind, else 0: gate kinds are added within an ABI version (no layout
@@ -218,6 +219,18 @@ int bj_merkle_tree_proof(bj_ctx *ctx, const uint64_t *d_tree, size_t num_leaves,
 int bj_poseidon2_permute(bj_ctx *ctx, uint64_t *d_states, size_t n_states);
 /* The same for the Poseidon (v1) permutation of BJ_HASHER_POSEIDON / BJ_TRANSCRIPT_POSEIDON; canonical words out. */
 int bj_poseidon_permute(bj_ctx *ctx, uint64_t *d_states, size_t n_states);
+/* One RUN of absorptions of the context's algebraic tree hasher over leaves whose columns arrive in groups (bj_prove hashes the
+ * witness this way while later groups are still on their way; bring-up / parity).  For every leaf I < num_leaves: the sponge state
+ * is (rate words 0, capacity words = 0 if first != 0, else d_capacity[k * num_leaves + I], k < 4, as any u64); then, eight
+ * columns at a time, rate words <- d_cols[(c + k) * col_stride + I] (zeros past n_cols), permute.  last == 0: the four capacity
+ * words go back to d_capacity (weak words: congruent to the state, not canonical) and d_digests is not touched; last != 0: the
+ * first four state words, canonical, go to d_digests[4 * I ..] and d_capacity is not written.  The groups of one leaf hashing
+ * (first = 1 on the first, last = 1 on the last, every group but the last a multiple of eight columns wide) give layer 0 of
+ * bj_merkle_tree_build over all the columns; num_leaves need not be a power of two.  d_capacity may be NULL when first and last
+ * are both set, d_digests when last == 0.  Refused: a byte hasher on the context (BJ_HASHER_BLAKE2S / BJ_HASHER_KECCAK256),
+ * n_cols == 0, n_cols % 8 != 0 with last == 0, num_leaves == 0, col_stride < num_leaves, a null pointer that the run uses. */
+int bj_merkle_leaves_absorb(bj_ctx *ctx, const uint64_t *d_cols, size_t col_stride, unsigned n_cols, size_t num_leaves,
+                            uint64_t *d_capacity, uint64_t *d_digests, int first, int last);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * FRI.  Replaces fold_multiple / interpolate_* (src/cs/implementations/fri/mod.rs:362-678).
@@ -285,6 +298,20 @@ int bj_deep_quotient_accumulate_sets(bj_ctx *ctx, const bj_deep_set *sets, unsig
  * are given as in the DEEP call; d_out_c0 / d_out_c1 receive n canonical values each. */
 int bj_linear_combination(bj_ctx *ctx, const uint64_t *const *h_src_c0, const uint64_t *const *h_src_c1, size_t n_src,
                           const uint64_t *h_challenges, size_t n, uint64_t *d_out_c0, uint64_t *d_out_c1);
+/* The words of chosen leaves of an oracle whose LDE is not kept, from its monomial forms (what a proof on a lean setup runs in
+ * place of the gather of its setup leaves; bring-up / parity):
+ *   d_out[j * n_cols + c] = sum_{i < n} mono_c[i] * x_j^i,   n = 2^log_n,   x_j = 7 * w_{nL}^{bitrev(first_leaf + d_idx[j])},
+ * as a canonical word — x_j is the x_I of bj_deep_quotient_accumulate at I = first_leaf + d_idx[j], i.e. the word bj_lde_batch
+ * writes at [c][I].  Column c holds its n coefficients at d_mono + c * col_stride, in natural order, or, for tiled != 0, in the
+ * tiled layout of bj_tiled_permute_batch (log_n = 22 only).  Coefficients may be any u64: the kernel sums the raw words times
+ * canonical powers in the 160-bit accumulator of csrc/gl.h (any u64 operands, exact up to 2^32 terms; a lane reduces it after at
+ * most 2048), so a word >= p counts as its residue. d_idx holds n_idx local leaf indices (u64; repeats allowed), first_leaf the first leaf
+ * of the caller's shard (0 on one device).  first_leaf + d_idx[j] < 2^(log_n + log_lde) for every j is the CALLER'S obligation:
+ * the indices are read on the device only; first_leaf itself is checked.  n_cols = 0 or n_idx = 0 does nothing.  Refused: null
+ * pointers, col_stride < n, tiled with log_n != 22, log_n + log_lde outside 1..32, first_leaf outside the domain,
+ * n_cols > 65535. */
+int bj_eval_monomials_at(bj_ctx *ctx, const uint64_t *d_mono, size_t col_stride, unsigned n_cols, unsigned log_n, unsigned log_lde,
+                         int tiled, size_t first_leaf, const uint64_t *d_idx, unsigned n_idx, uint64_t *d_out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Fiat–Shamir transcript (host side, tiny data, order-critical).  Replaces `Transcript` impls
@@ -312,6 +339,14 @@ typedef struct bj_transcript bj_transcript;
 /* bj_proof_config.pow_runner: the PoWRunner implementations of src/cs/implementations/pow.rs */
 #define BJ_POW_BLAKE2S256 1   /* pow.rs:50-133 */
 #define BJ_POW_KECCAK256 2    /* pow.rs:139-230 (original Keccak padding, as the tree hasher) */
+/* One batch of the prover's proof-of-work search (bring-up / parity): *h_result = the smallest nonce of [base, base + count) for
+ * which the first 8 digest bytes of hash( le64(h_seed5[0]) || ... || le64(h_seed5[4]) || le64(nonce) ), read as a little-endian
+ * u64, have at least pow_bits trailing zeros (the word 0 has 64), or ~0 when the window holds none.  h_seed5: five host words,
+ * hashed as they are (40 bytes).  Synchronous.  Refused: null pointers, a pow_runner other than BJ_POW_BLAKE2S256 /
+ * BJ_POW_KECCAK256, count == 0, count > 2^24 (the prover's batch), pow_bits > 64, base + count >= 2^64 (a window that wraps or
+ * holds the nonce ~0, which is the answer for none). */
+int bj_pow_search(bj_ctx *ctx, int pow_runner, const uint64_t *h_seed5, unsigned pow_bits, uint64_t base, uint64_t count,
+                  uint64_t *h_result);
 int bj_transcript_create(int kind, bj_transcript **out);
 void bj_transcript_destroy(bj_transcript *t);
 int bj_transcript_absorb(bj_transcript *t, const uint64_t *els, size_t n);

@@ -141,33 +141,18 @@ def test_lean_keyword_of_the_binding():
 
 def test_first_and_last_leaf():
     """Item 3: the evaluation kernel at leaf 0 (x = 7, the coset shift itself) and at leaf N - 1.  Which leaves a proof queries is up
-    to its transcript, so circuits of 2^8 rows are tried, seed after seed and 64 at the most, with the RESIDENT setup, until one
-    proof has queried leaf 0 and one leaf N - 1 (60 queries into 512 leaves: a seed hits a given leaf with probability 0.11);
-    those seeds' proofs are then made lean and compared.  Not finding both is a failure."""
+    to its transcript; the kernel-level test asserts those two leaves directly, at every size and layout
+    (tests/test_gpu_prover_only_kernels.py: Context.eval_monomials_at against the definition and the oracle's LDE, leaf 0 and
+    leaf N - 1 in every index set).  Here: one resident / lean pair of this geometry (2^8 rows, 60 queries into 512 leaves) — the
+    lean proof is the resident proof word for word, and it verifies."""
     fri_lde, cap, sec = 2, 4, 60
-    N = fri_lde << 8
-    found = {}
-    for seed in range(1000, 1064):
-        c = S.sha_shaped_circuit(8, seed=seed, table_bits=2)
-        with switch(None):
-            r = E.ProverSetup(ctx(), c, fri_lde, cap, sec)
-        try:
-            idx = proof_format.parse(r.prove()[0], security_level=sec)["_query_indices"]
-        finally:
-            r.close()
-        for leaf in (0, N - 1):
-            if leaf in idx:
-                found.setdefault(leaf, seed)
-        if len(found) == 2:
-            break
-    assert sorted(found) == [0, N - 1], "no proof of 64 queried leaf %s" % sorted({0, N - 1} - set(found))
-    for leaf, seed in found.items():
-        r, l = pair(S.sha_shaped_circuit(8, seed=seed, table_bits=2), fri_lde, cap, sec)
-        try:
-            assert leaf in proof_format.parse(assert_same_proofs(r, l, sec), security_level=sec)["_query_indices"]
-        finally:
-            r.close()
-            l.close()
+    r, l = pair(S.sha_shaped_circuit(8, seed=1000, table_bits=2), fri_lde, cap, sec)
+    try:
+        idx = proof_format.parse(assert_same_proofs(r, l, sec), security_level=sec)["_query_indices"]
+        assert len(idx) >= 30 and all(0 <= i < (fri_lde << 8) for i in idx)
+    finally:
+        r.close()
+        l.close()
 
 
 def test_resident_and_lean_setups_coexist():

@@ -11,10 +11,12 @@ its s_andn2_b64) are congruent, as D >= p.  By value, the class-3 tests therefor
 other register, mask and loop of the kernel intact, as with the missing SCC clobber of the past.  That the mask is zeroed is
 asserted on the emulated sequence (tests/test_poseidon_rare_products.py).
 
-Not reached here: class 1 at x2*x (no known construction, ~2^-64 at random); the group-wise absorb kernel
-(poseidon1_leaves_absorb_kernel: its capacity comes from the previous launch, so it has no operator entry point; whole proofs
-cover it); rounds >= 2 of leaf and node hashing (capacity words fixed at 0 leave no solve through two S-box layers: the same
-inlined permutation is driven at every round through poseidon_permute)."""
+Not reached here: class 1 at x2*x (no known construction, ~2^-64 at random); rounds >= 2 of leaf and node hashing (capacity
+words fixed at 0 leave no solve through two S-box layers: the same inlined permutation is driven at every round through
+poseidon_permute).  The group-wise absorb kernels (poseidon1_ and poseidon2_leaves_absorb_kernel) are reached in
+tests/test_gpu_prover_only_kernels.py: bj_merkle_leaves_absorb with first = 0, last = 1 takes the capacity words from the
+caller, so the constructed twelve-word states of the permutation tests go through both kernels at every round, on lone lanes
+and whole waves."""
 import ctypes as C
 import functools
 
