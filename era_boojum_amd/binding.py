@@ -118,6 +118,10 @@ class Context:
         """Give the proof workspace (arena, NTT scratch, host-witness staging) back to the device allocator."""
         self._check(self._lib.bj_ctx_release_workspace(self._h))
 
+    def lean_proofs(self, on=True):
+        """Context manager: the proofs started inside it are lean (binding.lean_proofs; a process-wide switch)."""
+        return lean_proofs(self._lib, on)
+
     def malloc(self, nbytes):
         p = C.c_void_p()
         self._check(self._lib.bj_malloc(self._h, nbytes, C.byref(p)))
@@ -1074,6 +1078,25 @@ def _setup_lean_switch(lib, on):
             os.environ.pop("BJ_SETUP_LEAN", None)
         else:
             os.environ["BJ_SETUP_LEAN"] = before
+        lib.bj_env_reload()
+
+
+@contextlib.contextmanager
+def lean_proofs(lib, on=True):
+    """Proofs started inside keep no LDE of their witness and stage-2 oracles (BJ_PROOF_LEAN, include/boojum_hip.h at bj_prove_dev):
+    the same bytes out of a workspace smaller by (nW + nS2) * (L - 1) * n words.  The switch is the process's, not a context's:
+    BJ_PROOF_LEAN is set to "1" (`on` false: to "0") and read by the library for the calls inside, then whatever the environment
+    held before comes back and is read again.  Like bj_env_reload it must not run beside another call into the library."""
+    before = os.environ.get("BJ_PROOF_LEAN")
+    os.environ["BJ_PROOF_LEAN"] = "1" if on else "0"
+    lib.bj_env_reload()
+    try:
+        yield
+    finally:
+        if before is None:
+            os.environ.pop("BJ_PROOF_LEAN", None)
+        else:
+            os.environ["BJ_PROOF_LEAN"] = before
         lib.bj_env_reload()
 
 

@@ -228,6 +228,7 @@ void load_env() {
     e.gates_windowed = str("BJ_GATES_WINDOWED").rfind("0", 0) != 0;
     e.prove_no_absorb = set("BJ_PROVE_NO_ABSORB");
     e.setup_lean = set("BJ_SETUP_LEAN") && str("BJ_SETUP_LEAN").rfind("0", 0) != 0;
+    e.proof_lean = set("BJ_PROOF_LEAN") && str("BJ_PROOF_LEAN").rfind("0", 0) != 0;
     e.prove_uniform_groups = set("BJ_PROVE_UNIFORM_GROUPS");
     e.copy_perm_wide_k = set("BJ_COPY_PERM_WIDE_K");
     if (set("BJ_PROVE_H2D_GROUP")) {

@@ -23,7 +23,8 @@ struct EnvConfig {
     bool gates_windowed = true;         // BJ_GATES_WINDOWED=0: per-gate kernel for the hand-written kinds
     bool prove_no_absorb = false;
     bool setup_lean = false;            // BJ_SETUP_LEAN: a single-device setup created while it is set drops its LDE once the tree stands; sampled per setup
-    bool copy_perm_wide_k = false;       // BJ_COPY_PERM_WIDE_K: quotient_copy_perm with 64-bit non-residue products even when they fit 32 bits (A/B, tests)
+    bool proof_lean = false;            // BJ_PROOF_LEAN: a single-device proof keeps no LDE of its witness and stage-2 oracles: monomials, trees and one coset buffer each; sampled when a proof starts
+    bool copy_perm_wide_k = false;      // BJ_COPY_PERM_WIDE_K: quotient_copy_perm with 64-bit non-residue products even when they fit 32 bits (A/B, tests)
     bool prove_uniform_groups = false;   // BJ_PROVE_UNIFORM_GROUPS: equal groups of G columns, one multi-block absorption run per group (round 4's GROUPING only: its launches absorbed eight columns each)
     bool async_stagger = true;           // BJ_ASYNC_STAGGER=0: bj_prove_async lanes start whenever they are given work (A/B)
     int async_mode = -1;                 // BJ_ASYNC_MODE: what a bj_prove_async lane does while its sibling proves: -1 by witness size (default), 0 bj_prove as is (+ stagger), 1 whole witness first, 2 groups + one hash

@@ -193,6 +193,7 @@ struct Proving {
     bool has_lookup;
     bool count_mult;         // no multiplicity column was supplied: round 1 counts it (count_multiplicities)
     bool absorb;             // host witness: the leaves absorb every column group as it lands (witness_from_host)
+    bool lean_p;             // BJ_PROOF_LEAN on one GPU: wit_lde / s2_lde hold ONE coset ([width][n]), rebuilt from mono / mono_s2 where a round reads another
     unsigned log_n, V, q;
     // N / Ln: leaves / column stride HELD BY THIS GPU (the whole domain on one GPU); Q: points of the quotient domain
     size_t n, N, Q, Ln, I0, capl;
@@ -230,7 +231,8 @@ struct Proving {
         Qe = Q / sh.world;
         VW = L.multiplicity();
         nW = L.widths[bj::ORACLE_WITNESS], nS2 = L.widths[bj::ORACLE_STAGE2];
-        absorb = hw && (S->hasher == BJ_HASHER_POSEIDON2 || S->hasher == BJ_HASHER_POSEIDON) && !bj::env().prove_no_absorb && !hw->no_absorb;
+        lean_p = bj::env().proof_lean && sh.world == 1;
+        absorb = hw && (S->hasher == BJ_HASHER_POSEIDON2 || S->hasher == BJ_HASHER_POSEIDON) && !bj::env().prove_no_absorb && !hw->no_absorb && !lean_p;
     }
     int reserve_workspace();
     int check_public_inputs();
@@ -241,6 +243,7 @@ struct Proving {
     int round2_stage2();
     int round3_quotient();
     int exchange_residues(u64 *Tl);
+    int commit_by_coset(const u64 *d_mono, unsigned nc, u64 *d_coset, u64 *d_tree);
     int round4_openings();
     void list_opened_columns();
     Src lde_src(const bj::Opened &o) const;
@@ -292,6 +295,7 @@ int Proving::reserve_workspace() {
                                                    !hw ? bj::WS_HOST_NONE : absorb ? bj::WS_HOST_ABSORBING : bj::WS_HOST_NOT_ABSORBING, new_pow != 0,
                                                    sched, sched_len, num_queries);
     shape.lean = S->lean;
+    shape.lean_oracles = lean_p;
     plan = bj::workspace_plan(shape);
     if (int rc = bj::arena_reset(ctx, std::max(plan.total(), ctx->arena_learned))) return rc;
     proof->ws_reserved = ctx->arena_elems * 8;
@@ -370,7 +374,7 @@ int Proving::witness_from_host(bool *hashed_in_groups) {
         if (count_mult && c1 == nW && (rc = count_multiplicities())) break;   // the last group: every lookup column has landed
         if (c0 < v1) rc = intt_cols(d_variables + (size_t)c0 * n, mono.p + (size_t)c0 * n, v1 - c0);
         if (!rc && has_lookup && c1 == nW) rc = intt_cols(d_multiplicities, mono.p + (size_t)L.multiplicity() * n, 1);
-        if (!rc) rc = lde_cols(mono.p + (size_t)c0 * n, wit_lde.p + (size_t)c0 * Ln, Ln, c1 - c0, S->log_L, S->c0, S->cl);
+        if (!rc && !lean_p) rc = lde_cols(mono.p + (size_t)c0 * n, wit_lde.p + (size_t)c0 * Ln, Ln, c1 - c0, S->log_L, S->c0, S->cl);
         if (absorb && !rc && plan[g].absorb_from != bj::NO_ABSORB) {
             const unsigned a0 = plan[g].absorb_from;
             bj::launch_tree_leaves_absorb(ctx->hasher, wit_lde.p + (size_t)a0 * Ln, Ln, c1 - a0, N, capacity.p, wit_tree.p, a0 == 0,
@@ -394,9 +398,24 @@ int Proving::count_multiplicities() {
     return bj::setup_lookup_multiplicities(ctx, hw ? "bj_prove" : "bj_prove_dev", S, d_variables, const_cast<u64 *>(d_multiplicities));
 }
 
+// The tree of an oracle that is kept as monomials only (lean_p): every coset under the tree is extended into d_coset [nc][n] and
+// its n leaves hashed before the next one overwrites it, then the node layers once.  Leaf i of the tree is row i of the LDE
+// ([column][coset][n], launch_tree_leaves reads leaf i at base + column * stride + i), so coset c's leaves are the digests
+// [c n, (c + 1) n) of the leaf layer, which is the first layer of d_tree (launch_tree_node_layers): 4 c n words in.
+// The tree covers the N / n cosets of the FRI domain, whatever the quotient's degree.  Leaves d_coset holding the last coset.
+int Proving::commit_by_coset(const u64 *d_mono, unsigned nc, u64 *d_coset, u64 *d_tree) {
+    for (unsigned c = 0; c < (unsigned)(N / n); c++) {
+        if (int rc = lde_cols(d_mono, d_coset, n, nc, S->log_L, c, 1)) return rc;
+        bj::launch_tree_leaves(ctx->hasher, d_coset, n, nullptr, nc, n, d_tree + 4 * (size_t)c * n, st);
+    }
+    bj::launch_tree_node_layers(ctx->hasher, d_tree, N, capl, st);
+    BJ_CHECK_LAUNCH(ctx);
+    return BJ_OK;
+}
+
 // ---------------- round 1: witness LDE + tree (prover.rs:270-353) ----------------
 // Reads d_variables, d_multiplicities (hw: the host witness).  Adds wit_lde, mono, mono_s2 (allocated only), wit_tree, wit_cap;
-// the transcript absorbs wit_cap; proof->stage_ms[7] is the leaf kernel's time.
+// the transcript absorbs wit_cap; proof->stage_ms[7] is the leaf kernel's time (lean_p: of the coset loop, transforms included).
 int Proving::round1_witness() {
     int rc = BJ_OK;
     bool hashed_in_groups = false;               // bj_prove: the witness leaves were absorbed group by group under the transfer
@@ -407,7 +426,7 @@ int Proving::round1_witness() {
     if (!hw) {
         rc = intt_cols(d_variables, mono.p, VW);
         if (!rc && has_lookup) rc = intt_cols(d_multiplicities, mono.p + (size_t)L.multiplicity() * n, 1);
-        if (!rc) rc = lde_cols(mono.p, wit_lde.p, Ln, nW, S->log_L, S->c0, S->cl);
+        if (!rc && !lean_p) rc = lde_cols(mono.p, wit_lde.p, Ln, nW, S->log_L, S->c0, S->cl);
     } else {
         rc = witness_from_host(&hashed_in_groups);
     }
@@ -415,13 +434,19 @@ int Proving::round1_witness() {
     if (!hashed_in_groups && (rc = wit_tree.take(ctx, bj::WS_WIT_TREE))) return rc;
     // witness tree; the leaf kernel (the dominant kernel of a proof) is bracketed by HIP events on the launch stream (with a
     // host witness hashed in groups the bracket spans the groups' transforms too: the roofline figure comes from bj_prove_dev)
-    if (!hashed_in_groups) {
+    if (lean_p) {   // with a host witness: after the last group has landed and been transformed (the stream is in order)
         BJ_HIP(ctx, hipEventRecord(ctx->ev0, st));
-        bj::launch_tree_leaves(ctx->hasher, wit_lde.p, Ln, nullptr, nW, N, wit_tree.p, st);
+        if ((rc = commit_by_coset(mono.p, nW, wit_lde.p, wit_tree.p))) return rc;
         BJ_HIP(ctx, hipEventRecord(ctx->ev1, st));
+    } else {
+        if (!hashed_in_groups) {
+            BJ_HIP(ctx, hipEventRecord(ctx->ev0, st));
+            bj::launch_tree_leaves(ctx->hasher, wit_lde.p, Ln, nullptr, nW, N, wit_tree.p, st);
+            BJ_HIP(ctx, hipEventRecord(ctx->ev1, st));
+        }
+        bj::launch_tree_node_layers(ctx->hasher, wit_tree.p, N, capl, st);
+        BJ_CHECK_LAUNCH(ctx);
     }
-    bj::launch_tree_node_layers(ctx->hasher, wit_tree.p, N, capl, st);
-    BJ_CHECK_LAUNCH(ctx);
     wit_cap.resize(4 * S->cap_size), s2_cap.resize(4 * S->cap_size), q_cap.resize(4 * S->cap_size);
     rc = bj::gather_cap(ctx, sh, wit_tree.p, N, S->cap_size, wit_cap.data());
     if (rc) return rc;
@@ -453,10 +478,10 @@ int Proving::round2_stage2() {
     BJ_CHECK_LAUNCH(ctx);
     if ((rc = s2_lde.take(ctx, bj::WS_S2_LDE))) return rc;
     rc = intt_cols(s2_nat.p, mono_s2.p, nS2);
-    if (!rc) rc = lde_cols(mono_s2.p, s2_lde.p, Ln, nS2, S->log_L, S->c0, S->cl);
+    if (!rc && !lean_p) rc = lde_cols(mono_s2.p, s2_lde.p, Ln, nS2, S->log_L, S->c0, S->cl);
     if (rc) return rc;
     if ((rc = s2_tree.take(ctx, bj::WS_S2_TREE))) return rc;
-    rc = bj_merkle_tree_build(ctx, s2_lde.p, Ln, nS2, N, capl, s2_tree.p);
+    rc = lean_p ? commit_by_coset(mono_s2.p, nS2, s2_lde.p, s2_tree.p) : bj_merkle_tree_build(ctx, s2_lde.p, Ln, nS2, N, capl, s2_tree.p);
     if (!rc) rc = bj::gather_cap(ctx, sh, s2_tree.p, N, S->cap_size, s2_cap.data());
     if (rc) return rc;
     tr.absorb_cap(s2_cap.data(), s2_cap.size());
@@ -508,18 +533,17 @@ int Proving::round3_quotient() {
     u64 *t0 = Tl, *t1 = Tl + Qe;
     const u64 *a_lookup = d_alphas.p, *a_spec = d_alphas.p + 2 * n_lookup_terms, *a_gates = a_spec + 2 * n_spec_terms,
               *a_l1 = a_gates + 2 * n_gate_terms;
-    // Every term kernel on `points` points from local point `first` on, with the setup's columns there given as `setup`.  The
-    // accumulators are per point, so the whole range at once (the setup's LDE is resident) and one coset after the other (a lean
-    // setup) write the same words.
-    auto terms_on = [&](size_t first, size_t points, const bj::Cols setup) {
-        const bj::Cols wit{wit_lde.p + first, Ln}, s2{s2_lde.p + first, Ln};
+    // Every term kernel on `points` points from local point `first` on, with the columns of the three oracles there given as
+    // `wit`, `s2` and `setup`.  The accumulators are per point, so the whole range at once (every LDE is resident) and one coset
+    // after the other (a lean setup, a lean proof) write the same words.
+    auto terms_on = [&](size_t first, size_t points, const bj::Cols wit, const bj::Cols s2, const bj::Cols setup) {
         auto sink = [&](const u64 *d_powers) { return bj::TermSink{d_powers, points, t0 + first, t1 + first}; };
         const bj::TermSink general = sink(a_gates), spec = sink(a_spec);
         bj::launch_circuit_gates(ctx, S, wit, setup.at(L.constant(0)), &general, &spec, st);
         if (has_lookup)
             bj::launch_quotient_lookup(bj::LookupArg{wit.at(L.lookup_var(0, 0)), setup.at(L.table(0)), S->tid_var ? nullptr : setup.at(L.table_id()).p,
                                                      wit.at(L.multiplicity()).p, S->lookup_reps, S->lookup_w, lbeta, lgamma},
-                                       s2.at(L.lookup_a(0)).p, s2.at(L.lookup_b()).p, Ln, sink(a_lookup), st);
+                                       s2.at(L.lookup_a(0)).p, s2.at(L.lookup_b()).p, s2.stride, sink(a_lookup), st);
         // variables + sigmas + z and the partial products + 1/(x - 1), accumulators read and written
         const int pc = bj::probe_begin(ctx, "quotient_copy_perm", 8.0 * (2.0 * V + 2 * (1 + L.n_partials) + 1) * (double)points + 32.0 * (double)points);
         const u64 *h_alpha_l1 = alphas.data() + (a_l1 - d_alphas.p);   // the same power on the host: it goes into the kernel's arguments
@@ -527,18 +551,26 @@ int Proving::round3_quotient() {
                                       s2, S->log_L, h_alpha_l1, sink(a_l1 + 2), I0 + first, S->d_inv_xm1 + first, st);
         bj::probe_end(ctx, pc);
     };
-    if (S->lean) {
-        // The setup kept no LDE: its columns are extended from the monomials one coset at a time into [width][n] words, and the
-        // terms of that coset's n points are taken before the next one overwrites them.  Highest coset first, so that coset 0 is
-        // what stays in the buffer: round 4 evaluates the setup's polynomials at z from it.  q == 0 cannot happen (a power of two).
-        if ((rc = setup_coset.take(ctx, bj::WS_SETUP_COSET))) return rc;
+    if (S->lean || lean_p) {
+        // An oracle that kept no LDE (the setup's, S->lean; the proof's own two, lean_p): its columns are extended from the monomials
+        // one coset at a time into [width][n] words, and the terms of that coset's n points are taken before the next one
+        // overwrites them; a resident one is read at that coset.  Highest coset first, so that coset 0 is what stays in the
+        // buffers: round 4 evaluates the polynomials at z from it.  q == 0 cannot happen (a power of two).  The quotient reads
+        // q cosets, the trees of rounds 1 and 2 covered fri_lde: neither bounds the other.
+        if (S->lean && (rc = setup_coset.take(ctx, bj::WS_SETUP_COSET))) return rc;
         for (unsigned c = q; c-- > 0 && !rc;) {
-            rc = lde_cols(S->d_mono, setup_coset.p, n, L.widths[bj::ORACLE_SETUP], S->log_L, c, 1);
-            if (!rc) terms_on((size_t)c * n, n, bj::Cols{setup_coset.p, n});
+            const size_t first = (size_t)c * n;
+            if (S->lean) rc = lde_cols(S->d_mono, setup_coset.p, n, L.widths[bj::ORACLE_SETUP], S->log_L, c, 1);
+            if (!rc && lean_p) rc = lde_cols(mono.p, wit_lde.p, n, nW, S->log_L, c, 1);
+            if (!rc && lean_p) rc = lde_cols(mono_s2.p, s2_lde.p, n, nS2, S->log_L, c, 1);
+            if (!rc)
+                terms_on(first, n, lean_p ? bj::Cols{wit_lde.p, n} : bj::Cols{wit_lde.p + first, Ln},
+                         lean_p ? bj::Cols{s2_lde.p, n} : bj::Cols{s2_lde.p + first, Ln},
+                         S->lean ? bj::Cols{setup_coset.p, n} : bj::Cols{S->d_lde + first, Ln});
         }
         if (rc) return rc;
     } else if (Qe) {
-        terms_on(0, Qe, bj::Cols{S->d_lde, Ln});
+        terms_on(0, Qe, bj::Cols{wit_lde.p, Ln}, bj::Cols{s2_lde.p, Ln}, bj::Cols{S->d_lde, Ln});
     }
     BJ_CHECK_LAUNCH(ctx);
     // flatten (= bit-reversal of the evaluations), iNTT on their coset (prover.rs:1386-1422)
@@ -578,10 +610,12 @@ int Proving::round3_quotient() {
 // An opened polynomial of the layout as its columns in the LDE arrays / in the monomial arrays (chunk j of the quotient:
 // coefficients [j*n, (j+1)*n) of T's two monomial forms, which lie Q apart instead of side by side).
 Src Proving::lde_src(const bj::Opened &o) const {
-    // a lean setup's columns exist on coset 0 only (setup_coset, stride n): enough for the evaluations of round 4, which read the
-    // first coset; DEEP never takes them from here (deep_set combines that set on the monomials)
+    // a lean setup's columns exist on coset 0 only (setup_coset, stride n), and so do a lean proof's witness and stage-2 columns
+    // (wit_lde, s2_lde, stride n): enough for the evaluations of round 4, which read the first coset; DEEP never takes them from
+    // here (deep_set combines those sets on the monomials)
     const u64 *bases[4] = {wit_lde.p, s2_lde.p, q_lde.p, S->lean ? setup_coset.p : S->d_lde};
-    const size_t strides[4] = {Ln, Ln, N, S->lean ? n : Ln};
+    const size_t os = lean_p ? n : Ln;
+    const size_t strides[4] = {os, os, N, S->lean ? n : Ln};
     const u64 *b = bases[o.oracle];
     return {b + o.col0 * strides[o.oracle], o.col1 == bj::NO_COLUMN ? nullptr : b + o.col1 * strides[o.oracle]};
 }
@@ -696,7 +730,8 @@ int Proving::flush_deep(DeepSets &D) {
 
 // One opening set: the polynomials ls (on the LDE) = ms (monomials) with the values vals at the point at.  Takes the next
 // ms.size() challenges; a large set gets its extended numerator (an arena buffer of 2 N words); queues the set for flush_deep.
-// on_monomials: the set goes that way whatever its size (its columns are on no FRI domain: the set at z under a lean setup).
+// on_monomials: the set goes that way whatever its size (its columns are on no FRI domain: the set at z under a lean setup, every
+// set of a lean proof).
 int Proving::deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector<Src> &ms, const u64 *vals, const u64 *at, bool on_monomials) {
     const u64 *ch = D.chs.data() + 2 * D.choff;
     D.choff += ms.size();
@@ -749,9 +784,10 @@ int Proving::round5a_deep() {
     if (sh.world > 1 && (rc = D.num_slice.take(ctx, bj::WS_NUM_SLICE))) return rc;
     const u64 zero2[2] = {0, 0};
     for (auto &set : sets) {   // in the order the challenges are handed out
-        if (set.point == bj::OPEN_AT_Z) rc = deep_set(D, srcs, msrcs, vz.data(), z, S->lean);
-        else if (set.point == bj::OPEN_AT_Z_OMEGA) rc = deep_set(D, zsrc, mz, vzo.data(), zo);
-        else if (set.point == bj::OPEN_AT_ZERO) rc = deep_set(D, lsrc, ml, v0.data(), zero2);
+        // lean_p: every set holds a witness or a stage-2 column (z(x), the lookup sums, a public input's variable), none of which is on the FRI domain
+        if (set.point == bj::OPEN_AT_Z) rc = deep_set(D, srcs, msrcs, vz.data(), z, S->lean || lean_p);
+        else if (set.point == bj::OPEN_AT_Z_OMEGA) rc = deep_set(D, zsrc, mz, vzo.data(), zo, lean_p);
+        else if (set.point == bj::OPEN_AT_ZERO) rc = deep_set(D, lsrc, ml, v0.data(), zero2, lean_p);
         else {
             std::vector<Src> ps, pl;
             std::vector<u64> pv;
@@ -762,7 +798,7 @@ int Proving::round5a_deep() {
                 pv.push_back(0);
             }
             const u64 at2[2] = {gl::pow(gl::omega(log_n), set.row), 0};
-            rc = deep_set(D, pl, ps, pv.data(), at2);
+            rc = deep_set(D, pl, ps, pv.data(), at2, lean_p);
         }
         if (rc) return rc;
     }
@@ -817,7 +853,8 @@ int Proving::gather_base_queries(Queries &qr) {
     const unsigned W = sh.world, depth = qr.depth;
     // a leaf lives on rank index / N; every rank gathers at (index mod N) and the owner's answer is kept
     const unsigned *widths = L.widths;
-    const u64 *bases[4] = {wit_lde.p, s2_lde.p, q_lde.p, S->d_lde};   // the last is null under a lean setup: evaluated below
+    const u64 *bases[4] = {wit_lde.p, s2_lde.p, q_lde.p, S->d_lde};   // the last is null under a lean setup, the first two hold one coset in a lean proof: evaluated below
+    const u64 *monos[4] = {lean_p ? mono.p : nullptr, lean_p ? mono_s2.p : nullptr, nullptr, S->lean ? S->d_mono : nullptr};   // all three in the layout intt_cols writes
     const size_t strides[4] = {Ln, Ln, N, Ln};
     const u64 *trees[4] = {wit_tree.p, s2_tree.p, q_tree.p, S->d_tree};
     int rc = BJ_OK;
@@ -835,8 +872,8 @@ int Proving::gather_base_queries(Queries &qr) {
     qr.gathered.resize(G * W);
     size_t off = 0;
     for (int o = 0; o < 4; o++) {
-        if ((unsigned)o == bj::ORACLE_SETUP && S->lean)   // the leaf's words are the setup polynomials at the leaf's point; the paths come from the kept tree
-            bj::launch_eval_monomials_at(S->d_mono, n, widths[o], log_n, S->tiled, ctx->tw_fwd, I0, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
+        if (monos[o])   // the leaf's words are the oracle's polynomials at the leaf's point; the paths come from the kept tree
+            bj::launch_eval_monomials_at(monos[o], n, widths[o], log_n, S->tiled, ctx->tw_fwd, I0, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
         else
             bj::launch_gather_rows(bases[o], strides[o], widths[o], d_idx.p, (unsigned)num_queries, d_g.p + off, st);
         off += (size_t)widths[o] * num_queries;

@@ -55,6 +55,7 @@ struct WorkspaceShape {
     unsigned world = 1;
     bool tiled = false;
     bool lean = false;                       // the setup keeps no LDE (bj_setup::lean): set by the prover, single device only
+    bool lean_oracles = false;               // the proof keeps no LDE of its witness and stage-2 oracles (BJ_PROOF_LEAN): one coset buffer each; set by the prover, world == 1 only
     size_t tree_words = 0;                   // bj_merkle_tree_digests(N, cap_size / world) * 4
     unsigned depth = 0;                      // path length of the base oracles: log2(N * world / cap_size)
     unsigned opened_cols = 0;                // base columns of the polynomials opened at z (an F_p^2 polynomial counts two)
@@ -129,15 +130,16 @@ inline WorkspacePlan workspace_plan(const WorkspaceShape &s) {
     };
     // round 1: witness
     if (s.mult_in_arena) P.take(WS_MULTIPLICITY, s.n);
-    P.take(WS_WIT_LDE, (size_t)s.nW * s.Ln);
+    const size_t oracle_stride = s.lean_oracles ? s.n : s.Ln;   // lean oracles: one coset of each at a time, rebuilt from the monomials
+    P.take(WS_WIT_LDE, (size_t)s.nW * oracle_stride);
     P.take(WS_MONO, (size_t)s.nW * s.n);
     P.take(WS_MONO_S2, (size_t)s.nS2 * s.n);
     P.take(WS_WIT_TREE, s.tree_words);
-    if (s.host_witness == WS_HOST_ABSORBING) P.take(WS_CAPACITY, 4 * s.N);
+    if (s.host_witness == WS_HOST_ABSORBING && !s.lean_oracles) P.take(WS_CAPACITY, 4 * s.N);   // lean oracles hash coset by coset, never group by group
     // round 2: stage 2
     P.take(WS_S2_NAT, (size_t)s.nS2 * s.n);
     P.take(WS_S2_SCRATCH, copy_perm_stage2_scratch_words(s.n_chunks, s.n));
-    P.take(WS_S2_LDE, (size_t)s.nS2 * s.Ln);
+    P.take(WS_S2_LDE, (size_t)s.nS2 * oracle_stride);
     P.take(WS_S2_TREE, s.tree_words);
     // round 3: quotient
     P.take(WS_ALPHAS, 2 * (size_t)s.alpha_terms);
@@ -163,8 +165,10 @@ inline WorkspacePlan workspace_plan(const WorkspaceShape &s) {
     if (s.has_lookup) sets.push_back(2 * (size_t)s.lookup_terms);
     sets.insert(sets.end(), s.pub_set_cols.begin(), s.pub_set_cols.end());
     for (size_t &cols : sets) {
-        // a lean setup has its columns on no FRI domain: the set opened at z, which holds them, always goes through its monomials
-        if (cols < WS_LARGE_SET && !(s.lean && &cols == &sets[0])) continue;
+        // a lean setup has its columns on no FRI domain: the set opened at z, which holds them, always goes through its monomials.
+        // Lean oracles: every set holds a witness or a stage-2 column (z and the lookup sums are stage 2, a public input is a
+        // variable), so every set does
+        if (cols < WS_LARGE_SET && !(s.lean && &cols == &sets[0]) && !s.lean_oracles) continue;
         P.take(WS_NUM_LDE, 2 * s.N);
         P.allow(WS_ARGS_COMBINE, column_list_arg_words(cols));
         if (sharded && s.n % W == 0 && s.n / W >= 256) P.allow(WS_GATHER_STAGING, gather_columns_staging_words(W, 2, s.n / W));

@@ -766,7 +766,19 @@ int bj_prove_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_
  * bj_setup_lookup_multiplicities below, once the lookup columns are resident and before the witness is committed — it replaces
  * the host-side count — and a tuple that is in no table row refuses the proof with that call's message),
  * public input values in location order.  Proof out (bj_proof_serialize).  Returns BJ_ERR_INVALID_ARG with
- * "constraint system is not satisfied" where the reference panics "unsatisfied" (prover.rs:1425-1438). */
+ * "constraint system is not satisfied" where the reference panics "unsatisfied" (prover.rs:1425-1438).
+ * Lean proofs: with BJ_PROOF_LEAN set in the environment (any value that does not start with '0'; read with the other switches,
+ * re-read by bj_env_reload) when a proof STARTS (a bj_prove_async lane: when the lane takes the proof up), that proof keeps no LDE
+ * of the two oracles it builds itself.  Kept: the monomials of the witness and stage-2 columns, both trees, and one coset buffer
+ * per oracle ([width][n] words in place of [width][L n], L = max(fri_lde_factor, quotient_degree)).  Rebuilt from the monomials:
+ * every coset under the trees, once, hashed before the next one overwrites it; every coset the quotient reads, once more, highest
+ * first, so that coset 0 is left for the evaluations at z; every opening set is combined on its monomials; the witness and stage-2
+ * words of the queried leaves are the polynomials evaluated at the leaves' points.  The proof bytes are identical.  The
+ * workspace (bj_proof_workspace_bytes) is smaller by (nW + nS2) (L - 1) n words less one extended numerator (2 N words) per
+ * small opening set; cost in time: DESIGN.md §5.  bj_prove hashes after the last column group has landed instead of group by
+ * group under the transfer.  A context that goes from lean to resident proofs grows its arena as for any larger proof; one that
+ * goes the other way keeps it until bj_ctx_release_workspace.  Single device only: a proof on a sharded setup ignores the
+ * switch, as bj_setup_create_sharded ignores BJ_SETUP_LEAN.  Lean setups and lean proofs combine freely. */
 int bj_prove(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_variables, const uint64_t *h_multiplicities,
              const uint64_t *h_public_values, bj_proof **out);
 /* same with the witness already resident in HBM ([num_vars + num_witness_cols][n] contiguous; not modified) */
@@ -983,7 +995,8 @@ size_t bj_proof_size_u64(const bj_proof *p);
 int bj_proof_serialize(const bj_proof *p, uint64_t *out);
 /* wall-clock per stage in ms, named after the reference's log lines: [0] witness LDE + tree, [1] second stage,
  * [2] quotient work and LDE + tree, [3] openings at z, [4] batched FRI opening computation (DEEP), [5] FRI, [6] queries;
- * [7] = duration of the witness-tree Poseidon2 leaf kernel alone, measured with HIP events on the launch stream */
+ * [7] = duration of the witness-tree Poseidon2 leaf kernel alone, measured with HIP events on the launch stream (a lean proof,
+ * BJ_PROOF_LEAN: of the loop over the cosets, so the leaf kernels AND the per-coset transforms between them) */
 int bj_proof_stage_ms(const bj_proof *p, float *out8);
 /* Per-kernel measurements of the proof (measurement only; SURVEY §8d "each evidenced by ... HBM GB/s against the roofline"): the
  * FIRST launch inside this proof of each probed kernel — "quotient_gates" (prover.rs:1031-1080), "quotient_copy_perm"

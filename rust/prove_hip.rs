@@ -46,6 +46,13 @@ pub struct HipCtx {
 }
 unsafe impl Send for HipCtx {}
 
+/// Lean proofs (BJ_PROOF_LEAN, boojum_hip.h at `bj_prove`) for every proof started from now on, process-wide: the same bytes out of
+/// a workspace without the witness and stage-2 LDEs.  Must not run beside any other call into the library (`bj_env_reload`).
+pub fn set_lean_proofs(on: bool) {
+    std::env::set_var("BJ_PROOF_LEAN", if on { "1" } else { "0" });
+    unsafe { bj_env_reload() };
+}
+
 impl HipCtx {
     pub fn new(device: i32) -> Result<Self, String> {
         // struct layouts (bj_gate_desc, bj_comm, ...) are those of the header these bindings were generated from
