@@ -193,7 +193,6 @@ struct Proving {
     bool has_lookup;
     bool count_mult;         // no multiplicity column was supplied: round 1 counts it (count_multiplicities)
     bool absorb;             // host witness: the leaves absorb every column group as it lands (witness_from_host)
-    bool lean_p;             // BJ_PROOF_LEAN on one GPU: wit_lde / s2_lde hold ONE coset ([width][n]), rebuilt from mono / mono_s2 where a round reads another
     unsigned log_n, V, q;
     // N / Ln: leaves / column stride HELD BY THIS GPU (the whole domain on one GPU); Q: points of the quotient domain
     size_t n, N, Q, Ln, I0, capl;
@@ -207,14 +206,13 @@ struct Proving {
     bj::host::Transcript tr;
     u64 beta[2], gamma[2], lbeta[2] = {0, 0}, lgamma[2] = {0, 0}, z[2], zo[2];   // challenges of rounds 2 and 4 (zo = z * omega)
     bj::WorkspacePlan plan;
+    // The four committed oracles (oracle_value.h) by ORACLE_*: width, stride and residency from the constructor, the pointers as the
+    // rounds take the buffers below.  The setup's is S's own; a lean one gets setup_coset for its evaluations in round 3.  After
+    // round 3 the coset buffer of a lean oracle holds coset 0, which round 4 evaluates from.
+    bj::Oracle oracle[4];
     bj::TmpBuf wit_lde, wit_tree, mono, mono_s2;   // mono: witness monomials, mono_s2: stage-2 monomials (both kept for DEEP)
-    bj::TmpBuf s2_lde, s2_tree, T, q_lde, q_tree, deep;
-    bj::TmpBuf setup_coset;    // lean setup: [setup width][n], one coset of its columns rebuilt from S->d_mono; after round 3 it holds coset 0
-    const u64 *Tm = nullptr;   // the 2 q chunks of n coefficients each of the quotient, in the monomial layout of this trace length
+    bj::TmpBuf s2_lde, s2_tree, T, q_lde, q_tree, deep, setup_coset;
     std::vector<u64> wit_cap, s2_cap, q_cap;
-    // base columns whose coset 0 is evaluated, in the order of prover.rs:1550-1683; msrcs: the monomial forms of the same
-    // polynomials, same order (for the DEEP numerator).  zsrc / mz: z(x), opened at z * omega; lsrc / ml: the lookup sums, at 0
-    std::vector<Src> srcs, msrcs, zsrc, mz, lsrc, ml;
     std::vector<u64> vz, vzo, v0;   // the opened values
     uint32_t sched[32];             // FRI folding schedule (bj_fri_schedule, before the workspace is reserved)
     uint32_t new_pow = 0;           // proof-of-work bits left once the query count is rounded
@@ -231,26 +229,31 @@ struct Proving {
         Qe = Q / sh.world;
         VW = L.multiplicity();
         nW = L.widths[bj::ORACLE_WITNESS], nS2 = L.widths[bj::ORACLE_STAGE2];
-        lean_p = bj::env().proof_lean && sh.world == 1;
-        absorb = hw && (S->hasher == BJ_HASHER_POSEIDON2 || S->hasher == BJ_HASHER_POSEIDON) && !bj::env().prove_no_absorb && !hw->no_absorb && !lean_p;
+        const bool lean_p = bj::env().proof_lean && sh.world == 1;   // BJ_PROOF_LEAN: the witness and stage-2 oracles keep no evaluations
+        oracle[bj::ORACLE_WITNESS] = bj::oracle_of(nW, n, Ln, !lean_p);
+        oracle[bj::ORACLE_STAGE2] = bj::oracle_of(nS2, n, Ln, !lean_p);
+        oracle[bj::ORACLE_QUOTIENT] = bj::oracle_of(2 * q, n, N, true);   // always resident, on the FRI domain; its monomials: T's chunk layout
+        oracle[bj::ORACLE_QUOTIENT].mono_parts = 2, oracle[bj::ORACLE_QUOTIENT].mono_part_gap = Q;
+        oracle[bj::ORACLE_SETUP] = S->oracle();
+        absorb = hw && (S->hasher == BJ_HASHER_POSEIDON2 || S->hasher == BJ_HASHER_POSEIDON) && !bj::env().prove_no_absorb && !hw->no_absorb &&
+                 oracle[bj::ORACLE_WITNESS].resident;
     }
     int reserve_workspace();
     int check_public_inputs();
     int open_transcript();
     int count_multiplicities();
     int round1_witness();
-    int witness_from_host(bool *hashed_in_groups);
+    int witness_from_host();
     int round2_stage2();
     int round3_quotient();
     int exchange_residues(u64 *Tl);
-    int commit_by_coset(const u64 *d_mono, unsigned nc, u64 *d_coset, u64 *d_tree);
+    enum Brought { MONOMIALS, EXTENDED, LEAVES_HASHED };   // how far its round has brought a resident oracle when it is committed
+    int commit(const bj::Oracle &o, std::vector<u64> &cap, Brought have, float *leaf_ms = nullptr);
     int round4_openings();
-    void list_opened_columns();
-    Src lde_src(const bj::Opened &o) const;
-    Src mono_src(const bj::Opened &o) const;
+    std::vector<Src> sources(const std::vector<bj::Opened> &polys, bool on_evals) const;
     int evaluate_at(u64 *w, u64 open_shift, const std::vector<Src> &ss, const u64 *at, std::vector<u64> &vals);
     int round5a_deep();
-    int deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector<Src> &ms, const u64 *vals, const u64 *at, bool on_monomials = false);
+    int deep_set(DeepSets &D, const std::vector<bj::Opened> &polys, const u64 *vals, const u64 *at);
     int flush_deep(DeepSets &D);
     int round5b_fri();
     int round6_queries(Queries &qr);
@@ -270,6 +273,8 @@ struct Proving {
     int lde_cols(const u64 *d_m, u64 *d_out, size_t out_stride, unsigned nc, unsigned log_lde, unsigned cb, unsigned cc) const {
         return bj::lde_cosets_strided(ctx, d_m, n, d_out, out_stride, log_n, nc, log_lde, cb, cc, S->tiled);
     }
+    // a lean oracle's coset buffer is made to hold coset c; a resident oracle has every coset
+    int rebuild(const bj::Oracle &o, unsigned c) const { return o.resident ? BJ_OK : lde_cols(o.mono, o.evals, o.stride, o.width, S->log_L, c, 1); }
 };
 
 // 1, x, x^2, ... as F_p^2 pairs (materialize_powers_serial, utils.rs:31; materialize_ext_challenge_powers, prover.rs:2374-2395)
@@ -294,8 +299,8 @@ int Proving::reserve_workspace() {
                                                    count_mult && !d_multiplicities,
                                                    !hw ? bj::WS_HOST_NONE : absorb ? bj::WS_HOST_ABSORBING : bj::WS_HOST_NOT_ABSORBING, new_pow != 0,
                                                    sched, sched_len, num_queries);
-    shape.lean = S->lean;
-    shape.lean_oracles = lean_p;
+    shape.lean = !oracle[bj::ORACLE_SETUP].resident;
+    shape.lean_oracles = !oracle[bj::ORACLE_WITNESS].resident;
     plan = bj::workspace_plan(shape);
     if (int rc = bj::arena_reset(ctx, std::max(plan.total(), ctx->arena_learned))) return rc;
     proof->ws_reserved = ctx->arena_elems * 8;
@@ -332,10 +337,11 @@ int Proving::open_transcript() {
 }
 
 // Round 1 with the witness in host memory (hw): queues the copies of every column group on the copy stream, then transforms
-// the groups on the proof stream as they land.  Reads mono, wit_lde (allocated); fills them.  With an algebraic tree hasher the
-// leaves are absorbed group by group as well: then wit_tree is allocated and its leaf layer written here (*hashed_in_groups).
-int Proving::witness_from_host(bool *hashed_in_groups) {
+// the groups on the proof stream as they land.  Reads mono, wit_lde, wit_tree (allocated); fills mono and, the oracle resident,
+// wit_lde.  absorb: the leaves are absorbed group by group as well, and the leaf layer of wit_tree is written here.
+int Proving::witness_from_host() {
     int rc = BJ_OK;
+    const bj::Oracle &wit = oracle[bj::ORACLE_WITNESS];
     // all copies are queued on the copy stream at once (they run back to back at PCIe speed); the proof stream picks the
     // groups up as they land.  Column nW - 1 is the multiplicity column when there are lookups.
     if (!ctx->copy_stream) BJ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
@@ -349,11 +355,7 @@ int Proving::witness_from_host(bool *hashed_in_groups) {
     const std::vector<bj::WitnessGroup> plan = bj::host_witness_plan(nW, G, absorb, bj::env().prove_uniform_groups);
     const unsigned n_groups = (unsigned)plan.size();
     bj::TmpBuf capacity;
-    if (absorb) {
-        if ((rc = wit_tree.take(ctx, bj::WS_WIT_TREE))) return rc;
-        if ((rc = capacity.take(ctx, bj::WS_CAPACITY))) return rc;
-        *hashed_in_groups = true;
-    }
+    if (absorb && (rc = capacity.take(ctx, bj::WS_CAPACITY))) return rc;
     for (unsigned g = 0; g < n_groups; g++) {
         if (!ctx->copy_ev[g]) BJ_HIP(ctx, hipEventCreateWithFlags(&ctx->copy_ev[g], hipEventDisableTiming));
         const unsigned c0 = plan[g].c0, c1 = plan[g].c1;
@@ -374,7 +376,7 @@ int Proving::witness_from_host(bool *hashed_in_groups) {
         if (count_mult && c1 == nW && (rc = count_multiplicities())) break;   // the last group: every lookup column has landed
         if (c0 < v1) rc = intt_cols(d_variables + (size_t)c0 * n, mono.p + (size_t)c0 * n, v1 - c0);
         if (!rc && has_lookup && c1 == nW) rc = intt_cols(d_multiplicities, mono.p + (size_t)L.multiplicity() * n, 1);
-        if (!rc && !lean_p) rc = lde_cols(mono.p + (size_t)c0 * n, wit_lde.p + (size_t)c0 * Ln, Ln, c1 - c0, S->log_L, S->c0, S->cl);
+        if (!rc && wit.resident) rc = lde_cols(mono.p + (size_t)c0 * n, wit_lde.p + (size_t)c0 * Ln, Ln, c1 - c0, S->log_L, S->c0, S->cl);
         if (absorb && !rc && plan[g].absorb_from != bj::NO_ABSORB) {
             const unsigned a0 = plan[g].absorb_from;
             bj::launch_tree_leaves_absorb(ctx->hasher, wit_lde.p + (size_t)a0 * Ln, Ln, c1 - a0, N, capacity.p, wit_tree.p, a0 == 0,
@@ -398,61 +400,60 @@ int Proving::count_multiplicities() {
     return bj::setup_lookup_multiplicities(ctx, hw ? "bj_prove" : "bj_prove_dev", S, d_variables, const_cast<u64 *>(d_multiplicities));
 }
 
-// The tree of an oracle that is kept as monomials only (lean_p): every coset under the tree is extended into d_coset [nc][n] and
-// its n leaves hashed before the next one overwrites it, then the node layers once.  Leaf i of the tree is row i of the LDE
-// ([column][coset][n], launch_tree_leaves reads leaf i at base + column * stride + i), so coset c's leaves are the digests
-// [c n, (c + 1) n) of the leaf layer, which is the first layer of d_tree (launch_tree_node_layers): 4 c n words in.
-// The tree covers the N / n cosets of the FRI domain, whatever the quotient's degree.  Leaves d_coset holding the last coset.
-int Proving::commit_by_coset(const u64 *d_mono, unsigned nc, u64 *d_coset, u64 *d_tree) {
-    for (unsigned c = 0; c < (unsigned)(N / n); c++) {
-        if (int rc = lde_cols(d_mono, d_coset, n, nc, S->log_L, c, 1)) return rc;
-        bj::launch_tree_leaves(ctx->hasher, d_coset, n, nullptr, nc, n, d_tree + 4 * (size_t)c * n, st);
+// Commits to an oracle whose monomials stand: the leaves of its tree over this rank's N points of the FRI domain, the node layers,
+// the cap into `cap` and into the transcript.  A resident oracle is extended first (have == MONOMIALS; a round that extends in its
+// own way, or has hashed the leaves as well, says so) and its leaves are hashed in one launch.  A lean one is extended one coset
+// at a time into its [width][n] buffer, the n leaves of the coset hashed before the next one overwrites it: leaf i of the tree is
+// row i of the LDE ([column][coset][n]), so coset c's leaves are the digests [c n, (c + 1) n) of the leaf layer, which is the first
+// layer of the tree, 4 c n words in.  The buffer is left holding the last coset.
+// leaf_ms: the leaf work is bracketed by HIP events on the launch stream and its time stored there: the leaf kernel alone
+// (resident), the coset loop with its transforms and the node layers (lean), what the caller bracketed itself (LEAVES_HASHED).
+int Proving::commit(const bj::Oracle &o, std::vector<u64> &cap, Brought have, float *leaf_ms) {
+    const bool timed = leaf_ms && have != LEAVES_HASHED;
+    if (o.resident) {
+        if (have == MONOMIALS)
+            if (int rc = lde_cols(o.mono, o.evals, o.stride, o.width, S->log_L, S->c0, S->cl)) return rc;
+        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->ev0, st));
+        if (have != LEAVES_HASHED) bj::launch_tree_leaves(ctx->hasher, o.evals, o.stride, nullptr, o.width, N, o.tree, st);
+        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->ev1, st));
+    } else {
+        if (timed) BJ_HIP(ctx, hipEventRecord(ctx->ev0, st));
+        for (unsigned c = 0; c < (unsigned)(N / n); c++) {
+            if (int rc = rebuild(o, c)) return rc;
+            bj::launch_tree_leaves(ctx->hasher, o.evals, o.stride, nullptr, o.width, n, o.tree + 4 * (size_t)c * n, st);
+        }
     }
-    bj::launch_tree_node_layers(ctx->hasher, d_tree, N, capl, st);
+    bj::launch_tree_node_layers(ctx->hasher, o.tree, N, capl, st);
     BJ_CHECK_LAUNCH(ctx);
+    if (timed && !o.resident) BJ_HIP(ctx, hipEventRecord(ctx->ev1, st));
+    cap.resize(4 * S->cap_size);
+    if (int rc = bj::gather_cap(ctx, sh, o.tree, N, S->cap_size, cap.data())) return rc;
+    if (leaf_ms) BJ_HIP(ctx, hipEventElapsedTime(leaf_ms, ctx->ev0, ctx->ev1));
+    tr.absorb_cap(cap.data(), cap.size());
     return BJ_OK;
 }
 
 // ---------------- round 1: witness LDE + tree (prover.rs:270-353) ----------------
 // Reads d_variables, d_multiplicities (hw: the host witness).  Adds wit_lde, mono, mono_s2 (allocated only), wit_tree, wit_cap;
-// the transcript absorbs wit_cap; proof->stage_ms[7] is the leaf kernel's time (lean_p: of the coset loop, transforms included).
+// the transcript absorbs wit_cap; proof->stage_ms[7] is the time of the leaf work (commit; with a host witness hashed in groups
+// the bracket spans the groups' transforms too: the roofline figure comes from bj_prove_dev).
 int Proving::round1_witness() {
     int rc = BJ_OK;
-    bool hashed_in_groups = false;               // bj_prove: the witness leaves were absorbed group by group under the transfer
+    bj::Oracle &wit = oracle[bj::ORACLE_WITNESS];
     if (count_mult && !hw && (rc = count_multiplicities())) return rc;   // before any proof work
     if ((rc = wit_lde.take(ctx, bj::WS_WIT_LDE))) return rc;
     if ((rc = mono.take(ctx, bj::WS_MONO))) return rc;
     if ((rc = mono_s2.take(ctx, bj::WS_MONO_S2))) return rc;
+    if ((rc = wit_tree.take(ctx, bj::WS_WIT_TREE))) return rc;
+    wit.mono = mono.p, wit.evals = wit_lde.p, wit.tree = wit_tree.p;
     if (!hw) {
         rc = intt_cols(d_variables, mono.p, VW);
         if (!rc && has_lookup) rc = intt_cols(d_multiplicities, mono.p + (size_t)L.multiplicity() * n, 1);
-        if (!rc && !lean_p) rc = lde_cols(mono.p, wit_lde.p, Ln, nW, S->log_L, S->c0, S->cl);
     } else {
-        rc = witness_from_host(&hashed_in_groups);
+        rc = witness_from_host();   // a resident oracle is extended there, group by group (a lean one: after the last group has landed)
     }
     if (rc) return rc;
-    if (!hashed_in_groups && (rc = wit_tree.take(ctx, bj::WS_WIT_TREE))) return rc;
-    // witness tree; the leaf kernel (the dominant kernel of a proof) is bracketed by HIP events on the launch stream (with a
-    // host witness hashed in groups the bracket spans the groups' transforms too: the roofline figure comes from bj_prove_dev)
-    if (lean_p) {   // with a host witness: after the last group has landed and been transformed (the stream is in order)
-        BJ_HIP(ctx, hipEventRecord(ctx->ev0, st));
-        if ((rc = commit_by_coset(mono.p, nW, wit_lde.p, wit_tree.p))) return rc;
-        BJ_HIP(ctx, hipEventRecord(ctx->ev1, st));
-    } else {
-        if (!hashed_in_groups) {
-            BJ_HIP(ctx, hipEventRecord(ctx->ev0, st));
-            bj::launch_tree_leaves(ctx->hasher, wit_lde.p, Ln, nullptr, nW, N, wit_tree.p, st);
-            BJ_HIP(ctx, hipEventRecord(ctx->ev1, st));
-        }
-        bj::launch_tree_node_layers(ctx->hasher, wit_tree.p, N, capl, st);
-        BJ_CHECK_LAUNCH(ctx);
-    }
-    wit_cap.resize(4 * S->cap_size), s2_cap.resize(4 * S->cap_size), q_cap.resize(4 * S->cap_size);
-    rc = bj::gather_cap(ctx, sh, wit_tree.p, N, S->cap_size, wit_cap.data());
-    if (rc) return rc;
-    BJ_HIP(ctx, hipEventElapsedTime(&proof->stage_ms[7], ctx->ev0, ctx->ev1));
-    tr.absorb_cap(wit_cap.data(), wit_cap.size());
-    return BJ_OK;
+    return commit(wit, wit_cap, !hw ? MONOMIALS : absorb ? LEAVES_HASHED : EXTENDED, &proof->stage_ms[7]);
 }
 
 // ---------------- round 2: copy-permutation + lookup polys (prover.rs:360-554) ----------------
@@ -477,15 +478,11 @@ int Proving::round2_stage2() {
     }
     BJ_CHECK_LAUNCH(ctx);
     if ((rc = s2_lde.take(ctx, bj::WS_S2_LDE))) return rc;
-    rc = intt_cols(s2_nat.p, mono_s2.p, nS2);
-    if (!rc && !lean_p) rc = lde_cols(mono_s2.p, s2_lde.p, Ln, nS2, S->log_L, S->c0, S->cl);
-    if (rc) return rc;
     if ((rc = s2_tree.take(ctx, bj::WS_S2_TREE))) return rc;
-    rc = lean_p ? commit_by_coset(mono_s2.p, nS2, s2_lde.p, s2_tree.p) : bj_merkle_tree_build(ctx, s2_lde.p, Ln, nS2, N, capl, s2_tree.p);
-    if (!rc) rc = bj::gather_cap(ctx, sh, s2_tree.p, N, S->cap_size, s2_cap.data());
-    if (rc) return rc;
-    tr.absorb_cap(s2_cap.data(), s2_cap.size());
-    return BJ_OK;
+    bj::Oracle &s2 = oracle[bj::ORACLE_STAGE2];
+    s2.mono = mono_s2.p, s2.evals = s2_lde.p, s2.tree = s2_tree.p;
+    if ((rc = intt_cols(s2_nat.p, mono_s2.p, nS2))) return rc;
+    return commit(s2, s2_cap, MONOMIALS);
 }
 
 // Sharded quotient: this rank's Qe evaluations Tl [2][Qe] -> the coefficients of the whole quotient in T, on every rank.
@@ -513,8 +510,8 @@ int Proving::exchange_residues(u64 *Tl) {
 }
 
 // ---------------- round 3: quotient (prover.rs:560-1495) ----------------
-// Reads wit_lde, s2_lde, the setup's LDE, beta / gamma / lbeta / lgamma.  Draws alpha; adds T (Tm: its chunks in the monomial
-// layout), q_lde, q_tree, q_cap; the transcript absorbs q_cap.  Fails when the quotient is not a polynomial.
+// Reads the witness, stage-2 and setup oracles, beta / gamma / lbeta / lgamma.  Draws alpha; adds T, the quotient oracle (its
+// monomials: T's chunks in the monomial layout) and q_cap; the transcript absorbs q_cap.  Fails when the quotient is not a polynomial.
 int Proving::round3_quotient() {
     const bool q_local = sh.world == 1;
     int rc = BJ_OK;
@@ -534,8 +531,8 @@ int Proving::round3_quotient() {
     const u64 *a_lookup = d_alphas.p, *a_spec = d_alphas.p + 2 * n_lookup_terms, *a_gates = a_spec + 2 * n_spec_terms,
               *a_l1 = a_gates + 2 * n_gate_terms;
     // Every term kernel on `points` points from local point `first` on, with the columns of the three oracles there given as
-    // `wit`, `s2` and `setup`.  The accumulators are per point, so the whole range at once (every LDE is resident) and one coset
-    // after the other (a lean setup, a lean proof) write the same words.
+    // `wit`, `s2` and `setup`.  The accumulators are per point, so the whole range at once (every oracle is resident) and one coset
+    // after the other (a lean one among them) write the same words.
     auto terms_on = [&](size_t first, size_t points, const bj::Cols wit, const bj::Cols s2, const bj::Cols setup) {
         auto sink = [&](const u64 *d_powers) { return bj::TermSink{d_powers, points, t0 + first, t1 + first}; };
         const bj::TermSink general = sink(a_gates), spec = sink(a_spec);
@@ -551,26 +548,23 @@ int Proving::round3_quotient() {
                                       s2, S->log_L, h_alpha_l1, sink(a_l1 + 2), I0 + first, S->d_inv_xm1 + first, st);
         bj::probe_end(ctx, pc);
     };
-    if (S->lean || lean_p) {
-        // An oracle that kept no LDE (the setup's, S->lean; the proof's own two, lean_p): its columns are extended from the monomials
-        // one coset at a time into [width][n] words, and the terms of that coset's n points are taken before the next one
-        // overwrites them; a resident one is read at that coset.  Highest coset first, so that coset 0 is what stays in the
-        // buffers: round 4 evaluates the polynomials at z from it.  q == 0 cannot happen (a power of two).  The quotient reads
-        // q cosets, the trees of rounds 1 and 2 covered fri_lde: neither bounds the other.
-        if (S->lean && (rc = setup_coset.take(ctx, bj::WS_SETUP_COSET))) return rc;
-        for (unsigned c = q; c-- > 0 && !rc;) {
-            const size_t first = (size_t)c * n;
-            if (S->lean) rc = lde_cols(S->d_mono, setup_coset.p, n, L.widths[bj::ORACLE_SETUP], S->log_L, c, 1);
-            if (!rc && lean_p) rc = lde_cols(mono.p, wit_lde.p, n, nW, S->log_L, c, 1);
-            if (!rc && lean_p) rc = lde_cols(mono_s2.p, s2_lde.p, n, nS2, S->log_L, c, 1);
-            if (!rc)
-                terms_on(first, n, lean_p ? bj::Cols{wit_lde.p, n} : bj::Cols{wit_lde.p + first, Ln},
-                         lean_p ? bj::Cols{s2_lde.p, n} : bj::Cols{s2_lde.p + first, Ln},
-                         S->lean ? bj::Cols{setup_coset.p, n} : bj::Cols{S->d_lde + first, Ln});
+    bj::Oracle &wit = oracle[bj::ORACLE_WITNESS], &s2 = oracle[bj::ORACLE_STAGE2], &setup = oracle[bj::ORACLE_SETUP];
+    if (wit.resident && s2.resident && setup.resident) {
+        if (Qe) terms_on(0, Qe, wit.cols_at(0), s2.cols_at(0), setup.cols_at(0));
+    } else {
+        // An oracle that kept no evaluations has its columns extended from the monomials one coset at a time, and the terms of that
+        // coset's n points are taken before the next one overwrites them; a resident one is read at that coset.  Highest coset
+        // first, so that coset 0 is what stays in the buffers: round 4 evaluates the polynomials at z from it.  q == 0 cannot
+        // happen (a power of two).  The quotient reads q cosets, the trees of rounds 1 and 2 covered fri_lde: neither bounds the other.
+        if (!setup.resident) {
+            if ((rc = setup_coset.take(ctx, bj::WS_SETUP_COSET))) return rc;
+            setup.evals = setup_coset.p;
         }
-        if (rc) return rc;
-    } else if (Qe) {
-        terms_on(0, Qe, bj::Cols{wit_lde.p, Ln}, bj::Cols{s2_lde.p, Ln}, bj::Cols{S->d_lde, Ln});
+        for (unsigned c = q; c-- > 0;) {
+            for (const bj::Oracle *o : {&setup, &wit, &s2})
+                if ((rc = rebuild(*o, c))) return rc;
+            terms_on((size_t)c * n, n, wit.cols_at(c), s2.cols_at(c), setup.cols_at(c));
+        }
     }
     BJ_CHECK_LAUNCH(ctx);
     // flatten (= bit-reversal of the evaluations), iNTT on their coset (prover.rs:1386-1422)
@@ -587,7 +581,7 @@ int Proving::round3_quotient() {
     if (rc) return rc;
     if (top[0] != 0 || top[1] != 0)
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove: constraint system is not satisfied (quotient is not a polynomial; prover.rs:1425-1438)");
-    Tm = T.p;
+    const u64 *Tm = T.p;   // the 2 q chunks of n coefficients each of the quotient, in the monomial layout of this trace length
     if (S->tiled) {   // the chunks come out of a transform of another size: one re-layout pass over 2 q n words
         bj::TmpBuf Tt;
         if ((rc = Tt.take(ctx, bj::WS_T_TILED))) return rc;
@@ -600,39 +594,18 @@ int Proving::round3_quotient() {
         rc = lde_cols(Tm + (size_t)e * Q, q_lde.p + (size_t)e * N, 2 * N, q, S->log_fri, sh.world > 1 ? S->c0 : 0, sh.world > 1 ? S->cl : S->fri_lde);
     if (rc) return rc;
     if ((rc = q_tree.take(ctx, bj::WS_Q_TREE))) return rc;
-    rc = bj_merkle_tree_build(ctx, q_lde.p, N, 2 * q, N, capl, q_tree.p);
-    if (!rc) rc = bj::gather_cap(ctx, sh, q_tree.p, N, S->cap_size, q_cap.data());
-    if (rc) return rc;
-    tr.absorb_cap(q_cap.data(), q_cap.size());
-    return BJ_OK;
+    bj::Oracle &quot = oracle[bj::ORACLE_QUOTIENT];
+    quot.mono = Tm, quot.evals = q_lde.p, quot.tree = q_tree.p;
+    return commit(quot, q_cap, EXTENDED);   // on the FRI domain, from the chunk layout: extended above
 }
 
-// An opened polynomial of the layout as its columns in the LDE arrays / in the monomial arrays (chunk j of the quotient:
-// coefficients [j*n, (j+1)*n) of T's two monomial forms, which lie Q apart instead of side by side).
-Src Proving::lde_src(const bj::Opened &o) const {
-    // a lean setup's columns exist on coset 0 only (setup_coset, stride n), and so do a lean proof's witness and stage-2 columns
-    // (wit_lde, s2_lde, stride n): enough for the evaluations of round 4, which read the first coset; DEEP never takes them from
-    // here (deep_set combines those sets on the monomials)
-    const u64 *bases[4] = {wit_lde.p, s2_lde.p, q_lde.p, S->lean ? setup_coset.p : S->d_lde};
-    const size_t os = lean_p ? n : Ln;
-    const size_t strides[4] = {os, os, N, S->lean ? n : Ln};
-    const u64 *b = bases[o.oracle];
-    return {b + o.col0 * strides[o.oracle], o.col1 == bj::NO_COLUMN ? nullptr : b + o.col1 * strides[o.oracle]};
-}
-Src Proving::mono_src(const bj::Opened &o) const {
-    if (o.oracle == bj::ORACLE_QUOTIENT) return {Tm + (size_t)(o.col0 / 2) * n, Tm + Q + (size_t)(o.col0 / 2) * n};
-    const u64 *bases[4] = {mono.p, mono_s2.p, nullptr, S->d_mono};
-    const u64 *b = bases[o.oracle];
-    return {b + (size_t)o.col0 * n, o.col1 == bj::NO_COLUMN ? nullptr : b + (size_t)o.col1 * n};
-}
-
-// Reads wit_lde, mono, s2_lde, mono_s2, q_lde, Tm and the setup's LDE and monomials.  Adds srcs / msrcs and the two small sets
-// opened elsewhere than at z: zsrc / mz and (with lookups) lsrc / ml.  F_p^2 polys contribute two columns.
-void Proving::list_opened_columns() {
-    for (const bj::Opened &o : L.opened) srcs.push_back(lde_src(o)), msrcs.push_back(mono_src(o));
-    zsrc = {srcs[L.at_z]};
-    mz = {msrcs[L.at_z]};
-    for (unsigned i = 0; i < L.n_lookup_terms; i++) lsrc.push_back(srcs[L.at_a + i]), ml.push_back(msrcs[L.at_a + i]);   // the A_i, then B
+// Opened polynomials of the layout as sources on the evaluations of their oracles or on the monomials (oracle_value.h).  On the
+// evaluations: from this rank's first coset on, which is all a lean oracle has (coset 0, left by round 3) — enough for round 4;
+// DEEP reads a set there only if bj::can_stream says its oracles are on the FRI domain.
+std::vector<Src> Proving::sources(const std::vector<bj::Opened> &polys, bool on_evals) const {
+    std::vector<Src> ss;
+    for (const bj::Opened &o : polys) ss.push_back(on_evals ? oracle[o.oracle].eval_src(o) : oracle[o.oracle].mono_src(o));
+    return ss;
 }
 
 // The polynomials `ss` at the point `at`, by barycentric evaluation on this GPU's first coset (shift open_shift); w: 2 n words
@@ -668,29 +641,28 @@ int Proving::evaluate_at(u64 *w, u64 open_shift, const std::vector<Src> &ss, con
 }
 
 // ---------------- round 4: openings (prover.rs:1501-1802) ----------------
-// Reads every oracle of rounds 1-3 (list_opened_columns).  Draws z; adds zo, srcs / msrcs and the small sets, vz, vzo, v0; the
-// transcript absorbs the opened values.
+// Reads every oracle of rounds 1-3 on this rank's first coset.  Draws z; adds zo, vz, vzo, v0; the transcript absorbs the opened values.
 int Proving::round4_openings() {
     int rc = BJ_OK;
     challenge2(z);
     bj::TmpBuf w;
     if ((rc = w.take(ctx, bj::WS_BARY_W))) return rc;
-    list_opened_columns();
+    const std::vector<bj::OpeningSet> sets = L.opening_sets(nullptr, nullptr, 0);   // everything at z, z(x) at z * omega, (lookups) the sums at 0
     // every rank evaluates from ITS first coset (shift 7*w^bitrev(c0)): the polynomials have degree < n, so the value
     // is the same field element whichever coset it is interpolated from — no exchange, identical transcripts
     const u64 open_shift = gl::mul(gl::GEN, gl::pow(gl::omega(log_n + S->log_L), gl::bitrev32(S->c0, S->log_L)));
-    if ((rc = evaluate_at(w.p, open_shift, srcs, z, vz))) return rc;
+    if ((rc = evaluate_at(w.p, open_shift, sources(sets[0].polys, true), z, vz))) return rc;
     tr.absorb(vz.data(), vz.size());
     {
         u64 om = gl::omega(log_n);
         zo[0] = gl::mul(gl::canon(z[0]), om);
         zo[1] = gl::mul(gl::canon(z[1]), om);
     }
-    if ((rc = evaluate_at(w.p, open_shift, zsrc, zo, vzo))) return rc;
+    if ((rc = evaluate_at(w.p, open_shift, sources(sets[1].polys, true), zo, vzo))) return rc;
     tr.absorb(vzo.data(), vzo.size());
     if (has_lookup) {
         u64 zero2[2] = {0, 0};
-        if ((rc = evaluate_at(w.p, open_shift, lsrc, zero2, v0))) return rc;
+        if ((rc = evaluate_at(w.p, open_shift, sources(sets[2].polys, true), zero2, v0))) return rc;
         tr.absorb(v0.data(), v0.size());
     }
     return BJ_OK;
@@ -728,17 +700,17 @@ int Proving::flush_deep(DeepSets &D) {
     return BJ_OK;
 }
 
-// One opening set: the polynomials ls (on the LDE) = ms (monomials) with the values vals at the point at.  Takes the next
-// ms.size() challenges; a large set gets its extended numerator (an arena buffer of 2 N words); queues the set for flush_deep.
-// on_monomials: the set goes that way whatever its size (its columns are on no FRI domain: the set at z under a lean setup, every
-// set of a lean proof).
-int Proving::deep_set(DeepSets &D, const std::vector<Src> &ls, const std::vector<Src> &ms, const u64 *vals, const u64 *at, bool on_monomials) {
+// One opening set: the polynomials polys with the values vals at the point at.  Takes the next polys.size() challenges; queues
+// the set for flush_deep: as it is, or (a large set, or one with a polynomial on no FRI domain: bj::can_stream) as its extended
+// numerator, an arena buffer of 2 N words.
+int Proving::deep_set(DeepSets &D, const std::vector<bj::Opened> &polys, const u64 *vals, const u64 *at) {
     const u64 *ch = D.chs.data() + 2 * D.choff;
-    D.choff += ms.size();
-    if (!on_monomials && bj::open_columns(ms.data(), ms.size()).size() < bj::WS_LARGE_SET) {   // a handful of columns: streaming them over the FRI domain is cheaper than an extra LDE pass
-        D.queue(ls, ch, vals, at);
+    D.choff += polys.size();
+    if (bj::base_columns(polys) < bj::WS_LARGE_SET && bj::can_stream(bj::oracle_mask(polys), bj::resident_mask(oracle))) {   // a handful of columns: streaming them over the FRI domain is cheaper than an extra LDE pass
+        D.queue(sources(polys, true), ch, vals, at);
         return BJ_OK;
     }
+    const std::vector<Src> ms = sources(polys, false);
     bj::TmpBuf num_lde;   // this set's extended numerator: alive until the sets are flushed
     if (int ra = num_lde.take(ctx, bj::WS_NUM_LDE)) return ra;
     int r;
@@ -784,23 +756,12 @@ int Proving::round5a_deep() {
     if (sh.world > 1 && (rc = D.num_slice.take(ctx, bj::WS_NUM_SLICE))) return rc;
     const u64 zero2[2] = {0, 0};
     for (auto &set : sets) {   // in the order the challenges are handed out
-        // lean_p: every set holds a witness or a stage-2 column (z(x), the lookup sums, a public input's variable), none of which is on the FRI domain
-        if (set.point == bj::OPEN_AT_Z) rc = deep_set(D, srcs, msrcs, vz.data(), z, S->lean || lean_p);
-        else if (set.point == bj::OPEN_AT_Z_OMEGA) rc = deep_set(D, zsrc, mz, vzo.data(), zo, lean_p);
-        else if (set.point == bj::OPEN_AT_ZERO) rc = deep_set(D, lsrc, ml, v0.data(), zero2, lean_p);
-        else {
-            std::vector<Src> ps, pl;
-            std::vector<u64> pv;
-            for (size_t i = 0; i < set.polys.size(); i++) {
-                pl.push_back(lde_src(set.polys[i]));
-                ps.push_back(mono_src(set.polys[i]));
-                pv.push_back(gl::canon(h_public_values[set.value[i]]));
-                pv.push_back(0);
-            }
-            const u64 at2[2] = {gl::pow(gl::omega(log_n), set.row), 0};
-            rc = deep_set(D, pl, ps, pv.data(), at2, lean_p);
-        }
-        if (rc) return rc;
+        const u64 row[2] = {gl::pow(gl::omega(log_n), set.row), 0};
+        std::vector<u64> pv;
+        if (set.point == bj::OPEN_AT_ROW)
+            for (unsigned v : set.value) pv.insert(pv.end(), {gl::canon(h_public_values[v]), 0});
+        const u64 *const vals[4] = {vz.data(), vzo.data(), v0.data(), pv.data()}, *const at[4] = {z, zo, zero2, row};
+        if ((rc = deep_set(D, set.polys, vals[set.point], at[set.point]))) return rc;
     }
     return flush_deep(D);
 }
@@ -848,19 +809,14 @@ struct Queries {
 };
 
 // Round 6, the base oracles: leaves and Merkle paths of the witness, stage-2, quotient and setup trees.
-// Reads qr.idxs, qr.depth, the four LDEs and trees; adds qr.block, qr.gathered.
+// Reads qr.idxs, qr.depth, the four oracles; adds qr.block, qr.gathered.
 int Proving::gather_base_queries(Queries &qr) {
     const unsigned W = sh.world, depth = qr.depth;
     // a leaf lives on rank index / N; every rank gathers at (index mod N) and the owner's answer is kept
-    const unsigned *widths = L.widths;
-    const u64 *bases[4] = {wit_lde.p, s2_lde.p, q_lde.p, S->d_lde};   // the last is null under a lean setup, the first two hold one coset in a lean proof: evaluated below
-    const u64 *monos[4] = {lean_p ? mono.p : nullptr, lean_p ? mono_s2.p : nullptr, nullptr, S->lean ? S->d_mono : nullptr};   // all three in the layout intt_cols writes
-    const size_t strides[4] = {Ln, Ln, N, Ln};
-    const u64 *trees[4] = {wit_tree.p, s2_tree.p, q_tree.p, S->d_tree};
     int rc = BJ_OK;
     bj::TmpBuf d_idx, d_g;
     size_t per_query = 0;
-    for (int o = 0; o < 4; o++) per_query += widths[o] + (size_t)depth * 4;
+    for (const bj::Oracle &o : oracle) per_query += o.width + (size_t)depth * 4;
     const size_t G = qr.block = per_query * num_queries;
     if ((rc = d_idx.take(ctx, bj::WS_QUERY_IDX, num_queries))) return rc;
     if ((rc = d_g.take(ctx, bj::WS_QUERY_BLOCK, G))) return rc;
@@ -871,13 +827,13 @@ int Proving::gather_base_queries(Queries &qr) {
     }
     qr.gathered.resize(G * W);
     size_t off = 0;
-    for (int o = 0; o < 4; o++) {
-        if (monos[o])   // the leaf's words are the oracle's polynomials at the leaf's point; the paths come from the kept tree
-            bj::launch_eval_monomials_at(monos[o], n, widths[o], log_n, S->tiled, ctx->tw_fwd, I0, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
-        else
-            bj::launch_gather_rows(bases[o], strides[o], widths[o], d_idx.p, (unsigned)num_queries, d_g.p + off, st);
-        off += (size_t)widths[o] * num_queries;
-        bj::launch_merkle_paths(trees[o], N, depth, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
+    for (const bj::Oracle &o : oracle) {
+        if (o.leaf_from_evals())
+            bj::launch_gather_rows(o.evals, o.stride, o.width, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
+        else   // the leaf's words are the oracle's polynomials at the leaf's point (the monomials in the layout intt_cols writes); the paths come from the kept tree
+            bj::launch_eval_monomials_at(o.mono, n, o.width, log_n, S->tiled, ctx->tw_fwd, I0, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
+        off += (size_t)o.width * num_queries;
+        bj::launch_merkle_paths(o.tree, N, depth, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
         off += (size_t)depth * 4 * num_queries;
     }
     BJ_CHECK_LAUNCH(ctx);

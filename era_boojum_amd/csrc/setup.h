@@ -6,6 +6,7 @@
 #include "ctx.h"
 #include "fri_types.h"
 #include "gate_program.h"
+#include "oracle_value.h"
 #include "proof_layout.h"
 
 #include <vector>
@@ -39,6 +40,14 @@ struct bj_setup : bj::CircuitShape {   // proof_layout.h: bj::circuit_shape fill
     gl::u64 *d_inv_xm1 = nullptr;      // 1 / (x - 1) on the points this GPU evaluates the quotient on (a property of the domain)
     uint32_t *d_placement = nullptr;   // bj_setup_create_from_placement: variable index per cell [V][n], PLACEMENT_NONE = placeholder
     std::vector<gl::u64> cap;
+
+    // The setup's committed oracle as a value (oracle_value.h).  A lean setup has no evaluations of its own: a proof points the value at
+    // a [width][n] coset buffer of its workspace
+    bj::Oracle oracle() const {
+        bj::Oracle o = bj::oracle_of(layout.widths[bj::ORACLE_SETUP], (size_t)1 << log_n, Ls, !lean);
+        o.mono = d_mono, o.evals = d_lde, o.tree = d_tree;
+        return o;
+    }
 };
 
 

@@ -17,8 +17,9 @@ extern "C" size_t bj_host_witness_plan(unsigned nW, unsigned G, int absorb, int 
 }
 
 // The workspace plan of a proof.  circuit9: log_n, num_vars, num_gp_vars, num_witness_cols, num_constant_cols, lookup_width,
-// lookup_reps, table_id_col, quotient_degree; flags4: tiled, multiplicity column counted into the arena, host-witness mode
-// (0 none, 1 absorbing, 2 not absorbing), proof of work; sched / num_queries: bj_fri_schedule of the proof config.
+// lookup_reps, table_id_col, quotient_degree; flags4: tiled (bit 0; bit 1: a lean setup, bit 2: a lean proof), multiplicity column
+// counted into the arena, host-witness mode (0 none, 1 absorbing, 2 not absorbing), proof of work; sched / num_queries:
+// bj_fri_schedule of the proof config.
 // out4: total words, words of the allowance entries, number of entries, words of the exact entries.
 extern "C" void bj_workspace_plan_summary(const unsigned *circuit9, unsigned fri_lde, unsigned cap_size, unsigned world, unsigned alpha_terms,
                                           const unsigned *pub_cols, const unsigned *pub_rows, size_t n_pub, const unsigned *flags4,
@@ -30,8 +31,10 @@ extern "C" void bj_workspace_plan_summary(const unsigned *circuit9, unsigned fri
     bj_proof_config cfg{};
     cfg.fri_lde_factor = fri_lde; cfg.cap_size = cap_size;
     const bj::ProofLayout L = bj::proof_layout(bj::circuit_shape(&c, &cfg));
-    const bj::WorkspacePlan P = bj::workspace_plan(bj::workspace_shape(L, world, flags4[0] != 0, alpha_terms, pub_cols, pub_rows, n_pub, flags4[1] != 0,
-                                                                       flags4[2], flags4[3] != 0, sched, sched_len, num_queries));
+    bj::WorkspaceShape s = bj::workspace_shape(L, world, (flags4[0] & 1) != 0, alpha_terms, pub_cols, pub_rows, n_pub, flags4[1] != 0, flags4[2],
+                                               flags4[3] != 0, sched, sched_len, num_queries);
+    s.lean = (flags4[0] & 2) != 0, s.lean_oracles = (flags4[0] & 4) != 0;
+    const bj::WorkspacePlan P = bj::workspace_plan(s);
     size_t exact = 0;
     for (const bj::WorkspaceEntry &e : P.entries)
         if (e.exact) exact += e.words;

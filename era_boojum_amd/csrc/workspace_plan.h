@@ -5,6 +5,7 @@
 // Plain C++17, no HIP: a host program can use it (tests/workspace_plan_check.cpp).
 #pragma once
 #include "callee_words.h"
+#include "oracle_value.h"
 #include "proof_layout.h"
 
 #include <cstddef>
@@ -54,13 +55,15 @@ struct WorkspaceShape {
     unsigned alpha_terms = 0;                // powers of the quotient challenge
     unsigned world = 1;
     bool tiled = false;
-    bool lean = false;                       // the setup keeps no LDE (bj_setup::lean): set by the prover, single device only
-    bool lean_oracles = false;               // the proof keeps no LDE of its witness and stage-2 oracles (BJ_PROOF_LEAN): one coset buffer each; set by the prover, world == 1 only
+    // the residency bits (oracle_value.h: resident_mask), set by the prover, single device only.  lean: the setup's oracle keeps no
+    // evaluations (bj_setup::lean); lean_oracles: nor do the witness and stage-2 oracles (BJ_PROOF_LEAN)
+    bool lean = false, lean_oracles = false;
     size_t tree_words = 0;                   // bj_merkle_tree_digests(N, cap_size / world) * 4
     unsigned depth = 0;                      // path length of the base oracles: log2(N * world / cap_size)
     unsigned opened_cols = 0;                // base columns of the polynomials opened at z (an F_p^2 polynomial counts two)
     unsigned lookup_terms = 0;               // lookup sums opened at 0 (A_i and B), each an F_p^2 polynomial
     std::vector<unsigned> pub_set_cols;      // one per public-input opening set (row): its columns
+    std::vector<unsigned> set_oracles;       // one per opening set, in challenge order: the oracles its polynomials belong to (oracle_mask)
     bool has_lookup = false;
     bool mult_in_arena = false;              // the multiplicity column is counted into a column of the arena
     unsigned host_witness = WS_HOST_NONE;
@@ -83,10 +86,12 @@ inline WorkspaceShape workspace_shape(const ProofLayout &L, unsigned world, bool
     w.cap_size = L.s.cap_size;
     w.tree_words = (2 * w.N - w.cap_size / world) * 4;   // bj_merkle_tree_digests of the local subtree
     while (((size_t)1 << w.depth) < w.N * world / w.cap_size) w.depth++;
-    for (const Opened &o : L.opened) w.opened_cols += o.col1 == NO_COLUMN ? 1 : 2;
+    w.opened_cols = base_columns(L.opened);
     w.has_lookup = L.has_lookup, w.lookup_terms = L.n_lookup_terms;
-    for (const OpeningSet &set : L.opening_sets(pub_cols, pub_rows, n_pub))
+    for (const OpeningSet &set : L.opening_sets(pub_cols, pub_rows, n_pub)) {
+        w.set_oracles.push_back(oracle_mask(set.polys));
         if (set.point == OPEN_AT_ROW) w.pub_set_cols.push_back((unsigned)set.polys.size());
+    }
     w.mult_in_arena = mult_in_arena, w.host_witness = host_witness, w.pow = pow;
     for (size_t i = 0; i < sched_len && i < 32; i++) w.sched[i] = sched[i];
     w.sched_len = sched_len < 32 ? sched_len : 32, w.num_queries = num_queries;
@@ -130,16 +135,17 @@ inline WorkspacePlan workspace_plan(const WorkspaceShape &s) {
     };
     // round 1: witness
     if (s.mult_in_arena) P.take(WS_MULTIPLICITY, s.n);
-    const size_t oracle_stride = s.lean_oracles ? s.n : s.Ln;   // lean oracles: one coset of each at a time, rebuilt from the monomials
-    P.take(WS_WIT_LDE, (size_t)s.nW * oracle_stride);
+    const unsigned resident = resident_mask(s.lean, s.lean_oracles);
+    auto is_resident = [resident](unsigned oracle) { return (resident >> oracle & 1) != 0; };
+    P.take(WS_WIT_LDE, oracle_of(s.nW, s.n, s.Ln, is_resident(ORACLE_WITNESS)).eval_words());
     P.take(WS_MONO, (size_t)s.nW * s.n);
     P.take(WS_MONO_S2, (size_t)s.nS2 * s.n);
     P.take(WS_WIT_TREE, s.tree_words);
-    if (s.host_witness == WS_HOST_ABSORBING && !s.lean_oracles) P.take(WS_CAPACITY, 4 * s.N);   // lean oracles hash coset by coset, never group by group
+    if (s.host_witness == WS_HOST_ABSORBING && is_resident(ORACLE_WITNESS)) P.take(WS_CAPACITY, 4 * s.N);   // a lean oracle is hashed coset by coset, never group by group
     // round 2: stage 2
     P.take(WS_S2_NAT, (size_t)s.nS2 * s.n);
     P.take(WS_S2_SCRATCH, copy_perm_stage2_scratch_words(s.n_chunks, s.n));
-    P.take(WS_S2_LDE, (size_t)s.nS2 * oracle_stride);
+    P.take(WS_S2_LDE, oracle_of(s.nS2, s.n, s.Ln, is_resident(ORACLE_STAGE2)).eval_words());
     P.take(WS_S2_TREE, s.tree_words);
     // round 3: quotient
     P.take(WS_ALPHAS, 2 * (size_t)s.alpha_terms);
@@ -148,7 +154,7 @@ inline WorkspacePlan workspace_plan(const WorkspaceShape &s) {
         P.take(WS_T_LOCAL, 2 * s.Qe);
         P.take(WS_RESIDUES, 2 * s.Q);
     }
-    if (s.lean) P.take(WS_SETUP_COSET, (size_t)s.n_setup * s.n);   // one coset of the setup columns at a time; round 4 reads the last one left in it
+    if (!is_resident(ORACLE_SETUP)) P.take(WS_SETUP_COSET, oracle_of(s.n_setup, s.n, s.Ln, false).eval_words());   // one coset of the setup columns at a time; round 4 reads the last one left in it
     if (s.tiled) P.take(WS_T_TILED, 2 * s.Q);
     P.take(WS_Q_LDE, (size_t)2 * s.q * s.N);
     P.take(WS_Q_TREE, s.tree_words);
@@ -164,11 +170,9 @@ inline WorkspacePlan workspace_plan(const WorkspaceShape &s) {
     std::vector<size_t> sets = {s.opened_cols, 2};
     if (s.has_lookup) sets.push_back(2 * (size_t)s.lookup_terms);
     sets.insert(sets.end(), s.pub_set_cols.begin(), s.pub_set_cols.end());
-    for (size_t &cols : sets) {
-        // a lean setup has its columns on no FRI domain: the set opened at z, which holds them, always goes through its monomials.
-        // Lean oracles: every set holds a witness or a stage-2 column (z and the lookup sums are stage 2, a public input is a
-        // variable), so every set does
-        if (cols < WS_LARGE_SET && !(s.lean && &cols == &sets[0]) && !s.lean_oracles) continue;
+    for (size_t i = 0; i < sets.size(); i++) {
+        size_t &cols = sets[i];
+        if (cols < WS_LARGE_SET && can_stream(s.set_oracles[i], resident)) continue;   // a handful of columns, all of them on the FRI domain
         P.take(WS_NUM_LDE, 2 * s.N);
         P.allow(WS_ARGS_COMBINE, column_list_arg_words(cols));
         if (sharded && s.n % W == 0 && s.n / W >= 256) P.allow(WS_GATHER_STAGING, gather_columns_staging_words(W, 2, s.n / W));

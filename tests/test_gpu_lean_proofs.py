@@ -251,6 +251,51 @@ def test_arena_sizes():
         ctx().release_workspace()
 
 
+def _plan_words(c, fri_lde, cap, sec, lean_proof):
+    """Total words of the workspace plan (csrc/workspace_plan.h) of a bj_prove_dev proof of c on one GPU, through the host helper."""
+    import ctypes as C
+    from era_boojum_amd import build
+    lib = C.CDLL(build.build_canon_helper())
+    lib.bj_workspace_plan_summary.restype = None
+    new_pow, nq, sched, _ = binding.fri_schedule(sec, cap, 0, fri_lde.bit_length() - 1, c.log_n)
+    u = lambda xs: (C.c_uint * max(len(xs), 1))(*xs)
+    nine = [c.log_n, c.num_vars, c.num_gp_vars, int(getattr(c, "num_witness_cols", 0)), c.num_constant_cols, c.lookup_width, c.lookup_reps,
+            c.table_id_col, c.quotient_degree]
+    # powers of the quotient challenge: lookup | gates | L1 | copy-permutation chunks (prover.hip, round 3)
+    alpha_terms = c.lookup_reps + 1 + sum(g.reps * g.num_terms for g in c.gates) + 1 + -(-c.num_vars // c.quotient_degree)
+    out = (C.c_size_t * 4)()
+    lib.bj_workspace_plan_summary(u(nine), C.c_uint(fri_lde), C.c_uint(cap), C.c_uint(1), C.c_uint(alpha_terms),
+                                  u([p[0] for p in c.public_inputs]), u([p[1] for p in c.public_inputs]), C.c_size_t(len(c.public_inputs)),
+                                  u([4 if lean_proof else 0, 0, 0, int(new_pow != 0)]), (C.c_uint32 * 32)(*sched), C.c_size_t(len(sched)),
+                                  C.c_size_t(nq), out)
+    return int(out[0])
+
+
+def test_same_probes_and_the_plan_of_each_mode():
+    """What byte identity does not show: a resident and a lean proof of one 2^7-row circuit list the same kernel probes in the same
+    order (bj_proof_kernel_stats), and each reserves exactly the total of the workspace plan of its mode (bj_proof_workspace_bytes
+    in a context whose workspace was released: the reservation IS the plan's total)."""
+    fri_lde, cap, sec = 8, 16, 20
+    c = S.sha_shaped_circuit(7, seed=107, table_bits=1)
+    assert c.lookup_reps > 0 and c.public_inputs and not c.specialized_gates   # every kind of opening set; no terms but the gates', lookups' and chunks'
+    s = E.ProverSetup(ctx(), c, fri_lde, cap, sec)
+    try:
+        probes, proofs = {}, {}
+        for mode in (False, True):
+            ctx().release_workspace()
+            with lean(mode):
+                proofs[mode] = on_device(s, lambda v, m: s.prove_dev(v, m)[0])
+            probes[mode] = list(s.last_kernels)
+            ws, plan = dict(s.last_workspace), _plan_words(c, fri_lde, cap, sec, mode)
+            print("lean %s: probes %s; reserved %d bytes, plan %d words" % (mode, probes[mode], ws["reserved_bytes"], plan))
+            assert ws["overflow_slabs"] == 0 and ws["reserved_bytes"] == 8 * plan
+        same(proofs[True], proofs[False])
+        assert len(probes[False]) >= 2 and probes[True] == probes[False]
+    finally:
+        s.close()
+        ctx().release_workspace()
+
+
 def test_tiled_monomials_at_2p22_rows():
     """2^22 rows, the one size where mono and mono_s2 lie in the tiled layout: the per-coset extension reads it, and the evaluation
     kernel reads it in place through its index map.  The circuit of the lean-setup test of this size: ten general-purpose columns,
