@@ -1055,10 +1055,11 @@ class CopyReport:
 
 
 class _Ticket:
-    """A proof in flight (bj_ticket) + the host arrays it reads."""
+    """A proof in flight (bj_ticket) + the host arrays it reads + the setup and the context its lane works on: while the ticket
+    lives, neither is collected under the lane's worker.  `handle` is None once it was waited for."""
 
-    def __init__(self, handle, keep):
-        self.handle, self.keep = handle, keep
+    def __init__(self, handle, keep, setup=None, ctx=None):
+        self.handle, self.keep, self.setup, self.ctx = handle, keep, setup, ctx
 
 
 @contextlib.contextmanager
@@ -1302,18 +1303,27 @@ class ProverSetup:
         t = C.c_void_p()
         self._ctx._check(self._lib.bj_prove_async(self._ctx._h, self._h, _np_ptr(v), _np_ptr(m) if c.lookup_reps and not count_multiplicities else None,
                                                   _np_ptr(pv), C.byref(t)))
-        return _Ticket(t, (v, m))
+        return _Ticket(t, (v, m), self, self._ctx)
 
     def done(self, ticket):
         """bj_proof_poll: True when `wait` would not block."""
-        return bool(self._lib.bj_proof_poll(ticket.handle))
+        if ticket.handle is None:
+            raise BoojumHipError("this ticket was waited for already")
+        rc = self._lib.bj_proof_poll(ticket.handle)
+        if rc < 0:
+            raise BoojumHipError("bj_proof_poll: %s: no live ticket (its context was destroyed)" % self._lib.bj_status_string(rc).decode())
+        return bool(rc)
 
     def wait(self, ticket):
         """bj_proof_wait: blocks until the ticket's proof is complete; returns (serialised proof, per-stage ms) like `prove`."""
+        if ticket.handle is None:
+            raise BoojumHipError("this ticket was waited for already: a ticket is waited for exactly once")
         h = C.c_void_p()
         t, ticket.handle = ticket.handle, None
         rc = self._lib.bj_proof_wait(t, C.byref(h))
-        ticket.keep = None
+        ticket.keep = ticket.setup = ticket.ctx = None
+        if rc != 0 and not self._ctx._h:   # the context was closed with the proof in flight: the library has freed proof and ticket
+            raise BoojumHipError("%s: the context was closed before the ticket was waited for" % self._lib.bj_status_string(rc).decode())
         self._ctx._check(rc)
         return self._finish(h)
 

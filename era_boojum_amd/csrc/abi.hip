@@ -2,6 +2,7 @@
 // Public contract: include/boojum_hip.h.  No CPU fallback anywhere in this file: every entry point either
 // enqueues HIP work on the context's device or returns an error.
 #include "ctx.h"
+#include "async_admission.h"
 #include "ntt_plan.h"
 #include "workspace_plan.h"
 
@@ -97,6 +98,81 @@ int arena_reset(bj_ctx *ctx, size_t need_elems) {
     return BJ_OK;
 }
 
+constexpr size_t RING_BYTES = (size_t)1 << 20, RING_MAX_BLOCK = (size_t)128 << 10;
+
+int stage_witness_elems(bj_ctx *ctx, size_t need) {
+    if (ctx->wit_stage_elems >= need) return BJ_OK;   // kept for the next proof (no 3 GB hipMalloc per proof)
+    if (ctx->wit_stage) BJ_HIP(ctx, hipFree(ctx->wit_stage));
+    ctx->wit_stage = nullptr;
+    ctx->wit_stage_elems = 0;
+    BJ_HIP(ctx, hipMalloc((void **)&ctx->wit_stage, need * 8));
+    ctx->wit_stage_elems = need;
+    return BJ_OK;
+}
+
+int ensure_scaled22(bj_ctx *ctx) {   // a table for 2^22 is a prefix of every larger one: built once per context, whatever tw_inv grows to
+    if (ctx->tw_inv_scaled22) return BJ_OK;
+    const size_t n = (size_t)1 << 22;
+    if (!ctx->tw_inv || ctx->tw_inv_log < 22) return fail(ctx, BJ_ERR_HIP, "internal error: the scaled twiddle table before the inverse twiddles of 2^22");
+    BJ_HIP(ctx, hipMalloc((void **)&ctx->tw_inv_scaled22, (n / 2) * sizeof(u64)));
+    bj::launch_scale_table(ctx->tw_inv, ctx->tw_inv_scaled22, n / 2, gl::inv(gl::canon((u64)n % gl::P)), ctx->stream);
+    BJ_CHECK_LAUNCH(ctx);
+    return BJ_OK;
+}
+
+void ctx_held(const bj_ctx *ctx, LaneBytes *out) {
+    *out = LaneBytes();
+    size_t arena = ctx->arena_elems;
+    for (const auto &sl : ctx->arena_slabs) arena += sl.second;
+    out->part[LANE_ARENA] = arena * 8;
+    out->part[LANE_STAGING] = ctx->wit_stage_elems * 8;
+    out->part[LANE_SCRATCH] = ctx->scratch_elems * 8;
+    out->part[LANE_TW_FWD] = ctx->tw_fwd ? ((size_t)1 << (ctx->tw_fwd_log - 1)) * 8 : 0;
+    out->part[LANE_TW_INV] = ctx->tw_inv ? ((size_t)1 << (ctx->tw_inv_log - 1)) * 8 : 0;
+    out->part[LANE_TW_SCALED22] = ctx->tw_inv_scaled22 ? ((size_t)1 << 21) * 8 : 0;
+}
+
+int ctx_reserve(bj_ctx *ctx, const LaneBytes &want) {
+    if (int rc = bind(ctx)) return rc;
+    if (ctx->in_proof) return fail(ctx, BJ_ERR_INVALID_ARG, "internal error: a workspace reserved under a running proof");
+    auto tw_log = [](size_t bytes) {   // a table of 2^(k-1) words serves 2^k points
+        unsigned k = 1;
+        while (((size_t)8 << (k - 1)) < bytes) k++;
+        return k;
+    };
+    const size_t arena = want.part[LANE_ARENA] / 8;
+    if (int rc = arena_reset(ctx, arena > ctx->arena_learned ? arena : ctx->arena_learned)) return rc;
+    if (int rc = stage_witness_elems(ctx, want.part[LANE_STAGING] / 8)) return rc;
+    if (int rc = ensure_scratch(ctx, want.part[LANE_SCRATCH] / 8)) return rc;
+    if (want.part[LANE_TW_FWD])
+        if (int rc = ensure_twiddles(ctx, tw_log(want.part[LANE_TW_FWD]), false)) return rc;
+    if (want.part[LANE_TW_INV])
+        if (int rc = ensure_twiddles(ctx, tw_log(want.part[LANE_TW_INV]), true)) return rc;
+    if (want.part[LANE_TW_SCALED22])
+        if (int rc = ensure_scaled22(ctx)) return rc;
+    // the small blocks a proof would otherwise create on first use: the pinned ring of the host -> device blocks, the copy stream
+    if (!ctx->h_ring) BJ_HIP(ctx, hipHostMalloc((void **)&ctx->h_ring, RING_BYTES, hipHostMallocDefault));
+    if (!ctx->copy_stream) BJ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    return BJ_OK;
+}
+
+int ctx_release_own_workspace(bj_ctx *ctx) {
+    BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->copy_stream) BJ_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+    if (int rc = arena_drop_slabs(ctx)) return rc;
+    if (ctx->arena) BJ_HIP(ctx, hipFree(ctx->arena));
+    ctx->arena = nullptr;
+    ctx->arena_elems = ctx->arena_off = 0;
+    ctx->arena_learned = 0;
+    if (ctx->d_scratch) BJ_HIP(ctx, hipFree(ctx->d_scratch));
+    ctx->d_scratch = nullptr;
+    ctx->scratch_elems = 0;
+    if (ctx->wit_stage) BJ_HIP(ctx, hipFree(ctx->wit_stage));
+    ctx->wit_stage = nullptr;
+    ctx->wit_stage_elems = 0;
+    return BJ_OK;
+}
+
 int TmpBuf::alloc(bj_ctx *c, size_t words) {
     ctx = c;
     from_arena = false;
@@ -139,7 +215,6 @@ int workspace_all_taken(bj_ctx *ctx) {
     return BJ_OK;
 }
 
-constexpr size_t RING_BYTES = (size_t)1 << 20, RING_MAX_BLOCK = (size_t)128 << 10;
 int h2d_async(bj_ctx *ctx, void *d_dst, const void *h_src, size_t bytes) {
     if (int rc = bind(ctx)) return rc;
     if (!bytes) return BJ_OK;
@@ -220,6 +295,7 @@ void load_env() {
     if (set("BJ_ASYNC_MODE")) e.async_mode = atoi(getenv("BJ_ASYNC_MODE"));
     e.async_stagger = str("BJ_ASYNC_STAGGER").rfind("0", 0) != 0;
     e.async_debug = set("BJ_ASYNC_DEBUG");
+    if (set("BJ_HBM_BUDGET_BYTES")) e.hbm_budget_bytes = (size_t)strtoull(getenv("BJ_HBM_BUDGET_BYTES"), nullptr, 10);
     e.peer_debug = set("BJ_PEER_DEBUG");
     if (set("BJ_PEER_TEST_FAIL_RANK")) e.peer_test_fail_rank = atoi(getenv("BJ_PEER_TEST_FAIL_RANK"));
     e.gate_no_aot = set("BJ_GATE_NO_AOT");
@@ -343,20 +419,7 @@ int bj_ctx_release_workspace(bj_ctx *ctx) {
     if (int rc = bj::bind(ctx)) return rc;
     if (ctx->in_proof) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_ctx_release_workspace: a proof is running");
     if (int rc = bj::pipeline_release_workspace(ctx)) return rc;
-    BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->copy_stream) BJ_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-    if (int rc = bj::arena_drop_slabs(ctx)) return rc;
-    if (ctx->arena) BJ_HIP(ctx, hipFree(ctx->arena));
-    ctx->arena = nullptr;
-    ctx->arena_elems = ctx->arena_off = 0;
-    ctx->arena_learned = 0;
-    if (ctx->d_scratch) BJ_HIP(ctx, hipFree(ctx->d_scratch));
-    ctx->d_scratch = nullptr;
-    ctx->scratch_elems = 0;
-    if (ctx->wit_stage) BJ_HIP(ctx, hipFree(ctx->wit_stage));
-    ctx->wit_stage = nullptr;
-    ctx->wit_stage_elems = 0;
-    return BJ_OK;
+    return bj::ctx_release_own_workspace(ctx);
 }
 
 int bj_ctx_set_stream(bj_ctx *ctx, void *hip_stream) {
@@ -504,10 +567,8 @@ static int intt_groups(bj_ctx *ctx, const u64 *d_in, size_t in_col_stride, u64 *
     if (int rc = ensure_scratch(ctx, (size_t)group * n)) return rc;
     const u64 n_inv = log_n ? gl::inv(gl::canon((u64)n % gl::P)) : 1;
     const u64 step = coset == 1 ? 1 : gl::inv(coset);
-    if (to_tiled && !ctx->tw_inv_scaled22) {   // a table for 2^22 is a prefix of every larger one: built once per context, whatever tw_inv grows to
-        BJ_HIP(ctx, hipMalloc((void **)&ctx->tw_inv_scaled22, (n / 2) * sizeof(u64)));
-        bj::launch_scale_table(ctx->tw_inv, ctx->tw_inv_scaled22, n / 2, n_inv, ctx->stream);
-    }
+    if (to_tiled)
+        if (int rc = bj::ensure_scaled22(ctx)) return rc;
     for (unsigned c0 = 0; c0 < n_cols; c0 += group) {
         const unsigned nc = n_cols - c0 < group ? n_cols - c0 : group;
         u64 *out = d_out + (size_t)c0 * out_col_stride;

@@ -16,6 +16,7 @@
 namespace bj {
 struct Pipeline;        // prove_async.hip: the two lanes of bj_prove_async
 struct WorkspacePlan;   // workspace_plan.h: the buffers of a proof, in the order it takes them
+struct LaneBytes;       // async_admission.h: what a context holds for proofs, one number per device allocation
 }
 
 struct bj_ctx {
@@ -74,6 +75,9 @@ struct bj_ctx {
     } probes[BJ_MAX_KERNEL_PROBES];
     unsigned probe_n = 0;
     bj::Pipeline *pipe = nullptr;   // bj_prove_async: created on first use, destroyed with the context
+    // a lane of bj_prove_async sets it for one proof that was admitted with a lean workspace (async_admission.h); wins over
+    // BJ_PROOF_LEAN.  -1: the environment decides; 1: the witness and stage-2 oracles keep no evaluations
+    int lean_override = -1;
     // bj_verify and bj_verify_batch keep one each, for bj_verify_kernel_ms and bj_verify_batch_ms: of the last call, events
     // (created on first use) before / after its uploads and after each of its two kernels, and the wall time of its host phase
     struct VerifyTiming {
@@ -106,6 +110,16 @@ int prove_host_copy_first(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_vari
                           const uint64_t *h_public_values, bj_proof **out, int mode);
 void pipeline_destroy(bj_ctx *ctx);              // waits for the asynchronous proofs in flight, ends the lanes
 int pipeline_release_workspace(bj_ctx *ctx);    // bj_ctx_release_workspace on every idle lane
+// Admission of bj_prove_async (async_admission.h).  ctx_held: what the context holds now.  ctx_reserve: grows every part that is
+// smaller than `want` (free and allocate; the tables are filled on the context's stream), so that a proof of that footprint
+// allocates nothing; the context must be idle.  ctx_release_own_workspace: bj_ctx_release_workspace without the lanes.
+// async_footprints (prover.hip): what a lane wants for a bj_prove of `setup`, its oracles resident and lean.
+void ctx_held(const bj_ctx *ctx, LaneBytes *out);
+int ctx_reserve(bj_ctx *ctx, const LaneBytes &want);
+int ctx_release_own_workspace(bj_ctx *ctx);
+int async_footprints(bj_ctx *ctx, const bj_setup *setup, LaneBytes *resident, LaneBytes *lean);
+int stage_witness_elems(bj_ctx *ctx, size_t need);   // the device staging of a host witness holds at least `need` words
+int ensure_scaled22(bj_ctx *ctx);                    // tw_inv_scaled22 exists (tw_inv must reach 2^22)
 int arena_reset(bj_ctx *ctx, size_t need_elems);
 int arena_drop_slabs(bj_ctx *ctx);
 gl::u64 *arena_alloc(bj_ctx *ctx, size_t elems);   // nullptr if the reservation was too small

@@ -28,7 +28,8 @@ struct EnvConfig {
     bool prove_uniform_groups = false;   // BJ_PROVE_UNIFORM_GROUPS: equal groups of G columns, one multi-block absorption run per group (round 4's GROUPING only: its launches absorbed eight columns each)
     bool async_stagger = true;           // BJ_ASYNC_STAGGER=0: bj_prove_async lanes start whenever they are given work (A/B)
     int async_mode = -1;                 // BJ_ASYNC_MODE: what a bj_prove_async lane does while its sibling proves: -1 by witness size (default), 0 bj_prove as is (+ stagger), 1 whole witness first, 2 groups + one hash
-    bool async_debug = false;            // BJ_ASYNC_DEBUG: a bj_prove_async lane reports each proof it ran on stderr
+    bool async_debug = false;            // BJ_ASYNC_DEBUG: a bj_prove_async lane reports each proof it ran on stderr, and each submission the rung it was admitted on
+    size_t hbm_budget_bytes = 0;         // BJ_HBM_BUDGET_BYTES (decimal; 0 or unset: no cap): the most a context and its bj_prove_async lanes may hold in arenas, staging, scratch and tables when a submission is admitted (async_admission.h)
     bool peer_debug = false;             // BJ_PEER_DEBUG: the peer transport traces its bulk exchanges on stderr
     int peer_test_fail_rank = -1;        // BJ_PEER_TEST_FAIL_RANK: test hook, this rank of the peer transport pretends it could not export its mailbox
     unsigned prove_h2d_group = 8;

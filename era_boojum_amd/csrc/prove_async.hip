@@ -9,7 +9,20 @@
 // thread.  bj_prove_async hands the witness to the next lane in turn and returns; the worker runs the ordinary bj_prove on the
 // lane's sub-context.  Nothing is shared between the lanes but the (read-only) setup, so every proof is the bytes bj_prove gives.
 // At most two proofs are in flight: a third submission waits for the lane it is due on.
+//
+// Memory.  A lane is a full context, so two of them beside the parent's own workspace are three proofs' worth of HBM.  Every
+// submission is therefore ADMITTED first (async_admission.h), on the submitting thread: the device's free bytes, capped by
+// BJ_HBM_BUDGET_BYTES, against what the proof's lane wants (the workspace plan of the proof, the witness staging, scratch and
+// tables).  First rung that fits: the lane it is due on with a resident workspace; that lane with a lean workspace (the same bytes,
+// BJ_PROOF_LEAN for this one proof); behind the other lane; the same once the idle parent has released its workspace; refused with
+// BJ_ERR_OOM before a ticket exists.  The lane's whole footprint is reserved at admission, while the lane is idle, so a proof on a
+// lane allocates and frees nothing while its sibling runs, and an out-of-memory is the status of bj_prove_async itself.
+//
+// Tickets.  Every live ticket is in a process-wide registry; bj_proof_wait and bj_proof_poll look the pointer up before they
+// read it, so a ticket that was waited for, was never issued or whose context is gone is BJ_ERR_INVALID_ARG, not a read of freed
+// memory.  Destroying the context frees the proofs and tickets nobody waited for.
 #include "ctx.h"
+#include "async_admission.h"
 
 #include <chrono>
 #include <condition_variable>
@@ -18,11 +31,13 @@
 #include <cstring>
 #include <mutex>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 struct bj_ticket {
     bj_ctx *parent = nullptr;
     unsigned lane = 0;
+    bool lean = false;             // admitted with a lean workspace: the lane proves with lean_override set
     const bj_setup *setup = nullptr;
     const uint64_t *h_variables = nullptr, *h_multiplicities = nullptr;
     std::vector<uint64_t> public_values;
@@ -36,8 +51,13 @@ struct bj_ticket {
 
 namespace bj {
 
+// the tickets bj_prove_async has handed out and nobody has waited for yet
+static std::mutex g_tickets_m;
+static std::unordered_set<const bj_ticket *> g_tickets;
+
 struct Lane {
     bj_ctx *sub = nullptr;
+    LaneBytes held;                // what sub holds, read on the submitting thread while the lane is idle
     hipStream_t stream = nullptr;
     std::thread worker;
     std::mutex m;
@@ -99,11 +119,13 @@ struct Lane {
                 started = std::chrono::steady_clock::now();
                 running = t->setup;
             }
+            sub->lean_override = t->lean ? 1 : -1;
             bj_proof *p = nullptr;
             const uint64_t *pub = t->has_public ? t->public_values.data() : nullptr;
             const bool overlapped = sibling && sibling->busy() && mode != 0;
             const int rc = overlapped ? prove_host_copy_first(sub, t->setup, t->h_variables, t->h_multiplicities, pub, &p, mode)
                                       : bj_prove(sub, t->setup, t->h_variables, t->h_multiplicities, pub, &p);
+            sub->lean_override = -1;
             if (bj::env().async_debug)
                 fprintf(stderr, "[lane %p] mode %d overlapped %d: picked up, ran %.1f ms (stagger %.1f ms)\n", (void *)this, mode, (int)overlapped,
                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - started).count(),
@@ -127,7 +149,6 @@ struct Lane {
 struct Pipeline {
     Lane lanes[2];
     unsigned next = 0;
-    unsigned created = 0;
 };
 
 static int lane_start(bj_ctx *ctx, Lane &L) {
@@ -146,18 +167,30 @@ static int lane_start(bj_ctx *ctx, Lane &L) {
 void pipeline_destroy(bj_ctx *ctx) {
     Pipeline *P = ctx->pipe;
     if (!P) return;
-    for (unsigned i = 0; i < P->created; i++) {      // first every worker ends (nothing of a lane may go while a sibling still proves) ...
-        Lane &L = P->lanes[i];
+    for (Lane &L : P->lanes) {      // first every worker ends (nothing of a lane may go while a sibling still proves) ...
+        if (!L.sub) continue;
         {
             std::unique_lock<std::mutex> lk(L.m);
-            L.cv.wait(lk, [&] { return L.job == nullptr; });   // a proof in flight finishes first (its ticket stays valid)
+            L.cv.wait(lk, [&] { return L.job == nullptr; });   // a proof in flight finishes first
             L.quit = true;
         }
         L.cv.notify_all();
         if (L.worker.joinable()) L.worker.join();
     }
-    for (unsigned i = 0; i < P->created; i++) {      // ... then the contexts go
-        Lane &L = P->lanes[i];
+    {   // ... then the tickets nobody waited for, with their proofs: a later wait or poll finds them in no registry
+        std::lock_guard<std::mutex> lk(g_tickets_m);
+        for (auto it = g_tickets.begin(); it != g_tickets.end();) {
+            bj_ticket *t = const_cast<bj_ticket *>(*it);
+            if (t->parent != ctx) {
+                ++it;
+                continue;
+            }
+            if (t->proof) bj_proof_destroy(t->proof);
+            delete t;
+            it = g_tickets.erase(it);
+        }
+    }
+    for (Lane &L : P->lanes) {      // ... then the contexts go
         if (L.sub) bj_ctx_destroy(L.sub);
         if (L.stream) (void)hipStreamDestroy(L.stream);
     }
@@ -168,13 +201,63 @@ void pipeline_destroy(bj_ctx *ctx) {
 int pipeline_release_workspace(bj_ctx *ctx) {
     Pipeline *P = ctx->pipe;
     if (!P) return BJ_OK;
-    for (unsigned i = 0; i < P->created; i++) {
-        Lane &L = P->lanes[i];
+    for (Lane &L : P->lanes) {
+        if (!L.sub) continue;
         std::unique_lock<std::mutex> lk(L.m);
         if (L.job) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_ctx_release_workspace: an asynchronous proof is running");
         if (int rc = bj_ctx_release_workspace(L.sub)) return fail(ctx, rc, "%s", L.sub->err.c_str());
     }
     return BJ_OK;
+}
+
+// Admission of one submission, on the submitting thread (async_admission.h): decides, starts the lane where it does not exist,
+// waits for it where it is busy and has to grow, and reserves the lane's whole footprint.  A lane that cannot be started or
+// reserved although the decision said it would fit (another process took the bytes) sends the submission down the ladder, so to
+// the lane that exists.  BJ_ERR_OOM with both byte counts in the message where nothing fits.
+static int admit_and_reserve(bj_ctx *ctx, const bj_setup *setup, AdmissionDecision *out) {
+    Pipeline *P = ctx->pipe;
+    AdmissionInput in;
+    if (int rc = async_footprints(ctx, setup, &in.resident, &in.lean)) return rc;
+    in.due = P->next;
+    in.parent_idle = !ctx->in_proof;
+    for (unsigned first = TWO_LANES_RESIDENT;;) {
+        ctx_held(ctx, &in.parent);
+        for (unsigned i = 0; i < 2; i++) {
+            Lane &L = P->lanes[i];
+            in.created[i] = L.sub != nullptr;
+            in.idle[i] = !in.created[i] || !L.busy();
+            if (in.created[i] && in.idle[i]) ctx_held(L.sub, &L.held);   // a busy lane holds what it held when it was given its proof
+            in.held[i] = in.created[i] ? L.held : LaneBytes();
+        }
+        size_t device_total = 0;
+        BJ_HIP(ctx, hipMemGetInfo(&in.device_free, &device_total));
+        in.budget = env().hbm_budget_bytes;
+        const AdmissionDecision d = admit(in, first);
+        if (env().async_debug)
+            fprintf(stderr, "[async %p] admission: %s on lane %u%s, reserves %zu bytes of %zu available (budget %zu, held %zu)\n", (void *)ctx,
+                    admission_name(d.rung), d.lane, d.lean ? " (lean)" : "", d.reserve_bytes, d.available, in.budget, in.held_total());
+        if (d.rung == REFUSE)
+            return fail(ctx, BJ_ERR_OOM, "bj_prove_async: the smallest plan (one lane, lean workspace) needs %zu more bytes, %zu bytes are available%s",
+                        d.reserve_bytes, d.available, in.budget ? " under BJ_HBM_BUDGET_BYTES" : "");
+        if (d.release_parent)
+            if (int rc = ctx_release_own_workspace(ctx)) return rc;
+        Lane &L = P->lanes[d.lane];
+        int rc = L.sub ? BJ_OK : lane_start(ctx, L);
+        if (!rc) {
+            {
+                std::unique_lock<std::mutex> lk(L.m);
+                L.cv.wait(lk, [&] { return L.job == nullptr; });   // the lane's workspace is its proof's until the proof is done
+            }
+            if ((rc = ctx_reserve(L.sub, d.want))) fail(ctx, rc, "%s", L.sub->err.c_str());
+            ctx_held(L.sub, &L.held);
+        }
+        if (!rc) {
+            *out = d;
+            return BJ_OK;
+        }
+        if (rc != BJ_ERR_OOM && rc != BJ_ERR_HIP) return rc;
+        first = d.rung + 1;   // the next rung down, with what is held now
+    }
 }
 
 }  // namespace bj
@@ -198,15 +281,14 @@ int bj_prove_async(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_variabl
         ctx->pipe->lanes[1].sibling = &ctx->pipe->lanes[0];
     }
     bj::Pipeline *P = ctx->pipe;
-    const unsigned li = P->next;
-    bj::Lane &L = P->lanes[li];
-    if (li >= P->created) {
-        if (int rc = bj::lane_start(ctx, L)) return rc;
-        P->created = li + 1;
-    }
+    bj::Lane *L = nullptr;
+    bj::AdmissionDecision d;
+    if (int rc = bj::admit_and_reserve(ctx, setup, &d)) return rc;   // no ticket exists yet: an out-of-memory is this call's status
+    L = &P->lanes[d.lane];
     bj_ticket *t = new bj_ticket();
     t->parent = ctx;
-    t->lane = li;
+    t->lane = d.lane;
+    t->lean = d.lean;
     t->setup = setup;
     t->h_variables = h_variables;
     t->h_multiplicities = h_multiplicities;
@@ -215,18 +297,30 @@ int bj_prove_async(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_variabl
         t->has_public = true;
     }
     {
-        std::unique_lock<std::mutex> lk(L.m);
-        L.cv.wait(lk, [&] { return L.job == nullptr; });   // at most two in flight: the proof this lane still runs comes first
-        L.job = t;
+        std::lock_guard<std::mutex> lk(bj::g_tickets_m);
+        bj::g_tickets.insert(t);
     }
-    L.cv.notify_all();
-    P->next = (li + 1) % 2;
+    {
+        std::unique_lock<std::mutex> lk(L->m);
+        L->cv.wait(lk, [&] { return L->job == nullptr; });   // at most two in flight (admission has waited for a lane it had to grow)
+        L->job = t;
+    }
+    L->cv.notify_all();
+    P->next = d.lane ^ 1;
     *out = t;
     return BJ_OK;
 }
 
+// A ticket that is in the registry is taken out of it by the one wait that gets it: the pointer of a ticket that was waited for,
+// was never issued or went with its context is refused before anything is read through it.
 int bj_proof_wait(bj_ticket *t, bj_proof **out) {
+    if (out) *out = nullptr;
     if (!t) return BJ_ERR_INVALID_ARG;
+    {
+        std::lock_guard<std::mutex> lk(bj::g_tickets_m);
+        if (!bj::g_tickets.erase(t))
+            return bj::fail(nullptr, BJ_ERR_INVALID_ARG, "bj_proof_wait: no live ticket (waited for already, never issued, or its context was destroyed)");
+    }
     bj_ctx *ctx = t->parent;
     bj::Lane &L = ctx->pipe->lanes[t->lane];
     {
@@ -245,6 +339,9 @@ int bj_proof_wait(bj_ticket *t, bj_proof **out) {
 
 int bj_proof_poll(const bj_ticket *t) {
     if (!t) return BJ_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> reg(bj::g_tickets_m);   // held while the ticket is read: no wait frees it meanwhile
+    if (!bj::g_tickets.count(t))
+        return bj::fail(nullptr, BJ_ERR_INVALID_ARG, "bj_proof_poll: no live ticket (waited for already, never issued, or its context was destroyed)");
     bj::Lane &L = t->parent->pipe->lanes[t->lane];
     std::lock_guard<std::mutex> lk(L.m);
     return t->done ? 1 : 0;

@@ -9,6 +9,7 @@
 // hasher + Poseidon2 transcript, PoW off — the configuration of the reference's SHA-256 bench
 // (src/gadgets/sha256/mod.rs:284-375).
 #include "ctx.h"
+#include "async_admission.h"
 #include "host_transcript.hpp"
 #include "fri_types.h"
 #include "gate_program.h"
@@ -229,7 +230,9 @@ struct Proving {
         Qe = Q / sh.world;
         VW = L.multiplicity();
         nW = L.widths[bj::ORACLE_WITNESS], nS2 = L.widths[bj::ORACLE_STAGE2];
-        const bool lean_p = bj::env().proof_lean && sh.world == 1;   // BJ_PROOF_LEAN: the witness and stage-2 oracles keep no evaluations
+        // BJ_PROOF_LEAN, or the lane of bj_prove_async that admitted this proof with a lean workspace (ctx.h: lean_override): the
+        // witness and stage-2 oracles keep no evaluations
+        const bool lean_p = (c->lean_override >= 0 ? c->lean_override != 0 : bj::env().proof_lean) && sh.world == 1;
         oracle[bj::ORACLE_WITNESS] = bj::oracle_of(nW, n, Ln, !lean_p);
         oracle[bj::ORACLE_STAGE2] = bj::oracle_of(nS2, n, Ln, !lean_p);
         oracle[bj::ORACLE_QUOTIENT] = bj::oracle_of(2 * q, n, N, true);   // always resident, on the FRI domain; its monomials: T's chunk layout
@@ -289,19 +292,28 @@ std::vector<u64> e2_powers(const u64 *x, size_t count) {
     return out;
 }
 
+// The shape of the workspace (workspace_plan.h) of a proof of S: from the setup, how the witness arrives, whether the witness and
+// stage-2 oracles keep their evaluations, and the FRI schedule.  One function behind the reservation of a proof and the admission
+// of bj_prove_async, which asks before a proof exists.
+bj::WorkspaceShape shape_of(const bj_setup *S, bool mult_in_arena, unsigned host_witness, bool lean_oracles, uint32_t new_pow, const uint32_t *sched,
+                            size_t sched_len, size_t num_queries) {
+    const bj::ProofLayout &L = S->layout;
+    const unsigned alpha_terms = L.n_lookup_terms + S->gates.n_spec_terms + S->gates.n_general_terms + 1 + L.n_chunks;
+    bj::WorkspaceShape shape = bj::workspace_shape(L, S->sh.world, S->tiled, alpha_terms, S->pub_cols.data(), S->pub_rows.data(), S->pub_cols.size(),
+                                                   mult_in_arena, host_witness, new_pow != 0, sched, sched_len, num_queries);
+    shape.lean = !S->oracle().resident;
+    shape.lean_oracles = lean_oracles;
+    return shape;
+}
+
 // Reads the setup's parameters and the sizes.  Adds the FRI schedule and the workspace plan; resets the context's arena to one
 // reservation for every buffer of the proof (a context that has seen a larger proof keeps its size); adds proof->ws_reserved.
 int Proving::reserve_workspace() {
     if (int rc = bj_fri_schedule(S->security, S->cap_size, S->pow_bits, S->log_fri, log_n, &new_pow, &num_queries, sched, &sched_len, &final_degree))
         return bj::fail(ctx, rc, "bj_prove: compute_fri_schedule failed");
-    const unsigned alpha_terms = L.n_lookup_terms + S->gates.n_spec_terms + S->gates.n_general_terms + 1 + L.n_chunks;
-    bj::WorkspaceShape shape = bj::workspace_shape(L, sh.world, S->tiled, alpha_terms, S->pub_cols.data(), S->pub_rows.data(), S->pub_cols.size(),
-                                                   count_mult && !d_multiplicities,
-                                                   !hw ? bj::WS_HOST_NONE : absorb ? bj::WS_HOST_ABSORBING : bj::WS_HOST_NOT_ABSORBING, new_pow != 0,
-                                                   sched, sched_len, num_queries);
-    shape.lean = !oracle[bj::ORACLE_SETUP].resident;
-    shape.lean_oracles = !oracle[bj::ORACLE_WITNESS].resident;
-    plan = bj::workspace_plan(shape);
+    plan = bj::workspace_plan(shape_of(S, count_mult && !d_multiplicities,
+                                       !hw ? bj::WS_HOST_NONE : absorb ? bj::WS_HOST_ABSORBING : bj::WS_HOST_NOT_ABSORBING,
+                                       !oracle[bj::ORACLE_WITNESS].resident, new_pow, sched, sched_len, num_queries));
     if (int rc = bj::arena_reset(ctx, std::max(plan.total(), ctx->arena_learned))) return rc;
     proof->ws_reserved = ctx->arena_elems * 8;
     return BJ_OK;
@@ -1080,14 +1092,7 @@ extern "C" {
 
 static int stage_witness(bj_ctx *ctx, const bj_setup *S) {
     const size_t n = (size_t)1 << S->log_n, need = (size_t)(S->layout.multiplicity() + 1) * n;   // the multiplicity column behind the others
-    if (ctx->wit_stage_elems < need) {   // device staging of the witness, kept for the next proof (no 3 GB hipMalloc per proof)
-        if (ctx->wit_stage) BJ_HIP(ctx, hipFree(ctx->wit_stage));
-        ctx->wit_stage = nullptr;
-        ctx->wit_stage_elems = 0;
-        BJ_HIP(ctx, hipMalloc((void **)&ctx->wit_stage, need * 8));
-        ctx->wit_stage_elems = need;
-    }
-    return BJ_OK;
+    return bj::stage_witness_elems(ctx, need);
 }
 
 int bj_prove_dev(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, const uint64_t *d_multiplicities,
@@ -1110,6 +1115,22 @@ int bj_prove(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_variables, const 
 }  // extern "C"
 
 namespace bj {
+// What a lane of bj_prove_async wants for a proof of S from a host witness (async_admission.h), its witness and stage-2 oracles
+// resident and lean.  The lane may take the proof as bj_prove or witness first (prove_host_copy_first): the plan of bj_prove where
+// it absorbs the column groups holds every buffer of the others and the capacity words, so that one is reserved.  Where
+// BJ_PROOF_LEAN makes every proof lean, both are the lean footprint.
+int async_footprints(bj_ctx *ctx, const bj_setup *S, LaneBytes *resident, LaneBytes *lean) {
+    uint32_t sched[32], new_pow = 0;
+    size_t sched_len = 0, num_queries = 0, final_degree = 0;
+    if (int rc = bj_fri_schedule(S->security, S->cap_size, S->pow_bits, S->log_fri, S->log_n, &new_pow, &num_queries, sched, &sched_len, &final_degree))
+        return fail(ctx, rc, "bj_prove_async: compute_fri_schedule failed");
+    const bool absorbs = (S->hasher == BJ_HASHER_POSEIDON2 || S->hasher == BJ_HASHER_POSEIDON) && !env().prove_no_absorb;
+    const WorkspaceShape shape = shape_of(S, false, absorbs ? WS_HOST_ABSORBING : WS_HOST_NOT_ABSORBING, false, new_pow, sched, sched_len, num_queries);
+    *lean = lane_footprint(shape, true);
+    *resident = env().proof_lean ? *lean : lane_footprint(shape, false);
+    return BJ_OK;
+}
+
 // bj_prove for a lane of bj_prove_async whose sibling is busy: the whole witness crosses PCIe first (one copy on the proof's
 // stream, while the other lane's proof has the CUs), then the proof runs as on a resident witness — one leaf kernel instead of
 // the group-wise absorption that bj_prove uses to hide the transfer behind its own hashing.  Same bytes either way.

@@ -223,27 +223,31 @@ lookup_polys_kernel(const u64 *lvars, size_t var_stride, const u64 *table_id, co
     constexpr unsigned LK_GROUP = 9;
     for (unsigned g0 = 0; g0 <= reps; g0 += LK_GROUP) {
         const unsigned cnt = (reps + 1 - g0) < LK_GROUP ? (reps + 1 - g0) : LK_GROUP;
+        // both loops unroll in full (a guard, no early exit), so den and pre are indexed by constants and stay in registers: indexed
+        // by a loop counter they lived in scratch memory, 304 bytes a lane, which the runtime reserves for every wave slot of every
+        // hardware queue that runs the kernel: about 165 MB of HBM per bj_prove_async lane that no plan knew of
         gl::e2 den[LK_GROUP], pre[LK_GROUP], run{1, 0};
 #pragma unroll
         for (unsigned k = 0; k < LK_GROUP; k++) {
-            if (k >= cnt) break;
-            const unsigned i = g0 + k;                       // i == reps -> the table aggregate (B)
-            gl::e2 acc = a.beta;
-            if (i < reps) {
-                for (unsigned j = 0; j < cps; j++) {
-                    u64 v = gl::canon(lvars[(size_t)(i * cps + j) * var_stride + r]);
-                    acc = gl::e2_add(acc, gl::e2_mul_base(a.gpow[j], v));
+            if (k < cnt) {
+                const unsigned i = g0 + k;                       // i == reps -> the table aggregate (B)
+                gl::e2 acc = a.beta;
+                if (i < reps) {
+                    for (unsigned j = 0; j < cps; j++) {
+                        u64 v = gl::canon(lvars[(size_t)(i * cps + j) * var_stride + r]);
+                        acc = gl::e2_add(acc, gl::e2_mul_base(a.gpow[j], v));
+                    }
+                    if (table_id) acc = gl::e2_add(acc, gl::e2_mul_base(a.gpow[w], tid));
+                } else {
+                    for (unsigned j = 0; j <= w; j++) {
+                        u64 v = gl::canon(tables[(size_t)j * tab_stride + r]);
+                        acc = gl::e2_add(acc, gl::e2_mul_base(a.gpow[j], v));
+                    }
                 }
-                if (table_id) acc = gl::e2_add(acc, gl::e2_mul_base(a.gpow[w], tid));
-            } else {
-                for (unsigned j = 0; j <= w; j++) {
-                    u64 v = gl::canon(tables[(size_t)j * tab_stride + r]);
-                    acc = gl::e2_add(acc, gl::e2_mul_base(a.gpow[j], v));
-                }
+                den[k] = acc;
+                pre[k] = run;
+                run = gl::e2_mul(run, acc);
             }
-            den[k] = acc;
-            pre[k] = run;
-            run = gl::e2_mul(run, acc);
         }
         gl::e2 inv_run = gl::e2_inv_chain(run);
 #pragma unroll

@@ -978,15 +978,30 @@ int bj_verify_batch_ms(bj_ctx *ctx, float *host_ms, float *upload_ms, float *ope
  * witness; every proof is byte for byte what bj_prove returns.  At most two proofs are in flight — a third submission blocks
  * until the lane it is due on is free.  h_variables / h_multiplicities (pinned host memory for full PCIe speed) must stay
  * valid and unchanged until bj_proof_wait returns (h_multiplicities NULL as for bj_prove: each lane counts the column in its own
- * scratch); h_public_values is copied.  Errors of the proof (unsatisfied witness, out
- * of memory) come back from bj_proof_wait with the text in bj_last_error(ctx).  Every ticket must be waited for exactly once.
- * Memory: each lane holds a workspace of its own (bj_proof_workspace_bytes); bj_ctx_release_workspace frees the lanes' too.
+ * scratch); h_public_values is copied.  Errors of the proof (unsatisfied witness) come back from bj_proof_wait with the text in
+ * bj_last_error(ctx).
+ * Memory: each lane is a context of its own — workspace arena, witness staging, scratch, twiddle tables — so two lanes beside a
+ * parent that also runs bj_prove hold THREE proofs' worth of HBM (about 3 x 65 GB at 2^22 rows of the bench circuit).  Every
+ * submission is therefore admitted first, on the calling thread, against the bytes available: the device's free bytes
+ * (hipMemGetInfo), capped by BJ_HBM_BUDGET_BYTES (decimal, 0 or unset: no cap; read with the other switches, re-read by
+ * bj_env_reload) less what this context and its lanes hold.  The first rung that fits is taken: (1) the lane the submission is
+ * due on, resident workspace; (2) that lane with a lean workspace — BJ_PROOF_LEAN for this one proof, the same bytes, and
+ * bj_proof_workspace_bytes of that proof reports the lean plan's reservation; (3) behind the other lane, which exists: one proof
+ * at a time; (4) the same after the idle parent context has given back its own workspace (as bj_ctx_release_workspace does; its
+ * next bj_prove reserves again); (5) BJ_ERR_OOM from bj_prove_async itself, no ticket, bj_last_error naming the bytes the smallest
+ * plan needs and the bytes available.  The lane's whole footprint is reserved at admission, so a proof on a lane allocates nothing
+ * while its sibling runs and bj_proof_wait does not report a workspace that did not fit.  BJ_ASYNC_DEBUG prints the rung taken.
+ * bj_ctx_release_workspace frees the lanes' workspaces too.
+ * Tickets: a ticket is waited for exactly once, and that is enforced: bj_proof_wait and bj_proof_poll look the pointer up among
+ * the live tickets of the process before they read it, and return BJ_ERR_INVALID_ARG for one that was waited for already, was
+ * never issued, or whose context was destroyed (bj_ctx_destroy lets the proofs in flight finish, then frees the proofs and
+ * tickets nobody waited for).
  * Single-device setups only (a sharded proof is a collective: its ranks are already concurrent). */
 typedef struct bj_ticket bj_ticket;
 int bj_prove_async(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_variables, const uint64_t *h_multiplicities,
                    const uint64_t *h_public_values, bj_ticket **out);
 int bj_proof_wait(bj_ticket *ticket, bj_proof **out);
-int bj_proof_poll(const bj_ticket *ticket); /* 1: complete (bj_proof_wait will not block), 0: still running */
+int bj_proof_poll(const bj_ticket *ticket); /* 1: complete (bj_proof_wait will not block), 0: still running, BJ_ERR_INVALID_ARG: no live ticket */
 void bj_proof_destroy(bj_proof *p);
 /* Flat little-endian u64 serialisation of Proof (proof.rs:121-136); layout documented in era_boojum_amd/proof_format.py:
  * header | schedule | public inputs | witness / stage-2 / quotient caps | values at z, z*omega, 0 | FRI caps |
@@ -1013,7 +1028,8 @@ int bj_proof_comm_stats(const bj_proof *p, float *ms_in_collectives, size_t *cal
 /* Workspace of the proof: bytes the context had reserved for it (one bump-allocated arena, sized from the setup's geometry
  * before the first kernel), the high-water mark the proof reached, and the number of overflow slabs it had to take because the
  * reservation was too small (0 on every configuration the test suite proves; a slab is a hipMalloc in the middle of a proof, and
- * the context reserves the learned size from the next proof on).  With bj_setup_device_bytes: what a rank holds. */
+ * the context reserves the learned size from the next proof on).  With bj_setup_device_bytes: what a rank holds.
+ * A proof that a lane of bj_prove_async ran with a lean workspace (admission, above) reports the lean plan's reservation. */
 int bj_proof_workspace_bytes(const bj_proof *p, size_t *reserved, size_t *high_water, size_t *overflow_slabs);
 
 #ifdef __cplusplus

@@ -531,8 +531,10 @@ impl<P: crate::field::traits::field_like::PrimeFieldLikeVectorized<Base = F>, CF
     ///     let mut prev = cs.prove_hip_async(&ctx, &setup, ws[0].clone());
     ///     for w in &ws[1..] { let cur = cs.prove_hip_async(&ctx, &setup, w.clone()); proofs.push(prev.wait(cfg)); prev = cur; }
     /// The next proof's PCIe transfer and first transforms run under the previous proof's latency-bound tail; every proof is the
-    /// bytes `prove_hip` returns.  The ticket owns the flattened witness (the library reads it until `wait` returns).
-    pub fn prove_hip_async<'a>(&self, ctx: &'a HipCtx, setup: &HipSetup, witness_set: WitnessSet<F>) -> HipTicket<'a> {
+    /// bytes `prove_hip` returns.  The ticket owns the flattened witness (the library reads it until `wait` returns) and borrows
+    /// the context AND the setup: a lane reads the setup's columns until the proof is done, so neither may be dropped before it.
+    /// `BJ_ERR_OOM` here (nothing fits, not even one lane with a lean workspace) panics in `check` before a ticket exists.
+    pub fn prove_hip_async<'a>(&self, ctx: &'a HipCtx, setup: &'a HipSetup, witness_set: WitnessSet<F>) -> HipTicket<'a> {
         let WitnessSet { public_inputs_values, public_inputs_with_locations, variables, witness, multiplicities } = witness_set;
         assert_eq!(public_inputs_values.len(), public_inputs_with_locations.len());
         assert_eq!(variables.len(), setup.num_vars);
@@ -550,13 +552,14 @@ impl<P: crate::field::traits::field_like::PrimeFieldLikeVectorized<Base = F>, CF
                 &mut raw,
             )
         });
-        HipTicket { ctx, raw, _vars: vars, _mult: mult }
+        HipTicket { ctx, _setup: setup, raw, _vars: vars, _mult: mult }
     }
 }
 
 /// A proof in flight (`bj_ticket`).  Dropping it without `wait` waits for the proof and discards it.
 pub struct HipTicket<'a> {
     ctx: &'a HipCtx,
+    _setup: &'a HipSetup,
     raw: *mut bj_ticket,
     _vars: Vec<u64>,
     _mult: Vec<u64>,
