@@ -5,6 +5,7 @@ import pytest
 
 import oracle as O
 from gpu_util import DevBuf, ctx, rand_gl
+from poseidon2_tree_cases import stream_carry_words as _ext_layer_carry_words     # the model of the planes, shared with the tree-kernel tests
 
 pytestmark = pytest.mark.gpu
 
@@ -228,20 +229,6 @@ def test_permutation_takes_the_rare_branches_of_its_products():
         ctx().poseidon2_permute(d.ptr, batch.shape[0])
         assert np.array_equal(d.get(batch.shape), np.tile(want, (reps, 1)))
         d.free()
-
-
-def _ext_layer_carry_words(state, rc):
-    """Which output words of the first external layer wrap in the fold of their low / high plane sums (tools/gen_p2_asm.py
-    `combine`: T = A + B.hi * EPS, then T.hi + B.lo >= 2^32) — a model of the planes, not of the field arithmetic."""
-    M = _ext_matrix()
-    hit = []
-    for i in range(12):
-        A = sum(M[i][j] * (state[j] & 0xFFFFFFFF) for j in range(12)) + (rc[i] & 0xFFFFFFFF)
-        B = sum(M[i][j] * (state[j] >> 32) for j in range(12)) + (rc[i] >> 32)
-        T = A + (B >> 32) * 0xFFFFFFFF
-        if (T >> 32) + (B & 0xFFFFFFFF) >= 1 << 32:
-            hit.append(i)
-    return hit
 
 
 def test_permutation_takes_the_out_of_line_carry_of_the_linear_layers():

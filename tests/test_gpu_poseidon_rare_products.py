@@ -13,7 +13,9 @@ asserted on the emulated sequence (tests/test_poseidon_rare_products.py).
 
 Not reached here: class 1 at x2*x (no known construction, ~2^-64 at random); rounds >= 2 of leaf and node hashing (capacity
 words fixed at 0 leave no solve through two S-box layers: the same inlined permutation is driven at every round through
-poseidon_permute).  The group-wise absorb kernels (poseidon1_ and poseidon2_leaves_absorb_kernel) are reached in
+poseidon_permute).  Poseidon2's tree kernels (BJ_HASHER_POSEIDON2: leaves, chunked leaves and nodes, per lane and lane-parallel,
+each with the permutation inlined or restated on its own) are driven at constructed first-round inputs in
+tests/test_gpu_poseidon2_tree_kernels.py; the tree test below is BJ_HASHER_POSEIDON (v1) only.  The group-wise absorb kernels (poseidon1_ and poseidon2_leaves_absorb_kernel) are reached in
 tests/test_gpu_prover_only_kernels.py: bj_merkle_leaves_absorb with first = 0, last = 1 takes the capacity words from the
 caller, so the constructed twelve-word states of the permutation tests go through both kernels at every round, on lone lanes
 and whole waves."""
