@@ -1,335 +1,15 @@
-// C-ABI layer of libboojum_hip.so: context management + argument validation + kernel orchestration.
+// C-ABI layer of libboojum_hip.so: the entry points of the context, the NTT family, the Merkle trees, the proof of work and the
+// FRI fold, each with its argument validation and kernel orchestration (the context's internals: ctx.hip).
 // Public contract: include/boojum_hip.h.  No CPU fallback anywhere in this file: every entry point either
 // enqueues HIP work on the context's device or returns an error.
 #include "ctx.h"
-#include "async_admission.h"
 #include "ntt_plan.h"
-#include "workspace_plan.h"
 
 #include <hip/hip_runtime.h>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <string>
-#include <vector>
 
 using gl::u64;
 
-namespace bj {
-
-// message of the last failed call that has no context (bj_vk_create), per host thread: bj_last_error(NULL)
-static std::string &thread_error() {
-    static thread_local std::string e;
-    return e;
-}
-
-int fail(bj_ctx *ctx, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (ctx) ctx->err = buf;
-    else thread_error() = buf;
-    return code;
-}
-
-int bind(bj_ctx *ctx) {
-    if (!ctx) return BJ_ERR_INVALID_ARG;
-    BJ_HIP(ctx, hipSetDevice(ctx->device));
-    return BJ_OK;
-}
-
-int ensure_twiddles(bj_ctx *ctx, unsigned log_n, bool inverse) {
-    u64 *&tab = inverse ? ctx->tw_inv : ctx->tw_fwd;
-    unsigned &have = inverse ? ctx->tw_inv_log : ctx->tw_fwd_log;
-    if (log_n <= have && tab) return BJ_OK;
-    if (log_n == 0) log_n = 1;
-    if (tab) {
-        BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        BJ_HIP(ctx, hipFree(tab));
-        tab = nullptr;
-        have = 0;
-    }
-    size_t half = (size_t)1 << (log_n - 1);
-    BJ_HIP(ctx, hipMalloc((void **)&tab, half * sizeof(u64)));
-    bj::launch_twiddles(tab, log_n, inverse, ctx->stream);
-    BJ_CHECK_LAUNCH(ctx);
-    have = log_n;
-    return BJ_OK;
-}
-
-int ensure_scratch(bj_ctx *ctx, size_t elems) {
-    if (elems <= ctx->scratch_elems) return BJ_OK;
-    if (ctx->d_scratch) {
-        BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        BJ_HIP(ctx, hipFree(ctx->d_scratch));
-        ctx->d_scratch = nullptr;
-        ctx->scratch_elems = 0;
-    }
-    BJ_HIP(ctx, hipMalloc((void **)&ctx->d_scratch, elems * sizeof(u64)));
-    ctx->scratch_elems = elems;
-    return BJ_OK;
-}
-
-int arena_drop_slabs(bj_ctx *ctx) {
-    if (ctx->arena_slabs.empty()) return BJ_OK;
-    BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (auto &sl : ctx->arena_slabs) (void)hipFree(sl.first);
-    ctx->arena_slabs.clear();
-    ctx->slab_off = 0;
-    return BJ_OK;
-}
-int arena_reset(bj_ctx *ctx, size_t need_elems) {
-    ctx->arena_off = 0;
-    ctx->arena_high_water = 0;
-    if (int rc = arena_drop_slabs(ctx)) return rc;
-    if (need_elems <= ctx->arena_elems) return BJ_OK;
-    if (ctx->arena) {
-        BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        BJ_HIP(ctx, hipFree(ctx->arena));
-        ctx->arena = nullptr;
-        ctx->arena_elems = 0;
-    }
-    BJ_HIP(ctx, hipMalloc((void **)&ctx->arena, need_elems * sizeof(u64)));
-    ctx->arena_elems = need_elems;
-    return BJ_OK;
-}
-
-constexpr size_t RING_BYTES = (size_t)1 << 20, RING_MAX_BLOCK = (size_t)128 << 10;
-
-int stage_witness_elems(bj_ctx *ctx, size_t need) {
-    if (ctx->wit_stage_elems >= need) return BJ_OK;   // kept for the next proof (no 3 GB hipMalloc per proof)
-    if (ctx->wit_stage) BJ_HIP(ctx, hipFree(ctx->wit_stage));
-    ctx->wit_stage = nullptr;
-    ctx->wit_stage_elems = 0;
-    BJ_HIP(ctx, hipMalloc((void **)&ctx->wit_stage, need * 8));
-    ctx->wit_stage_elems = need;
-    return BJ_OK;
-}
-
-int ensure_scaled22(bj_ctx *ctx) {   // a table for 2^22 is a prefix of every larger one: built once per context, whatever tw_inv grows to
-    if (ctx->tw_inv_scaled22) return BJ_OK;
-    const size_t n = (size_t)1 << 22;
-    if (!ctx->tw_inv || ctx->tw_inv_log < 22) return fail(ctx, BJ_ERR_HIP, "internal error: the scaled twiddle table before the inverse twiddles of 2^22");
-    BJ_HIP(ctx, hipMalloc((void **)&ctx->tw_inv_scaled22, (n / 2) * sizeof(u64)));
-    bj::launch_scale_table(ctx->tw_inv, ctx->tw_inv_scaled22, n / 2, gl::inv(gl::canon((u64)n % gl::P)), ctx->stream);
-    BJ_CHECK_LAUNCH(ctx);
-    return BJ_OK;
-}
-
-void ctx_held(const bj_ctx *ctx, LaneBytes *out) {
-    *out = LaneBytes();
-    size_t arena = ctx->arena_elems;
-    for (const auto &sl : ctx->arena_slabs) arena += sl.second;
-    out->part[LANE_ARENA] = arena * 8;
-    out->part[LANE_STAGING] = ctx->wit_stage_elems * 8;
-    out->part[LANE_SCRATCH] = ctx->scratch_elems * 8;
-    out->part[LANE_TW_FWD] = ctx->tw_fwd ? ((size_t)1 << (ctx->tw_fwd_log - 1)) * 8 : 0;
-    out->part[LANE_TW_INV] = ctx->tw_inv ? ((size_t)1 << (ctx->tw_inv_log - 1)) * 8 : 0;
-    out->part[LANE_TW_SCALED22] = ctx->tw_inv_scaled22 ? ((size_t)1 << 21) * 8 : 0;
-}
-
-int ctx_reserve(bj_ctx *ctx, const LaneBytes &want) {
-    if (int rc = bind(ctx)) return rc;
-    if (ctx->in_proof) return fail(ctx, BJ_ERR_INVALID_ARG, "internal error: a workspace reserved under a running proof");
-    auto tw_log = [](size_t bytes) {   // a table of 2^(k-1) words serves 2^k points
-        unsigned k = 1;
-        while (((size_t)8 << (k - 1)) < bytes) k++;
-        return k;
-    };
-    const size_t arena = want.part[LANE_ARENA] / 8;
-    if (int rc = arena_reset(ctx, arena > ctx->arena_learned ? arena : ctx->arena_learned)) return rc;
-    if (int rc = stage_witness_elems(ctx, want.part[LANE_STAGING] / 8)) return rc;
-    if (int rc = ensure_scratch(ctx, want.part[LANE_SCRATCH] / 8)) return rc;
-    if (want.part[LANE_TW_FWD])
-        if (int rc = ensure_twiddles(ctx, tw_log(want.part[LANE_TW_FWD]), false)) return rc;
-    if (want.part[LANE_TW_INV])
-        if (int rc = ensure_twiddles(ctx, tw_log(want.part[LANE_TW_INV]), true)) return rc;
-    if (want.part[LANE_TW_SCALED22])
-        if (int rc = ensure_scaled22(ctx)) return rc;
-    // the small blocks a proof would otherwise create on first use: the pinned ring of the host -> device blocks, the copy stream
-    if (!ctx->h_ring) BJ_HIP(ctx, hipHostMalloc((void **)&ctx->h_ring, RING_BYTES, hipHostMallocDefault));
-    if (!ctx->copy_stream) BJ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    return BJ_OK;
-}
-
-int ctx_release_own_workspace(bj_ctx *ctx) {
-    BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->copy_stream) BJ_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-    if (int rc = arena_drop_slabs(ctx)) return rc;
-    if (ctx->arena) BJ_HIP(ctx, hipFree(ctx->arena));
-    ctx->arena = nullptr;
-    ctx->arena_elems = ctx->arena_off = 0;
-    ctx->arena_learned = 0;
-    if (ctx->d_scratch) BJ_HIP(ctx, hipFree(ctx->d_scratch));
-    ctx->d_scratch = nullptr;
-    ctx->scratch_elems = 0;
-    if (ctx->wit_stage) BJ_HIP(ctx, hipFree(ctx->wit_stage));
-    ctx->wit_stage = nullptr;
-    ctx->wit_stage_elems = 0;
-    return BJ_OK;
-}
-
-int TmpBuf::alloc(bj_ctx *c, size_t words) {
-    ctx = c;
-    from_arena = false;
-    if (c->in_proof && (p = arena_alloc(c, words))) {
-        from_arena = true;
-        return BJ_OK;
-    }
-    if (hipMalloc((void **)&p, words ? words * 8 : 8) != hipSuccess) {
-        p = nullptr;
-        return fail(c, BJ_ERR_OOM, "out of device memory (%zu MiB)", words * 8 >> 20);
-    }
-    return BJ_OK;
-}
-int TmpBuf::take(bj_ctx *c, unsigned id, size_t words) {
-    const WorkspacePlan *plan = c->ws_plan;
-    if (!plan) return alloc(c, words);
-    while (c->ws_next < plan->entries.size() && !plan->entries[c->ws_next].exact) c->ws_next++;
-    if (c->ws_next == plan->entries.size())
-        return fail(c, BJ_ERR_HIP, "bj_prove: internal error: the workspace plan ends before %s", ws_name(id));
-    const WorkspaceEntry &e = plan->entries[c->ws_next];
-    if (e.id != id) return fail(c, BJ_ERR_HIP, "bj_prove: internal error: the workspace plan holds %s where the proof takes %s", ws_name(e.id), ws_name(id));
-    if (words && words != e.words)
-        return fail(c, BJ_ERR_HIP, "bj_prove: internal error: %s is planned with %zu words and taken with %zu", ws_name(id), e.words, words);
-    c->ws_next++;
-    ctx = c;
-    if (!(p = arena_alloc(c, e.words))) return fail(c, BJ_ERR_OOM, "workspace reservation too small for %zu MiB", e.words * 8 >> 20);
-    from_arena = true;   // never freed: a planned buffer may outlive the scope that took it
-    return BJ_OK;
-}
-TmpBuf::~TmpBuf() {
-    if (!p || from_arena) return;
-    if (drain) (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(p);
-}
-int workspace_all_taken(bj_ctx *ctx) {
-    const WorkspacePlan *plan = ctx->ws_plan;
-    for (size_t i = ctx->ws_next; plan && i < plan->entries.size(); i++)
-        if (plan->entries[i].exact)
-            return fail(ctx, BJ_ERR_HIP, "bj_prove: internal error: the proof ends without taking %s of its workspace plan", ws_name(plan->entries[i].id));
-    return BJ_OK;
-}
-
-int h2d_async(bj_ctx *ctx, void *d_dst, const void *h_src, size_t bytes) {
-    if (int rc = bind(ctx)) return rc;
-    if (!bytes) return BJ_OK;
-    if (!d_dst || !h_src) return fail(ctx, BJ_ERR_INVALID_ARG, "h2d_async: null pointer");
-    if (bytes > RING_MAX_BLOCK) return bj_memcpy_h2d(ctx, d_dst, h_src, bytes);
-    if (!ctx->h_ring) BJ_HIP(ctx, hipHostMalloc((void **)&ctx->h_ring, RING_BYTES, hipHostMallocDefault));
-    const size_t slot = (bytes + 63) & ~(size_t)63;
-    if (ctx->ring_off + slot > RING_BYTES) {   // wrap: the skipped tail counts as in flight, or a reset at a mid-ring offset
-        ctx->ring_inflight += RING_BYTES - ctx->ring_off;   // would let the next lap overwrite copies still queued
-        ctx->ring_off = 0;
-    }
-    if (ctx->ring_inflight + slot > RING_BYTES) {   // the ring wrapped onto copies that may not have run yet
-        BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->ring_inflight = 0;
-    }
-    std::memcpy(ctx->h_ring + ctx->ring_off, h_src, bytes);
-    BJ_HIP(ctx, hipMemcpyAsync(d_dst, ctx->h_ring + ctx->ring_off, bytes, hipMemcpyHostToDevice, ctx->stream));
-    ctx->ring_off += slot;
-    ctx->ring_inflight += slot;
-    return BJ_OK;
-}
-
-u64 *arena_alloc(bj_ctx *ctx, size_t elems) {
-    const size_t start = (ctx->arena_off + 63) & ~(size_t)63;   // 512-byte alignment
-    if (ctx->arena_slabs.empty() && start + elems <= ctx->arena_elems) {
-        ctx->arena_off = start + elems;
-        if (ctx->arena_off > ctx->arena_high_water) ctx->arena_high_water = ctx->arena_off;
-        return ctx->arena + start;
-    }
-    // the reservation was too small: overflow slabs (only inside a proof: the arena belongs to the proof in flight)
-    if (!ctx->in_proof) return nullptr;
-    if (!ctx->arena_slabs.empty()) {
-        auto &last = ctx->arena_slabs.back();
-        const size_t st = (ctx->slab_off + 63) & ~(size_t)63;
-        if (st + elems <= last.second) {
-            ctx->slab_off = st + elems;
-            ctx->arena_high_water += elems + 64;
-            return last.first + st;
-        }
-    }
-    const size_t slab = elems > ((size_t)1 << 25) ? elems : ((size_t)1 << 25);   // at least 256 MiB
-    u64 *p = nullptr;
-    if (hipMalloc((void **)&p, slab * sizeof(u64)) != hipSuccess) return nullptr;
-    ctx->arena_slabs.emplace_back(p, slab);
-    ctx->slab_off = elems;
-    if (ctx->arena_high_water < ctx->arena_off) ctx->arena_high_water = ctx->arena_off;
-    ctx->arena_high_water += elems + 64;
-    return p;
-}
-
-
-int probe_begin(bj_ctx *ctx, const char *name, double algorithmic_bytes) {
-    if (!ctx->in_proof || ctx->probe_n >= BJ_MAX_KERNEL_PROBES) return -1;
-    for (unsigned i = 0; i < ctx->probe_n; i++)
-        if (!strcmp(ctx->probes[i].name, name)) return -1;
-    auto &p = ctx->probes[ctx->probe_n];
-    if (!p.ev[0] && hipEventCreate(&p.ev[0]) != hipSuccess) return -1;
-    if (!p.ev[1] && hipEventCreate(&p.ev[1]) != hipSuccess) return -1;
-    p.name = name;
-    p.bytes = algorithmic_bytes;
-    p.closed = false;
-    if (hipEventRecord(p.ev[0], ctx->stream) != hipSuccess) return -1;
-    return (int)ctx->probe_n++;
-}
-void probe_end(bj_ctx *ctx, int idx) {
-    if (idx >= 0) ctx->probes[idx].closed = hipEventRecord(ctx->probes[idx].ev[1], ctx->stream) == hipSuccess;
-}
-
-namespace {
-EnvConfig g_env;
-std::once_flag g_env_once;
-void load_env() {
-    EnvConfig e;
-    auto set = [](const char *name) { return getenv(name) != nullptr; };
-    auto str = [](const char *name) { const char *v = getenv(name); return std::string(v ? v : ""); };
-    e.ntt_two_pass = str("BJ_NTT_TWO_PASS").rfind("0", 0) != 0;
-    e.mono_tiled = str("BJ_MONO_TILED").rfind("0", 0) != 0;
-    if (set("BJ_ASYNC_MODE")) e.async_mode = atoi(getenv("BJ_ASYNC_MODE"));
-    e.async_stagger = str("BJ_ASYNC_STAGGER").rfind("0", 0) != 0;
-    e.async_debug = set("BJ_ASYNC_DEBUG");
-    if (set("BJ_HBM_BUDGET_BYTES")) e.hbm_budget_bytes = (size_t)strtoull(getenv("BJ_HBM_BUDGET_BYTES"), nullptr, 10);
-    e.peer_debug = set("BJ_PEER_DEBUG");
-    if (set("BJ_PEER_TEST_FAIL_RANK")) e.peer_test_fail_rank = atoi(getenv("BJ_PEER_TEST_FAIL_RANK"));
-    e.gate_no_aot = set("BJ_GATE_NO_AOT");
-    e.gate_no_fuse = set("BJ_GATE_NO_FUSE");
-    e.gate_no_jit = set("BJ_GATE_NO_JIT");
-    e.gates_windowed = str("BJ_GATES_WINDOWED").rfind("0", 0) != 0;
-    e.prove_no_absorb = set("BJ_PROVE_NO_ABSORB");
-    e.setup_lean = set("BJ_SETUP_LEAN") && str("BJ_SETUP_LEAN").rfind("0", 0) != 0;
-    e.proof_lean = set("BJ_PROOF_LEAN") && str("BJ_PROOF_LEAN").rfind("0", 0) != 0;
-    e.prove_uniform_groups = set("BJ_PROVE_UNIFORM_GROUPS");
-    e.copy_perm_wide_k = set("BJ_COPY_PERM_WIDE_K");
-    if (set("BJ_PROVE_H2D_GROUP")) {
-        const unsigned v = (unsigned)strtoul(getenv("BJ_PROVE_H2D_GROUP"), nullptr, 10);
-        e.prove_h2d_group = v ? v : 8u;
-    }
-    if (set("BJ_NODES_LANEPAR_MAX")) e.nodes_lanepar_max = (size_t)strtoull(getenv("BJ_NODES_LANEPAR_MAX"), nullptr, 10);
-    if (set("BJ_VERIFY_THREADS")) {
-        const long v = strtol(getenv("BJ_VERIFY_THREADS"), nullptr, 10);
-        e.verify_threads = v < 1 ? 1u : v > 16 ? 16u : (unsigned)v;
-    }
-    e.jit_cache_dir = str("BJ_GATE_JIT_CACHE");
-    e.rccl_lib = str("BJ_RCCL_LIB");
-    g_env = e;
-}
-}  // namespace
-const EnvConfig &env() {
-    std::call_once(g_env_once, load_env);
-    return g_env;
-}
-void env_reload() {
-    (void)env();
-    load_env();
-}
-}  // namespace bj
 
 using bj::bind;
 using bj::ensure_scratch;
@@ -374,8 +54,8 @@ int bj_ctx_create(int device, bj_ctx **out) {
     if (hipSetDevice(device) != hipSuccess) return BJ_ERR_NO_DEVICE;
     bj_ctx *ctx = new bj_ctx();
     ctx->device = device;
-    if (hipMalloc((void **)&ctx->d_small, (64 + 64 * 32 + 4096 + bj::BJ_FRONT_TABLE_WORDS) * sizeof(u64)) != hipSuccess ||
-        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
+    if (hipMalloc((void **)&ctx->d_small, bj::SmallBlock::WORDS * sizeof(u64)) != hipSuccess || bj::ensure_event(ctx, ctx->ev0) ||
+        bj::ensure_event(ctx, ctx->ev1)) {
         delete ctx;
         return BJ_ERR_HIP;
     }
@@ -388,30 +68,10 @@ void bj_ctx_destroy(bj_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     bj::pipeline_destroy(ctx);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->tw_fwd) (void)hipFree(ctx->tw_fwd);
-    if (ctx->tw_inv) (void)hipFree(ctx->tw_inv);
-    if (ctx->tw_inv_scaled22) (void)hipFree(ctx->tw_inv_scaled22);
+    bj::ctx_drop_all(ctx);
     if (ctx->d_small) (void)hipFree(ctx->d_small);
-    if (ctx->d_ptrs) (void)hipFree((void *)ctx->d_ptrs);
-    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    if (ctx->wit_stage) (void)hipFree(ctx->wit_stage);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-    for (auto &pair : ctx->comm_ev)
-        for (hipEvent_t e : pair)
-            if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->copy_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &p : ctx->probes)
-        for (hipEvent_t e : p.ev)
-            if (e) (void)hipEventDestroy(e);
-    if (ctx->arena) (void)hipFree(ctx->arena);
-    for (auto &sl : ctx->arena_slabs) (void)hipFree(sl.first);
     if (ctx->h_ring) (void)hipHostFree(ctx->h_ring);
-    for (auto *t : {&ctx->verify_timing, &ctx->verify_batch_timing})
-        for (auto &e : t->ev)
-            if (e) (void)hipEventDestroy(e);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     delete ctx;
 }
 
@@ -471,7 +131,7 @@ int bj_memcpy_d2h(bj_ctx *ctx, void *h_dst, const void *d_src, size_t bytes) {
     if (!bytes) return BJ_OK;
     if (!h_dst || !d_src) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_memcpy_d2h: null pointer");
     if (bytes <= bj::RING_MAX_BLOCK) {   // small block: land in pinned memory (a pageable destination costs a staging pass in the runtime)
-        if (!ctx->h_ring) BJ_HIP(ctx, hipHostMalloc((void **)&ctx->h_ring, bj::RING_BYTES, hipHostMallocDefault));
+        if (int rc = bj::ensure_ring(ctx)) return rc;
         BJ_HIP(ctx, hipMemcpyAsync(ctx->h_ring, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));   // runs after every staged upload
         BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
         std::memcpy(h_dst, ctx->h_ring, bytes);
@@ -538,10 +198,10 @@ int bj_ntt_forward_batch(bj_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, uns
     if (coset == 0) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_ntt_forward_batch: coset shift must be non-zero");
     const u64 *scales = nullptr;
     if (coset != 1 && log_n > 0) {
-        bj::launch_round_scales(ctx->d_small + 64, &coset, 1, log_n, ctx->stream);
-        scales = ctx->d_small + 64;
+        bj::launch_round_scales(bj::round_scales(ctx), &coset, 1, log_n, ctx->stream);
+        scales = bj::round_scales(ctx);
     }
-    bj::launch_ntt_passes(d_in, d_out, ctx->tw_fwd, scales, log_n, n_cols, 1, col_stride, col_stride, ctx->stream, bj::front_table(ctx));
+    bj::launch_ntt_passes(d_in, d_out, ctx->tw_fwd.p, scales, log_n, n_cols, 1, col_stride, col_stride, ctx->stream, bj::front_table(ctx));
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }
@@ -572,12 +232,12 @@ static int intt_groups(bj_ctx *ctx, const u64 *d_in, size_t in_col_stride, u64 *
     for (unsigned c0 = 0; c0 < n_cols; c0 += group) {
         const unsigned nc = n_cols - c0 < group ? n_cols - c0 : group;
         u64 *out = d_out + (size_t)c0 * out_col_stride;
-        bj::launch_ntt_passes(d_in + (size_t)c0 * in_col_stride, ctx->d_scratch, ctx->tw_inv, nullptr, log_n, nc, 1, in_col_stride, n, ctx->stream,
+        bj::launch_ntt_passes(d_in + (size_t)c0 * in_col_stride, ctx->d_scratch.p, ctx->tw_inv.p, nullptr, log_n, nc, 1, in_col_stride, n, ctx->stream,
                               bj::front_table(ctx), false, to_tiled, true);
         if (to_tiled)
-            bj::launch_ntt_local12_pair_tiled(ctx->d_scratch, out, ctx->tw_inv, ctx->tw_inv_scaled22, n_inv, nc, n, out_col_stride, ctx->stream);
+            bj::launch_ntt_local12_pair_tiled(ctx->d_scratch.p, out, ctx->tw_inv.p, ctx->tw_inv_scaled22.p, n_inv, nc, n, out_col_stride, ctx->stream);
         else
-            bj::launch_bitrev_scale(ctx->d_scratch, out, log_n, nc, n, out_col_stride, n_inv, step, ctx->stream);
+            bj::launch_bitrev_scale(ctx->d_scratch.p, out, log_n, nc, n, out_col_stride, n_inv, step, ctx->stream);
     }
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
@@ -604,8 +264,8 @@ int lde_cosets_strided(bj_ctx *ctx, const u64 *d_mono, size_t in_col_stride, u64
     u64 w = gl::omega(log_n + log_lde);
     for (unsigned i = 0; i < coset_count; i++)
         shifts[i] = gl::mul(gl::GEN, gl::pow(w, gl::bitrev32(coset_begin + i, log_lde)));  // utils.rs:345-346, 370-373
-    bj::launch_round_scales(ctx->d_small + 64, shifts, coset_count, log_n ? log_n : 1, ctx->stream);
-    bj::launch_ntt_passes(d_mono, d_out, ctx->tw_fwd, log_n ? ctx->d_small + 64 : nullptr, log_n, n_cols, coset_count,
+    bj::launch_round_scales(bj::round_scales(ctx), shifts, coset_count, log_n ? log_n : 1, ctx->stream);
+    bj::launch_ntt_passes(d_mono, d_out, ctx->tw_fwd.p, log_n ? bj::round_scales(ctx) : nullptr, log_n, n_cols, coset_count,
                           in_col_stride, out_col_stride, ctx->stream, bj::front_table(ctx), tiled_in);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
@@ -690,12 +350,12 @@ int bj_bitreverse_batch(bj_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, unsi
     const size_t n = (size_t)1 << log_n;
     if (d_in == d_out) {
         if (int rc = ensure_scratch(ctx, (size_t)n_cols * n)) return rc;
-        bj::launch_bitrev_scale(d_in, ctx->d_scratch, log_n, n_cols, col_stride, n, 1, 1, ctx->stream);
+        bj::launch_bitrev_scale(d_in, ctx->d_scratch.p, log_n, n_cols, col_stride, n, 1, 1, ctx->stream);
         if (col_stride == n) {
-            BJ_HIP(ctx, hipMemcpyAsync(d_out, ctx->d_scratch, (size_t)n_cols * n * sizeof(u64),
+            BJ_HIP(ctx, hipMemcpyAsync(d_out, ctx->d_scratch.p, (size_t)n_cols * n * sizeof(u64),
                                        hipMemcpyDeviceToDevice, ctx->stream));
         } else {
-            BJ_HIP(ctx, hipMemcpy2DAsync(d_out, col_stride * sizeof(u64), ctx->d_scratch, n * sizeof(u64),
+            BJ_HIP(ctx, hipMemcpy2DAsync(d_out, col_stride * sizeof(u64), ctx->d_scratch.p, n * sizeof(u64),
                                          n * sizeof(u64), n_cols, hipMemcpyDeviceToDevice, ctx->stream));
         }
     } else {
@@ -793,19 +453,10 @@ int bj_merkle_tree_build_ptrs(bj_ctx *ctx, const uint64_t *const *h_col_ptrs, un
     if (!h_col_ptrs || n_cols == 0) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_merkle_tree_build_ptrs: no columns");
     for (unsigned c = 0; c < n_cols; c++)
         if (!h_col_ptrs[c]) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_merkle_tree_build_ptrs: null column %u", c);
-    if (n_cols > ctx->d_ptrs_cap) {
-        if (ctx->d_ptrs) {
-            BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            BJ_HIP(ctx, hipFree((void *)ctx->d_ptrs));
-            ctx->d_ptrs = nullptr;
-            ctx->d_ptrs_cap = 0;
-        }
-        size_t cap = n_cols < 1024 ? 1024 : n_cols;
-        BJ_HIP(ctx, hipMalloc((void **)&ctx->d_ptrs, cap * sizeof(u64 *)));
-        ctx->d_ptrs_cap = cap;
-    }
-    if (int rc = bj::h2d_async(ctx, (void *)ctx->d_ptrs, h_col_ptrs, n_cols * sizeof(u64 *))) return rc;  // staged: the caller's array may be transient
-    bj::launch_tree_leaves(ctx->hasher, nullptr, 0, ctx->d_ptrs, n_cols, num_leaves, d_tree, ctx->stream);
+    static_assert(sizeof(u64 *) == sizeof(u64), "a pointer table is a buffer of words");
+    if (int rc = ctx->d_ptrs.ensure(ctx, n_cols < 1024 ? 1024 : n_cols)) return rc;
+    if (int rc = bj::h2d_async(ctx, ctx->d_ptrs.p, h_col_ptrs, n_cols * sizeof(u64 *))) return rc;  // staged: the caller's array may be transient
+    bj::launch_tree_leaves(ctx->hasher, nullptr, 0, (const u64 **)ctx->d_ptrs.p, n_cols, num_leaves, d_tree, ctx->stream);
     bj::launch_tree_node_layers(ctx->hasher, d_tree, num_leaves, cap_size, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
@@ -898,10 +549,10 @@ int bj_pow_search(bj_ctx *ctx, int pow_runner, const uint64_t *h_seed5, unsigned
     if (base >= ~(u64)0 - count + 1) return fail(ctx, BJ_ERR_INVALID_ARG, "bj_pow_search: the window passes 2^64 - 1");
     if (int rc = ensure_scratch(ctx, 1)) return rc;   // the result word lives in the context's scratch
     const u64 none = ~(u64)0;
-    if (int rc = bj::h2d_async(ctx, ctx->d_scratch, &none, 8)) return rc;
-    bj::launch_pow(pow_runner, h_seed5, pow_bits, base, count, ctx->d_scratch, ctx->stream);
+    if (int rc = bj::h2d_async(ctx, ctx->d_scratch.p, &none, 8)) return rc;
+    bj::launch_pow(pow_runner, h_seed5, pow_bits, base, count, ctx->d_scratch.p, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
-    return bj_memcpy_d2h(ctx, h_result, ctx->d_scratch, 8);
+    return bj_memcpy_d2h(ctx, h_result, ctx->d_scratch.p, 8);
 }
 
 // --------------------------------------------------------------------------------------------------------- FRI
@@ -914,7 +565,7 @@ int bj_fri_fold(bj_ctx *ctx, const uint64_t *d_c0, const uint64_t *d_c1, size_t 
     if (log_full > 32 || len > ((size_t)1 << log_full))
         return fail(ctx, BJ_ERR_INVALID_ARG, "bj_fri_fold: array longer than the initial domain");
     if (int rc = ensure_twiddles(ctx, log_full, true)) return rc;
-    bj::launch_fri_fold_step(d_c0, d_c1, len, 1, d_o0, d_o1, ctx->tw_inv, coset_inv, ch0, ch1, ctx->stream);
+    bj::launch_fri_fold_step(d_c0, d_c1, len, 1, d_o0, d_o1, ctx->tw_inv.p, coset_inv, ch0, ch1, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }
@@ -928,7 +579,7 @@ int bj_fri_fold_step(bj_ctx *ctx, const uint64_t *d_c0, const uint64_t *d_c1, si
     if (log_full > 32 || len > ((size_t)1 << log_full))
         return fail(ctx, BJ_ERR_INVALID_ARG, "bj_fri_fold_step: array longer than the initial domain");
     if (int rc = ensure_twiddles(ctx, log_full, true)) return rc;
-    bj::launch_fri_fold_step(d_c0, d_c1, len, k, d_o0, d_o1, ctx->tw_inv, coset_inv, ch0, ch1, ctx->stream);
+    bj::launch_fri_fold_step(d_c0, d_c1, len, k, d_o0, d_o1, ctx->tw_inv.p, coset_inv, ch0, ch1, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }

@@ -25,6 +25,8 @@ inline const char *admission_name(unsigned rung) {
 
 // What a context holds for proofs, in bytes, one number per device allocation (each grows by free and allocate).
 enum LanePart : unsigned { LANE_ARENA, LANE_STAGING, LANE_SCRATCH, LANE_TW_FWD, LANE_TW_INV, LANE_TW_SCALED22, LANE_N_PARTS };
+// bj_ctx_release_workspace gives the arena, the staging and the scratch back; the three tables stay
+constexpr bool LANE_RELEASED[LANE_N_PARTS] = {true, true, true, false, false, false};
 struct LaneBytes {
     size_t part[LANE_N_PARTS] = {};
     size_t total() const {
@@ -32,8 +34,12 @@ struct LaneBytes {
         for (size_t p : part) s += p;
         return s;
     }
-    // what bj_ctx_release_workspace gives back: the tables stay
-    size_t releasable() const { return part[LANE_ARENA] + part[LANE_STAGING] + part[LANE_SCRATCH]; }
+    size_t releasable() const {   // what bj_ctx_release_workspace gives back
+        size_t s = 0;
+        for (unsigned i = 0; i < LANE_N_PARTS; i++)
+            if (LANE_RELEASED[i]) s += part[i];
+        return s;
+    }
 };
 // bytes that bringing a context from `held` to at least `want` allocates
 inline size_t grow_bytes(const LaneBytes &want, const LaneBytes &held) {
@@ -41,6 +47,15 @@ inline size_t grow_bytes(const LaneBytes &want, const LaneBytes &held) {
     for (unsigned i = 0; i < LANE_N_PARTS; i++)
         if (want.part[i] > held.part[i]) s += want.part[i] - held.part[i];
     return s;
+}
+
+// A twiddle table for 2^log_n points holds 2^(log_n - 1) words (one word below 2^1) and serves every smaller size as a prefix;
+// twiddle_log: the smallest log_n whose table has at least `bytes`.
+inline size_t twiddle_bytes(unsigned log_n) { return ((size_t)8 << (log_n ? log_n - 1 : 0)); }
+inline unsigned twiddle_log(size_t bytes) {
+    unsigned k = 1;
+    while (twiddle_bytes(k) < bytes) k++;
+    return k;
 }
 
 inline size_t intt_scratch_words(size_t len, size_t cols) {   // intt_groups (abi.hip): column groups whose scratch stays at 2^27 words
@@ -58,9 +73,11 @@ inline LaneBytes lane_extras(const WorkspaceShape &s) {
     if (t > scratch) scratch = t;
     if (s.has_lookup && 2 * s.n + 2 > scratch) scratch = 2 * s.n + 2;
     b.part[LANE_SCRATCH] = scratch * 8;
-    const size_t domain = s.Ln > s.N ? s.Ln : s.N;   // n times max(fri_lde, q): half as many twiddles
-    b.part[LANE_TW_FWD] = b.part[LANE_TW_INV] = (domain > 2 ? domain / 2 : 1) * 8;
-    if (s.tiled) b.part[LANE_TW_SCALED22] = ((size_t)1 << 21) * 8;
+    const size_t domain = s.Ln > s.N ? s.Ln : s.N;   // n times max(fri_lde, q), a power of two
+    unsigned log_domain = 0;
+    while (((size_t)1 << log_domain) < domain) log_domain++;
+    b.part[LANE_TW_FWD] = b.part[LANE_TW_INV] = twiddle_bytes(log_domain);
+    if (s.tiled) b.part[LANE_TW_SCALED22] = twiddle_bytes(22);
     return b;
 }
 // The footprint of a lane for shape `s` with the witness and stage-2 oracles resident or lean: the plan's total and the extras.

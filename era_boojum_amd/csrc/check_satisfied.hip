@@ -140,7 +140,7 @@ int check_impl(bj_ctx *ctx, const bj_setup *S, const u64 *d_variables, const u64
     const size_t o_slots = has_lookup ? take(n) : 0, o_count = has_lookup ? take(n) : 0, o_lo = has_lookup ? take(n) : 0;
     const size_t o_hi = has_lookup ? take(n / 2 + 1) : 0, o_cls = has_lookup ? take(n / 2 + 1) : 0;
     if (int rc = bj::ensure_scratch(ctx, off)) return rc;
-    u64 *W = ctx->d_scratch;
+    u64 *W = ctx->d_scratch.p;
     u64 *t0 = W + o_t, *t1 = t0 + n, *ctr = W + o_ctr, *d_alpha = W + o_alpha, *d_unit = W + o_unit;
 
     {

@@ -220,7 +220,7 @@ int bj_sigma_cells(bj_ctx *ctx, const uint64_t *d_sigmas, size_t sig_stride, uns
     const size_t n = (size_t)1 << log_n;
     if (sig_stride < n || cell_stride < n) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_sigma_cells: column stride below n");
     if (int rc = bj::ensure_scratch(ctx, table.size() + 2)) return rc;
-    u64 *d_table = ctx->d_scratch, *d_ctr = d_table + table.size();
+    u64 *d_table = ctx->d_scratch.p, *d_ctr = d_table + table.size();
     const u64 ctr0[2] = {NONE64, 0};
     if (int rc = bj::h2d_async(ctx, d_table, table.data(), table.size() * 8)) return rc;
     if (int rc = bj::h2d_async(ctx, d_ctr, ctr0, sizeof(ctr0))) return rc;
@@ -248,7 +248,7 @@ int bj_check_copy_constraints(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_
     const size_t bitmap_words = (cells + 63) / 64;   // u64 words of one bit per cell
     const size_t o_ctr = (table.size() + 1) & ~(size_t)1, o_seen = o_ctr + 8, o_multi = o_seen + bitmap_words;
     if (int rc = bj::ensure_scratch(ctx, o_multi + bitmap_words)) return rc;
-    u64 *W = ctx->d_scratch, *d_ctr = W + o_ctr;
+    u64 *W = ctx->d_scratch.p, *d_ctr = W + o_ctr;
     uint32_t *d_seen = (uint32_t *)(W + o_seen), *d_multi = (uint32_t *)(W + o_multi);
     hipStream_t st = ctx->stream;
     const u64 ctr0[8] = {NONE64, 0, NONE64, 0, NONE64, 0, 0, 0};

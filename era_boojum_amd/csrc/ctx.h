@@ -1,7 +1,10 @@
 // Internal: the context object behind the opaque `bj_ctx` of include/boojum_hip.h, shared by the C-ABI translation
-// units (abi.hip, fri_prover.hip, ...).
+// units (abi.hip, fri_prover.hip, ...).  Its memory, the workspace of the proof in flight, the probes and the environment
+// switches are defined in ctx.hip.
 #pragma once
 #include "../../include/boojum_hip.h"
+#include "arena_bump.h"
+#include "async_admission.h"
 #include "gl.h"
 #include "kernels.h"
 
@@ -15,35 +18,51 @@
 
 namespace bj {
 struct Pipeline;        // prove_async.hip: the two lanes of bj_prove_async
-struct WorkspacePlan;   // workspace_plan.h: the buffers of a proof, in the order it takes them
-struct LaneBytes;       // async_admission.h: what a context holds for proofs, one number per device allocation
+// A grow-only device allocation of a context: the six parts a proof is admitted by (async_admission.h) are one each.
+struct DevBuf {
+    gl::u64 *p = nullptr;
+    size_t words = 0;
+    size_t bytes() const { return words * sizeof(gl::u64); }
+    // at least `need` words: nothing if it is that large already, else the context's stream is drained and the block is freed and
+    // allocated again (the contents are lost; *grew says so).  BJ_ERR_OOM / BJ_ERR_HIP with the buffer left empty.
+    int ensure(bj_ctx *ctx, size_t need, bool *grew = nullptr);
+    hipError_t drop();   // frees and zeroes; the caller has drained whatever may still use the block
+};
+// The words of the context's small block (bj_ctx::d_small).  Nothing reads or writes SHIFTS any more; the offsets behind it
+// stay where they have always been.
+struct SmallBlock {
+    static constexpr size_t SHIFTS = 0;                            // 64 words
+    static constexpr size_t ROUND_SCALES = 64;                     // 64 cosets x 32 rounds (launch_round_scales)
+    static constexpr size_t GATHER = ROUND_SCALES + 64 * 32;       // what a collective gathers before it goes to the host
+    static constexpr size_t GATHER_WORDS = 4096;                   // evaluate_at sends from the first half into the second
+    static constexpr size_t GATHER_HALF = GATHER + GATHER_WORDS / 2;
+    static constexpr size_t FRONT_TABLE = GATHER + GATHER_WORDS;   // BJ_FRONT_TABLE_WORDS (kernels.h)
+    static constexpr size_t WORDS = FRONT_TABLE + BJ_FRONT_TABLE_WORDS;
+};
+constexpr size_t RING_BYTES = (size_t)1 << 20, RING_MAX_BLOCK = (size_t)128 << 10;   // the pinned ring, and the largest block that goes through it
 }
 
 struct bj_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
-    // twiddle caches (bit-reversed tables; a table for 2^k serves every smaller size as a prefix)
-    gl::u64 *tw_fwd = nullptr, *tw_inv = nullptr;
-    unsigned tw_fwd_log = 0, tw_inv_log = 0;
-    gl::u64 *tw_inv_scaled22 = nullptr;   // tw_inv[j] / 2^22, j < 2^21: the last round of a 2^22-point inverse transform into the tiled layout
-    gl::u64 *d_small = nullptr;  // 64 shifts + 64*32 per-round scales + 4096 for gathered Merkle caps + the front-pass twiddle table
-    const gl::u64 **d_ptrs = nullptr;
-    size_t d_ptrs_cap = 0;
-    gl::u64 *d_scratch = nullptr;  // big scratch for out-of-place steps
-    size_t scratch_elems = 0;
+    // twiddle caches (bit-reversed tables; a table for 2^k holds 2^(k-1) words and serves every smaller size as a prefix)
+    bj::DevBuf tw_fwd, tw_inv;
+    bj::DevBuf tw_inv_scaled22;   // tw_inv[j] / 2^22, j < 2^21: the last round of a 2^22-point inverse transform into the tiled layout
+    gl::u64 *d_small = nullptr;   // bj::SmallBlock
+    bj::DevBuf d_ptrs;            // the column pointers of bj_merkle_tree_build_ptrs
+    bj::DevBuf d_scratch;         // big scratch for out-of-place steps
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::vector<hipEvent_t> events;   // every event ensure_event has created on this context, destroyed with it
     // bump-allocated workspace reused across proofs (hipMalloc/hipFree of multi-GB buffers per proof is slow and
     // synchronising); grown on demand, reset at the start of every bj_prove_dev
-    gl::u64 *arena = nullptr;
-    size_t arena_elems = 0, arena_off = 0;
+    bj::DevBuf arena;
     // A proof whose buffers outgrow the reservation does not fail: further blocks come out of overflow slabs (hipMalloc in the
     // middle of a proof — slow, once), the proof reports its high-water mark (bj_proof_workspace_bytes) and the next reservation
     // on this context is at least that large.  The reservation is the total of the proof's plan and every buffer is taken from
     // that plan, so only an allowance that was no upper bound can lead here; the suite asserts that no proof needed a slab.
-    std::vector<std::pair<gl::u64 *, size_t>> arena_slabs;   // (base, elems), each slab bump-allocated like the arena
-    size_t slab_off = 0;                 // elements used in the last slab
-    size_t arena_high_water = 0;         // elements the proof in flight has taken (arena + slabs)
+    bj::ArenaBump bump;                  // where the next block goes (arena_bump.h)
+    std::vector<gl::u64 *> slab_base;    // the device blocks of bump.slabs
     size_t arena_learned = 0;            // largest high-water mark seen on this context
     int hasher = BJ_HASHER_POSEIDON2;   // tree hasher of the bj_merkle_tree_* calls (bj_ctx_set_tree_hasher / bj_prove)
     bool in_proof = false;       // bj_prove_dev is running: temporaries come out of the arena instead of hipMalloc
@@ -55,8 +74,7 @@ struct bj_ctx {
     size_t ring_off = 0, ring_inflight = 0;
     // bj_prove (host witness): device staging of the witness columns, kept across proofs, and a copy stream with one event
     // per column group so that the PCIe transfer of group k+1 runs under the iNTT / LDE of group k
-    gl::u64 *wit_stage = nullptr;
-    size_t wit_stage_elems = 0;
+    bj::DevBuf wit_stage;
     hipStream_t copy_stream = nullptr;
     hipEvent_t copy_ev[64] = {};
     // collectives of the sharded proof in flight: an event pair around each (created on first use, reused), summed into
@@ -102,8 +120,22 @@ int bind(bj_ctx *ctx);
 // host block -> device, ordered on ctx->stream like a kernel launch; returns without waiting (h_src may be reused at once)
 int h2d_async(bj_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);
 int ensure_twiddles(bj_ctx *ctx, unsigned log_n, bool inverse);
-int ensure_scratch(bj_ctx *ctx, size_t elems);
-inline gl::u64 *front_table(bj_ctx *ctx) { return ctx->d_small + 64 + 64 * 32 + 4096; }   // BJ_FRONT_TABLE_WORDS (kernels.h)
+inline unsigned twiddles_log(const bj_ctx *ctx, bool inverse) {   // the table serves up to 2^this points (0: none yet)
+    const DevBuf &t = inverse ? ctx->tw_inv : ctx->tw_fwd;
+    return t.p ? twiddle_log(t.bytes()) : 0;
+}
+inline int ensure_scratch(bj_ctx *ctx, size_t elems) { return ctx->d_scratch.ensure(ctx, elems); }
+inline gl::u64 *round_scales(bj_ctx *ctx) { return ctx->d_small + SmallBlock::ROUND_SCALES; }
+inline gl::u64 *gather_area(bj_ctx *ctx) { return ctx->d_small + SmallBlock::GATHER; }
+inline gl::u64 *gather_half(bj_ctx *ctx) { return ctx->d_small + SmallBlock::GATHER_HALF; }
+inline gl::u64 *front_table(bj_ctx *ctx) { return ctx->d_small + SmallBlock::FRONT_TABLE; }
+int ensure_ring(bj_ctx *ctx);                                                          // the pinned ring exists
+int ensure_event(bj_ctx *ctx, hipEvent_t &e, unsigned flags = hipEventDefault);   // e exists (created once, with `flags`)
+std::string &thread_error();   // message of the last failed call that has no context, per host thread
+// The one enumeration of what a context holds for proofs: the buffer behind each LanePart (async_admission.h says which of them
+// bj_ctx_release_workspace gives back).  The arena's part includes its overflow slabs.
+DevBuf &ctx_part(bj_ctx *ctx, unsigned part);
+void ctx_drop_all(bj_ctx *ctx);      // bj_ctx_destroy: every part, kept or not, and the events
 unsigned setup_world(const bj_setup *s);         // ranks of the proof a setup belongs to (1: single device)
 // mode 1: whole witness first, then as on a resident witness; mode 2: groups transferred and transformed as they land, hashed once
 int prove_host_copy_first(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_variables, const uint64_t *h_multiplicities,
@@ -118,10 +150,9 @@ void ctx_held(const bj_ctx *ctx, LaneBytes *out);
 int ctx_reserve(bj_ctx *ctx, const LaneBytes &want);
 int ctx_release_own_workspace(bj_ctx *ctx);
 int async_footprints(bj_ctx *ctx, const bj_setup *setup, LaneBytes *resident, LaneBytes *lean);
-int stage_witness_elems(bj_ctx *ctx, size_t need);   // the device staging of a host witness holds at least `need` words
+inline int stage_witness_elems(bj_ctx *ctx, size_t need) { return ctx->wit_stage.ensure(ctx, need); }   // kept for the next proof
 int ensure_scaled22(bj_ctx *ctx);                    // tw_inv_scaled22 exists (tw_inv must reach 2^22)
-int arena_reset(bj_ctx *ctx, size_t need_elems);
-int arena_drop_slabs(bj_ctx *ctx);
+int arena_reset(bj_ctx *ctx, size_t need_elems);     // a new proof: nothing taken, no slabs, at least need_elems words
 gl::u64 *arena_alloc(bj_ctx *ctx, size_t elems);   // nullptr if the reservation was too small
 // A block of device memory for the scope that holds it: out of the arena inside a proof (no hipMalloc / hipFree, no implicit
 // synchronisation; the arena is a bump allocator and gives nothing back before the next proof), hipMalloc'ed and freed otherwise.

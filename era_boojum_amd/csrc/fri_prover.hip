@@ -178,12 +178,12 @@ int bj::fri_prove_sharded(bj_ctx *ctx, const bj::Shard &sh, const u64 *d_c0, con
         // FRI fold by 2^k over m F_p^2 inputs, SURVEY §8d: 16 m + 16 m / 2^k
         const int pf = bj::probe_begin(ctx, "fri_fold_first", 16.0 * (double)loc_len * (1.0 + 1.0 / (double)(1u << k)));
         if (parts == 1) {
-            bj::launch_fri_fold_step(cur0, cur1, cur_len, k, nxt, nxt + out_len, ctx->tw_inv, kappa, oo.ch0, oo.ch1,
+            bj::launch_fri_fold_step(cur0, cur1, cur_len, k, nxt, nxt + out_len, ctx->tw_inv.p, kappa, oo.ch0, oo.ch1,
                                      ctx->stream);
             bj::probe_end(ctx, pf);
         } else {
             if ((rc = take(bj::WS_FRI_PART, 2 * loc_out, &part))) return bail(rc);   // [2][loc_out] of this rank, gathered into nxt = [2][out_len]
-            bj::launch_fri_fold_step(cur0, cur1, loc_len, k, part, part + loc_out, ctx->tw_inv, kappa, oo.ch0, oo.ch1,
+            bj::launch_fri_fold_step(cur0, cur1, loc_len, k, part, part + loc_out, ctx->tw_inv.p, kappa, oo.ch0, oo.ch1,
                                      ctx->stream, (size_t)sh.rank * loc_out);
             bj::probe_end(ctx, pf);
             rc = bj::all_gather_columns(ctx, sh, part, nxt, 2, loc_out);

@@ -68,9 +68,9 @@ int lookup_multiplicities(bj_ctx *ctx, const char *who, const u64 *d_lvars, size
     // scratch (words): 2 n 32-bit slots, n 64-bit counters, the smallest miss key and the number of misses
     if (int rc = ensure_scratch(ctx, 2 * n + 2)) return rc;
     hipStream_t st = ctx->stream;
-    uint32_t *slots = (uint32_t *)ctx->d_scratch;
-    unsigned long long *count = (unsigned long long *)(ctx->d_scratch + n);
-    u64 *miss = ctx->d_scratch + 2 * n;
+    uint32_t *slots = (uint32_t *)ctx->d_scratch.p;
+    unsigned long long *count = (unsigned long long *)(ctx->d_scratch.p + n);
+    u64 *miss = ctx->d_scratch.p + 2 * n;
     BJ_HIP(ctx, hipMemsetAsync(slots, 0xFF, 2 * n * sizeof(uint32_t), st));
     BJ_HIP(ctx, hipMemsetAsync(count, 0, n * 8, st));
     const u64 miss0[2] = {NONE64, 0};

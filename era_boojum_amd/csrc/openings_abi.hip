@@ -46,7 +46,7 @@ int bj_barycentric_weights(bj_ctx *ctx, unsigned log_n, uint64_t coset, const ui
     if (log_n > 30) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_barycentric_weights: log_n > 30");
     if (gl::canon(coset) == 0) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_barycentric_weights: zero coset");
     if (int rc = bj::ensure_twiddles(ctx, log_n ? log_n : 1, false)) return rc;
-    bj::launch_barycentric_weights(d_w0, d_w1, ctx->tw_fwd, log_n, coset, at2, ctx->stream);
+    bj::launch_barycentric_weights(d_w0, d_w1, ctx->tw_fwd.p, log_n, coset, at2, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }
@@ -124,7 +124,7 @@ int bj_eval_monomials_at(bj_ctx *ctx, const uint64_t *d_mono, size_t col_stride,
     if (first_leaf >= ((size_t)1 << log_full))   // the indices themselves are on the device: the caller's obligation
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_eval_monomials_at: first_leaf %zu passes the 2^%u-point domain", first_leaf, log_full);
     if (int rc = bj::ensure_twiddles(ctx, log_full, false)) return rc;
-    bj::launch_eval_monomials_at(d_mono, col_stride, n_cols, log_n, tiled != 0, ctx->tw_fwd, first_leaf, d_idx, n_idx, d_out, ctx->stream);
+    bj::launch_eval_monomials_at(d_mono, col_stride, n_cols, log_n, tiled != 0, ctx->tw_fwd.p, first_leaf, d_idx, n_idx, d_out, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }
@@ -178,7 +178,7 @@ int deep_accumulate_multi(bj_ctx *ctx, const ColumnList &L, unsigned log_n, unsi
     bj::TmpBuf args;
     DeviceColumns d;
     if (int rc = upload_columns(ctx, L, args, &d)) return rc;
-    bj::launch_deep_accumulate_multi(L.sets.data(), (unsigned)L.sets.size(), d.ptrs, d.coefs, N_local, I0, ctx->tw_fwd, d_dst_c0, d_dst_c1,
+    bj::launch_deep_accumulate_multi(L.sets.data(), (unsigned)L.sets.size(), d.ptrs, d.coefs, N_local, I0, ctx->tw_fwd.p, d_dst_c0, d_dst_c1,
                                      accumulate, ctx->stream);
     return launched_on_columns(ctx, args);
 }

@@ -76,8 +76,8 @@ int all_gather(bj_ctx *ctx, const Shard &sh, const u64 *d_send, u64 *d_recv, siz
         hipEvent_t *ev = nullptr;
         if (ctx->in_proof && ctx->comm_n < 48) {
             ev = ctx->comm_ev[ctx->comm_n];
-            if (!ev[0]) (void)hipEventCreate(&ev[0]);
-            if (!ev[1]) (void)hipEventCreate(&ev[1]);
+            (void)ensure_event(ctx, ev[0]);   // without its events a collective is not timed, and runs all the same
+            (void)ensure_event(ctx, ev[1]);
             if (ev[0] && ev[1]) (void)hipEventRecord(ev[0], ctx->stream);
         }
         if (int rc = sh.comm.all_gather_stream(sh.comm.user, d_send, d_recv, elems * 8, ctx->stream))
@@ -121,8 +121,8 @@ int gather_cap(bj_ctx *ctx, const Shard &sh, const u64 *d_tree_local, size_t lea
     if (sh.world == 1) return bj_merkle_tree_cap(ctx, d_tree_local, leaves_local, cap_size, h_cap);
     // the local cap fragment is the last layer of the local subtree
     const u64 *frag = d_tree_local + (2 * leaves_local - 2 * cap_l) * 4;
-    u64 *d_all = ctx->d_small + 64 + 64 * 32;   // 4096 u64 reserved for this (ctx.h)
-    if (cap_size * 4 > 4096) return fail(ctx, BJ_ERR_INVALID_ARG, "gather_cap: cap too large");
+    u64 *d_all = gather_area(ctx);
+    if (cap_size * 4 > SmallBlock::GATHER_WORDS) return fail(ctx, BJ_ERR_INVALID_ARG, "gather_cap: cap too large");
     if (int rc = all_gather(ctx, sh, frag, d_all, cap_l * 4)) return rc;
     return bj_memcpy_d2h(ctx, h_cap, d_all, cap_size * 32);
 }
@@ -315,7 +315,7 @@ int Proving::reserve_workspace() {
                                        !hw ? bj::WS_HOST_NONE : absorb ? bj::WS_HOST_ABSORBING : bj::WS_HOST_NOT_ABSORBING,
                                        !oracle[bj::ORACLE_WITNESS].resident, new_pow, sched, sched_len, num_queries));
     if (int rc = bj::arena_reset(ctx, std::max(plan.total(), ctx->arena_learned))) return rc;
-    proof->ws_reserved = ctx->arena_elems * 8;
+    proof->ws_reserved = ctx->bump.arena_words * 8;
     return BJ_OK;
 }
 
@@ -369,7 +369,7 @@ int Proving::witness_from_host() {
     bj::TmpBuf capacity;
     if (absorb && (rc = capacity.take(ctx, bj::WS_CAPACITY))) return rc;
     for (unsigned g = 0; g < n_groups; g++) {
-        if (!ctx->copy_ev[g]) BJ_HIP(ctx, hipEventCreateWithFlags(&ctx->copy_ev[g], hipEventDisableTiming));
+        if ((rc = bj::ensure_event(ctx, ctx->copy_ev[g], hipEventDisableTiming))) return rc;
         const unsigned c0 = plan[g].c0, c1 = plan[g].c1;
         const unsigned v1 = c1 < VW ? c1 : VW;         // variable / witness columns of this group: [c0, v1)
         if (c0 < v1)
@@ -479,7 +479,7 @@ int Proving::round2_stage2() {
     if ((rc = s2_nat.take(ctx, bj::WS_S2_NAT))) return rc;
     if ((rc = tmp.take(ctx, bj::WS_S2_SCRATCH))) return rc;
     const bj::Cols vars{d_variables, n}, nat{S->d_nat, n};
-    bj::launch_copy_perm_stage2(bj::CopyPermArg{vars, nat.at(L.sigma(0)), S->d_non_res, V, q, log_n, ctx->tw_fwd, beta, gamma, S->small_non_residues},
+    bj::launch_copy_perm_stage2(bj::CopyPermArg{vars, nat.at(L.sigma(0)), S->d_non_res, V, q, log_n, ctx->tw_fwd.p, beta, gamma, S->small_non_residues},
                                 tmp.p, s2_nat.p + (size_t)L.z() * n, s2_nat.p + (size_t)L.partial(0) * n, st);
     if (has_lookup) {
         challenge2(lbeta);
@@ -556,7 +556,7 @@ int Proving::round3_quotient() {
         // variables + sigmas + z and the partial products + 1/(x - 1), accumulators read and written
         const int pc = bj::probe_begin(ctx, "quotient_copy_perm", 8.0 * (2.0 * V + 2 * (1 + L.n_partials) + 1) * (double)points + 32.0 * (double)points);
         const u64 *h_alpha_l1 = alphas.data() + (a_l1 - d_alphas.p);   // the same power on the host: it goes into the kernel's arguments
-        bj::launch_quotient_copy_perm(bj::CopyPermArg{wit, setup.at(L.sigma(0)), S->d_non_res, V, q, log_n, ctx->tw_fwd, beta, gamma, S->small_non_residues},
+        bj::launch_quotient_copy_perm(bj::CopyPermArg{wit, setup.at(L.sigma(0)), S->d_non_res, V, q, log_n, ctx->tw_fwd.p, beta, gamma, S->small_non_residues},
                                       s2, S->log_L, h_alpha_l1, sink(a_l1 + 2), I0 + first, S->d_inv_xm1 + first, st);
         bj::probe_end(ctx, pc);
     };
@@ -628,7 +628,7 @@ int Proving::evaluate_at(u64 *w, u64 open_shift, const std::vector<Src> &ss, con
     const std::vector<const u64 *> ptrs = bj::open_columns(ss.data(), ss.size());
     std::vector<u64> raw(2 * ptrs.size());
     const size_t np = ptrs.size(), per = (np + sh.world - 1) / sh.world;
-    if (sh.world > 1 && np >= 8 * (size_t)sh.world && 2 * per * sh.world <= 2048) {
+    if (sh.world > 1 && np >= 8 * (size_t)sh.world && 2 * per * sh.world <= bj::SmallBlock::GATHER_WORDS / 2) {
         // many columns: rank r evaluates the slice [r*per, (r+1)*per) on its own coset, the values are all-gathered
         // (the value of a polynomial does not depend on the coset it was interpolated from)
         const size_t lo = (size_t)sh.rank * per, hi = lo + per < np ? lo + per : np;
@@ -637,7 +637,7 @@ int Proving::evaluate_at(u64 *w, u64 open_shift, const std::vector<Src> &ss, con
             r = bj_barycentric_eval_batch(ctx, ptrs.data() + lo, (unsigned)(hi - lo), log_n, w, w + n, mine.data());
             if (r) return r;
         }
-        u64 *d_part = ctx->d_small + 64 + 64 * 32, *d_all = d_part + 2048;   // the 4096-u64 gather area of the context
+        u64 *d_part = bj::gather_area(ctx), *d_all = bj::gather_half(ctx);
         if ((r = bj::h2d_async(ctx, d_part, mine.data(), 2 * per * 8))) return r;
         if ((r = bj::all_gather(ctx, sh, d_part, d_all, 2 * per))) return r;
         std::vector<u64> all(2 * per * sh.world);
@@ -843,7 +843,7 @@ int Proving::gather_base_queries(Queries &qr) {
         if (o.leaf_from_evals())
             bj::launch_gather_rows(o.evals, o.stride, o.width, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
         else   // the leaf's words are the oracle's polynomials at the leaf's point (the monomials in the layout intt_cols writes); the paths come from the kept tree
-            bj::launch_eval_monomials_at(o.mono, n, o.width, log_n, S->tiled, ctx->tw_fwd, I0, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
+            bj::launch_eval_monomials_at(o.mono, n, o.width, log_n, S->tiled, ctx->tw_fwd.p, I0, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
         off += (size_t)o.width * num_queries;
         bj::launch_merkle_paths(o.tree, N, depth, d_idx.p, (unsigned)num_queries, d_g.p + off, st);
         off += (size_t)depth * 4 * num_queries;
@@ -994,12 +994,12 @@ void Proving::read_back_stats() {
         if (hipEventElapsedTime(&e, ctx->probes[i].ev[0], ctx->probes[i].ev[1]) != hipSuccess) continue;
         proof->kernel_stats[proof->n_kernel_stats++] = {ctx->probes[i].name, e, ctx->probes[i].bytes};
     }
-    proof->ws_high_water = ctx->arena_high_water * 8;
-    proof->ws_overflow_slabs = ctx->arena_slabs.size();
+    proof->ws_high_water = ctx->bump.high_water * 8;
+    proof->ws_overflow_slabs = ctx->bump.slabs.size();
     // the context learns from a proof that outgrew its reservation; one that stayed inside it (every proof whose plan holds: the
     // reservation of a single-GPU proof IS its high-water mark) leaves the arena as it is, so the next proof re-allocates nothing
-    if (proof->ws_overflow_slabs && ctx->arena_high_water + ((size_t)1 << 17) > ctx->arena_learned)
-        ctx->arena_learned = ctx->arena_high_water + ((size_t)1 << 17);
+    if (proof->ws_overflow_slabs && ctx->bump.high_water + ((size_t)1 << 17) > ctx->arena_learned)
+        ctx->arena_learned = ctx->bump.high_water + ((size_t)1 << 17);
 }
 
 // Scope guards of a proof.  prove_impl declares them in this order, so they end in the reverse one: the FRI object first,
@@ -1109,7 +1109,7 @@ int bj_prove(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_variables, const 
     const unsigned group = bj::env().prove_h2d_group;
     const HostWitness hw{h_variables, h_multiplicities, group, false};
     // the copies are queued inside the proof (after the workspace is reserved); a previous proof on this context has drained
-    return prove_impl(ctx, S, ctx->wit_stage, ctx->wit_stage + (size_t)S->layout.multiplicity() * n, h_public_values, out, &hw, h_multiplicities == nullptr);
+    return prove_impl(ctx, S, ctx->wit_stage.p, ctx->wit_stage.p + (size_t)S->layout.multiplicity() * n, h_public_values, out, &hw, h_multiplicities == nullptr);
 }
 
 }  // extern "C"
@@ -1143,11 +1143,11 @@ int prove_host_copy_first(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_vari
     if (mode == 2) {   // transfer and transform in groups as bj_prove does, but ONE leaf kernel at the end: the sibling lane's kernels
                        // cover the transfer, so nothing is gained by absorbing group by group (extra launches, capacity round trips)
         const HostWitness hw{h_variables, h_multiplicities, env().prove_h2d_group, true};
-        return prove_impl(ctx, S, ctx->wit_stage, ctx->wit_stage + vw, h_public_values, out, &hw, h_multiplicities == nullptr);
+        return prove_impl(ctx, S, ctx->wit_stage.p, ctx->wit_stage.p + vw, h_public_values, out, &hw, h_multiplicities == nullptr);
     }
-    BJ_HIP(ctx, hipMemcpyAsync(ctx->wit_stage, h_variables, vw * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (S->lookup_reps && h_multiplicities) BJ_HIP(ctx, hipMemcpyAsync(ctx->wit_stage + vw, h_multiplicities, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = prove_impl(ctx, S, ctx->wit_stage, ctx->wit_stage + vw, h_public_values, out, nullptr, h_multiplicities == nullptr);
+    BJ_HIP(ctx, hipMemcpyAsync(ctx->wit_stage.p, h_variables, vw * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (S->lookup_reps && h_multiplicities) BJ_HIP(ctx, hipMemcpyAsync(ctx->wit_stage.p + vw, h_multiplicities, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = prove_impl(ctx, S, ctx->wit_stage.p, ctx->wit_stage.p + vw, h_public_values, out, nullptr, h_multiplicities == nullptr);
     (void)hipStreamSynchronize(ctx->stream);   // no queued copy may read the caller's witness after this returns
     return rc;
 }

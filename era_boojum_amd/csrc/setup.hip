@@ -218,7 +218,7 @@ int bj::setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_si
             if ((rc = bj::ensure_twiddles(ctx, s->log_n + s->log_L, false))) return bail(rc);
             if (hipMalloc((void **)&s->d_inv_xm1, Qe * 8) != hipSuccess)
                 return bail(bj::fail(ctx, BJ_ERR_OOM, "bj_setup_create: device allocation failed"));
-            bj::launch_inv_x_minus_one(ctx->tw_fwd, Qe, (size_t)s->c0 * n, s->d_inv_xm1, ctx->stream);
+            bj::launch_inv_x_minus_one(ctx->tw_fwd.p, Qe, (size_t)s->c0 * n, s->d_inv_xm1, ctx->stream);
             if (hipGetLastError() != hipSuccess) return bail(bj::fail(ctx, BJ_ERR_HIP, "bj_setup_create: launch failed"));
         }
     }

@@ -101,7 +101,7 @@ int placement_workspace(bj_ctx *ctx, unsigned num_vars, unsigned log_n, size_t s
     BJ_HIP(ctx, rocprim::radix_sort_pairs(nullptr, w->sort_bytes, k, v, w->cells, 0, 32, ctx->stream));
     const size_t half = (w->cells + 1) / 2, sort_elems = (w->sort_bytes + 7) / 8;   // a u32 array of `cells` in u64 words
     if (int rc = ensure_scratch(ctx, 4 * half + sort_elems + num_vars + 1 + staging_elems)) return rc;
-    u64 *p = ctx->d_scratch;
+    u64 *p = ctx->d_scratch.p;
     w->keys[0] = (u32 *)p;
     w->keys[1] = (u32 *)(p + half);
     w->vals[0] = (u32 *)(p + 2 * half);
@@ -140,7 +140,7 @@ int sigmas_from_keys(bj_ctx *ctx, const PlacementWorkspace &w, unsigned num_vars
     size_t bytes = w.sort_bytes;
     BJ_HIP(ctx, rocprim::radix_sort_pairs(w.sort_tmp, bytes, keys, vals, w.cells, 0, 32, ctx->stream));
     hipLaunchKernelGGL(sigma_scatter_kernel, dim3(blocks256(w.cells)), dim3(256), 0, ctx->stream, (const u32 *)keys.current(),
-                       (const u32 *)vals.current(), w.cells, (const u64 *)w.non_res, (const u64 *)ctx->tw_fwd, log_n, d_sigmas, sig_stride);
+                       (const u32 *)vals.current(), w.cells, (const u64 *)w.non_res, (const u64 *)ctx->tw_fwd.p, log_n, d_sigmas, sig_stride);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
 }

@@ -35,7 +35,7 @@ int bj_copy_perm_stage2(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride, 
     if (int rc = bj::h2d_async(ctx, nr.p, h_non_residues, 8 * (size_t)num_vars)) return rc;
     bool small_k = true;
     for (unsigned c = 0; c < num_vars; c++) small_k = small_k && gl::canon(h_non_residues[c]) < ((u64)1 << 32);
-    const bj::CopyPermArg cp{{d_vars, var_stride}, {d_sigmas, sig_stride}, nr.p, num_vars, chunk, log_n, ctx->tw_fwd, h_beta, h_gamma, small_k};
+    const bj::CopyPermArg cp{{d_vars, var_stride}, {d_sigmas, sig_stride}, nr.p, num_vars, chunk, log_n, ctx->tw_fwd.p, h_beta, h_gamma, small_k};
     bj::launch_copy_perm_stage2(cp, tmp.p, d_z, partials, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);
     return BJ_OK;
@@ -157,7 +157,7 @@ int bj_quotient_copy_perm(bj_ctx *ctx, const uint64_t *d_vars, size_t var_stride
     if (int rc = bj::h2d_async(ctx, al.p, h_alphas + 2, 16 * (size_t)n_chunks)) return rc;
     bool small_k = true;
     for (unsigned c = 0; c < num_vars; c++) small_k = small_k && gl::canon(h_non_residues[c]) < ((u64)1 << 32);
-    const bj::CopyPermArg cp{{d_vars, var_stride}, {d_sigmas, sig_stride}, nr.p, num_vars, chunk, log_n, ctx->tw_fwd, h_beta, h_gamma, small_k};
+    const bj::CopyPermArg cp{{d_vars, var_stride}, {d_sigmas, sig_stride}, nr.p, num_vars, chunk, log_n, ctx->tw_fwd.p, h_beta, h_gamma, small_k};
     bj::launch_quotient_copy_perm(cp, bj::Cols{d_stage2, stage2_stride}, log_lde, h_alphas /* the L1 power; al: the chunks' that follow it */,
                                   bj::TermSink{al.p, num_points, d_out0, d_out1}, first_point, nullptr, ctx->stream);
     BJ_CHECK_LAUNCH(ctx);

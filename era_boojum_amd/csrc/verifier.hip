@@ -705,7 +705,7 @@ int prepare(const bj_vk *K, const u64 *W, size_t n_words, unsigned flags, Prepar
 
 VerifyDeepShared deep_shared(const bj_ctx *ctx, const Geometry &G) {
     VerifyDeepShared sh{};
-    sh.roots = ctx->tw_inv;
+    sh.roots = ctx->tw_inv.p;
     sh.query_words = (uint32_t)G.sizes.query_words;
     sh.n_sets = G.n_sets;
     sh.n_fri = G.n_fri;
@@ -778,10 +778,10 @@ int judge(bj_ctx *ctx, const bj_vk *K, const Prepared *R, size_t n, bj_verify_re
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_verify_batch: the batch has more than 2^31 query openings");
     if (int rc = bj::ensure_scratch(ctx, P.total_words)) return rc;   // before anything is uploaded
     if (int rc = bj::ensure_twiddles(ctx, G.LOGN, true)) return rc;
-    u64 *D = ctx->d_scratch;
+    u64 *D = ctx->d_scratch.p;
     hipStream_t st = ctx->stream;
     for (auto &e : T->ev)
-        if (!e) BJ_HIP(ctx, hipEventCreate(&e));
+        if (int rc = bj::ensure_event(ctx, e)) return rc;
     std::vector<u64> block(P.host_words);
     for (size_t k = 0; k < dev.size(); k++)
         std::memcpy(block.data() + (P.tables[k] - P.host_block), R[dev[k]].tables.data(), R[dev[k]].tables.size() * 8);

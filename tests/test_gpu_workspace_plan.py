@@ -104,8 +104,9 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def plan_summary(case):
-    """(total, allowance, entries, exact) of the plan of one rank of `case`, in words / entries."""
+def plan_summary(case, alpha_terms=1):
+    """(total, allowance, entries, exact) of the plan of one rank of `case`, in words / entries.  alpha_terms: the powers of the
+    quotient challenge, which the total and the exact words depend on and the other two do not."""
     cname, entry, opt = CASES[case]
     c = circuit(cname)
     lib = C.CDLL(build.build_canon_helper())
@@ -117,7 +118,7 @@ def plan_summary(case):
     absorbing = HOST_NOT_ABSORBING if opt.get("no_absorb") else HOST_ABSORBING   # the setups here hash with Poseidon2
     flags = [0, int(bool(opt.get("count")) and entry == "dev" and c.lookup_reps > 0), absorbing if entry == "host" else HOST_NONE, int(new_pow != 0)]
     out = (C.c_size_t * 4)()
-    lib.bj_workspace_plan_summary(u(nine), C.c_uint(FRI_LDE), C.c_uint(CAP), C.c_uint(2 if entry == "sharded" else 1), C.c_uint(1),
+    lib.bj_workspace_plan_summary(u(nine), C.c_uint(FRI_LDE), C.c_uint(CAP), C.c_uint(2 if entry == "sharded" else 1), C.c_uint(alpha_terms),
                                   u([p[0] for p in c.public_inputs]), u([p[1] for p in c.public_inputs]), C.c_size_t(len(c.public_inputs)),
                                   u(flags), (C.c_uint32 * 32)(*sched), C.c_size_t(len(sched)), C.c_size_t(nq), out)
     return tuple(int(x) for x in out)

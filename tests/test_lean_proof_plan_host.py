@@ -62,4 +62,4 @@ def test_the_library_reads_the_switch_without_a_device():
     assert os.environ.get("BJ_PROOF_LEAN") == before
     header = open(os.path.join(ROOT, "include", "boojum_hip.h")).read()
     assert "BJ_PROOF_LEAN" in header and "proof bytes are identical" in header
-    assert 'set("BJ_PROOF_LEAN")' in open(os.path.join(CSRC, "abi.hip")).read()
+    assert 'set("BJ_PROOF_LEAN")' in open(os.path.join(CSRC, "ctx.hip")).read()

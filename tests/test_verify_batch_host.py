@@ -107,11 +107,11 @@ def test_rust_verify_batch_hip_uses_declared_symbols_only():
 
 
 def test_thread_switch_is_read_with_the_other_switches_only():
-    """BJ_VERIFY_THREADS is read in csrc/abi.hip::load_env and clamped to 1..16 there; nothing on the call path reads the
+    """BJ_VERIFY_THREADS is read in csrc/ctx.hip::load_env and clamped to 1..16 there; nothing on the call path reads the
     environment or asks the machine for its core count (that 1 and 16 threads report alike: tests/test_gpu_verify_batch.py)."""
     csrc = os.path.join(ROOT, "era_boojum_amd", "csrc")
     readers = [f for f in sorted(os.listdir(csrc)) if "BJ_VERIFY_THREADS\"" in open(os.path.join(csrc, f)).read()]
-    assert readers == ["abi.hip"]
-    assert "e.verify_threads = v < 1 ? 1u : v > 16 ? 16u : (unsigned)v;" in open(os.path.join(csrc, "abi.hip")).read()
+    assert readers == ["ctx.hip"]
+    assert "e.verify_threads = v < 1 ? 1u : v > 16 ? 16u : (unsigned)v;" in open(os.path.join(csrc, "ctx.hip")).read()
     verifier = open(os.path.join(csrc, "verifier.hip")).read()
     assert "hardware_concurrency" not in verifier and "getenv" not in verifier and "bj::env().verify_threads" in verifier
