@@ -100,4 +100,25 @@ inline NttPlan ntt_plan(const NttShape &sh) {
 // the two-pass plan: the only one that reads the tiled layout, and the one whose inverse transform can store it
 inline bool ntt_plan_is_two_pass(const NttShape &sh) { return ntt_plan(sh).pass[0].kind == NttPassKind::Front10; }
 
+// Columns per workgroup of the strided and local passes (grid: tiles x ceil(n_cols / cpb) x n_cosets, tiles = 2^(log_n - 12)).
+inline unsigned pick_cols_per_block(unsigned tiles, unsigned n_cols, unsigned n_cosets) {
+    // amortise the per-workgroup twiddle preparation over several columns, but keep >= ~4096 workgroups in flight
+    unsigned cpb = 8;
+    while (cpb > 1 && (size_t)tiles * ((n_cols + cpb - 1) / cpb) * n_cosets < 4096) cpb >>= 1;
+    return cpb;
+}
+
+// ntt_front10 runs at most eight cosets per launch (a tile's workgroups are one dispatch window on one XCD): the launch that starts
+// at coset c0 takes front10_launch_cosets(n_cosets, c0) of them, the next one starts FRONT10_COSETS_PER_LAUNCH further on.
+constexpr unsigned FRONT10_COSETS_PER_LAUNCH = 8;
+inline unsigned front10_launch_cosets(unsigned n_cosets, unsigned c0) {
+    return n_cosets - c0 < FRONT10_COSETS_PER_LAUNCH ? n_cosets - c0 : FRONT10_COSETS_PER_LAUNCH;
+}
+// columns per workgroup of one such launch (grid: tiles * nc x ceil(n_cols / cpb), tiles = 2^(12 - log2(lo values per tile)))
+inline unsigned front10_cols_per_block(unsigned tiles, unsigned n_cols, unsigned nc) {
+    unsigned cpb = 8;
+    while (cpb > 1 && (size_t)tiles * nc * ((n_cols + cpb - 1) / cpb) < 4096) cpb >>= 1;
+    return cpb;
+}
+
 }  // namespace bj

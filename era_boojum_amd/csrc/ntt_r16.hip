@@ -20,6 +20,7 @@
 // ds_read_b64 / ds_write_b64 (64 x 4-byte banks).
 #include "gl.h"
 #include "kernels.h"
+#include "ntt_plan.h"
 #include "tiled_layout.h"
 
 #include <cstdio>
@@ -776,12 +777,7 @@ __global__ void __launch_bounds__(256) tiled_permute_kernel(const u64 *in, u64 *
     }
 }
 
-static unsigned pick_cols_per_block(unsigned tiles, unsigned n_cols, unsigned n_cosets) {
-    // amortise the per-workgroup twiddle preparation over several columns, but keep >= ~4096 workgroups in flight
-    unsigned cpb = 8;
-    while (cpb > 1 && (size_t)tiles * ((n_cols + cpb - 1) / cpb) * n_cosets < 4096) cpb >>= 1;
-    return cpb;
-}
+// pick_cols_per_block, front10_launch_cosets, front10_cols_per_block: ntt_plan.h (tests/ntt_plan_check.cpp checks them on the host)
 
 // which instance of a pass serves io: 0 plain forward, 1 forward on a coset (per-round scales), 2 inverse (the inverse root's table; the
 // coset factors of an inverse transform are applied behind it, never as per-round scales)
@@ -884,10 +880,9 @@ void launch_ntt_front10(const NttIo &io, u64 *d_table, bool tiled_in, hipStream_
     const int lb = tiled_in ? TILED_LB : LBN;
     const unsigned tiles = 1u << (io.log_n - 10 - lb);
     const size_t n = (size_t)1 << io.log_n;
-    for (unsigned c0 = 0; c0 < n_cosets; c0 += 8) {   // at most eight cosets per launch: a tile's workgroups are one dispatch window on one XCD
-        const unsigned nc = n_cosets - c0 < 8 ? n_cosets - c0 : 8;
-        unsigned cpb = 8;
-        while (cpb > 1 && (size_t)tiles * nc * ((n_cols + cpb - 1) / cpb) < 4096) cpb >>= 1;
+    for (unsigned c0 = 0; c0 < n_cosets; c0 += FRONT10_COSETS_PER_LAUNCH) {   // at most eight cosets per launch: a tile's workgroups are one dispatch window on one XCD
+        const unsigned nc = front10_launch_cosets(n_cosets, c0);
+        const unsigned cpb = front10_cols_per_block(tiles, n_cols, nc);
         F10Args a{io.in, io.out + (size_t)c0 * n, d_table + (size_t)c0 * 1024, io.log_n, n_cols, cpb, nc, io.in_col_stride, io.out_col_stride};
         dim3 grid(tiles * nc, (n_cols + cpb - 1) / cpb, 1);
         void (*k)(F10Args);

@@ -2,7 +2,10 @@
 // for every log_n 0..30 x {aligned, unaligned} x {two_pass on, off} the plan tiles the rounds [0, log_n), obeys the rules each
 // kernel's launcher relies on, and is the row of the table below.  The table is the plan launch_ntt_passes ran before the plan
 // became a value, recorded by running that function with every launch replaced by a print; it is literal on purpose.
+// Then the launch arithmetic next to the plan: the columns per workgroup of the strided and local passes and the coset split of
+// ntt_front10, for the wide-LDE shapes of tests/test_gpu_lde_cosets.py.
 #include "ntt_plan.h"
+#include "tiled_layout.h"
 
 #include <cstdio>
 #include <string>
@@ -103,10 +106,101 @@ static void check(const NttShape &sh) {
     CHECK(ntt_plan_is_two_pass(sh) == (text == "F10 L12"));
 }
 
+static std::string plan_text(const NttShape &sh) {
+    const NttPlan plan = ntt_plan(sh);
+    std::string text;
+    for (unsigned i = 0; i < plan.n_passes; i++) text += (i ? " " : "") + name(plan.pass[i]);
+    return text;
+}
+
+// The wide-LDE shapes of tests/test_gpu_lde_cosets.py that exist to run the column loop of a strided or local workgroup more than once
+// (tests/lde_coset_shapes.py: MULTI_COLUMN; tests/test_ntt_plan_host.py compares the lines printed here with that list).  The GPU
+// cannot show cols_per_block: the claim is kept here, literal, against pick_cols_per_block.
+struct CpbCase {
+    unsigned log_n;
+    bool aligned;
+    unsigned n_cols, n_cosets;
+    const char *plan;
+    unsigned cpb, groups, last;   // columns per workgroup, workgroups per tile and coset, columns of the last one
+};
+static const CpbCase CPB_CASES[] = {
+    {12, true, 127, 64, "L12", 2, 64, 1},
+    {18, true, 3, 64, "F4 S4 L10", 8, 1, 3},
+    {18, false, 3, 64, "F5 S4 L9", 8, 1, 3},
+    {17, true, 3, 64, "R1 S4 L12", 2, 2, 1},
+};
+// The same shapes at the coset counts the suite had before (at most 8): one column per workgroup, which is why the loop never ran twice.
+static const CpbCase CPB_ONE[] = {
+    {12, true, 127, 8, "L12", 1, 127, 1},
+    {18, true, 3, 8, "F4 S4 L10", 1, 3, 1},
+    {17, true, 3, 8, "R1 S4 L12", 1, 3, 1},
+};
+
+static void check_cpb(const CpbCase &c, bool print) {
+    const NttShape sh{c.log_n, c.aligned, true};
+    const unsigned i = 0;
+    const unsigned tiles = 1u << (c.log_n - 12);   // launch_ntt_local12, launch_ntt_strided (ntt_r16.hip)
+    const unsigned cpb = pick_cols_per_block(tiles, c.n_cols, c.n_cosets);
+    const unsigned groups = (c.n_cols + cpb - 1) / cpb, last = c.n_cols - (groups - 1) * cpb;
+    CHECK(plan_text(sh) == c.plan);
+    CHECK(cpb == c.cpb);
+    CHECK(groups == c.groups);
+    CHECK(last == c.last);
+    CHECK(last >= 1 && last <= cpb);
+    if (print)
+        printf("cpb log_n=%u aligned=%d n_cols=%u n_cosets=%u plan=\"%s\" cpb=%u groups=%u last=%u\n", c.log_n, c.aligned, c.n_cols, c.n_cosets,
+               plan_text(sh).c_str(), cpb, groups, last);
+}
+
+// The launches of launch_ntt_front10 (ntt_r16.hip) for the three 2^22 cases (tests/lde_coset_shapes.py: FRONT10): its loop is
+//     for (c0 = 0; c0 < n_cosets; c0 += FRONT10_COSETS_PER_LAUNCH) { nc = front10_launch_cosets(n_cosets, c0); cpb = front10_cols_per_block(tiles, n_cols, nc); ... }
+// with tiles = 2^(12 - LB): LB = 4 for natural-order input (LBN there), TILED_LB for tiled input.
+struct Front10Case {
+    bool tiled;
+    unsigned n_cols, n_cosets;
+    const char *launches;   // "c0:nc:cpb,..."
+};
+static const Front10Case FRONT10_CASES[] = {
+    {false, 1, 3, "0:3:1"},
+    {false, 1, 9, "0:8:1,8:1:1"},
+    {true, 1, 11, "0:8:8,8:3:1"},
+};
+
+static void check_front10(const Front10Case &c) {
+    const NttShape sh{22, true, true};
+    const unsigned i = 0;
+    const unsigned tiles = 1u << (12 - (c.tiled ? TILED_LB : 4));
+    std::string text;
+    unsigned covered = 0;
+    for (unsigned c0 = 0; c0 < c.n_cosets; c0 += FRONT10_COSETS_PER_LAUNCH) {
+        const unsigned nc = front10_launch_cosets(c.n_cosets, c0);
+        CHECK(nc >= 1 && nc <= 8 && c0 == covered);
+        covered += nc;
+        text += (c0 ? "," : "") + std::to_string(c0) + ":" + std::to_string(nc) + ":" + std::to_string(front10_cols_per_block(tiles, c.n_cols, nc));
+    }
+    CHECK(covered == c.n_cosets);
+    CHECK(text == c.launches);
+    CHECK(ntt_plan_is_two_pass(sh));
+    printf("front10 tiled=%d n_cols=%u n_cosets=%u launches=%s\n", c.tiled, c.n_cols, c.n_cosets, text.c_str());
+}
+
 int main() {
     for (unsigned log_n = 0; log_n <= 30; log_n++)
         for (int aligned = 0; aligned < 2; aligned++)
             for (int two_pass = 0; two_pass < 2; two_pass++) check(NttShape{log_n, aligned != 0, two_pass != 0});
+
+    for (const CpbCase &c : CPB_CASES) check_cpb(c, true);
+    for (const CpbCase &c : CPB_ONE) check_cpb(c, false);
+    for (const Front10Case &c : FRONT10_CASES) check_front10(c);
+    {   // every launch of 1..64 cosets: whole launches of eight and one short one, in order, nothing left over
+        const NttShape sh{22, true, true};
+        unsigned i = 0;
+        for (unsigned n_cosets = 1; n_cosets <= 64; n_cosets++) {
+            unsigned covered = 0, launches = 0;
+            for (unsigned c0 = 0; c0 < n_cosets; c0 += FRONT10_COSETS_PER_LAUNCH, launches++) covered += front10_launch_cosets(n_cosets, c0);
+            CHECK(covered == n_cosets && launches == (n_cosets + 7) / 8);
+        }
+    }
 
     // ntt_aligned16: both pointers on 16-byte boundaries and both strides even
     alignas(16) static unsigned char buf[64];

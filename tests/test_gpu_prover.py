@@ -25,7 +25,8 @@ def _compare(pg, po):
         assert qg["fri_queries"] == qo["fri_queries"]
 
 
-@pytest.mark.parametrize("log_n,fri_lde,cap,sec,bits", [(9, 8, 16, 30, 2), (8, 2, 4, 20, 2), (12, 8, 16, 40, 2), (14, 4, 16, 50, 4)])
+@pytest.mark.parametrize("log_n,fri_lde,cap,sec,bits", [(9, 8, 16, 30, 2), (8, 2, 4, 20, 2), (12, 8, 16, 40, 2), (14, 4, 16, 50, 4),
+                                                      (13, 16, 16, 30, 2)])      # 16 cosets through real passes (R1 L12)
 def test_hip_proof_equals_oracle_proof_and_verifies(log_n, fri_lde, cap, sec, bits):
     c = S.sha_shaped_circuit(log_n, seed=100 + log_n, table_bits=bits)
     osetup = OP.Setup(c, fri_lde, cap, threads=8)
