@@ -7,6 +7,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _abi
+from . import _abi_diag
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 P = (1 << 64) - (1 << 32) + 1
@@ -22,6 +23,7 @@ _GateDesc, _Circuit, _ProofConfig = _abi.bj_gate_desc, _abi.bj_circuit, _abi.bj_
 _Comm, _ALL_GATHER_FN, _ALL_GATHER_STREAM_FN = _abi.bj_comm, _abi.bj_comm_all_gather, _abi.bj_comm_all_gather_stream
 _HOST_EXCHANGE_FN = _abi.bj_host_exchange_fn
 _VerifyReport, _UnsatReport, _CopyReport = _abi.bj_verify_report, _abi.bj_unsat_report, _abi.bj_copy_report
+_UnsatEntry = _abi_diag.bj_unsat_entry      # include/boojum_hip_diag.h: diagnostics beside the ABI, generated like _abi.py
 
 
 class BoojumHipError(RuntimeError):
@@ -49,7 +51,7 @@ def load_library():
             raise BoojumHipError("%s is missing: run `python -m era_boojum_amd.build` (hipcc, gfx950). "
                                  "There is no CPU fallback." % path)
         lib = C.CDLL(path)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_abi_diag.SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
             fn.restype = res
             fn.argtypes = args
@@ -1018,6 +1020,21 @@ class SatisfiabilityReport:
         return "Unsatisfied at table row %d: multiplicities sum to %d, %d lookups" % (self.row, self.expected, self.value)
 
 
+@dataclass(frozen=True)
+class UnsatEntry:
+    """bj_unsat_entry: one failure of a witness (bj_list_unsatisfied); the fields mean what they mean in SatisfiabilityReport."""
+    kind: int
+    gate: int
+    repetition: int
+    term: int
+    row: int
+    value: int
+    expected: int
+
+    def fields(self):
+        return (self.kind, self.gate, self.repetition, self.term, self.row, self.value, self.expected)
+
+
 COPY_OK, COPY_SIGMA_INVALID, COPY_SIGMA_NOT_PERMUTATION, COPY_VALUE_MISMATCH = (
     _abi.BJ_COPY_OK, _abi.BJ_COPY_SIGMA_INVALID, _abi.BJ_COPY_SIGMA_NOT_PERMUTATION, _abi.BJ_COPY_VALUE_MISMATCH)     # bj_copy_kind
 NO_CELL = 0xFFFFFFFF                # bj_sigma_cells: a word in no coset; bj_copy_report.variable: no placement index
@@ -1379,6 +1396,47 @@ class ProverSetup:
         self._ctx._check(self._lib.bj_check_satisfied_from_dumps(self._ctx._h, self._h, w, len(w), v, len(v) if v else 0, x, len(x) if x else 0,
                                                                  C.byref(r)))
         return self._report(r)
+
+    @staticmethod
+    def _entries(buf, n):
+        return [UnsatEntry(int(e.kind), int(e.gate), int(e.repetition), int(e.term), int(e.row), int(e.value), int(e.expected)) for e in (buf[:n] if n else [])]
+
+    def list_unsatisfied_dev(self, d_variables, d_multiplicities, capacity=1024):
+        """bj_list_unsatisfied on a witness already in HBM: (the first min(capacity, total) UnsatEntry records in the order of
+        include/boojum_hip.h, the five totals — [k] entries of kind k in the whole trace, [0] their sum)."""
+        buf = (_UnsatEntry * capacity)() if capacity else None
+        n, totals = C.c_size_t(0), (C.c_uint64 * 5)()
+        self._ctx._check(self._lib.bj_list_unsatisfied(self._ctx._h, self._h, d_variables, d_multiplicities, buf, capacity, C.byref(n), totals))
+        return self._entries(buf, n.value), tuple(int(x) for x in totals)
+
+    def list_unsatisfied(self, variables=None, multiplicities=None, capacity=1024):
+        """Every place where the witness fails the circuit (bj_list_unsatisfied), not the first one: (entries, totals) as
+        list_unsatisfied_dev returns them.  Arrays default to the circuit's own and are uploaded for the call."""
+        c = self.circuit
+        v = np.ascontiguousarray(c.variables if variables is None else variables, dtype=np.uint64)
+        if self.num_witness_cols and v.shape[0] == c.num_vars:
+            v = np.ascontiguousarray(np.concatenate([v, c.witness], axis=0))
+        d_v = self._ctx.upload(v)
+        d_m = None
+        try:
+            if c.lookup_reps:
+                d_m = self._ctx.upload(np.ascontiguousarray(c.multiplicities if multiplicities is None else multiplicities, dtype=np.uint64))
+            return self.list_unsatisfied_dev(d_v, d_m, capacity)
+        finally:
+            self._ctx.free(d_v)
+            if d_m is not None:
+                self._ctx.free(d_m)
+
+    def list_unsatisfied_from_dumps(self, witness_vec_dump, variables_hint_dump, witness_hint_dump=None, capacity=1024):
+        """bj_list_unsatisfied_from_dumps: the arguments of prove_from_dumps, the result of list_unsatisfied."""
+        w = bytes(witness_vec_dump)
+        v = bytes(variables_hint_dump) if variables_hint_dump is not None else None
+        x = bytes(witness_hint_dump) if witness_hint_dump is not None else None
+        buf = (_UnsatEntry * capacity)() if capacity else None
+        n, totals = C.c_size_t(0), (C.c_uint64 * 5)()
+        self._ctx._check(self._lib.bj_list_unsatisfied_from_dumps(self._ctx._h, self._h, w, len(w), v, len(v) if v else 0, x, len(x) if x else 0,
+                                                                  buf, capacity, C.byref(n), totals))
+        return self._entries(buf, n.value), tuple(int(x) for x in totals)
 
     def check_copy_constraints(self, d_variables):
         """bj_check_copy_constraints on a witness in HBM (the pointer prove_dev takes): a CopyReport, true when every copy

@@ -8,6 +8,7 @@
 //            per looked-up tuple, then expected (sum of the class's multiplicities) against counted per class.
 //   report   first failure in the order of include/boojum_hip.h.
 // All scratch is the context's (ensure_scratch); nothing here allocates, and no input is written.
+#include "check_shared.h"
 #include "ctx.h"
 #include "lookup_index.h"
 #include "setup.h"
@@ -17,11 +18,9 @@
 
 using gl::u64;
 using namespace bj::lookup;   // LookupShape, find_class, lookup_build_kernel, block_min_count, the slot conventions
+using namespace bj::check;    // CHECK_BLOCK, the weights, lookup_expected_kernel, expected_value (check_shared.h)
 
 namespace {
-
-constexpr unsigned CHECK_BLOCK = bj::lookup::INDEX_BLOCK;   // threads per block of every kernel here; also the points a row is replicated over
-constexpr u64 ALPHA_SEED = 0x626A5F636865636Bull;   // "bj_check" (include/boojum_hip.h)
 
 // counters the kernels reduce into: [2k] smallest key, [2k + 1] number, k = bj_unsat_kind - 1
 struct Counters {
@@ -72,24 +71,6 @@ __global__ void __launch_bounds__(CHECK_BLOCK) lookup_probe_kernel(LookupShape L
     block_min_count(live && !hit, key, miss_min, miss_cnt);
 }
 
-// one thread per table row: remember its class, add its canonical multiplicity to the class's 96-bit sum (lo, carries in hi)
-__global__ void __launch_bounds__(CHECK_BLOCK) lookup_expected_kernel(LookupShape L, const uint32_t *slots, const u64 *mult, uint32_t *class_of,
-                                                                     unsigned long long *lo, uint32_t *hi) {
-    const size_t r = (size_t)blockIdx.x * CHECK_BLOCK + threadIdx.x;
-    if (r >= L.n) return;
-    u64 t[MAX_TUPLE];
-    load_table_row(L, r, t);
-    const uint32_t cls = find_class(L, slots, t);
-    class_of[r] = cls;
-    const u64 m = gl::canon(mult[r]);
-    if (m) {
-        const u64 old = atomicAdd(lo + cls, (unsigned long long)m);
-        if (old + m < old) atomicAdd(hi + cls, 1u);
-    }
-}
-
-__host__ __device__ __forceinline__ u64 expected_value(u64 lo, uint32_t hi) { return gl::canon(gl::reduce128((u64)hi, lo)); }
-
 // one thread per table row; a representative compares its class's sum with its count (an integer below p)
 __global__ void __launch_bounds__(CHECK_BLOCK) lookup_compare_kernel(size_t n, const uint32_t *class_of, const unsigned long long *count,
                                                                     const unsigned long long *lo, const uint32_t *hi, u64 *bad_min, u64 *bad_cnt) {
@@ -98,15 +79,6 @@ __global__ void __launch_bounds__(CHECK_BLOCK) lookup_compare_kernel(size_t n, c
     if (r < n && class_of[r] == (uint32_t)r) bad = expected_value(lo[r], hi[r]) != (u64)count[r];
     block_min_count(bad, (u64)r, bad_min, bad_cnt);
 }
-
-u64 splitmix64(u64 &state) {
-    u64 z = (state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-unsigned blocks_for(size_t items) { return (unsigned)((items + CHECK_BLOCK - 1) / CHECK_BLOCK); }
 
 int check_impl(bj_ctx *ctx, const bj_setup *S, const u64 *d_variables, const u64 *d_multiplicities, bj_unsat_report *out) {
     if (int rc = bj::bind(ctx)) return rc;

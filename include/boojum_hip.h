@@ -835,6 +835,7 @@ int bj_check_satisfied(bj_ctx *ctx, const bj_setup *setup, const uint64_t *d_var
 int bj_check_satisfied_from_dumps(bj_ctx *ctx, const bj_setup *setup, const void *witness_vec, size_t witness_vec_len,
                                   const void *variables_hint, size_t variables_hint_len, const void *witness_hint,
                                   size_t witness_hint_len, bj_unsat_report *out);
+/* Every failure instead of the first, in this order carried through to the end: bj_list_unsatisfied in boojum_hip_diag.h. */
 
 /* ---- which cells break a copy constraint: the copy-permutation argument (src/cs/implementations/copy_permutation.rs) cell by cell ----
  * Raw columns handed to bj_prove / bj_prove_dev / bj_prove_async can satisfy every gate (bj_check_satisfied says BJ_SAT) and

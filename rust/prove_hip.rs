@@ -35,6 +35,11 @@ use crate::gpu_synthesizer::{GPUDataCapture, GatesSetForGPU, Index, Relation};
 #[path = "boojum_hip_sys.rs"]
 pub mod sys;
 use sys::*;
+// diagnostics beside the ABI (include/boojum_hip_diag.h): their generated declarations, and `HipSetup::list_unsatisfied` over them
+#[path = "boojum_hip_diag_sys.rs"]
+pub mod diag_sys;
+#[path = "list_unsatisfied_hip.rs"]
+mod list_unsatisfied_hip;
 
 type F = GoldilocksField;
 

@@ -23,6 +23,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "boojum_hip.h")
+DIAG_HEADER = os.path.join(ROOT, "include", "boojum_hip_diag.h")   # diagnostics beside the ABI: its own generated modules
 
 CType = collections.namedtuple("CType", "base consts extent fn")
 CType.__new__.__defaults__ = ((), None, None)
