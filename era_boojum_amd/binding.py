@@ -147,6 +147,18 @@ class Context:
         self.h2d(d, arr)
         return d
 
+    def witness_gather(self, d_placement, cols, log_n, d_values, n_values, d_cells):
+        """bj_witness_gather (boojum_hip_diag.h), the kernel behind prove_values on device arrays: d_cells[i] =
+        d_values[d_placement[i]] over a u32 placement [cols][n].  Returns True if a cell named a value at or beyond n_values."""
+        bad = C.c_uint(0)
+        self._check(self._lib.bj_witness_gather(self._h, C.c_void_p(d_placement), cols, log_n, C.c_void_p(d_values), n_values,
+                                                C.c_void_p(d_cells), C.byref(bad)))
+        return bool(bad.value)
+
+    def witness_gather_sweep_cells(self):
+        """bj_witness_gather_sweep_cells: the cells one sweep of the gather's grid covers on this device."""
+        return int(self._lib.bj_witness_gather_sweep_cells(self._h))
+
     def timer_start(self):
         self._check(self._lib.bj_timer_start(self._h))
 
@@ -1320,6 +1332,37 @@ class ProverSetup:
         t = C.c_void_p()
         self._ctx._check(self._lib.bj_prove_async(self._ctx._h, self._h, _np_ptr(v), _np_ptr(m) if c.lookup_reps and not count_multiplicities else None,
                                                   _np_ptr(pv), C.byref(t)))
+        return _Ticket(t, (v, m), self, self._ctx)
+
+    def set_witness_placement(self, wit_ids):
+        """bj_setup_set_witness_placement: wit_ids [num_witness_cols][n] integers, negative = empty cell (what `DenseWitnessCopyHint`
+        encodes; same layout as the variables' hint).  With it `prove_values` works on a circuit with non-copiable witness columns."""
+        from . import memcopy_format
+        blob = memcopy_format.write_variables_hint(wit_ids)
+        self._ctx._check(self._lib.bj_setup_set_witness_placement(self._ctx._h, self._h, blob, len(blob)))
+
+    @staticmethod
+    def _values_arrays(all_values, multiplicities):
+        v = np.ascontiguousarray(all_values, dtype=np.uint64)
+        m = None if multiplicities is None else np.ascontiguousarray(multiplicities, dtype=np.uint32)
+        return v, m
+
+    def prove_values(self, all_values, multiplicities=None):
+        """bj_prove_values: the proof from a WitnessVec's `all_values` and its u32 multiplicity counters (None: counted on the
+        device) on a setup made by `from_placement`; the public inputs are read through the placement.  Returns like `prove`."""
+        v, m = self._values_arrays(all_values, multiplicities)
+        h = C.c_void_p()
+        self._ctx._check(self._lib.bj_prove_values(self._ctx._h, self._h, _np_ptr(v) if v.size else None, v.size,
+                                                   m.ctypes.data_as(C.c_void_p) if m is not None else None, m.size if m is not None else 0, C.byref(h)))
+        return self._finish(h)
+
+    def prove_values_async(self, all_values, multiplicities=None):
+        """bj_prove_values_async: `prove_values` queued on one of the context's two lanes; returns a ticket for `wait`.  The
+        arrays are used in place when they are contiguous (uint64 / uint32) and kept alive by the ticket."""
+        v, m = self._values_arrays(all_values, multiplicities)
+        t = C.c_void_p()
+        self._ctx._check(self._lib.bj_prove_values_async(self._ctx._h, self._h, _np_ptr(v) if v.size else None, v.size,
+                                                         m.ctypes.data_as(C.c_void_p) if m is not None else None, m.size if m is not None else 0, C.byref(t)))
         return _Ticket(t, (v, m), self, self._ctx)
 
     def done(self, ticket):

@@ -65,10 +65,12 @@ inline size_t intt_scratch_words(size_t len, size_t cols) {   // intt_groups (ab
 // The fixed extras of a context that proves shape `s` from a host witness: the staging of the witness columns with the
 // multiplicity column behind them, the scratch of the widest inverse transform (upper bound: every witness or stage-2 column in one
 // call, T's two columns on the quotient domain) and of the multiplicity count, both twiddle tables up to the LDE domain, and the
-// scaled table of the tiled layout.  The arena is left 0.
+// scaled table of the tiled layout.  The arena is left 0.  A proof from values (s.n_values != 0, bj_prove_values) keeps all_values and
+// the u32 multiplicity counters in the staging behind the multiplicity column: values_staging_bytes more, and nothing else moves.
+inline size_t values_staging_bytes(size_t n, size_t n_values) { return n_values ? n_values * 8 + n * 4 : 0; }
 inline LaneBytes lane_extras(const WorkspaceShape &s) {
     LaneBytes b;
-    b.part[LANE_STAGING] = ((size_t)s.nW + (s.has_lookup ? 0 : 1)) * s.n * 8;
+    b.part[LANE_STAGING] = ((size_t)s.nW + (s.has_lookup ? 0 : 1)) * s.n * 8 + values_staging_bytes(s.n, s.n_values);
     size_t scratch = intt_scratch_words(s.n, s.nW > s.nS2 ? s.nW : s.nS2), t = intt_scratch_words(s.Q, 2);
     if (t > scratch) scratch = t;
     if (s.has_lookup && 2 * s.n + 2 > scratch) scratch = 2 * s.n + 2;

@@ -28,10 +28,11 @@ struct DevBuf {
     int ensure(bj_ctx *ctx, size_t need, bool *grew = nullptr);
     hipError_t drop();   // frees and zeroes; the caller has drained whatever may still use the block
 };
-// The words of the context's small block (bj_ctx::d_small).  Nothing reads or writes SHIFTS any more; the offsets behind it
-// stay where they have always been.
+// The words of the context's small block (bj_ctx::d_small).  Nothing reads or writes SHIFTS any more, but for its first word,
+// which is the flag of the witness gather (VALUES_BAD); the offsets behind it stay where they have always been.
 struct SmallBlock {
     static constexpr size_t SHIFTS = 0;                            // 64 words
+    static constexpr size_t VALUES_BAD = SHIFTS;                   // witness_gather_kernel: a cell named a value beyond all_values
     static constexpr size_t ROUND_SCALES = 64;                     // 64 cosets x 32 rounds (launch_round_scales)
     static constexpr size_t GATHER = ROUND_SCALES + 64 * 32;       // what a collective gathers before it goes to the host
     static constexpr size_t GATHER_WORDS = 4096;                   // evaluate_at sends from the first half into the second
@@ -129,6 +130,7 @@ inline gl::u64 *round_scales(bj_ctx *ctx) { return ctx->d_small + SmallBlock::RO
 inline gl::u64 *gather_area(bj_ctx *ctx) { return ctx->d_small + SmallBlock::GATHER; }
 inline gl::u64 *gather_half(bj_ctx *ctx) { return ctx->d_small + SmallBlock::GATHER_HALF; }
 inline gl::u64 *front_table(bj_ctx *ctx) { return ctx->d_small + SmallBlock::FRONT_TABLE; }
+inline unsigned *values_bad_flag(bj_ctx *ctx) { return reinterpret_cast<unsigned *>(ctx->d_small + SmallBlock::VALUES_BAD); }
 int ensure_ring(bj_ctx *ctx);                                                          // the pinned ring exists
 int ensure_event(bj_ctx *ctx, hipEvent_t &e, unsigned flags = hipEventDefault);   // e exists (created once, with `flags`)
 std::string &thread_error();   // message of the last failed call that has no context, per host thread
@@ -149,7 +151,13 @@ int pipeline_release_workspace(bj_ctx *ctx);    // bj_ctx_release_workspace on e
 void ctx_held(const bj_ctx *ctx, LaneBytes *out);
 int ctx_reserve(bj_ctx *ctx, const LaneBytes &want);
 int ctx_release_own_workspace(bj_ctx *ctx);
-int async_footprints(bj_ctx *ctx, const bj_setup *setup, LaneBytes *resident, LaneBytes *lean);
+int async_footprints(bj_ctx *ctx, const bj_setup *setup, LaneBytes *resident, LaneBytes *lean, bool values = false, size_t n_values = 0);
+// prover.hip, bj_prove_values[_async]: the refusals both share (before anything is queued), and the proof itself on a context
+// that passed them (no_absorb: a lane whose sibling is proving hashes the leaves once at the end)
+int values_check(bj_ctx *ctx, const char *who, const bj_setup *S, const uint64_t *h_values, size_t n_values, const uint32_t *h_multiplicities,
+                 size_t n_multiplicities);
+int prove_values_staged(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_values, size_t n_values, const uint32_t *h_multiplicities,
+                        size_t n_multiplicities, bj_proof **out, bool no_absorb);
 inline int stage_witness_elems(bj_ctx *ctx, size_t need) { return ctx->wit_stage.ensure(ctx, need); }   // kept for the next proof
 int ensure_scaled22(bj_ctx *ctx);                    // tw_inv_scaled22 exists (tw_inv must reach 2^22)
 int arena_reset(bj_ctx *ctx, size_t need_elems);     // a new proof: nothing taken, no slabs, at least need_elems words
@@ -211,6 +219,8 @@ int setup_create_impl(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_sigmas
                       bool lean = false);   // lean: drop the LDE once the tree stands (single device only; the callers pass env().setup_lean)
 void setup_adopt_placement(bj_setup *s, uint32_t *d_placement);   // [num_vars][n] u32, hipMalloc'ed
 const uint32_t *setup_placement(const bj_setup *s);               // nullptr unless created from a placement
+void setup_adopt_witness_placement(bj_setup *s, uint32_t *d_placement);   // [num_witness_cols][n] u32, hipMalloc'ed; replaces one held
+int setup_read_public_placement(bj_ctx *ctx, bj_setup *s);       // fills bj_setup::pub_place from the placements the setup holds
 // lookup_multiplicities.hip: the multiplicity column [n] counted from raw columns (the arguments of bj_lookup_multiplicities) or
 // from a setup's replicated natural-order columns and the variables.  In the context's scratch, on its stream; synchronises.
 // A looked-up tuple that is in no table row: BJ_ERR_INVALID_ARG, the message starts with `who` and names the first such lookup.

@@ -18,6 +18,7 @@
 //                                bits index all_values (hints/mod.rs:10-61, 104-118; src/cs/mod.rs:44-46, 151-181)
 // The reference holds no golden bytes for these formats (parity unpinned by vectors): the layouts follow the code cited.
 #include "ctx.h"
+#include "../../include/boojum_hip_diag.h"
 
 #include <cstring>
 #include <functional>
@@ -149,17 +150,15 @@ std::vector<u64> make_non_residues(size_t count, u64 domain_size) {
 }
 
 constexpr u64 PLACEHOLDER_BIT = 1ull << 63, LOW_U48 = (1ull << 48) - 1;
-// a cell of the copy hint (u64: bit 63 = placeholder, low 48 bits = index) or of a setup's resident placement (u32)
+// a cell of the copy hint (u64: bit 63 = placeholder, low 48 bits = index); a setup's resident u32 placement goes through
+// witness_gather_kernel (witness_values.hip)
 __device__ __forceinline__ bool cell_empty(u64 h) { return h & PLACEHOLDER_BIT; }
 __device__ __forceinline__ u64 cell_index(u64 h) { return h & LOW_U48; }
-__device__ __forceinline__ bool cell_empty(uint32_t h) { return h == bj::PLACEMENT_NONE; }
-__device__ __forceinline__ u64 cell_index(uint32_t h) { return h; }
 // witness_set_from_witness_vec (witness.rs:386-443): cell = value of its variable, 0 for a placeholder
-template <typename Cell>
-__global__ void materialize_cells_kernel(const Cell *hint, const u64 *values, size_t n_values, u64 *cells, size_t count, unsigned *bad) {
+__global__ void materialize_cells_kernel(const u64 *hint, const u64 *values, size_t n_values, u64 *cells, size_t count, unsigned *bad) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    const Cell h = hint[i];
+    const u64 h = hint[i];
     u64 v = 0;
     if (!cell_empty(h)) {
         const u64 idx = cell_index(h);
@@ -193,6 +192,36 @@ struct DeviceBlock {
         if (p) (void)hipFree(p);
     }
 };
+
+// WitnessVec (witness.rs:29-71) as views into its dump; n: rows of the trace, num_public: public inputs of the setup
+struct ParsedWitnessVec {
+    std::vector<uint64_t> pub_col, pub_row;
+    const unsigned char *values = nullptr, *mult = nullptr;   // all_values (u64 each), the multiplicity counters (u32 each)
+    uint64_t n_values = 0, n_mult = 0;
+};
+int parse_witness_vec(bj_ctx *ctx, const void *witness_vec, size_t witness_vec_len, unsigned num_public, size_t n, ParsedWitnessVec *out) {
+    Reader w(witness_vec, witness_vec_len);
+    const uint64_t n_pub = w.u64v();
+    if (!w.ok || n_pub != num_public)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "WitnessVec dump: %llu public input locations, the setup was made with %u",
+                        (unsigned long long)n_pub, num_public);
+    out->pub_col.resize(n_pub), out->pub_row.resize(n_pub);
+    for (uint64_t i = 0; i < n_pub; i++) {
+        out->pub_col[i] = w.u64v();
+        out->pub_row[i] = w.u64v();
+    }
+    const uint64_t n_values = w.u64v();      // lengths come from the dump: bound them by what is left of it before multiplying
+    const unsigned char *values = (w.ok && n_values <= (size_t)(w.end - w.p) / 8) ? w.skip((size_t)n_values * 8) : nullptr;
+    if (!values) w.ok = false;
+    const uint64_t n_mult = w.u64v();
+    const unsigned char *mult = (w.ok && n_mult <= (size_t)(w.end - w.p) / 4) ? w.skip((size_t)n_mult * 4) : nullptr;
+    if (!mult) w.ok = false;
+    if (!w.ok || !values || (n_mult && !mult) || w.p != w.end)
+        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "WitnessVec dump: truncated or trailing bytes");
+    if (n_mult > n) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "WitnessVec dump: %llu multiplicities for %zu rows", (unsigned long long)n_mult, n);
+    out->values = values, out->mult = mult, out->n_values = n_values, out->n_mult = n_mult;
+    return BJ_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -333,7 +362,41 @@ int bj_setup_create_from_placement(bj_ctx *ctx, const bj_circuit *circuit, const
         BJ_HIP(ctx, hipMemcpyAsync(w.keys[0], d_place, (size_t)V * n * 4, hipMemcpyDeviceToDevice, ctx->stream));
         return bj::sigmas_from_keys(ctx, w, V, log_n, circuit->non_residues, d_sigmas, n);
     };
-    return bj::setup_create_impl(ctx, circuit, nullptr, fill, h_constants, h_tables, config, nullptr, out, bj::env().setup_lean);
+    if (int rc = bj::setup_create_impl(ctx, circuit, nullptr, fill, h_constants, h_tables, config, nullptr, out, bj::env().setup_lean)) return rc;
+    if (int rc = bj::setup_read_public_placement(ctx, *out)) {
+        bj_setup_destroy(*out);
+        *out = nullptr;
+        return rc;
+    }
+    return BJ_OK;
+}
+
+int bj_setup_set_witness_placement(bj_ctx *ctx, bj_setup *setup, const void *witness_hint, size_t witness_hint_len) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!setup || !witness_hint) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_set_witness_placement: null argument");
+    unsigned log_n = 0, Wc = 0;
+    if (int rc = bj_setup_shape(setup, &log_n, nullptr, &Wc, nullptr)) return rc;
+    if (bj::setup_world(setup) != 1) return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_setup_set_witness_placement: single-device setups only");
+    if (!Wc) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_setup_set_witness_placement: the setup has no non-copiable witness columns");
+    const size_t n = (size_t)1 << log_n;
+    std::vector<const unsigned char *> col(Wc);
+    if (int rc = read_copy_hint(ctx, "DenseWitnessCopyHint", witness_hint, witness_hint_len, Wc, n, col.data())) return rc;
+    const unsigned G = Wc < 8 ? Wc : 8;
+    bj::PlacementWorkspace w;
+    if (int rc = bj::placement_workspace(ctx, Wc, log_n, (size_t)G * n, &w)) return rc;
+    DeviceBlock place;   // handed to the setup only once every column has been narrowed and checked
+    BJ_HIP(ctx, hipMalloc(&place.p, (size_t)Wc * n * 4));
+    for (unsigned c0 = 0; c0 < Wc; c0 += G) {
+        const unsigned g = Wc - c0 < G ? Wc - c0 : G;
+        for (unsigned k = 0; k < g; k++)
+            BJ_HIP(ctx, hipMemcpyAsync(w.staging + (size_t)k * n, col[c0 + k], n * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = bj::placement_narrow(ctx, w, w.staging, n, g, log_n, (uint32_t *)place.p + (size_t)c0 * n)) return rc;
+        BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the staging block is reused by the next group
+    }
+    if (int rc = bj::placement_check(ctx, w)) return rc;
+    bj::setup_adopt_witness_placement(setup, (uint32_t *)place.p);
+    place.p = nullptr;
+    return bj::setup_read_public_placement(ctx, setup);
 }
 
 }  // extern "C"
@@ -352,25 +415,11 @@ int bj::witness_from_dumps(bj_ctx *ctx, const char *who, const bj_setup *setup, 
         return bj::fail(ctx, BJ_ERR_INVALID_ARG, "%s: the setup has %u non-copiable witness columns: a DenseWitnessCopyHint "
                         "dump is %s", who, num_witness_cols, num_witness_cols ? "required" : "not expected");
     const size_t n = (size_t)1 << log_n;
-    Reader w(witness_vec, witness_vec_len);
-    const uint64_t n_pub = w.u64v();
-    if (!w.ok || n_pub != num_public)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "WitnessVec dump: %llu public input locations, the setup was made with %u",
-                        (unsigned long long)n_pub, num_public);
-    std::vector<uint64_t> pub_col(n_pub), pub_row(n_pub);
-    for (uint64_t i = 0; i < n_pub; i++) {
-        pub_col[i] = w.u64v();
-        pub_row[i] = w.u64v();
-    }
-    const uint64_t n_values = w.u64v();      // lengths come from the dump: bound them by what is left of it before multiplying
-    const unsigned char *values = (w.ok && n_values <= (size_t)(w.end - w.p) / 8) ? w.skip((size_t)n_values * 8) : nullptr;
-    if (!values) w.ok = false;
-    const uint64_t n_mult = w.u64v();
-    const unsigned char *mult = (w.ok && n_mult <= (size_t)(w.end - w.p) / 4) ? w.skip((size_t)n_mult * 4) : nullptr;
-    if (!mult) w.ok = false;
-    if (!w.ok || !values || (n_mult && !mult) || w.p != w.end)
-        return bj::fail(ctx, BJ_ERR_INVALID_ARG, "WitnessVec dump: truncated or trailing bytes");
-    if (n_mult > n) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "WitnessVec dump: %llu multiplicities for %zu rows", (unsigned long long)n_mult, n);
+    ParsedWitnessVec W;
+    if (int rc = parse_witness_vec(ctx, witness_vec, witness_vec_len, num_public, n, &W)) return rc;
+    const uint64_t n_pub = num_public, n_values = W.n_values, n_mult = W.n_mult;
+    const std::vector<uint64_t> &pub_col = W.pub_col, &pub_row = W.pub_row;
+    const unsigned char *values = W.values, *mult = W.mult;
     // DenseVariablesCopyHint, then DenseWitnessCopyHint (same layout, same indexing of all_values: witness.rs:445-490): the witness
     // columns travel right behind the variable columns, as bj_prove_dev takes them
     const unsigned total_cols = num_vars + num_witness_cols;
@@ -391,16 +440,15 @@ int bj::witness_from_dumps(bj_ctx *ctx, const char *who, const bj_setup *setup, 
     BJ_HIP(ctx, hipMemsetAsync(d_bad.p, 0, 4, ctx->stream));
     if (n_values) BJ_HIP(ctx, hipMemcpyAsync(d_values.p, values, n_values * 8, hipMemcpyHostToDevice, ctx->stream));
     if (placement) {
-        const size_t count = (size_t)num_vars * n;
-        hipLaunchKernelGGL(materialize_cells_kernel<uint32_t>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, placement,
-                           (const u64 *)d_values.p, (size_t)n_values, (u64 *)d_cells.p, count, (unsigned *)d_bad.p);
+        bj::launch_witness_gather(placement, (const u64 *)d_values.p, (size_t)n_values, (u64 *)d_cells.p, (size_t)num_vars * n, (unsigned *)d_bad.p,
+                                  ctx->stream);
     }
     for (unsigned c0 = placement ? num_vars : 0; c0 < total_cols; c0 += G) {
         const unsigned g = total_cols - c0 < G ? total_cols - c0 : G;
         for (unsigned k = 0; k < g; k++)
             BJ_HIP(ctx, hipMemcpyAsync((u64 *)d_hint.p + (size_t)k * n, hint_col[c0 + k], n * 8, hipMemcpyHostToDevice, ctx->stream));
         const size_t count = (size_t)g * n;
-        hipLaunchKernelGGL(materialize_cells_kernel<u64>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, (const u64 *)d_hint.p,
+        hipLaunchKernelGGL(materialize_cells_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, (const u64 *)d_hint.p,
                            (const u64 *)d_values.p, (size_t)n_values, (u64 *)d_cells.p + (size_t)c0 * n, count, (unsigned *)d_bad.p);
         BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the pageable source of the next group's copies is reused storage only for us
     }
@@ -430,6 +478,17 @@ extern "C" int bj_prove_from_dumps(bj_ctx *ctx, const bj_setup *setup, const voi
                                    bj_proof **out) {
     if (int rc = bj::bind(ctx)) return rc;
     if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_from_dumps: null argument");
+    unsigned log_n = 0, num_vars = 0, num_witness_cols = 0, num_public = 0;
+    if (setup && witness_vec && !variables_hint && !witness_hint && bj::setup_placement(setup) &&
+        bj_setup_shape(setup, &log_n, &num_vars, &num_witness_cols, &num_public) == BJ_OK && !num_witness_cols) {
+        // all_values alone on a setup that holds its placement: the dump is parsed and the proof is bj_prove_values'
+        ParsedWitnessVec W;
+        if (int rc = parse_witness_vec(ctx, witness_vec, witness_vec_len, num_public, (size_t)1 << log_n, &W)) return rc;
+        for (size_t i = 0; i < W.pub_col.size(); i++)
+            if (W.pub_col[i] >= num_vars || W.pub_row[i] >> log_n)
+                return bj::fail(ctx, BJ_ERR_INVALID_ARG, "WitnessVec dump: public input %zu outside the trace", i);
+        return bj_prove_values(ctx, setup, (const uint64_t *)W.values, (size_t)W.n_values, (const uint32_t *)W.mult, (size_t)W.n_mult, out);
+    }
     return bj::witness_from_dumps(ctx, "bj_prove_from_dumps", setup, witness_vec, witness_vec_len, variables_hint, variables_hint_len, witness_hint,
                                   witness_hint_len, [&](const uint64_t *d_cells, const uint64_t *d_mult, const uint64_t *h_pub) {
                                       return bj_prove_dev(ctx, setup, d_cells, d_mult, h_pub, out);

@@ -153,4 +153,11 @@ void launch_copy_check(const u64 *d_sigmas, const u64 *d_vars, unsigned num_vars
                        uint32_t *d_multi, u64 *d_ctr, hipStream_t s);
 void launch_copy_shared_target(const u64 *d_sigmas, unsigned num_vars, unsigned log_n, const u64 *d_table, const uint32_t *d_multi, u64 *d_ctr,
                                hipStream_t s);
+// witness_values.hip: witness_gather_kernel, d_cells[i] = d_values[d_placement[i]] for i < count (0 for PLACEMENT_NONE; 0 and *d_bad
+// raised for an index at or beyond n_values); the grid is sized to the CU count and strides, one sweep of it covers
+// witness_gather_sweep_cells().  launch_widen_counters: d_column[i] = d_counters[i] for i < n_counters, 0 up to n.
+void launch_witness_gather(const uint32_t *d_placement, const u64 *d_values, size_t n_values, u64 *d_cells, size_t count, unsigned *d_bad,
+                           hipStream_t s);
+size_t witness_gather_sweep_cells();
+void launch_widen_counters(const uint32_t *d_counters, size_t n_counters, u64 *d_column, size_t n, hipStream_t s);
 }  // namespace bj

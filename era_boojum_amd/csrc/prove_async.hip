@@ -22,6 +22,7 @@
 // read it, so a ticket that was waited for, was never issued or whose context is gone is BJ_ERR_INVALID_ARG, not a read of freed
 // memory.  Destroying the context frees the proofs and tickets nobody waited for.
 #include "ctx.h"
+#include "../../include/boojum_hip_diag.h"
 #include "async_admission.h"
 
 #include <chrono>
@@ -29,6 +30,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <unordered_set>
@@ -40,6 +42,11 @@ struct bj_ticket {
     bool lean = false;             // admitted with a lean workspace: the lane proves with lean_override set
     const bj_setup *setup = nullptr;
     const uint64_t *h_variables = nullptr, *h_multiplicities = nullptr;
+    // bj_prove_values_async: the proof is bj_prove_values' (h_variables and h_multiplicities above stay null)
+    bool from_values = false;
+    const uint64_t *h_values = nullptr;
+    const uint32_t *h_counters = nullptr;
+    size_t n_values = 0, n_counters = 0;
     std::vector<uint64_t> public_values;
     bool has_public = false;
     // result (written by the lane's worker under the lane's mutex)
@@ -123,8 +130,10 @@ struct Lane {
             bj_proof *p = nullptr;
             const uint64_t *pub = t->has_public ? t->public_values.data() : nullptr;
             const bool overlapped = sibling && sibling->busy() && mode != 0;
-            const int rc = overlapped ? prove_host_copy_first(sub, t->setup, t->h_variables, t->h_multiplicities, pub, &p, mode)
-                                      : bj_prove(sub, t->setup, t->h_variables, t->h_multiplicities, pub, &p);
+            // from values there is no transfer to put first: a lane whose sibling proves gathers and transforms in groups and hashes once
+            const int rc = t->from_values ? prove_values_staged(sub, t->setup, t->h_values, t->n_values, t->h_counters, t->n_counters, &p, overlapped)
+                           : overlapped   ? prove_host_copy_first(sub, t->setup, t->h_variables, t->h_multiplicities, pub, &p, mode)
+                                          : bj_prove(sub, t->setup, t->h_variables, t->h_multiplicities, pub, &p);
             sub->lean_override = -1;
             if (bj::env().async_debug)
                 fprintf(stderr, "[lane %p] mode %d overlapped %d: picked up, ran %.1f ms (stagger %.1f ms)\n", (void *)this, mode, (int)overlapped,
@@ -214,10 +223,10 @@ int pipeline_release_workspace(bj_ctx *ctx) {
 // waits for it where it is busy and has to grow, and reserves the lane's whole footprint.  A lane that cannot be started or
 // reserved although the decision said it would fit (another process took the bytes) sends the submission down the ladder, so to
 // the lane that exists.  BJ_ERR_OOM with both byte counts in the message where nothing fits.
-static int admit_and_reserve(bj_ctx *ctx, const bj_setup *setup, AdmissionDecision *out) {
+static int admit_and_reserve(bj_ctx *ctx, const bj_setup *setup, bool values, size_t n_values, AdmissionDecision *out) {
     Pipeline *P = ctx->pipe;
     AdmissionInput in;
-    if (int rc = async_footprints(ctx, setup, &in.resident, &in.lean)) return rc;
+    if (int rc = async_footprints(ctx, setup, &in.resident, &in.lean, values, n_values)) return rc;
     in.due = P->next;
     in.parent_idle = !ctx->in_proof;
     for (unsigned first = TWO_LANES_RESIDENT;;) {
@@ -264,17 +273,9 @@ static int admit_and_reserve(bj_ctx *ctx, const bj_setup *setup, AdmissionDecisi
 
 extern "C" {
 
-int bj_prove_async(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_variables, const uint64_t *h_multiplicities,
-                   const uint64_t *h_public_values, bj_ticket **out) {
-    if (int rc = bj::bind(ctx)) return rc;
-    if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_async: null out pointer");
-    *out = nullptr;
-    if (!setup || !h_variables) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_async: null argument");
-    unsigned n_pub = 0;
-    if (int rc = bj_setup_shape(setup, nullptr, nullptr, nullptr, &n_pub)) return bj::fail(ctx, rc, "bj_prove_async: bad setup");
-    if (bj::setup_world(setup) != 1)
-        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_prove_async: single-device setups only (the ranks of a sharded proof are concurrent already)");
-    if (n_pub && !h_public_values) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_async: public input values required");
+// The part of a submission both entry points share: admission (no ticket exists before it: an out-of-memory is the call's own
+// status), then the ticket `fill` completes goes to the lane admission chose.
+static int submit(bj_ctx *ctx, const bj_setup *setup, bool values, size_t n_values, const std::function<void(bj_ticket *)> &fill, bj_ticket **out) {
     if (!ctx->pipe) {
         ctx->pipe = new bj::Pipeline();
         ctx->pipe->lanes[0].sibling = &ctx->pipe->lanes[1];
@@ -283,19 +284,14 @@ int bj_prove_async(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_variabl
     bj::Pipeline *P = ctx->pipe;
     bj::Lane *L = nullptr;
     bj::AdmissionDecision d;
-    if (int rc = bj::admit_and_reserve(ctx, setup, &d)) return rc;   // no ticket exists yet: an out-of-memory is this call's status
+    if (int rc = bj::admit_and_reserve(ctx, setup, values, n_values, &d)) return rc;
     L = &P->lanes[d.lane];
     bj_ticket *t = new bj_ticket();
     t->parent = ctx;
     t->lane = d.lane;
     t->lean = d.lean;
     t->setup = setup;
-    t->h_variables = h_variables;
-    t->h_multiplicities = h_multiplicities;
-    if (n_pub) {
-        t->public_values.assign(h_public_values, h_public_values + n_pub);   // the caller's array may go away; the witness may not
-        t->has_public = true;
-    }
+    fill(t);
     {
         std::lock_guard<std::mutex> lk(bj::g_tickets_m);
         bj::g_tickets.insert(t);
@@ -309,6 +305,40 @@ int bj_prove_async(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_variabl
     P->next = d.lane ^ 1;
     *out = t;
     return BJ_OK;
+}
+
+int bj_prove_async(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_variables, const uint64_t *h_multiplicities,
+                   const uint64_t *h_public_values, bj_ticket **out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_async: null out pointer");
+    *out = nullptr;
+    if (!setup || !h_variables) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_async: null argument");
+    unsigned n_pub = 0;
+    if (int rc = bj_setup_shape(setup, nullptr, nullptr, nullptr, &n_pub)) return bj::fail(ctx, rc, "bj_prove_async: bad setup");
+    if (bj::setup_world(setup) != 1)
+        return bj::fail(ctx, BJ_ERR_UNSUPPORTED, "bj_prove_async: single-device setups only (the ranks of a sharded proof are concurrent already)");
+    if (n_pub && !h_public_values) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_async: public input values required");
+    return submit(ctx, setup, false, 0, [&](bj_ticket *t) {
+        t->h_variables = h_variables;
+        t->h_multiplicities = h_multiplicities;
+        if (n_pub) {
+            t->public_values.assign(h_public_values, h_public_values + n_pub);   // the caller's array may go away; the witness may not
+            t->has_public = true;
+        }
+    }, out);
+}
+
+int bj_prove_values_async(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_values, size_t n_values, const uint32_t *h_multiplicities,
+                          size_t n_multiplicities, bj_ticket **out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_values_async: null out pointer");
+    *out = nullptr;
+    if (int rc = bj::values_check(ctx, "bj_prove_values_async", setup, h_values, n_values, h_multiplicities, n_multiplicities)) return rc;
+    return submit(ctx, setup, true, n_values, [&](bj_ticket *t) {
+        t->from_values = true;
+        t->h_values = h_values, t->n_values = n_values;
+        t->h_counters = h_multiplicities, t->n_counters = n_multiplicities;
+    }, out);
 }
 
 // A ticket that is in the registry is taken out of it by the one wait that gets it: the pointer of a ticket that was waited for,

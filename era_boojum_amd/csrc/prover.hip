@@ -9,6 +9,7 @@
 // hasher + Poseidon2 transcript, PoW off — the configuration of the reference's SHA-256 bench
 // (src/gadgets/sha256/mod.rs:284-375).
 #include "ctx.h"
+#include "../../include/boojum_hip_diag.h"
 #include "async_admission.h"
 #include "host_transcript.hpp"
 #include "fri_types.h"
@@ -175,6 +176,20 @@ struct HostWitness {
     unsigned group;        // columns per group
     bool no_absorb;        // transfer and transform in groups, hash once at the end (a lane of bj_prove_async whose sibling is proving)
 };
+// bj_prove_values: the host holds a WitnessVec (witness.rs:29-71), not columns.  all_values crosses PCIe once, on the copy stream,
+// into the witness staging behind the multiplicity column, the u32 counters behind it; the columns of every group are then gathered
+// on the proof stream through the setup's resident placements (witness_gather_kernel) into the staging the host path copies into,
+// and everything below "how a group's columns arrive" is the host path's.
+struct ValuesWitness {
+    const uint64_t *h_values;
+    size_t n_values;
+    const uint32_t *h_multiplicities;   // nullptr: counted on the device
+    size_t n_multiplicities;
+    uint64_t *d_values;                 // [n_values] in the staging
+    uint32_t *d_counters;               // [n] u32 behind them
+    unsigned group;
+    bool no_absorb;
+};
 
 using Src = bj::OpenSrc;   // opening_args.h: a base-field column (c1 == nullptr) or the two columns of an F_p^2 polynomial
 struct DeepSets;
@@ -189,11 +204,13 @@ struct Proving {
     const bj::Shard &sh;
     hipStream_t st;
     const u64 *d_variables, *d_multiplicities, *h_public_values;
-    const HostWitness *hw;   // nullptr: the witness is resident (bj_prove_dev)
+    const HostWitness *hw;   // nullptr: the witness is resident (bj_prove_dev) ...
+    const ValuesWitness *vw = nullptr;   // ... or comes as values (bj_prove_values); never both
+    bool values_unchecked = false;       // gathers have been launched and their flag has not been read yet (check_values_flag)
     const bj::ProofLayout &L;   // proof_layout.h: the columns of every oracle, the opening order, the proof's words
     bool has_lookup;
     bool count_mult;         // no multiplicity column was supplied: round 1 counts it (count_multiplicities)
-    bool absorb;             // host witness: the leaves absorb every column group as it lands (witness_from_host)
+    bool absorb;             // staged witness: the leaves absorb every column group as it lands (witness_from_host)
     unsigned log_n, V, q;
     // N / Ln: leaves / column stride HELD BY THIS GPU (the whole domain on one GPU); Q: points of the quotient domain
     size_t n, N, Q, Ln, I0, capl;
@@ -221,8 +238,12 @@ struct Proving {
     bj_fri *fri = nullptr;
     u64 pow_challenge = 0;
 
-    Proving(bj_ctx *c, const bj_setup *s, const u64 *d_vars, const u64 *d_mult, const u64 *h_pub, const HostWitness *h, bool count)
-        : ctx(c), S(s), sh(s->sh), st(c->stream), d_variables(d_vars), d_multiplicities(d_mult), h_public_values(h_pub), hw(h), L(s->layout) {
+    // the witness columns arrive in the context's staging group by group: copied from the host, or gathered from values
+    bool staged() const { return hw || vw; }
+    unsigned staged_group() const { return hw ? hw->group : vw->group; }
+    Proving(bj_ctx *c, const bj_setup *s, const u64 *d_vars, const u64 *d_mult, const u64 *h_pub, const HostWitness *h, const ValuesWitness *v,
+            bool count)
+        : ctx(c), S(s), sh(s->sh), st(c->stream), d_variables(d_vars), d_multiplicities(d_mult), h_public_values(h_pub), hw(h), vw(v), L(s->layout) {
         has_lookup = L.has_lookup;
         count_mult = has_lookup && count;
         log_n = S->log_n, V = S->V, q = S->q;
@@ -238,8 +259,8 @@ struct Proving {
         oracle[bj::ORACLE_QUOTIENT] = bj::oracle_of(2 * q, n, N, true);   // always resident, on the FRI domain; its monomials: T's chunk layout
         oracle[bj::ORACLE_QUOTIENT].mono_parts = 2, oracle[bj::ORACLE_QUOTIENT].mono_part_gap = Q;
         oracle[bj::ORACLE_SETUP] = S->oracle();
-        absorb = hw && (S->hasher == BJ_HASHER_POSEIDON2 || S->hasher == BJ_HASHER_POSEIDON) && !bj::env().prove_no_absorb && !hw->no_absorb &&
-                 oracle[bj::ORACLE_WITNESS].resident;
+        absorb = staged() && (S->hasher == BJ_HASHER_POSEIDON2 || S->hasher == BJ_HASHER_POSEIDON) && !bj::env().prove_no_absorb &&
+                 !(hw ? hw->no_absorb : vw->no_absorb) && oracle[bj::ORACLE_WITNESS].resident;
     }
     int reserve_workspace();
     int check_public_inputs();
@@ -247,6 +268,10 @@ struct Proving {
     int count_multiplicities();
     int round1_witness();
     int witness_from_host();
+    int queue_host_copies(const std::vector<bj::WitnessGroup> &plan);
+    int queue_values_upload();
+    int gather_columns(unsigned c0, unsigned c1);
+    int check_values_flag();
     int round2_stage2();
     int round3_quotient();
     int exchange_residues(u64 *Tl);
@@ -312,7 +337,7 @@ int Proving::reserve_workspace() {
     if (int rc = bj_fri_schedule(S->security, S->cap_size, S->pow_bits, S->log_fri, log_n, &new_pow, &num_queries, sched, &sched_len, &final_degree))
         return bj::fail(ctx, rc, "bj_prove: compute_fri_schedule failed");
     plan = bj::workspace_plan(shape_of(S, count_mult && !d_multiplicities,
-                                       !hw ? bj::WS_HOST_NONE : absorb ? bj::WS_HOST_ABSORBING : bj::WS_HOST_NOT_ABSORBING,
+                                       !staged() ? bj::WS_HOST_NONE : absorb ? bj::WS_HOST_ABSORBING : bj::WS_HOST_NOT_ABSORBING,
                                        !oracle[bj::ORACLE_WITNESS].resident, new_pow, sched, sched_len, num_queries));
     if (int rc = bj::arena_reset(ctx, std::max(plan.total(), ctx->arena_learned))) return rc;
     proof->ws_reserved = ctx->bump.arena_words * 8;
@@ -322,7 +347,7 @@ int Proving::reserve_workspace() {
 // Reads the witness cells the public inputs name (from the host witness, or off the device: one synchronisation of the stream).
 // The values that go into the transcript must be the cells they claim to be (witness.rs:21-27).
 int Proving::check_public_inputs() {
-    if (S->pub_cols.empty()) return BJ_OK;
+    if (S->pub_cols.empty() || vw) return BJ_OK;   // from values: the public values were read through the placement, they ARE the cells
     std::vector<u64> cells(S->pub_cols.size());
     for (size_t i = 0; i < cells.size(); i++) {
         const size_t at = (size_t)S->pub_cols[i] * n + S->pub_rows[i];
@@ -348,28 +373,10 @@ int Proving::open_transcript() {
     return bj::ensure_twiddles(ctx, log_n + (S->L > S->fri_lde ? bj::log2_exact(S->L) : S->log_fri), false);
 }
 
-// Round 1 with the witness in host memory (hw): queues the copies of every column group on the copy stream, then transforms
-// the groups on the proof stream as they land.  Reads mono, wit_lde, wit_tree (allocated); fills mono and, the oracle resident,
-// wit_lde.  absorb: the leaves are absorbed group by group as well, and the leaf layer of wit_tree is written here.
-int Proving::witness_from_host() {
-    int rc = BJ_OK;
-    const bj::Oracle &wit = oracle[bj::ORACLE_WITNESS];
-    // all copies are queued on the copy stream at once (they run back to back at PCIe speed); the proof stream picks the
-    // groups up as they land.  Column nW - 1 is the multiplicity column when there are lookups.
-    if (!ctx->copy_stream) BJ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    // groups of G columns, at most 64 of them (one event each): a wide witness gets wider groups instead of an error.  With
-    // an algebraic tree hasher (Poseidon2 / Poseidon) and G a multiple of the sponge's rate, a group is also absorbed into the leaf sponges as soon
-    // as it is extended (the capacity words of every leaf wait in HBM between the groups), so that hashing — the dominant
-    // kernel — runs under the transfer of the later groups instead of after the last one has landed.
-    unsigned G = hw->group;
-    if ((nW + G - 1) / G > 64) G = (nW + 63) / 64;
-    if (absorb) G = (G + 7) / 8 * 8;
-    const std::vector<bj::WitnessGroup> plan = bj::host_witness_plan(nW, G, absorb, bj::env().prove_uniform_groups);
-    const unsigned n_groups = (unsigned)plan.size();
-    bj::TmpBuf capacity;
-    if (absorb && (rc = capacity.take(ctx, bj::WS_CAPACITY))) return rc;
-    for (unsigned g = 0; g < n_groups; g++) {
-        if ((rc = bj::ensure_event(ctx, ctx->copy_ev[g], hipEventDisableTiming))) return rc;
+// A host witness: the copies of every column group are queued on the copy stream at once, each followed by its event.
+int Proving::queue_host_copies(const std::vector<bj::WitnessGroup> &plan) {
+    for (unsigned g = 0; g < (unsigned)plan.size(); g++) {
+        if (int rc = bj::ensure_event(ctx, ctx->copy_ev[g], hipEventDisableTiming)) return rc;
         const unsigned c0 = plan[g].c0, c1 = plan[g].c1;
         const unsigned v1 = c1 < VW ? c1 : VW;         // variable / witness columns of this group: [c0, v1)
         if (c0 < v1)
@@ -380,11 +387,95 @@ int Proving::witness_from_host() {
                                        ctx->copy_stream));
         BJ_HIP(ctx, hipEventRecord(ctx->copy_ev[g], ctx->copy_stream));
     }
+    return BJ_OK;
+}
+
+// Values: all_values goes up once on the copy stream, followed by event 0; the u32 counters go up behind it, followed by event 1.
+// The gather's flag is cleared on the proof stream, in front of the first gather.
+int Proving::queue_values_upload() {
+    for (unsigned e = 0; e < 2; e++)
+        if (int rc = bj::ensure_event(ctx, ctx->copy_ev[e], hipEventDisableTiming)) return rc;
+    if (vw->n_values)
+        BJ_HIP(ctx, hipMemcpyAsync(vw->d_values, vw->h_values, vw->n_values * 8, hipMemcpyHostToDevice, ctx->copy_stream));
+    BJ_HIP(ctx, hipEventRecord(ctx->copy_ev[0], ctx->copy_stream));
+    if (has_lookup && !count_mult && vw->n_multiplicities)
+        BJ_HIP(ctx, hipMemcpyAsync(vw->d_counters, vw->h_multiplicities, vw->n_multiplicities * 4, hipMemcpyHostToDevice, ctx->copy_stream));
+    BJ_HIP(ctx, hipEventRecord(ctx->copy_ev[1], ctx->copy_stream));
+    BJ_HIP(ctx, hipMemsetAsync(bj::values_bad_flag(ctx), 0, 4, st));
+    return BJ_OK;
+}
+
+// Columns [c0, c1) of the witness (variables, then the non-copiable witness columns) gathered from the values through the setup's
+// placements, straight into the staging a host witness is copied into.
+int Proving::gather_columns(unsigned c0, unsigned c1) {
+    u64 *cells = const_cast<u64 *>(d_variables);
+    const unsigned ve = c1 < V ? c1 : V, wb = c0 > V ? c0 : V;   // [c0, ve): variable columns; [wb, c1): witness columns
+    if (c0 < ve)
+        bj::launch_witness_gather(S->d_placement + (size_t)c0 * n, vw->d_values, vw->n_values, cells + (size_t)c0 * n, (size_t)(ve - c0) * n,
+                                  bj::values_bad_flag(ctx), st);
+    if (wb < c1)
+        bj::launch_witness_gather(S->d_wit_placement + (size_t)(wb - V) * n, vw->d_values, vw->n_values, cells + (size_t)wb * n,
+                                  (size_t)(c1 - wb) * n, bj::values_bad_flag(ctx), st);
+    BJ_CHECK_LAUNCH(ctx);
+    values_unchecked = true;
+    return BJ_OK;
+}
+
+// Reads the gather's flag (synchronises; called where round 1 synchronises anyway): a cell that named a value at or beyond n_values
+// refuses the proof.  Nothing to do for any other witness source, or once the flag has been read after the last gather.
+int Proving::check_values_flag() {
+    if (!values_unchecked) return BJ_OK;
+    unsigned bad = 0;
+    if (int rc = bj_memcpy_d2h(ctx, &bad, bj::values_bad_flag(ctx), 4)) return rc;
+    values_unchecked = false;
+    if (bad) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_values: a cell names a variable beyond all_values");
+    return BJ_OK;
+}
+
+// Round 1 with the witness staged group by group (hw: copied from host memory; vw: gathered from values): walks the plan of
+// column groups, transforms each group on the proof stream as it arrives.  Reads mono, wit_lde, wit_tree (allocated); fills mono
+// and, the oracle resident, wit_lde.  absorb: the leaves are absorbed group by group as well, and the leaf layer of wit_tree is
+// written here.
+int Proving::witness_from_host() {
+    int rc = BJ_OK;
+    const bj::Oracle &wit = oracle[bj::ORACLE_WITNESS];
+    // all copies are queued on the copy stream at once (they run back to back at PCIe speed); the proof stream picks the
+    // groups up as they land.  Column nW - 1 is the multiplicity column when there are lookups.
+    if (!ctx->copy_stream) BJ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    // groups of G columns, at most 64 of them (one event each): a wide witness gets wider groups instead of an error.  With
+    // an algebraic tree hasher (Poseidon2 / Poseidon) and G a multiple of the sponge's rate, a group is also absorbed into the leaf sponges as soon
+    // as it is extended (the capacity words of every leaf wait in HBM between the groups), so that hashing — the dominant
+    // kernel — runs under the transfer of the later groups instead of after the last one has landed.
+    unsigned G = staged_group();
+    if ((nW + G - 1) / G > 64) G = (nW + 63) / 64;
+    if (absorb) G = (G + 7) / 8 * 8;
+    const std::vector<bj::WitnessGroup> plan = bj::host_witness_plan(nW, G, absorb, bj::env().prove_uniform_groups);
+    const unsigned n_groups = (unsigned)plan.size();
+    bj::TmpBuf capacity;
+    if (absorb && (rc = capacity.take(ctx, bj::WS_CAPACITY))) return rc;
+    if ((rc = hw ? queue_host_copies(plan) : queue_values_upload())) return rc;
     if (absorb) BJ_HIP(ctx, hipEventRecord(ctx->ev0, st));
     for (unsigned g = 0; g < n_groups && !rc; g++) {
         const unsigned c0 = plan[g].c0, c1 = plan[g].c1;
         const unsigned v1 = c1 < VW ? c1 : VW;
-        BJ_HIP(ctx, hipStreamWaitEvent(st, ctx->copy_ev[g], 0));
+        // how the group's columns arrive: a host witness group by group over PCIe, each behind its event; values once, behind the
+        // first event, and from then on every group is a gather on this stream that waits for nothing
+        if (hw) {
+            BJ_HIP(ctx, hipStreamWaitEvent(st, ctx->copy_ev[g], 0));
+        } else {
+            if (g == 0) BJ_HIP(ctx, hipStreamWaitEvent(st, ctx->copy_ev[0], 0));
+            if (c0 < v1 && (rc = gather_columns(c0, v1))) break;
+            if (c1 == nW && has_lookup) {
+                if (count_mult) {
+                    rc = check_values_flag();   // the count synchronises anyway, and must not name a tuple that a refused cell made
+                } else {
+                    BJ_HIP(ctx, hipStreamWaitEvent(st, ctx->copy_ev[1], 0));   // the counters went up behind the values
+                    bj::launch_widen_counters(vw->d_counters, vw->n_multiplicities, const_cast<u64 *>(d_multiplicities), n, st);
+                    BJ_CHECK_LAUNCH(ctx);
+                }
+                if (rc) break;
+            }
+        }
         if (count_mult && c1 == nW && (rc = count_multiplicities())) break;   // the last group: every lookup column has landed
         if (c0 < v1) rc = intt_cols(d_variables + (size_t)c0 * n, mono.p + (size_t)c0 * n, v1 - c0);
         if (!rc && has_lookup && c1 == nW) rc = intt_cols(d_multiplicities, mono.p + (size_t)L.multiplicity() * n, 1);
@@ -409,7 +500,8 @@ int Proving::count_multiplicities() {
         if (int rc = col.take(ctx, bj::WS_MULTIPLICITY)) return rc;
         d_multiplicities = col.p;
     }
-    return bj::setup_lookup_multiplicities(ctx, hw ? "bj_prove" : "bj_prove_dev", S, d_variables, const_cast<u64 *>(d_multiplicities));
+    return bj::setup_lookup_multiplicities(ctx, vw ? "bj_prove_values" : hw ? "bj_prove" : "bj_prove_dev", S, d_variables,
+                                           const_cast<u64 *>(d_multiplicities));
 }
 
 // Commits to an oracle whose monomials stand: the leaves of its tree over this rank's N points of the FRI domain, the node layers,
@@ -441,6 +533,7 @@ int Proving::commit(const bj::Oracle &o, std::vector<u64> &cap, Brought have, fl
     cap.resize(4 * S->cap_size);
     if (int rc = bj::gather_cap(ctx, sh, o.tree, N, S->cap_size, cap.data())) return rc;
     if (leaf_ms) BJ_HIP(ctx, hipEventElapsedTime(leaf_ms, ctx->ev0, ctx->ev1));
+    if (int rc = check_values_flag()) return rc;   // the stream has drained for the cap: no cap of a witness with a bad cell is absorbed
     tr.absorb_cap(cap.data(), cap.size());
     return BJ_OK;
 }
@@ -452,20 +545,20 @@ int Proving::commit(const bj::Oracle &o, std::vector<u64> &cap, Brought have, fl
 int Proving::round1_witness() {
     int rc = BJ_OK;
     bj::Oracle &wit = oracle[bj::ORACLE_WITNESS];
-    if (count_mult && !hw && (rc = count_multiplicities())) return rc;   // before any proof work
+    if (count_mult && !staged() && (rc = count_multiplicities())) return rc;   // before any proof work
     if ((rc = wit_lde.take(ctx, bj::WS_WIT_LDE))) return rc;
     if ((rc = mono.take(ctx, bj::WS_MONO))) return rc;
     if ((rc = mono_s2.take(ctx, bj::WS_MONO_S2))) return rc;
     if ((rc = wit_tree.take(ctx, bj::WS_WIT_TREE))) return rc;
     wit.mono = mono.p, wit.evals = wit_lde.p, wit.tree = wit_tree.p;
-    if (!hw) {
+    if (!staged()) {
         rc = intt_cols(d_variables, mono.p, VW);
         if (!rc && has_lookup) rc = intt_cols(d_multiplicities, mono.p + (size_t)L.multiplicity() * n, 1);
     } else {
         rc = witness_from_host();   // a resident oracle is extended there, group by group (a lean one: after the last group has landed)
     }
     if (rc) return rc;
-    return commit(wit, wit_cap, !hw ? MONOMIALS : absorb ? LEAVES_HASHED : EXTENDED, &proof->stage_ms[7]);
+    return commit(wit, wit_cap, !staged() ? MONOMIALS : absorb ? LEAVES_HASHED : EXTENDED, &proof->stage_ms[7]);
 }
 
 // ---------------- round 2: copy-permutation + lookup polys (prover.rs:360-554) ----------------
@@ -1030,7 +1123,7 @@ struct InProof {   // temporaries of the ABI calls of the rounds come out of the
         c->ws_plan = nullptr;
     }
 };
-struct CopyDrain {   // bj_prove: whatever way the proof ends, no queued copy may still read the caller's witness afterwards
+struct CopyDrain {   // bj_prove, bj_prove_values: whatever way the proof ends, no queued copy may still read the caller's witness afterwards
     bj_ctx *c;
     bool active;
     ~CopyDrain() {
@@ -1043,20 +1136,20 @@ struct FriGuard {
 };
 
 int prove_impl(bj_ctx *ctx, const bj_setup *S, const uint64_t *d_variables, const uint64_t *d_multiplicities,
-               const uint64_t *h_public_values, bj_proof **out, const HostWitness *hw, bool count) {
+               const uint64_t *h_public_values, bj_proof **out, const HostWitness *hw, bool count, const ValuesWitness *vw = nullptr) {
     if (int rc = bj::bind(ctx)) return rc;
     if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_dev: null out pointer");
     *out = nullptr;
     if (!S || !d_variables) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_dev: null argument");
     if (!S->pub_cols.empty() && !h_public_values) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_dev: public input values required");
     int rc = BJ_OK;
-    Proving P(ctx, S, d_variables, d_multiplicities, h_public_values, hw, count);
+    Proving P(ctx, S, d_variables, d_multiplicities, h_public_values, hw, vw, count);
     P.proof = new bj_proof();
     ProofGuard guard{P.proof};
     if ((rc = P.reserve_workspace())) return rc;
     InProof in_proof(ctx, &P.plan);
     bj::HasherGuard hasher_guard{ctx, ctx->hasher};
-    CopyDrain copy_drain{ctx, hw != nullptr};
+    CopyDrain copy_drain{ctx, hw != nullptr || vw != nullptr};
     ctx->hasher = (int)S->hasher;
     if ((rc = P.check_public_inputs())) return rc;
     StageTimer timer(P.st);
@@ -1112,20 +1205,77 @@ int bj_prove(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_variables, const 
     return prove_impl(ctx, S, ctx->wit_stage.p, ctx->wit_stage.p + (size_t)S->layout.multiplicity() * n, h_public_values, out, &hw, h_multiplicities == nullptr);
 }
 
+int bj_prove_values(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_values, size_t n_values, const uint32_t *h_multiplicities,
+                    size_t n_multiplicities, bj_proof **out) {
+    if (int rc = bj::bind(ctx)) return rc;
+    if (!out) return bj::fail(ctx, BJ_ERR_INVALID_ARG, "bj_prove_values: null out pointer");
+    *out = nullptr;
+    if (int rc = bj::values_check(ctx, "bj_prove_values", S, h_values, n_values, h_multiplicities, n_multiplicities)) return rc;
+    return bj::prove_values_staged(ctx, S, h_values, n_values, h_multiplicities, n_multiplicities, out, false);
+}
+
 }  // extern "C"
 
 namespace bj {
+// What bj_prove_values and bj_prove_values_async refuse before anything is queued; `who` starts the messages.
+int values_check(bj_ctx *ctx, const char *who, const bj_setup *S, const uint64_t *h_values, size_t n_values, const uint32_t *h_multiplicities,
+                 size_t n_multiplicities) {
+    if (!S) return fail(ctx, BJ_ERR_INVALID_ARG, "%s: null argument", who);
+    if (S->sh.world != 1)
+        return fail(ctx, BJ_ERR_UNSUPPORTED, "%s: single-device setups only (a sharded setup holds no placement)", who);
+    if (!S->d_placement)
+        return fail(ctx, BJ_ERR_INVALID_ARG, "%s: the setup holds no variable placement (make it with bj_setup_create_from_placement)", who);
+    if (S->Wc && !S->d_wit_placement)
+        return fail(ctx, BJ_ERR_INVALID_ARG, "%s: the setup has %u non-copiable witness columns and no witness placement "
+                                             "(bj_setup_set_witness_placement)", who, S->Wc);
+    if (n_values && !h_values) return fail(ctx, BJ_ERR_INVALID_ARG, "%s: null h_values with n_values %zu", who, n_values);
+    if (n_values > PLACEMENT_NONE) return fail(ctx, BJ_ERR_UNSUPPORTED, "%s: n_values %zu above 2^32 - 1 (the placement is u32)", who, n_values);
+    const size_t n = (size_t)1 << S->log_n;
+    if (n_multiplicities > n) return fail(ctx, BJ_ERR_INVALID_ARG, "%s: %zu multiplicities for %zu rows", who, n_multiplicities, n);
+    if (n_multiplicities && !h_multiplicities) return fail(ctx, BJ_ERR_INVALID_ARG, "%s: null h_multiplicities with n_multiplicities %zu", who, n_multiplicities);
+    if (S->pub_place.size() != S->pub_cols.size()) return fail(ctx, BJ_ERR_HIP, "%s: internal error: no placement entries for the public inputs", who);
+    for (uint32_t entry : S->pub_place)
+        if (entry != PLACEMENT_NONE && entry >= n_values) return fail(ctx, BJ_ERR_INVALID_ARG, "%s: a cell names a variable beyond all_values", who);
+    return BJ_OK;
+}
+
+// words of the witness staging of a proof from values: cells and multiplicity column, all_values, the u32 counters (lane_extras)
+static size_t values_staging_words(const bj_setup *S, size_t n_values) {
+    const size_t n = (size_t)1 << S->log_n;
+    return (size_t)(S->layout.multiplicity() + 1) * n + values_staging_bytes(n, n_values ? n_values : 1) / 8;
+}
+
+// The proof of bj_prove_values on a context whose checks have passed (values_check): by the calling thread, or by a lane of
+// bj_prove_values_async (no_absorb: its sibling is proving, the leaves are hashed once at the end).
+int prove_values_staged(bj_ctx *ctx, const bj_setup *S, const uint64_t *h_values, size_t n_values, const uint32_t *h_multiplicities,
+                        size_t n_multiplicities, bj_proof **out, bool no_absorb) {
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = stage_witness_elems(ctx, values_staging_words(S, n_values))) return rc;
+    const size_t n = (size_t)1 << S->log_n, vw_cols = S->layout.multiplicity();
+    u64 *stage = ctx->wit_stage.p, *d_values = stage + (vw_cols + 1) * n;
+    const ValuesWitness vw{h_values, n_values, h_multiplicities, n_multiplicities, d_values, reinterpret_cast<uint32_t *>(d_values + (n_values ? n_values : 1)),
+                           env().prove_h2d_group, no_absorb};
+    // a public input is the cell at its location: all_values at the placement entry the setup kept, 0 on a placeholder.  h_values
+    // may be a view into a dump (bj_prove_from_dumps) and unaligned: read with memcpy
+    std::vector<u64> pub(S->pub_place.size() ? S->pub_place.size() : 1, 0);
+    for (size_t i = 0; i < S->pub_place.size(); i++)
+        if (S->pub_place[i] != PLACEMENT_NONE) std::memcpy(&pub[i], reinterpret_cast<const unsigned char *>(h_values) + (size_t)S->pub_place[i] * 8, 8);
+    return prove_impl(ctx, S, stage, stage + vw_cols * n, pub.data(), out, nullptr, S->layout.has_lookup && h_multiplicities == nullptr, &vw);
+}
+
 // What a lane of bj_prove_async wants for a proof of S from a host witness (async_admission.h), its witness and stage-2 oracles
 // resident and lean.  The lane may take the proof as bj_prove or witness first (prove_host_copy_first): the plan of bj_prove where
 // it absorbs the column groups holds every buffer of the others and the capacity words, so that one is reserved.  Where
-// BJ_PROOF_LEAN makes every proof lean, both are the lean footprint.
-int async_footprints(bj_ctx *ctx, const bj_setup *S, LaneBytes *resident, LaneBytes *lean) {
+// BJ_PROOF_LEAN makes every proof lean, both are the lean footprint.  values: the proof is bj_prove_values_async's with that many
+// values (the staging holds them and the counters as well; an empty all_values counts as one word).
+int async_footprints(bj_ctx *ctx, const bj_setup *S, LaneBytes *resident, LaneBytes *lean, bool values, size_t n_values) {
     uint32_t sched[32], new_pow = 0;
     size_t sched_len = 0, num_queries = 0, final_degree = 0;
     if (int rc = bj_fri_schedule(S->security, S->cap_size, S->pow_bits, S->log_fri, S->log_n, &new_pow, &num_queries, sched, &sched_len, &final_degree))
         return fail(ctx, rc, "bj_prove_async: compute_fri_schedule failed");
     const bool absorbs = (S->hasher == BJ_HASHER_POSEIDON2 || S->hasher == BJ_HASHER_POSEIDON) && !env().prove_no_absorb;
-    const WorkspaceShape shape = shape_of(S, false, absorbs ? WS_HOST_ABSORBING : WS_HOST_NOT_ABSORBING, false, new_pow, sched, sched_len, num_queries);
+    WorkspaceShape shape = shape_of(S, false, absorbs ? WS_HOST_ABSORBING : WS_HOST_NOT_ABSORBING, false, new_pow, sched, sched_len, num_queries);
+    if (values) shape.n_values = n_values ? n_values : 1;
     *lean = lane_footprint(shape, true);
     *resident = env().proof_lean ? *lean : lane_footprint(shape, false);
     return BJ_OK;

@@ -39,6 +39,10 @@ struct bj_setup : bj::CircuitShape {   // proof_layout.h: bj::circuit_shape fill
     gl::u64 *d_non_res = nullptr;
     gl::u64 *d_inv_xm1 = nullptr;      // 1 / (x - 1) on the points this GPU evaluates the quotient on (a property of the domain)
     uint32_t *d_placement = nullptr;   // bj_setup_create_from_placement: variable index per cell [V][n], PLACEMENT_NONE = placeholder
+    uint32_t *d_wit_placement = nullptr;   // bj_setup_set_witness_placement: the same for the non-copiable witness columns [Wc][n]
+    // host copy of the placement entries at the public input locations (one per location, PLACEMENT_NONE where the placement that
+    // covers the column is not held): the public values of a proof from values are all_values[entry], read on the host
+    std::vector<uint32_t> pub_place;
     std::vector<gl::u64> cap;
 
     // The setup's committed oracle as a value (oracle_value.h).  A lean setup has no evaluations of its own: a proof points the value at

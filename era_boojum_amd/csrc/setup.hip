@@ -34,6 +34,7 @@ void bj_setup_destroy(bj_setup *s) {
     if (s->d_non_res) (void)hipFree(s->d_non_res);
     if (s->d_inv_xm1) (void)hipFree(s->d_inv_xm1);
     if (s->d_placement) (void)hipFree(s->d_placement);
+    if (s->d_wit_placement) (void)hipFree(s->d_wit_placement);
     for (auto &p : s->programs) p.release();
     for (auto &p : s->spec_programs) p.release();
     delete s;
@@ -53,6 +54,24 @@ int bj_setup_create_sharded(bj_ctx *ctx, const bj_circuit *c, const uint64_t *h_
 
 void bj::setup_adopt_placement(bj_setup *s, uint32_t *d_placement) { s->d_placement = d_placement; }
 const uint32_t *bj::setup_placement(const bj_setup *s) { return s->d_placement; }
+void bj::setup_adopt_witness_placement(bj_setup *s, uint32_t *d_placement) {
+    if (s->d_wit_placement) (void)hipFree(s->d_wit_placement);   // set again: the caller has no proof of this setup in flight
+    s->d_wit_placement = d_placement;
+}
+
+// The placement entries at the public input locations, from whichever placement covers the column; synchronises the context's stream.
+int bj::setup_read_public_placement(bj_ctx *ctx, bj_setup *s) {
+    const size_t n = (size_t)1 << s->log_n;
+    s->pub_place.assign(s->pub_cols.size(), PLACEMENT_NONE);
+    for (size_t i = 0; i < s->pub_cols.size(); i++) {
+        const unsigned c = s->pub_cols[i];
+        const uint32_t *from = c < s->V ? s->d_placement : s->d_wit_placement;
+        if (!from || c >= s->V + s->Wc) continue;
+        BJ_HIP(ctx, hipMemcpyAsync(&s->pub_place[i], from + (size_t)(c < s->V ? c : c - s->V) * n + s->pub_rows[i], 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    BJ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BJ_OK;
+}
 
 // Everything bj_setup_create refuses about a circuit description and a proof config, without touching a device: the geometry,
 // the config, the sharding requirements (comm != nullptr), and what bj::resolve_gates (gate_list.h) refuses about the gates, whose
@@ -267,6 +286,7 @@ int bj_setup_device_bytes(const bj_setup *s, size_t *bytes) {
     if (s->d_non_res) b += (size_t)s->V * 8;
     if (s->d_inv_xm1) b += (n * s->q) / s->sh.world * 8;
     if (s->d_placement) b += (size_t)s->V * n * 4;
+    if (s->d_wit_placement) b += (size_t)s->Wc * n * 4;
     *bytes = b;
     return BJ_OK;
 }

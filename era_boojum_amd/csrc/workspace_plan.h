@@ -70,6 +70,9 @@ struct WorkspaceShape {
     bool pow = false;
     uint32_t sched[32] = {};                 // bj_fri_schedule
     size_t sched_len = 0, num_queries = 0, cap_size = 0;
+    // a proof from a WitnessVec's values (bj_prove_values): the length of all_values; 0 for every other witness source.  The arena
+    // does not depend on it: the values wait in the witness staging (async_admission.h: lane_extras)
+    size_t n_values = 0;
 };
 
 // The shape of a proof of layout L split over `world` ranks (1: one GPU).  tiled: the monomials' layout (2^22-row traces);

@@ -3,9 +3,10 @@
  * boojum_hip.h is the drop-in boundary: its entry points and structs are counted and pinned by the test suite, and every one
  * of them replaces an interface of the reference.  What a host uses only while it debugs a circuit or a witness generator, and
  * what the reference has no counterpart for, is declared here instead; it needs nothing but the types of boojum_hip.h, changes
- * no layout of them and comes within the same BJ_ABI_VERSION.  tools/gen_py_abi.py and tools/gen_rust_bindings.py generate
- * era_boojum_amd/_abi_diag.py and rust/boojum_hip_diag_sys.rs from this header as they generate _abi.py and boojum_hip_sys.rs
- * from the other. */
+ * no layout of them and comes within the same BJ_ABI_VERSION.  So is an entry point added beside the pinned set that needs none of
+ * its structs changed: bj_prove_values / bj_prove_values_async / bj_setup_set_witness_placement, at the end of this file.
+ * tools/gen_py_abi.py and tools/gen_rust_bindings.py generate era_boojum_amd/_abi_diag.py and rust/boojum_hip_diag_sys.rs from
+ * this header as they generate _abi.py and boojum_hip_sys.rs from the other. */
 #ifndef BOOJUM_HIP_DIAG_H
 #define BOOJUM_HIP_DIAG_H
 
@@ -52,6 +53,45 @@ int bj_list_unsatisfied_from_dumps(bj_ctx *ctx, const bj_setup *setup, const voi
                                    const void *variables_hint, size_t variables_hint_len, const void *witness_hint,
                                    size_t witness_hint_len, bj_unsat_entry *h_entries, size_t capacity, size_t *n_entries,
                                    uint64_t totals[5]);
+
+/* ---- proofs from a WitnessVec's values (beside the pinned set of boojum_hip.h; no struct of it changes, ABI version 6) ----
+ * What a reference host holds per proof (prove_from_witness_vec_and_precomputations, convenience.rs:160): a WitnessVec
+ * (witness.rs:29-71) as plain arrays, not [column][n] witness columns.  h_values: all_values [n_values].  h_multiplicities: the
+ * u32 counters, concatenated per table as the reference keeps them [n_multiplicities <= n], zero-extended to the trace on the
+ * device; NULL / 0 with lookups: counted on the device as for bj_prove.  Public input values are the cells at the setup's public
+ * input locations and are read from h_values through the placement: none are passed (a public input on a placeholder cell has
+ * value 0).
+ * The setup must hold the variables' placement (bj_setup_create_from_placement) and, if the circuit has non-copiable witness
+ * columns, the witness placement (bj_setup_set_witness_placement): otherwise BJ_ERR_INVALID_ARG, the message naming what is
+ * missing.  Single device only: a sharded setup is BJ_ERR_UNSUPPORTED.  all_values crosses PCIe once (n_values * 8 bytes instead
+ * of the materialised columns), every column group is gathered on the device (witness_set_from_witness_vec, witness.rs:386-443)
+ * straight into the witness staging and transformed, extended and hashed as a group of bj_prove's host witness is.  The proof is
+ * byte for byte bj_prove's on the columns materialised from the same placement and values.  A cell that names a value at or
+ * beyond n_values refuses the proof — BJ_ERR_INVALID_ARG, "a cell names a variable beyond all_values" — before the witness cap
+ * enters the transcript.  Memory: the values and the counters wait in the context's witness staging behind the multiplicity
+ * column (n_values * 8 + n * 4 bytes more than for bj_prove); nothing is allocated per proof once the context has seen the size.
+ * bj_prove_values_async: tickets, bj_proof_wait / bj_proof_poll, lifetimes (h_values and h_multiplicities stay valid and
+ * unchanged until bj_proof_wait returns), error reporting and admission are those of bj_prove_async, the footprint being that of
+ * a host-witness proof plus the bytes above; the refusals above and BJ_ERR_OOM come from the submission, never from bj_proof_wait.
+ * bj_prove_from_dumps with a NULL variables hint and no witness hint is bj_prove_values on the arrays inside the dump. */
+int bj_prove_values(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_values, size_t n_values, const uint32_t *h_multiplicities,
+                    size_t n_multiplicities, bj_proof **out);
+int bj_prove_values_async(bj_ctx *ctx, const bj_setup *setup, const uint64_t *h_values, size_t n_values, const uint32_t *h_multiplicities,
+                          size_t n_multiplicities, bj_ticket **out);
+/* DenseWitnessCopyHint dump (hints/mod.rs:17-21; circuit->num_witness_cols columns of n cells) -> the resident u32 placement of
+ * the non-copiable witness columns of a single-device setup: same narrowing and limits as the variables' placement, 4 bytes per
+ * cell, counted by bj_setup_device_bytes.  Setting it again replaces the one held; not while a proof of the setup runs.
+ * Synchronises the context's stream. */
+int bj_setup_set_witness_placement(bj_ctx *ctx, bj_setup *setup, const void *witness_hint, size_t witness_hint_len);
+
+/* Test door of the kernel behind bj_prove_values (witness_gather_kernel, csrc/witness_values.hip) on caller-given device arrays:
+ * d_cells[i] = d_values[d_placement[i]] for the cols * 2^log_n cells of a u32 placement [cols][n]; 0xFFFFFFFF (a placeholder)
+ * gives 0, an index at or beyond n_values gives 0 and sets *bad (host memory) to non-zero.  The pointers need only their types'
+ * alignment.  On the context's stream; synchronises.  bj_witness_gather_sweep_cells: the cells one sweep of the launcher's grid
+ * covers on this device (a larger count takes the grid-stride loop round again); 0 for a context that cannot be bound. */
+int bj_witness_gather(bj_ctx *ctx, const uint32_t *d_placement, unsigned cols, unsigned log_n, const uint64_t *d_values, size_t n_values,
+                      uint64_t *d_cells, unsigned *bad);
+size_t bj_witness_gather_sweep_cells(bj_ctx *ctx);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,10 @@ use sys::*;
 pub mod diag_sys;
 #[path = "list_unsatisfied_hip.rs"]
 mod list_unsatisfied_hip;
+// proofs from a WitnessVec's values (bj_prove_values, declared in include/boojum_hip_diag.h): `prove_hip_from_values`
+#[path = "prove_values_hip.rs"]
+mod prove_values_hip;
+pub use prove_values_hip::prove_hip_from_values;
 
 type F = GoldilocksField;
 
